@@ -144,6 +144,36 @@ class StepRunner:
                 done += n
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, runner, rank, world):
+    """``--dump-outputs DIR``: what the timed path computed in its last step, as its caller receives it - the latents x after
+    the update (what ``Diffusion.sampling(vae=None)`` returns) and the UNet's noise prediction of that step - as float32
+    ``DIR/<name>.npy`` (``<name>_rank<r>.npy`` on several ranks).  Above 64 MB in all, a fixed seeded subset of the samples
+    is written (``sample_index.npy`` names them).  Returns the file names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"latents": runner.P.x_in, "eps": runner.P.out}
+    per_sample = sum(t[0].numel() * 4 for t in arrays.values())
+    keep = max(1, min(runner.batch, DUMP_BUDGET_BYTES // world // per_sample))
+    idx = None
+    if keep < runner.batch:
+        idx = np.sort(np.random.default_rng(0).choice(runner.batch, keep, replace=False))
+        arrays["sample_index"] = torch.from_numpy(idx.astype(np.float64))
+    sfx = "" if world == 1 else f"_rank{rank}"
+    names = []
+    for name, t in arrays.items():
+        v = t.detach().cpu()
+        if idx is not None and name != "sample_index":
+            v = v[torch.from_numpy(idx)]
+        if v.dtype != torch.float64:
+            v = v.float()
+        names.append(name + sfx + ".npy")
+        np.save(os.path.join(out_dir, names[-1]), v.numpy())
+    return names
+
+
 def cpu_info():
     """CPU model name, physical cores (distinct (package, core id) pairs) and logical CPUs from /proc/cpuinfo."""
     model, cores, logical, phys, core = "unknown", set(), 0, None, None
@@ -646,7 +676,11 @@ def main():
     ap.add_argument("--train-timeout", type=float, default=240.0, help="wall-clock limit of the multi-GPU training leg (seconds)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous / barrier / max-over-ranks only, no GPU work (CPU rehearsal of the N-rank control flow)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (latents, noise prediction) as DIR/*.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
@@ -693,6 +727,7 @@ def main():
     elapsed = wdist.max_over_ranks(elapsed, device=dev)
     ms_per_step = 1e3 * elapsed / a.steps
     finite = bool(torch.isfinite(runner.P.x_in).all().item())
+    dumped = dump_outputs(a.dump_outputs, runner, rank, world) if a.dump_outputs else None  # before any extra moves x on
 
     roof = None
     prof_extra = None
@@ -805,6 +840,8 @@ def main():
                                 per_call_setup_ms=setup_ms, kernel_sources_sha256=_lib_digest()),
                     roofline=roof, cpu_baseline=cpu, full_call=full_call, kernel_classes=prof_extra, train_step=train,
                     vae_decode=vae, phosc_variant=phosc_extra)
+        if dumped is not None:
+            line["dumped_outputs"] = dict(dir=os.path.abspath(a.dump_outputs), files=dumped)
         print(json.dumps(line))
     if world > 1:
         import torch.distributed as dist
