@@ -176,7 +176,16 @@ int wd_gemm_pack_w(const wd_bf16* hi, const wd_bf16* lo, int n, int ktot, wd_bf1
  * nchunk = max(1, hw_out / 64), as wd_gemm with 64-row tiles).
  * w3 != NULL: the 1x1 proj_out of the SpatialTransformer and its residual ride in the same launch (unet.py:406-412),
  *     out = resid3 + (resid + GEGLU(...) W2^T + b2) W3^T + b3
- * with w3 the wd_gemm_pack_w image of the [c][c] projection; the feed-forward result itself is then not stored. */
+ * with w3 the wd_gemm_pack_w image of the [c][c] projection; the feed-forward result itself is then not stored.
+ * x_in != NULL: the whole SpatialTransformer of the base model (one transformer block, c == inner == 320) in the same launch; the
+ *     panel's tokens come from x_in (fp32 [m][x_in_ld], the block input, also resid3) instead of x_hi / x_lo (then unused):
+ *         tok  = GroupNorm(x_in) Wpi^T + pi_b               norm (eps gn_eps, no SiLU) + proj_in, unet.py:398-402
+ *         tok1 = tok  + attn1(norm2(tok))                   folded cross-attention a (wd_xattn_fold planes mq_a / mot_a, bias xb_a)
+ *         tok2 = tok1 + attn2(norm2(tok1))                  folded cross-attention b, unet.py:337-345
+ *         x    = norm3(tok2) -> the feed-forward above, resid = tok2 (written to the fp32 scratch tok2 [m][320]; resid ignored)
+ *     GroupNorm statistics as wd_gemm_args.a32*: gn_part [batch][gn_nchunk][c / gn_pcpg][2], groups of gn_cpg channels, samples of
+ *     hw rows (hw % 64 == 0, m % hw == 0).  pi: wd_gemm_pack_w image of the [320][320] proj_in.  mq_* / mot_*: the per-sample
+ *     fragment-major planes of wd_xattn_fold; wd_xattn_supported(320, heads, L).  npass 3 and w3 only. */
 typedef struct wd_ff_args {
     const wd_bf16* x_hi;
     const wd_bf16* x_lo;
@@ -204,6 +213,30 @@ typedef struct wd_ff_args {
     int32_t stat_cpg;
     int32_t hw_out;
     int32_t npass;
+    const float* x_in;
+    int32_t x_in_ld;
+    int32_t hw;
+    const double* gn_part;
+    int32_t gn_nchunk, gn_pcpg, gn_cpg;
+    float gn_eps;
+    const float* gn_gamma;
+    const float* gn_beta;
+    const wd_bf16* pi_hi;
+    const wd_bf16* pi_lo;
+    const float* pi_b;
+    const float* ln2_gamma;
+    const float* ln2_beta;
+    const wd_bf16* mq_a;
+    const wd_bf16* mot_a;
+    const float* xb_a;
+    const wd_bf16* mq_b;
+    const wd_bf16* mot_b;
+    const float* xb_b;
+    const float* ln3_gamma;
+    const float* ln3_beta;
+    float ln_eps; /* norm2 and norm3 */
+    int32_t heads, L;
+    float* tok2;
 } wd_ff_args;
 int wd_ff_fused(const wd_ff_args* args, void* stream);
 int wd_ff_supported(int c, int inner); /* 1 when wd_ff_fused covers the shape */

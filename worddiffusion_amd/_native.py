@@ -50,7 +50,12 @@ class WdFfArgs(C.Structure):
                 ("w1_hi", _vp), ("w1_lo", _vp), ("b1", _vp), ("w2_hi", _vp), ("w2_lo", _vp), ("b2", _vp), ("resid", _vp),
                 ("resid_ld", C.c_int32), ("out_f32", _vp), ("out_ld", C.c_int32), ("out_hi", _vp), ("out_lo", _vp),
                 ("out_pl_ld", C.c_int32), ("w3_hi", _vp), ("w3_lo", _vp), ("b3", _vp), ("resid3", _vp), ("resid3_ld", C.c_int32),
-                ("stat_part", _vp), ("stat_cpg", C.c_int32), ("hw_out", C.c_int32), ("npass", C.c_int32)]
+                ("stat_part", _vp), ("stat_cpg", C.c_int32), ("hw_out", C.c_int32), ("npass", C.c_int32),
+                ("x_in", _vp), ("x_in_ld", C.c_int32), ("hw", C.c_int32), ("gn_part", _vp), ("gn_nchunk", C.c_int32),
+                ("gn_pcpg", C.c_int32), ("gn_cpg", C.c_int32), ("gn_eps", C.c_float), ("gn_gamma", _vp), ("gn_beta", _vp),
+                ("pi_hi", _vp), ("pi_lo", _vp), ("pi_b", _vp), ("ln2_gamma", _vp), ("ln2_beta", _vp), ("mq_a", _vp), ("mot_a", _vp),
+                ("xb_a", _vp), ("mq_b", _vp), ("mot_b", _vp), ("xb_b", _vp), ("ln3_gamma", _vp), ("ln3_beta", _vp),
+                ("ln_eps", C.c_float), ("heads", C.c_int32), ("L", C.c_int32), ("tok2", _vp)]
 
 
 class WdDwArgs(C.Structure):

@@ -13,6 +13,12 @@
 // of the second product, whose 64 x 320 result stays in 80 accumulator registers per wave (2 K-halves x 4 column groups, as
 // in wd_gemmw_kernel) over all chunks.  Every weight is read exactly once per workgroup, straight from its FRAGMENT-MAJOR image
 // (wd_gemm_pack_w) into the MFMA operand registers through a ring of six two-load groups (12 KB per wave in flight).
+//
+// FRONT: the panel also goes through the head of its SpatialTransformer first (base model, one block, unet.py:398-402,337-345):
+// GroupNorm of the fp32 block input applied while it is staged into the resident rows, proj_in through the same ring (the
+// K-half x column-group product of proj_out), both folded cross-attentions (wd_xattn.hip's arithmetic on 64 tokens instead of
+// 16) and norm3 straight into the resident rows - every step is token-local and a 64-token panel of the 8 x 32 level lies in one
+// sample, so the three launches of the chain and their three fp32 / plane round trips through HBM become phases of this one.
 #include "wd_gemm_epi.h"
 
 namespace {
@@ -30,9 +36,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned f_u32x4;
 
 __device__ __forceinline__ int f_lds_off(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
 
-template <int NPASS, bool PROJ>
+template <int NPASS, bool PROJ, bool FRONT>
 __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(!FRONT || (NPASS == 3 && PROJ), "the transformer front needs split-bf16 operands and the proj_out tail");
     constexpr int NPL = (NPASS == 1) ? 1 : 2;
     constexpr int SLAB = 2 * FBM * 128;            // one 64-deep K slab of 64 rows, both planes (plane stride FBM * 128)
     constexpr int A_BYTES = 5 * SLAB;              // the resident token rows: 320 channels
@@ -93,6 +100,324 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
                 ring[slot][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(p ? srd2_lo : srd2_hi, vo, live ? so : 0u, 0));
         }
     };
+    f32x4 acc2[4][5];
+    bf16x8 xa[4][NPL];
+    auto read_frags = [&](const char* slab_base, const int half) {  // the four row tiles of k-step `half` (0 / 1) of a 64-deep slab
+        const int ch = half * 4 + lq;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int ao = f_lds_off(i * 16 + l15, ch);
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) xa[i][p] = *reinterpret_cast<const bf16x8*>(slab_base + p * (FBM * 128) + ao);
+        }
+    };
+    auto mfma12 = [&](f32x4 (&acc)[4], const bf16x8 (&w)[NPL]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (NPL == 2) {
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][NPL - 1], w[0], acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][0], w[NPL - 1], acc[i], 0, 0, 0);
+            }
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][0], w[0], acc[i], 0, 0, 0);
+        }
+    };
+    constexpr int LDE = FC + 4;
+    float* ep = reinterpret_cast<float*>(smem);   // [FBM][LDE] fp32 image of a finished product (over s_a and 1 KB of s_h)
+    auto ksum_to_image = [&]() {  // the two K-halves of acc2 summed in a fixed order through the fp32 image (callers: barrier first)
+        for (int hh = 0; hh < 2; ++hh) {
+            if (kh == hh) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int t = 0; t < 5; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float* pe = ep + (i * 16 + 4 * lq + r) * LDE + cg * 80 + t * 16 + l15;
+                            *pe = (hh == 0) ? acc2[i][t][r] : *pe + acc2[i][t][r];
+                        }
+            }
+            __syncthreads();
+        }
+    };
+
+    if constexpr (FRONT) {
+        // ================= the transformer front: GroupNorm + proj_in, attn1, attn2, norm3 -> the resident rows =================
+        constexpr int SP = 65, PP = 72, KS32 = FC / 32;
+        const int b = m0 / a.hw;                                   // (hw % 64 == 0: the panel is one sample)
+        const int HJ = a.heads * a.L;                              // (<= 40: the (head, key) tiles 0..2 of 16 carry data)
+        char* fr = s_h + 4096;                                     // (s_h[0, 1024) lies under the fp32 image)
+        float* s_aff = reinterpret_cast<float*>(fr);               // [FC][2] GroupNorm scale / shift of the sample (staging only)
+        float* sS = reinterpret_cast<float*>(fr);                  // [FBM][SP] scores
+        wd_bf16* sP = reinterpret_cast<wd_bf16*>(fr + FBM * SP * 4);  // [2][FBM][PP] probability planes, padding columns 0
+        // ---- GroupNorm (affine folded per channel) from the producer's partials, as wd_gemmw_kernel<..., A32>
+        {
+            const int ngp = FC / a.gn_pcpg, ratio = a.gn_cpg / a.gn_pcpg;
+            for (int c = tid; c < FC; c += FNT) {
+                const int g = c / a.gn_cpg;
+                double su = 0.0, sq = 0.0;
+                for (int k = 0; k < ratio; ++k)
+                    for (int ck = 0; ck < a.gn_nchunk; ++ck) {
+                        const double* pp = a.gn_part + (((long)b * a.gn_nchunk + ck) * ngp + g * ratio + k) * 2;
+                        su += pp[0];
+                        sq += pp[1];
+                    }
+                const double n = (double)a.hw * a.gn_cpg;
+                const double mu = su / n;
+                double var = sq / n - mu * mu;
+                if (var < 0.0) var = 0.0;
+                const float rstd = (float)(1.0 / sqrt(var + (double)a.gn_eps));
+                const float sc = rstd * a.gn_gamma[c];
+                s_aff[2 * c] = sc;
+                s_aff[2 * c + 1] = a.gn_beta[c] - (float)mu * sc;
+            }
+            for (int e = tid; e < FBM * PP; e += FNT) reinterpret_cast<uint32_t*>(sP)[e] = 0u;
+        }
+        // ---- the panel's input rows (thread: row, 8 channels of each slab), then the first proj_in groups into the ring
+        const int arow = tid >> 3, ach = tid & 7;
+        float4 xv[5][2];
+        {
+            const float* xrow = a.x_in + (long)(m0 + arow) * a.x_in_ld + ach * 8;
+#pragma unroll
+            for (int sl = 0; sl < 5; ++sl) {
+                xv[sl][0] = *reinterpret_cast<const float4*>(xrow + sl * 64);
+                xv[sl][1] = *reinterpret_cast<const float4*>(xrow + sl * 64 + 4);
+            }
+        }
+        const __amdgpu_buffer_rsrc_t srdp_hi = make_srd(a.pi_hi), srdp_lo = make_srd(a.pi_lo);
+        auto issue_pi = [&](const int slot, const int g) {  // proj_in group g: k-step 2 (g / 5) + kh, column tile 5 cg + g % 5
+            const uint32_t so = (uint32_t)(((2 * (g / 5) + kh) * (FC / 16) + 5 * cg + g % 5) * 1024);
+#pragma unroll
+            for (int p = 0; p < NPL; ++p)
+                ring[slot][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(p ? srdp_lo : srdp_hi, lane16, so, 0));
+        };
+#pragma unroll
+        for (int g = 0; g < FRING; ++g) issue_pi(g, g);
+        __syncthreads();
+        // ---- y = x * scale + shift -> split-bf16 planes of the resident rows
+#pragma unroll
+        for (int sl = 0; sl < 5; ++sl) {
+            const float4* tab = reinterpret_cast<const float4*>(s_aff + 2 * (sl * 64 + ach * 8));  // (sc0 sh0 sc1 sh1) ...
+            const float4 t0 = tab[0], t1 = tab[1], t2 = tab[2], t3 = tab[3];
+            const float4 x0 = xv[sl][0], x1 = xv[sl][1];
+            float4 y0, y1;
+            y0.x = x0.x * t0.x + t0.y; y0.y = x0.y * t0.z + t0.w; y0.z = x0.z * t1.x + t1.y; y0.w = x0.w * t1.z + t1.w;
+            y1.x = x1.x * t2.x + t2.y; y1.y = x1.y * t2.z + t2.w; y1.z = x1.z * t3.x + t3.y; y1.w = x1.w * t3.z + t3.w;
+            uint2 h0, l0, h1, l1;
+            wd_split4(y0, h0, l0);
+            wd_split4(y1, h1, l1);
+            char* dst = s_a + sl * SLAB + f_lds_off(arow, ach);
+            *reinterpret_cast<f_u32x4*>(dst) = f_u32x4{h0.x, h0.y, h1.x, h1.y};
+            *reinterpret_cast<f_u32x4*>(dst + FBM * 128) = f_u32x4{l0.x, l0.y, l1.x, l1.y};
+        }
+        __syncthreads();
+        // ---- tok = rows Wpi^T: K = 320 as ten k-steps, K-half kh takes the k-steps 2 q + kh (wd_gemmw_kernel's order)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < 5; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc2[i][t][r] = 0.0f;
+#pragma unroll
+        for (int g = 0; g < 25; ++g) {
+            const int q = g / 5, t = g % 5;
+            if (t == 0) read_frags(s_a + q * SLAB, kh);
+            {
+                f32x4 col[4] = {acc2[0][t], acc2[1][t], acc2[2][t], acc2[3][t]};
+                mfma12(col, ring[g % FRING]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc2[i][t] = col[i];
+            }
+            if (g + FRING < 25) issue_pi(g % FRING, g + FRING);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+        ksum_to_image();
+        // ---- the rows as quarter-wave rows (xattn16_kernel's layout): wave w holds rows 8 w + 4 pp + lq, lane l15 the float4
+        // columns l15 + 16 i; tok = image + bias
+        float4 xr[2][5];
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const int n = (l15 + 16 * i) * 4, row = wave * 8 + pp * 4 + lq;
+                const float4 v = *reinterpret_cast<const float4*>(ep + row * LDE + n);
+                const float4 bx = *reinterpret_cast<const float4*>(a.pi_b + n);
+                xr[pp][i] = make_float4(v.x + bx.x, v.y + bx.y, v.z + bx.z, v.w + bx.w);
+            }
+        __syncthreads();  // the image is read: the planes go over it
+        // LayerNorm of the quarter-wave rows -> split-bf16 planes of the resident rows
+        auto ln_rows = [&](const float* gamma, const float* beta) {
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp) {
+                const int row = wave * 8 + pp * 4 + lq;
+                float s = 0.f;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) s += (xr[pp][i].x + xr[pp][i].y) + (xr[pp][i].z + xr[pp][i].w);
+                const float mean = wd_row16_sum(s) / (float)FC;
+                float q = 0.f;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const float a0 = xr[pp][i].x - mean, a1 = xr[pp][i].y - mean, a2 = xr[pp][i].z - mean, a3 = xr[pp][i].w - mean;
+                    q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+                }
+                const float rstd = 1.0f / sqrtf(wd_row16_sum(q) / (float)FC + a.ln_eps);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const int n = (l15 + 16 * i) * 4;
+                    const float4 ga = *reinterpret_cast<const float4*>(gamma + n);
+                    const float4 be = *reinterpret_cast<const float4*>(beta + n);
+                    const float4 x = xr[pp][i];
+                    float4 o;
+                    o.x = (x.x - mean) * rstd * ga.x + be.x; o.y = (x.y - mean) * rstd * ga.y + be.y;
+                    o.z = (x.z - mean) * rstd * ga.z + be.z; o.w = (x.w - mean) * rstd * ga.w + be.w;
+                    uint2 hi, lo;
+                    wd_split4(o, hi, lo);
+                    char* d = s_a + (n >> 6) * SLAB + f_lds_off(row, (n & 63) >> 3) + (n & 7) * 2;
+                    *reinterpret_cast<uint2*>(d) = hi;
+                    *reinterpret_cast<uint2*>(d + FBM * 128) = lo;
+                }
+            }
+        };
+        // ---- the two folded cross-attentions (wd_xattn.hip): wave w takes (head, key) tile w & 3 of the scores and the column
+        // group w & 3 of the output, both for the row tiles 2 (w >> 2) and 2 (w >> 2) + 1
+        const int ht = wave & 3, rp = wave >> 2;
+        const long pq = 64L * FC;                                  // elements of one plane of one sample's folded matrix
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps) {
+            const wd_bf16* mq = ps == 0 ? a.mq_a : a.mq_b;
+            const wd_bf16* mot = ps == 0 ? a.mot_a : a.mot_b;
+            const float* xb = ps == 0 ? a.xb_a : a.xb_b;
+            ln_rows(a.ln2_gamma, a.ln2_beta);  // (norm2 for both attentions, unet.py:337-345)
+            __builtin_amdgcn_sched_barrier(0);
+            bf16x8 bh[KS32], bl[KS32];
+            {
+                const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(mq + (long)b * 2 * pq), 0,
+                                                                                    (int)(2 * pq * 2), 0x00020000);
+                const uint32_t vo = ht * 16 + l15 < HJ ? lane16 : F_OOB;
+#pragma unroll
+                for (int ks = 0; ks < KS32; ++ks) {
+                    bh[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)((ht * KS32 + ks) << 10), 0));
+                    bl[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)(((ht * KS32 + ks) << 10) + pq * 2), 0));
+                }
+            }
+            __syncthreads();
+            // ---- scores S[token][hj] = LN(x) . Mq^T, three split products in independent accumulators
+            if (ht * 16 < HJ) {
+                f32x4 a_lh[2], a_hl[2], a_hh[2];
+#pragma unroll
+                for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a_lh[ri][r] = a_hl[ri][r] = a_hh[ri][r] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < KS32; ++ks)
+#pragma unroll
+                    for (int ri = 0; ri < 2; ++ri) {
+                        const char* ap = s_a + (ks >> 1) * SLAB + f_lds_off((2 * rp + ri) * 16 + l15, (ks & 1) * 4 + lq);
+                        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
+                        const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + FBM * 128);
+                        a_lh[ri] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[ks], a_lh[ri], 0, 0, 0);
+                        a_hl[ri] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[ks], a_hl[ri], 0, 0, 0);
+                        a_hh[ri] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[ks], a_hh[ri], 0, 0, 0);
+                    }
+#pragma unroll
+                for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        sS[((2 * rp + ri) * 16 + 4 * lq + r) * SP + ht * 16 + l15] = (a_lh[ri][r] + a_hl[ri][r]) + a_hh[ri][r];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // the operand of the output product does not depend on the softmax: requested now, it lands during the softmax
+            bf16x8 mh[2][5], ml[2][5];
+            {
+                const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(mot + (long)b * 2 * pq), 0,
+                                                                                    (int)(2 * pq * 2), 0x00020000);
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const uint32_t vo = ks * 32 + lq * 8 < HJ ? lane16 : F_OOB;
+#pragma unroll
+                    for (int t = 0; t < 5; ++t) {  // block (column tile, ks) = ((5 cg + t) 2 + ks) KB
+                        const uint32_t so = (uint32_t)((((5 * cg + t) * 2 + ks) << 10));
+                        mh[ks][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rm, vo, so, 0));
+                        ml[ks][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rm, vo, so + (uint32_t)(pq * 2), 0));
+                    }
+                }
+            }
+            __syncthreads();
+            // ---- softmax per (token, head) -> probability planes
+            for (int idx = tid; idx < FBM * a.heads; idx += FNT) {
+                const int t = idx / a.heads, h = idx - t * a.heads;
+                const float* pr = sS + t * SP + h * a.L;
+                wd_bf16* ph = sP + t * PP + h * a.L;
+                float mx = -3.4e38f;
+                for (int j = 0; j < a.L; ++j) mx = fmaxf(mx, pr[j]);
+                float sum = 0.f;
+                for (int j = 0; j < a.L; ++j) sum += __expf(pr[j] - mx);
+                const float inv = __fdividef(1.f, sum);
+                for (int j = 0; j < a.L; ++j) {
+                    uint32_t hi, lo;
+                    wd_split1(__expf(pr[j] - mx) * inv, hi, lo);
+                    ph[j] = (wd_bf16)hi;
+                    ph[FBM * PP + j] = (wd_bf16)lo;
+                }
+            }
+            __syncthreads();
+            // ---- output image O[token][n] = P . Mo (the token planes are dead: every wave passed the barrier after the scores)
+            {
+                f32x4 o[2][5];
+#pragma unroll
+                for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                    for (int t = 0; t < 5; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) o[ri][t][r] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                    for (int ri = 0; ri < 2; ++ri) {
+                        const wd_bf16* ap = sP + ((2 * rp + ri) * 16 + l15) * PP + lq * 8 + ks * 32;
+                        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
+                        const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + FBM * PP);
+#pragma unroll
+                        for (int t = 0; t < 5; ++t) o[ri][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, mh[ks][t], o[ri][t], 0, 0, 0);
+#pragma unroll
+                        for (int t = 0; t < 5; ++t) o[ri][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, ml[ks][t], o[ri][t], 0, 0, 0);
+#pragma unroll
+                        for (int t = 0; t < 5; ++t) o[ri][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, mh[ks][t], o[ri][t], 0, 0, 0);
+                    }
+#pragma unroll
+                for (int ri = 0; ri < 2; ++ri)
+#pragma unroll
+                    for (int t = 0; t < 5; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) ep[((2 * rp + ri) * 16 + 4 * lq + r) * LDE + (5 * cg + t) * 16 + l15] = o[ri][t][r];
+            }
+            __syncthreads();
+            // ---- + bias + residual (the rows are still in registers)
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const int n = (l15 + 16 * i) * 4, row = wave * 8 + pp * 4 + lq;
+                    const float4 bi = *reinterpret_cast<const float4*>(xb + n);
+                    const float4 at = *reinterpret_cast<const float4*>(ep + row * LDE + n);
+                    const float4 x = xr[pp][i];
+                    xr[pp][i] = make_float4(at.x + bi.x + x.x, at.y + bi.y + x.y, at.z + bi.z + x.z, at.w + bi.w + x.w);
+                }
+            __syncthreads();  // the image is read: the next planes go over it
+        }
+        // ---- tok2 -> its scratch (the residual of the feed-forward, read back by this same wave in the x' step), norm3 -> the
+        // resident rows, b1 -> LDS, then the first groups of chunk 0 into the ring
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+                *reinterpret_cast<float4*>(a.tok2 + (long)(m0 + wave * 8 + pp * 4 + lq) * FC + (l15 + 16 * i) * 4) = xr[pp][i];
+        ln_rows(a.ln3_gamma, a.ln3_beta);
+        for (int i = tid; i < 2 * a.inner; i += FNT) s_b1[i] = a.b1 ? a.b1[i] : 0.0f;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < FRING; ++g) issue(g, g, 0);
+    } else {
     // the first FRING groups go out before anything else (they have the whole prologue to land)
 #pragma unroll
     for (int g = 0; g < FRING; ++g) issue(g, g, 0);
@@ -114,36 +439,15 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
             for (int p = 0; p < NPL; ++p) *reinterpret_cast<f_u32x4*>(s_a + sl * SLAB + p * (FBM * 128) + dst) = v[sl][p];
         for (int i = tid; i < 2 * a.inner; i += FNT) s_b1[i] = a.b1 ? a.b1[i] : 0.0f;
     }
+    }
     __syncthreads();
 
-    f32x4 acc2[4][5];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int t = 0; t < 5; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc2[i][t][r] = 0.0f;
-
-    bf16x8 xa[4][NPL];
-    auto read_frags = [&](const char* slab_base, const int half) {  // the four row tiles of k-step `half` (0 / 1) of a 64-deep slab
-        const int ch = half * 4 + lq;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ao = f_lds_off(i * 16 + l15, ch);
-#pragma unroll
-            for (int p = 0; p < NPL; ++p) xa[i][p] = *reinterpret_cast<const bf16x8*>(slab_base + p * (FBM * 128) + ao);
-        }
-    };
-    auto mfma12 = [&](f32x4 (&acc)[4], const bf16x8 (&w)[NPL]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (NPL == 2) {
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][NPL - 1], w[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][0], w[NPL - 1], acc[i], 0, 0, 0);
-            }
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][0], w[0], acc[i], 0, 0, 0);
-        }
-    };
 
     // bias of this wave's hidden units (x and gate) changes per chunk: read inside the loop
     for (int j = 0; j < nchunk; ++j) {
@@ -203,23 +507,8 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
     }
 
     // ---- the two K-halves summed in a fixed order through the fp32 image, then the shared GEMM epilogue (+ b2, + x, planes / fp32)
-    constexpr int LDE = FC + 4;
-    float* ep = reinterpret_cast<float*>(smem);
     __syncthreads();
-    for (int hh = 0; hh < 2; ++hh) {
-        if (kh == hh) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int t = 0; t < 5; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float* pe = ep + (i * 16 + 4 * lq + r) * LDE + cg * 80 + t * 16 + l15;
-                        *pe = (hh == 0) ? acc2[i][t][r] : *pe + acc2[i][t][r];
-                    }
-        }
-        __syncthreads();
-    }
+    ksum_to_image();
     wd_gemm_args e = {};
     e.m = a.m;
     e.n = FC;
@@ -242,6 +531,10 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         // ---- x' = image + b2 + x -> split-bf16 planes IN PLACE (a row's 320 floats = 1296 bytes with the pitch; its planes take
         // 2 x 640): wave w converts rows 8 w .. 8 w + 7, every read of those rows before the first write (same wave, in order)
         constexpr int ROWB = LDE * 4;
+        const float* resid = FRONT ? a.tok2 : a.resid;
+        const int resid_ld = FRONT ? FC : a.resid_ld;
+        // (FRONT: this wave's own tok2 stores, long done - but a store and a later load are not ordered by the counters alone)
+        if (FRONT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         {
             float4 v[10];
 #pragma unroll
@@ -253,8 +546,8 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
                     const float4 q = *reinterpret_cast<const float4*>(a.b2 + c);
                     x.x += q.x; x.y += q.y; x.z += q.z; x.w += q.w;
                 }
-                if (a.resid && m < a.m) {
-                    const float4 q = *reinterpret_cast<const float4*>(a.resid + (long)m * a.resid_ld + c);
+                if (resid && m < a.m) {
+                    const float4 q = *reinterpret_cast<const float4*>(resid + (long)m * resid_ld + c);
                     x.x += q.x; x.y += q.y; x.z += q.z; x.w += q.w;
                 }
                 v[it] = x;
@@ -307,20 +600,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();  // every fragment read of the planes is done: the image goes over them
-        for (int hh = 0; hh < 2; ++hh) {
-            if (kh == hh) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int t = 0; t < 5; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float* pe = ep + (i * 16 + 4 * lq + r) * LDE + cg * 80 + t * 16 + l15;
-                            *pe = (hh == 0) ? acc2[i][t][r] : *pe + acc2[i][t][r];
-                        }
-            }
-            __syncthreads();
-        }
+        ksum_to_image();
         e.bias = a.b3;
         e.resid = a.resid3;
         e.resid_ld = a.resid3_ld;
@@ -329,7 +609,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #endif
 }
 
-template <int NPASS, bool PROJ>
+template <int NPASS, bool PROJ, bool FRONT = false>
 int launch_ff(const wd_ff_args& a, hipStream_t st) {
     constexpr int max_smem = 5 * 2 * FBM * 128 + 2 * 2 * 2 * FBM * 128 + 2 * F_MAX_INNER * 4;  // token rows + two h images + b1
     constexpr int red_smem = FBM * (FC + 4) * 4 + WD_STAT_SCRATCH;
@@ -338,15 +618,17 @@ int launch_ff(const wd_ff_args& a, hipStream_t st) {
     const int smem = loop_smem > red_smem ? loop_smem : red_smem;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wd_ff_kernel<NPASS, PROJ>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wd_ff_kernel<NPASS, PROJ, FRONT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 max_smem) != hipSuccess)
             return WD_ELAUNCH;
         attr_done = true;
     }
     const int nb = (a.m + FBM - 1) / FBM;
-    const double fl = 2.0 * (double)a.m * (3.0 * (double)a.inner * FC + (PROJ ? (double)FC * FC : 0.0));
+    // (FRONT: + proj_in and the two folded attentions, scores and output: 2 x 2 (heads L) c multiply-adds per token)
+    const double fl = 2.0 * (double)a.m * (3.0 * (double)a.inner * FC + (PROJ ? (double)FC * FC : 0.0) +
+                                           (FRONT ? (double)FC * FC + 4.0 * a.heads * a.L * FC : 0.0));
     WdLaunchScope scope(WD_CLS_FF, st, fl);
-    hipLaunchKernelGGL((wd_ff_kernel<NPASS, PROJ>), dim3(nb), dim3(FNT), smem, st, a);
+    hipLaunchKernelGGL((wd_ff_kernel<NPASS, PROJ, FRONT>), dim3(nb), dim3(FNT), smem, st, a);
     return wd_check_launch();
 }
 
@@ -360,9 +642,10 @@ extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
     if (!pa) return WD_EINVAL;
     const wd_ff_args& a = *pa;
     if (!wd_ff_supported(a.c, a.inner) || a.m <= 0 || (a.npass != 1 && a.npass != 3)) return WD_EINVAL;
-    if (!a.x_hi || !a.w1_hi || !a.w2_hi || (a.npass == 3 && (!a.x_lo || !a.w1_lo || !a.w2_lo))) return WD_EINVAL;
+    const bool front = a.x_in != nullptr;
+    if (!a.w1_hi || !a.w2_hi || (a.npass == 3 && (!a.w1_lo || !a.w2_lo))) return WD_EINVAL;
+    if (!front && (!a.x_hi || (a.npass == 3 && !a.x_lo) || a.x_ld % 8 || a.x_ld < a.c)) return WD_EINVAL;
     if (!a.out_f32 && !a.out_hi) return WD_EINVAL;
-    if (a.x_ld % 8 || a.x_ld < a.c) return WD_EINVAL;
     if ((a.out_ld | a.resid_ld | a.out_pl_ld) & 3) return WD_EINVAL;  // the vector epilogue
     if (a.resid && a.resid_ld <= 0) return WD_EINVAL;
     if ((long)a.m * a.x_ld * 2 >= 0x7FFFFFF0L || (long)2 * a.inner * a.c * 2 >= 0x7FFFFFF0L) return WD_EINVAL;
@@ -371,7 +654,16 @@ extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
     if (a.stat_part && (a.stat_cpg <= 0 || FC % a.stat_cpg || a.hw_out <= 0 || !(a.hw_out % FBM == 0 || FBM % a.hw_out == 0) ||
                         (FBM > a.hw_out && FBM / a.hw_out > WD_STAT_MAXNS)))
         return WD_EINVAL;
+    if (front) {
+        if (a.npass != 3 || !proj || a.x_in_ld < a.c || a.x_in_ld % 4 || a.hw <= 0 || a.hw % FBM || a.m % a.hw) return WD_EINVAL;
+        if (!a.gn_part || a.gn_nchunk <= 0 || a.gn_pcpg <= 0 || a.gn_cpg <= 0 || a.gn_cpg % a.gn_pcpg || FC % a.gn_cpg ||
+            !a.gn_gamma || !a.gn_beta)
+            return WD_EINVAL;
+        if (!a.pi_hi || !a.pi_lo || !a.pi_b || !a.ln2_gamma || !a.ln2_beta || !a.ln3_gamma || !a.ln3_beta || !a.tok2) return WD_EINVAL;
+        if (!a.mq_a || !a.mot_a || !a.xb_a || !a.mq_b || !a.mot_b || !a.xb_b || !wd_xattn_supported(a.c, a.heads, a.L)) return WD_EINVAL;
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (front) return launch_ff<3, true, true>(a, st);
     if (proj) return a.npass == 3 ? launch_ff<3, true>(a, st) : launch_ff<1, true>(a, st);
     return a.npass == 3 ? launch_ff<3, false>(a, st) : launch_ff<1, false>(a, st);
 }

@@ -371,6 +371,9 @@ class UNetEngine:
             raise N.NativeError("WDIFF_SLAB / WDIFF_CONV3 need a library built with WDIFF_EXPERIMENTAL=1 "
                                 "(python -m worddiffusion_amd.build --force)")
         self.fuse_xattn_pair = os.environ.get("WDIFF_FUSE_XATTN_PAIR", "1") != "0"
+        # the whole base-model SpatialTransformer of the 8 x 32 level (GroupNorm + proj_in, both folded cross-attentions, the
+        # feed-forward, proj_out) as one wd_ff_fused launch per 64-token panel; 0: the three-launch chain
+        self.fuse_st = os.environ.get("WDIFF_FUSE_ST", "1") != "0"
         self.fuse_out = os.environ.get("WDIFF_FUSE_OUT", "1") != "0"
         self.pack_kv = os.environ.get("WDIFF_PACK_KV", "1") != "0"         # long-context cross-attention: K/V images built once per call
         self.fuse_gn2 = os.environ.get("WDIFF_FUSE_GN2", "1") != "0"       # GroupNorm over [h | skip]: one apply launch for both
@@ -988,6 +991,12 @@ class UNetEngine:
         heads, d = mod.heads, mod.d_head
         inner = heads * d
         L = self._ctx_len
+        if (self.fuse_st and self.variant != "phosc" and len(mod.transformer_blocks) == 1 and inner == c == 320 and
+                self.npass == 3 and self.fuse_xattn and self.fuse_xattn_pair and self.fuse_ff and self.fuse_proj and
+                bool(self.lib.wd_xattn_supported(inner, heads, L)) and (M + 63) // 64 >= 192 and hw % 64 == 0 and
+                (name + ".tb0.ff1f.w") in self._w and
+                self._gn_in_consumer(P, ops, name + ".gn", [x], False, M, hw, inner)):
+            return self._transformer_fused(P, name, mod, x)
         tok = self._f32(P, M, inner)
         # (PHOSC variant: the first block's norm1 planes come out of proj_in's epilogue where its tiles hold whole rows)
         n1_pre = None
@@ -1146,6 +1155,44 @@ class UNetEngine:
                         want_stats=True)
         return Act(out, c, h, w, gg._stats, prod=gg)
 
+    def _transformer_fused(self, P, name, mod: SpatialTransformerParams, x: Act) -> Act:
+        """The SpatialTransformer (unet.py:398-412, one base-model block) as ONE wd_ff_fused launch with the transformer front
+        (wd_ff_args.x_in): GroupNorm + proj_in, both folded cross-attentions, norm3, the GEGLU feed-forward and proj_out + residual
+        per 64-token panel; the GroupNorm statistics of the result for the next ResBlock come out of its epilogue."""
+        B, M, hw, c = self._B, self._B * x.h * x.w, x.h * x.w, x.c
+        heads, d, L = mod.heads, mod.d_head, self._ctx_len
+        p = name + ".tb0"
+        folds = []
+        for tag in ("a1", "a2"):  # K/V/to_q/to_out folded per sample in the conditioning phase, as in _transformer
+            ko = self.kv_off[f"{p}.{tag}"]
+            mq = self._f32(P, B, heads * L, c)
+            mo = self._f32(P, B, heads * L, c)
+            mq_pl = torch.zeros((B, 2, 64, c), dtype=torch.bfloat16, device=self.device)
+            mot_pl = torch.zeros((B, 2, c, 64), dtype=torch.bfloat16, device=self.device)
+            P.keep += [mq_pl, mot_pl]
+            P.cond.append((self.lib.wd_xattn_fold,
+                           (self._kv.data_ptr() + 4 * ko, self.kv_total, self._kv.data_ptr() + 4 * (ko + c), self.kv_total, B,
+                            heads, L, d, float(d ** -0.5), self._w[f"{p}.{tag}.q.f32"].data_ptr(),
+                            self._w[f"{p}.{tag}.o.f32"].data_ptr(), c, mq.data_ptr(), mo.data_ptr(), mq_pl.data_ptr(),
+                            mot_pl.data_ptr()), f"{p}.{tag}:fold"))
+            folds.append((mq_pl, mot_pl))
+        tok2 = self._f32(P, M, c)
+        out = self._f32(P, M, c)
+        part, nchunk, pc = x.stats
+        pw = self._wfrag(name + ".pi.w")
+        front = dict(x_in=x.t.data_ptr(), x_in_ld=c, hw=hw, gn_part=part.data_ptr(), gn_nchunk=nchunk, gn_pcpg=pc, gn_cpg=c // 32,
+                     gn_eps=1e-6, gn_gamma=self._w[name + ".gn.g"].data_ptr(), gn_beta=self._w[name + ".gn.b"].data_ptr(),
+                     pi_hi=pw[0].data_ptr(), pi_lo=pw[1].data_ptr(), pi_b=self._w[name + ".pi.b"].data_ptr(),
+                     ln2_gamma=self._w[p + ".norm2.g"].data_ptr(), ln2_beta=self._w[p + ".norm2.b"].data_ptr(),
+                     mq_a=folds[0][0].data_ptr(), mot_a=folds[0][1].data_ptr(), xb_a=self._w[p + ".a1.o.b"].data_ptr(),
+                     mq_b=folds[1][0].data_ptr(), mot_b=folds[1][1].data_ptr(), xb_b=self._w[p + ".a2.o.b"].data_ptr(),
+                     ln3_gamma=self._w[p + ".norm3.g"].data_ptr(), ln3_beta=self._w[p + ".norm3.b"].data_ptr(), ln_eps=1e-5,
+                     heads=heads, L=L, tok2=tok2.data_ptr())
+        ffi = mod.transformer_blocks[0].ff.net[2].in_features
+        fa = self._ff_fused(P.step, p, None, tok2, M, c, ffi, out, None, proj=(name + ".po.w", self._w[name + ".po.b"], x.t, hw),
+                            front=front)
+        return Act(out, c, x.h, x.w, fa._stats, prod=fa)
+
     def _wfrag(self, wname):
         """The fragment-major image (wd_gemm_pack_w) of a packed matrix, kept up to date by refresh_weights."""
         if wname not in self._wf:
@@ -1154,13 +1201,18 @@ class UNetEngine:
             self._pack = None  # the next refresh_weights rebuilds the repack table with this image in it
         return self._wf[wname]
 
-    def _ff_fused(self, ops, p, n3, resid, M, inner, ffi, out_f32, out_pl, proj=None):
+    def _ff_fused(self, ops, p, n3, resid, M, inner, ffi, out_f32, out_pl, proj=None, front=None):
         """x + FeedForward(LN3(x)) (unet.py:343-344, :122-149) as one wd_ff_fused launch.  proj = (weight name, bias, residual
         tensor, hw): the SpatialTransformer's proj_out + residual (unet.py:406-412) in the same launch, with the GroupNorm statistics
-        of the result for the next ResBlock; returns the statistics tuple then."""
+        of the result for the next ResBlock; returns the statistics tuple then.  front: the wd_ff_args fields of the transformer
+        front (n3 is None then: the launch makes the norm3 rows itself)."""
         a = N.WdFfArgs()
         lo_ok = self.npass == 3
-        a.x_hi, a.x_lo, a.x_ld = n3[0].data_ptr(), (n3[1].data_ptr() if lo_ok else None), n3.shape[2]
+        if front is None:
+            a.x_hi, a.x_lo, a.x_ld = n3[0].data_ptr(), (n3[1].data_ptr() if lo_ok else None), n3.shape[2]
+        else:
+            for k, v in front.items():
+                setattr(a, k, v)
         a.m, a.c, a.inner = M, inner, ffi
         w1, w2 = self._wfrag(p + ".ff1f.w"), self._wfrag(p + ".ff2.w")
         a.w1_hi, a.w1_lo, a.b1 = w1[0].data_ptr(), w1[1].data_ptr(), self._w[p + ".ff1f.b"].data_ptr()
@@ -1184,7 +1236,8 @@ class UNetEngine:
                 a.stat_part, a.stat_cpg, a.hw_out = part.data_ptr(), inner // 32, hw
                 stats = (part, nchunk, inner // 32)
         self._cur_plan.keep.append(a)
-        ops.append((self.lib.wd_ff_fused, (C.byref(a),), p + (".ff + proj_out (fused)" if proj is not None else ".ff (fused)")))
+        what = ".ff (fused)" if proj is None else ".ff + proj_out (fused)" if front is None else ": gn + proj_in + a1 + a2 + ff + proj_out (fused)"
+        ops.append((self.lib.wd_ff_fused, (C.byref(a),), p + what))
         a._stats = stats
         return a
 
