@@ -2,7 +2,7 @@
 """Benchmark of the denoising hot path: images/s of 1000-step DDPM sampling (999 executed steps,
 reference train.py:221) of 64x256 word images = [4,8,32] latents, base UNet (unet.py semantics), batch 64 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 A "step" is one denoising step of the whole batch: UNet forward + x <- update with on-device noise + timestep
@@ -11,11 +11,13 @@ full sampling() call of B images per GPU delivers per second at the measured ste
 full call).  Ranks are independent (weak scaling, no collective in the timed loop): batch shards + per-sample
 Philox streams keyed by the global sample index.
 
-Prints ONE JSON line on rank 0 with the driver's fields plus
+Prints ONE JSON line on rank 0 with the driver's fields.  A plain run does only what they need: set-up, the W warm-up and K
+timed steps, --dump-outputs if given, the line.  --full adds the extras (null in a plain line), each after the timed steps:
   roofline     - the dominant kernel class (tap-gather MFMA GEMM): algorithmic FLOP / hipEvent-measured time;
   cpu_baseline - the CPU oracle (a port: the reference itself does not travel) on this box's host cores;
 and, at N = 1, extras that never cost the line: full_call (one real Diffusion.sampling() of 64 words x 999 steps), train_step
 (BASELINE configs[2]: the train.py loop, + one epoch over cached latents), phosc_variant (configs[4] on one GPU), vae_decode.
+The --no-* switches leave single extras out of a --full run.
 """
 from __future__ import annotations
 
@@ -661,13 +663,15 @@ def main():
     ap.add_argument("--variant", default="base", choices=["base", "phosc"],
                     help="base = BASELINE configs[1] (the headline); phosc = UNetModelPhosc with a 769-int PHOSC vector "
                          "(configs[4] model: 779-token context, 256-token self-attention), reported as an extra")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extras: roofline and kernel classes, CPU baseline, full sampling() "
+                         "call, PHOSC variant, training step, VAE decode (a plain run measures the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-vae", action="store_true", help="skip the VAE-decode extra (section 8f-2)")
     ap.add_argument("--train-steps", type=int, default=-1,
-                    help="also time this many train.py-style steps (0 = skip; default: 30 on one GPU, 0 on several - the "
-                         "multi-GPU run is the scaling measurement of the headline metric, pass a count to add the data-parallel "
-                         "training leg with its gradient all-reduce)")
+                    help="with --full, also time this many train.py-style steps (0 = skip; default: 30 on one GPU, 10 on several, "
+                         "where it is the data-parallel leg with its gradient all-reduce)")
     ap.add_argument("--no-full-call", action="store_true", help="skip the un-extrapolated full sampling() call")
     ap.add_argument("--no-phosc", action="store_true", help="skip the PHOSC-variant extra (BASELINE configs[4] on one GPU)")
     ap.add_argument("--train-worker", action="store_true",
@@ -675,7 +679,8 @@ def main():
                          "object from rank 0")
     ap.add_argument("--train-timeout", type=float, default=240.0, help="wall-clock limit of the multi-GPU training leg (seconds)")
     ap.add_argument("--launch-check", action="store_true",
-                    help="rendezvous / barrier / max-over-ranks only, no GPU work (CPU rehearsal of the N-rank control flow)")
+                    help="rendezvous / barrier / max-over-ranks only, no GPU work (CPU rehearsal of the N-rank control flow of a "
+                         "--full run)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (latents, noise prediction) as DIR/*.npy")
     a = ap.parse_args()
@@ -692,6 +697,11 @@ def main():
         return train_worker(a)
     if a.launch_check:
         return launch_check(a)
+    if not a.full:  # the headline alone: every extra off
+        if a.train_steps > 0:
+            ap.error("--train-steps times the training leg, an extra of --full")
+        a.no_roofline = a.no_phosc = a.no_full_call = a.no_cpu_baseline = a.no_vae = True
+        a.train_steps = 0
 
     from worddiffusion_amd import dist as wdist
     # WDIFF_BENCH_REHEARSE=1: every rank on cuda:0 with gloo - rehearses the N>1 control flow on a one-GPU box (numbers from

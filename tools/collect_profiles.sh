@@ -8,9 +8,9 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py > $OUT/${TAG}_bench_full.json 2> $OUT/${TAG}_bench_full.err || exit 1
+python3 $ROOT/bench.py --full > $OUT/${TAG}_bench_full.json 2> $OUT/${TAG}_bench_full.err || exit 1
 echo "[collect] bench done"
-B="$ROOT/bench.py --no-cpu-baseline --train-steps 0 --no-vae --no-full-call --no-phosc"
+B="$ROOT/bench.py --full --no-cpu-baseline --train-steps 0 --no-vae --no-full-call --no-phosc"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_bench -o b -- python3 $B > $OUT/${TAG}_prof_bench.log 2>&1 || exit 2
 echo "[collect] bench kernel stats done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_train -o t -- python3 $ROOT/tools/train_prof.py > $OUT/${TAG}_prof_train.log 2>&1 || exit 3
