@@ -117,9 +117,9 @@ typedef struct wd_gemm_args {
     /* GroupNorm of the RESULT in the combine launch (nn.GroupNorm of the consumer, unet.py:427-431 / :161-162, + SiLU): when
      * gn_gamma != NULL the planes out_hi / out_lo receive SiLU?((result - mean) * rstd * gn_gamma[col] + gn_beta[col]) with the
      * statistics of (sample, group of gn_cpg channels) instead of the result itself; out_f32 and stat_part are written as
-     * usual.  Only where one combine tile holds whole (sample, group) blocks: hw_out == 64, m % 64 == 0, n % 40 == 0,
-     * 40 % gn_cpg == 0, gn_cpg % stat_cpg == 0, stat_part and ws given, no activation, and the launch must be one that cuts K
-     * (wd_gemm_auto_ksplit(...) > 1 with ksplit = 0) - anything else returns an error rather than skip the norm. */
+     * usual.  Only where one combine tile holds whole (sample, group) blocks (hw_out == 64, 40 % gn_cpg == 0, stat_part given, no
+     * activation) and the launch cuts K or holds all of K (tile 64080); wd_gemm_check says whether a given launch does - anything
+     * else returns an error rather than skip the norm. */
     const float* gn_gamma;
     const float* gn_beta;
     float gn_eps;
@@ -158,6 +158,11 @@ typedef struct wd_gemm_args {
 } wd_gemm_args;
 
 int wd_gemm(const wd_gemm_args* args, void* stream);
+
+/* What wd_gemm would do with `args`, without launching anything (host only, no HIP call): WD_OK when wd_gemm accepts them, else
+ * WD_EINVAL.  On WD_OK and out != NULL, *out receives the args as the kernel sees them (tile, ksplit, tickets, slab_rows resolved).
+ * Callers ask this rather than restate the rules above. */
+int wd_gemm_check(const wd_gemm_args* args, wd_gemm_args* out);
 
 /* wd_gemm_args.w_layout == 3: the weights of a GEMM with n % 320 == 0, ktot % 64 == 0 in FRAGMENT-MAJOR order - the 16 bytes
  * lane l of a v_mfma_f32_16x16x32_bf16 B fragment holds, W[16 ct + (l & 15)][32 ks + 8 (l >> 4) .. + 8], at byte

@@ -377,3 +377,70 @@ def test_vae_decoder_state_dict_layout(tmp_path):
         assert torch.equal(v, back.state_dict()[k])
     with pytest.raises(Exception):
         back.decode(torch.zeros(1, 4, 4, 8))  # no CPU fallback
+
+
+# ---- wd_gemm_check: which wd_gemm launches are legal, asked without a GPU (the library is never launched here)
+_P = 1 << 20  # placeholder operand address: non-NULL, 16-byte aligned (wd_gemm_check reads no memory)
+
+
+def _gemm_args(m, n, hw_out, srcs, **fields):
+    """srcs: (c, ntaps, gathered, hw_src) per source; every pointer a placeholder."""
+    a = N.WdGemmArgs()
+    for i, (c, ntaps, gathered, hw_src) in enumerate(srcs):
+        s = a.src[i]
+        s.hi = s.lo = _P
+        s.gather = _P if gathered else None
+        s.ld, s.c, s.ntaps, s.hw_src = c, c, ntaps, hw_src
+    a.nsrc, a.npass, a.w_hi, a.w_lo = len(srcs), 3, _P, _P
+    a.m, a.n, a.ktot, a.hw_out = m, n, sum(c * t for c, t, _, _ in srcs), hw_out
+    a.out_f32, a.out_ld, a.ws, a.ws_floats = _P, n, _P, 128 * 128 * 160 * 8
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+_A32 = dict(a32=_P, a32_ld=320, a32_part=_P, a32_nchunk=4, a32_pcpg=10, a32_cpg=10, a32_gamma=_P, a32_beta=_P)
+_PLANES = dict(out_hi=_P, out_lo=_P)
+_GEMM_CHECK = {
+    # name: (args, resolved tile, resolved ksplit or None = "a K cut"); None instead of a tile: wd_gemm refuses the args
+    "8x32 3x3 conv, B 64": (_gemm_args(64 * 256, 320, 256, [(320, 9, True, 256)], w_layout=3, tile=64320, slab_rows=32), 64320, 1),
+    "4x16 conv, 64x80 whole K": (_gemm_args(64 * 64, 640, 64, [(640, 9, True, 64)], w_layout=3, tile=64080, slab_rows=16), 64080, 1),
+    "proj_in with a32": (_gemm_args(64 * 256, 320, 256, [(320, 1, False, 256)], w_layout=3, **_A32), 64320, 1),
+    "320 columns with ln": (_gemm_args(64 * 256, 320, 256, [(320, 1, False, 0)], w_layout=3, tile=64320, ln_gamma=_P, ln_beta=_P,
+                                       out_pl_ld=320, **_PLANES), 64320, 1),
+    "K cut with gn": (_gemm_args(8 * 64, 640, 64, [(640, 9, True, 64)], stat_part=_P, stat_cpg=20, gn_gamma=_P, gn_beta=_P, gn_cpg=20,
+                                 out_pl_ld=640, **_PLANES), 128160, None),
+    "Upsample, 4 phases": (_gemm_args(64 * 256, 320, 256, [(640, 4, True, 64)], w_layout=3, tile=64320, w_ngroups=4,
+                                      w_group_stride=320 * 4 * 640), 64320, 1),
+    "w_layout 3, n % 80": (_gemm_args(64 * 256, 360, 256, [(320, 9, True, 256)], w_layout=3, tile=64320, slab_rows=32), None, None),
+    "gn, resolved ksplit 1": (_gemm_args(256 * 64, 640, 64, [(640, 9, True, 64)], w_layout=3, tile=64320, stat_part=_P, stat_cpg=20,
+                                         gn_gamma=_P, gn_beta=_P, gn_cpg=20, out_pl_ld=640, **_PLANES), None, None),
+    "ln, misaligned out_hi": (_gemm_args(64 * 256, 320, 256, [(320, 1, False, 0)], w_layout=3, tile=64320, ln_gamma=_P, ln_beta=_P,
+                                         out_pl_ld=320, out_hi=_P + 2, out_lo=_P), None, None),
+    "GEGLU with statistics": (_gemm_args(64 * 256, 2560, 256, [(320, 1, False, 0)], act=N.ACT_GEGLU, tile=128160, stat_part=_P,
+                                         stat_cpg=80), None, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_GEMM_CHECK))
+def test_wd_gemm_check(name):
+    lib = N.lib()
+    a, tile, ksplit = _GEMM_CHECK[name]
+    req = bytes(a)
+    out = N.WdGemmArgs()
+    rc = lib.wd_gemm_check(ctypes.byref(a), ctypes.byref(out))
+    assert bytes(a) == req  # the request is left as it is
+    if tile is None:
+        assert rc == N.WD_EINVAL
+        assert lib.wd_gemm(ctypes.byref(a), None) == N.WD_EINVAL  # (returns before any HIP call)
+        return
+    assert rc == N.WD_OK and lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_OK
+    assert out.tile == tile and not out.tickets
+    assert out.ksplit > 1 if ksplit is None else out.ksplit == ksplit
+
+
+def test_wd_gemm_check_gn_needs_the_k_cut():
+    """The refusal above is the K cut's: the same launch without the norm is legal and resolves to ksplit 1."""
+    a = _gemm_args(256 * 64, 640, 64, [(640, 9, True, 64)], w_layout=3, tile=64320, stat_part=_P, stat_cpg=20)
+    out = N.WdGemmArgs()
+    assert N.lib().wd_gemm_check(ctypes.byref(a), ctypes.byref(out)) == N.WD_OK and out.ksplit == 1

@@ -2229,9 +2229,33 @@ extern "C" int wd_gemm_auto_ksplit(int m, int n, int ktot, int64_t ws_floats) {
     return wd_auto_ksplit(wd_auto_tile(m, n, nk64, true, (long)ws_floats), m, n, nk64, (long)ws_floats);
 }
 
-extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
-    if (!pa) return WD_EINVAL;
-    wd_gemm_args a = *pa;
+namespace {
+// the launch families of wd_gemm: wd_gemm_resolve picks one, wd_gemm runs it
+enum WdKernel {
+    K_GEMMQ,  // 64 x 80, all of K inside the workgroup (wd_gemmq_kernel; w_layout 3, tile 64080)
+    K_GEMMW,  // weights straight to registers (wd_gemmw_kernel; w_layout 3, tile 64320 or 128160)
+    K_V4,     // two co-resident 4-wave workgroups per CU (wd_gemm4_kernel; 128 x 160)
+    K_M16,    // the 16x16x32 MFMA form of the v2 kernel (wd_gemm2_kernel<..., M16>; 128 x 160)
+    K_V2,     // wd_gemm2_kernel with `ks` K-halves per workgroup
+    K_V1,     // wd_gemm_kernel (K not a multiple of 64, or WDIFF_GEMM_V1)
+    K_SLAB,   // WDIFF_EXPERIMENTAL: slab-order weights (wd_gemm3_kernel; w_layout 1)
+    K_CONV3,  // WDIFF_EXPERIMENTAL: row-shared taps (wd_conv3_kernel)
+    K_V8,     // WDIFF_EXPERIMENTAL: ring kernel with loader waves (wd_gemm8_kernel)
+    K_PP,     // WDIFF_EXPERIMENTAL: wd_gemm2_kernel<..., PP>
+};
+
+struct WdResolved {
+    wd_gemm_args a;  // the args as the kernel sees them: tile, ksplit, tickets, slab_rows and the dbg stagger bit resolved
+    WdKernel kernel;
+    int ks;          // K-halves per workgroup (K_V2, K_SLAB)
+};
+}  // namespace
+
+// Every check and every decision of wd_gemm, host only (no HIP call): WD_OK and `r` filled, or WD_EINVAL.
+static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
+    wd_gemm_args a = in;
+    static const int ks_env = getenv("WDIFF_GEMM_KS") ? atoi(getenv("WDIFF_GEMM_KS")) : 2;
+    r.ks = ks_env == 1 ? 1 : 2;
     if (a.ksplit < 0 || a.ksplit > WD_MAX_KSPLIT) return WD_EINVAL;
     if (a.w_layout == 3) {
         // fragment-major weights (wd_gemm_pack_w): the 64 x 320 weights-to-registers kernel only
@@ -2239,7 +2263,7 @@ extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
             return WD_EINVAL;
         if (a.tile == 0) a.tile = (a.a32 || a.ln_gamma) ? 64320 : 128160;
         if (a.n % (a.tile % 1000)) return WD_EINVAL;
-        if (a.tile == 64080) a.ksplit = 1;  // (all of K inside the workgroup: wd_gemmq_kernel; wd_gemmq_applies() is checked at the dispatch)
+        if (a.tile == 64080) a.ksplit = 1;  // (all of K inside the workgroup: wd_gemmq_kernel; wd_gemmq_applies() is checked below)
     }
     if (a.w_ngroups > 1) {
         // weight groups: the 64 x 320 weights-to-registers kernel only, a tile inside one run of rows, no K cut
@@ -2315,7 +2339,6 @@ extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
     if (a.act == WD_ACT_GEGLU && (a.n % 64 || a.tile == 0)) return WD_EINVAL;  // the tile fixes the x|gate packing
     if (a.rowvec && a.rowvec_ld <= 0) return WD_EINVAL;
     if (a.resid && a.resid_ld <= 0) return WD_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     if (a.w_layout == 3) {
         bool ok = a.src[0].ntaps <= 9 && (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
@@ -2331,13 +2354,15 @@ extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
         if (a.tile == 64080) {
             if (!wd_gemmq_applies(a)) return WD_EINVAL;
             if (a.gn_gamma && (40 % a.gn_cpg || 80 % a.gn_cpg)) return WD_EINVAL;
-            return wd_gemmq_launch(a, st);
+            r.a = a, r.kernel = K_GEMMQ;
+            return WD_OK;
         }
         const int nk64 = a.ktot / 64;
         if (a.ksplit == 0) a.ksplit = a.ws ? wd_auto_ksplit(a.tile, a.m, a.n, nk64, a.ws_floats) : 1;
         if (a.ksplit > 1 && (nk64 < a.ksplit || (long)a.ksplit * a.m * a.n > a.ws_floats)) a.ksplit = 1;
         if (a.gn_gamma && a.ksplit <= 1) return WD_EINVAL;
-        return wd_gemmw_launch(a, st);
+        r.a = a, r.kernel = K_GEMMW;
+        return WD_OK;
     }
 #ifndef WDIFF_EXPERIMENTAL
     if (a.w_layout == 1) return WD_EINVAL;  // (the slab kernel is an experimental build option)
@@ -2346,21 +2371,12 @@ extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
         // slab-order weights: v3 kernel only.  Contract: c % 32 == 0 (checked above), src[1] identity, slab_rows set.
         if (a.src[0].ntaps > 9 || a.slab_rows <= 0) return WD_EINVAL;
         if (a.nsrc == 2 && (a.src[1].gather || a.src[1].ntaps != 1)) return WD_EINVAL;
-        int t3 = a.tile;
-        if (t3 == 0) t3 = (a.act == WD_ACT_GEGLU || a.n % 160) ? 128064 : 128160;
-        if (a.act == WD_ACT_GEGLU && a.n % (t3 % 1000)) return WD_EINVAL;
+        if (a.tile == 0) a.tile = (a.act == WD_ACT_GEGLU || a.n % 160) ? 128064 : 128160;
+        if (a.act == WD_ACT_GEGLU && a.n % (a.tile % 1000)) return WD_EINVAL;
         if (a.slab_rows > 192) return WD_EINVAL;
-        static const int ks3_env = getenv("WDIFF_GEMM_KS") ? atoi(getenv("WDIFF_GEMM_KS")) : 2;
-#define WD_DISPATCH3(BM_, BN_)                                                                                   \
-    if (ks3_env == 1) return a.npass == 3 ? launch3<BM_, BN_, 3, 192, 1>(a, st) : launch3<BM_, BN_, 1, 192, 1>(a, st); \
-    return a.npass == 3 ? launch3<BM_, BN_, 3, 192, 2>(a, st) : launch3<BM_, BN_, 1, 192, 2>(a, st)
-        switch (t3) {
-            case 128064: WD_DISPATCH3(128, 64);
-            case 128128: WD_DISPATCH3(128, 128);
-            case 128160: WD_DISPATCH3(128, 160);
-            default: return WD_EINVAL;
-        }
-#undef WD_DISPATCH3
+        if (a.tile != 128064 && a.tile != 128128 && a.tile != 128160) return WD_EINVAL;
+        r.a = a, r.kernel = K_SLAB;
+        return WD_OK;
     }
 #endif
     bool conv3 = false;
@@ -2429,55 +2445,101 @@ extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
     }
     // the GroupNorm epilogue exists in the combine launch of the 128 x 160 kernels only: anything else is an error, not a skipped norm
     if (a.gn_gamma && !(a.ksplit > 1 && tile == 128160 && v2ok && !use_v4 && !conv3)) return WD_EINVAL;
-    static const int ks_env = getenv("WDIFF_GEMM_KS") ? atoi(getenv("WDIFF_GEMM_KS")) : 2;
-    const int ks = ks_env == 1 ? 1 : 2;
     static const int stagger_min = getenv("WDIFF_GEMM_STAGGER_MIN") ? atoi(getenv("WDIFF_GEMM_STAGGER_MIN")) : 10;
     static const bool stagger = getenv("WDIFF_GEMM_STAGGER") ? atoi(getenv("WDIFF_GEMM_STAGGER")) != 0 : true;
     static const bool m16 = getenv("WDIFF_GEMM_M16") ? atoi(getenv("WDIFF_GEMM_M16")) != 0 : true;
     static const bool pp = getenv("WDIFF_GEMM_PP") ? atoi(getenv("WDIFF_GEMM_PP")) != 0 : false;  // measured: no gain
+    a.tile = tile;
 #ifdef WDIFF_EXPERIMENTAL
-#define WD_DISPATCH_PP(BM_, BN_) \
-    if (v2ok && ks == 2 && pp) return a.npass == 3 ? launch2<BM_, BN_, 3, 2, true>(a, st) : launch2<BM_, BN_, 1, 2, true>(a, st);
+    if (conv3 && v2ok) return r.a = a, r.kernel = K_CONV3, WD_OK;
+#endif
+    if (tile != 128064 && tile != 128160 && tile != 128128 && tile != 64064) return WD_EINVAL;
+    if (tile == 128160) {
+        // second K-half group runs one stage late (see the kernel); the extra drain phase only pays on long K loops
+        if (use_v4) return r.a = a, r.kernel = K_V4, WD_OK;
+#ifdef WDIFF_EXPERIMENTAL
+        // ring kernel with dedicated loader waves (wd_gemm8_kernel): within +-5 % of the default kernel on every shape; no
+        // fused GroupNorm statistics (its 768-thread epilogue would need a larger statistics scratch).  WDIFF_GEMM_V8=1 takes it wherever legal, dbg 0x80000 forces it (parity tests).
+        static const int v8_env = getenv("WDIFF_GEMM_V8") ? atoi(getenv("WDIFF_GEMM_V8")) : 0;
+        bool v8ok = a.ktot % 32 == 0 && a.src[0].ntaps <= 9 && !a.stat_part && !a.gn_gamma && a.act != WD_ACT_GEGLU &&
+                    (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
+        for (int s8 = 0; s8 < a.nsrc; ++s8) v8ok = v8ok && (a.src[s8].c % 32 == 0);
+        if (v8ok && (v8_env == 1 || (a.dbg & 0x80000))) {
+            if (a.ksplit > 1 && (a.ktot / 32 < a.ksplit || (long)a.ksplit * a.m * a.n > a.ws_floats)) a.ksplit = 1;
+            a.tickets = nullptr;
+            return r.a = a, r.kernel = K_V8, WD_OK;
+        }
+#endif
+        if (v2ok && r.ks == 2 && m16 && stagger && nk64 / a.ksplit >= stagger_min) a.dbg |= 0x200;
+        if (v2ok && r.ks == 2 && m16) return r.a = a, r.kernel = K_M16, WD_OK;
+    }
+#ifdef WDIFF_EXPERIMENTAL
+    if (v2ok && r.ks == 2 && pp) return r.a = a, r.kernel = K_PP, WD_OK;
 #else
-#define WD_DISPATCH_PP(BM_, BN_) (void)pp;
+    (void)pp;
 #endif
-#define WD_DISPATCH(BM_, BN_)                                                                      \
-    WD_DISPATCH_PP(BM_, BN_)                                                                       \
-    if (v2ok && ks == 2) return a.npass == 3 ? launch2<BM_, BN_, 3, 2>(a, st) : launch2<BM_, BN_, 1, 2>(a, st); \
-    if (v2ok) return a.npass == 3 ? launch2<BM_, BN_, 3, 1>(a, st) : launch2<BM_, BN_, 1, 1>(a, st); \
-    a.ksplit = 1;                                                                                   \
-    a.tickets = nullptr;                                                                            \
-    return a.npass == 3 ? launch<BM_, BN_, 3>(a, st) : launch<BM_, BN_, 1>(a, st)
+    if (v2ok) return r.a = a, r.kernel = K_V2, WD_OK;
+    a.ksplit = 1;
+    a.tickets = nullptr;
+    r.a = a, r.kernel = K_V1;
+    return WD_OK;
+}
+
+extern "C" int wd_gemm_check(const wd_gemm_args* in, wd_gemm_args* out) {
+    if (!in) return WD_EINVAL;
+    WdResolved r;
+    const int rc = wd_gemm_resolve(*in, r);
+    if (rc == WD_OK && out) *out = r.a;
+    return rc;
+}
+
+extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {
+    if (!pa) return WD_EINVAL;
+    WdResolved r;
+    const int rc = wd_gemm_resolve(*pa, r);
+    if (rc != WD_OK) return rc;
+    const wd_gemm_args& a = r.a;
+    const bool p3 = a.npass == 3;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (r.kernel == K_GEMMQ) return wd_gemmq_launch(a, st);
+    if (r.kernel == K_GEMMW) return wd_gemmw_launch(a, st);
 #ifdef WDIFF_EXPERIMENTAL
-    if (conv3 && v2ok) return a.npass == 3 ? launch_conv3<3>(a, st) : launch_conv3<1>(a, st);
+    if (r.kernel == K_SLAB) {
+#define WD_DISPATCH3(BM_, BN_)                                                                                   \
+    if (r.ks == 1) return p3 ? launch3<BM_, BN_, 3, 192, 1>(a, st) : launch3<BM_, BN_, 1, 192, 1>(a, st); \
+    return p3 ? launch3<BM_, BN_, 3, 192, 2>(a, st) : launch3<BM_, BN_, 1, 192, 2>(a, st)
+        switch (a.tile) {
+            case 128064: WD_DISPATCH3(128, 64);
+            case 128128: WD_DISPATCH3(128, 128);
+            case 128160: WD_DISPATCH3(128, 160);
+            default: return WD_EINVAL;
+        }
+#undef WD_DISPATCH3
+    }
+    if (r.kernel == K_CONV3) return p3 ? launch_conv3<3>(a, st) : launch_conv3<1>(a, st);
+#define WD_DISPATCH_PP(BM_, BN_) \
+    if (r.kernel == K_PP) return p3 ? launch2<BM_, BN_, 3, 2, true>(a, st) : launch2<BM_, BN_, 1, 2, true>(a, st);
+#else
+#define WD_DISPATCH_PP(BM_, BN_)
 #endif
-    switch (tile) {
+#define WD_DISPATCH(BM_, BN_)                                                                       \
+    WD_DISPATCH_PP(BM_, BN_)                                                                        \
+    if (r.kernel == K_V2 && r.ks == 2) return p3 ? launch2<BM_, BN_, 3, 2>(a, st) : launch2<BM_, BN_, 1, 2>(a, st); \
+    if (r.kernel == K_V2) return p3 ? launch2<BM_, BN_, 3, 1>(a, st) : launch2<BM_, BN_, 1, 1>(a, st);             \
+    return p3 ? launch<BM_, BN_, 3>(a, st) : launch<BM_, BN_, 1>(a, st)
+    switch (a.tile) {
         case 128064: WD_DISPATCH(128, 64);
         case 128160:
-            // second K-half group runs one stage late (see the kernel); the extra drain phase only pays on long K loops
-            if (use_v4) return a.npass == 3 ? launch4<3>(a, st) : launch4<1>(a, st);
+            if (r.kernel == K_V4) return p3 ? launch4<3>(a, st) : launch4<1>(a, st);
 #ifdef WDIFF_EXPERIMENTAL
-            {
-                // ring kernel with dedicated loader waves (wd_gemm8_kernel): within +-5 % of the default kernel on every shape; no
-                // fused GroupNorm statistics (its 768-thread epilogue would need a larger statistics scratch).  WDIFF_GEMM_V8=1 takes it wherever legal, dbg 0x80000 forces it (parity tests).
-                static const int v8_env = getenv("WDIFF_GEMM_V8") ? atoi(getenv("WDIFF_GEMM_V8")) : 0;
-                bool v8ok = a.ktot % 32 == 0 && a.src[0].ntaps <= 9 && !a.stat_part && !a.gn_gamma && a.act != WD_ACT_GEGLU &&
-                            (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
-                for (int s8 = 0; s8 < a.nsrc; ++s8) v8ok = v8ok && (a.src[s8].c % 32 == 0);
-                if (v8ok && (v8_env == 1 || (a.dbg & 0x80000))) {
-                    if (a.ksplit > 1 && (a.ktot / 32 < a.ksplit || (long)a.ksplit * a.m * a.n > a.ws_floats)) a.ksplit = 1;
-                    a.tickets = nullptr;
-                    return a.npass == 3 ? launch8<3>(a, st) : launch8<1>(a, st);
-                }
-            }
+            if (r.kernel == K_V8) return p3 ? launch8<3>(a, st) : launch8<1>(a, st);
 #endif
-            if (v2ok && ks == 2 && m16 && stagger && nk64 / a.ksplit >= stagger_min) a.dbg |= 0x200;
-            if (v2ok && ks == 2 && m16)
-                return a.npass == 3 ? launch2<128, 160, 3, 2, false, true>(a, st) : launch2<128, 160, 1, 2, false, true>(a, st);
+            if (r.kernel == K_M16) return p3 ? launch2<128, 160, 3, 2, false, true>(a, st) : launch2<128, 160, 1, 2, false, true>(a, st);
             WD_DISPATCH(128, 160);
         case 128128: WD_DISPATCH(128, 128);
         case 64064: WD_DISPATCH(64, 64);
         default: return WD_EINVAL;
     }
 #undef WD_DISPATCH
+#undef WD_DISPATCH_PP
 }

@@ -104,9 +104,9 @@ def geglu_interleave(w: torch.Tensor, g: int = 32) -> torch.Tensor:
     return torch.stack([x, gt], dim=1).reshape(w.shape)
 
 
-def ff_fused_supported(c: int, inner: int) -> bool:
-    """The shapes csrc/wd_ff.hip covers (== wd_ff_supported of the library, which wd_ff_fused itself enforces)."""
-    return c == 320 and inner > 0 and inner % 128 == 0
+def wdirect_fills_chip(m: int, n: int) -> bool:
+    """Policy: the 64 x 320 weights-to-registers kernel (wd_gemm_args.w_layout 3) is taken where its tiles alone fill the chip."""
+    return ((m + 63) // 64) * (n // 320) >= 256
 
 
 def geglu_tile(inner: int) -> int:
@@ -491,7 +491,7 @@ class UNetEngine:
                     R.matrix(p + ".ff1.w", 2 * ffi, inner).fwd(tb.ff.net[0].proj.weight, g=g)
                     R.vector(p + ".ff1.b", tb.ff.net[0].proj.bias, g=g)
                     R.linear(p + ".ff2", tb.ff.net[2])
-                    if ff_fused_supported(inner, ffi):
+                    if N.lib().wd_ff_supported(inner, ffi):
                         # the fused feed-forward (csrc/wd_ff.hip): x | gate rows in blocks of 16, one MFMA tile each
                         R.matrix(p + ".ff1f.w", 2 * ffi, inner).fwd(tb.ff.net[0].proj.weight, g=16)
                         R.vector(p + ".ff1f.b", tb.ff.net[0].proj.bias, g=16)
@@ -634,8 +634,11 @@ class UNetEngine:
 
     def _gemm(self, ops, what, srcs, wname, m, hw_out, bias=None, rowvec=None, rowvec_ld=0, resid=None,
               resid_ld=0, resid_rows=None, act=N.ACT_NONE, out_f32=None, out_ld=0, out_pl=None, n=None, tile=0,
-              w_row_off=0, want_stats=False, a32=None, ln=None):
-        """a32 = (Act, norm name, eps, silu): src[0] is that fp32 map, normalised while it is staged (wd_gemm_args.a32*)."""
+              w_row_off=0, want_stats=False, a32=None, ln=None, w_groups=None):
+        """a32 = (Act, norm name, eps, silu): src[0] is that fp32 map, normalised while it is staged (wd_gemm_args.a32*).
+        ln: name of the LayerNorm whose output the epilogue also writes, as new planes ``a._ln_pl``, where wd_gemm takes it
+        (wd_gemm_args.ln_*; ``a._ln_pl`` is None otherwise).  w_groups = (count, stride): weight groups (wd_gemm_args.w_ngroups).
+        What wd_gemm can run is wd_gemm_check's answer; the tests written here are policy."""
         a = N.WdGemmArgs()
         for i, s in enumerate(srcs):
             a.src[i] = s
@@ -645,6 +648,26 @@ class UNetEngine:
         ktot = wp.shape[2]
         assert ktot == sum(s.ntaps * s.c for s in srcs), (what, ktot, [(s.ntaps, s.c) for s in srcs])
         nrows = wp.shape[1] if n is None else n
+        a.w_hi = wp[0].data_ptr() + 2 * w_row_off * ktot
+        a.w_lo = wp[1].data_ptr() + 2 * w_row_off * ktot
+        a.m, a.n, a.ktot, a.hw_out = m, nrows, ktot, hw_out
+        a.bias = _ptr(bias)
+        a.rowvec, a.rowvec_ld = rowvec, rowvec_ld
+        a.resid, a.resid_ld, a.resid_rows = resid, resid_ld, resid_rows
+        a.act = act
+        a.out_f32, a.out_ld = _ptr(out_f32), out_ld
+        if out_pl is not None:
+            a.out_hi, a.out_lo, a.out_pl_ld = out_pl[0].data_ptr(), out_pl[1].data_ptr(), out_pl.shape[2]
+        if a32 is not None:
+            self._set_a32(a, *a32)
+        if w_groups is not None:
+            a.w_ngroups, a.w_group_stride = w_groups
+        a.tile = tile
+        if self._ws is None:
+            self._ws = torch.empty(128 * 128 * 160 * 8, dtype=torch.float32, device=self.device)  # 84 MB split-K scratch
+        a.ksplit, a.ws, a.ws_floats = 0, self._ws.data_ptr(), self._ws.numel()
+        self._give_tickets(a, m, nrows)
+        # ---- kernel form: the policy below picks a candidate, wd_gemm_check says whether it is legal
         span = 0
         if self.use_slab and w_row_off == 0 and (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather)):
             tabnp = getattr(srcs[0], "_tab_np", None)
@@ -652,41 +675,23 @@ class UNetEngine:
             # the slab kernel runs 128-row panels: only worth it when they fill the chip
             if span > 192 or ((m + 127) // 128) * max(1, nrows // 160) < 96:
                 span = 0
-        wdirect = (self.use_wdirect and not span and not self.use_conv3 and w_row_off == 0 and n is None and act == N.ACT_NONE and
-                   tile == 0 and nrows % 320 == 0 and ktot % 64 == 0 and all(s.c % 64 == 0 for s in srcs) and srcs[0].ntaps <= 9 and
-                   (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather)) and
-                   # (the K-cut layers of the 4 x 16 level stay on the LDS-staged kernel: this one is 5 % faster on their long loops
-                   # in isolation and 2 % slower inside the step)
-                   ((m + 63) // 64) * (nrows // 320) >= 256)
-        # 3x3 layers over 64-position samples (the 4 x 16 level): 64 x 80 tiles with all of K inside the workgroup (wd_gemmq_kernel) instead
-        # of a K cut over workgroups + combine launch
         s0 = srcs[0]
-        sm_down = s0.ntaps == 9 and getattr(s0, "_down_w", 0) == 16 and s0.hw_src == 256   # the stride-2 convolution 8x32 -> 4x16
-        sm_conv = (s0.ntaps == 9 and getattr(s0, "_same_w", 0) in (16, 32) and s0.hw_src == 64) or sm_down
-        sm_ident = s0.ntaps == 1 and not s0.gather
-        smallmap = (self.use_smallmap and not wdirect and not span and not self.use_conv3 and a32 is None and ln is None and
-                    w_row_off == 0 and n is None and act == N.ACT_NONE and tile == 0 and self.npass == 3 and hw_out == 64 and
-                    (sm_conv or sm_ident) and (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather)) and
-                    m % 64 == 0 and nrows % 80 == 0 and all(q.c % 64 == 0 for q in srcs) and not resid_rows and
-                    128 <= (m // 64) * (nrows // 80) <= 512)
-        assert a32 is None or wdirect, what
-        if a32 is not None:
-            x32, gname, eps, silu = a32
-            part, nchunk, pc = x32.stats
-            a.a32, a.a32_ld, a.a32_part = x32.t.data_ptr(), x32.c, part.data_ptr()
-            a.a32_nchunk, a.a32_pcpg, a.a32_cpg = nchunk, pc, x32.c // 32
-            a.a32_gamma, a.a32_beta = self._w[gname + ".g"].data_ptr(), self._w[gname + ".b"].data_ptr()
-            a.a32_eps, a.a32_silu = float(eps), int(silu)
-        if smallmap:
+        # fragment-major weights only for whole matrices with the auto tile and no activation, and not beside the experimental kernels
+        frag = not span and not self.use_conv3 and w_row_off == 0 and n is None and act == N.ACT_NONE and tile == 0
+        # the image width of a 3x3 gather table (wd_gemm_args.slab_rows): the OUTPUT width for a stride-2 table
+        width = (getattr(s0, "_down_w", 0) or getattr(s0, "_same_w", 0)) if s0.ntaps == 9 else 0
+        # (the K-cut layers of the 4 x 16 level stay on the LDS-staged kernel: the weights-to-registers kernel is 5 % faster on their
+        # long loops in isolation and 2 % slower inside the step - hence the chip-fill rule)
+        wdirect = (frag and self.use_wdirect and wdirect_fills_chip(m, nrows) and
+                   self._legal(a, w_layout=3, tile=64320, slab_rows=getattr(s0, "_same_w", 0) if s0.ntaps == 9 else 0))
+        # 3x3 layers over 64-position samples (the 4 x 16 level): 64 x 80 tiles with all of K inside the workgroup (wd_gemmq_kernel)
+        # instead of a K cut over workgroups + combine launch, where that grid holds 128 to 512 tiles
+        smallmap = (frag and not wdirect and self.use_smallmap and hw_out == 64 and 128 <= (m // 64) * (nrows // 80) <= 512 and
+                    self._legal(a, w_layout=3, tile=64080, slab_rows=width))
+        assert (a32 is None and w_groups is None) or wdirect, what
+        if wdirect or smallmap:
             wf = self._wfrag(wname)
             a.w_hi, a.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
-            a.w_layout, a.slab_rows = 3, (16 if sm_down else srcs[0]._same_w if sm_conv else 0)
-            tile = 64080
-        elif wdirect:
-            wf = self._wfrag(wname)
-            a.w_hi, a.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
-            a.w_layout, a.slab_rows = 3, getattr(srcs[0], "_same_w", 0) if srcs[0].ntaps == 9 else 0
-            tile = 64320
         elif span:
             meta = (srcs[0].ntaps, srcs[0].c, srcs[1].c if len(srcs) > 1 else 0)
             if wname not in self._w3:
@@ -696,45 +701,72 @@ class UNetEngine:
             w3 = self._w3[wname]
             a.w_hi, a.w_lo = w3[0].data_ptr(), w3[1].data_ptr()
             a.w_layout, a.slab_rows = 1, span
-            tile = 0 if tile == 0 else tile
         else:
-            a.w_hi = wp[0].data_ptr() + 2 * w_row_off * ktot
-            a.w_lo = wp[1].data_ptr() + 2 * w_row_off * ktot
             same_w = getattr(srcs[0], "_same_w", 0)  # (a hint: lets the kernel compute the source-row table; WDIFF_CONV3=1 also
             #                                           selects the row-shared-taps kernel for it)
             if (same_w and srcs[0].ntaps == 9 and srcs[0].c % 64 == 0 and act == N.ACT_NONE and tile == 0 and
                     (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather and srcs[1].c % 64 == 0))):
                 a.w_layout, a.slab_rows = 2, same_w  # 3x3 same-convolution: the taps of a kernel row share their A tile
-        a.m, a.n, a.ktot, a.hw_out = m, nrows, ktot, hw_out
-        a.bias = _ptr(bias)
-        a.rowvec, a.rowvec_ld = rowvec, rowvec_ld
-        a.resid, a.resid_ld, a.resid_rows = resid, resid_ld, resid_rows
-        a.act = act
-        a.out_f32, a.out_ld = _ptr(out_f32), out_ld
-        if out_pl is not None:
-            a.out_hi, a.out_lo, a.out_pl_ld = out_pl[0].data_ptr(), out_pl[1].data_ptr(), out_pl.shape[2]
-        a.tile = tile
-        if ln is not None:  # out_pl receives LayerNorm(result) * gamma + beta (name of the norm's packed vectors)
-            assert wdirect and nrows == 320 and out_pl is not None, what
-            a.ln_gamma, a.ln_beta, a.ln_eps = self._w[ln + ".g"].data_ptr(), self._w[ln + ".b"].data_ptr(), 1e-5
+        a._ln_pl = None
+        if ln is not None and self.fuse_ln and not self.use_slab:  # (WDIFF_SLAB=1 runs keep the LayerNorm launches)
+            pl = torch.zeros((2, m, nrows), dtype=torch.bfloat16, device=self.device)
+            if self._legal(a, out_hi=pl[0].data_ptr(), out_lo=pl[1].data_ptr(), out_pl_ld=nrows, ln_gamma=self._w[ln + ".g"].data_ptr(),
+                           ln_beta=self._w[ln + ".b"].data_ptr(), ln_eps=1e-5):
+                self._cur_plan.keep.append(pl)
+                a._ln_pl = pl
         stats = None
-        if want_stats and self.fuse_stats and nrows % 32 == 0 and (hw_out % 128 == 0 or hw_out == 64):
+        # (the consumer's GroupNorm has 32 groups; the statistics layout is kept to sample sizes that are a multiple of the
+        # 128-row panel or exactly 64 rows, and off the experimental slab kernel)
+        if want_stats and self.fuse_stats and nrows % 32 == 0 and (hw_out % 128 == 0 or hw_out == 64) and not span:
             cpg = nrows // 32
-            bn = (tile % 1000) if tile else (160 if nrows % 160 == 0 else 64)
-            if bn % cpg == 0 and (tile == 0 or tile // 1000 == 128 or wdirect or smallmap) and not span:
-                nchunk = max(1, hw_out // (64 if (wdirect or smallmap) else 128))  # (the statistics are kept per row panel of the tile)
+            r = self._resolved(a, stat_part=a.ws, stat_cpg=cpg)  # (a placeholder for the partials: the count depends on the tile)
+            if r is not None:
+                nchunk = max(1, hw_out // (r.tile // 1000))  # (the statistics are kept per row panel of the tile)
                 part = torch.zeros((m // hw_out, nchunk, 32, 2), dtype=torch.float64, device=self.device)
                 self._cur_plan.keep.append(part)
                 a.stat_part, a.stat_cpg = part.data_ptr(), cpg
                 stats = (part, nchunk, cpg)
         a._stats = stats
-        if self._ws is None:
-            self._ws = torch.empty(128 * 128 * 160 * 8, dtype=torch.float32, device=self.device)  # 84 MB split-K scratch
-        a.ksplit, a.ws, a.ws_floats = 0, self._ws.data_ptr(), self._ws.numel()
-        self._give_tickets(a, m, nrows)
         self._cur_plan.keep.append(a)
         ops.append((self.lib.wd_gemm, (C.byref(a),), what))
         return a
+
+    def _resolved(self, a, **fields) -> Optional[N.WdGemmArgs]:
+        """``a`` with ``fields`` set (on a copy) as wd_gemm would launch it, or None where wd_gemm refuses it (wd_gemm_check)."""
+        b = N.WdGemmArgs.from_buffer_copy(a)
+        for k, v in fields.items():
+            setattr(b, k, v)
+        out = N.WdGemmArgs()
+        return out if self.lib.wd_gemm_check(C.byref(b), C.byref(out)) == N.WD_OK else None
+
+    def _legal(self, a, apply=True, **fields) -> bool:
+        """Does wd_gemm take ``a`` with ``fields`` set?  If it does (and ``apply``), they are set on ``a`` itself."""
+        if self._resolved(a, **fields) is None:
+            return False
+        if apply:
+            for k, v in fields.items():
+                setattr(a, k, v)
+        return True
+
+    def _set_a32(self, a, x32: "Act", gname, eps, silu):
+        part, nchunk, pc = x32.stats
+        a.a32, a.a32_ld, a.a32_part = x32.t.data_ptr(), x32.c, part.data_ptr()
+        a.a32_nchunk, a.a32_pcpg, a.a32_cpg = nchunk, pc, x32.c // 32
+        a.a32_gamma, a.a32_beta = self._w[gname + ".g"].data_ptr(), self._w[gname + ".b"].data_ptr()
+        a.a32_eps, a.a32_silu = float(eps), int(silu)
+
+    def _wdirect_ok(self, srcs, m, n, hw_out, a32=None, **fields) -> bool:
+        """Would wd_gemm run a GEMM over ``srcs`` into m x n as the 64 x 320 weights-to-registers kernel (with a32 / ``fields``)?
+        Asked before the GEMM is planned; weights and output are placeholders (wd_gemm_check reads no memory)."""
+        a = N.WdGemmArgs()
+        for i, s in enumerate(srcs):
+            a.src[i] = s
+        a.nsrc, a.npass, a.m, a.n, a.ktot, a.hw_out = len(srcs), self.npass, m, n, sum(s.ntaps * s.c for s in srcs), hw_out
+        a.w_layout, a.tile = 3, 64320
+        a.w_hi = a.w_lo = a.out_f32 = 16
+        if a32 is not None:
+            self._set_a32(a, *a32)
+        return self._legal(a, apply=False, **fields)
 
     def _give_tickets(self, a, m, n):
         """Arrival counters for the in-launch split-K combine of one wd_gemm launch: a range of its own inside a zeroed
@@ -795,16 +827,9 @@ class UNetEngine:
                 ops.append((self.lib.wd_gn_fold_chunks, (part.data_ptr(), B, nchunk, ngs, folded.data_ptr()), what + ":fold chunks"))
                 part, nchunk = folded, 1
                 s.stats = (part, nchunk, pc)
-            if not has_perm and self._gn_in_combine(s, raw, hw, cpg, pc, nchunk, coff):
-                # the producer is a K-cut GEMM whose combine tiles (64 rows x 40 columns) hold whole (sample, group) blocks: its
-                # combine launch normalises the rows it has just summed and writes these planes (wd_gemm_args.gn_*)
-                pr = s.prod
-                pr.gn_gamma, pr.gn_beta = gam.data_ptr() + 4 * coff, bet.data_ptr() + 4 * coff
-                pr.gn_eps, pr.gn_silu, pr.gn_cpg = float(eps), int(silu), cpg
-                pr.out_hi = pl[0].data_ptr() + 2 * coff
-                pr.out_lo = (pl[1].data_ptr() + 2 * coff) if self.npass == 3 else None
-                pr.out_pl_ld = ctot
-            else:
+            # (_gn_in_combine: the producer is a K-cut GEMM whose combine tiles (64 rows x 40 columns) hold whole (sample, group)
+            # blocks - its combine launch normalises the rows it has just summed and writes these planes)
+            if has_perm or not self._gn_in_combine(s, raw, gam, bet, eps, silu, cpg, pl, coff):
                 todo.append((s, part, nchunk, pc, coff))
             coff += s.c
         lo = pl[1].data_ptr() if self.npass == 3 else None
@@ -825,19 +850,20 @@ class UNetEngine:
                              int(silu), pl[0].data_ptr(), lo, ctot, c0, rhi, rlo), what + ":apply"))
         return pl, raw
 
-    def _gn_in_consumer(self, P, ops, what, srcs: List[Act], want_raw, M, hw, ncols, taps=1) -> bool:
-        """Can the convolution that consumes this GroupNorm apply it itself (wd_gemm_args.a32*)?  One fp32 source with known (or
-        computable) statistics, a consumer that takes the 64 x 320 weights-to-registers kernel, tiles inside one sample.
+    def _gn_in_consumer(self, P, ops, what, srcs: List[Act], want_raw, M, hw, ncols, taps=1, gather=None) -> bool:
+        """Can the convolution that consumes this GroupNorm (``what``: also the norm's name) apply it itself (wd_gemm_args.a32*)?
+        One fp32 source with known (or computable) statistics, a consumer that takes the 64 x 320 weights-to-registers kernel
+        (``_wdirect_ok``: wd_gemm_check on its args with the a32 fields).
         Measured at B = 64: a 1x1 consumer (proj_in: five stages, no SiLU) loses nothing and saves the wd_gn_apply launch; a 3x3
         consumer normalises and activates every element nine times (once per tap) and runs ~30 us longer per launch than the
         10 us launch it saves (step 2.095 -> 2.137 ms with all of them on) - WDIFF_FUSE_GN_IN=2 switches those on anyway."""
-        if not (self.fuse_gn_in and self.use_wdirect and self.npass == 3 and len(srcs) == 1 and not want_raw and not self.use_conv3):
+        if not (self.fuse_gn_in and self.use_wdirect and len(srcs) == 1 and not want_raw and not self.use_conv3):
             return False
         if taps > 1 and self.fuse_gn_in < 2:
             return False
-        s = srcs[0]
-        if s.c % 64 or s.c > 1024 or hw % 64 or ncols % 320 or ((M + 63) // 64) * (ncols // 320) < 256:
+        if not wdirect_fills_chip(M, ncols):
             return False
+        s = srcs[0]
         if s.stats is None:  # no producer-side statistics: one pass over the tensor
             nchunk = self.lib.wd_gn_nchunk(hw)
             pc = s.c // 32
@@ -845,13 +871,7 @@ class UNetEngine:
             P.keep.append(part)
             ops.append((self.lib.wd_gn_stats, (s.t.data_ptr(), s.c, self._B, hw, s.c, pc, part.data_ptr()), what + ":stats"))
             s.stats = (part, nchunk, pc)
-        return (s.c // 32) % s.stats[2] == 0
-
-    def _ln_in_producer(self, M, ncols) -> bool:
-        """Does a 1x1 / linear GEMM with these output dimensions run as 64 x 320 weights-to-registers tiles holding whole rows
-        (so that its epilogue can emit the next LayerNorm, wd_gemm_args.ln_*)?"""
-        return (self.fuse_ln and self.use_wdirect and not self.use_slab and not self.use_conv3 and ncols == 320 and
-                (M + 63) // 64 >= 256)
+        return self._wdirect_ok([self._src32(s, taps, gather, hw)], M, ncols, hw, a32=(s, what, 0.0, False))
 
     def _src32(self, x: Act, ntaps=1, gather=None, hw_src=0) -> N.WdSrc:
         """src[0] of a GEMM that reads the fp32 map itself (a32): channel count, taps and gather table only."""
@@ -862,23 +882,18 @@ class UNetEngine:
         s.ld, s.c, s.ntaps, s.hw_src = x.c, x.c, ntaps, hw_src
         return s
 
-    def _gn_in_combine(self, s: Act, raw, hw, cpg, pc, nchunk, coff) -> bool:
-        """Can the GEMM that produced ``s`` apply this GroupNorm in its split-K combine launch (wd_gemm_args.gn_*)?  The
-        conditions of include/wdiff_hip.h, checked here so that the plan never asks for what wd_gemm would refuse."""
+    def _gn_in_combine(self, s: Act, raw, gam, bet, eps, silu, cpg, pl, coff) -> bool:
+        """Let the GEMM that produced ``s`` apply this GroupNorm as it combines its K slices (or in its own epilogue where it holds
+        all of K) and write columns coff.. of the planes ``pl`` (wd_gemm_args.gn_*), where wd_gemm_check accepts that.  The
+        producer must write exactly this tensor, with no planes of its own yet."""
         pr = s.prod
         if pr is None or not isinstance(pr, N.WdGemmArgs) or not self.fuse_gn or raw is not None or self.use_conv3:
             return False
-        if pr.out_f32 != s.t.data_ptr() or pr.out_hi or pr.gn_gamma or pr.n != s.c or not pr.stat_part or not pr.ws:
+        if pr.out_f32 != s.t.data_ptr() or pr.out_hi or pr.gn_gamma or pr.n != s.c:
             return False
-        if hw != 64 or pr.hw_out != 64 or pr.m % 64 or s.c % 160 or 40 % cpg or cpg % pc or nchunk != 1 or coff % 4:
-            return False
-        if pr.act != N.ACT_NONE or pr.resid_rows or pr.ksplit != 0 or pr.w_layout == 1 or pr.dbg:
-            return False
-        if pr.tile == 64080:  # all of K in the producer's workgroups (wd_gemmq_kernel): the norm runs in its own epilogue
-            return pr.w_layout == 3
-        if pr.tile != (64320 if pr.w_layout == 3 else 0):
-            return False
-        return self.lib.wd_gemm_auto_ksplit(pr.m, pr.n, pr.ktot, pr.ws_floats) > 1
+        return self._legal(pr, gn_gamma=gam.data_ptr() + 4 * coff, gn_beta=bet.data_ptr() + 4 * coff, gn_eps=float(eps),
+                           gn_silu=int(silu), gn_cpg=cpg, out_hi=pl[0].data_ptr() + 2 * coff,
+                           out_lo=(pl[1].data_ptr() + 2 * coff) if self.npass == 3 else None, out_pl_ld=pl.shape[2])
 
     def _ln(self, P, ops, what, x: torch.Tensor, rows, c, name):
         pl = self._planes(P, rows, c)
@@ -898,7 +913,7 @@ class UNetEngine:
         tab, _, _ = self._table(h, w, "same")
         need_raw = cin != cout
         h1 = self._f32(P, M, cout)
-        if self._gn_in_consumer(P, ops, name + ".gn1", srcs, need_raw, M, hw, cout, taps=9):
+        if self._gn_in_consumer(P, ops, name + ".gn1", srcs, need_raw, M, hw, cout, taps=9, gather=tab):
             s1, in1 = self._src32(srcs[0], 9, tab, hw), (srcs[0], name + ".gn1", 1e-5, True)
             raw = None
         else:
@@ -908,7 +923,7 @@ class UNetEngine:
                         bias=self._w[name + ".c1.b"], rowvec=self._film.data_ptr() + 4 * self.film_off[name],
                         rowvec_ld=self.film_total, out_f32=h1, out_ld=cout, want_stats=True, a32=in1)
         h1a = Act(h1, cout, h, w, g1._stats, prod=g1)
-        if self._gn_in_consumer(P, ops, name + ".gn2", [h1a], False, M, hw, cout, taps=9):
+        if self._gn_in_consumer(P, ops, name + ".gn2", [h1a], False, M, hw, cout, taps=9, gather=tab):
             s2, in2 = self._src32(h1a, 9, tab, hw), (h1a, name + ".gn2", 1e-5, True)
         else:
             a2, _ = self._gn(P, ops, name + ".gn2", [h1a], name + ".gn2", 1e-5, True)
@@ -925,9 +940,10 @@ class UNetEngine:
         return Act(out, cout, h, w, g2._stats, prod=g2)
 
     def _up_phases_ok(self, mod) -> bool:
-        """Shapes the phase form of an Upsample covers (the 64 x 320 weights-to-registers kernel with weight groups)."""
+        """Is the phase form of an Upsample switched on (the 64 x 320 weights-to-registers kernel with weight groups; whether it
+        takes a given shape, ``_resample`` asks wd_gemm_check)?"""
         return (getattr(self, "use_up_phases", False) and self.use_wdirect and self.fuse_gn2 and self.npass == 3 and not self.use_slab and
-                not self.use_conv3 and mod.cin % 64 == 0 and mod.cout % 320 == 0)
+                not self.use_conv3)
 
     def _resample(self, P, name, mod, x: Act, mode: str, tile: int = 0) -> Act:
         ops = P.step
@@ -946,8 +962,8 @@ class UNetEngine:
                                             pl[1].data_ptr() if self.npass == 3 else None, x.c), name + ":split"))
         out = self._f32(P, B * ho * wo, mod.cout)
         hw = x.h * x.w
-        if (mode == "up" and tile == 0 and (name + ".wph0") in self._w and self._up_phases_ok(mod) and hw % 64 == 0 and
-                (B * 4 * hw // 64) * (mod.cout // 320) >= 256):
+        src4 = None
+        if mode == "up" and tile == 0 and (name + ".wph0") in self._w and self._up_phases_ok(mod) and wdirect_fills_chip(B * 4 * hw, mod.cout):
             # four 2x2 convolutions of the source map, one per output phase: 4 taps instead of 9, the weight image picked per tile;
             # the rows of a sample come out phase-major (Act.perm: the decoder block's GroupNorm reads them in raster order)
             key = (x.h, x.w, "up4")
@@ -957,6 +973,11 @@ class UNetEngine:
                 self._tabs[key] = (dt, dp)
                 self._tab_np[dt.data_ptr()] = t4
             tab4, perm = self._tabs[key]
+            src4 = self._src(pl, x.c, 4, tab4, hw)
+            groups = (4, mod.cout * 4 * x.c)
+            if not self._wdirect_ok([src4], B * 4 * hw, mod.cout, 4 * hw, w_ngroups=groups[0], w_group_stride=groups[1]):
+                src4 = None
+        if src4 is not None:
             if (name + ".wph0") not in self._wf:   # the four fragment-major images side by side (one base + a stride for the kernel)
                 grp = torch.empty((2, 4, mod.cout, 4 * x.c), dtype=torch.bfloat16, device=self.device)
                 st = torch.cuda.current_stream(self.device).cuda_stream
@@ -964,10 +985,8 @@ class UNetEngine:
                     self._wf[f"{name}.wph{ph}"] = grp[:, ph]
                     self._pack_wf(f"{name}.wph{ph}", grp[:, ph], st)
                 self._pack = None
-            gg = self._gemm(ops, name + ".conv (4 phases)", [self._src(pl, x.c, 4, tab4, hw)], name + ".wph0", B * 4 * hw, 4 * hw,
-                            bias=self._w[name + ".b"], out_f32=out, out_ld=mod.cout, want_stats=True)
-            assert gg.tile == 64320 and gg.w_layout == 3, name
-            gg.w_ngroups, gg.w_group_stride = 4, mod.cout * 4 * x.c
+            gg = self._gemm(ops, name + ".conv (4 phases)", [src4], name + ".wph0", B * 4 * hw, 4 * hw,
+                            bias=self._w[name + ".b"], out_f32=out, out_ld=mod.cout, want_stats=True, w_groups=groups)
             return Act(out, mod.cout, ho, wo, gg._stats, prod=None, perm=perm)
         gg = self._gemm(ops, name + ".conv", [self._src(pl, x.c, 9, tab, x.h * x.w)], name + ".w", B * ho * wo, ho * wo,
                         bias=self._w[name + ".b"], out_f32=out, out_ld=mod.cout, want_stats=True, tile=tile)
@@ -999,17 +1018,15 @@ class UNetEngine:
             return self._transformer_fused(P, name, mod, x)
         tok = self._f32(P, M, inner)
         # (PHOSC variant: the first block's norm1 planes come out of proj_in's epilogue where its tiles hold whole rows)
-        n1_pre = None
-        ln1 = None
-        if self.variant == "phosc" and self._ln_in_producer(M, inner):
-            n1_pre, ln1 = self._planes(P, M, inner), f"{name}.tb0.norm1"
+        ln1 = f"{name}.tb0.norm1" if self.variant == "phosc" else None
         if self._gn_in_consumer(P, ops, name + ".gn", [x], False, M, hw, inner):
-            self._gemm(ops, name + ".proj_in", [self._src32(x, hw_src=hw)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
-                       out_f32=tok, out_ld=inner, a32=(x, name + ".gn", 1e-6, False), out_pl=n1_pre, ln=ln1)
+            g_in = self._gemm(ops, name + ".proj_in", [self._src32(x, hw_src=hw)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
+                              out_f32=tok, out_ld=inner, a32=(x, name + ".gn", 1e-6, False), ln=ln1)
         else:
             g, _ = self._gn(P, ops, name + ".gn", [x], name + ".gn", 1e-6, False)
-            self._gemm(ops, name + ".proj_in", [self._src(g, c)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
-                       out_f32=tok, out_ld=inner, out_pl=n1_pre, ln=ln1)
+            g_in = self._gemm(ops, name + ".proj_in", [self._src(g, c)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
+                              out_f32=tok, out_ld=inner, ln=ln1)
+        n1_pre = g_in._ln_pl
         xpl = None
         fuse = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))
 
@@ -1077,10 +1094,9 @@ class UNetEngine:
                 o1 = self._planes(P, M, inner)
                 self._attention(ops, p + ".a1", qkv.data_ptr(), 3 * inner, qkv.data_ptr() + 4 * inner, 3 * inner,
                                 qkv.data_ptr() + 8 * inner, 3 * inner, heads, hw, hw, d, scale, o1)
-                n2_pre = self._planes(P, M, inner) if (not fuse and self._ln_in_producer(M, inner)) else None
-                self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
-                           resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner, out_pl=n2_pre,
-                           ln=(p + ".norm2") if n2_pre is not None else None)
+                n2_pre = self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
+                                    resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner,
+                                    ln=None if fuse else p + ".norm2")._ln_pl
             elif fuse:
                 folded("a1", p, tok, tok1, "norm2")  # the base model reads norm2 for both attentions (unet.py:337-345)
             else:
@@ -1122,11 +1138,8 @@ class UNetEngine:
                 else:
                     self._attention(ops, p + ".a2", q2.data_ptr(), inner, kp, self.kv_total, vp, self.kv_total, heads, hw, L, d,
                                     scale, o2)
-                if self._ln_in_producer(M, inner):
-                    n3 = self._planes(P, M, inner)
-                self._gemm(ops, p + ".a2.out", [self._src(o2, inner)], p + ".a2.o.w", M, hw, bias=self._w[p + ".a2.o.b"],
-                           resid=tok1.data_ptr(), resid_ld=inner, out_f32=tok2, out_ld=inner, out_pl=n3,
-                           ln=(p + ".norm3") if n3 is not None else None)
+                n3 = self._gemm(ops, p + ".a2.out", [self._src(o2, inner)], p + ".a2.o.w", M, hw, bias=self._w[p + ".a2.o.b"],
+                                resid=tok1.data_ptr(), resid_ld=inner, out_f32=tok2, out_ld=inner, ln=p + ".norm3")._ln_pl
             # ---- GEGLU feed-forward
             if n3 is None:
                 n3 = self._ln(P, ops, p + ".norm3", tok2, M, inner, p + ".norm3")
