@@ -4,7 +4,7 @@ TEST INFRASTRUCTURE - not part of the product.  Only ``tests/``,
 ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 this module; the product path (``worddiffusion_amd``) never does.
 
-This is a restatement, in plain functional fp32 PyTorch on the CPU, of what the
+This is a restatement, in plain functional fp32 (or float64) PyTorch on the CPU, of what the
 reference's ``unet.UNetModel.forward`` (``unet.py:1499-1836``) and
 ``unetPhosc.UNetModelPhosc.forward`` (``unetPhosc.py:1068-1159``) compute.  It
 works directly on a reference-layout ``state_dict`` (reference key names, OIHW /
@@ -27,11 +27,12 @@ Tensor = torch.Tensor
 
 
 # ------------------------------------------------------------------------------------------- a1
-def timestep_embedding(t: Tensor, dim: int, max_period: float = 10000.0) -> Tensor:
-    """unet.py:96-116: [cos(t f_k), sin(t f_k)], f_k = exp(-ln(max_period) k / half)."""
+def timestep_embedding(t: Tensor, dim: int, max_period: float = 10000.0, dtype: torch.dtype = torch.float32) -> Tensor:
+    """unet.py:96-116: [cos(t f_k), sin(t f_k)], f_k = exp(-ln(max_period) k / half).
+    The frequencies and the arguments t f_k are fp32, as unet.py forms them; cos / sin are taken in ``dtype``."""
     half = dim // 2
     freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    args = (t[:, None].float() * freqs[None]).to(dtype)
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
@@ -69,7 +70,7 @@ def character_encoder(sd: Dict[str, Tensor], ids: Tensor, max_seq_len: int, alwa
 
 # ------------------------------------------------------------------------------------------- a4
 def group_norm(x: Tensor, w: Tensor, b: Tensor, eps: float) -> Tensor:
-    return F.group_norm(x.float(), 32, w, b, eps)
+    return F.group_norm(x.to(w.dtype), 32, w, b, eps)
 
 
 def resblock(sd: Dict[str, Tensor], p: str, x: Tensor, emb: Tensor) -> Tensor:
@@ -216,17 +217,19 @@ class UNetOracle:
     """Functional forward over a reference-layout state_dict.
 
     variant: 'base' = unet.UNetModel, 'phosc' = unetPhosc.UNetModelPhosc.
-    phosc_on: args.phosc==1 or args.phos==1 (unetPhosc.py:1120)."""
+    phosc_on: args.phosc==1 or args.phos==1 (unetPhosc.py:1120).
+    Computes in float64 when the state_dict holds float64 tensors (a high-precision reference), else in fp32."""
 
     def __init__(self, cfg: dict, sd: Dict[str, Tensor], variant: str = "base", phosc_on: bool = False):
         assert variant in ("base", "phosc")
         self.cfg = dict(cfg)
-        self.sd = {k: v.detach().float() if not v.requires_grad else v for k, v in sd.items()}
+        self.dtype = torch.float64 if any(v.dtype == torch.float64 for v in sd.values()) else torch.float32
+        self.sd = {k: v.detach().to(self.dtype) if not v.requires_grad else v for k, v in sd.items()}
         self.variant = variant
         self.phosc_on = phosc_on
         self.layout = build_layout(cfg)
         self.depth = cfg.get("transformer_depth", 1)
-        self.pe = positional_encoding(cfg.get("max_seq_len", 20), cfg["context_dim"])
+        self.pe = positional_encoding(cfg.get("max_seq_len", 20), cfg["context_dim"]).to(self.dtype)  # (an fp32 buffer in unet.py)
 
     def _run(self, layers, prefix, h, emb, context, taps):
         sd = self.sd
@@ -249,7 +252,7 @@ class UNetOracle:
     def embed(self, t: Tensor, y: Optional[Tensor]) -> Tensor:
         """unet.py:1550-1581: time MLP + label embedding."""
         sd = self.sd
-        e = timestep_embedding(t, self.cfg["model_channels"])
+        e = timestep_embedding(t, self.cfg["model_channels"], dtype=self.dtype)
         e = F.linear(e, sd["time_embed.0.weight"], sd["time_embed.0.bias"])
         e = F.linear(F.silu(e), sd["time_embed.2.weight"], sd["time_embed.2.bias"])
         if self.cfg.get("num_classes") is not None:
@@ -279,7 +282,7 @@ class UNetOracle:
         ctx = self.context(context, phosc)
         if taps is not None and ctx is not None:
             taps["context"] = ctx
-        h = x.float()
+        h = x.to(self.dtype)
         hs = []
         for i, layers in enumerate(self.layout["inputs"]):
             h = self._run(layers, f"input_blocks.{i}.", h, emb, ctx, taps)

@@ -230,9 +230,9 @@ def test_noise_images_and_ema_surface():
 
 
 def test_full_size_properties_b64():
-    """BASELINE configs[1] size (B=64, base UNet, 320 channels): the oracle would need minutes, so check
-    size-independent properties: determinism, and per-sample independence (GroupNorm/LayerNorm/attention are
-    per-sample: sample b of the batch == the same sample run alone)."""
+    """BASELINE configs[1] size (B=64, base UNet, 320 channels): determinism, per-sample independence (GroupNorm/LayerNorm/attention
+    are per-sample: sample b of the batch == the same sample run alone), and every sample against the oracle (a few seconds of
+    CPU at this size)."""
     m = build(FULL, "base", False, seed=0)
     inp = synthetic_inputs(64, seed=2)
     o1 = call(m, "base", inp["x"], inp["t"], inp["context"], inp["y"])
@@ -242,14 +242,16 @@ def test_full_size_properties_b64():
         ob = call(m, "base", inp["x"][b:b + 1], inp["t"][b:b + 1], inp["context"][b:b + 1], inp["y"][b:b + 1])
         # (B=1 and B=64 pick different tiles / k-splits: fp32 summation order differs, nothing else)
         assert max_rel(ob.cpu(), o1[b:b + 1].cpu()) < 5e-5, b
-    # ... and two of them against the oracle itself
+    # ... and all 64 against the oracle itself, sample by sample
     shapes = U.state_dict_shapes(FULL, "base")
     from worddiffusion_amd.synthetic import synthetic_tensor
     sd = {k: torch.from_numpy(synthetic_tensor(k, s, 0)) for k, s in shapes}
     orc = U.UNetOracle(FULL, sd, "base", False)
     with torch.no_grad():
-        ref = orc(inp["x"][:2], inp["t"][:2], inp["context"][:2], inp["y"][:2])
-    assert max_rel(o1[:2].cpu(), ref) < 1e-4
+        ref = orc(inp["x"], inp["t"], inp["context"], inp["y"])
+    out = o1.cpu()
+    errs = [max_rel(out[b], ref[b]) for b in range(64)]
+    assert max(errs) < 1e-4, [(b, e) for b, e in enumerate(errs) if e >= 1e-4]
 
 
 def test_upsample_as_four_phases_equals_the_nine_tap_form():
@@ -270,7 +272,7 @@ def test_upsample_as_four_phases_equals_the_nine_tap_form():
 def test_full_size_properties_b64_phosc():
     """BASELINE configs[4]'s one-GPU share at the benchmark batch: UNetModelPhosc (args.phosc = 1), 320 channels, 10 word ids +
     the 769-int PHOSC vector (779-key cross-attention, 256-key self-attention), B = 64 - determinism, per-sample independence
-    (sample b of the batch == the same sample run alone) and two samples against the oracle."""
+    (sample b of the batch == the same sample run alone) and every sample against the oracle."""
     m = build(FULL, "phosc", True, seed=0)
     inp = synthetic_inputs(64, seed=4, phosc_len=769)
     o1 = call(m, "phosc", inp["x"], inp["t"], inp["context"], inp["y"], inp["phosc"])
@@ -284,8 +286,10 @@ def test_full_size_properties_b64_phosc():
     sd = {k: torch.from_numpy(synthetic_tensor(k, s, 0)) for k, s in shapes}
     orc = U.UNetOracle(FULL, sd, "phosc", True)
     with torch.no_grad():
-        ref = orc(inp["x"][:2], inp["t"][:2], inp["context"][:2], inp["y"][:2], inp["phosc"][:2])
-    assert max_rel(o1[:2].cpu(), ref) < 1e-4
+        ref = orc(inp["x"], inp["t"], inp["context"], inp["y"], inp["phosc"])
+    out = o1.cpu()
+    errs = [max_rel(out[b], ref[b]) for b in range(64)]
+    assert max(errs) < 1e-4, [(b, e) for b, e in enumerate(errs) if e >= 1e-4]
 
 
 def test_optimizer_side_of_train_step(golden_dir):
