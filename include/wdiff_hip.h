@@ -354,6 +354,18 @@ int wd_emb_combine(const float* time, const float* label, const int64_t* y, int 
 int wd_select_rows(const float* table, const int32_t* t_dev, int batch, int64_t row_floats, int chunk, float* out,
                    void* stream);
 
+/* Writer-style interpolation (unet.py:1558-1573): the label row of a sample is the blend (1 - m_b) * label[s1] + m_b * label[s2]
+ * of two writers, evaluated in fp32 as two products and one sum.  pairs is int32 (s1, s2) per row, mix is fp32 [B]; ids are
+ * clamped to [0, num_classes) - the host range-checks them.
+ * wd_emb_combine_mix: wd_emb_combine with that blend as the label term; pairs is [T][B][2] (row t*B + b).  With m_b = 0 / 1 the
+ * planes equal wd_emb_combine's for y_b = s1 / s2 bit for bit.
+ * wd_label_mix: the blended rows themselves, out fp32 [B][ted], pairs [B][2] (the residual rows of the time_embed.2 GEMM on
+ * the path that does not tabulate). */
+int wd_emb_combine_mix(const float* time, const float* label, const int32_t* pairs, const float* mix, int num_classes, int T, int B,
+                       int ted, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream);
+int wd_label_mix(const float* label, const int32_t* pairs, const float* mix, int num_classes, int B, int ted, float* out,
+                 void* stream);
+
 /* Two chained folded cross-attentions in one launch (attn1 then attn2 of a base-model BasicTransformerBlock, unet.py:337-345;
  * both read LayerNorm parameters of their own, here norm2 twice): out = B(A(x)) with A/B = x + bias + softmax(LN(x).Mq^T).Mo,
  * optionally followed by the next LayerNorm as operand planes.  MFMA form only (planes from wd_xattn_fold). */
@@ -384,6 +396,13 @@ int wd_tokens_to_nchw(const float* x, int ld, int batch, int c, int hw, float* o
 int wd_ddpm_step(float* x, const float* eps, int batch, int n_per_sample, const float* ca, const float* cb,
                  const float* cs, const int32_t* t_dev, const float* noise, uint64_t seed, uint64_t sample_offset,
                  void* stream);
+
+/* wd_ddpm_step on the guided prediction eps = torch.lerp(second, first, scale) (train.py:228), formed as torch forms it:
+ * first - (first - second) * (1 - scale) when |scale| >= 0.5, second + scale * (first - second) otherwise.  The update and the
+ * Philox stream are wd_ddpm_step's, bit for bit.  eps_out != NULL also receives eps. */
+int wd_ddpm_step_cfg(float* x, const float* first, const float* second, float scale, float* eps_out, int batch, int n_per_sample,
+                     const float* ca, const float* cb, const float* cs, const int32_t* t_dev, const float* noise, uint64_t seed,
+                     uint64_t sample_offset, void* stream);
 
 /* *t_dev += delta; t64[b] = *t_dev for b < batch (the int64 timesteps vector the UNet takes, train.py:222). */
 int wd_advance_timestep(int32_t* t_dev, int delta, int64_t* t64, int batch, void* stream);

@@ -231,6 +231,93 @@ __global__ void select_rows_kernel(const float* __restrict__ table, const int32_
         reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(table)[base + i];
 }
 
+// ---- writer-style interpolation (unet.py:1558-1573) ----------------------------------------------------------------------
+// y = (1 - m) * label[s1] + m * label[s2] with the reference's fp32 op order: two products, one sum (no contraction in this
+// file).  Ids are range-checked on the host and clamped here, as in emb_combine_kernel.
+__device__ __forceinline__ float4 label_mix4(const float* __restrict__ label, const int32_t* __restrict__ pair, int num_classes,
+                                             int ted, int cx, float m) {
+    int s1 = pair[0], s2 = pair[1];
+    s1 = s1 < 0 ? 0 : (s1 >= num_classes ? num_classes - 1 : s1);
+    s2 = s2 < 0 ? 0 : (s2 >= num_classes ? num_classes - 1 : s2);
+    const float4 a = *reinterpret_cast<const float4*>(label + (long)s1 * ted + cx);
+    const float4 b = *reinterpret_cast<const float4*>(label + (long)s2 * ted + cx);
+    const float om = 1.0f - m;
+    return make_float4(om * a.x + m * b.x, om * a.y + m * b.y, om * a.z + m * b.z, om * a.w + m * b.w);
+}
+
+// emb_combine_kernel with the label row replaced by the blend of the pair of (t, b): row t*B + b
+__global__ void emb_combine_mix_kernel(const float* __restrict__ time, const float* __restrict__ label,
+                                       const int32_t* __restrict__ pairs, const float* __restrict__ mix, int num_classes, int T, int B,
+                                       int ted, wd_bf16* __restrict__ out_hi, wd_bf16* __restrict__ out_lo, int out_ld) {
+    const int t4 = ted >> 2;
+    const long total = (long)T * B * t4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / t4;
+        const int cx = (int)(i - row * t4) * 4;
+        const int t = (int)(row / B), b = (int)(row - (long)t * B);
+        float4 v = *reinterpret_cast<const float4*>(time + (long)t * ted + cx);
+        const float4 l = label_mix4(label, pairs + 2 * row, num_classes, ted, cx, mix[b]);
+        v.x += l.x; v.y += l.y; v.z += l.z; v.w += l.w;
+        v.x = wd_silu(v.x); v.y = wd_silu(v.y); v.z = wd_silu(v.z); v.w = wd_silu(v.w);
+        uint2 hi, lo;
+        wd_split4(v, hi, lo);
+        *reinterpret_cast<uint2*>(out_hi + row * out_ld + cx) = hi;
+        if (out_lo) *reinterpret_cast<uint2*>(out_lo + row * out_ld + cx) = lo;
+    }
+}
+
+__global__ void label_mix_kernel(const float* __restrict__ label, const int32_t* __restrict__ pairs, const float* __restrict__ mix,
+                                 int num_classes, int B, int ted, float* __restrict__ out) {
+    const int t4 = ted >> 2;
+    const long total = (long)B * t4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / t4), cx = (int)(i - (long)b * t4) * 4;
+        *reinterpret_cast<float4*>(out + (long)b * ted + cx) = label_mix4(label, pairs + 2 * b, num_classes, ted, cx, mix[b]);
+    }
+}
+
+// torch.lerp(second, first, s) as ATen evaluates it: the weight >= 0.5 form is first - (first - second) * (1 - s)
+__device__ __forceinline__ float lerp_cfg(float first, float second, float s, float oms, bool high) {
+    const float d = first - second;
+    return high ? first - d * oms : second + s * d;
+}
+
+// ddpm_step_kernel on eps = lerp(second, first, scale)
+__global__ void ddpm_step_cfg_kernel(float* __restrict__ x, const float* __restrict__ first, const float* __restrict__ second,
+                                     float scale, float* __restrict__ eps_out, int batch, int n4, const float* __restrict__ ca,
+                                     const float* __restrict__ cb, const float* __restrict__ cs, const int32_t* __restrict__ t_dev,
+                                     const float* __restrict__ noise, uint64_t seed, uint64_t sample_offset) {
+    const int t = *t_dev;
+    const float a = ca[t], bb = cb[t], s = cs[t];
+    const float oms = 1.0f - scale;
+    const bool high = fabsf(scale) >= 0.5f;
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / n4);
+        const uint32_t e4 = (uint32_t)(i - (long)b * n4);
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t > 1) {
+            if (noise) z = reinterpret_cast<const float4*>(noise)[i];
+            else z = philox_normal4(seed, sample_offset + (uint64_t)b, (uint32_t)t, e4);
+        }
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 fv = reinterpret_cast<const float4*>(first)[i];
+        const float4 sv = reinterpret_cast<const float4*>(second)[i];
+        float4 ev;
+        ev.x = lerp_cfg(fv.x, sv.x, scale, oms, high);
+        ev.y = lerp_cfg(fv.y, sv.y, scale, oms, high);
+        ev.z = lerp_cfg(fv.z, sv.z, scale, oms, high);
+        ev.w = lerp_cfg(fv.w, sv.w, scale, oms, high);
+        if (eps_out) reinterpret_cast<float4*>(eps_out)[i] = ev;
+        float4 o;
+        o.x = a * (xv.x - bb * ev.x) + s * z.x;
+        o.y = a * (xv.y - bb * ev.y) + s * z.y;
+        o.z = a * (xv.z - bb * ev.z) + s * z.z;
+        o.w = a * (xv.w - bb * ev.w) + s * z.w;
+        reinterpret_cast<float4*>(x)[i] = o;
+    }
+}
+
 }  // namespace
 
 extern "C" int wd_timestep_embedding(const int64_t* t, int batch, const float* freqs, int half, wd_bf16* out_hi,
@@ -361,5 +448,39 @@ extern "C" int wd_select_rows(const float* table, const int32_t* t_dev, int batc
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(select_rows_kernel, dim3(grid_for((long)batch * (row_floats / 4))), dim3(256), 0, st, table, t_dev, batch,
                        (long)(row_floats / 4), chunk, out);
+    return wd_check_launch();
+}
+
+extern "C" int wd_emb_combine_mix(const float* time, const float* label, const int32_t* pairs, const float* mix, int num_classes,
+                                  int T, int B, int ted, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream) {
+    if (!time || !label || !pairs || !mix || !out_hi || num_classes <= 0 || T <= 0 || B <= 0 || ted <= 0 || ted % 4 || out_ld % 4 ||
+        out_ld < ted)
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(emb_combine_mix_kernel, dim3(grid_for((long)T * B * (ted / 4))), dim3(256), 0, st, time, label, pairs, mix,
+                       num_classes, T, B, ted, out_hi, out_lo, out_ld);
+    return wd_check_launch();
+}
+
+extern "C" int wd_label_mix(const float* label, const int32_t* pairs, const float* mix, int num_classes, int B, int ted, float* out,
+                            void* stream) {
+    if (!label || !pairs || !mix || !out || num_classes <= 0 || B <= 0 || ted <= 0 || ted % 4) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(label_mix_kernel, dim3(grid_for((long)B * (ted / 4))), dim3(256), 0, st, label, pairs, mix, num_classes, B, ted,
+                       out);
+    return wd_check_launch();
+}
+
+extern "C" int wd_ddpm_step_cfg(float* x, const float* first, const float* second, float scale, float* eps_out, int batch,
+                                int n_per_sample, const float* ca, const float* cb, const float* cs, const int32_t* t_dev,
+                                const float* noise, uint64_t seed, uint64_t sample_offset, void* stream) {
+    if (!x || !first || !second || !ca || !cb || !cs || !t_dev || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4)
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(ddpm_step_cfg_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, first, second,
+                       scale, eps_out, batch, n_per_sample / 4, ca, cb, cs, t_dev, noise, seed, sample_offset);
     return wd_check_launch();
 }

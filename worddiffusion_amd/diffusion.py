@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import random
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -56,8 +57,29 @@ def label_padding_underscore(labels: str, num_tokens: int = NUM_TOKENS, max_len:
     return _pad_ids(labels.replace(" ", "_"), LETTER2INDEX_UNDERSCORE, num_tokens, max_len)
 
 
+STYLE_ID_MAX = 338  # unet.py:1561-1564 / unetPhosc.py:1096-1099 hard-code randint(0, 338), whatever num_classes is
+
+
+def draw_style_pairs(n: int, rng=random):
+    """``n`` writer pairs drawn the way one reference forward draws its pair (unet.py:1561-1564): ``s1 = randint(0, 338)``, then
+    ``s2`` likewise, redrawn while equal to ``s1`` - from Python's global ``random`` unless ``rng`` is given.  Drawing the pairs
+    of a whole sampling call up front, in loop order, leaves the generator in the state the reference's loop leaves it in."""
+    out = []
+    for _ in range(n):
+        s1 = rng.randint(0, STYLE_ID_MAX)
+        s2 = rng.randint(0, STYLE_ID_MAX)
+        while s1 == s2:
+            s2 = rng.randint(0, STYLE_ID_MAX)
+        out.append((s1, s2))
+    return out
+
+
 def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _dptr(t):
+    return None if t is None else t.data_ptr()
 
 
 class EMA:
@@ -151,16 +173,27 @@ class Diffusion:
 
     # --------------------------------------------------------------------------------------------------
     def _denoise(self, model, n, text_features, labels, phosc, device, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, calls_model=None, deterministic=False):
+                 sample_offset=0, record=None, use_graph=True, calls_model=None, deterministic=False, mix=None,
+                 record_pred=None):
+        """mix = (pairs int32 [nf, T, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
+        step, forward f of timestep t reading pairs[f, t]; nf = 2 ends the step with the guided update (``wd_ddpm_step_cfg``).
+        record_pred: a list that receives, per model-calling step, the predictions of its forwards (and, for nf = 2, the guided
+        one) - eager launches only, like ``record``."""
         lib = N.lib()
         eng = model.engine
+        nf = 0 if mix is None else int(mix[0].shape[0])
+        if nf:
+            eng.check_pairs(mix[0])  # first: nothing is launched for an id that does not fit the table
+            labels = None  # unused in this mode (unet.py:1558-1573)
         eng.refresh_weights()
-        eng.check_ids(text_features, labels, phosc)  # host tensors here: no device sync
+        eng.check_ids(text_features, labels, phosc, need_y=not nf)  # host tensors here: no device sync
         h, w = self.img_size[0] // 8, self.img_size[1] // 8
         ctx_len = text_features.shape[1]
         phosc_len = 0 if phosc is None else phosc.shape[1]
         T = self.noise_steps
-        P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=T if self.tabulate_film else 0)
+        # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
+        P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=T if (self.tabulate_film or nf) else 0, mix=nf)
+        fps = nf or self.forwards_per_step
         ca, cb, cs = self._step_tables(device)
         if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
             cs = torch.zeros_like(cs)
@@ -178,6 +211,9 @@ class Diffusion:
                 N.check(lib.wd_randn(P.x_in.data_ptr(), n, npix, seed, sample_offset, 0, st), "wd_randn")
             eng.load_inputs(P, None, None, text_features.to(device), labels.to(device) if labels is not None else None,
                             phosc.to(device) if phosc is not None else None, check=False)
+            if nf:
+                eng.load_mix(P, mix[0].to(device), mix[1].to(device), check=False)
+            eps_g = torch.empty_like(P.out) if (nf == 2 and record_pred is not None) else None
             t_dev = P.t_dev
             t_dev.fill_(T - 1)
             P.t_in.fill_(T - 1)
@@ -188,11 +224,18 @@ class Diffusion:
 
             def one_step(stream, forward=True):
                 if forward:
-                    for _ in range(self.forwards_per_step):
+                    for _ in range(1 if nf else fps):
                         P.run_step(stream)
-                N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
-                                         cs.data_ptr(), t_dev.data_ptr(), zbuf.data_ptr() if zbuf is not None else None,
-                                         seed, sample_offset, stream), "wd_ddpm_step")
+                if nf == 2:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
+                    if forward:
+                        P.run_step1(stream)
+                    N.check(lib.wd_ddpm_step_cfg(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr(), float(mix[2]),
+                                                 _dptr(eps_g), n, npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
+                                                 t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddpm_step_cfg")
+                else:
+                    N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
+                                             cs.data_ptr(), t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream),
+                            "wd_ddpm_step")
                 N.check(lib.wd_advance_timestep(t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream),
                         "wd_advance_timestep")
 
@@ -207,7 +250,7 @@ class Diffusion:
                 return g
 
             gexec = gskip = None
-            if use_graph and record is None:
+            if use_graph and record is None and record_pred is None:
                 gexec = capture(True)
                 if calls_model is not None:
                     gskip = capture(False)  # steps that reuse the previous predicted noise: update only
@@ -227,6 +270,8 @@ class Diffusion:
                     N.check(lib.wd_graph_launch(gexec if fwd else gskip, st), "wd_graph_launch")
                 else:
                     one_step(st, fwd)
+                if record_pred is not None and fwd:
+                    record_pred.append((P.out.clone(),) if nf != 2 else (P.out.clone(), P.out1.clone(), eps_g.clone()))
             x = P.x_in.clone()
         torch.cuda.current_stream(device).wait_stream(side)
         if gexec is not None:
@@ -234,9 +279,41 @@ class Diffusion:
             lib.wd_graph_destroy(gexec)
             if gskip is not None:
                 lib.wd_graph_destroy(gskip)
-        self.last_stats = dict(steps=T - 1, forwards_per_step=self.forwards_per_step, graph=gexec is not None,
-                               seed=seed, sample_offset=sample_offset, model_calls=ncalls)
+        self.last_stats = dict(steps=T - 1, forwards_per_step=fps, graph=gexec is not None,
+                               seed=seed, sample_offset=sample_offset, model_calls=ncalls * (nf or 1))
         return x
+
+    def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, calls_model=None):
+        """The ``mix`` argument of ``_denoise`` for a sampler call, or None where the call does not interpolate.
+
+        Fixed-pair mode (``style_pairs`` given: one ``(s1, s2)`` or an int tensor [n, 2]; ``mix_rate`` a float or fp32 [n]): the
+        same pair at every step, so the two guidance forwards of train.py:223-228 are identical and one runs.
+        Reference mode (``model.interpolation`` and a ``mix_rate``): every forward of the reference's loop draws a pair of its own
+        (unet.py:1561-1564) - they are drawn here, all of them, in loop order, before anything is launched; with
+        ``cfg_scale > 0`` a step runs both forwards and the guided update.
+        Otherwise ``mix_rate`` is ignored, as the reference's forward ignores it (unet.py:1558), and ``random`` is not touched."""
+        T = self.noise_steps
+        if style_pairs is not None:
+            if mix_rate is None:
+                raise ValueError("style_pairs needs a mix_rate (a float, or one per sample)")
+            sp = torch.as_tensor(style_pairs)
+            if sp.is_floating_point() or sp.shape not in ((2,), (n, 2)):
+                raise ValueError(f"style_pairs must be (s1, s2) or an integer tensor [{n}, 2]")
+            tab = sp.to(torch.int32).cpu().reshape(-1, 2).expand(n, 2).reshape(1, 1, n, 2).expand(1, T, n, 2).contiguous()
+        elif mix_rate is not None and getattr(model, "interpolation", False):
+            steps = [i for i in reversed(range(1, T)) if calls_model is None or calls_model(i)]
+            nf = 2 if (cfg_scale > 0 and calls_model is None) else 1
+            drawn = draw_style_pairs(nf * len(steps))
+            tab = torch.zeros((nf, T, n, 2), dtype=torch.int32)
+            for k, i in enumerate(steps):
+                for f in range(nf):
+                    tab[f, i] = torch.tensor(drawn[nf * k + f], dtype=torch.int32)
+        else:
+            return None
+        m = torch.as_tensor(mix_rate, dtype=torch.float32).cpu().reshape(-1)
+        if m.numel() not in (1, n):
+            raise ValueError(f"mix_rate must be a float or hold one rate per sample ({n})")
+        return tab, m.expand(n).contiguous(), float(cfg_scale)
 
     def _text_features(self, x_text, n, underscore=False):
         words = [x_text] * n if isinstance(x_text, str) else list(x_text)
@@ -261,15 +338,21 @@ class Diffusion:
 
     @torch.no_grad()
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
-                 noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None):
+                 noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
+                 style_pairs=None, record_pred=None):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
         ``'_'`` alphabet of the ModifyCondition scripts (default: when the model's table has the 54 rows that alphabet
         needs).  Like the reference (``train.py:201,238``) the model is put in eval mode for the loop and in TRAIN mode
-        afterwards, whatever mode it came in."""
-        if mix_rate is not None:
-            raise NotImplementedError("mix_rate interpolation (unet.py:1558-1573)")
+        afterwards, whatever mode it came in.
+
+        ``mix_rate`` (writer-style interpolation, ``_mix_setup``): ignored unless the model was built with
+        ``args.interpolation`` - then every forward blends a freshly drawn pair of writers and, with ``cfg_scale > 0``, a step
+        is two forwards and ``torch.lerp(second, first, cfg_scale)`` (``last_stats["forwards_per_step"] == 2``) - or
+        ``style_pairs`` is given: the writers to blend, the same at every step (one forward per step).  ``labels`` is unused
+        in both modes.  ``record_pred`` receives every step's predictions (eager launches)."""
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale)
         if underscore is None:
             underscore = int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE
         model.eval()
@@ -286,7 +369,8 @@ class Diffusion:
             phosc = phoscLabels.int()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_T, noise=noise, seed=seed,
-                              sample_offset=sample_offset, record=record, use_graph=use_graph)
+                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
+                              record_pred=record_pred)
         finally:
             model.train()  # train.py:238 (unconditional)
         return self._finish(x, vae, args)
@@ -302,7 +386,8 @@ class Diffusion:
 
     @torch.no_grad()
     def sampling3(self, epoch, x_t, words, phoscLabels, model, model1, vae, emaOld, noiseInput, n, x_text, labels, args,
-                  mix_rate=None, cfg_scale=3, seed=None, sample_offset=0, use_graph=True, x_T=None, noise=None, record=None):
+                  mix_rate=None, cfg_scale=3, seed=None, sample_offset=0, use_graph=True, x_T=None, noise=None, record=None, *,
+                  style_pairs=None):
         """Bulk-regeneration sampler of ``regenerateFromtrain2.py:465-648`` (same argument order): the predicted noise is
         refreshed only on the steps of ``sampling3_calls_model`` (1 in 5) and reused in between, and unless
         ``args.fullSampling`` the update is deterministic (no ``sqrt(beta) * noise`` term, ``:618``).  ``noiseInput == 0``
@@ -310,9 +395,10 @@ class Diffusion:
         a ``vae`` is given, the denoised latents otherwise.  The per-step ``flagGen.txt`` poll (``:523-530``) is not
         reproduced.  ``x_T`` / ``noise`` / ``record`` (as in ``sampling``): the start latent, the per-step draws and a list that
         receives every step's x - how the tests replay the trajectories recorded from the reference's own loop
-        (``tests/golden/ddpm_traj_sampling3.npz``, ``oracle/make_golden_sampling3.py``)."""
-        if mix_rate is not None:
-            raise NotImplementedError("mix_rate interpolation (unet.py:1558-1573)")
+        (``tests/golden/ddpm_traj_sampling3.npz``, ``oracle/make_golden_sampling3.py``).  ``mix_rate`` / ``style_pairs`` as in
+        ``sampling``; this loop calls the model once per model-calling step, so with ``args.interpolation`` one pair is drawn for
+        each of those steps and none for the others.  (The reference's own loop accepts ``mix_rate`` and does not hand it to
+        the model, ``:587,591``: there the argument has no effect; here it selects the blend, as it does in ``sampling``.)"""
         if emaOld == 1:
             model = model1
         model.eval()  # and it stays in eval mode: ``#model.train()`` is commented out at regenerateFromtrain2.py:622
@@ -331,10 +417,11 @@ class Diffusion:
             phosc = phoscLabels.int()
         full = bool(getattr(args, "fullSampling", False))
         T = self.noise_steps
+        calls_model = None if full else (lambda i: self.sampling3_calls_model(i, T, epoch))
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, 0, calls_model=calls_model or (lambda i: True))
         x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_t if noiseInput == 0 else x_T, noise=noise, seed=seed,
                           sample_offset=sample_offset, record=record, use_graph=use_graph,
-                          calls_model=None if full else (lambda i: self.sampling3_calls_model(i, T, epoch)),
-                          deterministic=not full)
+                          calls_model=calls_model, deterministic=not full, mix=mix)
         if vae is None:
             return x
         image = self._finish(x, vae, args)

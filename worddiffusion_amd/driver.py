@@ -11,6 +11,8 @@ depend on the batch size or the number of ranks.  Host-side pieces restated from
   * ``write_png``     - 8-bit RGB / grey PNG without PIL / cv2 (the reference saves through torchvision + PIL,
                         ``train.py:104-137``);
   * ``regenerate``    - the loop; ``vae=None`` writes latents (``.npy``), a duck-typed VAE (``vae.decode(z).sample``) PNGs.
+  * ``interpolate``   - one strip per gt row: the row's word in ``mix_steps`` styles from writer ``s1`` to writer ``s2``
+                        (``sampling.py --interpolation --mix_rate`` renders one such blend of two random writers per call).
 """
 from __future__ import annotations
 
@@ -92,13 +94,14 @@ def write_png(path: str, img: np.ndarray) -> None:
 @torch.no_grad()
 def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: Dict[str, int], args, vae=None,
                batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
-               world: Optional[int] = None, skip_steps: bool = False, phosc_of=None):
+               world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
     ``<image>.png`` (a VAE was given) or ``<image>.npy`` (latents).  ``skip_steps`` selects the step-skipping sampler of
     ``regenerateFromtrain2.py`` (``Diffusion.sampling3``); ``phosc_of(word) -> int tensor [769]`` supplies PHOSC vectors for
-    ``UNetModelPhosc`` (``args.phosc == 1``)."""
+    ``UNetModelPhosc`` (``args.phosc == 1``).  ``mix_rate`` is handed to the sampler as ``full_sampling.py:171`` hands it: it has
+    an effect on a model built with ``args.interpolation`` only."""
     r0, w0, _ = env_rank_world()
     rank = r0 if rank is None else rank
     world = w0 if world is None else world
@@ -112,7 +115,7 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         words = [t for _, _, t in chunk]
         labels = torch.tensor([wr_dict[s] for s, _, _ in chunk], dtype=torch.int64)
         phosc = torch.stack([phosc_of(wd) for wd in words]) if phosc_of is not None else None
-        kw = dict(seed=seed, sample_offset=start + b0)
+        kw = dict(seed=seed, sample_offset=start + b0, mix_rate=mix_rate)
         if skip_steps:
             res = diffusion.sampling3(0, None, words, phosc, model, model, vae, 0, 1, len(chunk), words, labels, args, **kw)
             res = res if vae is None else res[2]
@@ -128,6 +131,52 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                     arr = (item.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).numpy()
                     write_png(os.path.join(out_dir, f"{image}.png"), arr if arr.shape[2] == 3 else arr[:, :, 0])
     return start, (torch.cat(outs) if outs else torch.empty(0))
+
+
+@torch.no_grad()
+def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, style_pair: Tuple[int, int], mix_steps: int = 8,
+                vae=None, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None,
+                phosc_of=None):
+    """One interpolation strip per gt row (this rank's shard of them): the row's word sampled ``mix_steps`` times in one call,
+    sample j with the writer embedding ``(1 - m_j) * label[s1] + m_j * label[s2]``, ``m = linspace(0, 1, mix_steps)``
+    (``Diffusion.sampling(..., style_pairs=)``, one forward per step).  Sample j of row r is global sample ``r * mix_steps + j``
+    of the noise stream, whatever the sharding.
+
+    Returns ``(start, [mix_steps, ...] tensor per row)``.  With ``out_dir``, ``<image>_interp.png`` is written per row: the
+    decoded images side by side when a VAE is given; otherwise the latents are kept as ``<image>_interp.npy`` and the PNG is a
+    grey preview of them (per sample the 4 channels stacked, min-max scaled over the strip)."""
+    if mix_steps < 2:
+        raise ValueError("mix_steps must be at least 2 (the two writers themselves)")
+    r0, w0, _ = env_rank_world()
+    rank = r0 if rank is None else rank
+    world = w0 if world is None else world
+    start, count = shard_range(len(rows), rank, world)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    m = torch.linspace(0, 1, mix_steps)
+    labels = torch.zeros(mix_steps, dtype=torch.int64)  # unused: the pair replaces the writer id
+    outs = []
+    for r in range(start, start + count):
+        _, image, word = rows[r]
+        phosc = torch.stack([phosc_of(word)] * mix_steps) if phosc_of is not None else None
+        res = diffusion.sampling(model, vae, mix_steps, word, labels, args, mix_rate=m, phoscLabels=phosc, seed=seed,
+                                 sample_offset=r * mix_steps, style_pairs=tuple(int(s) for s in style_pair)).detach().cpu()
+        outs.append(res)
+        if out_dir is None:
+            continue
+        if vae is None:
+            np.save(os.path.join(out_dir, f"{image}_interp.npy"), res.numpy())
+            lo, hi = float(res.min()), float(res.max())
+            tiles = ((res - lo) / max(hi - lo, 1e-12) * 255).round().to(torch.uint8)  # [N, c, h, w]
+            n, c, h, w = tiles.shape
+            strip = tiles.reshape(n, c * h, w).permute(1, 0, 2).reshape(c * h, n * w).numpy()
+        else:
+            arr = (res.clamp(0, 1) * 255).round().to(torch.uint8)  # [N, ch, H, W]
+            n, c, h, w = arr.shape
+            strip = arr.permute(2, 0, 3, 1).reshape(h, n * w, c).numpy()
+            strip = strip if c == 3 else strip[:, :, 0]
+        write_png(os.path.join(out_dir, f"{image}_interp.png"), strip)
+    return start, outs
 
 
 def main(argv=None):
@@ -153,6 +202,14 @@ def main(argv=None):
                     help="53: the 52-letter alphabet of train.py; 54: the '_' alphabet of trainModifyCondition.py:68")
     ap.add_argument("--skip_steps", type=int, default=0, help="1: regenerateFromtrain2.py's step-skipping sampler")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--interpolation", type=bool, nargs="?", const=True, default=False,
+                    help="args.interpolation of the reference (sampling.py:64; any value is true, as there): with --mix_rate "
+                         "every forward blends two random writers")
+    ap.add_argument("--mix_rate", type=float, default=None, help="weight of the second writer, 0..1 (sampling.py:65)")
+    ap.add_argument("--style_pair", type=int, nargs=2, default=None, metavar=("S1", "S2"),
+                    help="two writer class indices: one strip per gt row from S1 to S2 in --mix_steps samples is written "
+                         "instead of the rows themselves")
+    ap.add_argument("--mix_steps", type=int, default=8)
     ap.add_argument("--stable_dif_path", default=None,
                     help="local Stable-Diffusion checkout in diffusers layout (its vae/ subfolder is read; train.py:415): with it "
                          "the rows are decoded and written as PNGs, without it as latents (.npy)")
@@ -160,7 +217,7 @@ def main(argv=None):
     rank, world, local = env_rank_world()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
-    args = types.SimpleNamespace(device=dev, interpolation=False, charLevelEmb=0, charImages=0, attentionMaps=0, ocrTraining=0,
+    args = types.SimpleNamespace(device=dev, interpolation=bool(a.interpolation), charLevelEmb=0, charImages=0, attentionMaps=0, ocrTraining=0,
                                  imgConditioned=0, wrdChrWrStyl=0, phosc=a.phosc, phos=0, latent=True, fullSampling=False)
     rows = read_gt(a.gt_train)
     wr = writer_dict(rows, a.writer_dict)
@@ -182,9 +239,14 @@ def main(argv=None):
         if not a.alphabet_csv:
             ap.error("--phosc 1 needs --alphabet_csv (the PHOS shape-count table)")
         phosc_of = make_phosc_of(a.alphabet_csv)
+    if a.style_pair is not None:
+        start, res = interpolate(ema_model, diffusion, rows, args, tuple(a.style_pair), a.mix_steps, vae=vae,
+                                 out_dir=os.path.join(a.save_path, "images"), seed=a.seed, phosc_of=phosc_of)
+        print(f"[rank {rank}/{world}] strips of rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
+        return
     start, res = regenerate(ema_model, diffusion, rows, wr, args, vae=vae, batch=a.batch_size,
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
-                            phosc_of=phosc_of)
+                            phosc_of=phosc_of, mix_rate=a.mix_rate)
     print(f"[rank {rank}/{world}] rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
 
 

@@ -328,6 +328,10 @@ class Plan:
     def run_step(self, stream):
         self._run(self.step, stream)
 
+    def run_step1(self, stream):
+        """The second forward of a step of the two-forward interpolation plan (``UNetEngine.plan`` mix = 2)."""
+        self._run(self.step1, stream)
+
 
 def _ptr(t: Optional[torch.Tensor], byte_off: int = 0):
     return None if t is None else t.data_ptr() + byte_off
@@ -1255,11 +1259,16 @@ class UNetEngine:
         return a
 
     # ------------------------------------------------------------------------------------------ plan
-    def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0) -> Plan:
+    def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0) -> Plan:
         """film_steps = T > 0 (the DDPM sampler): the whole time / writer embedding path (timestep_embedding, time_embed,
         label_emb, SiLU, every emb_layers) is tabulated for all T timesteps by ``P.film`` ops - one large GEMM per
-        ``sampling()`` call instead of three 64-row GEMMs per step - and each step copies its rows (``wd_select_rows``)."""
-        key = (B, H, W, ctx_len, phosc_len, self.npass, film_steps)
+        ``sampling()`` call instead of three 64-row GEMMs per step - and each step copies its rows (``wd_select_rows``).
+
+        mix > 0 (writer-style interpolation, unet.py:1558-1573): the label term of a sample is the blend of a pair of writers
+        (``P.pairs`` / ``P.mix_m``, filled by ``load_mix``) instead of ``label[y]``.  With the table, ``mix`` is the number of
+        forwards per step (1 or 2) that read rows of their own - pairs indexed (forward, t, b); ``P.step`` reads the rows of
+        forward 0 and writes ``P.out``, ``P.step1`` (mix = 2) those of forward 1 and writes ``P.out1``."""
+        key = (B, H, W, ctx_len, phosc_len, self.npass, film_steps) + ((("mix", mix),) if mix else ())
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)  # most recently used last
             return self._plans[key]
@@ -1318,6 +1327,13 @@ class UNetEngine:
         # ---- per-step: time/label embedding (unet.py:1550-1581) + all emb_layers at once (unet.py:609-615,660)
         step = P.step
         has_lab = m.num_classes is not None
+        if mix and not has_lab:
+            raise ValueError("writer-style interpolation needs a class-conditional model (num_classes)")
+        if mix not in (0, 1, 2) or (mix == 2 and not film_steps):
+            raise ValueError(f"mix = {mix}: 1 or 2 forwards per step with the table, 1 without")
+        P.mix = mix
+        if mix:
+            P.mix_m = torch.zeros((B,), dtype=torch.float32, device=dev)
         self._film = self._f32(P, B, self.film_total)
         P.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
         P.film = []
@@ -1328,7 +1344,8 @@ class UNetEngine:
             # planes and the emb_layers GEMM of a chunk run when the loop enters it (P.film_prepare, same stream, a fraction
             # of one step each).
             T = film_steps
-            chunk = min(T, max(8, FILM_CHUNK_ROWS // B))
+            nf = max(1, mix)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
+            chunk = min(T, max(8, FILM_CHUNK_ROWS // (B * nf)))
             nchunks = (T + chunk - 1) // chunk
             Tp = nchunks * chunk
             film = P.film
@@ -1343,11 +1360,13 @@ class UNetEngine:
             tm = self._f32(P, Tp, ted)
             self._gemm(film, "time_embed.2[all t]", [self._src(e1, ted)], "te2.w", Tp, 1, bias=self._w["te2.b"], out_f32=tm,
                        out_ld=ted)
-            e2 = self._planes(P, chunk * B, ted)
-            P.film_table = self._f32(P, chunk * B, self.film_total)
+            e2 = self._planes(P, nf * chunk * B, ted)
+            P.film_table = self._f32(P, nf * chunk * B, self.film_total)
             P.film_chunk, P.film_nchunks, P.film_loaded = chunk, nchunks, -1
+            if mix:
+                P.pairs = torch.zeros((nf, Tp, B, 2), dtype=torch.int32, device=dev)
             chunk_gemm = []
-            self._gemm(chunk_gemm, "emb_layers(all)[chunk of t]", [self._src(e2, ted)], "film.w", chunk * B, 1,
+            self._gemm(chunk_gemm, "emb_layers(all)[chunk of t]", [self._src(e2, ted)], "film.w", nf * chunk * B, 1,
                        bias=self._w["film.b"], out_f32=P.film_table, out_ld=self.film_total)
             lab = self._w["label"].data_ptr() if has_lab else None
             yin = P.y_in.data_ptr() if has_lab else None
@@ -1358,8 +1377,15 @@ class UNetEngine:
                 c = int(t) // chunk
                 if c == P.film_loaded:
                     return False
-                N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, e2[0].data_ptr(),
-                                           e2[1].data_ptr() if lo_ok else None, ted, stream), "SiLU(time + label)[chunk of t]")
+                if mix:
+                    for f in range(nf):  # table f: rows f*chunk*B.. of the planes, pairs[f][c*chunk..]
+                        N.check(lib.wd_emb_combine_mix(tm.data_ptr() + 4 * c * chunk * ted, lab, P.pairs[f, c * chunk].data_ptr(),
+                                                       P.mix_m.data_ptr(), ncls, chunk, B, ted, e2[0, f * chunk * B].data_ptr(),
+                                                       e2[1, f * chunk * B].data_ptr() if lo_ok else None, ted, stream),
+                                "SiLU(time + blended label)[chunk of t]")
+                else:
+                    N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, e2[0].data_ptr(),
+                                               e2[1].data_ptr() if lo_ok else None, ted, stream), "SiLU(time + label)[chunk of t]")
                 Plan._run(chunk_gemm, stream)
                 P.film_loaded = c
                 return True
@@ -1367,7 +1393,18 @@ class UNetEngine:
             P.film_prepare = film_prepare
             step.append((lib.wd_select_rows, (P.film_table.data_ptr(), P.t_dev.data_ptr(), B, self.film_total, chunk,
                                               self._film.data_ptr()), "film rows of step t"))
+            if mix == 2:
+                select1 = (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), P.t_dev.data_ptr(), B, self.film_total, chunk,
+                                                self._film.data_ptr()), "film rows of step t, second forward")
         else:
+            if mix:
+                # the blended rows [B, ted] (wd_label_mix) are the residual of the time_embed.2 GEMM, row b for sample b
+                P.pairs = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+                lab_rows = self._f32(P, B, ted)
+                id_rows = torch.arange(B, dtype=torch.int64, device=dev)
+                P.keep.append(id_rows)
+                step.append((lib.wd_label_mix, (self._w["label"].data_ptr(), P.pairs.data_ptr(), P.mix_m.data_ptr(), m.num_classes,
+                                                B, ted, lab_rows.data_ptr()), "blended label rows"))
             te = self._planes(P, B, mc)
             step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2,
                                                      te[0].data_ptr(), te[1].data_ptr() if lo_ok else None, mc),
@@ -1377,8 +1414,8 @@ class UNetEngine:
                        out_pl=e1)
             e2 = self._planes(P, B, ted)  # SiLU(emb): the only form any consumer reads (emb_layers start with SiLU)
             self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
-                       resid=self._w["label"].data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
-                       resid_rows=P.y_in.data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
+                       resid=(lab_rows if mix else self._w["label"]).data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
+                       resid_rows=(id_rows if mix else P.y_in).data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
             self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"],
                        out_f32=self._film, out_ld=self.film_total)
 
@@ -1440,6 +1477,12 @@ class UNetEngine:
                        cur.h * cur.w, bias=self._w["out.b"], out_f32=otok, out_ld=oc)
             step.append((lib.wd_tokens_to_nchw, (otok.data_ptr(), oc, B, oc, cur.h * cur.w, P.out.data_ptr()),
                          "tokens_to_nchw"))
+        if mix == 2:
+            # the second forward of a step: its own FiLM rows, the same launches, the prediction kept beside the first one
+            fn, args, what = step[-1]
+            assert args[-1] == P.out.data_ptr(), what
+            P.out1 = torch.empty_like(P.out)
+            P.step1 = [select1] + step[1:-1] + [(fn, args[:-1] + (P.out1.data_ptr(),), what)]
         self._plans[key] = P
         return P
 
@@ -1469,6 +1512,27 @@ class UNetEngine:
             if lo < 0 or hi >= bound:
                 raise IndexError(f"{what} out of range: [{lo}, {hi}] does not fit a table of {bound} rows")
 
+    def check_pairs(self, pairs):
+        """Host-side range check of the writer pairs of the interpolation path (any integer tensor [..., 2]); the reference's
+        ``label_emb`` lookup raises an index error for such an id (unet.py:1567)."""
+        nc = self.model.num_classes
+        if nc is None:
+            raise ValueError("writer-style interpolation needs a class-conditional model (num_classes)")
+        lo, hi = int(pairs.min()), int(pairs.max())
+        if lo < 0 or hi >= nc:
+            raise IndexError(f"writer id (style pair) out of range: [{lo}, {hi}] does not fit a table of {nc} rows")
+
+    def load_mix(self, P: Plan, pairs, mix_rate, check=True):
+        """pairs: int tensor shaped like ``P.pairs`` up to its leading timestep padding ([mix, T, B, 2] with the table, [B, 2]
+        without); mix_rate: fp32 [B]."""
+        if check:
+            self.check_pairs(pairs)
+        if P.pairs.dim() == 4:
+            P.pairs[:, :pairs.shape[1]].copy_(pairs, non_blocking=True)
+        else:
+            P.pairs.copy_(pairs, non_blocking=True)
+        P.mix_m.copy_(mix_rate, non_blocking=True)
+
     def load_inputs(self, P: Plan, x=None, t=None, context=None, y=None, phosc=None, check=True):
         if check:
             self.check_ids(context, y, phosc, need_y=False)
@@ -1483,14 +1547,21 @@ class UNetEngine:
         if phosc is not None:
             P.phosc_in.copy_(phosc.to(torch.int32) if phosc.dtype != torch.int32 else phosc, non_blocking=True)
 
-    def forward(self, x, t, context, y, phosc=None):
+    def forward(self, x, t, context, y, phosc=None, mix=None):
+        """mix = (int pairs [B, 2], fp32 mix rates [B]): the writer term is the blend of each sample's pair and ``y`` is unused
+        (unet.py:1558-1573)."""
         self.refresh_weights()
         B, _, H, W = x.shape
         ctx_len = 0 if context is None else context.shape[1]
         phosc_len = 0 if phosc is None else phosc.shape[1]
-        P = self.plan(B, H, W, ctx_len, phosc_len)
-        self.check_ids(context, y, phosc)
+        if mix is not None:
+            self.check_pairs(mix[0])
+            y = None
+        P = self.plan(B, H, W, ctx_len, phosc_len, mix=1 if mix is not None else 0)
+        self.check_ids(context, y, phosc, need_y=mix is None)
         self.load_inputs(P, x, t, context, y, phosc, check=False)
+        if mix is not None:
+            self.load_mix(P, mix[0], mix[1], check=False)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         P.run_cond(stream)
         P.run_step(stream)

@@ -185,9 +185,6 @@ class UNetBase(nn.Module):
         pass
 
     def _check_common(self, x, timesteps, mix_rate):
-        if self.interpolation and mix_rate is not None:
-            raise NotImplementedError("writer-style interpolation (mix_rate) draws two random writers on the host "
-                                      "(unet.py:1558-1573); not on the accelerated path")
         if timesteps is None:
             raise ValueError("timesteps is required")
         if x.dim() != 4 or x.shape[1] != self.in_channels:
@@ -208,8 +205,22 @@ class UNetBase(nn.Module):
                 self._train_engine.set_precision(mode)
         return self._train_engine
 
-    def _run(self, x, timesteps, context, y, phosc=None):
-        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+    def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None):
+        autograd = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if self.interpolation and mix_rate is not None:
+            # unet.py:1558-1573 / unetPhosc.py:1093-1108: one pair of writers per call from Python's global ``random``, the same
+            # blended row for every sample; ``y`` is unused.  (Without args.interpolation the reference ignores mix_rate.)
+            if autograd:
+                raise NotImplementedError("mix_rate under autograd: the reference's training loop never passes it "
+                                          "(train.py:287); the interpolation forward is inference-only")
+            from .diffusion import draw_style_pairs
+            pair = draw_style_pairs(1)[0]
+            B = x.shape[0]
+            pairs = torch.tensor([pair] * B, dtype=torch.int32)
+            m = mix_rate.float().reshape(-1).expand(B) if torch.is_tensor(mix_rate) else torch.full((B,), float(mix_rate))
+            out = self.engine.forward(x.float(), timesteps, context, y, phosc, mix=(pairs, m))
+            return out.type(x.dtype)
+        if autograd:
             # ``predicted_noise = model(...)`` inside the training loop (train.py:287): the result carries a grad_fn whose
             # backward runs the HIP backward list and fills ``param.grad`` (reference layouts), so ``loss.backward()``,
             # ``optimizer.step()`` and ``ema.step_ema`` of the reference loop work unchanged.

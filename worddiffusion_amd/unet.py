@@ -35,4 +35,4 @@ class UNetModel(UNetBase):
             if _arg(self.args, "imgConditioned", 0) == 1:
                 raise NotImplementedError("args.imgConditioned=1 drops the writer embedding (unet.py:1578-1579)")
             assert y is not None and tuple(y.shape) == (x.shape[0],), "y must be [B] (unet.py:1555)"
-        return self._run(x, timesteps, context, y)
+        return self._run(x, timesteps, context, y, mix_rate=mix_rate)

@@ -25,4 +25,4 @@ class UNetModelPhosc(UNetBase):
             if phoscLabels is None:
                 raise ValueError("args.phosc/phos is set: phoscLabels [B, n] is required (unetPhosc.py:1120-1123)")
             phosc = phoscLabels.int()
-        return self._run(x, timesteps, context, y, phosc)
+        return self._run(x, timesteps, context, y, phosc, mix_rate=mix_rate)
