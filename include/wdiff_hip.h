@@ -411,6 +411,32 @@ int wd_advance_timestep(int32_t* t_dev, int delta, int64_t* t64, int batch, void
 int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sample_offset, uint32_t stream_id,
              void* stream);
 
+/* The tail of AutoencoderKL.encode (train.py:277-278: vae.encode(images).latent_dist.sample() * 0.18215) in one launch:
+ * quant_conv (1x1, 2L -> 2L), chunk into mean | logvar, clamp, the posterior draw, the scale and the layout change.
+ *   moments_tok  encoder.conv_out's token-major fp32 output [batch*hw][ld], ld >= 2L, columns 0..2L-1 read;
+ *   w, bias      quant_conv.weight [2L][2L](x1x1) and .bias [2L], fp32, reference layout - never split into bf16 planes (logvar
+ *                goes through exp: a 1e-5 relative error of the split would be multiplied by |logvar| / 2);
+ *   mean, logvar NCHW fp32 [batch][L][hw]; logvar is clamped to [-30, 20] (NaN passes, as torch.clamp);
+ *   sample       NULL, or NCHW fp32: scale * (mean + exp(0.5 * logvar) * z).
+ * Rounding order (plain fp32, no fma contraction anywhere): output o of quant_conv at a position with moments x is
+ *   ((w[o][0]*x[0] + w[o][1]*x[1]) + ... + w[o][2L-1]*x[2L-1]) + bias[o]    - products rounded, summed left to right, bias last;
+ * the draw is  t0 = 0.5f*logvar; t1 = expf(t0); t2 = t1*z; t3 = mean + t2; sample = scale*t3, each rounded on its own.
+ * noise != NULL (needs sample): z is read from it (NCHW, parity tests).  Otherwise z ~ N(0,1) from Philox4x32-10, bit-identical
+ * to what wd_randn writes for (batch, L*hw, seed, sample_offset, WD_STREAM_VAE_POSTERIOR): sample i depends on
+ * (seed, sample_offset + i) only, not on how a batch is cut into launches.
+ * WD_EINVAL (nothing launched): a NULL required pointer, L outside 1..WD_VAE_MAX_LATENT, ld < 2L, L*hw not a multiple of 4,
+ * noise without sample, mean / logvar / sample / noise not 16-byte aligned.  Does not allocate or synchronise (capturable). */
+#define WD_VAE_MAX_LATENT 8
+#define WD_STREAM_VAE_POSTERIOR 3 /* stream ids taken so far: 0 x_T, 1 noise_images eps, 2 the training step's eps */
+int wd_vae_posterior(const float* moments_tok, int ld, const float* w, const float* bias, int batch, int L, int hw, float* mean,
+                     float* logvar, float* sample, float scale, const float* noise, uint64_t seed, uint64_t sample_offset,
+                     void* stream);
+
+/* The same draw from stored moments (latent_dist.sample() called after encode): mean, logvar (already clamped), sample and
+ * noise are fp32 [batch][n_per_sample], n_per_sample % 4 == 0, 16-byte aligned; z as in wd_vae_posterior, bit for bit. */
+int wd_posterior_sample(const float* mean, const float* logvar, int batch, int n_per_sample, float* sample, float scale,
+                        const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
+
 /* x_t = sqrt_ah[t_b] * x + sqrt_1m_ah[t_b] * eps  (Diffusion.noise_images, train.py:190-194); the two tables
  * sqrt(alpha_hat) and sqrt(1 - alpha_hat) are tabulated by the caller (fp32, reference op order). */
 int wd_noise_images(const float* x, const float* eps, const int64_t* t, const float* sqrt_ah, const float* sqrt_1m_ah,

@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "wdiff_hip.h")
 
 WD_OK, WD_EINVAL, WD_ELAUNCH, WD_ESTATE = 0, -1, -2, -3
 ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
+VAE_MAX_LATENT, STREAM_VAE_POSTERIOR = 8, 3  # WD_VAE_MAX_LATENT, WD_STREAM_VAE_POSTERIOR of the header
 NCLASS = 13
 CLASS_NAMES = ("gemm", "gn_stats", "gn_apply", "layernorm", "attention", "other", "gemm_other_tiles", "gemm_splitk_reduce",
                "gemm_two_per_cu", "gemm_weights_to_registers", "feed_forward_fused", "weight_gradient", "gemm_small_maps_whole_k")
@@ -110,6 +111,8 @@ _SIGS = {
     "wd_ddpm_step": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "wd_advance_timestep": (_i, [_vp, _i, _vp, _i, _vp]),
     "wd_randn": (_i, [_vp, _i, _i, _u64, _u64, C.c_uint32, _vp]),
+    "wd_vae_posterior": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _u64, _u64, _vp]),
+    "wd_posterior_sample": (_i, [_vp, _vp, _i, _i, _vp, _f, _vp, _u64, _u64, _vp]),
     "wd_noise_images": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wd_copy2d": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _vp]),
     "wd_ema_update": (_i, [_vp, _vp, C.c_int64, C.c_double, _vp]),

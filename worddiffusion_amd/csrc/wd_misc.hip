@@ -318,6 +318,124 @@ __global__ void ddpm_step_cfg_kernel(float* __restrict__ x, const float* __restr
     }
 }
 
+// ---- AutoencoderKL posterior (DiagonalGaussianDistribution of the encoder's moments) --------------------------------
+// One draw for four consecutive elements of a sample, shared by both kernels below:
+//   sample = scale * (mean + exp(0.5 * logvar) * z), every operation rounded on its own (no contraction in this file);
+// z from ``noise`` (float4 index i4 of the whole batch) or from the Philox stream of wd_randn under WD_STREAM_VAE_POSTERIOR.
+__device__ __forceinline__ float4 posterior_draw4(const float4 m, const float4 lv, float scale, const float* __restrict__ noise,
+                                                  long i4, uint64_t seed, uint64_t sample, uint32_t e4) {
+    const float4 z = noise ? reinterpret_cast<const float4*>(noise)[i4]
+                           : philox_normal4(seed, sample, 0x80000000u | (uint32_t)WD_STREAM_VAE_POSTERIOR, e4);
+    float4 o;
+    o.x = scale * (m.x + expf(0.5f * lv.x) * z.x);
+    o.y = scale * (m.y + expf(0.5f * lv.y) * z.y);
+    o.z = scale * (m.z + expf(0.5f * lv.z) * z.z);
+    o.w = scale * (m.w + expf(0.5f * lv.w) * z.w);
+    return o;
+}
+
+constexpr int kVaeMaxK = 2 * WD_VAE_MAX_LATENT;
+
+// quant_conv output o at one position: ((w[o][0] x[0] + w[o][1] x[1]) + ... + w[o][K-1] x[K-1]) + bias[o], plain fp32
+__device__ __forceinline__ float quant_dot(const float* __restrict__ w, const float (&x)[kVaeMaxK], int K2, float bias) {
+    float acc = w[0] * x[0];
+#pragma unroll
+    for (int k = 1; k < kVaeMaxK; ++k)
+        if (k < K2) acc = acc + w[k] * x[k];
+    return acc + bias;
+}
+
+__device__ __forceinline__ float clamp_logvar(float v) { return v < -30.0f ? -30.0f : (v > 20.0f ? 20.0f : v); }  // NaN passes, as torch.clamp
+
+__device__ __forceinline__ void load_moments(const float* __restrict__ row, int K2, int vec, float (&x)[kVaeMaxK]) {
+    if (vec) {  // K2 % 4 == 0, rows 16-byte aligned
+#pragma unroll
+        for (int k = 0; k < kVaeMaxK; k += 4)
+            if (k < K2) {
+                const float4 v = *reinterpret_cast<const float4*>(row + k);
+                x[k] = v.x; x[k + 1] = v.y; x[k + 2] = v.z; x[k + 3] = v.w;
+            }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kVaeMaxK; ++k)
+            if (k < K2) x[k] = row[k];
+    }
+}
+
+// hw % 4 == 0: one thread owns four consecutive positions of a sample: it reads their token rows once and writes, per latent
+// channel, one float4 of mean / logvar / sample (consecutive threads -> consecutive float4s of a channel plane).
+__global__ void vae_posterior_rows_kernel(const float* __restrict__ moments, int ld, int vec, const float* __restrict__ w,
+                                          const float* __restrict__ bias, int batch, int L, int hw, float* __restrict__ mean,
+                                          float* __restrict__ logvar, float* __restrict__ sample, float scale,
+                                          const float* __restrict__ noise, uint64_t seed, uint64_t sample_offset) {
+    const int K2 = 2 * L, hw4 = hw >> 2;
+    const long total = (long)batch * hw4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / hw4), p0 = (int)(i - (long)b * hw4) * 4;
+        float x[4][kVaeMaxK];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) load_moments(moments + ((long)b * hw + p0 + j) * ld, K2, vec, x[j]);
+#pragma unroll
+        for (int l = 0; l < WD_VAE_MAX_LATENT; ++l) {
+            if (l >= L) break;
+            const float* wm = w + l * K2;
+            const float* wv = w + (L + l) * K2;
+            const float bm = bias[l], bv = bias[L + l];
+            const float4 m = make_float4(quant_dot(wm, x[0], K2, bm), quant_dot(wm, x[1], K2, bm), quant_dot(wm, x[2], K2, bm),
+                                         quant_dot(wm, x[3], K2, bm));
+            const float4 lv = make_float4(clamp_logvar(quant_dot(wv, x[0], K2, bv)), clamp_logvar(quant_dot(wv, x[1], K2, bv)),
+                                          clamp_logvar(quant_dot(wv, x[2], K2, bv)), clamp_logvar(quant_dot(wv, x[3], K2, bv)));
+            const uint32_t e4 = (uint32_t)(((long)l * hw + p0) >> 2);
+            const long o4 = (long)b * ((long)L * hw4) + e4;
+            reinterpret_cast<float4*>(mean)[o4] = m;
+            reinterpret_cast<float4*>(logvar)[o4] = lv;
+            if (sample)
+                reinterpret_cast<float4*>(sample)[o4] = posterior_draw4(m, lv, scale, noise, o4, seed, sample_offset + (uint64_t)b, e4);
+        }
+    }
+}
+
+// any hw with L * hw % 4 == 0: one thread per float4 of the NCHW output; its four elements may lie in two channel planes, so
+// each one finds its own (channel, position) and reads that position's token row (the rows stay in cache: a map of odd size is small).
+__global__ void vae_posterior_flat_kernel(const float* __restrict__ moments, int ld, int vec, const float* __restrict__ w,
+                                          const float* __restrict__ bias, int batch, int L, int hw, float* __restrict__ mean,
+                                          float* __restrict__ logvar, float* __restrict__ sample, float scale,
+                                          const float* __restrict__ noise, uint64_t seed, uint64_t sample_offset) {
+    const int K2 = 2 * L, n4 = (L * hw) >> 2;
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / n4);
+        const uint32_t e4 = (uint32_t)(i - (long)b * n4);
+        float mv[4], lvv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int idx = (int)e4 * 4 + j, l = idx / hw, p = idx - l * hw;
+            float x[kVaeMaxK];
+            load_moments(moments + ((long)b * hw + p) * ld, K2, vec, x);
+            mv[j] = quant_dot(w + l * K2, x, K2, bias[l]);
+            lvv[j] = clamp_logvar(quant_dot(w + (L + l) * K2, x, K2, bias[L + l]));
+        }
+        const float4 m = make_float4(mv[0], mv[1], mv[2], mv[3]), lv = make_float4(lvv[0], lvv[1], lvv[2], lvv[3]);
+        reinterpret_cast<float4*>(mean)[i] = m;
+        reinterpret_cast<float4*>(logvar)[i] = lv;
+        if (sample) reinterpret_cast<float4*>(sample)[i] = posterior_draw4(m, lv, scale, noise, i, seed, sample_offset + (uint64_t)b, e4);
+    }
+}
+
+__global__ void posterior_sample_kernel(const float* __restrict__ mean, const float* __restrict__ logvar, int batch, int n4,
+                                        float* __restrict__ sample, float scale, const float* __restrict__ noise, uint64_t seed,
+                                        uint64_t sample_offset) {
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / n4);
+        reinterpret_cast<float4*>(sample)[i] =
+            posterior_draw4(reinterpret_cast<const float4*>(mean)[i], reinterpret_cast<const float4*>(logvar)[i], scale, noise, i, seed,
+                            sample_offset + (uint64_t)b, (uint32_t)(i - (long)b * n4));
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 extern "C" int wd_timestep_embedding(const int64_t* t, int batch, const float* freqs, int half, wd_bf16* out_hi,
@@ -482,5 +600,35 @@ extern "C" int wd_ddpm_step_cfg(float* x, const float* first, const float* secon
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(ddpm_step_cfg_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, first, second,
                        scale, eps_out, batch, n_per_sample / 4, ca, cb, cs, t_dev, noise, seed, sample_offset);
+    return wd_check_launch();
+}
+
+extern "C" int wd_vae_posterior(const float* moments_tok, int ld, const float* w, const float* bias, int batch, int L, int hw,
+                                float* mean, float* logvar, float* sample, float scale, const float* noise, uint64_t seed,
+                                uint64_t sample_offset, void* stream) {
+    if (!moments_tok || !w || !bias || !mean || !logvar || batch <= 0 || hw <= 0 || L < 1 || L > WD_VAE_MAX_LATENT || ld < 2 * L ||
+        ((long)L * hw) % 4 || (long)L * hw > 0x7fffffffL || (noise && !sample))
+        return WD_EINVAL;
+    if (!aligned16(mean) || !aligned16(logvar) || !aligned16(sample) || !aligned16(noise)) return WD_EINVAL;
+    const int vec = (L % 2 == 0) && (ld % 4 == 0) && aligned16(moments_tok);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    if (hw % 4 == 0)
+        hipLaunchKernelGGL(vae_posterior_rows_kernel, dim3(grid_for((long)batch * (hw / 4))), dim3(256), 0, st, moments_tok, ld, vec, w,
+                           bias, batch, L, hw, mean, logvar, sample, scale, noise, seed, sample_offset);
+    else
+        hipLaunchKernelGGL(vae_posterior_flat_kernel, dim3(grid_for((long)batch * (L * hw / 4))), dim3(256), 0, st, moments_tok, ld, vec,
+                           w, bias, batch, L, hw, mean, logvar, sample, scale, noise, seed, sample_offset);
+    return wd_check_launch();
+}
+
+extern "C" int wd_posterior_sample(const float* mean, const float* logvar, int batch, int n_per_sample, float* sample, float scale,
+                                   const float* noise, uint64_t seed, uint64_t sample_offset, void* stream) {
+    if (!mean || !logvar || !sample || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4) return WD_EINVAL;
+    if (!aligned16(mean) || !aligned16(logvar) || !aligned16(sample) || !aligned16(noise)) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(posterior_sample_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, mean, logvar, batch,
+                       n_per_sample / 4, sample, scale, noise, seed, sample_offset);
     return wd_check_launch();
 }

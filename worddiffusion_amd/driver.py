@@ -11,6 +11,8 @@ depend on the batch size or the number of ranks.  Host-side pieces restated from
   * ``write_png``     - 8-bit RGB / grey PNG without PIL / cv2 (the reference saves through torchvision + PIL,
                         ``train.py:104-137``);
   * ``regenerate``    - the loop; ``vae=None`` writes latents (``.npy``), a duck-typed VAE (``vae.decode(z).sample``) PNGs.
+  * ``--encode_images`` - the other direction: the gt rows' images through the VAE encoder into a latent cache
+                        (``latents.build_latent_cache``), then exit.
   * ``interpolate``   - one strip per gt row: the row's word in ``mix_steps`` styles from writer ``s1`` to writer ``s2``
                         (``sampling.py --interpolation --mix_rate`` renders one such blend of two random writers per call).
 """
@@ -213,10 +215,26 @@ def main(argv=None):
     ap.add_argument("--stable_dif_path", default=None,
                     help="local Stable-Diffusion checkout in diffusers layout (its vae/ subfolder is read; train.py:415): with it "
                          "the rows are decoded and written as PNGs, without it as latents (.npy)")
+    ap.add_argument("--encode_images", default=None, metavar="DIR",
+                    help="build a latent cache instead of sampling: encode DIR/<image>.png of every gt row with the VAE encoder of "
+                         "--stable_dif_path, write --latents_out and exit (the --vaeFromDict 1 input of the training scripts)")
+    ap.add_argument("--latents_out", default=None, metavar="FILE", help="--encode_images: the container to write (.safetensors / .npz)")
+    ap.add_argument("--latent_mode", default="sample", choices=["sample", "mode"],
+                    help="--encode_images: a posterior draw per image (keyed by --seed and the row index) or the posterior mean")
     a = ap.parse_args(argv)
     rank, world, local = env_rank_world()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
+    if a.encode_images:
+        if not a.stable_dif_path or not a.latents_out:
+            ap.error("--encode_images needs --stable_dif_path (the VAE) and --latents_out (the file to write)")
+        from .latents import build_latent_cache
+        from .vae import AutoencoderKL
+        vae = AutoencoderKL.from_pretrained(a.stable_dif_path, subfolder="vae").to(dev)
+        rows = read_gt(a.gt_train)
+        build_latent_cache(vae, rows, a.encode_images, a.latents_out, mode=a.latent_mode == "mode", seed=a.seed, batch=a.batch_size)
+        print(f"latents of {len({r[1] for r in rows})} images ({a.latent_mode}) written to {a.latents_out}")
+        return
     args = types.SimpleNamespace(device=dev, interpolation=bool(a.interpolation), charLevelEmb=0, charImages=0, attentionMaps=0, ocrTraining=0,
                                  imgConditioned=0, wrdChrWrStyl=0, phosc=a.phosc, phos=0, latent=True, fullSampling=False)
     rows = read_gt(a.gt_train)

@@ -33,13 +33,17 @@ def conv_gather_table(h: int, w: int, mode: str) -> Tuple[np.ndarray, int, int]:
     """int32 [9][h_out*w_out] source position (or -1 = zero padding) per 3x3 tap.
 
     mode 'same': 3x3 pad 1 (unet.py:595); 'down': 3x3 stride 2 pad 1 (unet.py:540-542);
-    'up': nearest x2 then 3x3 pad 1 (unet.py:497-499) - (h, w) is the INPUT size in all modes."""
+    'up': nearest x2 then 3x3 pad 1 (unet.py:497-499); 'down_rb': zero padding on the right and bottom only, then 3x3 stride 2
+    pad 0 (the ``Downsample2D`` of the AutoencoderKL encoder: output (y, x) reads (2y + ky, 2x + kx)) - (h, w) is the INPUT size
+    in all modes."""
     if mode == "same":
         ho, wo = h, w
     elif mode == "down":
         ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     elif mode == "up":
         ho, wo = 2 * h, 2 * w
+    elif mode == "down_rb":
+        ho, wo = (h - 2) // 2 + 1, (w - 2) // 2 + 1
     else:
         raise ValueError(mode)
     yy, xx = np.meshgrid(np.arange(ho), np.arange(wo), indexing="ij")
@@ -52,6 +56,9 @@ def conv_gather_table(h: int, w: int, mode: str) -> Tuple[np.ndarray, int, int]:
         elif mode == "down":
             sy, sx = 2 * yy + dy, 2 * xx + dx
             ok = (sy >= 0) & (sy < h) & (sx >= 0) & (sx < w)
+        elif mode == "down_rb":
+            sy, sx = 2 * yy + dy + 1, 2 * xx + dx + 1
+            ok = (sy < h) & (sx < w)
         else:
             uy, ux = yy + dy, xx + dx  # coordinates in the upsampled map
             ok = (uy >= 0) & (uy < ho) & (ux >= 0) & (ux < wo)
@@ -609,6 +616,8 @@ class UNetEngine:
             self._tab_np[dt.data_ptr()] = tab
             if mode == "down":
                 self._down_w[dt.data_ptr()] = wo
+            # ('down_rb' records nothing: a width hint becomes wd_gemm_args.slab_rows, with which the kernel COMPUTES the source rows of
+            # the pad-1 geometry instead of reading the table - the right / bottom table must be read)
             if mode == "same":
                 self._same_w[dt.data_ptr()] = w
         return self._tabs[key]

@@ -15,6 +15,9 @@ container with the same content:
 and a user converts their own pickles once, offline, in their own environment, with ``convert_latent_dict`` (it takes the
 dictionary object they loaded themselves - see INTEGRATION.md).
 
+A cache is MADE here with ``build_latent_cache`` (the package's own AutoencoderKL encoder over the gt rows' images, scaled by
+0.18215 like the reference's), and ``train_epoch(..., vae=...)`` encodes pixel batches on the fly instead (``train.py:277-278``).
+
 ``CachedLatentDataset`` mirrors the reference dataset's item (``trainModifyCondition.py:460-477``: image name, latent, word
 ids through ``label_padding``, writer index, transcription[, PHOSC vector]) and batches it on the host; ``train_epoch`` is the
 batch loop of ``train.py:261-295`` with the loop body replaced by one ``TrainStep`` call.
@@ -58,6 +61,60 @@ def convert_latent_dict(obj: Mapping[str, object], path: str, field: str = "imag
     for k, v in obj.items():
         flat[str(k)] = v[field] if isinstance(v, Mapping) else v
     return save_latent_cache(path, flat)
+
+
+def load_image(path: str) -> torch.Tensor:
+    """``Image.open(path).convert('RGB')`` -> ``ToTensor`` -> ``Normalize((0.5,)*3, (0.5,)*3)`` (``train.py:126,361-362``):
+    float32 [3, H, W] in [-1, 1]."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+    t = torch.from_numpy(a.copy()).permute(2, 0, 1).to(torch.float32).div_(255.0)
+    return t.sub_(0.5).div_(0.5)
+
+
+@torch.no_grad()
+def encode_images(vae, images: torch.Tensor, *, seed: int, sample_offset: int = 0, mode: bool = False) -> torch.Tensor:
+    """Float images [B, 3, H, W] in [-1, 1] (H, W multiples of ``2**(levels - 1)``) -> scaled latents [B, L, h, w]: the two lines
+    ``vae.encode(images).latent_dist.sample() * 0.18215`` of ``train.py:277-278`` (``mode=True``: the posterior mean instead of
+    a draw).  Image ``i``'s noise depends on ``(seed, sample_offset + i)`` only."""
+    if images.dim() != 4 or not images.is_floating_point():
+        raise ValueError(f"images must be a float tensor [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+    return vae.encode_latents(images.to(torch.float32), seed=seed, sample_offset=sample_offset, mode=mode)
+
+
+def build_latent_cache(vae, rows: Sequence[Tuple[str, str, str]], image_dir: str, out_path: str, *, mode: bool = False,
+                       seed: int = 0, batch: int = 64, suffix: str = ".png", device=None) -> str:
+    """Encodes the image of every gt row (``image_dir/<image><suffix>``) and writes ``{image + suffix: latent}`` with
+    ``save_latent_cache``: what the reference's ``--vaeFromDict 1`` dictionaries hold (tensors [1, L, h, w], already scaled by
+    0.18215, fed to the UNet as they are, ``trainModifyCondition.py:708-709``), in the container ``LatentCache`` reads.  The draw of
+    a row is keyed by its index in ``rows`` (``sample_offset``), so the cache does not depend on ``batch``.  A row listed twice is
+    encoded once.  Images of one batch must share a size."""
+    if device is None:
+        device = next(vae.parameters()).device if hasattr(vae, "parameters") else "cpu"
+    todo, seen = [], set()
+    for i, (_, image, _) in enumerate(rows):
+        if image not in seen:
+            seen.add(image)
+            todo.append((i, image + suffix))
+    out: Dict[str, torch.Tensor] = {}
+    for b0 in range(0, len(todo), batch):
+        part = todo[b0:b0 + batch]
+        imgs = [load_image(os.path.join(image_dir, name)) for _, name in part]
+        if any(t.shape != imgs[0].shape for t in imgs):
+            raise ValueError(f"images of one batch must share a size: {sorted({tuple(t.shape) for t in imgs})}")
+        x = torch.stack(imgs).to(device)
+        # consecutive row indices share one launch; a gap (a repeated image was dropped) starts a new one
+        j = 0
+        while j < len(part):
+            k = j + 1
+            while k < len(part) and part[k][0] == part[k - 1][0] + 1:
+                k += 1
+            lat = encode_images(vae, x[j:k], seed=seed, sample_offset=part[j][0], mode=mode).cpu()
+            for (_, name), t in zip(part[j:k], lat):
+                out[name] = t[None]  # [1, L, h, w], as the reference's dictionaries
+            j = k
+    return save_latent_cache(out_path, out)
 
 
 class LatentCache:
@@ -188,12 +245,16 @@ class CachedLatentDataset:
 
 def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epoch: int = 0, seed: int = 0,
                 max_batches: Optional[int] = None, rank: int = 0, world: int = 1, shuffle: bool = True,
-                on_batch: Optional[Callable[[int, torch.Tensor], None]] = None) -> Dict[str, object]:
+                on_batch: Optional[Callable[[int, torch.Tensor], None]] = None, vae=None) -> Dict[str, object]:
     """One epoch of ``train.py:261-295`` over cached latents: for every batch ``step(latents, word ids, writer ids[, PHOSC])``
     (``training.TrainStep``: timesteps, noise, forward, loss, backward, gradient all-reduce, AdamW, EMA).
     ``max_batches=30`` reproduces the reference's ``if i == 30: break`` (``train.py:263-264``).  The loss stays on the
     device; it is read once at the end (the reference's per-batch ``loss.item()``, ``train.py:295``, is available through
-    ``on_batch``).  Returns the number of batches / images and the mean loss."""
+    ``on_batch``).  Returns the number of batches / images and the mean loss.
+
+    ``vae``: the dataset's batches carry pixels (``"images"``: float [B, 3, H, W] in [-1, 1]) instead of ``"latents"`` and every
+    batch is encoded first, ``vae.encode(images).latent_dist.sample() * 0.18215`` (``train.py:277-278``), with the noise of an
+    image keyed by ``(seed, position in the epoch's global image sequence)``."""
     import queue
     import threading
     if hasattr(dataset, "preload"):
@@ -225,7 +286,11 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
             break
         if isinstance(b, BaseException):
             raise b
-        lat = b["latents"].to(device, non_blocking=True)
+        if vae is not None and "images" in b:
+            off = ((epoch * 1000003 + i) * world + rank) * batch_size
+            lat = encode_images(vae, b["images"].to(device, non_blocking=True), seed=seed, sample_offset=off)
+        else:
+            lat = b["latents"].to(device, non_blocking=True)
         words = b["words"].to(device, non_blocking=True)
         s_id = b["s_id"].to(device, non_blocking=True)
         ph = b["phosc"].to(device, non_blocking=True) if "phosc" in b else None
