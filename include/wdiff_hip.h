@@ -407,6 +407,28 @@ int wd_ddpm_step_cfg(float* x, const float* first, const float* second, float sc
 /* *t_dev += delta; t64[b] = *t_dev for b < batch (the int64 timesteps vector the UNet takes, train.py:222). */
 int wd_advance_timestep(int32_t* t_dev, int delta, int64_t* t64, int batch, void* stream);
 
+/* One DDIM update (Song et al. 2020, eq. 12) over a subsequence tau of S visited timesteps; k = *k_dev is the index of the
+ * current one, t = *t_dev = tau[k] its timestep.  With a = alpha_hat[tau[k]], p = alpha_hat of the predecessor (tau[k+1];
+ * alpha_hat[0] after the last entry) and sigma = eta * sqrt((1-p)/(1-a)) * sqrt(1 - a/p), the caller tabulates per k
+ *   c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt(p), c4 = sqrt(max(1 - p - sigma^2, 0)), c5 = sigma   (fp32 [S] each)
+ * and the kernel evaluates, every operation rounded to fp32 on its own and in this order (no fma contraction),
+ *   x0 = (x - c1[k] * e) * c2[k];   x = (c3[k] * x0 + c4[k] * e) + c5[k] * z.
+ * e = eps, or torch.lerp(second, eps, scale) when second != NULL, bit for bit as torch's device kernel forms it for any
+ * weight: fma(-(eps - second), 1 - scale, eps) for |scale| >= 0.5, fma(scale, eps - second, second) below - one rounding
+ * each, where wd_ddpm_step_cfg rounds the product and the sum separately (the same value where the product is exact, as
+ * at scale = 3).  eps_out != NULL receives e.
+ * z: read from noise when given, else the draw wd_ddpm_step makes for (seed, sample_offset + sample index, t) - a sample's
+ * noise at timestep t is the DDPM sampler's, whatever the batch size or sharding.  c5[k] == 0 (eta = 0): z is neither read
+ * nor drawn and the term is omitted (not multiplied by zero).  WD_EINVAL: a required pointer is NULL, n_per_sample % 4, or
+ * x / eps / second / noise / eps_out is not 16-byte aligned. */
+int wd_ddim_step(float* x, const float* eps, const float* second, float scale, float* eps_out, int batch, int n_per_sample,
+                 const float* c1, const float* c2, const float* c3, const float* c4, const float* c5, const int32_t* k_dev,
+                 const int32_t* t_dev, const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
+
+/* The table-driven wd_advance_timestep: k = min(*k_dev + 1, S - 1); *k_dev = k; *t_dev = tau[k]; t64[b] = tau[k] for b < batch
+ * (tau int32 [S]).  After the last visited step k stays at S - 1. */
+int wd_next_timestep(int32_t* k_dev, const int32_t* tau, int S, int32_t* t_dev, int64_t* t64, int batch, void* stream);
+
 /* N(0,1) fill with the same Philox stream family (x_T, train.py:217; noise_images eps, train.py:193). */
 int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sample_offset, uint32_t stream_id,
              void* stream);

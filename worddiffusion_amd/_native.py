@@ -142,6 +142,8 @@ _SIGS = {
     "wd_emb_combine_mix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "wd_label_mix": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "wd_ddpm_step_cfg": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "wd_ddim_step": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "wd_next_timestep": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
     "wd_xattn_pair": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f,
                            _vp, _vp, _i, _vp]),
     "wd_add": (_i, [_vp, _vp, C.c_int64, _vp]),

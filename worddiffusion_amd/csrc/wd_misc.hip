@@ -318,6 +318,83 @@ __global__ void ddpm_step_cfg_kernel(float* __restrict__ x, const float* __restr
     }
 }
 
+// torch.lerp(second, first, s) bit for bit for any weight: torch's device kernel is compiled with contraction, so both of its
+// forms, ``second + s * (first - second)`` below 0.5 and ``first - (first - second) * (1 - s)`` from 0.5 on, are ONE fused
+// multiply-add.  lerp_cfg rounds the product and the sum separately, which is the same value only where the product is exact
+// (s = 3 and s = 0.25 are such weights: 1 - s = -2 and s are powers of two).  The fma is spelled out: this file compiles with
+// contraction off.
+__device__ __forceinline__ float lerp_guided(float first, float second, float s, float oms, bool high) {
+    const float d = first - second;
+    return high ? __builtin_fmaf(-d, oms, first) : __builtin_fmaf(s, d, second);
+}
+
+// DDIM update (Song et al. 2020, eq. 12) on the step index k = *k_dev of the visited-timestep tables:
+//   x0 = (x - c1[k] * e) * c2[k];  x = (c3[k] * x0 + c4[k] * e) + c5[k] * z,  every operation rounded on its own;
+// e = eps, or lerp_guided(eps, second, scale) when second != NULL.  c5[k] == 0: no z is read or drawn and the term is omitted.
+__global__ void ddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ second, float scale,
+                                 float* __restrict__ eps_out, int batch, int n4, const float* __restrict__ c1,
+                                 const float* __restrict__ c2, const float* __restrict__ c3, const float* __restrict__ c4,
+                                 const float* __restrict__ c5, const int32_t* __restrict__ k_dev, const int32_t* __restrict__ t_dev,
+                                 const float* __restrict__ noise, uint64_t seed, uint64_t sample_offset) {
+    const int k = *k_dev;
+    const int t = *t_dev;
+    const float a1 = c1[k], a2 = c2[k], a3 = c3[k], a4 = c4[k], sg = c5[k];
+    const float oms = 1.0f - scale;
+    const bool high = fabsf(scale) >= 0.5f;
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        float4 ev = reinterpret_cast<const float4*>(eps)[i];
+        if (second) {
+            const float4 sv = reinterpret_cast<const float4*>(second)[i];
+            ev.x = lerp_guided(ev.x, sv.x, scale, oms, high);
+            ev.y = lerp_guided(ev.y, sv.y, scale, oms, high);
+            ev.z = lerp_guided(ev.z, sv.z, scale, oms, high);
+            ev.w = lerp_guided(ev.w, sv.w, scale, oms, high);
+        }
+        if (eps_out) reinterpret_cast<float4*>(eps_out)[i] = ev;
+        float4 o;
+        o.x = a3 * ((xv.x - a1 * ev.x) * a2) + a4 * ev.x;
+        o.y = a3 * ((xv.y - a1 * ev.y) * a2) + a4 * ev.y;
+        o.z = a3 * ((xv.z - a1 * ev.z) * a2) + a4 * ev.z;
+        o.w = a3 * ((xv.w - a1 * ev.w) * a2) + a4 * ev.w;
+        if (sg != 0.0f) {
+            float4 z;
+            if (noise) z = reinterpret_cast<const float4*>(noise)[i];
+            else {
+                const int b = (int)(i / n4);
+                z = philox_normal4(seed, sample_offset + (uint64_t)b, (uint32_t)t, (uint32_t)(i - (long)b * n4));
+            }
+            o.x = o.x + sg * z.x;
+            o.y = o.y + sg * z.y;
+            o.z = o.z + sg * z.z;
+            o.w = o.w + sg * z.w;
+        }
+        reinterpret_cast<float4*>(x)[i] = o;
+    }
+}
+
+// advance_kernel over a table of visited timesteps: k <- min(k + 1, S - 1), t <- tau[k]
+__global__ void next_timestep_kernel(int32_t* k_dev, const int32_t* __restrict__ tau, int S, int32_t* t_dev, int64_t* t64,
+                                     int batch) {
+    __shared__ int kn, tn;
+    if (threadIdx.x == 0) {
+        int k = *k_dev + 1;
+        if (k > S - 1) k = S - 1;  // the last visited step stays current: nothing is read past the tables
+        if (k < 0) k = 0;
+        kn = k;
+        tn = tau[k];
+    }
+    __syncthreads();
+    const int v = tn;
+    for (int b = threadIdx.x; b < batch; b += blockDim.x) t64[b] = (int64_t)v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *k_dev = kn;
+        *t_dev = v;
+    }
+}
+
 // ---- AutoencoderKL posterior (DiagonalGaussianDistribution of the encoder's moments) --------------------------------
 // One draw for four consecutive elements of a sample, shared by both kernels below:
 //   sample = scale * (mean + exp(0.5 * logvar) * z), every operation rounded on its own (no contraction in this file);
@@ -600,6 +677,28 @@ extern "C" int wd_ddpm_step_cfg(float* x, const float* first, const float* secon
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(ddpm_step_cfg_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, first, second,
                        scale, eps_out, batch, n_per_sample / 4, ca, cb, cs, t_dev, noise, seed, sample_offset);
+    return wd_check_launch();
+}
+
+extern "C" int wd_ddim_step(float* x, const float* eps, const float* second, float scale, float* eps_out, int batch, int n_per_sample,
+                            const float* c1, const float* c2, const float* c3, const float* c4, const float* c5,
+                            const int32_t* k_dev, const int32_t* t_dev, const float* noise, uint64_t seed, uint64_t sample_offset,
+                            void* stream) {
+    if (!x || !eps || !c1 || !c2 || !c3 || !c4 || !c5 || !k_dev || !t_dev || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4)
+        return WD_EINVAL;
+    if (!aligned16(x) || !aligned16(eps) || !aligned16(second) || !aligned16(noise) || !aligned16(eps_out)) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, eps, second, scale,
+                       eps_out, batch, n_per_sample / 4, c1, c2, c3, c4, c5, k_dev, t_dev, noise, seed, sample_offset);
+    return wd_check_launch();
+}
+
+extern "C" int wd_next_timestep(int32_t* k_dev, const int32_t* tau, int S, int32_t* t_dev, int64_t* t64, int batch, void* stream) {
+    if (!k_dev || !tau || !t_dev || !t64 || S <= 0 || batch <= 0) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(next_timestep_kernel, dim3(1), dim3(256), 0, st, k_dev, tau, S, t_dev, t64, batch);
     return wd_check_launch();
 }
 

@@ -171,11 +171,44 @@ class Diffusion:
             self._tables = tuple(t.to(device).contiguous() for t in (ca, cb, cs))
         return self._tables
 
+    def ddim_timesteps(self, steps=None, timesteps=None):
+        """The timesteps a DDIM call visits, strictly decreasing: ``steps`` of them spread evenly over [1, T-1] in integer
+        arithmetic (first T-1, last 1), or the explicit ``timesteps`` after validation.  The predecessor of an entry is the
+        next one; the predecessor of the last is index 0 of the schedule, which is never stepped from (train.py:221)."""
+        T = self.noise_steps
+        if timesteps is not None:
+            tau = [int(t) for t in timesteps]
+            if not tau or any(t < 1 or t > T - 1 for t in tau) or any(a <= b for a, b in zip(tau, tau[1:])):
+                raise ValueError(f"timesteps must be strictly decreasing with every value in [1, {T - 1}]")
+            return tau
+        S = int(steps)
+        if not 1 <= S <= T - 1:
+            raise ValueError(f"steps must be in [1, {T - 1}] for a schedule of {T} noise steps (got {steps})")
+        if S == 1:
+            return [T - 1]
+        return list(reversed([1 + ((T - 2) * k) // (S - 1) for k in range(S)]))
+
+    def _ddim_tables(self, tau, eta, device):
+        """The five per-step coefficients of ``wd_ddim_step`` (fp32 [S] each), with a = alpha_hat[tau[k]], p = alpha_hat of the
+        predecessor and sigma = eta sqrt((1-p)/(1-a)) sqrt(1 - a/p):  c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt(p),
+        c4 = sqrt(max(1 - p - sigma^2, 0)), c5 = sigma.  Evaluated in float64 from the fp32 betas (alpha and its cumprod
+        recomputed in float64: the fp32 ``1 - alpha_hat[0]`` has lost half its digits) and rounded to fp32 once."""
+        ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
+        tau = [int(t) for t in tau]
+        a = ah[tau]
+        p = ah[tau[1:] + [0]]
+        sigma = float(eta) * torch.sqrt((1 - p) / (1 - a)) * torch.sqrt(1 - a / p)
+        c4 = torch.sqrt(torch.clamp(1 - p - sigma * sigma, min=0.0))
+        return tuple(c.float().to(device).contiguous() for c in (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt(p), c4, sigma))
+
     # --------------------------------------------------------------------------------------------------
     def _denoise(self, model, n, text_features, labels, phosc, device, x_T=None, noise=None, seed=None,
                  sample_offset=0, record=None, use_graph=True, calls_model=None, deterministic=False, mix=None,
-                 record_pred=None):
-        """mix = (pairs int32 [nf, T, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
+                 record_pred=None, ddim=None):
+        """ddim = (tau, (c1..c5) on the host, eta): the DDIM loop over the visited timesteps ``tau`` - ``film_prepare(k)`` -> forward(s) ->
+        ``wd_ddim_step`` -> ``wd_next_timestep``, S = len(tau) times; FiLM rows, pairs and ``noise`` are indexed by the step
+        index k (``noise[k]`` is read only where c5[k] != 0).  None: the DDPM loop below, launch for launch as before.
+        mix = (pairs int32 [nf, T, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
         step, forward f of timestep t reading pairs[f, t]; nf = 2 ends the step with the guided update (``wd_ddpm_step_cfg``).
         record_pred: a list that receives, per model-calling step, the predictions of its forwards (and, for nf = 2, the guided
         one) - eager launches only, like ``record``."""
@@ -192,7 +225,14 @@ class Diffusion:
         phosc_len = 0 if phosc is None else phosc.shape[1]
         T = self.noise_steps
         # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
-        P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=T if (self.tabulate_film or nf) else 0, mix=nf)
+        film_steps = T if (self.tabulate_film or nf) else 0
+        if ddim is None:
+            P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf)
+        else:
+            tau, dtab, eta = ddim
+            S = len(tau)
+            P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
+                         film_timesteps=tuple(tau) if film_steps else None)
         fps = nf or self.forwards_per_step
         ca, cb, cs = self._step_tables(device)
         if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
@@ -215,20 +255,36 @@ class Diffusion:
                 eng.load_mix(P, mix[0].to(device), mix[1].to(device), check=False)
             eps_g = torch.empty_like(P.out) if (nf == 2 and record_pred is not None) else None
             t_dev = P.t_dev
-            t_dev.fill_(T - 1)
-            P.t_in.fill_(T - 1)
+            t_first = T - 1 if ddim is None else tau[0]
+            t_dev.fill_(t_first)
+            P.t_in.fill_(t_first)
             zbuf = torch.zeros_like(P.x_in) if noise is not None else None
+            if ddim is not None:
+                stochastic = [v != 0.0 for v in dtab[4].tolist()]  # (host tables: no device sync)
+                c1, c2, c3, c4, c5 = (c.to(device) for c in dtab)
+                tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
+                k_dev = P.k_dev
+                k_dev.zero_()
             P.run_cond(st)
             P.run_film(st)  # time MLP of every timestep; the FiLM rows follow per chunk of timesteps (P.film_prepare)
-            P.film_prepare(T - 1, st)  # before the capture: the captured step only reads the table
+            # before the capture: the captured step only reads the table (its rows are indexed by t, or by the DDIM step index)
+            P.film_prepare(T - 1 if ddim is None else 0, st)
 
             def one_step(stream, forward=True):
                 if forward:
                     for _ in range(1 if nf else fps):
                         P.run_step(stream)
-                if nf == 2:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
-                    if forward:
-                        P.run_step1(stream)
+                if nf == 2 and forward:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
+                    P.run_step1(stream)
+                if ddim is not None:
+                    N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if nf == 2 else None,
+                                             float(mix[2]) if nf == 2 else 0.0, _dptr(eps_g), n, npix, c1.data_ptr(), c2.data_ptr(),
+                                             c3.data_ptr(), c4.data_ptr(), c5.data_ptr(), k_dev.data_ptr(), t_dev.data_ptr(),
+                                             _dptr(zbuf), seed, sample_offset, stream), "wd_ddim_step")
+                    N.check(lib.wd_next_timestep(k_dev.data_ptr(), tau_dev.data_ptr(), S, t_dev.data_ptr(), P.t_in.data_ptr(), n,
+                                                 stream), "wd_next_timestep")
+                    return
+                if nf == 2:
                     N.check(lib.wd_ddpm_step_cfg(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr(), float(mix[2]),
                                                  _dptr(eps_g), n, npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
                                                  t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddpm_step_cfg")
@@ -256,7 +312,21 @@ class Diffusion:
                     gskip = capture(False)  # steps that reuse the previous predicted noise: update only
             k = 0
             ncalls = 0
-            for i in reversed(range(1, T)):
+            for j in range(S if ddim is not None else 0):  # the DDIM loop: step index j, timestep tau[j]
+                if record is not None:
+                    record.append(P.x_in.clone())
+                if zbuf is not None and stochastic[j]:
+                    zbuf.copy_(noise[j].to(device))
+                ncalls += 1
+                if film_steps:
+                    P.film_prepare(j, st)
+                if gexec is not None:
+                    N.check(lib.wd_graph_launch(gexec, st), "wd_graph_launch")
+                else:
+                    one_step(st)
+                if record_pred is not None:
+                    record_pred.append((P.out.clone(),) if nf != 2 else (P.out.clone(), P.out1.clone(), eps_g.clone()))
+            for i in reversed(range(1, T)) if ddim is None else ():
                 if record is not None:
                     record.append(P.x_in.clone())
                 if zbuf is not None and i > 1:
@@ -281,9 +351,11 @@ class Diffusion:
                 lib.wd_graph_destroy(gskip)
         self.last_stats = dict(steps=T - 1, forwards_per_step=fps, graph=gexec is not None,
                                seed=seed, sample_offset=sample_offset, model_calls=ncalls * (nf or 1))
+        if ddim is not None:
+            self.last_stats.update(sampler="ddim", steps=S, eta=float(eta), timesteps=list(tau))
         return x
 
-    def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, calls_model=None):
+    def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, calls_model=None, visited=None):
         """The ``mix`` argument of ``_denoise`` for a sampler call, or None where the call does not interpolate.
 
         Fixed-pair mode (``style_pairs`` given: one ``(s1, s2)`` or an int tensor [n, 2]; ``mix_rate`` a float or fp32 [n]): the
@@ -291,8 +363,10 @@ class Diffusion:
         Reference mode (``model.interpolation`` and a ``mix_rate``): every forward of the reference's loop draws a pair of its own
         (unet.py:1561-1564) - they are drawn here, all of them, in loop order, before anything is launched; with
         ``cfg_scale > 0`` a step runs both forwards and the guided update.
-        Otherwise ``mix_rate`` is ignored, as the reference's forward ignores it (unet.py:1558), and ``random`` is not touched."""
-        T = self.noise_steps
+        Otherwise ``mix_rate`` is ignored, as the reference's forward ignores it (unet.py:1558), and ``random`` is not touched.
+        ``visited`` = S (the DDIM sampler): the table is indexed by the step index, [nf, S, n, 2], and pairs are drawn for the S
+        visited steps only, in loop order."""
+        T = self.noise_steps if visited is None else int(visited)
         if style_pairs is not None:
             if mix_rate is None:
                 raise ValueError("style_pairs needs a mix_rate (a float, or one per sample)")
@@ -301,7 +375,10 @@ class Diffusion:
                 raise ValueError(f"style_pairs must be (s1, s2) or an integer tensor [{n}, 2]")
             tab = sp.to(torch.int32).cpu().reshape(-1, 2).expand(n, 2).reshape(1, 1, n, 2).expand(1, T, n, 2).contiguous()
         elif mix_rate is not None and getattr(model, "interpolation", False):
-            steps = [i for i in reversed(range(1, T)) if calls_model is None or calls_model(i)]
+            if visited is not None:
+                steps = list(range(T))
+            else:
+                steps = [i for i in reversed(range(1, T)) if calls_model is None or calls_model(i)]
             nf = 2 if (cfg_scale > 0 and calls_model is None) else 1
             drawn = draw_style_pairs(nf * len(steps))
             tab = torch.zeros((nf, T, n, 2), dtype=torch.int32)
@@ -373,6 +450,45 @@ class Diffusion:
                               record_pred=record_pred)
         finally:
             model.train()  # train.py:238 (unconditional)
+        return self._finish(x, vae, args)
+
+    @torch.no_grad()
+    def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
+                      phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
+                      use_graph=True, underscore=None, style_pairs=None):
+        """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
+        ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
+        deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
+        noise of a sample at timestep t is the draw ``sampling`` makes there (same Philox key), whatever the batch or sharding.
+        The last step lands on index 0 of the schedule (alpha_hat[0], not 1), the index the reference never steps from.
+        Everything else follows ``sampling``: eval mode for the loop and TRAIN mode afterwards, ``vae=None`` returns latents,
+        ``phoscLabels`` for the PHOSC model, ``mix_rate`` / ``style_pairs`` as there (pairs are drawn for the visited steps
+        only).  ``noise``: one tensor per visited step, read only where sigma != 0; ``record`` / ``record_pred`` as in
+        ``sampling``.  ``last_stats`` carries ``sampler="ddim"``, ``steps``, ``eta`` and ``timesteps``."""
+        tau = self.ddim_timesteps(steps, timesteps)
+        if noise is not None and len(noise) != len(tau):
+            raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
+        device = torch.device(getattr(args, "device", self.device))
+        if device.type != "cuda":
+            raise N.NativeError("Diffusion.sampling_ddim runs on an MI355X only (no CPU fallback)")
+        if self.img_size is None or not (getattr(args, "latent", True) == True):  # noqa: E712
+            raise NotImplementedError("latent=False")
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, visited=len(tau))
+        if underscore is None:
+            underscore = int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE
+        model.eval()
+        tf = self._text_features(x_text, n, underscore)
+        phosc = None
+        if getattr(args, "phosc", 0) == 1 or getattr(args, "phos", 0) == 1:
+            if phoscLabels is None:
+                raise ValueError("args.phosc/phos set but phoscLabels missing")
+            phosc = phoscLabels.int()
+        try:
+            x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_T, noise=noise, seed=seed, sample_offset=sample_offset,
+                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
+                              ddim=(tau, self._ddim_tables(tau, eta, "cpu"), eta))
+        finally:
+            model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
 
     sample = sampling  # sampling.py:119 / full_sampling.py:167 call .sample(...)

@@ -93,17 +93,27 @@ def write_png(path: str, img: np.ndarray) -> None:
         f.write(png)
 
 
+def _check_sampler(sampler: str, skip_steps=False) -> None:
+    if sampler not in ("ddpm", "ddim"):
+        raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+    if sampler == "ddim" and skip_steps:
+        raise ValueError("sampler='ddim' and skip_steps are two ways to run fewer steps: choose one")
+
+
 @torch.no_grad()
 def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: Dict[str, int], args, vae=None,
                batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
-               world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None):
+               world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
+               ddim_steps: int = 50, eta: float = 0.0):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
     ``<image>.png`` (a VAE was given) or ``<image>.npy`` (latents).  ``skip_steps`` selects the step-skipping sampler of
     ``regenerateFromtrain2.py`` (``Diffusion.sampling3``); ``phosc_of(word) -> int tensor [769]`` supplies PHOSC vectors for
     ``UNetModelPhosc`` (``args.phosc == 1``).  ``mix_rate`` is handed to the sampler as ``full_sampling.py:171`` hands it: it has
-    an effect on a model built with ``args.interpolation`` only."""
+    an effect on a model built with ``args.interpolation`` only.  ``sampler="ddim"``: ``Diffusion.sampling_ddim`` over
+    ``ddim_steps`` timesteps with ``eta`` instead of the full ``sampling`` loop."""
+    _check_sampler(sampler, skip_steps)
     r0, w0, _ = env_rank_world()
     rank = r0 if rank is None else rank
     world = w0 if world is None else world
@@ -118,7 +128,9 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         labels = torch.tensor([wr_dict[s] for s, _, _ in chunk], dtype=torch.int64)
         phosc = torch.stack([phosc_of(wd) for wd in words]) if phosc_of is not None else None
         kw = dict(seed=seed, sample_offset=start + b0, mix_rate=mix_rate)
-        if skip_steps:
+        if sampler == "ddim":
+            res = diffusion.sampling_ddim(model, vae, len(chunk), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
+        elif skip_steps:
             res = diffusion.sampling3(0, None, words, phosc, model, model, vae, 0, 1, len(chunk), words, labels, args, **kw)
             res = res if vae is None else res[2]
         else:
@@ -138,10 +150,11 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
 @torch.no_grad()
 def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, style_pair: Tuple[int, int], mix_steps: int = 8,
                 vae=None, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None,
-                phosc_of=None):
+                phosc_of=None, sampler: str = "ddpm", ddim_steps: int = 50, eta: float = 0.0):
     """One interpolation strip per gt row (this rank's shard of them): the row's word sampled ``mix_steps`` times in one call,
     sample j with the writer embedding ``(1 - m_j) * label[s1] + m_j * label[s2]``, ``m = linspace(0, 1, mix_steps)``
-    (``Diffusion.sampling(..., style_pairs=)``, one forward per step).  Sample j of row r is global sample ``r * mix_steps + j``
+    (``Diffusion.sampling(..., style_pairs=)``, one forward per step; ``sampler="ddim"``: ``sampling_ddim`` over ``ddim_steps``
+    timesteps with ``eta``).  Sample j of row r is global sample ``r * mix_steps + j``
     of the noise stream, whatever the sharding.
 
     Returns ``(start, [mix_steps, ...] tensor per row)``.  With ``out_dir``, ``<image>_interp.png`` is written per row: the
@@ -149,6 +162,7 @@ def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, st
     grey preview of them (per sample the 4 channels stacked, min-max scaled over the strip)."""
     if mix_steps < 2:
         raise ValueError("mix_steps must be at least 2 (the two writers themselves)")
+    _check_sampler(sampler)
     r0, w0, _ = env_rank_world()
     rank = r0 if rank is None else rank
     world = w0 if world is None else world
@@ -161,8 +175,11 @@ def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, st
     for r in range(start, start + count):
         _, image, word = rows[r]
         phosc = torch.stack([phosc_of(word)] * mix_steps) if phosc_of is not None else None
-        res = diffusion.sampling(model, vae, mix_steps, word, labels, args, mix_rate=m, phoscLabels=phosc, seed=seed,
-                                 sample_offset=r * mix_steps, style_pairs=tuple(int(s) for s in style_pair)).detach().cpu()
+        kw = dict(mix_rate=m, phoscLabels=phosc, seed=seed, sample_offset=r * mix_steps, style_pairs=tuple(int(s) for s in style_pair))
+        if sampler == "ddim":
+            res = diffusion.sampling_ddim(model, vae, mix_steps, word, labels, args, steps=ddim_steps, eta=eta, **kw).detach().cpu()
+        else:
+            res = diffusion.sampling(model, vae, mix_steps, word, labels, args, **kw).detach().cpu()
         outs.append(res)
         if out_dir is None:
             continue
@@ -181,12 +198,8 @@ def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, st
     return start, outs
 
 
-def main(argv=None):
-    """``python -m worddiffusion_amd.driver --gt_train gt.txt --models_path run/ --save_path out/`` (one process per GPU under
-    torchrun; flags follow ``full_sampling.py:40-66`` where they exist)."""
-    import copy
-    import types
-    from . import Diffusion, UNetModel, UNetModelPhosc
+def build_parser() -> argparse.ArgumentParser:
+    """The command line of ``main`` (flags follow ``full_sampling.py:40-66`` where they exist); needs no device."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gt_train", required=True)
     ap.add_argument("--models_path", default=None, help="directory holding models/ema_ckpt.pt (reference layout)")
@@ -203,6 +216,10 @@ def main(argv=None):
     ap.add_argument("--vocab_size", type=int, default=53, choices=[53, 54],
                     help="53: the 52-letter alphabet of train.py; 54: the '_' alphabet of trainModifyCondition.py:68")
     ap.add_argument("--skip_steps", type=int, default=0, help="1: regenerateFromtrain2.py's step-skipping sampler")
+    ap.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"],
+                    help="ddpm: every one of the noise_steps - 1 steps (train.py:221); ddim: --ddim_steps of them (Song et al. 2020)")
+    ap.add_argument("--ddim_steps", type=int, default=50, help="--sampler ddim: UNet evaluations per image")
+    ap.add_argument("--eta", type=float, default=0.0, help="--sampler ddim: 0 deterministic .. 1 the DDPM posterior variance")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--interpolation", type=bool, nargs="?", const=True, default=False,
                     help="args.interpolation of the reference (sampling.py:64; any value is true, as there): with --mix_rate "
@@ -221,7 +238,26 @@ def main(argv=None):
     ap.add_argument("--latents_out", default=None, metavar="FILE", help="--encode_images: the container to write (.safetensors / .npz)")
     ap.add_argument("--latent_mode", default="sample", choices=["sample", "mode"],
                     help="--encode_images: a posterior draw per image (keyed by --seed and the row index) or the posterior mean")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.sampler == "ddim" and a.skip_steps:
+        ap.error("--sampler ddim and --skip_steps 1 are two ways to run fewer steps: choose one")
+    if a.sampler == "ddim" and not 1 <= a.ddim_steps <= a.noise_steps - 1:
+        ap.error(f"--ddim_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    return ap, a
+
+
+def main(argv=None):
+    """``python -m worddiffusion_amd.driver --gt_train gt.txt --models_path run/ --save_path out/`` (one process per GPU under
+    torchrun)."""
+    import copy
+    import types
+    from . import Diffusion, UNetModel, UNetModelPhosc
+    ap, a = parse_args(argv)
     rank, world, local = env_rank_world()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
@@ -259,12 +295,13 @@ def main(argv=None):
         phosc_of = make_phosc_of(a.alphabet_csv)
     if a.style_pair is not None:
         start, res = interpolate(ema_model, diffusion, rows, args, tuple(a.style_pair), a.mix_steps, vae=vae,
-                                 out_dir=os.path.join(a.save_path, "images"), seed=a.seed, phosc_of=phosc_of)
+                                 out_dir=os.path.join(a.save_path, "images"), seed=a.seed, phosc_of=phosc_of, sampler=a.sampler,
+                                 ddim_steps=a.ddim_steps, eta=a.eta)
         print(f"[rank {rank}/{world}] strips of rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
         return
     start, res = regenerate(ema_model, diffusion, rows, wr, args, vae=vae, batch=a.batch_size,
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
-                            phosc_of=phosc_of, mix_rate=a.mix_rate)
+                            phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta)
     print(f"[rank {rank}/{world}] rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
 
 

@@ -1268,7 +1268,8 @@ class UNetEngine:
         return a
 
     # ------------------------------------------------------------------------------------------ plan
-    def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0) -> Plan:
+    def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0,
+             film_timesteps: Optional[tuple] = None) -> Plan:
         """film_steps = T > 0 (the DDPM sampler): the whole time / writer embedding path (timestep_embedding, time_embed,
         label_emb, SiLU, every emb_layers) is tabulated for all T timesteps by ``P.film`` ops - one large GEMM per
         ``sampling()`` call instead of three 64-row GEMMs per step - and each step copies its rows (``wd_select_rows``).
@@ -1276,8 +1277,17 @@ class UNetEngine:
         mix > 0 (writer-style interpolation, unet.py:1558-1573): the label term of a sample is the blend of a pair of writers
         (``P.pairs`` / ``P.mix_m``, filled by ``load_mix``) instead of ``label[y]``.  With the table, ``mix`` is the number of
         forwards per step (1 or 2) that read rows of their own - pairs indexed (forward, t, b); ``P.step`` reads the rows of
-        forward 0 and writes ``P.out``, ``P.step1`` (mix = 2) those of forward 1 and writes ``P.out1``."""
+        forward 0 and writes ``P.out``, ``P.step1`` (mix = 2) those of forward 1 and writes ``P.out1``.
+
+        film_timesteps = tau (the DDIM sampler, with film_steps = T): the table covers the S visited timesteps only - row k is
+        timestep tau[k], ``P.film_prepare`` takes the step index k, ``wd_select_rows`` reads it from ``P.k_dev`` and the pairs
+        of the interpolation path are indexed (forward, k, b)."""
         key = (B, H, W, ctx_len, phosc_len, self.npass, film_steps) + ((("mix", mix),) if mix else ())
+        if film_timesteps is not None:
+            film_timesteps = tuple(int(t) for t in film_timesteps)
+            if not film_steps or not film_timesteps or min(film_timesteps) < 0 or max(film_timesteps) >= film_steps:
+                raise ValueError("film_timesteps needs film_steps = T and timesteps in [0, T)")
+            key += (("tau", film_timesteps),)
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)  # most recently used last
             return self._plans[key]
@@ -1345,6 +1355,7 @@ class UNetEngine:
             P.mix_m = torch.zeros((B,), dtype=torch.float32, device=dev)
         self._film = self._f32(P, B, self.film_total)
         P.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
+        P.k_dev = torch.zeros((1,), dtype=torch.int32, device=dev)  # index into film_timesteps (the table-driven loop)
         P.film = []
         if film_steps:
             # the table holds ``chunk`` consecutive timesteps (rows (t % chunk) * B + b), not all T: T*B*film_total fp32 was
@@ -1352,13 +1363,17 @@ class UNetEngine:
             # B.  The time MLP (T rows, cheap) is still evaluated for every t once per call (P.film); the SiLU(time + label)
             # planes and the emb_layers GEMM of a chunk run when the loop enters it (P.film_prepare, same stream, a fraction
             # of one step each).
-            T = film_steps
+            T = film_steps if film_timesteps is None else len(film_timesteps)  # rows of the table: all t, or the visited ones
             nf = max(1, mix)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
-            chunk = min(T, max(8, FILM_CHUNK_ROWS // (B * nf)))
+            # (a table over all t keeps at least 8 timesteps resident; one over the visited steps is cut by rows alone)
+            chunk = min(T, max(8 if film_timesteps is None else 1, FILM_CHUNK_ROWS // (B * nf)))
             nchunks = (T + chunk - 1) // chunk
             Tp = nchunks * chunk
             film = P.film
-            tt = torch.arange(Tp, dtype=torch.int64, device=dev)
+            if film_timesteps is None:
+                tt = torch.arange(Tp, dtype=torch.int64, device=dev)
+            else:  # row k holds timestep tau[k]; the padding rows repeat the last one and are never selected
+                tt = torch.tensor(film_timesteps + (film_timesteps[-1],) * (Tp - T), dtype=torch.int64, device=dev)
             P.keep.append(tt)
             te = self._planes(P, Tp, mc)
             film.append((lib.wd_timestep_embedding, (tt.data_ptr(), Tp, self._w["freqs"].data_ptr(), mc // 2, te[0].data_ptr(),
@@ -1400,10 +1415,11 @@ class UNetEngine:
                 return True
 
             P.film_prepare = film_prepare
-            step.append((lib.wd_select_rows, (P.film_table.data_ptr(), P.t_dev.data_ptr(), B, self.film_total, chunk,
+            row_dev = P.t_dev if film_timesteps is None else P.k_dev
+            step.append((lib.wd_select_rows, (P.film_table.data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
                                               self._film.data_ptr()), "film rows of step t"))
             if mix == 2:
-                select1 = (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), P.t_dev.data_ptr(), B, self.film_total, chunk,
+                select1 = (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
                                                 self._film.data_ptr()), "film rows of step t, second forward")
         else:
             if mix:
