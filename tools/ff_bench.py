@@ -2,6 +2,10 @@
 """Micro-benchmark of wd_ff_fused at the 8x32 level of the headline batch (run on the GPU box).
 
     python tools/ff_bench.py [--proj 1] [--iters 30]        WDIFF_LIB=<other .so> for A/B builds of the kernel
+    python tools/ff_bench.py --front 1 [--m 16384 | --m 64]  the launch with the transformer front (GroupNorm + proj_in + both
+                                                             cross-attentions + norm3 ahead of the feed-forward), random block of
+                                                             tests/test_gpu_st_fused.py: the full chip (m = 16384: 256 panels) or
+                                                             one workgroup alone (m = 64: one sample of 64 tokens)
 """
 import argparse
 import ctypes as C
@@ -22,12 +26,52 @@ def planes(x):
     return torch.stack([hi, (x - hi.float()).to(torch.bfloat16)], 0).contiguous()
 
 
+def timed(launch, iters):
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        launch()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / iters
+
+
+def front(m, iters):
+    from tests.test_gpu_st_fused import _Block  # the seeded transformer block the fused launch is tested on
+    if m % 256 == 0:
+        blk = _Block(m // 256)
+    elif m == 64:  # one panel: the same block as one sample of 64 tokens
+        blk = _Block(1)
+        blk.hw = blk.m = 64
+        blk.x = blk.x[:64].contiguous()
+        blk.nchunk = blk.lib.wd_gn_nchunk(64)
+        blk.part = torch.zeros(1, blk.nchunk, 32, 2, dtype=torch.float64, device=DEV)
+        N.check(blk.lib.wd_gn_stats(blk.x.data_ptr(), blk.c, 1, 64, blk.c, blk.c // 32, blk.part.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream), "stats")
+    else:
+        sys.exit("--front: m is a multiple of 256 (samples of 8 x 32 tokens) or 64 (one workgroup)")
+    out = torch.empty(blk.m, blk.c, device=DEV)
+    stat = torch.empty(blk.B, blk.hw // 64, 32, 2, dtype=torch.float64, device=DEV)
+    tok2 = torch.empty(blk.m, blk.c, device=DEV)
+    f = blk.fused_args(out, stat, tok2)
+    st = torch.cuda.current_stream().cuda_stream
+    N.check(blk.lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused (front)")
+    us = timed(lambda: blk.lib.wd_ff_fused(C.byref(f), st), iters)
+    print(f"wd_ff_fused front m={blk.m} ({blk.m // 64} workgroups): {us:7.1f} us   lib {N.LIB_PATH}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--proj", type=int, default=1)
+    ap.add_argument("--front", type=int, default=0)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--m", type=int, default=16384)
     a = ap.parse_args()
+    if a.front:
+        return front(a.m, a.iters)
     lib = N.lib()
     st = torch.cuda.current_stream().cuda_stream
     m, c, inner = a.m, 320, 1280
@@ -60,16 +104,8 @@ def main():
         f.w3_hi, f.w3_lo, f.b3 = w3f[0].data_ptr(), w3f[1].data_ptr(), b3.data_ptr()
         f.resid3, f.resid3_ld = res3.data_ptr(), c
     f.hw_out, f.npass = 1, 3
-    for _ in range(3):
-        N.check(lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused")
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
-        lib.wd_ff_fused(C.byref(f), st)
-    e1.record()
-    torch.cuda.synchronize()
-    us = 1e3 * e0.elapsed_time(e1) / a.iters
+    N.check(lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused")
+    us = timed(lambda: lib.wd_ff_fused(C.byref(f), st), a.iters)
     fl = 2.0 * m * (3.0 * inner * c + (c * c if a.proj else 0))
     print(f"wd_ff_fused m={m} proj={a.proj}: {us:7.1f} us  {fl / us / 1e6:6.1f} TF/s algorithmic ({3 * fl / us / 1e6:6.1f} MFMA)   lib {N.LIB_PATH}")
 

@@ -149,30 +149,14 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         float* s_aff = reinterpret_cast<float*>(fr);               // [FC][2] GroupNorm scale / shift of the sample (staging only)
         float* sS = reinterpret_cast<float*>(fr);                  // [FBM][SP] scores
         wd_bf16* sP = reinterpret_cast<wd_bf16*>(fr + FBM * SP * 4);  // [2][FBM][PP] probability planes, padding columns 0
-        // ---- GroupNorm (affine folded per channel) from the producer's partials, as wd_gemmw_kernel<..., A32>
-        {
-            const int ngp = FC / a.gn_pcpg, ratio = a.gn_cpg / a.gn_pcpg;
-            for (int c = tid; c < FC; c += FNT) {
-                const int g = c / a.gn_cpg;
-                double su = 0.0, sq = 0.0;
-                for (int k = 0; k < ratio; ++k)
-                    for (int ck = 0; ck < a.gn_nchunk; ++ck) {
-                        const double* pp = a.gn_part + (((long)b * a.gn_nchunk + ck) * ngp + g * ratio + k) * 2;
-                        su += pp[0];
-                        sq += pp[1];
-                    }
-                const double n = (double)a.hw * a.gn_cpg;
-                const double mu = su / n;
-                double var = sq / n - mu * mu;
-                if (var < 0.0) var = 0.0;
-                const float rstd = (float)(1.0 / sqrt(var + (double)a.gn_eps));
-                const float sc = rstd * a.gn_gamma[c];
-                s_aff[2 * c] = sc;
-                s_aff[2 * c + 1] = a.gn_beta[c] - (float)mu * sc;
-            }
-            for (int e = tid; e < FBM * PP; e += FNT) reinterpret_cast<uint32_t*>(sP)[e] = 0u;
-        }
-        // ---- the panel's input rows (thread: row, 8 channels of each slab), then the first proj_in groups into the ring
+        // the per-channel vectors of the phases below, staged once: 7 x FC floats behind the front's scratch, inside the second h
+        // image (which the chunk loop first writes in chunk 1, long after norm3 has read them)
+        float* s_vec = reinterpret_cast<float*>(s_h + 40960);
+        const float* s_pib = s_vec;
+        const float* s_ln2g = s_vec + FC, * s_ln2b = s_vec + 2 * FC, * s_ln3g = s_vec + 3 * FC, * s_ln3b = s_vec + 4 * FC;
+        const float* s_xba = s_vec + 5 * FC, * s_xbb = s_vec + 6 * FC;
+        // ---- every request of the prologue goes out before anything waits: the panel's input rows (thread: row, 8 channels of
+        // each slab), the first proj_in groups into the ring, the staged vectors and b1 - none depends on the GroupNorm table
         const int arow = tid >> 3, ach = tid & 7;
         float4 xv[5][2];
         {
@@ -192,6 +176,71 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         };
 #pragma unroll
         for (int g = 0; g < FRING; ++g) issue_pi(g, g);
+        // (wave v < 7 takes vector v: FC / 4 = 80 float4s, lane: its own and 64 + lane % 16, the same value from four lanes)
+        const int sv = wave < 7 ? wave : 6;
+        const float* vsrc = sv == 0 ? a.pi_b : sv == 1 ? a.ln2_gamma : sv == 2 ? a.ln2_beta : sv == 3 ? a.ln3_gamma : sv == 4 ? a.ln3_beta
+                            : sv == 5 ? a.xb_a : a.xb_b;
+        const float4 vst0 = *reinterpret_cast<const float4*>(vsrc + lane * 4);
+        const float4 vst1 = *reinterpret_cast<const float4*>(vsrc + (64 + l15) * 4);
+        constexpr int NB1 = 2 * F_MAX_INNER / FNT;                 // b1: units past 2 * inner (or all, without a bias) read as 0
+        float b1v[NB1];
+        {
+            const __amdgpu_buffer_rsrc_t sb1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.b1), 0, a.b1 ? 2 * a.inner * 4 : 0, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < NB1; ++k)
+                b1v[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(sb1, (uint32_t)(tid + k * FNT) * 4u, 0, 0));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        for (int e = tid; e < FBM * PP; e += FNT) reinterpret_cast<uint32_t*>(sP)[e] = 0u;
+        // ---- GroupNorm (affine folded per channel) from the producer's partials, as wd_gemmw_kernel<..., A32>
+        {
+            const int ngp = FC / a.gn_pcpg, ratio = a.gn_cpg / a.gn_pcpg;
+            for (int c = tid; c < FC; c += FNT) {
+                const int g = c / a.gn_cpg;
+                const float gam = a.gn_gamma[c], bet = a.gn_beta[c];
+                // the partials of the group, k outer and chunk inner as wd_gemmw_kernel sums them, but requested eight at a time
+                // (a term past the end re-reads the batch's first and is not added): one wait per batch, not one per term
+                double su = 0.0, sq = 0.0;
+                const int nterm = ratio * a.gn_nchunk;
+                int k = 0, ck = 0;
+                for (int t0 = 0; t0 < nterm; t0 += 8) {
+                    const int k0 = k, ck0 = ck;
+                    double2 pv[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const bool live = t0 + u < nterm;
+                        const int kk = live ? k : k0, cc = live ? ck : ck0;
+                        pv[u] = *reinterpret_cast<const double2*>(a.gn_part + (((long)b * a.gn_nchunk + cc) * ngp + g * ratio + kk) * 2);
+                        if (++ck == a.gn_nchunk) {
+                            ck = 0;
+                            ++k;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (t0 + u < nterm) {
+                            su += pv[u].x;
+                            sq += pv[u].y;
+                        }
+                }
+                const double n = (double)a.hw * a.gn_cpg;
+                const double mu = su / n;
+                double var = sq / n - mu * mu;
+                if (var < 0.0) var = 0.0;
+                const float rstd = (float)(1.0 / sqrt(var + (double)a.gn_eps));
+                const float sc = rstd * gam;
+                s_aff[2 * c] = sc;
+                s_aff[2 * c + 1] = bet - (float)mu * sc;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (wave < 7) {
+            *reinterpret_cast<float4*>(s_vec + sv * FC + lane * 4) = vst0;
+            *reinterpret_cast<float4*>(s_vec + sv * FC + (64 + l15) * 4) = vst1;
+        }
+#pragma unroll
+        for (int k = 0; k < NB1; ++k)
+            if (tid + k * FNT < 2 * a.inner) s_b1[tid + k * FNT] = b1v[k];
         __syncthreads();
         // ---- y = x * scale + shift -> split-bf16 planes of the resident rows
 #pragma unroll
@@ -241,7 +290,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
             for (int i = 0; i < 5; ++i) {
                 const int n = (l15 + 16 * i) * 4, row = wave * 8 + pp * 4 + lq;
                 const float4 v = *reinterpret_cast<const float4*>(ep + row * LDE + n);
-                const float4 bx = *reinterpret_cast<const float4*>(a.pi_b + n);
+                const float4 bx = *reinterpret_cast<const float4*>(s_pib + n);
                 xr[pp][i] = make_float4(v.x + bx.x, v.y + bx.y, v.z + bx.z, v.w + bx.w);
             }
         __syncthreads();  // the image is read: the planes go over it
@@ -282,24 +331,26 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         // group w & 3 of the output, both for the row tiles 2 (w >> 2) and 2 (w >> 2) + 1
         const int ht = wave & 3, rp = wave >> 2;
         const long pq = 64L * FC;                                  // elements of one plane of one sample's folded matrix
+        // the score operand depends only on the sample and the attention: requested a phase ahead (attention 1: here, acc2 is
+        // dead; attention 2: after attention 1's output product, when mh / ml are dead), it lands under the LayerNorm
+        bf16x8 bh[KS32], bl[KS32];
+        auto issue_mq = [&](const wd_bf16* mq) {
+            const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(mq + (long)b * 2 * pq), 0,
+                                                                                (int)(2 * pq * 2), 0x00020000);
+            const uint32_t vo = ht * 16 + l15 < HJ ? lane16 : F_OOB;
+#pragma unroll
+            for (int ks = 0; ks < KS32; ++ks) {
+                bh[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)((ht * KS32 + ks) << 10), 0));
+                bl[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)(((ht * KS32 + ks) << 10) + pq * 2), 0));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        issue_mq(a.mq_a);
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
-            const wd_bf16* mq = ps == 0 ? a.mq_a : a.mq_b;
             const wd_bf16* mot = ps == 0 ? a.mot_a : a.mot_b;
-            const float* xb = ps == 0 ? a.xb_a : a.xb_b;
-            ln_rows(a.ln2_gamma, a.ln2_beta);  // (norm2 for both attentions, unet.py:337-345)
-            __builtin_amdgcn_sched_barrier(0);
-            bf16x8 bh[KS32], bl[KS32];
-            {
-                const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(mq + (long)b * 2 * pq), 0,
-                                                                                    (int)(2 * pq * 2), 0x00020000);
-                const uint32_t vo = ht * 16 + l15 < HJ ? lane16 : F_OOB;
-#pragma unroll
-                for (int ks = 0; ks < KS32; ++ks) {
-                    bh[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)((ht * KS32 + ks) << 10), 0));
-                    bl[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, vo, (uint32_t)(((ht * KS32 + ks) << 10) + pq * 2), 0));
-                }
-            }
+            const float* xb = ps == 0 ? s_xba : s_xbb;
+            ln_rows(s_ln2g, s_ln2b);  // (norm2 for both attentions, unet.py:337-345)
             __syncthreads();
             // ---- scores S[token][hj] = LN(x) . Mq^T, three split products in independent accumulators
             if (ht * 16 < HJ) {
@@ -348,12 +399,32 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
                 const int t = idx / a.heads, h = idx - t * a.heads;
                 const float* pr = sS + t * SP + h * a.L;
                 wd_bf16* ph = sP + t * PP + h * a.L;
+                // the first 10 keys stay in registers, each exponential evaluated once (a key past L re-reads the last one: no
+                // effect on the maximum, not added, not stored); the sums run in key order as before
+                float ex[10];
+#pragma unroll
+                for (int j = 0; j < 10; ++j) ex[j] = pr[j < a.L ? j : a.L - 1];
                 float mx = -3.4e38f;
-                for (int j = 0; j < a.L; ++j) mx = fmaxf(mx, pr[j]);
+#pragma unroll
+                for (int j = 0; j < 10; ++j) mx = fmaxf(mx, ex[j]);
+                for (int j = 10; j < a.L; ++j) mx = fmaxf(mx, pr[j]);
                 float sum = 0.f;
-                for (int j = 0; j < a.L; ++j) sum += __expf(pr[j] - mx);
+#pragma unroll
+                for (int j = 0; j < 10; ++j) {
+                    ex[j] = __expf(ex[j] - mx);
+                    sum += j < a.L ? ex[j] : 0.f;
+                }
+                for (int j = 10; j < a.L; ++j) sum += __expf(pr[j] - mx);
                 const float inv = __fdividef(1.f, sum);
-                for (int j = 0; j < a.L; ++j) {
+#pragma unroll
+                for (int j = 0; j < 10; ++j)
+                    if (j < a.L) {
+                        uint32_t hi, lo;
+                        wd_split1(ex[j] * inv, hi, lo);
+                        ph[j] = (wd_bf16)hi;
+                        ph[FBM * PP + j] = (wd_bf16)lo;
+                    }
+                for (int j = 10; j < a.L; ++j) {
                     uint32_t hi, lo;
                     wd_split1(__expf(pr[j] - mx) * inv, hi, lo);
                     ph[j] = (wd_bf16)hi;
@@ -391,6 +462,15 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ep[((2 * rp + ri) * 16 + 4 * lq + r) * LDE + (5 * cg + t) * 16 + l15] = o[ri][t][r];
             }
+            // mh / ml / o are dead: the second attention's score operand, or (the ring is free since proj_in) the first groups of
+            // chunk 0, which land under the residual add, the tok2 stores and norm3
+            if (ps == 0) {
+                issue_mq(a.mq_b);
+            } else {
+#pragma unroll
+                for (int g = 0; g < FRING; ++g) issue(g, g, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             __syncthreads();
             // ---- + bias + residual (the rows are still in registers)
 #pragma unroll
@@ -406,17 +486,13 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
             __syncthreads();  // the image is read: the next planes go over it
         }
         // ---- tok2 -> its scratch (the residual of the feed-forward, read back by this same wave in the x' step), norm3 -> the
-        // resident rows, b1 -> LDS, then the first groups of chunk 0 into the ring
+        // resident rows
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
             for (int i = 0; i < 5; ++i)
                 *reinterpret_cast<float4*>(a.tok2 + (long)(m0 + wave * 8 + pp * 4 + lq) * FC + (l15 + 16 * i) * 4) = xr[pp][i];
-        ln_rows(a.ln3_gamma, a.ln3_beta);
-        for (int i = tid; i < 2 * a.inner; i += FNT) s_b1[i] = a.b1 ? a.b1[i] : 0.0f;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < FRING; ++g) issue(g, g, 0);
+        ln_rows(s_ln3g, s_ln3b);
     } else {
     // the first FRING groups go out before anything else (they have the whole prologue to land)
 #pragma unroll
