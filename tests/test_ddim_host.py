@@ -1,6 +1,6 @@
 """Host side of the DDIM sampler: the visited-timestep schedule, the coefficient tables against their float64 restatement
-(``tests/_ddim_ref.py``), the identity with the reference-pinned DDPM update at S = T-1, eta = 1, the bound symbols and the
-driver's command line.  No GPU."""
+(``tests/_ddim_ref.py``), the identity with the reference-pinned DDPM update at S = T-1, eta = 1, what every sampler's description hands the one
+reverse loop, the bound symbols and the driver's command line.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -78,6 +78,60 @@ def test_full_sequence_eta1_is_the_ddpm_mean(T):
         worst = max(worst, float((got.double() - ref).abs().max() / ref.abs().max()))
     print(f"DDIM(S = T-1, eta = 1) against the DDPM mean, T = {T}: max_rel {worst:.3e}")
     assert worst < 1e-5
+
+
+def test_visited_steps_restate_the_reference_loops():
+    """``Diffusion._ddpm`` / ``_ddim`` describe the steps the one reverse loop visits - (film_prepare argument, calls the model,
+    entry of ``noise`` or None) - against the loops themselves, written out: train.py:221-236 (``for i in reversed(range(1,
+    T))``, a fresh ``randn`` while i > 1), regenerateFromtrain2.py:532-620 (the same loop, the model behind the predicate of
+    :536, the draw made on every step) and the DDIM loop over tau (a draw only where sigma != 0)."""
+    T = 12
+    d = Diffusion(noise_steps=T)
+
+    def ddpm_loop(calls):
+        want, drawn = [], 0
+        for i in reversed(range(1, T)):
+            z = None
+            if i > 1:
+                z, drawn = drawn, drawn + 1
+            want.append((i, calls(i), z))
+        return want
+
+    s = d._ddpm()
+    assert s.steps == ddpm_loop(lambda i: True) and (s.t_first, s.tau) == (11, None)
+    assert [a for a, _, _ in s.steps] == list(range(11, 0, -1)) and all(f for _, f, _ in s.steps)
+    assert [z for _, _, z in s.steps] == list(range(10)) + [None]
+    s3 = d._ddpm(lambda i: Diffusion.sampling3_calls_model(i, T, 0), deterministic=True)
+    assert s3.steps == ddpm_loop(lambda i: Diffusion.sampling3_calls_model(i, T, 0)) and (s3.t_first, s3.tau) == (11, None)
+    assert [a for a, f, _ in s3.steps if f] == [11, 10, 5]
+    assert [z for _, _, z in s3.steps] == list(range(10)) + [None]  # counted on the skipped steps too
+    assert s.stats == s3.stats == dict(steps=T - 1)  # the updates, not the model calls
+    # the pairs of an interpolating call are drawn for the model-calling steps of that same list, in loop order
+    import random
+    import types
+    from worddiffusion_amd.diffusion import draw_style_pairs
+    random.seed(5)
+    tab, _, _ = d._mix_setup(types.SimpleNamespace(interpolation=True), 2, 0.37, None, 0, sampler=s3)
+    after = random.getstate()
+    random.seed(5)
+    pairs = draw_style_pairs(3)
+    assert random.getstate() == after and tab.shape == (1, T, 2, 2)
+    assert [tuple(tab[0, i, 0].tolist()) for i in (11, 10, 5)] == pairs and not tab[0, [9, 8, 7, 6, 4, 3, 2, 1, 0]].any()
+
+    d8 = Diffusion(noise_steps=8)
+    tau = [7, 4, 1]
+    for eta in (0.0, 1.0):
+        c5 = d8._ddim_tables(tau, eta, "cpu")[4]
+        want = []
+        for j in range(len(tau)):
+            want.append((j, True, j if float(c5[j]) != 0 else None))
+        sd = d8._ddim(tau, eta)
+        assert sd.steps == want and (sd.t_first, sd.tau) == (7, tau)
+        assert sd.stats == dict(sampler="ddim", steps=3, eta=eta, timesteps=tau)
+        if eta == 0.0:
+            assert [z for _, _, z in sd.steps] == [None] * 3
+        else:
+            assert [z for _, _, z in sd.steps] == [0, 1, 2]  # sigma > 0 at every step, the last (predecessor: index 0) included
 
 
 def test_ddim_symbols_are_declared_and_bound():

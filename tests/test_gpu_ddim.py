@@ -250,6 +250,16 @@ def test_graph_replay_equals_eager_over_a_chunked_visited_step_table(monkeypatch
     assert torch.equal(outs[0], outs[1])
     assert torch.equal(outs[0], default)
     assert torch.isfinite(default).all() and float(default.std()) > 0
+    # without the table (time MLP + emb_layers inside every step): graph == eager as well, and the tabulated result to the bar
+    # ``test_film_table_chunks_equal_the_per_step_path`` holds the same two paths to under ``sampling``
+    diff.tabulate_film = False
+    mp = _model(UNetModel, SMALL, 9)
+    per_step = [diff.sampling_ddim(mp, None, n, "text", labels, args, use_graph=g, **kw) for g in (True, False)]
+    assert getattr(next(iter(mp.engine._plans.values())), "film_nchunks", 0) == 0 and not diff.last_stats["graph"]
+    assert torch.equal(per_step[0], per_step[1])
+    err = max_rel(per_step[0].cpu(), default.cpu())
+    print(f"ddim without the FiLM table against the tabulated result: max_rel {err:.3e}")
+    assert err < 1e-5
 
 
 # ------------------------------------------------------------------------------------------------ 7. determinism and sharding

@@ -275,6 +275,36 @@ def test_interpolation_graph_replay_equals_eager_launches(monkeypatch, mode):
     assert not torch.equal(diff.sampling(m, None, 3, "text", labels, args, **kw), outs[0])
 
 
+def test_sampling3_step_skipping_draws_one_pair_per_model_call(monkeypatch):
+    """``sampling3`` on a model built with args.interpolation, same shapes: the skipped steps run the update alone (the second
+    captured graph), call no model and draw no pair."""
+    from worddiffusion_amd import engine
+    monkeypatch.setattr(engine, "FILM_CHUNK_ROWS", 8)
+    T = 12
+    args = make_args(device=DEV, interpolation=True, fullSampling=False)
+    m = _model(UNetModelPhosc, CFG, 9, interpolation=True)
+    diff = Diffusion(noise_steps=T, img_size=(32, 64), args=args)
+    labels = torch.tensor([4, 5, 6], dtype=torch.int64)
+    calls = [i for i in reversed(range(1, T)) if Diffusion.sampling3_calls_model(i, T, 0)]
+    assert calls == [11, 10, 5]
+
+    def run(mix_rate, use_graph=True):
+        random.seed(31)
+        out = diff.sampling3(0, None, ["text"] * 3, None, m, m, None, 0, 1, 3, "text", labels, args, mix_rate=mix_rate,
+                             seed=21, use_graph=use_graph)
+        assert diff.last_stats["graph"] == use_graph
+        assert diff.last_stats["model_calls"] == len(calls) and diff.last_stats["forwards_per_step"] == 1
+        return out, random.getstate()
+
+    (graph, after), (eager, after_eager) = run(0.37), run(0.37, use_graph=False)
+    assert torch.equal(graph, eager)
+    assert torch.isfinite(graph).all() and float(graph.std()) > 0
+    random.seed(31)
+    draw_style_pairs(len(calls))
+    assert after == after_eager == random.getstate()
+    assert not torch.equal(run(0.9)[0], graph)
+
+
 # ------------------------------------------------------------------------------------------------ 6. fixed pairs
 def test_fixed_pair_strip_properties_full_config():
     """B = 11 mix rates from 0 to 1 between two chosen writers, one word, on the FULL base config (interpolation not set)."""

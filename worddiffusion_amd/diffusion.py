@@ -1,9 +1,11 @@
 """``Diffusion`` / ``EMA`` / ``label_padding`` with the reference's call surface (``train.py:42-52,140-251``).
 
-The reverse loop of ``Diffusion.sampling`` (``train.py:221-236``) runs entirely on the device: the step-invariant
-conditioning (word embedding, cross-attention K/V) is computed once, one denoising step (UNet forward + the
-``x <- 1/sqrt(a) (x - (1-a)/sqrt(1-ah) eps) + sqrt(b) z`` update with on-device Philox noise + timestep decrement)
-is captured into a hipGraph and replayed ``noise_steps - 1`` times; there is no per-step host->device traffic.
+Every sampler runs through the one reverse loop of ``Diffusion._denoise``, entirely on the device: the step-invariant
+conditioning (word embedding, cross-attention K/V) is computed once, one denoising step (UNet forward(s) + the sampler's
+update with on-device Philox noise + its timestep advance) is captured into a hipGraph and replayed once per visited step;
+there is no per-step host->device traffic.  What a sampler is to that loop is a ``_Sampler``, fixed on the host before
+anything is launched: ``_ddpm`` (``sampling``, ``train.py:221-236``: ``x <- 1/sqrt(a) (x - (1-a)/sqrt(1-ah) eps) + sqrt(b) z``
+at t = T-1 .. 1; ``sampling3`` skips the model on most of those steps) and ``_ddim`` (``sampling_ddim``: a subsequence).
 
 Facts preserved from the reference: the method is ``sampling`` (``sample`` is provided as
 an alias because ``sampling.py:119`` calls it); index 0 of the schedule is never used; with ``cfg_scale > 0``
@@ -15,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import random
-from typing import List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -114,6 +116,16 @@ class EMA:
         ema_model.load_state_dict(model.state_dict())
 
 
+class _Sampler(NamedTuple):
+    """What one sampler is to the reverse loop of ``Diffusion._denoise`` (built by ``Diffusion._ddpm`` / ``_ddim``, no GPU)."""
+    # per visited step, in loop order: (film_prepare argument = row of the pairs table, calls the model, index into ``noise`` or None)
+    steps: list
+    t_first: int  # the timestep of the first step
+    tau: Optional[list]  # the visited timesteps when FiLM rows and pairs are indexed by the step index; None: indexed by t
+    update: Callable  # update(lib, P, guide, zbuf, seed, sample_offset, device) -> end_step(stream), the launches that end a step
+    stats: dict  # what ``last_stats`` reports of the sampler itself
+
+
 class Diffusion:
     """``train.py:174-251`` (T=1000) / ``trainModifyCondition.py:515-622`` (T=600)."""
 
@@ -128,7 +140,6 @@ class Diffusion:
         self.img_size = img_size
         self.device = dev
         self._tables = None
-        self._graphs = {}
         self.forwards_per_step = 1
         self.tabulate_film = os.environ.get("WDIFF_FILM_TABLE", "1") != "0"
         self.last_stats = {}
@@ -202,14 +213,65 @@ class Diffusion:
         return tuple(c.float().to(device).contiguous() for c in (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt(p), c4, sigma))
 
     # --------------------------------------------------------------------------------------------------
-    def _denoise(self, model, n, text_features, labels, phosc, device, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, calls_model=None, deterministic=False, mix=None,
-                 record_pred=None, ddim=None):
-        """ddim = (tau, (c1..c5) on the host, eta): the DDIM loop over the visited timesteps ``tau`` - ``film_prepare(k)`` -> forward(s) ->
-        ``wd_ddim_step`` -> ``wd_next_timestep``, S = len(tau) times; FiLM rows, pairs and ``noise`` are indexed by the step
-        index k (``noise[k]`` is read only where c5[k] != 0).  None: the DDPM loop below, launch for launch as before.
-        mix = (pairs int32 [nf, T, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
-        step, forward f of timestep t reading pairs[f, t]; nf = 2 ends the step with the guided update (``wd_ddpm_step_cfg``).
+    def _ddpm(self, calls_model=None, deterministic=False):
+        """The DDPM family: t = T-1 .. 1 (train.py:221), the model called where ``calls_model(t)`` holds (None: everywhere; a
+        step that does not call it reuses the previous predicted noise) and one entry of ``noise`` per step while t > 1,
+        counted on skipped steps too.  A step ends with ``wd_ddpm_step`` (the guided ``wd_ddpm_step_cfg`` after two
+        forwards) and ``wd_advance_timestep``."""
+        T = self.noise_steps
+        steps = [(i, calls_model is None or bool(calls_model(i)), T - 1 - i if i > 1 else None) for i in reversed(range(1, T))]
+
+        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+            ca, cb, cs = self._step_tables(device)
+            if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
+                cs = torch.zeros_like(cs)
+            n, npix = P.x_in.shape[0], P.x_in[0].numel()
+
+            def end_step(stream):
+                if guide is not None:
+                    N.check(lib.wd_ddpm_step_cfg(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr(), guide[0],
+                                                 _dptr(guide[1]), n, npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
+                                                 P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddpm_step_cfg")
+                else:
+                    N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
+                                             cs.data_ptr(), P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream),
+                            "wd_ddpm_step")
+                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream),
+                        "wd_advance_timestep")
+            return end_step
+        # (``steps`` is T - 1 even when steps skip the model: it counts the updates)
+        return _Sampler(steps, T - 1, None, update, dict(steps=T - 1))
+
+    def _ddim(self, tau, eta):
+        """DDIM over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows, pairs and ``noise`` are indexed by k,
+        the model is called at every step and ``noise[k]`` is read only where c5[k] != 0.  A step ends with ``wd_ddim_step``
+        and ``wd_next_timestep``."""
+        tabs = self._ddim_tables(tau, eta, "cpu")
+        steps = [(k, True, k if s != 0.0 else None) for k, s in enumerate(tabs[4].tolist())]  # (host tables: no device sync)
+
+        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+            c = [t.to(device) for t in tabs]
+            tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
+            P.k_dev.zero_()
+            n, npix = P.x_in.shape[0], P.x_in[0].numel()
+            scale, eps_g = guide or (0.0, None)
+
+            def end_step(stream):
+                N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
+                                         scale, _dptr(eps_g), n, npix, *(t.data_ptr() for t in c), P.k_dev.data_ptr(),
+                                         P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddim_step")
+                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
+                                             P.t_in.data_ptr(), n, stream), "wd_next_timestep")
+            return end_step
+        stats = dict(sampler="ddim", steps=len(tau), eta=float(eta), timesteps=list(tau))
+        return _Sampler(steps, tau[0], list(tau), update, stats)
+
+    def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
+                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None):
+        """The one reverse loop.  Per visited step of ``sampler`` (``_ddpm`` / ``_ddim``): this step's ``noise`` entry into
+        the noise buffer if it has one, ``film_prepare`` and the forward(s) when the step calls the model, the sampler's update.
+        mix = (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
+        step, forward f of a step reading pairs[f, its film_prepare argument]; nf = 2 ends the step with the guided update.
         record_pred: a list that receives, per model-calling step, the predictions of its forwards (and, for nf = 2, the guided
         one) - eager launches only, like ``record``."""
         lib = N.lib()
@@ -223,23 +285,13 @@ class Diffusion:
         h, w = self.img_size[0] // 8, self.img_size[1] // 8
         ctx_len = text_features.shape[1]
         phosc_len = 0 if phosc is None else phosc.shape[1]
-        T = self.noise_steps
         # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
-        film_steps = T if (self.tabulate_film or nf) else 0
-        if ddim is None:
-            P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf)
-        else:
-            tau, dtab, eta = ddim
-            S = len(tau)
-            P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
-                         film_timesteps=tuple(tau) if film_steps else None)
+        film_steps = self.noise_steps if (self.tabulate_film or nf) else 0
+        P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
+                     film_timesteps=tuple(sampler.tau) if (film_steps and sampler.tau is not None) else None)
         fps = nf or self.forwards_per_step
-        ca, cb, cs = self._step_tables(device)
-        if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
-            cs = torch.zeros_like(cs)
-        T = self.noise_steps
+        ncalls = sum(fwd for _, fwd, _ in sampler.steps)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-        npix = P.x_in[0].numel()
 
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
@@ -248,52 +300,29 @@ class Diffusion:
             if x_T is not None:
                 P.x_in.copy_(x_T.to(device))
             else:
-                N.check(lib.wd_randn(P.x_in.data_ptr(), n, npix, seed, sample_offset, 0, st), "wd_randn")
+                N.check(lib.wd_randn(P.x_in.data_ptr(), n, P.x_in[0].numel(), seed, sample_offset, 0, st), "wd_randn")
             eng.load_inputs(P, None, None, text_features.to(device), labels.to(device) if labels is not None else None,
                             phosc.to(device) if phosc is not None else None, check=False)
             if nf:
                 eng.load_mix(P, mix[0].to(device), mix[1].to(device), check=False)
             eps_g = torch.empty_like(P.out) if (nf == 2 and record_pred is not None) else None
-            t_dev = P.t_dev
-            t_first = T - 1 if ddim is None else tau[0]
-            t_dev.fill_(t_first)
-            P.t_in.fill_(t_first)
+            P.t_dev.fill_(sampler.t_first)
+            P.t_in.fill_(sampler.t_first)
             zbuf = torch.zeros_like(P.x_in) if noise is not None else None
-            if ddim is not None:
-                stochastic = [v != 0.0 for v in dtab[4].tolist()]  # (host tables: no device sync)
-                c1, c2, c3, c4, c5 = (c.to(device) for c in dtab)
-                tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
-                k_dev = P.k_dev
-                k_dev.zero_()
+            end_step = sampler.update(lib, P, (float(mix[2]), eps_g) if nf == 2 else None, zbuf, seed, sample_offset, device)
             P.run_cond(st)
             P.run_film(st)  # time MLP of every timestep; the FiLM rows follow per chunk of timesteps (P.film_prepare)
             # before the capture: the captured step only reads the table (its rows are indexed by t, or by the DDIM step index)
-            P.film_prepare(T - 1 if ddim is None else 0, st)
+            if sampler.steps:
+                P.film_prepare(sampler.steps[0][0], st)
 
             def one_step(stream, forward=True):
                 if forward:
                     for _ in range(1 if nf else fps):
                         P.run_step(stream)
-                if nf == 2 and forward:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
-                    P.run_step1(stream)
-                if ddim is not None:
-                    N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if nf == 2 else None,
-                                             float(mix[2]) if nf == 2 else 0.0, _dptr(eps_g), n, npix, c1.data_ptr(), c2.data_ptr(),
-                                             c3.data_ptr(), c4.data_ptr(), c5.data_ptr(), k_dev.data_ptr(), t_dev.data_ptr(),
-                                             _dptr(zbuf), seed, sample_offset, stream), "wd_ddim_step")
-                    N.check(lib.wd_next_timestep(k_dev.data_ptr(), tau_dev.data_ptr(), S, t_dev.data_ptr(), P.t_in.data_ptr(), n,
-                                                 stream), "wd_next_timestep")
-                    return
-                if nf == 2:
-                    N.check(lib.wd_ddpm_step_cfg(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr(), float(mix[2]),
-                                                 _dptr(eps_g), n, npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
-                                                 t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddpm_step_cfg")
-                else:
-                    N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
-                                             cs.data_ptr(), t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream),
-                            "wd_ddpm_step")
-                N.check(lib.wd_advance_timestep(t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream),
-                        "wd_advance_timestep")
+                    if nf == 2:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
+                        P.run_step1(stream)
+                end_step(stream)
 
             def capture(forward):
                 N.check(lib.wd_graph_begin(st), "wd_graph_begin")
@@ -308,34 +337,15 @@ class Diffusion:
             gexec = gskip = None
             if use_graph and record is None and record_pred is None:
                 gexec = capture(True)
-                if calls_model is not None:
+                if ncalls < len(sampler.steps):
                     gskip = capture(False)  # steps that reuse the previous predicted noise: update only
-            k = 0
-            ncalls = 0
-            for j in range(S if ddim is not None else 0):  # the DDIM loop: step index j, timestep tau[j]
+            for row, fwd, z in sampler.steps:
                 if record is not None:
                     record.append(P.x_in.clone())
-                if zbuf is not None and stochastic[j]:
-                    zbuf.copy_(noise[j].to(device))
-                ncalls += 1
-                if film_steps:
-                    P.film_prepare(j, st)
-                if gexec is not None:
-                    N.check(lib.wd_graph_launch(gexec, st), "wd_graph_launch")
-                else:
-                    one_step(st)
-                if record_pred is not None:
-                    record_pred.append((P.out.clone(),) if nf != 2 else (P.out.clone(), P.out1.clone(), eps_g.clone()))
-            for i in reversed(range(1, T)) if ddim is None else ():
-                if record is not None:
-                    record.append(P.x_in.clone())
-                if zbuf is not None and i > 1:
-                    zbuf.copy_(noise[k].to(device))
-                    k += 1
-                fwd = calls_model is None or bool(calls_model(i))
-                ncalls += int(fwd)
+                if zbuf is not None and z is not None:
+                    zbuf.copy_(noise[z].to(device))
                 if fwd:
-                    P.film_prepare(i, st)  # FiLM rows of timestep i (computed per chunk of timesteps, see engine.plan)
+                    P.film_prepare(row, st)  # FiLM rows of this step (computed per chunk of rows, see engine.plan)
                 if gexec is not None:
                     N.check(lib.wd_graph_launch(gexec if fwd else gskip, st), "wd_graph_launch")
                 else:
@@ -349,13 +359,11 @@ class Diffusion:
             lib.wd_graph_destroy(gexec)
             if gskip is not None:
                 lib.wd_graph_destroy(gskip)
-        self.last_stats = dict(steps=T - 1, forwards_per_step=fps, graph=gexec is not None,
-                               seed=seed, sample_offset=sample_offset, model_calls=ncalls * (nf or 1))
-        if ddim is not None:
-            self.last_stats.update(sampler="ddim", steps=S, eta=float(eta), timesteps=list(tau))
+        self.last_stats = dict(sampler.stats, forwards_per_step=fps, graph=gexec is not None, seed=seed,
+                               sample_offset=sample_offset, model_calls=ncalls * (nf or 1))
         return x
 
-    def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, calls_model=None, visited=None):
+    def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, *, sampler=None):
         """The ``mix`` argument of ``_denoise`` for a sampler call, or None where the call does not interpolate.
 
         Fixed-pair mode (``style_pairs`` given: one ``(s1, s2)`` or an int tensor [n, 2]; ``mix_rate`` a float or fp32 [n]): the
@@ -364,9 +372,11 @@ class Diffusion:
         (unet.py:1561-1564) - they are drawn here, all of them, in loop order, before anything is launched; with
         ``cfg_scale > 0`` a step runs both forwards and the guided update.
         Otherwise ``mix_rate`` is ignored, as the reference's forward ignores it (unet.py:1558), and ``random`` is not touched.
-        ``visited`` = S (the DDIM sampler): the table is indexed by the step index, [nf, S, n, 2], and pairs are drawn for the S
-        visited steps only, in loop order."""
-        T = self.noise_steps if visited is None else int(visited)
+        ``sampler`` (default ``_ddpm()``) says which steps those are: pairs are drawn for its model-calling steps only, in loop
+        order, and the table is indexed as its FiLM rows are - by t, [nf, T, n, 2], or by the step index of its ``tau``,
+        [nf, S, n, 2]."""
+        sampler = sampler or self._ddpm()
+        T = self.noise_steps if sampler.tau is None else len(sampler.tau)
         if style_pairs is not None:
             if mix_rate is None:
                 raise ValueError("style_pairs needs a mix_rate (a float, or one per sample)")
@@ -375,11 +385,8 @@ class Diffusion:
                 raise ValueError(f"style_pairs must be (s1, s2) or an integer tensor [{n}, 2]")
             tab = sp.to(torch.int32).cpu().reshape(-1, 2).expand(n, 2).reshape(1, 1, n, 2).expand(1, T, n, 2).contiguous()
         elif mix_rate is not None and getattr(model, "interpolation", False):
-            if visited is not None:
-                steps = list(range(T))
-            else:
-                steps = [i for i in reversed(range(1, T)) if calls_model is None or calls_model(i)]
-            nf = 2 if (cfg_scale > 0 and calls_model is None) else 1
+            steps = [row for row, fwd, _ in sampler.steps if fwd]
+            nf = 2 if cfg_scale > 0 else 1
             drawn = draw_style_pairs(nf * len(steps))
             tab = torch.zeros((nf, T, n, 2), dtype=torch.int32)
             for k, i in enumerate(steps):
@@ -398,6 +405,23 @@ class Diffusion:
             raise ValueError("x_text must be one word or a list of n words")
         pad = label_padding_underscore if underscore else label_padding
         return torch.tensor(np.array([pad(w, NUM_TOKENS) for w in words], dtype="int64"))
+
+    def _prepare(self, who, model, n, x_text, args, phoscLabels, underscore=None, check_latent=True):
+        """What every sampler entry point settles before its loop: (device, word ids, PHOSC labels or None)."""
+        device = torch.device(getattr(args, "device", self.device))
+        if device.type != "cuda":
+            raise N.NativeError(f"Diffusion.{who} runs on an MI355X only (no CPU fallback)")
+        if check_latent and (self.img_size is None or not (getattr(args, "latent", True) == True)):  # noqa: E712
+            raise NotImplementedError("latent=False")
+        if underscore is None:
+            underscore = int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE
+        tf = self._text_features(x_text, n, underscore)
+        phosc = None
+        if getattr(args, "phosc", 0) == 1 or getattr(args, "phos", 0) == 1:
+            if phoscLabels is None:
+                raise ValueError("args.phosc/phos set but phoscLabels missing")
+            phosc = phoscLabels.int()
+        return device, tf, phosc
 
     def _finish(self, x, vae, args):
         """``train.py:238-250``: latents / 0.18215 -> vae.decode -> [0,1] image (vae is duck-typed)."""
@@ -429,23 +453,12 @@ class Diffusion:
         is two forwards and ``torch.lerp(second, first, cfg_scale)`` (``last_stats["forwards_per_step"] == 2``) - or
         ``style_pairs`` is given: the writers to blend, the same at every step (one forward per step).  ``labels`` is unused
         in both modes.  ``record_pred`` receives every step's predictions (eager launches)."""
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale)
-        if underscore is None:
-            underscore = int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE
+        device, tf, phosc = self._prepare("sampling", model, n, x_text, args, phoscLabels, underscore)
+        sampler = self._ddpm()
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
-        device = torch.device(getattr(args, "device", self.device))
-        if device.type != "cuda":
-            raise N.NativeError("Diffusion.sampling runs on an MI355X only (no CPU fallback)")
-        if self.img_size is None or not (getattr(args, "latent", True) == True):  # noqa: E712
-            raise NotImplementedError("latent=False")
-        tf = self._text_features(x_text, n, underscore)
-        phosc = None
-        if getattr(args, "phosc", 0) == 1 or getattr(args, "phos", 0) == 1:
-            if phoscLabels is None:
-                raise ValueError("args.phosc/phos set but phoscLabels missing")
-            phosc = phoscLabels.int()
         try:
-            x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_T, noise=noise, seed=seed,
+            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
                               record_pred=record_pred)
         finally:
@@ -468,25 +481,13 @@ class Diffusion:
         tau = self.ddim_timesteps(steps, timesteps)
         if noise is not None and len(noise) != len(tau):
             raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
-        device = torch.device(getattr(args, "device", self.device))
-        if device.type != "cuda":
-            raise N.NativeError("Diffusion.sampling_ddim runs on an MI355X only (no CPU fallback)")
-        if self.img_size is None or not (getattr(args, "latent", True) == True):  # noqa: E712
-            raise NotImplementedError("latent=False")
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, visited=len(tau))
-        if underscore is None:
-            underscore = int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE
+        device, tf, phosc = self._prepare("sampling_ddim", model, n, x_text, args, phoscLabels, underscore)
+        sampler = self._ddim(tau, eta)
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
-        tf = self._text_features(x_text, n, underscore)
-        phosc = None
-        if getattr(args, "phosc", 0) == 1 or getattr(args, "phos", 0) == 1:
-            if phoscLabels is None:
-                raise ValueError("args.phosc/phos set but phoscLabels missing")
-            phosc = phoscLabels.int()
         try:
-            x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_T, noise=noise, seed=seed, sample_offset=sample_offset,
-                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
-                              ddim=(tau, self._ddim_tables(tau, eta, "cpu"), eta))
+            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
+                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
@@ -518,26 +519,17 @@ class Diffusion:
         if emaOld == 1:
             model = model1
         model.eval()  # and it stays in eval mode: ``#model.train()`` is commented out at regenerateFromtrain2.py:622
-        device = torch.device(getattr(args, "device", self.device))
-        if device.type != "cuda":
-            raise N.NativeError("Diffusion.sampling3 runs on an MI355X only (no CPU fallback)")
         if isinstance(x_text, str) or len(x_text) <= 1:
             word_list = [x_text if isinstance(x_text, str) else x_text[0]] * n
         else:
             word_list = list(words)
-        tf = self._text_features(word_list, n, int(model.word_emb.embedding.weight.shape[0]) == VOCAB_SIZE_UNDERSCORE)
-        phosc = None
-        if getattr(args, "phosc", 0) == 1 or getattr(args, "phos", 0) == 1:
-            if phoscLabels is None:
-                raise ValueError("args.phosc/phos set but phoscLabels missing")
-            phosc = phoscLabels.int()
+        device, tf, phosc = self._prepare("sampling3", model, n, word_list, args, phoscLabels, check_latent=False)
         full = bool(getattr(args, "fullSampling", False))
-        T = self.noise_steps
-        calls_model = None if full else (lambda i: self.sampling3_calls_model(i, T, epoch))
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, 0, calls_model=calls_model or (lambda i: True))
-        x = self._denoise(model, n, tf, labels, phosc, device, x_T=x_t if noiseInput == 0 else x_T, noise=noise, seed=seed,
-                          sample_offset=sample_offset, record=record, use_graph=use_graph,
-                          calls_model=calls_model, deterministic=not full, mix=mix)
+        sampler = self._ddpm(None if full else (lambda i: self.sampling3_calls_model(i, self.noise_steps, epoch)),
+                             deterministic=not full)
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, 0, sampler=sampler)  # (one forward per step: no guidance here)
+        x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_t if noiseInput == 0 else x_T, noise=noise,
+                          seed=seed, sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix)
         if vae is None:
             return x
         image = self._finish(x, vae, args)
