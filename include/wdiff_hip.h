@@ -58,7 +58,13 @@ typedef struct wd_src {
  * with A = [src0 taps | src1 taps] along k.
  * Replaces nn.Conv2d 3x3 / stride-2 / nearest-x2+3x3 / 1x1 and nn.Linear on the path:
  * unet.py:595,621,632 (ResBlock convs + skip), :540 (Downsample), :488-499 (Upsample), :364,375 (proj_in/out),
- * :175-183 (attention projections), :125,145 (GEGLU feed-forward), :1201-1205 (time MLP), :611 (emb_layers). */
+ * :175-183 (attention projections), :125,145 (GEGLU feed-forward), :1201-1205 (time MLP), :611 (emb_layers).
+ * Every operand has a row pitch of its own (wd_src.ld, rowvec_ld, resid_ld, out_ld, out_pl_ld, a32_ld), so each may be a column
+ * window of a wider buffer.  A pitch narrower than the columns the launch touches in a row is WD_EINVAL, not a fold of rows onto
+ * one another: with n_out = n (n / 2 under WD_ACT_GEGLU), out_ld >= n_out when out_f32 is set, out_pl_ld >= n_out when out_hi is
+ * set, resid_ld >= n_out when resid is set, rowvec_ld >= n_out when rowvec is set, and ld >= c for every planes source.  The
+ * launch reads and writes nothing outside those windows (rows [0, m), the stated columns): pitch padding and neighbouring rows
+ * are never stored to and never reach a stored value or a statistic. */
 typedef struct wd_gemm_args {
     wd_src src[2];
     int32_t nsrc;
@@ -104,7 +110,8 @@ typedef struct wd_gemm_args {
     double* stat_part;    /* NULL, or [m / hw_out][nchunk][n / stat_cpg][2] (sum, sum of squares) of the finished output per
                            * (sample, 128-row chunk, channel group): GroupNorm statistics for the consumer (wd_gn_apply),
                            * nchunk = max(1, hw_out / 128).  Needs 128-row tiles, hw_out | 128 or 128 | hw_out, whole
-                           * groups per column tile; not with GEGLU */
+                           * groups per column tile, the vector epilogue (out_ld, rowvec_ld, resid_ld, out_pl_ld multiples of 4;
+                           * bias, rowvec, resid, out_f32 16-byte and out_hi / out_lo 8-byte aligned); not with GEGLU */
     int32_t stat_cpg;     /* channels per statistics group */
     int32_t dbg;          /* 0 in production.  0x400: take the two-workgroups-per-CU kernel (wd_gemm4_kernel) wherever it is
                              legal, whatever the grid size (parity tests); other bits are timing experiments */
@@ -163,6 +170,9 @@ int wd_gemm(const wd_gemm_args* args, void* stream);
  * WD_EINVAL.  On WD_OK and out != NULL, *out receives the args as the kernel sees them (tile, ksplit, tickets, slab_rows resolved).
  * Callers ask this rather than restate the rules above. */
 int wd_gemm_check(const wd_gemm_args* args, wd_gemm_args* out);
+/* The launch family wd_gemm would run `args` on, by the name csrc/wd_gemm.hip gives it ("K_V1", "K_V2", "K_M16", "K_V4", "K_GEMMW",
+ * "K_GEMMQ", ...; a static string), NULL where wd_gemm_check refuses them.  Host only: lets a test pin the kernel a case is about. */
+const char* wd_gemm_check_kernel(const wd_gemm_args* args);
 
 /* wd_gemm_args.w_layout == 3: the weights of a GEMM with n % 320 == 0, ktot % 64 == 0 in FRAGMENT-MAJOR order - the 16 bytes
  * lane l of a v_mfma_f32_16x16x32_bf16 B fragment holds, W[16 ct + (l & 15)][32 ks + 8 (l >> 4) .. + 8], at byte

@@ -1,0 +1,84 @@
+"""Guard bands and poison for the kernel tests: an operand is a window of a wider, taller buffer whose every other element holds
+a fixed NaN bit pattern.  A store outside the window changes the pattern (assert_untouched names the first element); a read
+outside it brings a NaN into the window (assert_finite names the first).  Plain functions, no fixtures."""
+import torch
+
+NAN32 = 0x7FFBADAD  # a NaN as fp32 and as the high half of an fp64 (both halves of a double get it); no arithmetic produces it
+NAN16 = 0x7FD5      # a bf16 NaN
+_INT = {torch.float32: (torch.int32, 1, NAN32), torch.int32: (torch.int32, 1, NAN32), torch.float64: (torch.int32, 2, NAN32),
+        torch.bfloat16: (torch.int16, 1, NAN16)}
+
+
+def _ints(t):
+    """t's bits as integers [..., rows, ld * k] (k = integers per element), and the fill pattern."""
+    it, k, pat = _INT[t.dtype]
+    return (t if t.dtype == it else t.view(it)), k, pat
+
+
+def poisoned(shape, dtype, device="cpu"):
+    it, k, pat = _INT[dtype]
+    shape = tuple(shape)
+    raw = torch.full(shape[:-1] + (shape[-1] * k,), pat, dtype=it, device=device)
+    return raw if dtype == it else raw.view(dtype)
+
+
+def guarded(rows, cols, ld, col0, dtype, guard_rows=2, device="cpu", planes=0):
+    """(buf, view): buf has rows + 2 * guard_rows rows of pitch ld, every element the NaN pattern; view is the rows x cols window
+    at row guard_rows, column col0.  planes = 2: two such buffers stacked (the hi / lo planes), view [2][rows][cols]."""
+    assert 0 <= col0 and col0 + cols <= ld and guard_rows >= 0
+    lead = (planes,) if planes else ()
+    buf = poisoned(lead + (rows + 2 * guard_rows, ld), dtype, device)
+    return buf, buf[..., guard_rows:guard_rows + rows, col0:col0 + cols]
+
+
+def pitched(x, ld, col0, guard_rows=2, device="cpu"):
+    """The 2-D tensor x placed as guarded() places a window, NaN everywhere else."""
+    buf, view = guarded(x.shape[0], x.shape[1], ld, col0, x.dtype, guard_rows, device)
+    view.copy_(x)
+    return buf, view
+
+
+def split_planes(x):
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo], 0)
+
+
+def pitched_planes(x, ld, col0, guard_rows=2, device="cpu"):
+    """The split-bf16 planes of x ([2][rows][c]: hi = bf16(x), lo = bf16(x - hi)) placed the same way, bf16 NaN outside."""
+    buf, view = guarded(x.shape[0], x.shape[1], ld, col0, torch.bfloat16, guard_rows, device, planes=2)
+    view.copy_(split_planes(x.float()))
+    return buf, view
+
+
+def view_spec(buf, view):
+    """(row0, rows, col0, cols) of a window made by guarded() inside its buffer."""
+    ld = buf.shape[-1]
+    off = view.storage_offset() - buf.storage_offset()
+    off %= buf.shape[-2] * ld  # (the same window in every plane)
+    return off // ld, view.shape[-2], off % ld, view.shape[-1]
+
+
+def assert_untouched(buf, spec, name="buffer"):
+    """Everything of buf outside the window still holds the fill pattern, compared as integers.  spec: the view guarded()
+    returned, or (row0, rows, col0, cols)."""
+    row0, rows, col0, cols = view_spec(buf, spec) if torch.is_tensor(spec) else spec
+    ints, k, pat = _ints(buf.detach().cpu())
+    bad = ints != pat
+    bad[..., row0:row0 + rows, col0 * k:(col0 + cols) * k] = False
+    if bool(bad.any()):
+        idx = [int(v) for v in bad.nonzero()[0]]
+        r, c = idx[-2], idx[-1] // k
+        where = f"plane {idx[0]}, " if len(idx) == 3 else ""
+        val = buf[tuple(idx[:-2]) + (r, c)].item()
+        raise AssertionError(f"{name}: write outside the {rows} x {cols} window at (row {row0}, column {col0}): {int(bad.sum())} "
+                             f"element(s), first at {where}(row {r}, column {c}) = {val!r}")
+
+
+def assert_finite(view, name="window"):
+    """Every window value is finite (an unwritten element or a poisoned operand read shows as NaN)."""
+    v = view.detach().float().cpu() if view.dtype == torch.bfloat16 else view.detach().cpu()
+    bad = ~torch.isfinite(v)
+    if bool(bad.any()):
+        idx = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(f"{name}: {int(bad.sum())} non-finite value(s), first at {idx} = {v[idx].item()!r}")

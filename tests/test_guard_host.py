@@ -1,0 +1,63 @@
+"""The guard-band helper of the pitched-operand kernel tests (tests/_guard.py) can fail: one element written into the padding and
+one NaN put into a window are both reported, with their position, for every element type the kernels write.  No GPU."""
+import pytest
+import torch
+
+from tests import _guard as G
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16, torch.int32])
+@pytest.mark.parametrize("planes", [0, 2])
+def test_guard_bands_report_a_write_outside_the_window(dtype, planes):
+    buf, view = G.guarded(5, 6, 12, 4, dtype, planes=planes)
+    assert buf.shape[-2:] == (9, 12) and view.shape[-2:] == (5, 6) and G.view_spec(buf, view) == (2, 5, 4, 6)
+    if dtype.is_floating_point:
+        assert bool(torch.isnan(buf.float()).all())  # the fill is a NaN in every type
+    G.assert_untouched(buf, view)
+    view.fill_(1)  # the whole window may change
+    G.assert_untouched(buf, view)
+    G.assert_untouched(buf, (2, 5, 4, 6))
+    for r, c in [(2, 3), (2, 10), (1, 4), (7, 9), (0, 0), (8, 11), (4, 0)]:  # left / right padding, rows before / after, corners
+        b2 = buf.clone()
+        b2[..., r, c] = 3
+        with pytest.raises(AssertionError, match=rf"\(row {r}, column {c}\) = 3"):
+            G.assert_untouched(b2, (2, 5, 4, 6), "out")
+    if planes:
+        b2 = buf.clone()
+        b2[1, 6, 11] = 0
+        with pytest.raises(AssertionError, match=r"plane 1, \(row 6, column 11\)"):
+            G.assert_untouched(b2, view)
+
+
+def test_guard_sees_half_a_double_change():
+    buf, view = G.guarded(2, 2, 4, 1, torch.float64)
+    ints = buf.view(torch.int32)
+    ints[3, 7] = 0  # the high half of (row 3, column 3)
+    with pytest.raises(AssertionError, match=r"\(row 3, column 3\)"):
+        G.assert_untouched(buf, view)
+
+
+def test_poisoned_operands_and_the_finite_check():
+    x = torch.arange(12, dtype=torch.float32).reshape(3, 4) * (1 + 2.0 ** -12)  # hi = k, lo = k / 4096: exact
+    buf, view = G.pitched(x, 8, 4)
+    assert torch.equal(view, x) and int(torch.isnan(buf).sum()) == buf.numel() - 12
+    G.assert_untouched(buf, view)
+    G.assert_finite(view)
+    pbuf, pview = G.pitched_planes(x, 16, 8)
+    assert pbuf.shape == (2, 7, 16) and pbuf.dtype == torch.bfloat16
+    assert torch.equal(pview[0].float() + pview[1].float(), x)
+    assert int(torch.isnan(pbuf.float()).sum()) == pbuf.numel() - 24
+    G.assert_untouched(pbuf, pview)
+    G.assert_finite(pview)
+    view[1, 2] = float("nan")
+    with pytest.raises(AssertionError, match=r"first at \(1, 2\)"):
+        G.assert_finite(view, "out")
+    pview[1, 0, 3] = float("inf")
+    with pytest.raises(AssertionError, match=r"first at \(1, 0, 3\)"):
+        G.assert_finite(pview)
+    # a value computed from a poisoned element is itself caught
+    out, oview = G.guarded(3, 4, 4, 0, torch.float32, guard_rows=0)
+    buf, view = G.pitched(x, 8, 4)
+    oview.copy_(buf[2:5, 3:7] + 1)  # a window read one column too far to the left
+    with pytest.raises(AssertionError, match=r"3 non-finite"):
+        G.assert_finite(oview)

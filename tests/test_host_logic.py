@@ -444,3 +444,55 @@ def test_wd_gemm_check_gn_needs_the_k_cut():
     a = _gemm_args(256 * 64, 640, 64, [(640, 9, True, 64)], w_layout=3, tile=64320, stat_part=_P, stat_cpg=20)
     out = N.WdGemmArgs()
     assert N.lib().wd_gemm_check(ctypes.byref(a), ctypes.byref(out)) == N.WD_OK and out.ksplit == 1
+
+
+# ---- a pitch narrower than the width it spans is refused (each on an otherwise legal launch: the wide form resolves)
+def _narrow_cases():
+    lin = [(64, 1, False, 0)]
+    base = dict(tile=128064)
+    return {
+        "out_ld": (dict(m=130, n=100, hw_out=1, srcs=lin, **base), dict(out_ld=96)),
+        "out_ld zero": (dict(m=130, n=100, hw_out=1, srcs=lin, **base), dict(out_ld=0)),
+        "out_ld, GEGLU": (dict(m=130, n=128, hw_out=1, srcs=lin, act=N.ACT_GEGLU, out_ld=64, **base), dict(out_ld=60)),
+        "out_pl_ld": (dict(m=130, n=100, hw_out=1, srcs=lin, out_pl_ld=100, **_PLANES, **base), dict(out_pl_ld=96)),
+        "out_pl_ld, GEGLU": (dict(m=130, n=128, hw_out=1, srcs=lin, act=N.ACT_GEGLU, out_ld=64, out_pl_ld=64, **_PLANES, **base),
+                             dict(out_pl_ld=56)),
+        "resid_ld": (dict(m=130, n=100, hw_out=1, srcs=lin, resid=_P, resid_ld=100, **base), dict(resid_ld=99)),
+        "rowvec_ld": (dict(m=192, n=100, hw_out=64, srcs=lin, rowvec=_P, rowvec_ld=100, **base), dict(rowvec_ld=96)),
+        "src ld": (dict(m=130, n=100, hw_out=1, srcs=lin, **base), dict(src_ld=(0, 56))),
+        "second src ld": (dict(m=192, n=160, hw_out=64, srcs=[(64, 9, True, 64), (128, 1, False, 0)], tile=128160), dict(src_ld=(1, 64))),
+        "src ld, w_layout 3": (dict(m=192, n=320, hw_out=64, srcs=[(64, 9, True, 64)], w_layout=3, tile=64320), dict(src_ld=(0, 32))),
+        "src ld, 64x80": (dict(m=192, n=160, hw_out=64, srcs=[(64, 9, True, 64)], w_layout=3, tile=64080, slab_rows=16),
+                          dict(src_ld=(0, 56))),
+    }
+
+
+@pytest.mark.parametrize("name", sorted(_narrow_cases()))
+def test_wd_gemm_check_refuses_a_pitch_narrower_than_the_width(name):
+    lib = N.lib()
+    legal, narrow = _narrow_cases()[name]
+    legal = dict(legal)
+    a = _gemm_args(legal.pop("m"), legal.pop("n"), legal.pop("hw_out"), legal.pop("srcs"), **legal)
+    assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_OK and lib.wd_gemm_check_kernel(ctypes.byref(a)) is not None
+    for k, v in narrow.items():
+        if k == "src_ld":
+            a.src[v[0]].ld = v[1]
+        else:
+            setattr(a, k, v)
+    assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_EINVAL
+    assert lib.wd_gemm_check_kernel(ctypes.byref(a)) is None
+    assert lib.wd_gemm(ctypes.byref(a), None) == N.WD_EINVAL  # (returns before any HIP call)
+
+
+@pytest.mark.parametrize("field,off", [("out_f32", 4), ("bias", 8), ("rowvec", 4), ("resid", 12), ("out_hi", 2), ("out_lo", 4)])
+def test_wd_gemm_check_statistics_need_the_vector_epilogue(field, off):
+    """The fused GroupNorm statistics are column sums the vector epilogue keeps: a pointer off its grid selects the scalar
+    epilogue, which keeps none, so such a launch is refused (as an odd pitch already was) rather than left to write sums of nothing."""
+    lib = N.lib()
+    kw = dict(tile=128160, stat_part=_P, stat_cpg=5, bias=_P, rowvec=_P, rowvec_ld=160, resid=_P, resid_ld=160, out_pl_ld=160, **_PLANES)
+    a = _gemm_args(192, 160, 64, [(64, 9, True, 64)], **kw)
+    assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_OK
+    setattr(a, field, _P + off)
+    assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_EINVAL
+    a.stat_part = None  # the same launch without statistics is legal: it takes the scalar epilogue
+    assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_OK

@@ -75,6 +75,7 @@ class WdDwItem(C.Structure):
 _SIGS = {
     "wd_gemm": (_i, [C.POINTER(WdGemmArgs), _vp]),
     "wd_gemm_check": (_i, [C.POINTER(WdGemmArgs), C.POINTER(WdGemmArgs)]),
+    "wd_gemm_check_kernel": (C.c_char_p, [C.POINTER(WdGemmArgs)]),
     "wd_dw": (_i, [C.POINTER(WdDwArgs), _vp]),
     "wd_dw_supported": (_i, [_i, _i, _i, _i, _i]),
     "wd_dw_slices": (_i, [_i, _i, _i, _i]),

@@ -1324,12 +1324,7 @@ __global__ void __launch_bounds__(256) wd_gemm_reduce_kernel(const wd_gemm_args 
     {
         // the epilogue's vector path can sum the slabs itself (no LDS image, one barrier less, the slab / residual / row-vector
         // loads of a row in flight together); same conditions as its own `vec` test plus aligned slabs
-        const bool direct = v4 && (((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) == 0) &&
-                            (((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) |
-                               reinterpret_cast<uintptr_t>(a.resid) | reinterpret_cast<uintptr_t>(a.out_f32) |
-                               reinterpret_cast<uintptr_t>(a.ws)) & 15) == 0) &&
-                            (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0) &&
-                            n0 + BN <= a.n;
+        const bool direct = v4 && wd_epilogue_vec_ok(a) && (reinterpret_cast<uintptr_t>(a.ws) & 15) == 0 && n0 + BN <= a.n;
         if (direct) {
             wd_gemm_args b = a;
             b.ksplit = 1;
@@ -2278,7 +2273,8 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         const int bm = (a.tile ? a.tile / 1000 : 128);
         if (!((a.hw_out % bm == 0) || (bm % a.hw_out == 0 && bm / a.hw_out <= WD_STAT_MAXNS))) return WD_EINVAL;
         if ((bm != 128 && a.w_layout != 3) || bn % a.stat_cpg) return WD_EINVAL;
-        if ((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) return WD_EINVAL;  // vector epilogue only
+        // vector epilogue only: an odd pitch or a pointer off the 16-byte / 8-byte grid takes the scalar path, which keeps no column sums
+        if (!wd_epilogue_vec_ok(a)) return WD_EINVAL;
         if (a.tile == 0) a.tile = bm * 1000 + bn;  // keep 128-row panels (no 64x64 fallback)
     }
     if (a.ksplit > 1 && (!a.ws || a.act == WD_ACT_GEGLU || a.w_layout == 1)) return WD_EINVAL;
@@ -2296,11 +2292,8 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         if (!a.gn_beta || !a.stat_part || !a.out_hi || (!a.ws && a.tile != 64080) || a.hw_out != 64 || a.m % 64 || a.n % 160 || a.gn_cpg <= 0 ||
             40 % a.gn_cpg || a.stat_cpg <= 0 || a.gn_cpg % a.stat_cpg || a.act != WD_ACT_NONE || a.resid_rows || a.w_layout == 1)
             return WD_EINVAL;
-        if (((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) ||
-            ((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) | reinterpret_cast<uintptr_t>(a.resid) |
-              reinterpret_cast<uintptr_t>(a.out_f32) | reinterpret_cast<uintptr_t>(a.ws) | reinterpret_cast<uintptr_t>(a.gn_gamma) |
-              reinterpret_cast<uintptr_t>(a.gn_beta)) & 15) ||
-            ((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7))
+        if (!wd_epilogue_vec_ok(a) ||
+            ((reinterpret_cast<uintptr_t>(a.ws) | reinterpret_cast<uintptr_t>(a.gn_gamma) | reinterpret_cast<uintptr_t>(a.gn_beta)) & 15))
             return WD_EINVAL;
         a.tickets = nullptr;  // the norm lives in the combine launch
     }
@@ -2339,6 +2332,14 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
     if (a.act == WD_ACT_GEGLU && (a.n % 64 || a.tile == 0)) return WD_EINVAL;  // the tile fixes the x|gate packing
     if (a.rowvec && a.rowvec_ld <= 0) return WD_EINVAL;
     if (a.resid && a.resid_ld <= 0) return WD_EINVAL;
+    {   // a pitch spans at least the columns the launch touches in a row (a narrower one folds rows onto one another)
+        const int nout = a.act == WD_ACT_GEGLU ? a.n / 2 : a.n;
+        if ((a.out_f32 && a.out_ld < nout) || (a.out_hi && a.out_pl_ld < nout) || (a.resid && a.resid_ld < nout) ||
+            (a.rowvec && a.rowvec_ld < nout))
+            return WD_EINVAL;
+        for (int s = 0; s < a.nsrc; ++s)
+            if (!(s == 0 && a.a32) && a.src[s].ld < a.src[s].c) return WD_EINVAL;
+    }
 
     if (a.w_layout == 3) {
         bool ok = a.src[0].ntaps <= 9 && (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
@@ -2435,11 +2436,7 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         static const bool fuse_env = getenv("WDIFF_GEMM_FUSE_COMBINE") ? atoi(getenv("WDIFF_GEMM_FUSE_COMBINE")) != 0 : false;
         const int bn = tile % 1000, bm = tile / 1000;
         const long ntile = (long)((a.m + bm - 1) / bm) * ((a.n + bn - 1) / bn);
-        const bool aligned = (a.n & 3) == 0 && a.n % bn == 0 && (((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) == 0) &&
-                             (((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) |
-                                reinterpret_cast<uintptr_t>(a.resid) | reinterpret_cast<uintptr_t>(a.out_f32) |
-                                reinterpret_cast<uintptr_t>(a.ws)) & 15) == 0) &&
-                             (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0);
+        const bool aligned = (a.n & 3) == 0 && a.n % bn == 0 && wd_epilogue_vec_ok(a) && (reinterpret_cast<uintptr_t>(a.ws) & 15) == 0;
         if (!((fuse_env || (a.dbg & 0x2000)) && a.tickets && a.ksplit > 1 && v2ok && !use_v4 && !conv3 && aligned && ntile <= a.ntickets))
             a.tickets = nullptr;
     }
@@ -2491,6 +2488,25 @@ extern "C" int wd_gemm_check(const wd_gemm_args* in, wd_gemm_args* out) {
     const int rc = wd_gemm_resolve(*in, r);
     if (rc == WD_OK && out) *out = r.a;
     return rc;
+}
+
+extern "C" const char* wd_gemm_check_kernel(const wd_gemm_args* in) {
+    if (!in) return nullptr;
+    WdResolved r;
+    if (wd_gemm_resolve(*in, r) != WD_OK) return nullptr;
+    switch (r.kernel) {
+        case K_GEMMQ: return "K_GEMMQ";
+        case K_GEMMW: return "K_GEMMW";
+        case K_V4: return "K_V4";
+        case K_M16: return "K_M16";
+        case K_V2: return "K_V2";
+        case K_V1: return "K_V1";
+        case K_SLAB: return "K_SLAB";
+        case K_CONV3: return "K_CONV3";
+        case K_V8: return "K_V8";
+        case K_PP: return "K_PP";
+    }
+    return nullptr;
 }
 
 extern "C" int wd_gemm(const wd_gemm_args* pa, void* stream) {

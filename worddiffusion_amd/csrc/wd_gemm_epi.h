@@ -18,6 +18,16 @@ namespace {
 constexpr int WD_STAT_SCRATCH = 40 * 1024;  // LDS behind the epilogue image for the per-thread column sums
 constexpr int WD_STAT_MAXNS = 2;          // samples per 128-row panel the fused statistics support (hw_out >= 64)
 
+// Does the epilogue take its 16-byte path for these args: every epilogue pitch a multiple of 4 elements, the fp32 operands on the
+// 16-byte grid and the output planes on the 8-byte grid.  The one statement of that rule: the epilogue itself, the combine
+// launch and the host checks (wd_gemm_resolve: statistics, gn_*, tickets need this path) all ask here.
+__host__ __device__ __forceinline__ bool wd_epilogue_vec_ok(const wd_gemm_args& a) {
+    return (((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) == 0) &&
+           (((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) |
+              reinterpret_cast<uintptr_t>(a.resid) | reinterpret_cast<uintptr_t>(a.out_f32)) & 15) == 0) &&
+           (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0);
+}
+
 // WS: the tile's values are not in the LDS image but still spread over the split-K slabs of a.ws - the combine pass sums them
 // here, row by row in the thread's own (row lane, column quad) pattern, instead of staging the sums through LDS first (the
 // statistics scratch behind the image position is used as usual).  Vector path only; the caller checks.
@@ -32,10 +42,7 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
     const int no0 = geglu ? n0 / 2 : n0;
     const bool stats = a.stat_part != nullptr;
     // 16-byte path needs aligned rows everywhere; otherwise (odd leading dimensions) one element at a time
-    const bool vec = (((a.out_ld | a.rowvec_ld | a.resid_ld | a.out_pl_ld) & 3) == 0) &&
-                     (((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) |
-                        reinterpret_cast<uintptr_t>(a.resid) | reinterpret_cast<uintptr_t>(a.out_f32)) & 15) == 0) &&
-                     (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0);
+    const bool vec = wd_epilogue_vec_ok(a);
     if (!vec) {
         for (int i = tid; i < BM * ocols; i += NT) {
             const int row = i / ocols, c = i - row * ocols;

@@ -777,6 +777,7 @@ class UNetEngine:
         a.nsrc, a.npass, a.m, a.n, a.ktot, a.hw_out = len(srcs), self.npass, m, n, sum(s.ntaps * s.c for s in srcs), hw_out
         a.w_layout, a.tile = 3, 64320
         a.w_hi = a.w_lo = a.out_f32 = 16
+        a.out_ld = n  # (a dense m x n output: wd_gemm_check refuses a pitch narrower than the width)
         if a32 is not None:
             self._set_a32(a, *a32)
         return self._legal(a, apply=False, **fields)
