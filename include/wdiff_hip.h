@@ -297,7 +297,7 @@ int wd_gn_apply2(const float* xa, int lda, int ca, const double* part_a, int nch
 /* out[b][o][y][x] (NCHW, o < oc <= 4) = Conv3x3(SiLU?(GroupNorm(x)))[o] + bias[o] in one launch, fp32 VALU: the UNet's last layer
  * (GroupNorm32, SiLU, conv 320 -> 4; unet.py:1453-1458) and any other few-output-channel 3x3 (pad 1, stride 1).
  * x: token-major fp32 [batch*h*w][ld]; part / nchunk / part_cpg: GroupNorm statistics as for wd_gn_apply; weight: the
- * parameter itself, fp32 [oc][c][3][3].  wd_gn_conv3x3_few_supported(c, w, oc): c % 64 == 0, w <= 64, oc <= 4, LDS fit. */
+ * parameter itself, fp32 [oc][c][3][3].  wd_gn_conv3x3_few_supported(c, w, oc): c % 64 == 0, w <= 64, oc <= 4. */
 int wd_gn_conv3x3_few_supported(int c, int w, int oc);
 int wd_gn_conv3x3_few(const float* x, int ld, int batch, int h, int w, int c, int cpg, const double* part, int nchunk, int part_cpg,
                       const float* gamma, const float* beta, float eps, int silu, const float* weight, const float* bias, int oc,
@@ -392,6 +392,17 @@ int wd_embed_tokens(const void* ids, int ids_are_i64, int rows, int seq_len, con
 /* x NCHW [B][cin][h][w] -> im2col planes [B*h*w][kpad], column tap*cin + ci (3x3, pad 1); unet.py:1251. */
 int wd_im2col3x3(const float* x, int batch, int cin, int h, int w, wd_bf16* out_hi, wd_bf16* out_lo, int kpad,
                  void* stream);
+
+/* The first layer as a direct fp32 convolution (3x3, pad 1, cin <= 4; unet.py:1251), without im2col planes:
+ * out[(b*h*w + p)*ld + o] = bias[o] + sum weight[o][ci][tap] * x[b][ci][..] (fp32 FMAs), weight = the parameter [cout][cin][3][3].
+ * part (may be NULL): GroupNorm statistics partials [batch][wd_conv3x3_in_nchunk(h*w)][cout / stat_cpg][2] in fp64 (sum, sum of
+ * squares of the fp32 results over 64-token chunks) - the layout wd_gemm's stat_part has for 64-row panels, read by wd_gn_apply.
+ * wd_conv3x3_in_supported(cin, h, w, cout): 1 <= cin <= 4, w <= 64, (h + 2) * (w + 2) <= 2048, cout % 4 == 0, cout <= 2048, and
+ * the padded sample + the weights within 64 KB of LDS. */
+int wd_conv3x3_in_supported(int cin, int h, int w, int cout);
+int wd_conv3x3_in_nchunk(int hw);
+int wd_conv3x3_in(const float* x, int batch, int cin, int h, int w, const float* weight, const float* bias, int cout, float* out,
+                  int ld, double* part, int stat_cpg, void* stream);
 
 /* layout changes at the API edge: NCHW [B][c][hw] <-> token-major [B*hw][ld]. */
 int wd_nchw_to_tokens(const float* x, int batch, int c, int hw, float* out, int ld, void* stream);

@@ -107,6 +107,9 @@ _SIGS = {
     "wd_timestep_embedding": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "wd_embed_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "wd_im2col3x3": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "wd_conv3x3_in_supported": (_i, [_i, _i, _i, _i]),
+    "wd_conv3x3_in_nchunk": (_i, [_i]),
+    "wd_conv3x3_in": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "wd_nchw_to_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "wd_tokens_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "wd_ddpm_step": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),

@@ -223,141 +223,208 @@ __global__ void split_kernel(const float* __restrict__ x, int ld, int rows, int 
 
 // ---- out[b][o][y][x] = Conv3x3(SiLU(GroupNorm(x)))[o] + bias[o] for a convolution with FEW output channels (<= 4): the UNet's
 // last layer (unet.py:1453-1458: GroupNorm32, SiLU, conv 320 -> 4).  As a GEMM it fills 4 of a tile's 64 columns; here one
-// workgroup owns one image row of one sample and walks the channels in chunks of 64: the chunk's 3 x (W + 2) pixel tile is
-// normalised + SiLU'd into LDS (zero halo) next to the chunk's weights as [channel][tap][4], and multiplied in fp32 on the VALU
-// (lanes = pixels, so the weight reads are broadcasts).  The rows of the NEXT chunk are requested before the current one is
-// multiplied, so the HBM latency of a chunk hides under the previous chunk's arithmetic.
-// grid (H, batch), block 256 = PXL pixel lanes x (256 / PXL) channel groups; W <= 64, c % 64 == 0, weights = the parameter
-// [oc][c][3][3].
+// workgroup owns a tile of 4 image rows x 16 columns of one sample and walks the channels in chunks of 64: the chunk's 6 x 18 pixel
+// tile (halo included, zero outside the image) is normalised + SiLU'd into LDS once, next to the chunk's weights as
+// [channel][tap][4], and multiplied in fp32 on the VALU.
+// lane = (channel slot s, column x) with x in the low four bits, so the 16 lanes of a DPP row are the 16 columns of the tile.  A
+// lane owns the 4 pixels of its column and 2 of the chunk's channels (8 waves x 4 slots x 2 = 64): per channel it reads the six
+// rows of its column (8 bytes per row for both channels), takes the left and right neighbours from the neighbouring lanes by DPP
+// row shifts - the two lanes at the ends of a row keep the halo column's value instead, the `old` operand of the shift - and reads
+// the channel's 9 x 4 weights once into registers for 144 products.  (One pixel per lane needed a weight read per four products.)
+// What a chunk needs from global memory - its rows, its weights, gamma and beta - is requested two chunks ahead, into registers,
+// so that the latency of a chunk hides under the arithmetic of the two before it.
+// grid (batch, ceil(W / 16), ceil(H / 4)), block 512; c % 64 == 0, weights = the parameter [oc][c][3][3].
 constexpr int GC_CH = 64;            // channels per chunk
 constexpr int GC_PITCH = GC_CH + 4;  // floats per pixel in the tile (shifts the banks from pixel to pixel)
-template <int PXL>
-__global__ void __launch_bounds__(256) gn_conv_few_kernel(const float* __restrict__ x, int ld, int H, int W, int c, int cpg, int nchunk,
-                                                         int part_cpg, const double* __restrict__ part,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                         int silu, const float* __restrict__ w, const float* __restrict__ bias, int oc,
-                                                         float* __restrict__ out) {
-    constexpr int CG = 256 / PXL, CPT = GC_CH / CG;  // channel groups, channels per thread and chunk
-    constexpr int NLD = 3 * PXL * (GC_CH / 4) / 256;  // float4 of a chunk's rows per thread (6 at 32 pixel lanes, 12 at 64)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_w = reinterpret_cast<float*>(smem);   // [GC_CH][9][4]: this chunk's weights
-    float* s_t = s_w + 9 * GC_CH * 4;               // [3][W + 2][GC_PITCH]
+constexpr int GC_TR = 4, GC_TC = 16;  // the tile: rows x columns
+constexpr int GC_NT = 512, GC_SLOTS = GC_NT / GC_TC, GC_CPS = GC_CH / GC_SLOTS;  // threads, channel slots, channels per slot and chunk
+constexpr int GC_ITEMS = (GC_TR + 2) * (GC_TC + 2) * (GC_CH / 4);                // float4 of a chunk's tile
+constexpr int GC_NLD = (GC_ITEMS + GC_NT - 1) / GC_NT;                           // ... per thread (4, the last one partly)
+constexpr int GC_NWV = (4 * GC_CH * 9 + GC_NT - 1) / GC_NT;                      // weights of a chunk per thread (5, the last one partly)
+constexpr int GC_TILE_FLOATS = (GC_TR + 2) * (GC_TC + 2) * GC_PITCH;
+constexpr int GC_RED_FLOATS = GC_SLOTS * GC_TR * GC_TC * 4;  // the partial sums at the end: [slot][pixel][4]
+static_assert(GC_CPS == 2, "a lane reads its two channels of a pixel as one float2");
+
+// lane i of a DPP row (16 lanes) gets v of lane i - 1 (shr) / i + 1 (shl); the lane without such a neighbour keeps `old`
+__device__ __forceinline__ float gc_from_left(float old, float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x111, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float gc_from_right(float old, float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x101, 0xf, 0xf, false));
+}
+
+__global__ void __launch_bounds__(GC_NT) gn_conv_few_kernel(const float* __restrict__ x, int ld, int H, int W, int c, int cpg, int nchunk,
+                                                           int part_cpg, const double* __restrict__ part,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                           int silu, const float* __restrict__ w, const float* __restrict__ bias, int oc,
+                                                           float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float s_t[GC_TILE_FLOATS > GC_RED_FLOATS ? GC_TILE_FLOATS : GC_RED_FLOATS];
+    __shared__ __attribute__((aligned(16))) float s_w[GC_CH * 9 * 4];  // [channel][tap][4]: this chunk's weights
     __shared__ float s_mean[32], s_rstd[32];
-    // grid (batch, H): consecutive workgroup ids = consecutive samples, so the rows of one sample - each of which is read by the
-    // workgroups of the rows above and below too - are dealt to the same XCD and re-read from its L2 (with (H, batch) the eight rows
-    // of a sample went to eight XCDs: 58.8 MB fetched for a 21 MB input)
-    const int b = blockIdx.x, y = blockIdx.y, tid = threadIdx.x;
+    // grid.x = batch: consecutive workgroup ids = consecutive samples, so the tiles of one sample - whose halos overlap - are dealt
+    // to the same XCD and re-read from its L2
+    const int b = blockIdx.x, x0 = blockIdx.y * GC_TC, y0 = blockIdx.z * GC_TR, tid = threadIdx.x;
     const int hw = H * W, ng = c / cpg;
-    // this thread's share of a chunk's three rows: item i = tid + 256 k -> (row r, pixel px, channel quad c4)
-    float4 pv[NLD];
-    auto request = [&](int c0) {
-#pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int i = tid + 256 * k;
-            const int r = i / (PXL * (GC_CH / 4)), rem = i - r * (PXL * (GC_CH / 4));
-            const int px = rem / (GC_CH / 4), c4 = rem - px * (GC_CH / 4);
-            const int yy = y + r - 1;
-            pv[k] = (yy >= 0 && yy < H && px < W)
-                        ? *reinterpret_cast<const float4*>(x + ((long)b * hw + (long)yy * W + px) * ld + c0 + c4 * 4)
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+    // what a thread brings in for a chunk: its share of the tile (item i = tid + 512 k -> tile row r, tile column px, channel quad
+    // c4 - the same quad for all of them, 512 being a multiple of the 16 quads of a chunk), of the weights, and gamma / beta of its
+    // quad.  Two chunks are in flight: chunk i + 2 is requested when chunk i has been written to LDS.
+    struct Pre {
+        float4 pv[GC_NLD], ga, be;
+        float wv[GC_NWV];
     };
-    request(0);
-    if (tid < ng) {
-        const int ratio = cpg / part_cpg, ngs = c / part_cpg;
-        double ds = 0.0, dq = 0.0;
-        for (int j = 0; j < nchunk; ++j) {
-            const double* p = part + (((long)b * nchunk + j) * ngs + tid * ratio) * 2;
-            for (int k = 0; k < ratio; ++k) {
-                ds += p[2 * k];
-                dq += p[2 * k + 1];
+    const int cq = (tid & (GC_CH / 4 - 1)) * 4;
+    // Every load is unconditional and in bounds - coordinates outside the image are clamped onto it (their values are never used:
+    // the tile gets zeros there), a chunk past the last one re-reads the last - so that the requests are straight-line code and
+    // the compiler's vmcnt bookkeeping can wait for the older chunk while the newer one is still in flight (a branch around a load
+    // makes it wait for everything).
+    auto request = [&](Pre& P, int c0w) {
+        const int c0 = min(c0w, c - GC_CH);
+#pragma unroll
+        for (int k = 0; k < GC_NLD; ++k) {
+            const int i = tid + GC_NT * k;
+            const int r = i / ((GC_TC + 2) * (GC_CH / 4)), rem = i - r * ((GC_TC + 2) * (GC_CH / 4));
+            const int px = rem / (GC_CH / 4), c4 = rem - px * (GC_CH / 4);
+            const int yy = min(max(y0 + r - 1, 0), H - 1), xx = min(max(x0 + px - 1, 0), W - 1);
+            P.pv[k] = *reinterpret_cast<const float4*>(x + ((long)b * hw + (long)yy * W + xx) * ld + c0 + c4 * 4);
+        }
+#pragma unroll
+        for (int k = 0; k < GC_NWV; ++k) {  // weights [o][c0 .. c0+63][9]: contiguous per o
+            const int i = min(tid + GC_NT * k, 4 * GC_CH * 9 - 1);
+            const int o = i / (GC_CH * 9), rem = i - o * (GC_CH * 9);
+            P.wv[k] = w[((long)min(o, oc - 1) * c + c0) * 9 + rem];
+        }
+        P.ga = make_float4(gamma[c0 + cq], gamma[c0 + cq + 1], gamma[c0 + cq + 2], gamma[c0 + cq + 3]);
+        P.be = make_float4(beta[c0 + cq], beta[c0 + cq + 1], beta[c0 + cq + 2], beta[c0 + cq + 3]);
+    };
+    Pre pa, pb;
+    request(pa, 0);
+    request(pb, GC_CH);
+    // mean and 1 / std of the groups: 16 threads per group fold the chunk partials (one global round trip for up to 16 chunks
+    // instead of one per chunk), one thread sums their sixteen terms in order
+    {
+        double* s_ps = reinterpret_cast<double*>(s_t);  // [16][32][2]
+        const int g = tid & 31, jl = tid >> 5;
+        if (g < ng) {
+            const int ratio = cpg / part_cpg, ngs = c / part_cpg;
+            double ds = 0.0, dq = 0.0;
+            for (int j = jl; j < nchunk; j += GC_NT / 32) {
+                const double* p = part + (((long)b * nchunk + j) * ngs + g * ratio) * 2;
+                for (int k = 0; k < ratio; ++k) {
+                    ds += p[2 * k];
+                    dq += p[2 * k + 1];
+                }
             }
+            s_ps[(jl * 32 + g) * 2] = ds;
+            s_ps[(jl * 32 + g) * 2 + 1] = dq;
         }
-        const double n = (double)hw * cpg;
-        const double mean = ds / n;
-        double var = dq / n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        s_mean[tid] = (float)mean;
-        s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+        __syncthreads();
+        if (tid < ng) {
+            double ds = 0.0, dq = 0.0;
+            for (int l = 0; l < GC_NT / 32; ++l) {
+                ds += s_ps[(l * 32 + tid) * 2];
+                dq += s_ps[(l * 32 + tid) * 2 + 1];
+            }
+            const double n = (double)hw * cpg;
+            const double mean = ds / n;
+            double var = dq / n - mean * mean;
+            if (var < 0.0) var = 0.0;
+            s_mean[tid] = (float)mean;
+            s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+        }
     }
-    // the tile's halo columns and the weight slots of o >= oc stay zero for the whole kernel
-    for (int i = tid; i < 3 * 2 * (GC_CH / 4); i += 256) {
-        const int r = i / (2 * (GC_CH / 4)), rem = i - r * (2 * (GC_CH / 4));
-        const int side = rem / (GC_CH / 4), c4 = rem - side * (GC_CH / 4);
-        *reinterpret_cast<float4*>(s_t + ((long)r * (W + 2) + (side ? W + 1 : 0)) * GC_PITCH + c4 * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (int i = tid; i < 9 * GC_CH; i += 256) *reinterpret_cast<float4*>(s_w + (long)i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    const int pl = tid % PXL, cg = tid / PXL;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int c0 = 0; c0 < c; c0 += GC_CH) {
-        // ---- this chunk: weights [o][c0 .. c0+63][9] (contiguous per o) -> [channel][tap][4]; rows normalised (+ SiLU) -> tile
-        for (int i = tid; i < oc * GC_CH * 9; i += 256) {
+    const int lx = tid & (GC_TC - 1), slot = tid / GC_TC;
+    const bool edge = lx == 0 || lx == GC_TC - 1;
+    // this lane's column in tile row 0 (row r is r * 18 pixels on), and the halo column next to it (read by the lanes at the
+    // ends of a row only); its channels' weights
+    const float* at = s_t + (lx + 1) * GC_PITCH + slot * GC_CPS;
+    const float* ah = s_t + (lx == 0 ? 0 : GC_TC + 1) * GC_PITCH + slot * GC_CPS;
+    const float* wt = s_w + slot * GC_CPS * 36;
+    float acc[GC_TR][4];
+#pragma unroll
+    for (int r = 0; r < GC_TR; ++r)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[r][o] = 0.f;
+    auto chunk = [&](Pre& P, int c0) {
+        // ---- this chunk: weights -> [channel][tap][4] (the slots of o >= oc zero); tile normalised (+ SiLU), zero outside the image
+#pragma unroll
+        for (int k = 0; k < GC_NWV; ++k) {
+            const int i = tid + GC_NT * k;
             const int o = i / (GC_CH * 9), rem = i - o * (GC_CH * 9);  // rem = channel * 9 + tap: the parameter's own order
-            s_w[rem * 4 + o] = w[((long)o * c + c0) * 9 + rem];
+            if (o < 4) s_w[rem * 4 + o] = o < oc ? P.wv[k] : 0.f;
         }
-        // (the channel quad of a thread's items is the same for all of them: 256 is a multiple of the 16 quads of a chunk)
         float sc[4], sh[4];
         {
-            const int ch = c0 + (tid & (GC_CH / 4 - 1)) * 4;
+            const float ga[4] = {P.ga.x, P.ga.y, P.ga.z, P.ga.w}, be[4] = {P.be.x, P.be.y, P.be.z, P.be.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int g = (ch + j) / cpg;
-                sc[j] = s_rstd[g] * gamma[ch + j];
-                sh[j] = beta[ch + j] - s_mean[g] * sc[j];
+                const int g = (c0 + cq + j) / cpg;
+                sc[j] = s_rstd[g] * ga[j];
+                sh[j] = be[j] - s_mean[g] * sc[j];
             }
         }
 #pragma unroll
-        for (int k = 0; k < NLD; ++k) {
-            const int i = tid + 256 * k;
-            const int r = i / (PXL * (GC_CH / 4)), rem = i - r * (PXL * (GC_CH / 4));
+        for (int k = 0; k < GC_NLD; ++k) {
+            const int i = tid + GC_NT * k;
+            if (i >= GC_ITEMS) continue;
+            const int r = i / ((GC_TC + 2) * (GC_CH / 4)), rem = i - r * ((GC_TC + 2) * (GC_CH / 4));
             const int px = rem / (GC_CH / 4), c4 = rem - px * (GC_CH / 4);
-            const int yy = y + r - 1;
-            if (px >= W) continue;
+            const int yy = y0 + r - 1, xx = x0 + px - 1;
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (yy >= 0 && yy < H) {
-                const float4 v = pv[k];
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const float4 v = P.pv[k];
                 o = make_float4(v.x * sc[0] + sh[0], v.y * sc[1] + sh[1], v.z * sc[2] + sh[2], v.w * sc[3] + sh[3]);
                 if (silu) {
                     o.x = wd_silu(o.x); o.y = wd_silu(o.y); o.z = wd_silu(o.z); o.w = wd_silu(o.w);
                 }
             }
-            *reinterpret_cast<float4*>(s_t + ((long)r * (W + 2) + px + 1) * GC_PITCH + c4 * 4) = o;
+            *reinterpret_cast<float4*>(s_t + (r * (GC_TC + 2) + px) * GC_PITCH + c4 * 4) = o;
         }
-        if (c0 + GC_CH < c) request(c0 + GC_CH);  // in flight while this chunk is multiplied
+        request(P, c0 + 2 * GC_CH);  // in flight while this chunk and the next are multiplied
         __syncthreads();
-        if (pl < W) {
+        // ---- every lane multiplies (a lane outside the image sees zeros and stores nothing): the row shifts need all 64
+        float a[GC_TR + 2][3][GC_CPS];  // [tile row][dx][channel of the slot]
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+        for (int r = 0; r < GC_TR + 2; ++r) {
+            const float2 ce = *reinterpret_cast<const float2*>(at + r * (GC_TC + 2) * GC_PITCH);
+            float2 ha = make_float2(0.f, 0.f);
+            if (edge) ha = *reinterpret_cast<const float2*>(ah + r * (GC_TC + 2) * GC_PITCH);
+            a[r][1][0] = ce.x; a[r][1][1] = ce.y;
+            a[r][0][0] = gc_from_left(ha.x, ce.x); a[r][0][1] = gc_from_left(ha.y, ce.y);
+            a[r][2][0] = gc_from_right(ha.x, ce.x); a[r][2][1] = gc_from_right(ha.y, ce.y);
+        }
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const float* at = s_t + ((long)dy * (W + 2) + pl + dx) * GC_PITCH + cg * CPT;
-                    const float* wt = s_w + ((long)(cg * CPT) * 9 + dy * 3 + dx) * 4;
+        for (int j = 0; j < GC_CPS; ++j)
 #pragma unroll
-                    for (int k = 0; k < CPT / 4; ++k) {
-                        const float4 a = *reinterpret_cast<const float4*>(at + 4 * k);
-                        const float4 w0 = *reinterpret_cast<const float4*>(wt + (4 * k + 0) * 36);
-                        const float4 w1 = *reinterpret_cast<const float4*>(wt + (4 * k + 1) * 36);
-                        const float4 w2 = *reinterpret_cast<const float4*>(wt + (4 * k + 2) * 36);
-                        const float4 w3 = *reinterpret_cast<const float4*>(wt + (4 * k + 3) * 36);
-                        acc.x += a.x * w0.x; acc.y += a.x * w0.y; acc.z += a.x * w0.z; acc.w += a.x * w0.w;
-                        acc.x += a.y * w1.x; acc.y += a.y * w1.y; acc.z += a.y * w1.z; acc.w += a.y * w1.w;
-                        acc.x += a.z * w2.x; acc.y += a.z * w2.y; acc.z += a.z * w2.z; acc.w += a.z * w2.w;
-                        acc.x += a.w * w3.x; acc.y += a.w * w3.y; acc.z += a.w * w3.z; acc.w += a.w * w3.w;
-                    }
+            for (int t = 0; t < 9; ++t) {
+                const float4 w4 = *reinterpret_cast<const float4*>(wt + (j * 9 + t) * 4);
+#pragma unroll
+                for (int r = 0; r < GC_TR; ++r) {
+                    const float v = a[r + t / 3][t % 3][j];
+                    acc[r][0] += v * w4.x; acc[r][1] += v * w4.y; acc[r][2] += v * w4.z; acc[r][3] += v * w4.w;
                 }
-        }
+            }
         __syncthreads();
+    };
+    for (int c0 = 0;; c0 += 2 * GC_CH) {  // (no branch joins behind a request: see there)
+        chunk(pa, c0);
+        if (c0 + GC_CH >= c) break;
+        chunk(pb, c0 + GC_CH);
+        if (c0 + 2 * GC_CH >= c) break;
     }
-    // ---- sum the channel groups in a fixed order, add the bias, write NCHW
-    float* s_red = s_t;  // [CG][PXL][4]
-    *reinterpret_cast<float4*>(s_red + ((long)cg * PXL + pl) * 4) = acc;
+    // ---- sum the channel slots in a fixed order, add the bias, write NCHW
+    float* s_red = s_t;  // [slot][tile pixel = r * 16 + x][4]
+#pragma unroll
+    for (int r = 0; r < GC_TR; ++r)
+        *reinterpret_cast<float4*>(s_red + ((slot * GC_TR + r) * GC_TC + lx) * 4) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
     __syncthreads();
-    for (int i = tid; i < W * oc; i += 256) {
-        const int o = i / W, px = i - o * W;
+    for (int i = tid; i < GC_TR * GC_TC * oc; i += GC_NT) {
+        const int o = i / (GC_TR * GC_TC), p = i - o * (GC_TR * GC_TC);
+        const int yy = y0 + p / GC_TC, xx = x0 + p % GC_TC;
+        if (yy >= H || xx >= W) continue;
         float v = bias ? bias[o] : 0.f;
-        for (int g = 0; g < CG; ++g) v += s_red[((long)g * PXL + px) * 4 + o];
-        out[(((long)b * oc + o) * H + y) * W + px] = v;
+        for (int g = 0; g < GC_SLOTS; ++g) v += s_red[(g * GC_TR * GC_TC + p) * 4 + o];
+        out[(((long)b * oc + o) * H + yy) * W + xx] = v;
     }
 }
 
@@ -434,12 +501,8 @@ extern "C" int wd_gn_apply2(const float* xa, int lda, int ca, const double* part
     return wd_check_launch();
 }
 
-// the tile region doubles as the [row][channel group][pixel lane][4] reduction image at the end
-static int gn_conv_tile_floats(int w) { return 3 * (w + 2) * GC_PITCH > 1024 ? 3 * (w + 2) * GC_PITCH : 1024; }
-
 extern "C" int wd_gn_conv3x3_few_supported(int c, int w, int oc) {
-    return c > 0 && c % GC_CH == 0 && w > 0 && w <= 64 && oc >= 1 && oc <= 4 &&
-           (size_t)(9 * GC_CH * 4 + gn_conv_tile_floats(w)) * sizeof(float) <= 64 * 1024;
+    return c > 0 && c % GC_CH == 0 && w > 0 && w <= 64 && oc >= 1 && oc <= 4;
 }
 
 extern "C" int wd_gn_conv3x3_few(const float* x, int ld, int batch, int h, int w, int c, int cpg, const double* part, int nchunk,
@@ -447,15 +510,11 @@ extern "C" int wd_gn_conv3x3_few(const float* x, int ld, int batch, int h, int w
                                  const float* bias, int oc, float* out, void* stream) {
     if (!x || !part || !gamma || !beta || !weight || !out || batch <= 0 || h <= 0 || nchunk <= 0 || part_cpg <= 0) return WD_EINVAL;
     if (!wd_gn_conv3x3_few_supported(c, w, oc) || ld % 4 || cpg <= 0 || c % cpg || c / cpg > 32 || cpg % part_cpg) return WD_EINVAL;
+    if ((h + GC_TR - 1) / GC_TR > 65535) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const size_t smem = (size_t)(9 * GC_CH * 4 + gn_conv_tile_floats(w)) * sizeof(float);  // <= 64 KB: no attribute needed
     WdLaunchScope scope(WD_CLS_OTHER, st);
-    if (w <= 32)
-        hipLaunchKernelGGL(gn_conv_few_kernel<32>, dim3(batch, h), dim3(256), smem, st, x, ld, h, w, c, cpg, nchunk, part_cpg, part,
-                           gamma, beta, eps, silu, weight, bias, oc, out);
-    else
-        hipLaunchKernelGGL(gn_conv_few_kernel<64>, dim3(batch, h), dim3(256), smem, st, x, ld, h, w, c, cpg, nchunk, part_cpg, part,
-                           gamma, beta, eps, silu, weight, bias, oc, out);
+    hipLaunchKernelGGL(gn_conv_few_kernel, dim3(batch, (w + GC_TC - 1) / GC_TC, (h + GC_TR - 1) / GC_TR), dim3(GC_NT), 0, st, x, ld, h,
+                       w, c, cpg, nchunk, part_cpg, part, gamma, beta, eps, silu, weight, bias, oc, out);
     return wd_check_launch();
 }
 

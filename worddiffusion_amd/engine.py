@@ -386,6 +386,7 @@ class UNetEngine:
         # feed-forward, proj_out) as one wd_ff_fused launch per 64-token panel; 0: the three-launch chain
         self.fuse_st = os.environ.get("WDIFF_FUSE_ST", "1") != "0"
         self.fuse_out = os.environ.get("WDIFF_FUSE_OUT", "1") != "0"
+        self.fuse_in = os.environ.get("WDIFF_FUSE_IN", "1") != "0"         # the first convolution as one direct fp32 launch
         self.pack_kv = os.environ.get("WDIFF_PACK_KV", "1") != "0"         # long-context cross-attention: K/V images built once per call
         self.fuse_gn2 = os.environ.get("WDIFF_FUSE_GN2", "1") != "0"       # GroupNorm over [h | skip]: one apply launch for both
         self.fuse_gn = os.environ.get("WDIFF_FUSE_GN", "1") != "0"         # GroupNorm in the producer's split-K combine launch
@@ -417,6 +418,7 @@ class UNetEngine:
         self.kpad_in = ((9 * cin_conv.in_channels + 31) // 32) * 32
         R.matrix("in.w", cin_conv.out_channels, self.kpad_in).fwd(cin_conv.weight)
         R.vector("in.b", cin_conv.bias)
+        R.vector("in.w.f32", cin_conv.weight)  # the direct first convolution reads the parameter layout itself
         R.linear("te0", m.time_embed[0])
         R.linear("te2", m.time_embed[2])
         if m.num_classes is not None:
@@ -1446,13 +1448,27 @@ class UNetEngine:
                        out_f32=self._film, out_ld=self.film_total)
 
         # ---- trunk
-        xin = self._planes(P, B * H * W, self.kpad_in)
-        step.append((lib.wd_im2col3x3, (P.x_in.data_ptr(), B, m.in_channels, H, W, xin[0].data_ptr(),
-                                        xin[1].data_ptr() if lo_ok else None, self.kpad_in), "im2col"))
         h0 = self._f32(P, B * H * W, mc)
-        g0 = self._gemm(step, "input_blocks.0", [self._src(xin, self.kpad_in)], "in.w", B * H * W, H * W,
-                        bias=self._w["in.b"], out_f32=h0, out_ld=mc, want_stats=True)
-        cur = Act(h0, mc, H, W, g0._stats)
+        if self.fuse_in and self.variant != "phosc" and lib.wd_conv3x3_in_supported(m.in_channels, H, W, mc) and mc % 32 == 0:
+            # the 4-channel 3x3 as a direct fp32 convolution: no im2col planes, and the statistics partials of the consumer's
+            # GroupNorm (32 groups) in the layout the GEMM's epilogue gives them
+            stats = None
+            if self.fuse_stats:
+                nchunk = lib.wd_conv3x3_in_nchunk(H * W)
+                part = torch.zeros((B, nchunk, 32, 2), dtype=torch.float64, device=dev)
+                P.keep.append(part)
+                stats = (part, nchunk, mc // 32)
+            step.append((lib.wd_conv3x3_in, (P.x_in.data_ptr(), B, m.in_channels, H, W, self._w["in.w.f32"].data_ptr(),
+                                             self._w["in.b"].data_ptr(), mc, h0.data_ptr(), mc,
+                                             stats[0].data_ptr() if stats else None, mc // 32), "input_blocks.0: conv3x3 from NCHW"))
+            cur = Act(h0, mc, H, W, stats)
+        else:
+            xin = self._planes(P, B * H * W, self.kpad_in)
+            step.append((lib.wd_im2col3x3, (P.x_in.data_ptr(), B, m.in_channels, H, W, xin[0].data_ptr(),
+                                            xin[1].data_ptr() if lo_ok else None, self.kpad_in), "im2col"))
+            g0 = self._gemm(step, "input_blocks.0", [self._src(xin, self.kpad_in)], "in.w", B * H * W, H * W,
+                            bias=self._w["in.b"], out_f32=h0, out_ld=mc, want_stats=True)
+            cur = Act(h0, mc, H, W, g0._stats)
         hs = [cur]
 
         def run_layers(prefix, blk, cur, extra=None):
