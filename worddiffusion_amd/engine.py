@@ -634,6 +634,13 @@ class UNetEngine:
         P.keep.append(t)
         return t
 
+    def _hilo(self, planes: Optional[torch.Tensor], byte_off: int = 0):
+        """(hi, lo) pointers of operand planes [2, rows, ld] for a kernel: the low plane exists in three-pass mode only (lo is
+        None otherwise); (None, None) for no planes at all."""
+        if planes is None:
+            return None, None
+        return planes[0].data_ptr() + byte_off, (planes[1].data_ptr() + byte_off if self.npass == 3 else None)
+
     def _src(self, planes: torch.Tensor, c: int, ntaps: int = 1, gather: Optional[torch.Tensor] = None,
              hw_src: int = 0, col_off: int = 0) -> N.WdSrc:
         s = N.WdSrc()
@@ -821,14 +828,7 @@ class UNetEngine:
         pl = self._planes(P, B * hw, ctot)
         raw = self._planes(P, B * hw, ctot) if want_raw else None
         for s in srcs:
-            if s.stats is None:  # no producer-side statistics: one pass over the tensor (32 groups of c/32 channels)
-                nchunk = self.lib.wd_gn_nchunk(hw)
-                pc = s.c // 32
-                part = torch.empty((B, nchunk, 32, 2), dtype=torch.float64, device=self.device)
-                P.keep.append(part)
-                ops.append((self.lib.wd_gn_stats, (s.t.data_ptr(), s.c, B, hw, s.c, pc, part.data_ptr()),
-                            what + ":stats"))
-                s.stats = (part, nchunk, pc)
+            self._gn_stats(P, ops, what, s)
         coff = 0
         gam, bet = self._w[gname + ".g"], self._w[gname + ".b"]
         todo = []  # (source, part, nchunk, pc, coff) of the sources that need an apply launch
@@ -848,14 +848,13 @@ class UNetEngine:
             if has_perm or not self._gn_in_combine(s, raw, gam, bet, eps, silu, cpg, pl, coff):
                 todo.append((s, part, nchunk, pc, coff))
             coff += s.c
-        lo = pl[1].data_ptr() if self.npass == 3 else None
-        rhi = raw[0].data_ptr() if raw is not None else None
-        rlo = raw[1].data_ptr() if (raw is not None and self.npass == 3) else None
+        hi, lo = self._hilo(pl)
+        rhi, rlo = self._hilo(raw)
         if len(todo) == 2 and self.fuse_gn2:  # [h | skip] of a decoder block: one launch for both halves of the concat
             (sa, pa, na, pca, ca), (sb, pb, nb_, pcb, cb) = todo
             ops.append((self.lib.wd_gn_apply2,
                         (sa.t.data_ptr(), sa.c, sa.c, pa.data_ptr(), na, pca, ca, sb.t.data_ptr(), sb.c, sb.c, pb.data_ptr(), nb_, pcb, cb,
-                         B, hw, cpg, gam.data_ptr(), bet.data_ptr(), eps, int(silu), pl[0].data_ptr(), lo, ctot, rhi, rlo,
+                         B, hw, cpg, gam.data_ptr(), bet.data_ptr(), eps, int(silu), hi, lo, ctot, rhi, rlo,
                          sa.perm.data_ptr() if sa.perm is not None else None),
                         what + ":apply"))
         else:
@@ -863,8 +862,20 @@ class UNetEngine:
             for s, part, nchunk, pc, c0 in todo:
                 ops.append((self.lib.wd_gn_apply,
                             (s.t.data_ptr(), s.c, B, hw, s.c, cpg, part.data_ptr(), nchunk, pc, gam.data_ptr(), bet.data_ptr(), eps,
-                             int(silu), pl[0].data_ptr(), lo, ctot, c0, rhi, rlo), what + ":apply"))
+                             int(silu), hi, lo, ctot, c0, rhi, rlo), what + ":apply"))
         return pl, raw
+
+    def _gn_stats(self, P, ops, what, s: Act):
+        """GroupNorm statistics of a map whose producer left none: one pass over the tensor (32 groups of c/32 channels)."""
+        if s.stats is None:
+            B, hw = self._B, s.h * s.w
+            nchunk = self.lib.wd_gn_nchunk(hw)
+            pc = s.c // 32
+            part = torch.empty((B, nchunk, 32, 2), dtype=torch.float64, device=self.device)
+            P.keep.append(part)
+            ops.append((self.lib.wd_gn_stats, (s.t.data_ptr(), s.c, B, hw, s.c, pc, part.data_ptr()), what + ":stats"))
+            s.stats = (part, nchunk, pc)
+        return s.stats
 
     def _gn_in_consumer(self, P, ops, what, srcs: List[Act], want_raw, M, hw, ncols, taps=1, gather=None) -> bool:
         """Can the convolution that consumes this GroupNorm (``what``: also the norm's name) apply it itself (wd_gemm_args.a32*)?
@@ -880,13 +891,7 @@ class UNetEngine:
         if not wdirect_fills_chip(M, ncols):
             return False
         s = srcs[0]
-        if s.stats is None:  # no producer-side statistics: one pass over the tensor
-            nchunk = self.lib.wd_gn_nchunk(hw)
-            pc = s.c // 32
-            part = torch.empty((self._B, nchunk, 32, 2), dtype=torch.float64, device=self.device)
-            P.keep.append(part)
-            ops.append((self.lib.wd_gn_stats, (s.t.data_ptr(), s.c, self._B, hw, s.c, pc, part.data_ptr()), what + ":stats"))
-            s.stats = (part, nchunk, pc)
+        self._gn_stats(P, ops, what, s)
         return self._wdirect_ok([self._src32(s, taps, gather, hw)], M, ncols, hw, a32=(s, what, 0.0, False))
 
     def _src32(self, x: Act, ntaps=1, gather=None, hw_src=0) -> N.WdSrc:
@@ -907,15 +912,15 @@ class UNetEngine:
             return False
         if pr.out_f32 != s.t.data_ptr() or pr.out_hi or pr.gn_gamma or pr.n != s.c:
             return False
+        hi, lo = self._hilo(pl, 2 * coff)
         return self._legal(pr, gn_gamma=gam.data_ptr() + 4 * coff, gn_beta=bet.data_ptr() + 4 * coff, gn_eps=float(eps),
-                           gn_silu=int(silu), gn_cpg=cpg, out_hi=pl[0].data_ptr() + 2 * coff,
-                           out_lo=(pl[1].data_ptr() + 2 * coff) if self.npass == 3 else None, out_pl_ld=pl.shape[2])
+                           gn_silu=int(silu), gn_cpg=cpg, out_hi=hi, out_lo=lo, out_pl_ld=pl.shape[2])
 
     def _ln(self, P, ops, what, x: torch.Tensor, rows, c, name):
         pl = self._planes(P, rows, c)
         ops.append((self.lib.wd_layernorm,
                     (x.data_ptr(), c, rows, c, self._w[name + ".g"].data_ptr(), self._w[name + ".b"].data_ptr(), 1e-5,
-                     pl[0].data_ptr(), pl[1].data_ptr() if self.npass == 3 else None, c), what))
+                     *self._hilo(pl), c), what))
         return pl
 
     # ------------------------------------------------------------------------------------------ blocks
@@ -971,11 +976,10 @@ class UNetEngine:
         if (pr is not None and self.fuse_split and not pr.out_hi and pr.out_f32 == x.t.data_ptr() and
                 (pr.n if isinstance(pr, N.WdGemmArgs) else pr.c) == x.c):
             # the producing GEMM writes the planes beside its fp32 output (one launch and one pass over the tensor less)
-            pr.out_hi, pr.out_lo = pl[0].data_ptr(), (pl[1].data_ptr() if self.npass == 3 else None)
+            pr.out_hi, pr.out_lo = self._hilo(pl)
             pr.out_pl_ld = x.c
         else:
-            ops.append((self.lib.wd_split, (x.t.data_ptr(), x.c, B * x.h * x.w, x.c, 0, pl[0].data_ptr(),
-                                            pl[1].data_ptr() if self.npass == 3 else None, x.c), name + ":split"))
+            ops.append((self.lib.wd_split, (x.t.data_ptr(), x.c, B * x.h * x.w, x.c, 0, *self._hilo(pl), x.c), name + ":split"))
         out = self._f32(P, B * ho * wo, mod.cout)
         hw = x.h * x.w
         src4 = None
@@ -1012,11 +1016,25 @@ class UNetEngine:
                    out_rows=None, out_row0=0):
         B = self._B
         ops.append((self.lib.wd_attention,
-                    (q, ldq, k, ldk, v, ldv, B, heads, nq, nk, d, float(scale), _ptr(out_f32),
-                     out_pl[0].data_ptr() if out_pl is not None else None,
-                     out_pl[1].data_ptr() if (out_pl is not None and self.npass == 3) else None,
+                    (q, ldq, k, ldk, v, ldv, B, heads, nq, nk, d, float(scale), _ptr(out_f32), *self._hilo(out_pl),
                      out_pl.shape[2] if out_pl is not None else out_f32.shape[-1],
                      nq if out_rows is None else out_rows, out_row0), what))
+
+    def _xattn_fold(self, P, at, heads, d):
+        """K/V/to_q/to_out of the cross-attention ``at`` (its ``kv_off`` key) folded per sample in the conditioning phase
+        (csrc/wd_xattn.hip): (mq, mo) fp32 and their MFMA operand images (mq_pl, mot_pl)."""
+        B, L, inner = self._B, self._ctx_len, heads * d
+        ko = self.kv_off[at]
+        mq = self._f32(P, B, heads * L, inner)
+        mo = self._f32(P, B, heads * L, inner)
+        mq_pl = torch.zeros((B, 2, 64, inner), dtype=torch.bfloat16, device=self.device)   # MFMA operands (padded rows 0)
+        mot_pl = torch.zeros((B, 2, inner, 64), dtype=torch.bfloat16, device=self.device)
+        P.keep += [mq_pl, mot_pl]
+        P.cond.append((self.lib.wd_xattn_fold,
+                       (self._kv.data_ptr() + 4 * ko, self.kv_total, self._kv.data_ptr() + 4 * (ko + inner), self.kv_total, B,
+                        heads, L, d, float(d ** -0.5), self._w[at + ".q.f32"].data_ptr(), self._w[at + ".o.f32"].data_ptr(), inner,
+                        mq.data_ptr(), mo.data_ptr(), mq_pl.data_ptr(), mot_pl.data_ptr()), at + ":fold"))
+        return mq, mo, mq_pl, mot_pl
 
     def _transformer(self, P, name, mod: SpatialTransformerParams, x: Act) -> Act:
         ops = P.step
@@ -1046,49 +1064,32 @@ class UNetEngine:
         xpl = None
         fuse = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))
 
-        def fold(tag, p):
-            """K/V/to_q/to_out of one cross-attention folded per sample in the conditioning phase (csrc/wd_xattn.hip)."""
-            ko = self.kv_off[f"{p}.{tag}"]
-            mq = self._f32(P, B, heads * L, inner)
-            mo = self._f32(P, B, heads * L, inner)
-            mq_pl = torch.zeros((B, 2, 64, inner), dtype=torch.bfloat16, device=self.device)   # MFMA operands (padded rows 0)
-            mot_pl = torch.zeros((B, 2, inner, 64), dtype=torch.bfloat16, device=self.device)
-            P.keep += [mq_pl, mot_pl]
-            P.cond.append((self.lib.wd_xattn_fold,
-                           (self._kv.data_ptr() + 4 * ko, self.kv_total, self._kv.data_ptr() + 4 * (ko + inner), self.kv_total, B,
-                            heads, L, d, float(d ** -0.5), self._w[f"{p}.{tag}.q.f32"].data_ptr(),
-                            self._w[f"{p}.{tag}.o.f32"].data_ptr(), inner, mq.data_ptr(), mo.data_ptr(), mq_pl.data_ptr(),
-                            mot_pl.data_ptr()), f"{p}.{tag}:fold"))
-            return mq, mo, mq_pl, mot_pl
-
         def folded(tag, p, x_in, x_out, ln_name, next_ln=None):
             """x_out = x_in + to_out(attention(to_q(LN(x_in)), K, V)) in one launch.  next_ln: also emit the following
             LayerNorm as operand planes."""
-            mq, mo, mq_pl, mot_pl = fold(tag, p)
+            mq, mo, mq_pl, mot_pl = self._xattn_fold(P, f"{p}.{tag}", heads, d)
             npl = self._planes(P, M, inner) if next_ln else None
             ops.append((self.lib.wd_xattn_fused,
                         (x_in.data_ptr(), inner, B, hw, inner, self._w[f"{p}.{ln_name}.g"].data_ptr(),
                          self._w[f"{p}.{ln_name}.b"].data_ptr(), 1e-5, mq.data_ptr(), mo.data_ptr(), heads, L,
                          self._w[f"{p}.{tag}.o.b"].data_ptr(), x_out.data_ptr(), inner,
                          self._w[f"{p}.{next_ln}.g"].data_ptr() if next_ln else None,
-                         self._w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5,
-                         npl[0].data_ptr() if next_ln else None,
-                         npl[1].data_ptr() if (next_ln and self.npass == 3) else None, inner, mq_pl.data_ptr(), mot_pl.data_ptr()),
+                         self._w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5, *self._hilo(npl), inner,
+                         mq_pl.data_ptr(), mot_pl.data_ptr()),
                         f"{p}.{tag}:folded"))
             return npl
 
         def folded_pair(p, x_in, x_out):
             """Both cross-attentions of a base-model block (each behind norm2, unet.py:337-345) and norm3 in one launch."""
-            _, _, qa, oa = fold("a1", p)
-            _, _, qb, ob = fold("a2", p)
+            _, _, qa, oa = self._xattn_fold(P, p + ".a1", heads, d)
+            _, _, qb, ob = self._xattn_fold(P, p + ".a2", heads, d)
             npl = self._planes(P, M, inner)
             g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
             ops.append((self.lib.wd_xattn_pair,
                         (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, g2, b2, qa.data_ptr(), oa.data_ptr(),
                          self._w[f"{p}.a1.o.b"].data_ptr(), g2, b2, qb.data_ptr(), ob.data_ptr(),
                          self._w[f"{p}.a2.o.b"].data_ptr(), x_out.data_ptr(), inner, self._w[f"{p}.norm3.g"].data_ptr(),
-                         self._w[f"{p}.norm3.b"].data_ptr(), 1e-5, npl[0].data_ptr(),
-                         npl[1].data_ptr() if self.npass == 3 else None, inner), f"{p}.a1+a2:folded"))
+                         self._w[f"{p}.norm3.b"].data_ptr(), 1e-5, *self._hilo(npl), inner), f"{p}.a1+a2:folded"))
             return npl
 
         for di, tb in enumerate(mod.transformer_blocks):
@@ -1149,8 +1150,8 @@ class UNetEngine:
                     P.cond.append((self.lib.wd_attention_pack_kv,
                                    (kp, self.kv_total, vp, self.kv_total, B, heads, L, d, img.data_ptr()), p + ".a2:pack kv"))
                     ops.append((self.lib.wd_attention_packed,
-                                (q2.data_ptr(), inner, img.data_ptr(), B, heads, hw, L, d, float(scale), None, o2[0].data_ptr(),
-                                 o2[1].data_ptr() if self.npass == 3 else None, inner, hw, 0), p + ".a2"))
+                                (q2.data_ptr(), inner, img.data_ptr(), B, heads, hw, L, d, float(scale), None, *self._hilo(o2), inner,
+                                 hw, 0), p + ".a2"))
                 else:
                     self._attention(ops, p + ".a2", q2.data_ptr(), inner, kp, self.kv_total, vp, self.kv_total, heads, hw, L, d,
                                     scale, o2)
@@ -1188,23 +1189,10 @@ class UNetEngine:
         """The SpatialTransformer (unet.py:398-412, one base-model block) as ONE wd_ff_fused launch with the transformer front
         (wd_ff_args.x_in): GroupNorm + proj_in, both folded cross-attentions, norm3, the GEGLU feed-forward and proj_out + residual
         per 64-token panel; the GroupNorm statistics of the result for the next ResBlock come out of its epilogue."""
-        B, M, hw, c = self._B, self._B * x.h * x.w, x.h * x.w, x.c
+        M, hw, c = self._B * x.h * x.w, x.h * x.w, x.c
         heads, d, L = mod.heads, mod.d_head, self._ctx_len
         p = name + ".tb0"
-        folds = []
-        for tag in ("a1", "a2"):  # K/V/to_q/to_out folded per sample in the conditioning phase, as in _transformer
-            ko = self.kv_off[f"{p}.{tag}"]
-            mq = self._f32(P, B, heads * L, c)
-            mo = self._f32(P, B, heads * L, c)
-            mq_pl = torch.zeros((B, 2, 64, c), dtype=torch.bfloat16, device=self.device)
-            mot_pl = torch.zeros((B, 2, c, 64), dtype=torch.bfloat16, device=self.device)
-            P.keep += [mq_pl, mot_pl]
-            P.cond.append((self.lib.wd_xattn_fold,
-                           (self._kv.data_ptr() + 4 * ko, self.kv_total, self._kv.data_ptr() + 4 * (ko + c), self.kv_total, B,
-                            heads, L, d, float(d ** -0.5), self._w[f"{p}.{tag}.q.f32"].data_ptr(),
-                            self._w[f"{p}.{tag}.o.f32"].data_ptr(), c, mq.data_ptr(), mo.data_ptr(), mq_pl.data_ptr(),
-                            mot_pl.data_ptr()), f"{p}.{tag}:fold"))
-            folds.append((mq_pl, mot_pl))
+        folds = [self._xattn_fold(P, f"{p}.{tag}", heads, d)[2:] for tag in ("a1", "a2")]
         tok2 = self._f32(P, M, c)
         out = self._f32(P, M, c)
         part, nchunk, pc = x.stats
@@ -1236,9 +1224,8 @@ class UNetEngine:
         of the result for the next ResBlock; returns the statistics tuple then.  front: the wd_ff_args fields of the transformer
         front (n3 is None then: the launch makes the norm3 rows itself)."""
         a = N.WdFfArgs()
-        lo_ok = self.npass == 3
         if front is None:
-            a.x_hi, a.x_lo, a.x_ld = n3[0].data_ptr(), (n3[1].data_ptr() if lo_ok else None), n3.shape[2]
+            (a.x_hi, a.x_lo), a.x_ld = self._hilo(n3), n3.shape[2]
         else:
             for k, v in front.items():
                 setattr(a, k, v)
@@ -1250,7 +1237,7 @@ class UNetEngine:
         if out_f32 is not None:
             a.out_f32, a.out_ld = out_f32.data_ptr(), inner
         if out_pl is not None:
-            a.out_hi, a.out_lo, a.out_pl_ld = out_pl[0].data_ptr(), (out_pl[1].data_ptr() if lo_ok else None), out_pl.shape[2]
+            (a.out_hi, a.out_lo), a.out_pl_ld = self._hilo(out_pl), out_pl.shape[2]
         a.hw_out, a.npass = 1, self.npass
         stats = None
         if proj is not None:
@@ -1271,6 +1258,121 @@ class UNetEngine:
         return a
 
     # ------------------------------------------------------------------------------------------ plan
+    @staticmethod
+    def _cached_plan(plans: Dict[tuple, Plan], key, room: int = 0) -> Optional[Plan]:
+        """The plan kept under ``key`` (now the most recently used one), or None; then, for an engine that keeps at most
+        ``room`` plans, the least recently used ones go before the caller builds its own (a plan holds ~1 GB of buffers at
+        B = 64).  The caller stores what it built as ``plans[key]``."""
+        if key in plans:
+            plans[key] = plans.pop(key)  # most recently used last
+            return plans[key]
+        while room and len(plans) >= room:
+            plans.pop(next(iter(plans)))
+        return None
+
+    def _begin_plan(self, P: Plan, B: int) -> Plan:
+        """Every block builder (_gemm, _gn, _resblock, ...) reads the plan under construction and its batch from the engine."""
+        self._cur_plan = P
+        self._B = B
+        return P
+
+    def _inputs(self, P: Plan, H, W, ctx_len, phosc_len):
+        """Persistent inputs (the caller copies into these, ``load_inputs``; graph replays read them).  An absent token group
+        keeps one column, so that the buffer has an address."""
+        m, B, dev = self.model, self._B, self.device
+        P.x_in = torch.zeros((B, m.in_channels, H, W), dtype=torch.float32, device=dev)
+        P.t_in = torch.zeros((B,), dtype=torch.int64, device=dev)
+        P.y_in = torch.zeros((B,), dtype=torch.int64, device=dev)
+        P.ctx_in = torch.zeros((B, max(ctx_len, 1)), dtype=torch.int64, device=dev)
+        P.phosc_in = torch.zeros((B, max(phosc_len, 1)), dtype=torch.int32, device=dev)
+
+    def _conditioning(self, P: Plan, ops, ctx_len, phosc_len) -> List[tuple]:
+        """CharacterEncoder (unet.py:851-874) of each token group into ``P.ctx_pl`` + K/V of every cross-attention (``self._kv``).
+        Returns (ids, n_tok, row0, i64, embedding planes, qkv) per group: what a backward pass through it reads."""
+        m, lib, B = self.model, self.lib, self._B
+        cd = m.context_dim
+        msl = m.max_seq_len
+        L = self._ctx_len = ctx_len + phosc_len
+        P.ctx_pl = self._planes(P, B * L, cd)
+        groups = []
+        for (ids, n_tok, row0, i64) in ((P.ctx_in, ctx_len, 0, 1), (P.phosc_in, phosc_len, ctx_len, 0)):
+            if n_tok == 0:
+                continue
+            use_pe = (self.variant == "base") or (n_tok <= msl)  # unetPhosc.py:726-729 skips the table for PHOSC vectors
+            if use_pe and n_tok > msl:
+                raise ValueError(f"context length {n_tok} exceeds max_seq_len {msl} (the reference fails too)")
+            e = self._planes(P, B * n_tok, cd)
+            ops.append((lib.wd_embed_tokens,
+                        (ids.data_ptr(), i64, B * n_tok, n_tok, self._w["we.table"].data_ptr(), self._w["we.table"].shape[0], cd,
+                         self._w["pe"].data_ptr() if use_pe else None, *self._hilo(e), cd), "word_emb.embedding"))
+            qkv = self._f32(P, B * n_tok, 3 * cd)
+            self._gemm(ops, "word_emb.qkv", [self._src(e, cd)], "we.qkv.w", B * n_tok, n_tok, bias=self._w["we.qkv.b"],
+                       out_f32=qkv, out_ld=3 * cd)
+            # Word_Attention: softmax(q k^T) v without 1/sqrt(d) (unet.py:831-835)
+            self._attention(ops, "word_emb.attention", qkv.data_ptr(), 3 * cd, qkv.data_ptr() + 4 * cd, 3 * cd,
+                            qkv.data_ptr() + 8 * cd, 3 * cd, 1, n_tok, n_tok, cd, 1.0, P.ctx_pl, out_rows=L, out_row0=row0)
+            groups.append((ids, n_tok, row0, i64, e, qkv))
+        if self.kv_total:
+            self._kv = self._f32(P, B * L, self.kv_total)
+            self._gemm(ops, "cross.kv", [self._src(P.ctx_pl, cd)], "kv.w", B * L, L, out_f32=self._kv, out_ld=self.kv_total)
+        return groups
+
+    def _head_gemm(self, P: Plan, ops, what, x: torch.Tensor, w: str, label="im2col", want_stats=True, tile=0):
+        """3x3 / pad 1 convolution ``w`` (weights ``w``.w over the padded im2col width ``kpad_in``, bias ``w``.b) of an NCHW fp32
+        tensor with few channels: wd_im2col3x3 into operand planes + one GEMM.  Returns the token-major result (with its
+        GroupNorm statistics where wanted and available) and the im2col planes."""
+        B, cin, H, W = x.shape
+        xin = self._planes(P, B * H * W, self.kpad_in)
+        ops.append((self.lib.wd_im2col3x3, (x.data_ptr(), B, cin, H, W, *self._hilo(xin), self.kpad_in), label))
+        cout = self._w[w + ".w"].shape[1]
+        h0 = self._f32(P, B * H * W, cout)
+        g0 = self._gemm(ops, what, [self._src(xin, self.kpad_in)], w + ".w", B * H * W, H * W, bias=self._w[w + ".b"], out_f32=h0,
+                        out_ld=cout, want_stats=want_stats, tile=tile)
+        return Act(h0, cout, H, W, g0._stats), xin
+
+    def _trunk(self, P: Plan, cur: Act) -> Act:
+        """Input blocks after the first convolution, middle block, output blocks over the skip stack."""
+        m = self.model
+        hs = [cur]
+
+        def run_layers(prefix, blk, cur, extra=None):
+            for j, mod in enumerate(blk):
+                name = f"{prefix}.{j}"
+                if isinstance(mod, ResBlockParams):
+                    cur = self._resblock(P, name, mod, [cur] + ([extra] if (extra is not None and j == 0) else []))
+                elif isinstance(mod, SpatialTransformerParams):
+                    cur = self._transformer(P, name, mod, cur)
+                elif isinstance(mod, DownsampleParams):
+                    cur = self._resample(P, name, mod, cur, "down")
+                elif isinstance(mod, UpsampleParams):
+                    cur = self._resample(P, name, mod, cur, "up")
+                else:
+                    raise TypeError(type(mod))
+            return cur
+
+        for i, blk in enumerate(m.input_blocks):
+            if i == 0:
+                continue
+            cur = run_layers(f"in{i}", blk, cur)
+            hs.append(cur)
+        cur = run_layers("mid", m.middle_block, cur)
+        for i, blk in enumerate(m.output_blocks):
+            cur = run_layers(f"out{i}", blk, cur, extra=hs.pop())
+        return cur
+
+    def _tail_gemm(self, P: Plan, ops, what, x: Act, eps, nchw: Optional[torch.Tensor] = None):
+        """GroupNorm ``out.gn`` + SiLU into operand planes, then the 3x3 / pad 1 convolution ``out.w`` as a GEMM into token rows;
+        ``nchw``: the tensor a wd_tokens_to_nchw launch then writes them to.  Returns the planes and the token rows."""
+        B, hw = self._B, x.h * x.w
+        g, _ = self._gn(P, ops, "out.gn", [x], "out.gn", eps, True)
+        tab, _, _ = self._table(x.h, x.w, "same")
+        oc = self._w["out.w"].shape[1]
+        otok = self._f32(P, B * hw, oc)
+        self._gemm(ops, what, [self._src(g, x.c, 9, tab, hw)], "out.w", B * hw, hw, bias=self._w["out.b"], out_f32=otok, out_ld=oc)
+        if nchw is not None:
+            ops.append((self.lib.wd_tokens_to_nchw, (otok.data_ptr(), oc, B, oc, hw, nchw.data_ptr()), "tokens_to_nchw"))
+        return g, otok
+
     def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0,
              film_timesteps: Optional[tuple] = None) -> Plan:
         """film_steps = T > 0 (the DDPM sampler): the whole time / writer embedding path (timestep_embedding, time_embed,
@@ -1291,60 +1393,20 @@ class UNetEngine:
             if not film_steps or not film_timesteps or min(film_timesteps) < 0 or max(film_timesteps) >= film_steps:
                 raise ValueError("film_timesteps needs film_steps = T and timesteps in [0, T)")
             key += (("tau", film_timesteps),)
-        if key in self._plans:
-            self._plans[key] = self._plans.pop(key)  # most recently used last
-            return self._plans[key]
-        while len(self._plans) >= max(1, PLAN_CACHE_SIZE):  # a plan holds ~1 GB of buffers at B = 64: keep a few shapes only
-            self._plans.pop(next(iter(self._plans)))
+        P = self._cached_plan(self._plans, key, room=max(1, PLAN_CACHE_SIZE))
+        if P is not None:
+            return P
         m = self.model
         lib = self.lib
         if ctx_len + phosc_len == 0:
             raise NotImplementedError("context=None: every reference script conditions on the word (unet.py:1605)")
-        P = Plan()
-        self._cur_plan = P
-        self._B = B
-        L = ctx_len + phosc_len
-        self._ctx_len = L
+        P = self._begin_plan(Plan(), B)
         dev = self.device
         mc = m.model_channels
         ted = 4 * mc
-        cd = m.context_dim
-        lo_ok = self.npass == 3
-
-        # ---- persistent inputs (the caller copies into these; graph replays read them)
-        P.x_in = torch.zeros((B, m.in_channels, H, W), dtype=torch.float32, device=dev)
-        P.t_in = torch.zeros((B,), dtype=torch.int64, device=dev)
-        P.y_in = torch.zeros((B,), dtype=torch.int64, device=dev)
-        P.ctx_in = torch.zeros((B, max(ctx_len, 1)), dtype=torch.int64, device=dev)
-        P.phosc_in = torch.zeros((B, max(phosc_len, 1)), dtype=torch.int32, device=dev)
-
-        # ---- conditioning: CharacterEncoder (unet.py:851-874) + K/V of every cross-attention
-        cond = P.cond
-        ctx_pl = self._planes(P, B * L, cd)
-        msl = m.max_seq_len
-        for (ids, n_tok, row0, i64) in ((P.ctx_in, ctx_len, 0, 1), (P.phosc_in, phosc_len, ctx_len, 0)):
-            if n_tok == 0:
-                continue
-            use_pe = (self.variant == "base") or (n_tok <= msl)
-            if use_pe and n_tok > msl:
-                raise ValueError(f"context length {n_tok} exceeds max_seq_len {msl} (the reference fails too)")
-            e = self._planes(P, B * n_tok, cd)
-            cond.append((lib.wd_embed_tokens,
-                         (ids.data_ptr(), i64, B * n_tok, n_tok, self._w["we.table"].data_ptr(),
-                          self._w["we.table"].shape[0], cd, self._w["pe"].data_ptr() if use_pe else None,
-                          e[0].data_ptr(), e[1].data_ptr() if lo_ok else None, cd), "word_emb.embedding"))
-            qkv = self._f32(P, B * n_tok, 3 * cd)
-            self._gemm(cond, "word_emb.qkv", [self._src(e, cd)], "we.qkv.w", B * n_tok, n_tok,
-                       bias=self._w["we.qkv.b"], out_f32=qkv, out_ld=3 * cd)
-            # Word_Attention: softmax(q k^T) v without 1/sqrt(d) (unet.py:831-835)
-            self._attention(cond, "word_emb.attention", qkv.data_ptr(), 3 * cd, qkv.data_ptr() + 4 * cd, 3 * cd,
-                            qkv.data_ptr() + 8 * cd, 3 * cd, 1, n_tok, n_tok, cd, 1.0, ctx_pl, out_rows=L,
-                            out_row0=row0)
-        P.ctx_pl = ctx_pl
-        if self.kv_total:
-            self._kv = self._f32(P, B * L, self.kv_total)
-            self._gemm(cond, "cross.kv", [self._src(ctx_pl, cd)], "kv.w", B * L, L, out_f32=self._kv,
-                       out_ld=self.kv_total)
+        self._inputs(P, H, W, ctx_len, phosc_len)
+        # step-invariant: run once per call (P.cond)
+        self._conditioning(P, P.cond, ctx_len, phosc_len)
 
         # ---- per-step: time/label embedding (unet.py:1550-1581) + all emb_layers at once (unet.py:609-615,660)
         step = P.step
@@ -1379,8 +1441,8 @@ class UNetEngine:
                 tt = torch.tensor(film_timesteps + (film_timesteps[-1],) * (Tp - T), dtype=torch.int64, device=dev)
             P.keep.append(tt)
             te = self._planes(P, Tp, mc)
-            film.append((lib.wd_timestep_embedding, (tt.data_ptr(), Tp, self._w["freqs"].data_ptr(), mc // 2, te[0].data_ptr(),
-                                                     te[1].data_ptr() if lo_ok else None, mc), "timestep_embedding[all t]"))
+            film.append((lib.wd_timestep_embedding, (tt.data_ptr(), Tp, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
+                         "timestep_embedding[all t]"))
             e1 = self._planes(P, Tp, ted)
             self._gemm(film, "time_embed.0[all t]", [self._src(te, mc)], "te0.w", Tp, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
                        out_pl=e1)
@@ -1407,12 +1469,12 @@ class UNetEngine:
                 if mix:
                     for f in range(nf):  # table f: rows f*chunk*B.. of the planes, pairs[f][c*chunk..]
                         N.check(lib.wd_emb_combine_mix(tm.data_ptr() + 4 * c * chunk * ted, lab, P.pairs[f, c * chunk].data_ptr(),
-                                                       P.mix_m.data_ptr(), ncls, chunk, B, ted, e2[0, f * chunk * B].data_ptr(),
-                                                       e2[1, f * chunk * B].data_ptr() if lo_ok else None, ted, stream),
+                                                       P.mix_m.data_ptr(), ncls, chunk, B, ted,
+                                                       *self._hilo(e2, 2 * f * chunk * B * ted), ted, stream),
                                 "SiLU(time + blended label)[chunk of t]")
                 else:
-                    N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, e2[0].data_ptr(),
-                                               e2[1].data_ptr() if lo_ok else None, ted, stream), "SiLU(time + label)[chunk of t]")
+                    N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, *self._hilo(e2), ted,
+                                               stream), "SiLU(time + label)[chunk of t]")
                 Plan._run(chunk_gemm, stream)
                 P.film_loaded = c
                 return True
@@ -1434,8 +1496,7 @@ class UNetEngine:
                 step.append((lib.wd_label_mix, (self._w["label"].data_ptr(), P.pairs.data_ptr(), P.mix_m.data_ptr(), m.num_classes,
                                                 B, ted, lab_rows.data_ptr()), "blended label rows"))
             te = self._planes(P, B, mc)
-            step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2,
-                                                     te[0].data_ptr(), te[1].data_ptr() if lo_ok else None, mc),
+            step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
                          "timestep_embedding"))
             e1 = self._planes(P, B, ted)
             self._gemm(step, "time_embed.0", [self._src(te, mc)], "te0.w", B, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
@@ -1447,11 +1508,11 @@ class UNetEngine:
             self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"],
                        out_f32=self._film, out_ld=self.film_total)
 
-        # ---- trunk
-        h0 = self._f32(P, B * H * W, mc)
+        # ---- head: the first convolution
         if self.fuse_in and self.variant != "phosc" and lib.wd_conv3x3_in_supported(m.in_channels, H, W, mc) and mc % 32 == 0:
             # the 4-channel 3x3 as a direct fp32 convolution: no im2col planes, and the statistics partials of the consumer's
             # GroupNorm (32 groups) in the layout the GEMM's epilogue gives them
+            h0 = self._f32(P, B * H * W, mc)
             stats = None
             if self.fuse_stats:
                 nchunk = lib.wd_conv3x3_in_nchunk(H * W)
@@ -1463,62 +1524,21 @@ class UNetEngine:
                                              stats[0].data_ptr() if stats else None, mc // 32), "input_blocks.0: conv3x3 from NCHW"))
             cur = Act(h0, mc, H, W, stats)
         else:
-            xin = self._planes(P, B * H * W, self.kpad_in)
-            step.append((lib.wd_im2col3x3, (P.x_in.data_ptr(), B, m.in_channels, H, W, xin[0].data_ptr(),
-                                            xin[1].data_ptr() if lo_ok else None, self.kpad_in), "im2col"))
-            g0 = self._gemm(step, "input_blocks.0", [self._src(xin, self.kpad_in)], "in.w", B * H * W, H * W,
-                            bias=self._w["in.b"], out_f32=h0, out_ld=mc, want_stats=True)
-            cur = Act(h0, mc, H, W, g0._stats)
-        hs = [cur]
-
-        def run_layers(prefix, blk, cur, extra=None):
-            for j, mod in enumerate(blk):
-                name = f"{prefix}.{j}"
-                if isinstance(mod, ResBlockParams):
-                    cur = self._resblock(P, name, mod, [cur] + ([extra] if (extra is not None and j == 0) else []))
-                elif isinstance(mod, SpatialTransformerParams):
-                    cur = self._transformer(P, name, mod, cur)
-                elif isinstance(mod, DownsampleParams):
-                    cur = self._resample(P, name, mod, cur, "down")
-                elif isinstance(mod, UpsampleParams):
-                    cur = self._resample(P, name, mod, cur, "up")
-                else:
-                    raise TypeError(type(mod))
-            return cur
-
-        for i, blk in enumerate(m.input_blocks):
-            if i == 0:
-                continue
-            cur = run_layers(f"in{i}", blk, cur)
-            hs.append(cur)
-        cur = run_layers("mid", m.middle_block, cur)
-        for i, blk in enumerate(m.output_blocks):
-            cur = run_layers(f"out{i}", blk, cur, extra=hs.pop())
+            cur, _ = self._head_gemm(P, step, "input_blocks.0", P.x_in, "in")
+        cur = self._trunk(P, cur)
+        # ---- tail
         oc = m.out_channels
         P.out = torch.empty((B, oc, cur.h, cur.w), dtype=torch.float32, device=dev)
         if self.fuse_out and lib.wd_gn_conv3x3_few_supported(cur.c, cur.w, oc) and cur.c % 32 == 0:
             # GroupNorm + SiLU + the 320 -> 4 convolution + NCHW in one fp32 launch (as a GEMM it fills 4 of 64 tile columns)
-            if cur.stats is None:
-                nchunk = lib.wd_gn_nchunk(cur.h * cur.w)
-                part = torch.empty((B, nchunk, 32, 2), dtype=torch.float64, device=dev)
-                P.keep.append(part)
-                step.append((lib.wd_gn_stats, (cur.t.data_ptr(), cur.c, B, cur.h * cur.w, cur.c, cur.c // 32, part.data_ptr()),
-                             "out.gn:stats"))
-                cur.stats = (part, nchunk, cur.c // 32)
-            part, nchunk, pc = cur.stats
+            part, nchunk, pc = self._gn_stats(P, step, "out.gn", cur)
             step.append((lib.wd_gn_conv3x3_few,
                          (cur.t.data_ptr(), cur.c, B, cur.h, cur.w, cur.c, cur.c // 32, part.data_ptr(), nchunk, pc,
                           self._w["out.gn.g"].data_ptr(), self._w["out.gn.b"].data_ptr(), 1e-5, 1,
                           self._w["out.w.f32"].data_ptr(), self._w["out.b"].data_ptr(), oc, P.out.data_ptr()),
                          "out: GroupNorm + SiLU + conv3x3 -> NCHW"))
         else:
-            g, _ = self._gn(P, step, "out.gn", [cur], "out.gn", 1e-5, True)
-            tab, _, _ = self._table(cur.h, cur.w, "same")
-            otok = self._f32(P, B * cur.h * cur.w, oc)
-            self._gemm(step, "out.conv", [self._src(g, cur.c, 9, tab, cur.h * cur.w)], "out.w", B * cur.h * cur.w,
-                       cur.h * cur.w, bias=self._w["out.b"], out_f32=otok, out_ld=oc)
-            step.append((lib.wd_tokens_to_nchw, (otok.data_ptr(), oc, B, oc, cur.h * cur.w, P.out.data_ptr()),
-                         "tokens_to_nchw"))
+            self._tail_gemm(P, step, "out.conv", cur, 1e-5, nchw=P.out)
         if mix == 2:
             # the second forward of a step: its own FiLM rows, the same launches, the prediction kept beside the first one
             fn, args, what = step[-1]

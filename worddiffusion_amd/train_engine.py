@@ -296,9 +296,8 @@ class TrainEngine(UNetEngine):
 
     def _dw(self, ops, what, dpl, d_ld, planes, col_off, c, ftab, ntaps, hw_out, hw_src, M, n, out: torch.Tensor, out_ld, acc):
         a = N.WdDwArgs()
-        a.d_hi, a.d_lo = dpl[0].data_ptr(), (dpl[1].data_ptr() if self.npass == 3 else None)
-        a.x_hi = planes[0].data_ptr() + 2 * col_off
-        a.x_lo = planes[1].data_ptr() + 2 * col_off if self.npass == 3 else None
+        a.d_hi, a.d_lo = self._hilo(dpl)
+        a.x_hi, a.x_lo = self._hilo(planes, 2 * col_off)
         a.gather = _ptr(ftab)
         a.grad, a.grad_ld, a.ws, a.ws_floats = out.data_ptr(), out_ld, self._ws.data_ptr(), self._ws.numel()
         a.d_ld, a.x_ld, a.ntaps, a.hw_out, a.hw_src = d_ld, planes.shape[2], ntaps, hw_out, hw_src
@@ -320,9 +319,8 @@ class TrainEngine(UNetEngine):
                     continue
                 arr = (N.WdDwItem * len(grp))()
                 for i, it in enumerate(grp):
-                    arr[i].d_hi, arr[i].d_lo = it["dpl"][0].data_ptr(), (it["dpl"][1].data_ptr() if self.npass == 3 else None)
-                    arr[i].x_hi = it["planes"][0].data_ptr() + 2 * it["col_off"]
-                    arr[i].x_lo = it["planes"][1].data_ptr() + 2 * it["col_off"] if self.npass == 3 else None
+                    arr[i].d_hi, arr[i].d_lo = self._hilo(it["dpl"])
+                    arr[i].x_hi, arr[i].x_lo = self._hilo(it["planes"], 2 * it["col_off"])
                     arr[i].grad, arr[i].grad_ld = it["wg"].data_ptr(), it["out_ld"]
                     arr[i].d_ld, arr[i].x_ld, arr[i].accumulate = it["d_ld"], it["planes"].shape[2], self._pacc(it["wg"])
                 dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
@@ -348,7 +346,6 @@ class TrainEngine(UNetEngine):
         # and column sums from the saved pre-activation and the gradient of the activation's output (dout is None then)
         ldd = dout.shape[1] if dout is not None else n
         mpad = _rup(M, 64)
-        lo_ok = self.npass == 3
         need_dx = any(s.get("dx") for s in segs)
         # weight gradients straight from the row-major planes (wd_dw: transposed LDS reads) wherever the shape allows; the rest goes
         # through transposed copies of both operands and wd_gemm
@@ -391,15 +388,12 @@ class TrainEngine(UNetEngine):
         if geglu is not None:
             u, dh, inner = geglu
             assert dout is None and n == 2 * inner and npad == n and fuse_cs and film_off is None, what
-            ops.append((lib.wd_dout_prep_geglu, (u.data_ptr(), u.shape[1], dh.data_ptr(), dh.shape[1], M, inner, mpad,
-                                                 _ptr(dpl[0]) if need_dpl else None,
-                                                 (_ptr(dpl[1]) if lo_ok else None) if need_dpl else None,
+            ops.append((lib.wd_dout_prep_geglu, (u.data_ptr(), u.shape[1], dh.data_ptr(), dh.shape[1], M, inner, mpad, *self._hilo(dpl),
                                                  _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None,
                                                  _ptr(colpart)), what + ":prep(geglu bwd)"))
         elif need_dpl or need_dw or fuse_cs:
             # one pass over d(output): row-major planes (data gradient, wd_dw), transposed planes (wd_gemm weight gradient), column sums
-            ops.append((lib.wd_dout_prep, (dout.data_ptr(), ldd, M, n, npad, mpad, _ptr(dpl[0]) if need_dpl else None,
-                                           (_ptr(dpl[1]) if lo_ok else None) if need_dpl else None,
+            ops.append((lib.wd_dout_prep, (dout.data_ptr(), ldd, M, n, npad, mpad, *self._hilo(dpl),
                                            _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None,
                                            _ptr(colpart)), what + ":prep(dout)"))
         for si, s in enumerate(segs):
@@ -634,8 +628,7 @@ class TrainEngine(UNetEngine):
         tab, ho, wo = self._table(x.h, x.w, mode)
         hw_in, M_in = x.h * x.w, B * x.h * x.w
         pl = self._planes(P, M_in, x.c)
-        ops.append((self.lib.wd_split, (x.t.data_ptr(), x.c, M_in, x.c, 0, pl[0].data_ptr(),
-                                        pl[1].data_ptr() if self.npass == 3 else None, x.c), name + ":split"))
+        ops.append((self.lib.wd_split, (x.t.data_ptr(), x.c, M_in, x.c, 0, *self._hilo(pl), x.c), name + ":split"))
         outt = self._f32(P, B * ho * wo, mod.cout)
         gg = self._gemm(ops, name + ".conv", [self._src(pl, x.c, 9, tab, hw_in)], name + ".w", B * ho * wo, ho * wo,
                         bias=self._w[name + ".b"], out_f32=outt, out_ld=mod.cout, want_stats=True)
@@ -679,7 +672,6 @@ class TrainEngine(UNetEngine):
         inner = heads * d
         L = self._ctx_len
         scale = d ** -0.5
-        lo_ok = self.npass == 3
         gpl, _ = self._gn(P, ops, name + ".gn", [x], name + ".gn", 1e-6, False)
         self._gn_names[id(mod.norm)] = name + ".gn"
         tok = self._f32(P, M, inner)
@@ -721,8 +713,7 @@ class TrainEngine(UNetEngine):
             self._gemm(ops, p + ".ff1", [self._src(n3, inner)], p + ".ff1u.w", M, hw, bias=self._w[p + ".ff1u.b"], out_f32=u,
                        out_ld=2 * ffi)
             ffh = self._planes(P, M, ffi)
-            ops.append((lib.wd_geglu_fwd, (u.data_ptr(), 2 * ffi, M, ffi, ffh[0].data_ptr(), ffh[1].data_ptr() if lo_ok else None,
-                                           ffi), p + ".geglu"))
+            ops.append((lib.wd_geglu_fwd, (u.data_ptr(), 2 * ffi, M, ffi, *self._hilo(ffh), ffi), p + ".geglu"))
             nxt = self._f32(P, M, inner)
             xpl = self._planes(P, M, inner)
             self._gemm(ops, p + ".ff2", [self._src(ffh, ffi)], p + ".ff2.w", M, hw, bias=self._w[p + ".ff2.b"],
@@ -848,8 +839,9 @@ class TrainEngine(UNetEngine):
 
     def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0) -> TrainPlan:
         key = (B, H, W, ctx_len, phosc_len, self.npass)
-        if key in self._tplans:
-            return self._tplans[key]
+        P = self._cached_plan(self._tplans, key)
+        if P is not None:
+            return P
         if self._tplans:
             # scratch buffers and the gradient-accumulate flags are sized / decided per plan: one live shape at a time
             self._tplans.clear()
@@ -860,11 +852,8 @@ class TrainEngine(UNetEngine):
             raise NotImplementedError("context=None: every reference script conditions on the word (unet.py:1605)")
         if phosc_len and self.variant != "phosc":
             raise ValueError("phoscLabels are an input of UNetModelPhosc only")
-        P = TrainPlan()
-        self._cur_plan = P
-        self._B = B
+        P = self._begin_plan(TrainPlan(), B)
         L = ctx_len + phosc_len
-        self._ctx_len = L
         self._tape = []
         self._pw = set()
         self._deferred, self._deferred_outs = [], {}
@@ -874,109 +863,43 @@ class TrainEngine(UNetEngine):
         mc = m.model_channels
         ted = 4 * mc
         cd = m.context_dim
-        lo_ok = self.npass == 3
         self._size_scratch(B, H, W, L, ctx_len, phosc_len)
         step = P.step
-
-        P.x_in = torch.zeros((B, m.in_channels, H, W), dtype=torch.float32, device=dev)
-        P.t_in = torch.zeros((B,), dtype=torch.int64, device=dev)
-        P.y_in = torch.zeros((B,), dtype=torch.int64, device=dev)
-        P.ctx_in = torch.zeros((B, ctx_len), dtype=torch.int64, device=dev)
-        P.phosc_in = torch.zeros((B, max(phosc_len, 1)), dtype=torch.int32, device=dev)
-
-        # ---- conditioning path (differentiated, so it is part of every step): CharacterEncoder + all K/V projections
-        we = m.word_emb
-        msl = m.max_seq_len
-        ctx_pl = self._planes(P, B * L, cd)
-        groups = []
-        for (ids, n_tok, row0, i64) in ((P.ctx_in, ctx_len, 0, 1), (P.phosc_in, phosc_len, ctx_len, 0)):
-            if n_tok == 0:
-                continue
-            use_pe = (self.variant == "base") or (n_tok <= msl)  # unetPhosc.py:726-729 skips the table for PHOSC vectors
-            if use_pe and n_tok > msl:
-                raise ValueError(f"context length {n_tok} exceeds max_seq_len {msl} (the reference fails too)")
-            e = self._planes(P, B * n_tok, cd)
-            step.append((lib.wd_embed_tokens, (ids.data_ptr(), i64, B * n_tok, n_tok, self._w["we.table"].data_ptr(),
-                                               self._w["we.table"].shape[0], cd, self._w["pe"].data_ptr() if use_pe else None,
-                                               e[0].data_ptr(), e[1].data_ptr() if lo_ok else None, cd), "word_emb.embedding"))
-            qkv = self._f32(P, B * n_tok, 3 * cd)
-            self._gemm(step, "word_emb.qkv", [self._src(e, cd)], "we.qkv.w", B * n_tok, n_tok, bias=self._w["we.qkv.b"],
-                       out_f32=qkv, out_ld=3 * cd)
-            # Word_Attention: softmax(q k^T) v without 1/sqrt(d) (unet.py:831-835)
-            self._attention(step, "word_emb.attention", qkv.data_ptr(), 3 * cd, qkv.data_ptr() + 4 * cd, 3 * cd,
-                            qkv.data_ptr() + 8 * cd, 3 * cd, 1, n_tok, n_tok, cd, 1.0, ctx_pl, out_rows=L, out_row0=row0)
-            groups.append((ids, n_tok, row0, i64, e, qkv))
-        self._kv = self._f32(P, B * L, self.kv_total)
+        self._inputs(P, H, W, ctx_len, phosc_len)
+        # the conditioning path is differentiated, so it is part of every step
+        groups = self._conditioning(P, step, ctx_len, phosc_len)
         self._dkv = self._f32(P, B * L, self.kv_total)
-        self._gemm(step, "cross.kv", [self._src(ctx_pl, cd)], "kv.w", B * L, L, out_f32=self._kv, out_ld=self.kv_total)
 
         # ---- time / writer embedding with the SiLU pre-activations kept
         te = self._planes(P, B, mc)
-        step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, te[0].data_ptr(),
-                                                 te[1].data_ptr() if lo_ok else None, mc), "timestep_embedding"))
+        step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
+                     "timestep_embedding"))
         pre1 = self._f32(P, B, ted)
         self._gemm(step, "time_embed.0", [self._src(te, mc)], "te0.w", B, 1, bias=self._w["te0.b"], out_f32=pre1, out_ld=ted)
         e1 = self._planes(P, B, ted)
-        step.append((lib.wd_split, (pre1.data_ptr(), ted, B, ted, 1, e1[0].data_ptr(), e1[1].data_ptr() if lo_ok else None, ted),
-                     "time_embed.1(SiLU)"))
+        step.append((lib.wd_split, (pre1.data_ptr(), ted, B, ted, 1, *self._hilo(e1), ted), "time_embed.1(SiLU)"))
         has_lab = m.num_classes is not None
         pre2 = self._f32(P, B, ted)
         self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
                    resid=self._w["label"].data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
                    resid_rows=P.y_in.data_ptr() if has_lab else None, out_f32=pre2, out_ld=ted)
         e2 = self._planes(P, B, ted)
-        step.append((lib.wd_split, (pre2.data_ptr(), ted, B, ted, 1, e2[0].data_ptr(), e2[1].data_ptr() if lo_ok else None, ted),
-                     "emb_layers.0(SiLU)"))
+        step.append((lib.wd_split, (pre2.data_ptr(), ted, B, ted, 1, *self._hilo(e2), ted), "emb_layers.0(SiLU)"))
         self._film = self._f32(P, B, self.film_total)
         self._dfilm = self._f32(P, B, self.film_total)
         self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"], out_f32=self._film,
                    out_ld=self.film_total)
 
-        # ---- trunk
-        xin = self._planes(P, B * H * W, self.kpad_in)
-        step.append((lib.wd_im2col3x3, (P.x_in.data_ptr(), B, m.in_channels, H, W, xin[0].data_ptr(),
-                                        xin[1].data_ptr() if lo_ok else None, self.kpad_in), "im2col"))
-        h0 = self._f32(P, B * H * W, mc)
-        g0 = self._gemm(step, "input_blocks.0", [self._src(xin, self.kpad_in)], "in.w", B * H * W, H * W, bias=self._w["in.b"],
-                        out_f32=h0, out_ld=mc, want_stats=True)
-        first = TAct(h0, mc, H, W, g0._stats)
-        cur = first
-        hs = [cur]
-
-        def run_layers(prefix, blk, cur, extra=None):
-            for j, mod in enumerate(blk):
-                name = f"{prefix}.{j}"
-                if isinstance(mod, ResBlockParams):
-                    cur = self._resblock(P, name, mod, [cur] + ([extra] if (extra is not None and j == 0) else []))
-                elif isinstance(mod, SpatialTransformerParams):
-                    cur = self._transformer(P, name, mod, cur)
-                elif isinstance(mod, DownsampleParams):
-                    cur = self._resample(P, name, mod, cur, "down")
-                elif isinstance(mod, UpsampleParams):
-                    cur = self._resample(P, name, mod, cur, "up")
-                else:
-                    raise TypeError(type(mod))
-            return cur
-
-        for i, blk in enumerate(m.input_blocks):
-            if i == 0:
-                continue
-            cur = run_layers(f"in{i}", blk, cur)
-            hs.append(cur)
-        cur = run_layers("mid", m.middle_block, cur)
-        for i, blk in enumerate(m.output_blocks):
-            cur = run_layers(f"out{i}", blk, cur, extra=hs.pop())
-        last = cur
+        # ---- head, trunk, tail: the GEMM forms, whose operand planes the backward list reads
+        head, xin = self._head_gemm(P, step, "input_blocks.0", P.x_in, "in")
+        first = TAct(head.t, mc, H, W, head.stats)
+        last = self._trunk(P, first)
         self._gn_names[id(m.out[0])] = "out.gn"
-        gpl, _ = self._gn(P, step, "out.gn", [last], "out.gn", 1e-5, True)
-        tab, _, _ = self._table(last.h, last.w, "same")
         oc = m.out_channels
         Mo, hwo = B * last.h * last.w, last.h * last.w
-        otok = self._f32(P, Mo, oc)
-        self._gemm(step, "out.conv", [self._src(gpl, last.c, 9, tab, hwo)], "out.w", Mo, hwo, bias=self._w["out.b"],
-                   out_f32=otok, out_ld=oc)
         P.out = torch.empty((B, oc, last.h, last.w), dtype=torch.float32, device=dev)
-        step.append((lib.wd_tokens_to_nchw, (otok.data_ptr(), oc, B, oc, hwo, P.out.data_ptr()), "tokens_to_nchw"))
+        gpl, _ = self._tail_gemm(P, step, "out.conv", last, 1e-5, nchw=P.out)
+        tab, _, _ = self._table(last.h, last.w, "same")
 
         # ================================ backward list ================================
         bops = P.bwd
@@ -1054,8 +977,9 @@ class TrainEngine(UNetEngine):
         kv_w = self._pgroup(kv_params)
         dctx = self._f32(P, B * L, cd)
         self._bwd_linear(P, "cross.kv", self._dkv, B * L, self.kv_total, L,
-                         [dict(planes=ctx_pl, c=cd, ntaps=1, hw_src=L, wb="B:kv.w", wgrad=kv_w, dx=[(dctx, cd, 0, 0, cd)],
+                         [dict(planes=P.ctx_pl, c=cd, ntaps=1, hw_src=L, wb="B:kv.w", wgrad=kv_w, dx=[(dctx, cd, 0, 0, cd)],
                                dx_rows=B * L, dx_hw=L)])
+        we = m.word_emb
         at = we.attention
         qkv_w = self._pgroup([at.linear_query.weight, at.linear_key.weight, at.linear_value.weight])
         qkv_b = self._pgroup([at.linear_query.bias, at.linear_key.bias, at.linear_value.bias])
@@ -1107,13 +1031,7 @@ class TrainEngine(UNetEngine):
             raise NotImplementedError("context=None")
         self.check_ids(context, y, phosc)
         P = self.plan_train(B, H, W, context.shape[1], 0 if phosc is None else phosc.shape[1])
-        P.x_in.copy_(x, non_blocking=True)
-        P.t_in.copy_(t, non_blocking=True)
-        P.ctx_in.copy_(context, non_blocking=True)
-        if phosc is not None:
-            P.phosc_in.copy_(phosc.to(torch.int32) if phosc.dtype != torch.int32 else phosc, non_blocking=True)
-        if y is not None:
-            P.y_in.copy_(y, non_blocking=True)
+        self.load_inputs(P, x, t, context, y, phosc, check=False)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         P.run_step(stream)
         self._live = P

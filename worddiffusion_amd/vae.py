@@ -466,34 +466,19 @@ class VAEDecoderEngine(UNetEngine):
 
     def plan_decode(self, B: int, H: int, W: int) -> Plan:
         key = ("vae", B, H, W, self.npass)
-        if key in self._plans:
-            return self._plans[key]
+        P = self._cached_plan(self._plans, key)
+        if P is not None:
+            return P
         m, lib, dev = self.model, self.lib, self.device
         d = m.decoder
         lat = m.config.latent_channels
-        lo_ok = self.npass == 3
-        P = Plan()
-        self._cur_plan = P
-        self._B = B
+        P = self._begin_plan(Plan(), B)
         step = P.step
-        M = B * H * W
         P.z_in = torch.zeros((B, lat, H, W), dtype=torch.float32, device=dev)
-        zc = self._planes(P, M, self.kpad_in)
-        step.append((lib.wd_im2col3x3, (P.z_in.data_ptr(), B, lat, H, W, zc[0].data_ptr(), zc[1].data_ptr() if lo_ok else None,
-                                        self.kpad_in), "im2col(z)"))
-        zq_tok = self._f32(P, M, lat)
-        self._gemm(step, "post_quant_conv", [self._src(zc, self.kpad_in)], "pq.w", M, H * W, bias=self._w["pq.b"],
-                   out_f32=zq_tok, out_ld=lat)
+        zq_tok = self._head_gemm(P, step, "post_quant_conv", P.z_in, "pq", label="im2col(z)", want_stats=False)[0].t
         zq = self._f32(P, B, lat, H, W)
         step.append((lib.wd_tokens_to_nchw, (zq_tok.data_ptr(), lat, B, lat, H * W, zq.data_ptr()), "tokens_to_nchw(z)"))
-        zi = self._planes(P, M, self.kpad_in)
-        step.append((lib.wd_im2col3x3, (zq.data_ptr(), B, lat, H, W, zi[0].data_ptr(), zi[1].data_ptr() if lo_ok else None,
-                                        self.kpad_in), "im2col(post_quant z)"))
-        c0 = d.conv_in.out_channels
-        h0 = self._f32(P, M, c0)
-        g0 = self._gemm(step, "decoder.conv_in", [self._src(zi, self.kpad_in)], "in.w", M, H * W, bias=self._w["in.b"],
-                        out_f32=h0, out_ld=c0, want_stats=True, tile=self.TILE)
-        cur = Act(h0, c0, H, W, g0._stats)
+        cur, _ = self._head_gemm(P, step, "decoder.conv_in", zq, "in", label="im2col(post_quant z)", tile=self.TILE)
         cur = self._vae_resnet(P, "mid.r0", d.mid_block.resnets[0], cur)
         cur = self._vae_attention(P, cur)
         cur = self._vae_resnet(P, "mid.r1", d.mid_block.resnets[1], cur)
@@ -502,14 +487,8 @@ class VAEDecoderEngine(UNetEngine):
                 cur = self._vae_resnet(P, f"up{i}.r{j}", r, cur)
             if hasattr(ub, "upsamplers"):
                 cur = self._resample(P, f"up{i}.us", ub.upsamplers[0], cur, "up", tile=self.TILE)
-        g, _ = self._gn(P, step, "out.gn", [cur], "out.gn", 1e-6, True)
-        tab, _, _ = self._table(cur.h, cur.w, "same")
-        oc = d.conv_out.out_channels
-        otok = self._f32(P, B * cur.h * cur.w, oc)
-        self._gemm(step, "decoder.conv_out", [self._src(g, cur.c, 9, tab, cur.h * cur.w)], "out.w", B * cur.h * cur.w,
-                   cur.h * cur.w, bias=self._w["out.b"], out_f32=otok, out_ld=oc)
-        P.out = torch.empty((B, oc, cur.h, cur.w), dtype=torch.float32, device=dev)
-        step.append((lib.wd_tokens_to_nchw, (otok.data_ptr(), oc, B, oc, cur.h * cur.w, P.out.data_ptr()), "tokens_to_nchw"))
+        P.out = torch.empty((B, d.conv_out.out_channels, cur.h, cur.w), dtype=torch.float32, device=dev)
+        self._tail_gemm(P, step, "decoder.conv_out", cur, 1e-6, nchw=P.out)
         self._plans[key] = P
         return P
 
@@ -572,26 +551,14 @@ class VAEEncoderEngine(VAEDecoderEngine):
 
     def plan_encode(self, B: int, H: int, W: int) -> Plan:
         key = ("vae.enc", B, H, W, self.npass)
-        if key in self._plans:
-            return self._plans[key]
-        m, lib, dev = self.model, self.lib, self.device
-        e = m.encoder
-        cin = m.config.in_channels
-        lo_ok = self.npass == 3
-        P = Plan()
-        self._cur_plan = P
-        self._B = B
+        P = self._cached_plan(self._plans, key)
+        if P is not None:
+            return P
+        e = self.model.encoder
+        P = self._begin_plan(Plan(), B)
         step = P.step
-        M = B * H * W
-        P.x_in = torch.zeros((B, cin, H, W), dtype=torch.float32, device=dev)
-        xc = self._planes(P, M, self.kpad_in)
-        step.append((lib.wd_im2col3x3, (P.x_in.data_ptr(), B, cin, H, W, xc[0].data_ptr(), xc[1].data_ptr() if lo_ok else None,
-                                        self.kpad_in), "im2col(x)"))
-        c0 = e.conv_in.out_channels
-        h0 = self._f32(P, M, c0)
-        g0 = self._gemm(step, "encoder.conv_in", [self._src(xc, self.kpad_in)], "in.w", M, H * W, bias=self._w["in.b"],
-                        out_f32=h0, out_ld=c0, want_stats=True, tile=self.TILE)
-        cur = Act(h0, c0, H, W, g0._stats)
+        P.x_in = torch.zeros((B, self.model.config.in_channels, H, W), dtype=torch.float32, device=self.device)
+        cur, _ = self._head_gemm(P, step, "encoder.conv_in", P.x_in, "in", label="im2col(x)", tile=self.TILE)
         for i, db in enumerate(e.down_blocks):
             for j, r in enumerate(db.resnets):
                 cur = self._vae_resnet(P, f"down{i}.r{j}", r, cur)
@@ -600,12 +567,7 @@ class VAEEncoderEngine(VAEDecoderEngine):
         cur = self._vae_resnet(P, "mid.r0", e.mid_block.resnets[0], cur)
         cur = self._vae_attention(P, cur)
         cur = self._vae_resnet(P, "mid.r1", e.mid_block.resnets[1], cur)
-        g, _ = self._gn(P, step, "out.gn", [cur], "out.gn", 1e-6, True)
-        tab, _, _ = self._table(cur.h, cur.w, "same")
-        oc = e.conv_out.out_channels
-        P.moments = self._f32(P, B * cur.h * cur.w, oc)
-        self._gemm(step, "encoder.conv_out", [self._src(g, cur.c, 9, tab, cur.h * cur.w)], "out.w", B * cur.h * cur.w,
-                   cur.h * cur.w, bias=self._w["out.b"], out_f32=P.moments, out_ld=oc)
+        _, P.moments = self._tail_gemm(P, step, "encoder.conv_out", cur, 1e-6)  # (token rows: wd_vae_posterior reads them)
         P.lat_hw = (cur.h, cur.w)
         self._plans[key] = P
         return P
