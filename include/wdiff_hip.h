@@ -470,7 +470,8 @@ int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sa
  * WD_EINVAL (nothing launched): a NULL required pointer, L outside 1..WD_VAE_MAX_LATENT, ld < 2L, L*hw not a multiple of 4,
  * noise without sample, mean / logvar / sample / noise not 16-byte aligned.  Does not allocate or synchronise (capturable). */
 #define WD_VAE_MAX_LATENT 8
-#define WD_STREAM_VAE_POSTERIOR 3 /* stream ids taken so far: 0 x_T, 1 noise_images eps, 2 the training step's eps */
+#define WD_STREAM_VAE_POSTERIOR 3 /* stream ids taken so far: 0 x_T, 1 noise_images eps, 2 the training step's eps, 3 this one; */
+#define WD_STREAM_DROPOUT0 0x100  /* 0x100 + layer: the training dropout mask of ResBlock `layer` (wd_dropout below) */
 int wd_vae_posterior(const float* moments_tok, int ld, const float* w, const float* bias, int batch, int L, int hw, float* mean,
                      float* logvar, float* sample, float scale, const float* noise, uint64_t seed, uint64_t sample_offset,
                      void* stream);
@@ -613,6 +614,39 @@ int wd_gn_bwd_fused_supported(int hw, int c, int cpg);
 int wd_gn_bwd_fused(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
                     const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off, float eps,
                     int silu, float* sums, float* dx, int dx_ld, int accumulate, void* stream);
+
+/* Training dropout (nn.Dropout(p) of ResBlock.out_layers, unet.py:616-623) on the output of a GroupNorm(+SiLU): the mask is a
+ * function of (seed, global sample row, layer, position) alone and is never stored - the forward and both backward passes
+ * recompute it.  One Philox4x32-10 draw covers four consecutive elements:
+ *   counter = (e4, tag, row & 0xffffffff, row >> 32), key = (seed & 0xffffffff, seed >> 32),
+ *   idx = token * c + ch (token = y * W + x, ch the channel inside this norm, c its channel count), e4 = idx >> 2, element idx
+ *   reads output word idx & 3 and is kept iff word >= thr; row = row_base (+ *row_base_dev) + b;
+ *   tag = 0x80000000 | (WD_STREAM_DROPOUT0 + layer); thr = (uint32)(p * 2^32 + 0.5); scale = (float)(1 / (1 - p)).
+ * A kept value is one fp32 product v * scale (rounded on its own), a dropped one exactly zero. */
+typedef struct {
+    uint64_t seed;
+    uint64_t row_base;
+    const uint64_t* row_base_dev; /* NULL, or added to row_base (read on device) */
+    uint32_t tag, thr;
+    float scale;
+} wd_dropout;
+/* wd_gn_apply with the mask on the normalised(+SiLU) planes (the raw planes carry none). */
+int wd_gn_apply_dropout(const float* x, int ld, int batch, int hw, int c, int cpg, const double* part, int nchunk, int part_cpg,
+                        const float* gamma, const float* beta, float eps, int silu,
+                        wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, int c_off,
+                        wd_bf16* raw_hi, wd_bf16* raw_lo, const wd_dropout* d, void* stream);
+/* The GroupNorm backward entry points above with dz' = keep ? fp32(dz * scale) : 0 formed as dz is loaded (both passes): bit for
+ * bit what they compute from a dz masked beforehand.  WD_EINVAL for d == NULL or c % 4; wd_gn_bwd_fused_supported governs
+ * wd_gn_bwd_fused_dropout too. */
+int wd_gn_bwd_stats_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+                            const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off, float eps,
+                            int silu, float* sums, const wd_dropout* d, void* stream);
+int wd_gn_bwd_apply_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+                            const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off, float eps,
+                            int silu, const float* sums, float* dx, int dx_ld, int accumulate, const wd_dropout* d, void* stream);
+int wd_gn_bwd_fused_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+                            const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off, float eps,
+                            int silu, float* sums, float* dx, int dx_ld, int accumulate, const wd_dropout* d, void* stream);
 
 /* LayerNorm backward (nn.LayerNorm of BasicTransformerBlock, unet.py:314-316): dx (+=), and colpart[blk][2][c] (blk < wd_layernorm_bwd_nblk(rows)) whose column sums are
  * [d gamma | d beta]. */

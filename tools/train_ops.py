@@ -1,6 +1,7 @@
 """Per-launch table of one TRAINING step at the configs[2] shape (B = 64, base UNet): every op of the forward and backward launch
 lists timed on its own (hipEvent pair around REP back-to-back launches, after warm passes), summed per kind at the end.  The ops run
-eagerly and alone here, so their sum differs a little from the replayed graph's step time."""
+eagerly and alone here, so their sum differs a little from the replayed graph's step time.  DROPOUT=P: with nn.Dropout(P) in every
+ResBlock (the wd_gn_apply_dropout / wd_gn_bwd_*_dropout launches)."""
 import collections
 import os
 import sys
@@ -16,6 +17,13 @@ B = int(os.environ.get("B", "64"))
 REP = int(os.environ.get("REP", "10"))
 dev = torch.device("cuda:0")
 model, args = bench.build_model(dev, os.environ.get("PREC", "bf16x3"), "base")
+p_drop = float(os.environ.get("DROPOUT", "0"))
+if p_drop:
+    from worddiffusion_amd.layers import ResBlockParams  # noqa: E402
+    model.dropout = p_drop
+    for mod in model.modules():
+        if isinstance(mod, ResBlockParams):
+            mod.out_layers[2].p = p_drop
 model.train()
 eng = model.train_engine
 inp = synthetic_inputs(B, seed=7, hw=(8, 32), num_classes=339)
@@ -47,7 +55,7 @@ with torch.cuda.stream(stream):
             rows.append((phase, what, getattr(fn, "__name__", str(fn)), us, info))
 kinds = collections.OrderedDict()
 for phase, what, name, us, info in rows:
-    print(f"{phase} {what[:52]:52s} {name[:20]:20s} {us:8.1f} us  {info}")
+    print(f"{phase} {what[:52]:52s} {name[:24]:24s} {us:8.1f} us  {info}")
     tag = what.split(":")
     kind = name
     if name == "wd_gemm":

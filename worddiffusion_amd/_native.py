@@ -96,6 +96,7 @@ _SIGS = {
     "wd_gn_conv3x3_few_supported": (_i, [_i, _i, _i]),
     "wd_gn_conv3x3_few": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _vp, _vp]),
     "wd_gn_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "wd_gn_apply_dropout": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "wd_gn_apply2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _vp,
                           _vp, _vp, _vp]),
     "wd_layernorm": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp]),
@@ -158,6 +159,9 @@ _SIGS = {
     "wd_gn_bwd_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp]),
     "wd_gn_bwd_fused_supported": (_i, [_i, _i, _i]),
     "wd_gn_bwd_fused": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp]),
+    "wd_gn_bwd_stats_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp]),
+    "wd_gn_bwd_apply_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "wd_gn_bwd_fused_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "wd_layernorm_bwd_nblk": (_i, [_i]),
     "wd_layernorm_bwd": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _i, _i, _vp, _vp]),
     "wd_attention_bwd_small_nwg": (_i, [_i, _i, _i, _i]),

@@ -10,6 +10,7 @@
 //   wd_geglu_fwd/bwd, wd_silu_bwd, wd_pool2x2_sum (nearest-x2 upsample backward), wd_embedding_bwd
 // Reductions are two-stage with fixed order (no float atomics): gradients are bitwise reproducible.
 #include "wd_common.h"
+#include "wd_philox.h"
 
 namespace {
 
@@ -282,10 +283,24 @@ __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColRef* __restr
 // ---- GroupNorm (+SiLU) backward, pass 1: per (sample, chunk, channel) sums of dy and dy * xhat,
 // sums[b][chunk][2][c] (planar: row-summing it gives [d beta | d gamma])
 constexpr int GB_TOK = 32;
+// DROP (all three GroupNorm backward kernels): dz is masked as it is loaded, dz' = keep ? fp32(dz * scale) : 0 - the training
+// dropout of wd_gn_apply_dropout recomputed from the same key (wd_philox.h); everything after the load is the plain kernel's
+// arithmetic, so the result is bit for bit that of the plain kernel on a dz masked beforehand.
+__device__ __forceinline__ void gn_bwd_drop4(const wd_dropout& d, uint64_t drow, int token, int c, int ch, float (&dz4)[4]) {
+    bool keep[4];
+    wd_dropout_keep4(d, drow, token, c, ch, keep);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dz4[k] = wd_dropout_apply(keep[k], dz4[k], d.scale);
+}
+
+// D: nothing (the plain kernel: its signature and code are those of the kernel without the feature), or one wd_dropout
+template <typename... D>
 __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, int ld, const float* __restrict__ dz, int dz_ld,
                                     int dz_off, int hw, int c, int cpg, const double* __restrict__ part, int nchunk_f,
                                     int part_cpg, const float* __restrict__ gamma, const float* __restrict__ beta, int c_off,
-                                    float eps, int silu, int nchunk, float* __restrict__ sums) {
+                                    float eps, int silu, int nchunk, float* __restrict__ sums, const D... dd) {
+    constexpr bool DROP = sizeof...(D) != 0;
+    const auto& d = wd_dropout_of(dd...);
     // grid (nchunk, batch), block (64 * ceil(c/4/64), 2); sums: [b][chunk][2][c] (planar)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_mean = reinterpret_cast<float*>(smem);
@@ -322,7 +337,9 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, int ld, const f
             const long row = (long)b * hw + t;
             const float4 xv = *reinterpret_cast<const float4*>(x + row * ld + cx);
             const float4 dv = *reinterpret_cast<const float4*>(dz + row * dz_ld + dz_off + cx);
-            const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+            float ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            if constexpr (DROP) gn_bwd_drop4(d, wd_dropout_row(d, b), t, c, cx, ds4);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int g = (cx + k) / cpg;
@@ -349,11 +366,14 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, int ld, const f
 
 // pass 2: dx = rstd * (gamma dy - m1_g - xhat m2_g),  m1_g = mean_g(gamma dy), m2_g = mean_g(gamma dy xhat)
 constexpr int GA_TOK = 16;
+template <typename... D>
 __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, int ld, const float* __restrict__ dz, int dz_ld, int dz_off,
                                     int hw, int c, int cpg, const double* __restrict__ part, int nchunk_f, int part_cpg,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, int c_off, float eps,
                                     int silu, const float* __restrict__ sums, int nchunk, float* __restrict__ dx, int dx_ld,
-                                    int accumulate) {
+                                    int accumulate, const D... dd) {
+    constexpr bool DROP = sizeof...(D) != 0;
+    const auto& d = wd_dropout_of(dd...);
     __shared__ float s_mean[32], s_rstd[32], s_m1[32], s_m2[32];
     const int b = blockIdx.y;
     const int ng = c / cpg;
@@ -390,6 +410,8 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, int ld, const f
     __syncthreads();
     const int c4 = c >> 2;
     const int t0 = blockIdx.x * GA_TOK, nt = min(GA_TOK, hw - t0);
+    uint64_t drow = 0;
+    if constexpr (DROP) drow = wd_dropout_row(d, b);
     if (c4 <= (int)blockDim.x) {
         // thread = (token lane, channel quad): the quad is fixed, so the group lookups (integer divisions by a run-time cpg) and
         // the per-channel constants are set up once per thread instead of once per element
@@ -407,7 +429,9 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, int ld, const f
             const long row = (long)b * hw + t0 + t;
             const float4 xv = *reinterpret_cast<const float4*>(x + row * ld + cx);
             const float4 dv = *reinterpret_cast<const float4*>(dz + row * dz_ld + dz_off + cx);
-            const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+            float ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            if constexpr (DROP) gn_bwd_drop4(d, drow, t0 + t, c, cx, ds4);
             float o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -433,7 +457,9 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, int ld, const f
         const float4 dv = *reinterpret_cast<const float4*>(dz + row * dz_ld + dz_off + cx);
         const float4 ga = *reinterpret_cast<const float4*>(gamma + c_off + cx);
         const float4 be = *reinterpret_cast<const float4*>(beta + c_off + cx);
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+        if constexpr (DROP) gn_bwd_drop4(d, drow, t0 + t, c, cx, ds4);
         const float gam[4] = {ga.x, ga.y, ga.z, ga.w}, bet[4] = {be.x, be.y, be.z, be.w};
         float o[4];
 #pragma unroll
@@ -929,11 +955,15 @@ constexpr int GF_CB = 40;      // channels per workgroup (4 groups of 10, 2 of 2
 constexpr int GF_NT = 256;
 constexpr int GF_Q = GF_CB / 4;            // channel quads
 constexpr int GF_RPP = GF_NT / GF_Q;       // token lanes (25; 250 threads work)
+template <typename... D>
 __global__ void __launch_bounds__(GF_NT) gn_bwd_fused_kernel(const float* __restrict__ x, int ld, const float* __restrict__ dz, int dz_ld,
                                                             int dz_off, int hw, int c, int cpg, const double* __restrict__ part,
                                                             int nchunk_f, int part_cpg, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, int c_off, float eps, int silu,
-                                                            float* __restrict__ sums, float* __restrict__ dx, int dx_ld, int accumulate) {
+                                                            float* __restrict__ sums, float* __restrict__ dx, int dx_ld, int accumulate,
+                                                            const D... dd) {
+    constexpr bool DROP = sizeof...(D) != 0;
+    const auto& d = wd_dropout_of(dd...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_dy = reinterpret_cast<float*>(smem);           // [hw][GF_CB]
     float* s_xh = s_dy + (long)hw * GF_CB;                    // [hw][GF_CB]
@@ -974,12 +1004,16 @@ __global__ void __launch_bounds__(GF_NT) gn_bwd_fused_kernel(const float* __rest
         bet[k] = beta[c_off + c0 + cx + k];
     }
     float a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
+    uint64_t drow = 0;
+    if constexpr (DROP) drow = wd_dropout_row(d, b);
     if (work) {
         for (int t = tl; t < hw; t += GF_RPP) {
             const long row = (long)b * hw + t;
             const float4 xv = *reinterpret_cast<const float4*>(x + row * ld + c0 + cx);
             const float4 dv = *reinterpret_cast<const float4*>(dz + row * dz_ld + dz_off + c0 + cx);
-            const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+            float ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+            if constexpr (DROP) gn_bwd_drop4(d, drow, t, c, c0 + cx, ds4);
             float dy[4], xh[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -1047,33 +1081,53 @@ extern "C" int wd_gn_bwd_fused_supported(int hw, int c, int cpg) {
            (long)hw * GF_CB * 8 + GF_RPP * 2 * GF_CB * 4 <= 150 * 1024;
 }
 
-extern "C" int wd_gn_bwd_fused(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+// d == NULL: the plain kernels
+static int gn_bwd_fused_launch(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
                                const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off,
-                               float eps, int silu, float* sums, float* dx, int dx_ld, int accumulate, void* stream) {
+                               float eps, int silu, float* sums, float* dx, int dx_ld, int accumulate, const wd_dropout* d, void* stream) {
     if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0) return WD_EINVAL;
     if (!wd_gn_bwd_fused_supported(hw, c, cpg)) return WD_EINVAL;
     if (ld % 4 || dz_ld % 4 || dz_off % 4 || dx_ld % 4 || c_off % 4 || cpg % part_cpg) return WD_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dx)) & 15) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int smem = hw * GF_CB * 8 + GF_RPP * 2 * GF_CB * 4;
-    static int attr_max = 0;
-    if (smem > attr_max) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
-            hipSuccess)
-            return WD_ELAUNCH;
-        attr_max = smem;
+    static int attr_max[2] = {0, 0};  // [plain, dropout]
+    if (smem > attr_max[d != nullptr]) {
+        const void* fn = d ? reinterpret_cast<const void*>(&gn_bwd_fused_kernel<wd_dropout>) : reinterpret_cast<const void*>(&gn_bwd_fused_kernel<>);
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return WD_ELAUNCH;
+        attr_max[d != nullptr] = smem;
     }
     WdLaunchScope scope(WD_CLS_OTHER, st);
-    hipLaunchKernelGGL(gn_bwd_fused_kernel, dim3(c / GF_CB, batch), dim3(GF_NT), smem, st, x, ld, dz, dz_ld, dz_off, hw, c, cpg, part,
-                       nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx, dx_ld, accumulate);
+    if (d)
+        hipLaunchKernelGGL(gn_bwd_fused_kernel<wd_dropout>, dim3(c / GF_CB, batch), dim3(GF_NT), smem, st, x, ld, dz, dz_ld, dz_off, hw, c, cpg,
+                           part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx, dx_ld, accumulate, *d);
+    else
+        hipLaunchKernelGGL(gn_bwd_fused_kernel<>, dim3(c / GF_CB, batch), dim3(GF_NT), smem, st, x, ld, dz, dz_ld, dz_off, hw, c, cpg, part,
+                           nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx, dx_ld, accumulate);
     return wd_check_launch();
+}
+
+extern "C" int wd_gn_bwd_fused(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+                               const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off,
+                               float eps, int silu, float* sums, float* dx, int dx_ld, int accumulate, void* stream) {
+    return gn_bwd_fused_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx,
+                               dx_ld, accumulate, nullptr, stream);
+}
+
+extern "C" int wd_gn_bwd_fused_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c, int cpg,
+                                       const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off,
+                                       float eps, int silu, float* sums, float* dx, int dx_ld, int accumulate, const wd_dropout* d,
+                                       void* stream) {
+    if (!d) return WD_EINVAL;
+    return gn_bwd_fused_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx,
+                               dx_ld, accumulate, d, stream);
 }
 
 extern "C" int wd_gn_bwd_nchunk(int hw) { return (hw + GB_TOK - 1) / GB_TOK; }
 
-extern "C" int wd_gn_bwd_stats(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
+static int gn_bwd_stats_launch(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
                                int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
-                               const float* beta, int c_off, float eps, int silu, float* sums, void* stream) {
+                               const float* beta, int c_off, float eps, int silu, float* sums, const wd_dropout* d, void* stream) {
     if (!x || !dz || !part || !gamma || !beta || !sums || batch <= 0 || hw <= 0 || c <= 0 || cpg <= 0) return WD_EINVAL;
     if (c % 4 || ld % 4 || dz_ld % 4 || dz_off % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1081,8 +1135,48 @@ extern "C" int wd_gn_bwd_stats(const float* x, int ld, const float* dz, int dz_l
     const int bx = 64 * ((c / 4 + 63) / 64);
     if (bx * 2 > 1024) return WD_EINVAL;
     WdLaunchScope scope(WD_CLS_OTHER, st);
-    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(nchunk, batch), dim3(bx, 2), (64 + 4 * c) * sizeof(float), st, x, ld, dz,
-                       dz_ld, dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, nchunk, sums);
+    if (d)
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<wd_dropout>, dim3(nchunk, batch), dim3(bx, 2), (64 + 4 * c) * sizeof(float), st, x, ld, dz,
+                           dz_ld, dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, nchunk, sums, *d);
+    else
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<>, dim3(nchunk, batch), dim3(bx, 2), (64 + 4 * c) * sizeof(float), st, x, ld, dz,
+                           dz_ld, dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, nchunk, sums);
+    return wd_check_launch();
+}
+
+extern "C" int wd_gn_bwd_stats(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
+                               int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
+                               const float* beta, int c_off, float eps, int silu, float* sums, void* stream) {
+    return gn_bwd_stats_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums,
+                               nullptr, stream);
+}
+
+extern "C" int wd_gn_bwd_stats_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
+                                       int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
+                                       const float* beta, int c_off, float eps, int silu, float* sums, const wd_dropout* d,
+                                       void* stream) {
+    if (!d) return WD_EINVAL;
+    return gn_bwd_stats_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, d,
+                               stream);
+}
+
+static int gn_bwd_apply_launch(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
+                               int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
+                               const float* beta, int c_off, float eps, int silu, const float* sums, float* dx, int dx_ld,
+                               int accumulate, const wd_dropout* d, void* stream) {
+    if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0 || hw <= 0) return WD_EINVAL;
+    if (c % 4 || ld % 4 || dz_ld % 4 || dz_off % 4 || dx_ld % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg)
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    if (d)
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<wd_dropout>, dim3((hw + GA_TOK - 1) / GA_TOK, batch), dim3(256), 0, st, x, ld, dz, dz_ld,
+                           dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, wd_gn_bwd_nchunk(hw),
+                           dx, dx_ld, accumulate, *d);
+    else
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<>, dim3((hw + GA_TOK - 1) / GA_TOK, batch), dim3(256), 0, st, x, ld, dz, dz_ld,
+                           dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, wd_gn_bwd_nchunk(hw),
+                           dx, dx_ld, accumulate);
     return wd_check_launch();
 }
 
@@ -1090,15 +1184,17 @@ extern "C" int wd_gn_bwd_apply(const float* x, int ld, const float* dz, int dz_l
                                int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
                                const float* beta, int c_off, float eps, int silu, const float* sums, float* dx, int dx_ld,
                                int accumulate, void* stream) {
-    if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0 || hw <= 0) return WD_EINVAL;
-    if (c % 4 || ld % 4 || dz_ld % 4 || dz_off % 4 || dx_ld % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg)
-        return WD_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    WdLaunchScope scope(WD_CLS_OTHER, st);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((hw + GA_TOK - 1) / GA_TOK, batch), dim3(256), 0, st, x, ld, dz, dz_ld,
-                       dz_off, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, wd_gn_bwd_nchunk(hw),
-                       dx, dx_ld, accumulate);
-    return wd_check_launch();
+    return gn_bwd_apply_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx,
+                               dx_ld, accumulate, nullptr, stream);
+}
+
+extern "C" int wd_gn_bwd_apply_dropout(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
+                                       int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
+                                       const float* beta, int c_off, float eps, int silu, const float* sums, float* dx, int dx_ld,
+                                       int accumulate, const wd_dropout* d, void* stream) {
+    if (!d) return WD_EINVAL;
+    return gn_bwd_apply_launch(x, ld, dz, dz_ld, dz_off, batch, hw, c, cpg, part, nchunk_f, part_cpg, gamma, beta, c_off, eps, silu, sums, dx,
+                               dx_ld, accumulate, d, stream);
 }
 
 extern "C" int wd_layernorm_bwd_nblk(int rows) { return (rows + LB_ROWS - 1) / LB_ROWS; }

@@ -3,6 +3,7 @@
 // first conv unet.py:1251; Diffusion.sampling update train.py:229-236; noise_images train.py:190-194;
 // EMA train.py:151-159.
 #include "wd_common.h"
+#include "wd_philox.h"
 
 // The DDPM update, noise_images and the EMA are compared bit-for-bit with the reference's unfused fp32 torch ops:
 // no mul+add contraction anywhere in this translation unit.  (Plain operators are used on purpose: the header
@@ -92,22 +93,7 @@ __global__ void tok_to_nchw_kernel(const float* __restrict__ x, int ld, int batc
     }
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011) --------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+// ---- normal draws from Philox4x32-10 (wd_philox.h) ---------------------------------------------------
 __device__ __forceinline__ float4 philox_normal4(uint64_t seed, uint64_t sample, uint32_t tag, uint32_t e4) {
     uint32_t c[4] = {e4, tag, (uint32_t)sample, (uint32_t)(sample >> 32)};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));

@@ -3,6 +3,7 @@
 // Reference: GroupNorm32 unet.py:427-431 (eps 1e-5), Normalize unet.py:161-162 (eps 1e-6),
 // nn.LayerNorm unet.py:314-316, SiLU unet.py:594,618.
 #include "wd_common.h"
+#include "wd_philox.h"
 
 namespace {
 
@@ -53,11 +54,24 @@ struct GnSrc {  // one source tensor of a GroupNorm over a channel concat: its r
     const int32_t* perm;  // NULL, or [hw]: the row (inside its sample) that holds position t - a producer that wrote its rows in another order
 };
 
-// grid (token tiles, batch, sources): blockIdx.z picks the source
+__device__ __forceinline__ float4 gn_drop4(const wd_dropout& d, uint64_t drow, int token, int c, int ch, float4 y) {
+    bool keep[4];
+    wd_dropout_keep4(d, drow, token, c, ch, keep);
+    return make_float4(wd_dropout_apply(keep[0], y.x, d.scale), wd_dropout_apply(keep[1], y.y, d.scale),
+                       wd_dropout_apply(keep[2], y.z, d.scale), wd_dropout_apply(keep[3], y.w, d.scale));
+}
+
+// grid (token tiles, batch, sources): blockIdx.z picks the source.
+// D: nothing (the plain kernel - its signature and code are those of the kernel without the feature), or one wd_dropout (DROP): the
+// training dropout mask (wd_philox.h) on the normalised(+SiLU) value before the split - one draw per float4, the lane's four
+// channels being four consecutive elements (c % 4 == 0).
+template <typename... D>
 __global__ void gn_apply_kernel(const GnSrc s0, const GnSrc s1, int hw, int cpg, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, float eps, int silu, wd_bf16* __restrict__ out_hi,
                                 wd_bf16* __restrict__ out_lo, int out_ld, wd_bf16* __restrict__ raw_hi,
-                                wd_bf16* __restrict__ raw_lo) {
+                                wd_bf16* __restrict__ raw_lo, const D... dd) {
+    constexpr bool DROP = sizeof...(D) != 0;
+    const auto& d = wd_dropout_of(dd...);
     const GnSrc& sr = blockIdx.z ? s1 : s0;
     const float* __restrict__ x = sr.x;
     const double* __restrict__ part = sr.part;
@@ -86,6 +100,8 @@ __global__ void gn_apply_kernel(const GnSrc s0, const GnSrc s1, int hw, int cpg,
     __syncthreads();
     const int c4 = c >> 2;
     const int t0 = blockIdx.x * AP_TOK, nt = min(AP_TOK, hw - t0);
+    uint64_t drow = 0;
+    if constexpr (DROP) drow = wd_dropout_row(d, b);
     if (c4 <= 256) {
         // thread = (token lane, channel quad): the quad is fixed, so y = v * scale + shift with four per-thread constants each
         // (the group lookups - integer divisions by a run-time cpg - happen once, not per element)
@@ -107,6 +123,7 @@ __global__ void gn_apply_kernel(const GnSrc s0, const GnSrc s1, int hw, int cpg,
             if (silu) {
                 y.x = wd_silu(y.x); y.y = wd_silu(y.y); y.z = wd_silu(y.z); y.w = wd_silu(y.w);
             }
+            if constexpr (DROP) y = gn_drop4(d, drow, t0 + t, c, cx, y);
             uint2 h, l;
             wd_split4(y, h, l);
             const long o = row * out_ld + c_off + cx;
@@ -140,6 +157,7 @@ __global__ void gn_apply_kernel(const GnSrc s0, const GnSrc s1, int hw, int cpg,
         if (silu) {
             y.x = wd_silu(y.x); y.y = wd_silu(y.y); y.z = wd_silu(y.z); y.w = wd_silu(y.w);
         }
+        if constexpr (DROP) y = gn_drop4(d, drow, t0 + t, c, cx, y);
         uint2 h, l;
         wd_split4(y, h, l);
         const long o = row * out_ld + c_off + cx;
@@ -477,8 +495,23 @@ extern "C" int wd_gn_apply(const float* x, int ld, int batch, int hw, int c, int
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_GNAPPLY, st);
     const GnSrc s0 = {x, part, ld, c, nchunk, part_cpg, c_off, nullptr};
-    hipLaunchKernelGGL(gn_apply_kernel, dim3((hw + AP_TOK - 1) / AP_TOK, batch, 1), dim3(256), 0, st, s0, s0, hw, cpg, gamma, beta, eps,
+    hipLaunchKernelGGL(gn_apply_kernel<>, dim3((hw + AP_TOK - 1) / AP_TOK, batch, 1), dim3(256), 0, st, s0, s0, hw, cpg, gamma, beta, eps,
                        silu, out_hi, out_lo, out_ld, raw_hi, raw_lo);
+    return wd_check_launch();
+}
+
+extern "C" int wd_gn_apply_dropout(const float* x, int ld, int batch, int hw, int c, int cpg, const double* part, int nchunk,
+                                   int part_cpg, const float* gamma, const float* beta, float eps, int silu, wd_bf16* out_hi,
+                                   wd_bf16* out_lo, int out_ld, int c_off, wd_bf16* raw_hi, wd_bf16* raw_lo, const wd_dropout* d,
+                                   void* stream) {
+    if (!x || !part || !gamma || !beta || !out_hi || !d || batch <= 0 || hw <= 0 || c <= 0 || cpg <= 0 || nchunk <= 0 || part_cpg <= 0)
+        return WD_EINVAL;
+    if (c % 4 || ld % 4 || out_ld % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_GNAPPLY, st);
+    const GnSrc s0 = {x, part, ld, c, nchunk, part_cpg, c_off, nullptr};
+    hipLaunchKernelGGL(gn_apply_kernel<wd_dropout>, dim3((hw + AP_TOK - 1) / AP_TOK, batch, 1), dim3(256), 0, st, s0, s0, hw, cpg, gamma,
+                       beta, eps, silu, out_hi, out_lo, out_ld, raw_hi, raw_lo, *d);
     return wd_check_launch();
 }
 
@@ -496,7 +529,7 @@ extern "C" int wd_gn_apply2(const float* xa, int lda, int ca, const double* part
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_GNAPPLY, st);
     const GnSrc s0 = {xa, part_a, lda, ca, nchunk_a, part_cpg_a, c_off_a, perm_a}, s1 = {xb, part_b, ldb, cb, nchunk_b, part_cpg_b, c_off_b, nullptr};
-    hipLaunchKernelGGL(gn_apply_kernel, dim3((hw + AP_TOK - 1) / AP_TOK, batch, 2), dim3(256), 0, st, s0, s1, hw, cpg, gamma, beta, eps,
+    hipLaunchKernelGGL(gn_apply_kernel<>, dim3((hw + AP_TOK - 1) / AP_TOK, batch, 2), dim3(256), 0, st, s0, s1, hw, cpg, gamma, beta, eps,
                        silu, out_hi, out_lo, out_ld, raw_hi, raw_lo);
     return wd_check_launch();
 }

@@ -806,8 +806,9 @@ class UNetEngine:
         a.tickets, a.ntickets = tk.data_ptr() + 4 * P._ticket_off, ntick
         P._ticket_off += ntick
 
-    def _gn(self, P, ops, what, srcs: List[Act], gname, eps, silu, want_raw=False):
-        """GroupNorm over the channel concat of ``srcs`` -> planes [M, sum c] (+ raw planes)."""
+    def _gn(self, P, ops, what, srcs: List[Act], gname, eps, silu, want_raw=False, dropout=None):
+        """GroupNorm over the channel concat of ``srcs`` -> planes [M, sum c] (+ raw planes).  dropout: the wd_dropout of a training
+        ResBlock's second norm (one source) - the norm then takes the wd_gn_apply_dropout launch and is never fused into its producer."""
         B = self._B
         h, w = srcs[0].h, srcs[0].w
         hw = h * w
@@ -845,7 +846,7 @@ class UNetEngine:
                 s.stats = (part, nchunk, pc)
             # (_gn_in_combine: the producer is a K-cut GEMM whose combine tiles (64 rows x 40 columns) hold whole (sample, group)
             # blocks - its combine launch normalises the rows it has just summed and writes these planes)
-            if has_perm or not self._gn_in_combine(s, raw, gam, bet, eps, silu, cpg, pl, coff):
+            if has_perm or dropout is not None or not self._gn_in_combine(s, raw, gam, bet, eps, silu, cpg, pl, coff):
                 todo.append((s, part, nchunk, pc, coff))
             coff += s.c
         hi, lo = self._hilo(pl)
@@ -857,6 +858,12 @@ class UNetEngine:
                          B, hw, cpg, gam.data_ptr(), bet.data_ptr(), eps, int(silu), hi, lo, ctot, rhi, rlo,
                          sa.perm.data_ptr() if sa.perm is not None else None),
                         what + ":apply"))
+        elif dropout is not None:
+            assert not has_perm and len(srcs) == 1, what
+            (s, part, nchunk, pc, c0), = todo
+            ops.append((self.lib.wd_gn_apply_dropout,
+                        (s.t.data_ptr(), s.c, B, hw, s.c, cpg, part.data_ptr(), nchunk, pc, gam.data_ptr(), bet.data_ptr(), eps,
+                         int(silu), hi, lo, ctot, c0, rhi, rlo, C.byref(dropout)), what + ":apply+dropout"))
         else:
             assert not has_perm, what
             for s, part, nchunk, pc, c0 in todo:

@@ -205,8 +205,19 @@ class UNetBase(nn.Module):
                 self._train_engine.set_precision(mode)
         return self._train_engine
 
+    def set_dropout_state(self, seed: int, row_base: int = 0):
+        """Keys the training dropout of ``model(...)`` under autograd (``dropout.py``): the Philox seed, and the global row the
+        next training forward gives its sample 0 - every forward then advances it by its batch."""
+        eng = self.train_engine
+        eng.dropout_seed, eng.dropout_row_base = int(seed), int(row_base)
+        return self
+
     def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None):
         autograd = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if self.training and not autograd and float(self.dropout) > 0:
+            # the inference engine has no dropout: running it here would silently skip the layer train mode asks for
+            raise NotImplementedError(f"train mode with dropout={self.dropout} outside autograd: the HIP inference path applies "
+                                      "no dropout - call model.eval() first (or run under autograd to train)")
         if self.interpolation and mix_rate is not None:
             # unet.py:1558-1573 / unetPhosc.py:1093-1108: one pair of writers per call from Python's global ``random``, the same
             # blended row for every sample; ``y`` is unused.  (Without args.interpolation the reference ignores mix_rate.)

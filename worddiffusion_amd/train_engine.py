@@ -26,6 +26,7 @@ import os
 import torch
 
 from . import _native as N
+from . import dropout as DO
 from .backward import conv_bwd_table
 from .engine import Act, Plan, UNetEngine, _ptr
 from .layers import DownsampleParams, ResBlockParams, SpatialTransformerParams, UpsampleParams
@@ -45,6 +46,20 @@ class TrainPlan(Plan):
         super().__init__()
         self.bwd: List[tuple] = []
         self.dout: Optional[torch.Tensor] = None
+        # training dropout: the wd_dropout of every ResBlock with p > 0 (read by the host at launch or capture) and the device
+        # row base they all point to - uint64 [1] kept as int64 bits -, so a captured step draws new masks when replayed
+        self.dropouts: List[DO.WdDropout] = []
+        self.row_base: Optional[torch.Tensor] = None
+
+    def set_dropout_seed(self, seed: int):
+        for d in self.dropouts:
+            d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def set_row_base(self, row_base: int):
+        """Queues the write of the global row of sample 0 on the current stream (a no-op for a plan without dropout)."""
+        if self.dropouts:
+            v = int(row_base) & 0xFFFFFFFFFFFFFFFF
+            self.row_base.fill_(v - (1 << 64) if v >= (1 << 63) else v)
 
     def run_bwd(self, stream, begin: int = 0, end: Optional[int] = None):
         self._run(self.bwd[begin:end], stream)
@@ -87,6 +102,11 @@ class TrainEngine(UNetEngine):
         self._done_at: Dict[int, int] = {}           # gradient buffer data_ptr -> index of the last closure that writes it
         self._closure = 0
         self._cut_closures: Optional[List[int]] = None  # closures after which a bucket ends (fixed by the first plan)
+        # training dropout through model(...) under autograd: the mask key, and the global row of the next forward's sample 0
+        # (advanced by the batch after every training forward); TrainStep keys its own steps (training.py)
+        self.dropout_seed = 0
+        self.dropout_row_base = 0
+        self._layer_of: Optional[Dict[int, int]] = None  # id(ResBlock) -> dropout layer (dropout.layer_ids)
 
     def set_precision(self, mode: str):
         old = self.npass
@@ -456,7 +476,20 @@ class TrainEngine(UNetEngine):
                 else:
                     self._colsum(ops, what + ":dbias", dout.data_ptr(), ldd, M, n, M, b.data_ptr(), n, self._pacc(b))
 
-    def _gn_bwd(self, P, what, srcs: List[TAct], gn: torch.nn.GroupNorm, eps, silu, dz: torch.Tensor):
+    def _dropout_args(self, P, mod: ResBlockParams, p: float) -> DO.WdDropout:
+        """The wd_dropout of ResBlock ``mod``: layer tag, threshold and scale fixed here, the seed set before every launch or
+        capture (TrainPlan.set_dropout_seed), the row read on the device from the plan's row base."""
+        if self._layer_of is None:
+            ids = DO.layer_ids(self.model)
+            self._layer_of = {id(m_): ids[n_ + "."] for n_, m_ in self.model.named_modules() if isinstance(m_, ResBlockParams)}
+        d = DO.WdDropout()
+        d.seed, d.row_base, d.row_base_dev = 0, 0, P.row_base.data_ptr()
+        d.tag, d.thr, d.scale = DO.tag(self._layer_of[id(mod)]), DO.threshold(p), float(DO.scale(p))
+        P.dropouts.append(d)
+        return d
+
+    def _gn_bwd(self, P, what, srcs: List[TAct], gn: torch.nn.GroupNorm, eps, silu, dz: torch.Tensor, dropout=None):
+        """dropout: the wd_dropout the forward masked this norm's output with (one source) - dz is masked on load."""
         ops = P.bwd
         lib = self.lib
         B = self._B
@@ -478,7 +511,15 @@ class TrainEngine(UNetEngine):
             common = (s.t.data_ptr(), s.c, dz.data_ptr(), ctot, off, B, hw, s.c, cpg, part.data_ptr(), nchunk, pc,
                       gw.data_ptr(), gb.data_ptr(), off, eps, int(silu), sums.data_ptr())
             g, acc = self._gacc(P, s)
-            if fused:
+            if dropout is not None:
+                assert len(srcs) == 1, what
+                dr = (C.byref(dropout),)
+                if fused:
+                    ops.append((lib.wd_gn_bwd_fused_dropout, common + (g.data_ptr(), s.c, acc) + dr, what + ":bwd+dropout"))
+                else:
+                    ops.append((lib.wd_gn_bwd_stats_dropout, common + dr, what + ":stats+dropout"))
+                    ops.append((lib.wd_gn_bwd_apply_dropout, common + (g.data_ptr(), s.c, acc) + dr, what + ":apply+dropout"))
+            elif fused:
                 ops.append((lib.wd_gn_bwd_fused, common + (g.data_ptr(), s.c, acc), what + ":bwd"))
             else:
                 ops.append((lib.wd_gn_bwd_stats, common, what + ":stats"))
@@ -538,8 +579,9 @@ class TrainEngine(UNetEngine):
         cin, cout = mod.cin, mod.cout
         tab, _, _ = self._table(h, w, "same")
         need_raw = cin != cout
-        if mod.out_layers[2].p != 0:
-            raise NotImplementedError("dropout > 0 in the HIP training step (train.py builds the UNet with dropout 0)")
+        # nn.Dropout(p) of out_layers (unet.py:616-623): on the planes conv2 reads, recomputed by the backward of the second norm
+        p_drop = DO.check_p(mod.out_layers[2].p)
+        drop = self._dropout_args(P, mod, p_drop) if p_drop > 0 else None
         cpg = cin // 32
         parts = None
         if any(s.c % cpg for s in srcs):
@@ -559,7 +601,7 @@ class TrainEngine(UNetEngine):
                         bias=self._w[name + ".c1.b"], rowvec=self._film.data_ptr() + 4 * self.film_off[name],
                         rowvec_ld=self.film_total, out_f32=h1t, out_ld=cout, want_stats=True)
         h1 = TAct(h1t, cout, h, w, g1._stats)
-        a2, _ = self._gn(P, ops, name + ".gn2", [h1], name + ".gn2", 1e-5, True)
+        a2, _ = self._gn(P, ops, name + ".gn2", [h1], name + ".gn2", 1e-5, True, dropout=drop)
         outt = self._f32(P, M, cout)
         if need_raw:
             g2 = self._gemm(ops, name + ".conv2+skip", [self._src(a2, cout, 9, tab, hw), self._src(raw, cin)],
@@ -600,7 +642,7 @@ class TrainEngine(UNetEngine):
                     bops.append((self.lib.wd_copy2d, (g.data_ptr(), 4 * cout, dO.data_ptr(), 4 * cout, 4 * cout, M),
                                  name + ":dresid"))
             self._bwd_linear(P, name + ".conv2", dO, M, cout, hw, segs, bias=biases)
-            self._gn_bwd(P, name + ".gn2", [h1], mod.out_layers[0], 1e-5, True, da2)
+            self._gn_bwd(P, name + ".gn2", [h1], mod.out_layers[0], 1e-5, True, da2, dropout=drop)
             da1 = self._f32(P, M, cin)
             self._bwd_linear(P, name + ".conv1", h1.g, M, cout, hw,
                              [dict(planes=a1, c=cin, ntaps=9, ftab=tab, btab=btab, hw_src=hw, wb="B:" + name + ".c1.w",
@@ -838,7 +880,9 @@ class TrainEngine(UNetEngine):
             self._ws = torch.empty(max(128 * 128 * 160 * 8, 8 * 2 * cmax * 9 * cmax), dtype=torch.float32, device=self.device)
 
     def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0) -> TrainPlan:
-        key = (B, H, W, ctx_len, phosc_len, self.npass)
+        # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1): refused before any device work; a plan is built for its p's
+        drops = tuple(DO.check_p(mod.out_layers[2].p) for _, mod in self._walk() if isinstance(mod, ResBlockParams))
+        key = (B, H, W, ctx_len, phosc_len, self.npass) + ((drops,) if any(drops) else ())
         P = self._cached_plan(self._tplans, key)
         if P is not None:
             return P
@@ -853,6 +897,7 @@ class TrainEngine(UNetEngine):
         if phosc_len and self.variant != "phosc":
             raise ValueError("phoscLabels are an input of UNetModelPhosc only")
         P = self._begin_plan(TrainPlan(), B)
+        P.row_base = torch.zeros(1, dtype=torch.int64, device=self.device)
         L = ctx_len + phosc_len
         self._tape = []
         self._pw = set()
@@ -1032,6 +1077,10 @@ class TrainEngine(UNetEngine):
         self.check_ids(context, y, phosc)
         P = self.plan_train(B, H, W, context.shape[1], 0 if phosc is None else phosc.shape[1])
         self.load_inputs(P, x, t, context, y, phosc, check=False)
+        if P.dropouts:
+            P.set_dropout_seed(self.dropout_seed)
+            P.set_row_base(self.dropout_row_base)
+            self.dropout_row_base += B
         stream = torch.cuda.current_stream(self.device).cuda_stream
         P.run_step(stream)
         self._live = P

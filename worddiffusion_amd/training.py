@@ -152,6 +152,10 @@ class TrainStep:
         with torch.cuda.stream(self._stream):
             st = self._stream.cuda_stream
             P.t_in.copy_(t, non_blocking=True)
+            # training dropout: masks keyed like the eps rows below - (seed, global row of the step) -, the row read on the device
+            # so that the captured step draws new masks every time it is replayed
+            P.set_dropout_seed(self.seed)
+            P.set_row_base((self.step_index * self.world + self.rank) * B)
             P.ctx_in.copy_(text_features, non_blocking=True)
             if phoscLabels is not None:  # UNetModelPhosc: PHOSC vector appended to the context (unetPhosc.py:1119-1131)
                 P.phosc_in.copy_(phoscLabels.to(torch.int32) if phoscLabels.dtype != torch.int32 else phoscLabels,
