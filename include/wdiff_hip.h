@@ -533,7 +533,8 @@ int wd_mse_loss(const float* pred, const float* target, int64_t n, float* grad, 
  * out[(t*c + ch)][mm] (tap_minor = 0) or out[(ch*ntaps + t)][mm] (tap_minor = 1: the OIHW order of a conv weight)
  *   = in[src(mm, t)][ch] for mm < m (0 beyond, up to mpad): split-bf16 planes [ntaps*c][mpad].
  * in: planes (in_is_f32 = 0; in_lo may be NULL) or one fp32 matrix (in_is_f32 = 1, split on the fly); src = row mm, or
- * through the 3x3 gather table as in wd_gemm (zero row for -1). */
+ * through the 3x3 gather table as in wd_gemm (zero row for -1).  mpad >= m and mpad % 4 == 0 (four tokens per store), else
+ * WD_EINVAL; gather == NULL requires ntaps == 1.  (The training engine passes a multiple of 64.) */
 int wd_transpose_planes(const void* in_hi, const void* in_lo, int in_is_f32, int ld, int c, const int32_t* gather, int ntaps,
                         int hw_out, int hw_src, int m, int mpad, int tap_minor, wd_bf16* out_hi, wd_bf16* out_lo,
                         void* stream);
@@ -590,7 +591,8 @@ int wd_dw_args_bytes(void);
 
 /* (bias gradients of the layers above; gradient of the FiLM vector emb_out[..., None, None], unet.py:660-661)
  * out[s][col] (+)= scale * sum over rows [s*seg, (s+1)*seg) of x[row][col]; fixed summation order.
- * scratch: ceil(rows/seg) * ceil(seg/64) * c floats.  (bias gradients: seg = rows; FiLM gradient: seg = hw.) */
+ * scratch: ceil(rows/seg) * ceil(seg/128) * c floats (one partial row per 128-row block of a segment); WD_EINVAL when
+ * scratch_floats is less.  (bias gradients: seg = rows; FiLM gradient: seg = hw.) */
 int wd_colsum(const float* x, int ld, int rows, int c, int seg, float* out, int out_ld, int accumulate, float scale,
               float* scratch, int64_t scratch_floats, void* stream);
 
@@ -654,7 +656,7 @@ int wd_layernorm_bwd_nblk(int rows);
 int wd_layernorm_bwd(const float* x, int ld, const float* dy, int dy_ld, int rows, int c, const float* gamma, float eps,
                      float* dx, int dx_ld, int accumulate, float* colpart, void* stream);
 
-/* softmax-attention backward (CrossAttention.forward unet.py:185-279, Word_Attention :823-836) for nk <= 16 keys: dq[B*nq][lddq]; dkv_part[b][nwg][2][nk][heads*d] = per-workgroup partial
+/* softmax-attention backward (CrossAttention.forward unet.py:185-279, Word_Attention :823-836) for nk <= 16 keys: dq[B*nq][lddq]; dkv_part[b][nwg][nk][2][heads*d] = per-workgroup partial
  * sums of (dK, dV) over their tokens (nwg returned; the caller column-sums them). */
 /* number of per-workgroup dK/dV partial slabs wd_attention_bwd_small writes per batch element (0 = unsupported shape) */
 int wd_attention_bwd_small_nwg(int heads, int nq, int nk, int d);

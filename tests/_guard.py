@@ -31,6 +31,14 @@ def guarded(rows, cols, ld, col0, dtype, guard_rows=2, device="cpu", planes=0):
     return buf, buf[..., guard_rows:guard_rows + rows, col0:col0 + cols]
 
 
+def guarded_flat(n, dtype, pad=64, device="cpu"):
+    """(buf, view): a contiguous run of n elements - a scratch buffer, a [b][chunk][2][c] block of sums, any output that has no pitch
+    of its own - with pad poisoned elements before and after it.  buf is [1][n + 2 * pad], view its 1-D window of n elements
+    (pad = 64 keeps a 16-byte aligned buffer's window 16-byte aligned for every element type)."""
+    buf, view = guarded(1, n, n + 2 * pad, pad, dtype, 0, device)
+    return buf, view[0]
+
+
 def pitched(x, ld, col0, guard_rows=2, device="cpu"):
     """The 2-D tensor x placed as guarded() places a window, NaN everywhere else."""
     buf, view = guarded(x.shape[0], x.shape[1], ld, col0, x.dtype, guard_rows, device)
@@ -56,7 +64,7 @@ def view_spec(buf, view):
     ld = buf.shape[-1]
     off = view.storage_offset() - buf.storage_offset()
     off %= buf.shape[-2] * ld  # (the same window in every plane)
-    return off // ld, view.shape[-2], off % ld, view.shape[-1]
+    return off // ld, (view.shape[-2] if view.dim() > 1 else 1), off % ld, view.shape[-1]  # (1-D: the window of guarded_flat)
 
 
 def assert_untouched(buf, spec, name="buffer"):

@@ -269,6 +269,49 @@ def test_upsample_as_four_phases_equals_the_nine_tap_form():
     assert torch.isfinite(outs[0]).all() and max_rel(outs[0].cpu(), outs[1].cpu()) < 2e-5
 
 
+def test_weights_change_after_a_phase_major_upsample_plan():
+    """A parameter update after the phase plan exists (EMA sampling during training): refresh_weights re-derives the summed-tap
+    tensor, repacks the four phase matrices from its pieces (column offset t * cin) and writes the grouped fragment-major images
+    in the same launch.  B = 64 is the smallest batch whose plan holds the phase launch: its 4 B tiles of 64 rows must fill the
+    256 CUs (engine.wdirect_fills_chip)."""
+    from worddiffusion_amd.engine import wdirect_fills_chip
+    B, scale = 64, 1.25
+    assert wdirect_fills_chip(B * 4 * 64, 320) and not wdirect_fills_chip((B - 1) * 4 * 64, 320)
+    inp = synthetic_inputs(B, seed=3)
+    m = build(FULL, "base", False, seed=1)
+    eng = m.engine
+    assert eng.use_up_phases
+    before = call(m, "base", inp["x"], inp["t"], inp["context"], inp["y"])
+    P = next(iter(eng._plans.values()))
+    assert sum(1 for _, _, what in P.step if "4 phases" in what) == 1
+    names = sorted(k for k in eng._wf if ".wph" in k)
+    assert len(names) == 4 and all(n in eng._w for n in names)
+    old = {n: eng._wf[n].clone() for n in names}
+    with torch.no_grad():
+        for p_ in m.parameters():
+            p_.mul_(scale)
+    eng.refresh_weights()
+    assert eng._pack[4] == []
+    st = torch.cuda.current_stream(DEV).cuda_stream
+    for n in names:
+        want = torch.empty(eng._wf[n].shape, dtype=torch.bfloat16, device=DEV)
+        eng._pack_wf(n, want, st)
+        torch.cuda.synchronize()
+        assert torch.equal(eng._wf[n], want), n
+        assert not torch.equal(eng._wf[n], old[n]), n
+    after = call(m, "base", inp["x"], inp["t"], inp["context"], inp["y"])
+    assert next(iter(eng._plans.values())) is P  # the plan built before the update ran again
+    fresh = build(FULL, "base", False, seed=1)
+    fresh.engine.use_up_phases = False
+    with torch.no_grad():
+        for p_ in fresh.parameters():
+            p_.mul_(scale)
+    ref = call(fresh, "base", inp["x"], inp["t"], inp["context"], inp["y"])
+    assert all("4 phases" not in what for _, _, what in next(iter(fresh.engine._plans.values())).step)
+    assert torch.isfinite(after).all() and not torch.equal(after, before)
+    assert max_rel(after.cpu(), ref.cpu()) < 2e-5
+
+
 def test_full_size_properties_b64_phosc():
     """BASELINE configs[4]'s one-GPU share at the benchmark batch: UNetModelPhosc (args.phosc = 1), 320 channels, 10 word ids +
     the 769-int PHOSC vector (779-key cross-attention, 256-key self-attention), B = 64 - determinism, per-sample independence

@@ -61,3 +61,40 @@ def test_poisoned_operands_and_the_finite_check():
     oview.copy_(buf[2:5, 3:7] + 1)  # a window read one column too far to the left
     with pytest.raises(AssertionError, match=r"3 non-finite"):
         G.assert_finite(oview)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16])
+def test_flat_guard_reports_a_write_before_and_after_the_run(dtype):
+    """guarded_flat: the contiguous outputs of the backward kernels (scratch, [b][chunk][2][c] sums, [b][nwg][nk][2][inner] partials)."""
+    buf, view = G.guarded_flat(2 * 3 * 2 * 8, dtype, pad=16)
+    assert buf.shape == (1, 96 + 32) and view.shape == (96,) and view.is_contiguous() and G.view_spec(buf, view) == (0, 1, 16, 96)
+    assert view.data_ptr() - buf.data_ptr() == 16 * buf.element_size()
+    assert bool(torch.isnan(buf.float()).all())
+    G.assert_untouched(buf, view)
+    view.view(2, 3, 2, 8).fill_(1)  # the kernels' own shape over the same storage
+    G.assert_untouched(buf, view)
+    G.assert_finite(view.view(2, 3, 2, 8))
+    for c in (15, 112, 0, 127):  # the element before the run, the one after it, the two ends of the buffer
+        b2 = buf.clone()
+        b2[0, c] = 3
+        with pytest.raises(AssertionError, match=rf"\(row 0, column {c}\) = 3"):
+            G.assert_untouched(b2, (0, 1, 16, 96), "sums")
+    view[95] = float("nan")
+    with pytest.raises(AssertionError, match=r"first at \(1, 2, 1, 7\)"):
+        G.assert_finite(view.view(2, 3, 2, 8))
+
+
+def test_a_window_as_wide_as_its_buffer_is_guarded_by_rows_alone():
+    """The transposed planes [n][mpad] have no pitch of their own: a row of the next channel (or a row past the last) is the guard,
+    and an empty window (a launch that must not happen) makes every element one."""
+    buf, view = G.guarded(3, 8, 8, 0, torch.bfloat16, guard_rows=1, planes=2)
+    view.fill_(0)
+    G.assert_untouched(buf, view)
+    for r in (0, 4):
+        b2 = buf.clone()
+        b2[1, r, 2] = 0
+        with pytest.raises(AssertionError, match=rf"plane 1, \(row {r}, column 2\)"):
+            G.assert_untouched(b2, view)
+    with pytest.raises(AssertionError, match=r"24 element\(s\), first at plane 0, \(row 1, column 0\)"):
+        G.assert_untouched(buf[:1], (0, 0, 0, 0))
+    G.assert_untouched(G.poisoned((2, 5, 8), torch.bfloat16), (0, 0, 0, 0))

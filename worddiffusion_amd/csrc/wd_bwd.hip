@@ -481,7 +481,7 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, int ld, const f
 }
 
 // ---- LayerNorm backward: one wave per row; a block walks LB_ROWS rows and emits per-column partial sums of
-// dy * xhat (-> d gamma) and dy (-> d beta): colpart[blk][c][2]
+// dy * xhat (-> d gamma) and dy (-> d beta): colpart[blk][2][c] (planar: [d gamma | d beta])
 constexpr int LB_MAX4 = 8;
 constexpr int LB_ROWS = 16;
 // MAX4 = float4 per lane and row (c <= 256 MAX4): the per-lane row image and the column sums live in registers, so the small
@@ -920,6 +920,7 @@ extern "C" int wd_transpose_planes(const void* in_hi, const void* in_lo, int in_
     if (!in_hi || !out_hi || c <= 0 || m <= 0 || mpad < m || ntaps < 1 || (gather && (hw_out <= 0 || hw_src <= 0)))
         return WD_EINVAL;
     if (!gather && ntaps != 1) return WD_EINVAL;
+    if (mpad & 3) return WD_EINVAL;  // four tokens per 8-byte store: a ragged last quad would run into the next channel row
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     const dim3 grid((mpad + 63) / 64, (c + 63) / 64, ntaps);
@@ -1086,6 +1087,7 @@ static int gn_bwd_fused_launch(const float* x, int ld, const float* dz, int dz_l
                                const double* part, int nchunk_f, int part_cpg, const float* gamma, const float* beta, int c_off,
                                float eps, int silu, float* sums, float* dx, int dx_ld, int accumulate, const wd_dropout* d, void* stream) {
     if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0) return WD_EINVAL;
+    if (hw <= 0 || c <= 0 || cpg <= 0 || part_cpg <= 0) return WD_EINVAL;  // (before any % below)
     if (!wd_gn_bwd_fused_supported(hw, c, cpg)) return WD_EINVAL;
     if (ld % 4 || dz_ld % 4 || dz_off % 4 || dx_ld % 4 || c_off % 4 || cpg % part_cpg) return WD_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dx)) & 15) return WD_EINVAL;
@@ -1128,7 +1130,8 @@ extern "C" int wd_gn_bwd_nchunk(int hw) { return (hw + GB_TOK - 1) / GB_TOK; }
 static int gn_bwd_stats_launch(const float* x, int ld, const float* dz, int dz_ld, int dz_off, int batch, int hw, int c,
                                int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
                                const float* beta, int c_off, float eps, int silu, float* sums, const wd_dropout* d, void* stream) {
-    if (!x || !dz || !part || !gamma || !beta || !sums || batch <= 0 || hw <= 0 || c <= 0 || cpg <= 0) return WD_EINVAL;
+    if (!x || !dz || !part || !gamma || !beta || !sums || batch <= 0 || hw <= 0 || c <= 0 || cpg <= 0 || part_cpg <= 0)
+        return WD_EINVAL;
     if (c % 4 || ld % 4 || dz_ld % 4 || dz_off % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nchunk = wd_gn_bwd_nchunk(hw);
@@ -1164,7 +1167,8 @@ static int gn_bwd_apply_launch(const float* x, int ld, const float* dz, int dz_l
                                int cpg, const double* part, int nchunk_f, int part_cpg, const float* gamma,
                                const float* beta, int c_off, float eps, int silu, const float* sums, float* dx, int dx_ld,
                                int accumulate, const wd_dropout* d, void* stream) {
-    if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0 || hw <= 0) return WD_EINVAL;
+    if (!x || !dz || !part || !gamma || !beta || !sums || !dx || batch <= 0 || hw <= 0 || c <= 0 || cpg <= 0 || part_cpg <= 0)
+        return WD_EINVAL;
     if (c % 4 || ld % 4 || dz_ld % 4 || dz_off % 4 || dx_ld % 4 || c_off % 4 || c % cpg || c / cpg > 32 || cpg % part_cpg)
         return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
