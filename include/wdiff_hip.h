@@ -200,7 +200,12 @@ int wd_gemm_pack_w(const wd_bf16* hi, const wd_bf16* lo, int n, int ktot, wd_bf1
  *         x    = norm3(tok2) -> the feed-forward above, resid = tok2 (written to the fp32 scratch tok2 [m][320]; resid ignored)
  *     GroupNorm statistics as wd_gemm_args.a32*: gn_part [batch][gn_nchunk][c / gn_pcpg][2], groups of gn_cpg channels, samples of
  *     hw rows (hw % 64 == 0, m % hw == 0).  pi: wd_gemm_pack_w image of the [320][320] proj_in.  mq_* / mot_*: the per-sample
- *     fragment-major planes of wd_xattn_fold; wd_xattn_supported(320, heads, L).  npass 3 and w3 only. */
+ *     fragment-major planes of wd_xattn_fold; wd_xattn_supported(320, heads, L).  npass 3 and w3 only.
+ * w32_hi != NULL (with w3, npass 3): the folded tail.  No non-linearity separates the two last products, so
+ *     out = resid3 + GEGLU(...) W32^T + resid W3^T + b32,   W32 = W3 W2 ([c][inner]),  b32 = W3 b2 + b3   (wd_linear_fold)
+ * with w32 the wd_gemm_pack_w image of W32: resid W3^T is formed before the hidden chunks, the chunks add their part on top, and
+ * the feed-forward result is never materialised (w2 / b2 / b3 are not read).  With x_in, tok2 may be NULL and is then not written.
+ * Without x_in, resid is required. */
 typedef struct wd_ff_args {
     const wd_bf16* x_hi;
     const wd_bf16* x_lo;
@@ -252,6 +257,9 @@ typedef struct wd_ff_args {
     float ln_eps; /* norm2 and norm3 */
     int32_t heads, L;
     float* tok2;
+    const wd_bf16* w32_hi; /* folded tail (needs w3, npass 3): see above */
+    const wd_bf16* w32_lo;
+    const float* b32;
 } wd_ff_args;
 int wd_ff_fused(const wd_ff_args* args, void* stream);
 int wd_ff_supported(int c, int inner); /* 1 when wd_ff_fused covers the shape */
@@ -383,6 +391,21 @@ int wd_xattn_pair(const float* x, int ld, int batch, int hw, int c, float eps, i
                   const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a, const float* gamma_b,
                   const float* beta_b, const wd_bf16* mq_pl_b, const wd_bf16* mot_pl_b, const float* bias_b, float* out, int out_ld,
                   const float* gamma2, const float* beta2, float eps2, wd_bf16* n_hi, wd_bf16* n_lo, int n_ld, void* stream);
+
+/* wd_xattn_pair (or, with mq_pl_b == NULL, the single folded cross-attention a in its MFMA form: gamma_b .. bias_b unused) that
+ * also writes its result as raw operand planes r_hi / r_lo [rows][r_ld] (r_lo may be NULL): the A operand of a product that
+ * reads it next.  out, n_hi / n_lo are what wd_xattn_pair / wd_xattn_fused write, bit for bit. */
+int wd_xattn_planes(const float* x, int ld, int batch, int hw, int c, float eps, int heads, int L, const float* gamma_a,
+                    const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a, const float* gamma_b,
+                    const float* beta_b, const wd_bf16* mq_pl_b, const wd_bf16* mot_pl_b, const float* bias_b, float* out, int out_ld,
+                    const float* gamma2, const float* beta2, float eps2, wd_bf16* n_hi, wd_bf16* n_lo, int n_ld, wd_bf16* r_hi,
+                    wd_bf16* r_lo, int r_ld, void* stream);
+
+/* Two linear layers with nothing between them as one: w32 [c][ffi] = w3 [c][inner] . w2 [inner][ffi] and b32 [c] = w3 . b2 + b3
+ * (b2 / b3 may be NULL: zeros).  fp64 products summed in ascending k and rounded once to fp32; no library GEMM.  The folded tail
+ * of wd_ff_fused and the two-source ff2 + proj_out GEMM of the SpatialTransformer read the result (unet.py:145,406-412). */
+int wd_linear_fold(const float* w3, const float* w2, const float* b2, const float* b3, int c, int inner, int ffi, float* w32,
+                   float* b32, void* stream);
 
 /* nn.Embedding lookup + positional encoding (CharacterEncoder, unet.py:860-872; PE skipped when pe == NULL,
  * unetPhosc.py:726-729): planes[r][:] = table[ids[r]][:] + pe[r % seq_len][:]. ids are int64 or int32. */

@@ -56,7 +56,8 @@ class WdFfArgs(C.Structure):
                 ("gn_pcpg", C.c_int32), ("gn_cpg", C.c_int32), ("gn_eps", C.c_float), ("gn_gamma", _vp), ("gn_beta", _vp),
                 ("pi_hi", _vp), ("pi_lo", _vp), ("pi_b", _vp), ("ln2_gamma", _vp), ("ln2_beta", _vp), ("mq_a", _vp), ("mot_a", _vp),
                 ("xb_a", _vp), ("mq_b", _vp), ("mot_b", _vp), ("xb_b", _vp), ("ln3_gamma", _vp), ("ln3_beta", _vp),
-                ("ln_eps", C.c_float), ("heads", C.c_int32), ("L", C.c_int32), ("tok2", _vp)]
+                ("ln_eps", C.c_float), ("heads", C.c_int32), ("L", C.c_int32), ("tok2", _vp),
+                ("w32_hi", _vp), ("w32_lo", _vp), ("b32", _vp)]
 
 
 class WdDwArgs(C.Structure):
@@ -151,6 +152,9 @@ _SIGS = {
     "wd_next_timestep": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
     "wd_xattn_pair": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f,
                            _vp, _vp, _i, _vp]),
+    "wd_xattn_planes": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f,
+                             _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "wd_linear_fold": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "wd_add": (_i, [_vp, _vp, C.c_int64, _vp]),
     "wd_permute_dw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "wd_colsum": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, C.c_int64, _vp]),

@@ -19,6 +19,13 @@
 // K-half x column-group product of proj_out), both folded cross-attentions (wd_xattn.hip's arithmetic on 64 tokens instead of
 // 16) and norm3 straight into the resident rows - every step is token-local and a 64-token panel of the 8 x 32 level lies in one
 // sample, so the three launches of the chain and their three fp32 / plane round trips through HBM become phases of this one.
+//
+// FOLD (wd_ff_args.w32_*, with PROJ): nothing non-linear lies between the second product and proj_out, so
+//     out = x_in + h (Wo W2)^T + x Wo^T + (Wo b2 + bo)
+// with W32 = Wo W2 and b32 derived once per weight refresh (wd_linear_fold).  x Wo^T goes into the accumulators BEFORE the chunk
+// loop - x is then still at hand: in the front's registers, or read from `resid` - the chunk loop adds h W32^T on top, and one
+// K-half sum and the epilogue finish.  x' is never formed: no fp32 scratch of x (21 MB written, read back and written back per
+// launch at 64 x 8 x 32), no in-place plane split over the image, one K-half sum instead of two; the multiply-adds are the same.
 #include "wd_gemm_epi.h"
 
 namespace {
@@ -36,10 +43,11 @@ typedef __attribute__((ext_vector_type(4))) unsigned f_u32x4;
 
 __device__ __forceinline__ int f_lds_off(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
 
-template <int NPASS, bool PROJ, bool FRONT>
+template <int NPASS, bool PROJ, bool FRONT, bool FOLD>
 __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(!FRONT || (NPASS == 3 && PROJ), "the transformer front needs split-bf16 operands and the proj_out tail");
+    static_assert(!FOLD || (NPASS == 3 && PROJ), "the folded tail is the proj_out tail in split-bf16");
     constexpr int NPL = (NPASS == 1) ? 1 : 2;
     constexpr int SLAB = 2 * FBM * 128;            // one 64-deep K slab of 64 rows, both planes (plane stride FBM * 128)
     constexpr int A_BYTES = 5 * SLAB;              // the resident token rows: 320 channels
@@ -62,7 +70,9 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(p), 0, 0x7FFFFFF0, 0x00020000);
     };
     const __amdgpu_buffer_rsrc_t srd1_hi = make_srd(a.w1_hi), srd1_lo = make_srd(a.w1_lo ? a.w1_lo : a.w1_hi);
-    const __amdgpu_buffer_rsrc_t srd2_hi = make_srd(a.w2_hi), srd2_lo = make_srd(a.w2_lo ? a.w2_lo : a.w2_hi);
+    // (FOLD: the second product runs against W32 = W3 W2, and W3 meets tok2 BEFORE the chunk loop - see the header of the file)
+    const __amdgpu_buffer_rsrc_t srd2_hi = make_srd(FOLD ? a.w32_hi : a.w2_hi),
+                                 srd2_lo = make_srd(FOLD ? a.w32_lo : a.w2_lo ? a.w2_lo : a.w2_hi);
     const __amdgpu_buffer_rsrc_t srd3_hi = make_srd(PROJ ? a.w3_hi : a.w2_hi), srd3_lo = make_srd(PROJ ? (a.w3_lo ? a.w3_lo : a.w3_hi) : a.w2_hi);
     const uint32_t lane16 = lane * 16;
     const int nct1 = (2 * a.inner) >> 4;          // column tiles of W1 (x / gate tiles alternate: wd_ff_fused's packing)
@@ -74,7 +84,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
     auto issue = [&](const int slot, const int g, const int j) {  // slot, g compile-time; j run-time (uniform)
         const bool live = j < nchunk;
         const uint32_t vo = live ? lane16 : F_OOB;
-        if (PROJ && g < FRING) {
+        if (PROJ && !FOLD && g < FRING) {
             // the first groups of "chunk nchunk" are the first groups of the proj_out product (k-step 2 (g / 5) + kh, tile g % 5): ONE
             // pair of loads with the descriptor and offset selected - a load inside a run-time branch makes hipcc's wait-count pass
             // assume it may not have been issued, every such branch lowers the vmcnt it dares to wait for by two, and the six of
@@ -140,6 +150,43 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         }
     };
 
+    // ---- FOLD: acc2 = tok2 W3^T from the tok2 planes in the resident rows (K = 320 as ten k-steps, K-half kh takes the k-steps
+    // 2 q + kh, as proj_in), BEFORE the chunk loop adds h W32^T on top.  Group g rides in ring slot (g + 5) % 6, so that the 25th
+    // leaves the ring where chunk 0 expects it: the last six refills are chunk 0's first groups.
+    auto issue_w3 = [&](const int slot, const int g) {
+        const uint32_t so = (uint32_t)(((2 * (g / 5) + kh) * (FC / 16) + 5 * cg + g % 5) * 1024);
+#pragma unroll
+        for (int p = 0; p < NPL; ++p)
+            ring[slot][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(p ? srd3_lo : srd3_hi, lane16, so, 0));
+    };
+    // the groups of the slabs [q0, q1), whose planes start at `slabs` (callers: the first FRING groups requested, the planes
+    // complete and a barrier passed)
+    auto fold_product = [&](const int q0, const int q1, const char* slabs) {
+        if (q0 == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int t = 0; t < 5; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc2[i][t][r] = 0.0f;
+        }
+#pragma unroll
+        for (int g = 0; g < 25; ++g) {
+            const int q = g / 5, t = g % 5;
+            if (q < q0 || q >= q1) continue;
+            if (t == 0) read_frags(slabs + (q - q0) * SLAB, kh);
+            {
+                f32x4 col[4] = {acc2[0][t], acc2[1][t], acc2[2][t], acc2[3][t]};
+                mfma12(col, ring[(g + 5) % FRING]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc2[i][t] = col[i];
+            }
+            if (g + FRING < 25) issue_w3((g + 5) % FRING, g + FRING);
+            else issue((g + 5) % FRING, g + FRING - 25, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
     if constexpr (FRONT) {
         // ================= the transformer front: GroupNorm + proj_in, attn1, attn2, norm3 -> the resident rows =================
         constexpr int SP = 65, PP = 72, KS32 = FC / 32;
@@ -151,7 +198,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         wd_bf16* sP = reinterpret_cast<wd_bf16*>(fr + FBM * SP * 4);  // [2][FBM][PP] probability planes, padding columns 0
         // the per-channel vectors of the phases below, staged once: 7 x FC floats behind the front's scratch, inside the second h
         // image (which the chunk loop first writes in chunk 1, long after norm3 has read them)
-        float* s_vec = reinterpret_cast<float*>(s_h + 40960);
+        float* s_vec = reinterpret_cast<float*>(s_h + (FOLD ? 49152 : 40960));  // (FOLD: 48 KB of tok2 planes lie in front of them)
         const float* s_pib = s_vec;
         const float* s_ln2g = s_vec + FC, * s_ln2b = s_vec + 2 * FC, * s_ln3g = s_vec + 3 * FC, * s_ln3b = s_vec + 4 * FC;
         const float* s_xba = s_vec + 5 * FC, * s_xbb = s_vec + 6 * FC;
@@ -468,7 +515,10 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
                 issue_mq(a.mq_b);
             } else {
 #pragma unroll
-                for (int g = 0; g < FRING; ++g) issue(g, g, 0);
+                for (int g = 0; g < FRING; ++g) {
+                    if (FOLD) issue_w3((g + 5) % FRING, g);
+                    else issue(g, g, 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();
@@ -487,16 +537,87 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         }
         // ---- tok2 -> its scratch (the residual of the feed-forward, read back by this same wave in the x' step), norm3 -> the
         // resident rows
+        if constexpr (!FOLD) {
 #pragma unroll
-        for (int pp = 0; pp < 2; ++pp)
+            for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
-            for (int i = 0; i < 5; ++i)
-                *reinterpret_cast<float4*>(a.tok2 + (long)(m0 + wave * 8 + pp * 4 + lq) * FC + (l15 + 16 * i) * 4) = xr[pp][i];
+                for (int i = 0; i < 5; ++i)
+                    *reinterpret_cast<float4*>(a.tok2 + (long)(m0 + wave * 8 + pp * 4 + lq) * FC + (l15 + 16 * i) * 4) = xr[pp][i];
+        } else {
+            // tok2 is not stored (a.tok2, for debugging: buffer stores that a NULL pointer turns into out-of-range ones - no branch
+            // around memory operations while the ring is in flight).  The product needs acc2, the ring and the fragments, with the
+            // rows beside them the kernel spills: the rows wait in the resident rows' LDS (free until norm3; thread-private float4s,
+            // [.][tid] so that a wave's accesses are contiguous) and their planes go through the h images, slabs 0-2 then 3-4
+            const __amdgpu_buffer_rsrc_t st2 = __builtin_amdgcn_make_buffer_rsrc(a.tok2, 0, a.tok2 ? 0x7FFFFFF0 : 0, 0x00020000);
+            float4* park = reinterpret_cast<float4*>(s_a);
+            auto planes = [&](const int pp, const int i, const int i0) {
+                const int n = (l15 + 16 * i) * 4, row = wave * 8 + pp * 4 + lq;
+                uint2 hi, lo;
+                wd_split4(xr[pp][i], hi, lo);
+                char* d = s_h + (i - i0) * SLAB + f_lds_off(row, (n & 63) >> 3) + (n & 7) * 2;
+                *reinterpret_cast<uint2*>(d) = hi;
+                *reinterpret_cast<uint2*>(d + FBM * 128) = lo;
+            };
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const int n = (l15 + 16 * i) * 4, row = wave * 8 + pp * 4 + lq;
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f_u32x4, xr[pp][i]), st2, (uint32_t)(((m0 + row) * FC + n) * 4), 0, 0);
+                    park[(pp * 5 + i) * FNT + tid] = xr[pp][i];
+                    if (i < 3) planes(pp, i, 0);
+                }
+            __syncthreads();
+            fold_product(0, 3, s_h);
+            __syncthreads();  // every fragment read of the slabs 0-2 is done: 3-4 go over them
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+                for (int i = 3; i < 5; ++i) {
+                    xr[pp][i] = park[(pp * 5 + i) * FNT + tid];
+                    planes(pp, i, 3);
+                }
+            __syncthreads();
+            fold_product(3, 5, s_h);
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+                for (int i = 0; i < 5; ++i) xr[pp][i] = park[(pp * 5 + i) * FNT + tid];
+            __syncthreads();  // every row is back in its registers: norm3 goes over them
+        }
         ln_rows(s_ln3g, s_ln3b);
     } else {
     // the first FRING groups go out before anything else (they have the whole prologue to land)
 #pragma unroll
-    for (int g = 0; g < FRING; ++g) issue(g, g, 0);
+    for (int g = 0; g < FRING; ++g) {
+        if (FOLD) issue_w3((g + 5) % FRING, g);
+        else issue(g, g, 0);
+    }
+    if constexpr (FOLD) {
+        // ---- tok2 (a.resid, fp32) -> split-bf16 planes in the resident rows, its product with W3, and only then the norm3 rows
+        const int arow = tid >> 3, ach = tid & 7;
+        const bool rok = m0 + arow < a.m;
+        const float* xrow = a.resid + (long)(rok ? m0 + arow : 0) * a.resid_ld + ach * 8;
+        float4 xv[5][2];
+#pragma unroll
+        for (int sl = 0; sl < 5; ++sl) {
+            xv[sl][0] = *reinterpret_cast<const float4*>(xrow + sl * 64);
+            xv[sl][1] = *reinterpret_cast<const float4*>(xrow + sl * 64 + 4);
+        }
+#pragma unroll
+        for (int sl = 0; sl < 5; ++sl) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            uint2 h0, l0, h1, l1;
+            wd_split4(rok ? xv[sl][0] : z, h0, l0);
+            wd_split4(rok ? xv[sl][1] : z, h1, l1);
+            char* dst = s_a + sl * SLAB + f_lds_off(arow, ach);
+            *reinterpret_cast<f_u32x4*>(dst) = f_u32x4{h0.x, h0.y, h1.x, h1.y};
+            *reinterpret_cast<f_u32x4*>(dst + FBM * 128) = f_u32x4{l0.x, l0.y, l1.x, l1.y};
+        }
+        __syncthreads();
+        fold_product(0, 5, s_a);
+        __syncthreads();  // every fragment read of the tok2 planes is done: the norm3 rows go over them
+    }
 
     // ---- the token rows: global planes -> LDS (5 slabs x 2 planes, 16-byte chunks, the GEMM stage image)
     {
@@ -518,12 +639,14 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
     }
     __syncthreads();
 
+    if constexpr (!FOLD) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int t = 0; t < 5; ++t)
+            for (int t = 0; t < 5; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc2[i][t][r] = 0.0f;
+                for (int r = 0; r < 4; ++r) acc2[i][t][r] = 0.0f;
+    }
 
     // bias of this wave's hidden units (x and gate) changes per chunk: read inside the loop
     for (int j = 0; j < nchunk; ++j) {
@@ -602,6 +725,12 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         e.bias = a.b2;
         e.resid = a.resid;
         e.resid_ld = a.resid_ld;
+        wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
+    } else if constexpr (FOLD) {
+        // the image already is tok2 W3^T + h (W3 W2)^T: + b32 = W3 b2 + b3, + x_in
+        e.bias = a.b32;
+        e.resid = a.resid3;
+        e.resid_ld = a.resid3_ld;
         wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
     } else {
         // ---- x' = image + b2 + x -> split-bf16 planes IN PLACE (a row's 320 floats = 1296 bytes with the pitch; its planes take
@@ -685,7 +814,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #endif
 }
 
-template <int NPASS, bool PROJ, bool FRONT = false>
+template <int NPASS, bool PROJ, bool FRONT = false, bool FOLD = false>
 int launch_ff(const wd_ff_args& a, hipStream_t st) {
     constexpr int max_smem = 5 * 2 * FBM * 128 + 2 * 2 * 2 * FBM * 128 + 2 * F_MAX_INNER * 4;  // token rows + two h images + b1
     constexpr int red_smem = FBM * (FC + 4) * 4 + WD_STAT_SCRATCH;
@@ -694,7 +823,7 @@ int launch_ff(const wd_ff_args& a, hipStream_t st) {
     const int smem = loop_smem > red_smem ? loop_smem : red_smem;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wd_ff_kernel<NPASS, PROJ, FRONT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wd_ff_kernel<NPASS, PROJ, FRONT, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 max_smem) != hipSuccess)
             return WD_ELAUNCH;
         attr_done = true;
@@ -704,7 +833,7 @@ int launch_ff(const wd_ff_args& a, hipStream_t st) {
     const double fl = 2.0 * (double)a.m * (3.0 * (double)a.inner * FC + (PROJ ? (double)FC * FC : 0.0) +
                                            (FRONT ? (double)FC * FC + 4.0 * a.heads * a.L * FC : 0.0));
     WdLaunchScope scope(WD_CLS_FF, st, fl);
-    hipLaunchKernelGGL((wd_ff_kernel<NPASS, PROJ, FRONT>), dim3(nb), dim3(FNT), smem, st, a);
+    hipLaunchKernelGGL((wd_ff_kernel<NPASS, PROJ, FRONT, FOLD>), dim3(nb), dim3(FNT), smem, st, a);
     return wd_check_launch();
 }
 
@@ -726,6 +855,9 @@ extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
     if (a.resid && a.resid_ld <= 0) return WD_EINVAL;
     if ((long)a.m * a.x_ld * 2 >= 0x7FFFFFF0L || (long)2 * a.inner * a.c * 2 >= 0x7FFFFFF0L) return WD_EINVAL;
     const bool proj = a.w3_hi != nullptr;
+    const bool fold = a.w32_hi != nullptr;
+    if (fold && (!proj || a.npass != 3 || !a.w32_lo || !a.b32 || (!front && !a.resid) || (long)a.m * FC * 4 >= 0x7FFFFFF0L))
+        return WD_EINVAL;
     if (proj && ((a.npass == 3 && !a.w3_lo) || (a.resid3 && (a.resid3_ld <= 0 || (a.resid3_ld & 3))))) return WD_EINVAL;
     if (a.stat_part && (a.stat_cpg <= 0 || FC % a.stat_cpg || a.hw_out <= 0 || !(a.hw_out % FBM == 0 || FBM % a.hw_out == 0) ||
                         (FBM > a.hw_out && FBM / a.hw_out > WD_STAT_MAXNS)))
@@ -735,10 +867,11 @@ extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
         if (!a.gn_part || a.gn_nchunk <= 0 || a.gn_pcpg <= 0 || a.gn_cpg <= 0 || a.gn_cpg % a.gn_pcpg || FC % a.gn_cpg ||
             !a.gn_gamma || !a.gn_beta)
             return WD_EINVAL;
-        if (!a.pi_hi || !a.pi_lo || !a.pi_b || !a.ln2_gamma || !a.ln2_beta || !a.ln3_gamma || !a.ln3_beta || !a.tok2) return WD_EINVAL;
+        if (!a.pi_hi || !a.pi_lo || !a.pi_b || !a.ln2_gamma || !a.ln2_beta || !a.ln3_gamma || !a.ln3_beta || (!a.tok2 && !fold)) return WD_EINVAL;
         if (!a.mq_a || !a.mot_a || !a.xb_a || !a.mq_b || !a.mot_b || !a.xb_b || !wd_xattn_supported(a.c, a.heads, a.L)) return WD_EINVAL;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (fold) return front ? launch_ff<3, true, true, true>(a, st) : launch_ff<3, true, false, true>(a, st);
     if (front) return launch_ff<3, true, true>(a, st);
     if (proj) return a.npass == 3 ? launch_ff<3, true>(a, st) : launch_ff<1, true>(a, st);
     return a.npass == 3 ? launch_ff<3, false>(a, st) : launch_ff<1, false>(a, st);

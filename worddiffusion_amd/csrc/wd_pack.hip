@@ -158,7 +158,40 @@ __global__ void __launch_bounds__(256) repack_multi_kernel(const PackRef* __rest
     }
 }
 
+// W32 = W3 W2 and b32 = W3 b2 + b3 of two linear layers with nothing between them (ff.net[2] then proj_out, unet.py:145,406-412):
+// one thread per element, fp64 products summed in ascending k, rounded once to fp32 - the same bits on every call.  Row c of the
+// grid is the bias.
+__global__ void __launch_bounds__(256) linear_fold_kernel(const float* __restrict__ w3, const float* __restrict__ w2,
+                                                          const float* __restrict__ b2, const float* __restrict__ b3, int c, int inner,
+                                                          int ffi, float* __restrict__ w32, float* __restrict__ b32) {
+    const int j = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
+    if (n == c) {
+        if (j >= c) return;
+        double acc = 0.0;
+        if (b2)
+            for (int k = 0; k < inner; ++k) acc += (double)w3[(int64_t)j * inner + k] * (double)b2[k];
+        if (b3) acc += (double)b3[j];
+        b32[j] = (float)acc;
+        return;
+    }
+    if (j >= ffi) return;
+    const float* row = w3 + (int64_t)n * inner;
+    double acc = 0.0;
+    for (int k = 0; k < inner; ++k) acc += (double)row[k] * (double)w2[(int64_t)k * ffi + j];
+    w32[(int64_t)n * ffi + j] = (float)acc;
+}
+
 }  // namespace
+
+extern "C" int wd_linear_fold(const float* w3, const float* w2, const float* b2, const float* b3, int c, int inner, int ffi,
+                              float* w32, float* b32, void* stream) {
+    if (!w3 || !w2 || !w32 || !b32 || c <= 0 || inner <= 0 || ffi <= 0 || c > 65534) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    const int nx = ((ffi > c ? ffi : c) + 255) / 256;
+    hipLaunchKernelGGL(linear_fold_kernel, dim3(nx, c + 1), dim3(256), 0, st, w3, w2, b2, b3, c, inner, ffi, w32, b32);
+    return wd_check_launch();
+}
 
 extern "C" int wd_repack_entry_bytes(void) { return (int)sizeof(PackRef); }
 extern "C" int wd_repack_tile(void) { return PT; }

@@ -308,7 +308,8 @@ __global__ void __launch_bounds__(256, 3) xattn16_kernel(const float* __restrict
                                                       const XaLayer lb, float eps, int heads, int L, float* __restrict__ out,
                                                       int out_ld, const float* __restrict__ gamma2,
                                                       const float* __restrict__ beta2, float eps2, wd_bf16* __restrict__ n_hi,
-                                                      wd_bf16* __restrict__ n_lo, int n_ld) {
+                                                      wd_bf16* __restrict__ n_lo, int n_ld, wd_bf16* __restrict__ r_hi,
+                                                      wd_bf16* __restrict__ r_lo, int r_ld) {
     constexpr int XT = 16, NTH = 256;
     constexpr int C = NI * 32, XP = C + 8, OP = C + 4, SP = 65, PP = 72, NT = NI / 2, KS32 = C / 32;
     static_assert(NI % 2 == 0, "column tiles per wave");
@@ -510,6 +511,16 @@ __global__ void __launch_bounds__(256, 3) xattn16_kernel(const float* __restrict
             if (ok && last) *reinterpret_cast<float4*>(out + (row0 + trow) * out_ld + n) = xr[i];
             s += (xr[i].x + xr[i].y) + (xr[i].z + xr[i].w);
         }
+        if (r_hi && last && ok) {  // the result itself as operand planes (the A operand of a product that follows)
+#pragma unroll
+            for (int i = 0; i < FI; ++i) {
+                const int n = (l15 + 16 * i) * 4;
+                uint2 hi, lo;
+                wd_split4(xr[i], hi, lo);
+                *reinterpret_cast<uint2*>(r_hi + (row0 + trow) * r_ld + n) = hi;
+                if (r_lo) *reinterpret_cast<uint2*>(r_lo + (row0 + trow) * r_ld + n) = lo;
+            }
+        }
         if (n_hi && last) {
             const float mean = wd_row16_sum(s) / (float)C;
             float q = 0.f;
@@ -543,7 +554,7 @@ __global__ void __launch_bounds__(256, 3) xattn16_kernel(const float* __restrict
 template <int NI, int NP>
 int launch16(const float* x, int ld, int batch, int hw, const XaLayer& la, const XaLayer& lb, float eps, int heads, int L,
              float* out, int out_ld, const float* gamma2, const float* beta2, float eps2, wd_bf16* n_hi, wd_bf16* n_lo, int n_ld,
-             hipStream_t st) {
+             hipStream_t st, wd_bf16* r_hi = nullptr, wd_bf16* r_lo = nullptr, int r_ld = 0) {
     constexpr int C = NI * 32, XTM = 16;
     constexpr size_t xb = (size_t)2 * XTM * (C + 8) * 2 > (size_t)XTM * (C + 4) * 4 ? (size_t)2 * XTM * (C + 8) * 2 : (size_t)XTM * (C + 4) * 4;
     constexpr size_t smem = xb + (size_t)XTM * 65 * 4 + (size_t)2 * XTM * 72 * 2 + (size_t)6 * C * 4;
@@ -554,10 +565,10 @@ int launch16(const float* x, int ld, int batch, int hw, const XaLayer& la, const
     // registers and ran 33.5 us instead of 27.8.)
     if (L == 10)
         hipLaunchKernelGGL((xattn16_kernel<NI, NP, 10>), grid, dim3(256), smem, st, x, ld, hw, la, lb, eps, heads, L, out, out_ld,
-                           gamma2, beta2, eps2, n_hi, n_lo, n_ld);
+                           gamma2, beta2, eps2, n_hi, n_lo, n_ld, r_hi, r_lo, r_ld);
     else
         hipLaunchKernelGGL((xattn16_kernel<NI, NP, 0>), grid, dim3(256), smem, st, x, ld, hw, la, lb, eps, heads, L, out, out_ld,
-                           gamma2, beta2, eps2, n_hi, n_lo, n_ld);
+                           gamma2, beta2, eps2, n_hi, n_lo, n_ld, r_hi, r_lo, r_ld);
     return wd_check_launch();
 }
 
@@ -617,18 +628,37 @@ extern "C" int wd_xattn_fused(const float* x, int ld, int batch, int hw, int c, 
     return WD_EINVAL;
 }
 
+extern "C" int wd_xattn_planes(const float* x, int ld, int batch, int hw, int c, float eps, int heads, int L, const float* gamma_a,
+                               const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a,
+                               const float* gamma_b, const float* beta_b, const wd_bf16* mq_pl_b, const wd_bf16* mot_pl_b,
+                               const float* bias_b, float* out, int out_ld, const float* gamma2, const float* beta2, float eps2,
+                               wd_bf16* n_hi, wd_bf16* n_lo, int n_ld, wd_bf16* r_hi, wd_bf16* r_lo, int r_ld, void* stream) {
+    if (!x || !out || !gamma_a || !beta_a || !mq_pl_a || !mot_pl_a || !bias_a || batch <= 0 || hw <= 0) return WD_EINVAL;
+    const bool pair = mq_pl_b != nullptr;
+    if (pair && (!gamma_b || !beta_b || !mot_pl_b || !bias_b)) return WD_EINVAL;
+    if (!wd_xattn_supported(c, heads, L) || ld % 4 || out_ld % 4 || (n_hi && (n_ld % 4 || !gamma2 || !beta2)) ||
+        (r_hi && r_ld % 4) || (r_lo && !r_hi))
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const XaLayer la = {gamma_a, beta_a, mq_pl_a, mot_pl_a, bias_a};
+    const XaLayer lb = pair ? XaLayer{gamma_b, beta_b, mq_pl_b, mot_pl_b, bias_b} : la;
+#define WD_XP(NI_, NP_) \
+    return launch16<NI_, NP_>(x, ld, batch, hw, la, lb, eps, heads, L, out, out_ld, gamma2, beta2, eps2, n_hi, n_lo, n_ld, st, r_hi, r_lo, r_ld)
+    if (c == 320) {
+        if (pair) WD_XP(10, 2);
+        WD_XP(10, 1);
+    }
+    if (pair) WD_XP(2, 2);
+    WD_XP(2, 1);
+#undef WD_XP
+}
+
 extern "C" int wd_xattn_pair(const float* x, int ld, int batch, int hw, int c, float eps, int heads, int L, const float* gamma_a,
                              const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a,
                              const float* gamma_b, const float* beta_b, const wd_bf16* mq_pl_b, const wd_bf16* mot_pl_b,
                              const float* bias_b, float* out, int out_ld, const float* gamma2, const float* beta2, float eps2,
                              wd_bf16* n_hi, wd_bf16* n_lo, int n_ld, void* stream) {
-    if (!x || !out || !gamma_a || !beta_a || !mq_pl_a || !mot_pl_a || !bias_a || !gamma_b || !beta_b || !mq_pl_b || !mot_pl_b ||
-        !bias_b || batch <= 0 || hw <= 0)
-        return WD_EINVAL;
-    if (!wd_xattn_supported(c, heads, L) || ld % 4 || out_ld % 4 || (n_hi && (n_ld % 4 || !gamma2 || !beta2))) return WD_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const XaLayer la = {gamma_a, beta_a, mq_pl_a, mot_pl_a, bias_a}, lb = {gamma_b, beta_b, mq_pl_b, mot_pl_b, bias_b};
-    if (c == 320)
-        return launch16<10, 2>(x, ld, batch, hw, la, lb, eps, heads, L, out, out_ld, gamma2, beta2, eps2, n_hi, n_lo, n_ld, st);
-    return launch16<2, 2>(x, ld, batch, hw, la, lb, eps, heads, L, out, out_ld, gamma2, beta2, eps2, n_hi, n_lo, n_ld, st);
+    if (!mq_pl_b) return WD_EINVAL;
+    return wd_xattn_planes(x, ld, batch, hw, c, eps, heads, L, gamma_a, beta_a, mq_pl_a, mot_pl_a, bias_a, gamma_b, beta_b, mq_pl_b,
+                           mot_pl_b, bias_b, out, out_ld, gamma2, beta2, eps2, n_hi, n_lo, n_ld, nullptr, nullptr, 0, stream);
 }

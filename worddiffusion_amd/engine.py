@@ -347,6 +347,8 @@ def _ptr(t: Optional[torch.Tensor], byte_off: int = 0):
 class UNetEngine:
     """Builds and runs the launch plan for one model instance."""
 
+    fold_proj = False   # (class default: _recipes() of an engine that never ran __init__ describes the parameters' own operands only)
+
     def __init__(self, model, variant: str):
         self.model = model
         self.variant = variant  # 'base' | 'phosc'
@@ -385,6 +387,9 @@ class UNetEngine:
         # the whole base-model SpatialTransformer of the 8 x 32 level (GroupNorm + proj_in, both folded cross-attentions, the
         # feed-forward, proj_out) as one wd_ff_fused launch per 64-token panel; 0: the three-launch chain
         self.fuse_st = os.environ.get("WDIFF_FUSE_ST", "1") != "0"
+        # proj_out folded into the feed-forward's second product (no non-linearity between them): W32 = W3 W2 and b32 = W3 b2 + b3
+        # are derived once per weight refresh (wd_linear_fold), the materialised x' = ff2(...) + tok2 and its launch / passes go
+        self.fold_proj = os.environ.get("WDIFF_FOLD_PROJ", "1") != "0"
         self.fuse_out = os.environ.get("WDIFF_FUSE_OUT", "1") != "0"
         self.fuse_in = os.environ.get("WDIFF_FUSE_IN", "1") != "0"         # the first convolution as one direct fp32 launch
         self.pack_kv = os.environ.get("WDIFF_PACK_KV", "1") != "0"         # long-context cross-attention: K/V images built once per call
@@ -508,6 +513,28 @@ class UNetEngine:
                         # the fused feed-forward (csrc/wd_ff.hip): x | gate rows in blocks of 16, one MFMA tile each
                         R.matrix(p + ".ff1f.w", 2 * ffi, inner).fwd(tb.ff.net[0].proj.weight, g=16)
                         R.vector(p + ".ff1f.b", tb.ff.net[0].proj.bias, g=16)
+                if self.fold_proj:
+                    # the last block's ff.net[2] and proj_out as one product: derived tensors (W32, b32), refreshed before every repack
+                    tb = mod.transformer_blocks[-1]
+                    lin, po = tb.ff.net[2], mod.proj_out
+                    ffi, dev = lin.in_features, po.weight.device
+                    key = name + ".w32"
+                    if key not in self._derived or self._derived[key][0].device != dev:
+                        w32 = torch.empty((mod.ch, ffi), dtype=torch.float32, device=dev)
+                        b32 = torch.empty((mod.ch,), dtype=torch.float32, device=dev)
+
+                        def fold(lin=lin, po=po, w32=w32, b32=b32, rows=mod.ch, k=inner, cols=ffi):
+                            st = torch.cuda.current_stream(w32.device).cuda_stream
+                            N.check(self.lib.wd_linear_fold(po.weight.data_ptr(), lin.weight.data_ptr(), _ptr(lin.bias), _ptr(po.bias),
+                                                            rows, k, cols, w32.data_ptr(), b32.data_ptr(), st), "wd_linear_fold")
+
+                        self._derived[key] = (w32, fold)          # (writes both tensors in place)
+                        self._derived[name + ".b32"] = (b32, None)
+                    w32, b32 = self._derived[key][0], self._derived[name + ".b32"][0]
+                    R.matrix(name + ".po32.w", mod.ch, ffi + inner).fwd(w32).fwd(po.weight, col_off=ffi)   # [W32 | W3]
+                    R.vector(name + ".b32", b32)
+                    if inner == mod.ch and N.lib().wd_ff_supported(inner, ffi):
+                        R.matrix(name + ".w32.w", mod.ch, ffi).fwd(w32)   # the fused kernel's image in w2's place
         self.film_total = off
         self.kv_total = kvo
         ted = m.time_embed[2].out_features
@@ -589,7 +616,9 @@ class UNetEngine:
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.no_grad():
             for buf, fn in self._derived.values():
-                buf.copy_(fn())
+                r = fn() if fn is not None else None   # (None: a native launch wrote the tensors in place)
+                if r is not None:
+                    buf.copy_(r)
         N.check(self.lib.wd_repack_multi(table.data_ptr(), n, chunks, stream), "wd_repack_multi")
         for name in wf_left:
             self._pack_wf(name, self._wf[name], stream)
@@ -1071,11 +1100,20 @@ class UNetEngine:
         xpl = None
         fuse = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))
 
-        def folded(tag, p, x_in, x_out, ln_name, next_ln=None):
+        def folded(tag, p, x_in, x_out, ln_name, next_ln=None, raw=None):
             """x_out = x_in + to_out(attention(to_q(LN(x_in)), K, V)) in one launch.  next_ln: also emit the following
-            LayerNorm as operand planes."""
+            LayerNorm as operand planes.  raw: planes that take x_out itself (wd_xattn_planes)."""
             mq, mo, mq_pl, mot_pl = self._xattn_fold(P, f"{p}.{tag}", heads, d)
             npl = self._planes(P, M, inner) if next_ln else None
+            if raw is not None:
+                ops.append((self.lib.wd_xattn_planes,
+                            (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, self._w[f"{p}.{ln_name}.g"].data_ptr(),
+                             self._w[f"{p}.{ln_name}.b"].data_ptr(), mq_pl.data_ptr(), mot_pl.data_ptr(),
+                             self._w[f"{p}.{tag}.o.b"].data_ptr(), None, None, None, None, None, x_out.data_ptr(), inner,
+                             self._w[f"{p}.{next_ln}.g"].data_ptr() if next_ln else None,
+                             self._w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5, *self._hilo(npl), inner,
+                             *self._hilo(raw), inner), f"{p}.{tag}:folded + planes"))
+                return npl
             ops.append((self.lib.wd_xattn_fused,
                         (x_in.data_ptr(), inner, B, hw, inner, self._w[f"{p}.{ln_name}.g"].data_ptr(),
                          self._w[f"{p}.{ln_name}.b"].data_ptr(), 1e-5, mq.data_ptr(), mo.data_ptr(), heads, L,
@@ -1086,27 +1124,40 @@ class UNetEngine:
                         f"{p}.{tag}:folded"))
             return npl
 
-        def folded_pair(p, x_in, x_out):
-            """Both cross-attentions of a base-model block (each behind norm2, unet.py:337-345) and norm3 in one launch."""
+        def folded_pair(p, x_in, x_out, raw=None):
+            """Both cross-attentions of a base-model block (each behind norm2, unet.py:337-345) and norm3 in one launch.  raw:
+            planes that take x_out itself (wd_xattn_planes)."""
             _, _, qa, oa = self._xattn_fold(P, p + ".a1", heads, d)
             _, _, qb, ob = self._xattn_fold(P, p + ".a2", heads, d)
             npl = self._planes(P, M, inner)
             g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
-            ops.append((self.lib.wd_xattn_pair,
-                        (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, g2, b2, qa.data_ptr(), oa.data_ptr(),
-                         self._w[f"{p}.a1.o.b"].data_ptr(), g2, b2, qb.data_ptr(), ob.data_ptr(),
-                         self._w[f"{p}.a2.o.b"].data_ptr(), x_out.data_ptr(), inner, self._w[f"{p}.norm3.g"].data_ptr(),
-                         self._w[f"{p}.norm3.b"].data_ptr(), 1e-5, *self._hilo(npl), inner), f"{p}.a1+a2:folded"))
+            args = (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, g2, b2, qa.data_ptr(), oa.data_ptr(),
+                    self._w[f"{p}.a1.o.b"].data_ptr(), g2, b2, qb.data_ptr(), ob.data_ptr(),
+                    self._w[f"{p}.a2.o.b"].data_ptr(), x_out.data_ptr(), inner, self._w[f"{p}.norm3.g"].data_ptr(),
+                    self._w[f"{p}.norm3.b"].data_ptr(), 1e-5, *self._hilo(npl), inner)
+            if raw is not None:
+                ops.append((self.lib.wd_xattn_planes, args + (*self._hilo(raw), inner), f"{p}.a1+a2:folded + planes"))
+            else:
+                ops.append((self.lib.wd_xattn_pair, args, f"{p}.a1+a2:folded"))
             return npl
 
         for di, tb in enumerate(mod.transformer_blocks):
             p = f"{name}.tb{di}"
             scale = d ** -0.5
             n3 = None
+            last = di == len(mod.transformer_blocks) - 1
+            ffi = tb.ff.net[2].in_features
+            ff_fused = self.fuse_ff and (p + ".ff1f.w") in self._w and (M + 63) // 64 >= 192
+            # the unfused tail folded (ff2 + proj_out as one two-source GEMM): it reads tok2 as operand planes, which the MFMA form
+            # of the folded cross-attention writes beside the fp32 rows
+            tok2pl = None
+            if (last and not ff_fused and self.fold_proj and self.npass == 3 and fuse and (name + ".po32.w") in self._w and
+                    not os.environ.get("WDIFF_XATTN_VALU")):
+                tok2pl = self._planes(P, M, inner)
             # ---- attn1
             if fuse and self.variant != "phosc" and self.fuse_xattn_pair:
                 tok2 = self._f32(P, M, inner)
-                n3 = folded_pair(p, tok, tok2)
+                n3 = folded_pair(p, tok, tok2, raw=tok2pl)
             tok1 = self._f32(P, M, inner) if n3 is None else None
             if n3 is not None:
                 pass
@@ -1138,7 +1189,7 @@ class UNetEngine:
                 pass
             elif fuse:
                 tok2 = self._f32(P, M, inner)
-                n3 = folded("a2", p, tok1, tok2, "norm2", next_ln="norm3")
+                n3 = folded("a2", p, tok1, tok2, "norm2", next_ln="norm3", raw=tok2pl)
             else:
                 tok2 = self._f32(P, M, inner)
                 n2 = n2_pre if (self.variant == "phosc" and n2_pre is not None) else \
@@ -1167,11 +1218,17 @@ class UNetEngine:
             # ---- GEGLU feed-forward
             if n3 is None:
                 n3 = self._ln(P, ops, p + ".norm3", tok2, M, inner, p + ".norm3")
-            last = di == len(mod.transformer_blocks) - 1
+            if tok2pl is not None:
+                ffh = self._planes(P, M, ffi)
+                self._gemm(ops, p + ".ff1", [self._src(n3, inner)], p + ".ff1.w", M, hw, bias=self._w[p + ".ff1.b"],
+                           act=N.ACT_GEGLU, out_pl=ffh, tile=geglu_tile(ffi))
+                out = self._f32(P, M, c)
+                gg = self._gemm(ops, name + ".ff2 + proj_out", [self._src(ffh, ffi), self._src(tok2pl, inner)], name + ".po32.w", M, hw,
+                                bias=self._w[name + ".b32"], resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True)
+                return Act(out, c, h, w, gg._stats, prod=gg)
             tok = self._f32(P, M, inner)
             xpl = self._planes(P, M, inner) if last else None
-            ffi = tb.ff.net[2].in_features
-            if self.fuse_ff and (p + ".ff1f.w") in self._w and (M + 63) // 64 >= 192:
+            if ff_fused:
                 # one workgroup per 64 tokens: worth it once they fill the chip (the 8 x 32 level at batch >= 48)
                 if last and self.fuse_proj and inner == c:
                     out = self._f32(P, M, c)
@@ -1200,7 +1257,8 @@ class UNetEngine:
         heads, d, L = mod.heads, mod.d_head, self._ctx_len
         p = name + ".tb0"
         folds = [self._xattn_fold(P, f"{p}.{tag}", heads, d)[2:] for tag in ("a1", "a2")]
-        tok2 = self._f32(P, M, c)
+        # (folded tail: the kernel keeps tok2 on chip - no scratch)
+        tok2 = None if self._fold_fused(name) else self._f32(P, M, c)
         out = self._f32(P, M, c)
         part, nchunk, pc = x.stats
         pw = self._wfrag(name + ".pi.w")
@@ -1211,11 +1269,15 @@ class UNetEngine:
                      mq_a=folds[0][0].data_ptr(), mot_a=folds[0][1].data_ptr(), xb_a=self._w[p + ".a1.o.b"].data_ptr(),
                      mq_b=folds[1][0].data_ptr(), mot_b=folds[1][1].data_ptr(), xb_b=self._w[p + ".a2.o.b"].data_ptr(),
                      ln3_gamma=self._w[p + ".norm3.g"].data_ptr(), ln3_beta=self._w[p + ".norm3.b"].data_ptr(), ln_eps=1e-5,
-                     heads=heads, L=L, tok2=tok2.data_ptr())
+                     heads=heads, L=L, tok2=_ptr(tok2))
         ffi = mod.transformer_blocks[0].ff.net[2].in_features
         fa = self._ff_fused(P.step, p, None, tok2, M, c, ffi, out, None, proj=(name + ".po.w", self._w[name + ".po.b"], x.t, hw),
                             front=front)
         return Act(out, c, x.h, x.w, fa._stats, prod=fa)
+
+    def _fold_fused(self, name) -> bool:
+        """Does wd_ff_fused run the proj_out tail of SpatialTransformer ``name`` folded (wd_ff_args.w32_*)?"""
+        return self.fold_proj and self.npass == 3 and (name + ".w32.w") in self._w
 
     def _wfrag(self, wname):
         """The fragment-major image (wd_gemm_pack_w) of a packed matrix, kept up to date by refresh_weights."""
@@ -1240,7 +1302,7 @@ class UNetEngine:
         w1, w2 = self._wfrag(p + ".ff1f.w"), self._wfrag(p + ".ff2.w")
         a.w1_hi, a.w1_lo, a.b1 = w1[0].data_ptr(), w1[1].data_ptr(), self._w[p + ".ff1f.b"].data_ptr()
         a.w2_hi, a.w2_lo, a.b2 = w2[0].data_ptr(), w2[1].data_ptr(), self._w[p + ".ff2.b"].data_ptr()
-        a.resid, a.resid_ld = resid.data_ptr(), inner
+        a.resid, a.resid_ld = _ptr(resid), inner
         if out_f32 is not None:
             a.out_f32, a.out_ld = out_f32.data_ptr(), inner
         if out_pl is not None:
@@ -1252,6 +1314,9 @@ class UNetEngine:
             w3 = self._wfrag(wname)
             a.w3_hi, a.w3_lo, a.b3 = w3[0].data_ptr(), w3[1].data_ptr(), b3.data_ptr()
             a.resid3, a.resid3_ld = x_in.data_ptr(), inner
+            if self._fold_fused(wname[:-len(".po.w")]):
+                w32 = self._wfrag(wname[:-len(".po.w")] + ".w32.w")
+                a.w32_hi, a.w32_lo, a.b32 = w32[0].data_ptr(), w32[1].data_ptr(), self._w[wname[:-len(".po.w")] + ".b32"].data_ptr()
             if self.fuse_stats and inner % 32 == 0 and hw % 64 == 0:
                 nchunk = hw // 64
                 part = torch.zeros((M // hw, nchunk, 32, 2), dtype=torch.float64, device=self.device)

@@ -78,6 +78,7 @@ class TrainEngine(UNetEngine):
         self.use_wdirect = os.environ.get("WDIFF_TRAIN_WDIRECT", "0") != "0"
         self.use_smallmap = os.environ.get("WDIFF_TRAIN_SMALLMAP", "1") != "0"   # (forward only; -0.085 ms per step)
         self.fuse_ff = self.fuse_proj = False
+        self.fold_proj = False       # (the backward pass differentiates ff.net[2] and proj_out as the two layers they are)
         self.use_up_phases = False   # (the backward pass differentiates the 3x3 form)
         self.fuse_gn_in = 0
         self.use_dw = os.environ.get("WDIFF_TRAIN_DW", "1") != "0"  # weight gradients through wd_dw (csrc/wd_dw.hip) where it applies
