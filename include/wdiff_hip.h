@@ -263,7 +263,7 @@ typedef struct wd_ff_args {
 } wd_ff_args;
 int wd_ff_fused(const wd_ff_args* args, void* stream);
 int wd_ff_supported(int c, int inner); /* 1 when wd_ff_fused covers the shape */
-int wd_ff_args_bytes(void);
+int wd_ff_args_bytes(void); /* sizeof(wd_ff_args) as this library was built */
 
 /* The number of K slices wd_gemm picks by itself (ksplit = 0, tile = 0) for an m x n x ktot product with a workspace of
  * ws_floats floats and no GEGLU: 1 = no cut.  (What a caller needs to know before it asks for the GroupNorm epilogue.) */
@@ -518,19 +518,26 @@ int wd_copy2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch, 
 int wd_ema_update(float* ema, const float* p, int64_t n, double beta, void* stream);
 
 /* Multi-tensor fused AdamW (+ EMA of the weights) - the optimiser side of the training step, train.py:290-294,405,146-170.
- * table: device array of ntensor records {float* p; const float* g; float* m; float* v; float* ema (or NULL);
- * int64 n; int64 chunk0} (wd_adamw_table_entry_bytes() each), chunk0 = running sum of ceil(n / wd_adamw_chunk());
+ * table: device array of ntensor wd_adamw_table_entry records, chunk0 = running sum of ceil(n / wd_adamw_chunk());
  * total_chunks = that sum over all tensors.  Same fp32 op order as torch.optim.AdamW's single-tensor update at `step`
  * (1-based).  ema_mode 0: none, 1: ema = p (the first 2000 steps of the reference), 2: ema = ema*beta + (1-beta)*p. */
-int wd_adamw_table_entry_bytes(void);
+typedef struct wd_adamw_table_entry {
+    float* p;
+    const float* g; /* NULL: the loss does not reach the parameter; AdamW skips it, the EMA still runs */
+    float* m;
+    float* v;
+    float* ema;     /* may be NULL */
+    int64_t n;
+    int64_t chunk0; /* index of this tensor's first chunk */
+} wd_adamw_table_entry;
+int wd_adamw_table_entry_bytes(void); /* sizeof(wd_adamw_table_entry) as this library was built */
 int wd_adamw_chunk(void);
 int wd_adamw_multi(const void* table, int ntensor, int64_t total_chunks, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int64_t step, int ema_mode, double ema_beta, void* stream);
 
 /* Table-driven weight repack (one launch refreshes every packed operand after an optimiser step; the reference reads
- * its parameters in place, unet.py forward).  Entry layout (wd_repack_entry_bytes() = 80 bytes, little endian):
- *   u64 src0, u64 src1 (0 = none), u64 dst_hi, u64 dst_lo, i32 N, C, T, mode, i32 npad, ld, g, ntile_c, i64 chunk0,
- *   i32 row_off, col_off (mode 3 only)
+ * its parameters in place, unet.py forward).  table: device array of nentries wd_repack_entry records (below), one per piece
+ * of a packed operand.
  * mode 0: dst[perm_g(n)][t*C + c]   = split(src0[n][c][t])   (forward operand; perm_g = GEGLU x|gate interleave, g=0 none)
  * mode 1: dst[c][t*npad + n]        = split(src0[n][c][t]), 0 for N <= n < npad   (data-gradient operand)
  * mode 2: dstf[perm_g(i)]           = src0[i] (+ src1[i]), i < N   (fp32 vectors)
@@ -538,7 +545,17 @@ int wd_adamw_multi(const void* table, int ntensor, int64_t total_chunks, double 
  *         row count (% 16 == 0), the piece sits at (row_off, col_off); needs C % 32 == 0, T in {1, 9}, even col_off
  * dst pointers are pre-offset to the piece's (row, column) origin; ld = row pitch in elements.  A mode-0/1 piece owns
  * ceil(N or npad / tile) * ceil(C / tile) chunks (tile = wd_repack_tile()), a mode-2 piece ceil(N / wd_repack_vchunk()). */
-int wd_repack_entry_bytes(void);
+typedef struct wd_repack_entry {
+    const float* src0; /* [N][C][T] (T = 9 for 3x3 kernels, 1 for linears) or a vector of N floats */
+    const float* src1; /* NULL, or a second addend (mode 2 only: conv bias + skip bias) */
+    void* dst_hi;      /* planes: the bf16 hi plane; mode 2: the fp32 destination */
+    void* dst_lo;
+    int32_t N, C, T, mode;
+    int32_t npad, ld, g, ntile_c; /* ntile_c = ceil(C / tile) */
+    int64_t chunk0;    /* index of this piece's first chunk */
+    int32_t row_off, col_off; /* mode 3 only */
+} wd_repack_entry;
+int wd_repack_entry_bytes(void); /* sizeof(wd_repack_entry) as this library was built */
 int wd_repack_tile(void);
 int wd_repack_vchunk(void);
 int wd_repack_multi(const void* table, int nentries, int64_t total_chunks, void* stream);
@@ -607,10 +624,10 @@ int wd_dw(const wd_dw_args* a, void* stream);
  * run - for a captured graph, as long as the graph).  ws: [nslice][nitems][n][ntaps][c] floats. */
 int wd_dw_group(const wd_dw_args* a, const wd_dw_item* items_host, const wd_dw_item* items_dev, int nitems, void* stream);
 int wd_dw_group_slices(int m, int n, int c, int ntaps, int nitems);
-int wd_dw_item_bytes(void);
+int wd_dw_item_bytes(void); /* sizeof(wd_dw_item) as this library was built */
 int wd_dw_supported(int m, int n, int c, int ntaps, int hw_out); /* m % 64, n % 160, c % 160, hw_out % 64 == 0, hw_out <= 1024 */
 int wd_dw_slices(int m, int n, int c, int ntaps);               /* the automatic nslice */
-int wd_dw_args_bytes(void);
+int wd_dw_args_bytes(void); /* sizeof(wd_dw_args) as this library was built */
 
 /* (bias gradients of the layers above; gradient of the FiLM vector emb_out[..., None, None], unet.py:660-661)
  * out[s][col] (+)= scale * sum over rows [s*seg, (s+1)*seg) of x[row][col]; fixed summation order.
@@ -703,11 +720,17 @@ int wd_dout_prep_geglu(const float* u, int u_ld, const float* dh, int dh_ld, int
 int wd_colsum_finish(const float* part, int nblk, int c, int nseg, float* out, int out_ld, int accumulate, float scale,
                      void* stream);
 /* The same finish for `n` (partials -> gradient) pairs in one launch (nseg = 1 each).  `table` is a device array of
- * wd_colsum_entry_bytes()-sized records {const float* part; float* out; int32 nblk, c, ld, accumulate; float scale; int32 pad}:
- * out[0..c) (+)= scale * sum over k < nblk of part[k * ld + col]; max_c = the widest entry.  Entries of one launch must write
- * distinct `out` ranges.  Used by the training backward for every bias / norm-affine gradient at once (reference: those terms
- * of loss.backward(), train.py:291). */
-int wd_colsum_entry_bytes(void);
+ * wd_colsum_entry records: out[0..c) (+)= scale * sum over k < nblk of part[k * ld + col]; max_c = the widest entry.  Entries of
+ * one launch must write distinct `out` ranges.  Used by the training backward for every bias / norm-affine gradient at once
+ * (reference: those terms of loss.backward(), train.py:291). */
+typedef struct wd_colsum_entry {
+    const float* part;
+    float* out;
+    int32_t nblk, c, ld, accumulate;
+    float scale;
+    int32_t pad;
+} wd_colsum_entry;
+int wd_colsum_entry_bytes(void); /* sizeof(wd_colsum_entry) as this library was built */
 int wd_colsum_finish_multi(const void* table, int n, int max_c, void* stream);
 
 /* Attention backward (CrossAttention.forward unetPhosc.py:157-198, Word_Attention :696-708) for any number of keys <= 1024

@@ -1,4 +1,6 @@
-"""ctypes binding of libwdiff_hip.so (include/wdiff_hip.h).
+"""ctypes binding of libwdiff_hip.so, derived at import from its public header (include/wdiff_hip.h): the Structure classes,
+the argument types of every function and the WD_* constants are parsed from the header, so there is no second copy to keep in
+step with it.
 
 The product path has no CPU or eager-PyTorch fallback: if the shared library is missing or a symbol is
 absent, importing/using it raises.
@@ -13,186 +15,101 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WDIFF_LIB") or os.path.join(_HERE, "libwdiff_hip.so")  # (WDIFF_LIB: A/B builds of the kernels)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "wdiff_hip.h")
 
-WD_OK, WD_EINVAL, WD_ELAUNCH, WD_ESTATE = 0, -1, -2, -3
-ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
-VAE_MAX_LATENT, STREAM_VAE_POSTERIOR = 8, 3  # WD_VAE_MAX_LATENT, WD_STREAM_VAE_POSTERIOR of the header
-NCLASS = 13
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "uint16_t": C.c_uint16, "float": C.c_float, "double": C.c_double, "char": C.c_char}
+_DECL = re.compile(r"(?:const\s+)?(\w+)(?:\s*(\*+)\s*|\s+)(\w+)((?:\s*,\s*\w+)*)\s*(?:\[(\d+)\])?")
+_ITEMS = [re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;\s*"),  # struct: (body, name)
+          re.compile(r"typedef\s+(\w+)\s+(\w+)\s*;\s*"),                        # alias: (known type, name)
+          re.compile(r"([^;{}()]+)\(([^()]*)\)\s*;\s*")]                          # prototype: (result and name, parameters)
+
+
+def parse_header(text: str):
+    """The C subset include/wdiff_hip.h is written in -> (structs, prototypes, defines):
+    structs     {C name: ctypes.Structure subclass} for every ``typedef struct [tag] { ... } name;``
+    prototypes  {function: (restype, [(parameter name, ctype), ...])}
+    defines     {name: value} for every integer ``#define WD_*``
+    A pointer is c_void_p (callers pass ``tensor.data_ptr()`` or None), except ``char*`` (c_char_p) and, for a parameter, a
+    pointer to a struct of the header (POINTER of its class).  Anything outside that subset raises ValueError: a header edit the
+    binding would mistype must fail at import, not in a kernel."""
+    types = dict(_SCALARS)
+    structs, protos, defines, code = {}, {}, {}, []
+    for line in re.sub(r"/\*.*?\*/", " ", text, flags=re.S).splitlines():
+        d = line.strip()
+        m = re.fullmatch(r"#\s*define\s+(WD_\w+)\s+\(?\s*(-?(?:0[xX][0-9a-fA-F]+|\d+))\s*\)?", d)
+        if m:
+            defines[m[1]] = int(m[2], 0)
+        elif not d.startswith("#"):
+            code.append(line)
+        elif not re.fullmatch(r"#\s*(ifn?def\s+\w+|endif|include\s*<\w+\.h>|define\s+(?!WD_)\w+)", d):
+            raise ValueError(f"preprocessor line outside the header's grammar: {d!r}")
+    code, wrapped = re.subn(r'extern\s+"C"\s*\{', "", "\n".join(code))
+    code = code.strip()
+    if wrapped:
+        if not code.endswith("}"):
+            raise ValueError('extern "C" { is not closed at the end of the header')
+        code = code[:-1].rstrip()
+
+    def decl(text, param):
+        """``[const] type[*..] name[, name..][[n]]`` -> [(name, ctype), ...]"""
+        m = _DECL.fullmatch(text.strip())
+        if not m or (m[1] not in types and not (m[1] == "void" and m[2])):
+            raise ValueError(f"declaration outside the header's grammar: {text.strip()!r}")
+        base, stars, names = types.get(m[1]), m[2] or "", [m[3]] + re.findall(r"\w+", m[4])
+        if not stars:
+            t = base
+        elif base is C.c_char and stars == "*":
+            t = C.c_char_p
+        elif param and stars == "*" and m[1] in structs:
+            t = C.POINTER(base)
+        else:
+            t = C.c_void_p
+        return [(n, t * int(m[5]) if m[5] else t) for n in names]
+
+    pos = 0
+    while pos < len(code):
+        hit = next(((i, m) for i, m in enumerate(r.match(code, pos) for r in _ITEMS) if m), None)
+        if hit is None:
+            raise ValueError(f"declaration outside the header's grammar: {code[pos:pos + 80]!r}")
+        kind, m = hit
+        if kind == 0:
+            fields = [f for part in m[1].split(";") if part.strip() for f in decl(part, False)]
+            cls = type("".join(w.capitalize() for w in m[2].split("_")), (C.Structure,), {"_fields_": fields})
+            types[m[2]] = structs[m[2]] = cls
+        elif kind == 1:
+            types[m[2]] = decl(f"{m[1]} {m[2]}", False)[0][1]
+        else:
+            params = [] if m[2].strip() == "void" else [decl(part, True)[0] for part in m[2].split(",")]
+            (name, res), = decl(m[1], True)
+            protos[name] = (res, params)
+        pos = m.end()
+    return structs, protos, defines
+
+
+with open(HEADER_PATH) as _f:
+    STRUCTS, _PROTOS, DEFINES = parse_header(_f.read())
+
+WdSrc, WdGemmArgs, WdFfArgs, WdDwArgs, WdDwItem, WdDropout, WdRepackEntry, WdAdamwTableEntry, WdColsumEntry = (
+    STRUCTS[n] for n in ("wd_src", "wd_gemm_args", "wd_ff_args", "wd_dw_args", "wd_dw_item", "wd_dropout", "wd_repack_entry",
+                         "wd_adamw_table_entry", "wd_colsum_entry"))
+WD_OK, WD_EINVAL, WD_ELAUNCH, WD_ESTATE = (DEFINES[n] for n in ("WD_OK", "WD_EINVAL", "WD_ELAUNCH", "WD_ESTATE"))
+ACT_NONE, ACT_SILU, ACT_GEGLU = (DEFINES[n] for n in ("WD_ACT_NONE", "WD_ACT_SILU", "WD_ACT_GEGLU"))
+VAE_MAX_LATENT, STREAM_VAE_POSTERIOR, STREAM_DROPOUT0, NCLASS = (
+    DEFINES[n] for n in ("WD_VAE_MAX_LATENT", "WD_STREAM_VAE_POSTERIOR", "WD_STREAM_DROPOUT0", "WD_NCLASS"))
 CLASS_NAMES = ("gemm", "gn_stats", "gn_apply", "layernorm", "attention", "other", "gemm_other_tiles", "gemm_splitk_reduce",
                "gemm_two_per_cu", "gemm_weights_to_registers", "feed_forward_fused", "weight_gradient", "gemm_small_maps_whole_k")
+assert len(CLASS_NAMES) == NCLASS, "CLASS_NAMES must name every profiling class of the header (WD_NCLASS)"
 
-_vp = C.c_void_p
-_i = C.c_int
-_f = C.c_float
-_u64 = C.c_uint64
-
-
-class WdSrc(C.Structure):
-    _fields_ = [("hi", _vp), ("lo", _vp), ("gather", _vp), ("ld", C.c_int32), ("c", C.c_int32),
-                ("ntaps", C.c_int32), ("hw_src", C.c_int32)]
-
-
-class WdGemmArgs(C.Structure):
-    _fields_ = [("src", WdSrc * 2), ("nsrc", C.c_int32), ("npass", C.c_int32), ("w_hi", _vp), ("w_lo", _vp),
-                ("m", C.c_int32), ("n", C.c_int32), ("ktot", C.c_int32), ("hw_out", C.c_int32),
-                ("bias", _vp), ("rowvec", _vp), ("rowvec_ld", C.c_int32), ("resid", _vp), ("resid_ld", C.c_int32),
-                ("resid_rows", _vp), ("act", C.c_int32), ("out_f32", _vp), ("out_ld", C.c_int32),
-                ("out_hi", _vp), ("out_lo", _vp), ("out_pl_ld", C.c_int32), ("tile", C.c_int32),
-                ("w_layout", C.c_int32), ("slab_rows", C.c_int32), ("ksplit", C.c_int32), ("ws", _vp),
-                ("ws_floats", C.c_int64), ("stat_part", _vp), ("stat_cpg", C.c_int32), ("dbg", C.c_int32),
-                ("tickets", _vp), ("ntickets", C.c_int32), ("gn_gamma", _vp), ("gn_beta", _vp), ("gn_eps", C.c_float),
-                ("gn_silu", C.c_int32), ("gn_cpg", C.c_int32), ("a32", _vp), ("a32_ld", C.c_int32), ("a32_part", _vp),
-                ("a32_nchunk", C.c_int32), ("a32_pcpg", C.c_int32), ("a32_cpg", C.c_int32), ("a32_gamma", _vp), ("a32_beta", _vp),
-                ("a32_eps", C.c_float), ("a32_silu", C.c_int32), ("ln_gamma", _vp), ("ln_beta", _vp), ("ln_eps", C.c_float),
-                ("w_ngroups", C.c_int32), ("w_group_stride", C.c_int64)]
-
-
-class WdFfArgs(C.Structure):
-    _fields_ = [("x_hi", _vp), ("x_lo", _vp), ("x_ld", C.c_int32), ("m", C.c_int32), ("c", C.c_int32), ("inner", C.c_int32),
-                ("w1_hi", _vp), ("w1_lo", _vp), ("b1", _vp), ("w2_hi", _vp), ("w2_lo", _vp), ("b2", _vp), ("resid", _vp),
-                ("resid_ld", C.c_int32), ("out_f32", _vp), ("out_ld", C.c_int32), ("out_hi", _vp), ("out_lo", _vp),
-                ("out_pl_ld", C.c_int32), ("w3_hi", _vp), ("w3_lo", _vp), ("b3", _vp), ("resid3", _vp), ("resid3_ld", C.c_int32),
-                ("stat_part", _vp), ("stat_cpg", C.c_int32), ("hw_out", C.c_int32), ("npass", C.c_int32),
-                ("x_in", _vp), ("x_in_ld", C.c_int32), ("hw", C.c_int32), ("gn_part", _vp), ("gn_nchunk", C.c_int32),
-                ("gn_pcpg", C.c_int32), ("gn_cpg", C.c_int32), ("gn_eps", C.c_float), ("gn_gamma", _vp), ("gn_beta", _vp),
-                ("pi_hi", _vp), ("pi_lo", _vp), ("pi_b", _vp), ("ln2_gamma", _vp), ("ln2_beta", _vp), ("mq_a", _vp), ("mot_a", _vp),
-                ("xb_a", _vp), ("mq_b", _vp), ("mot_b", _vp), ("xb_b", _vp), ("ln3_gamma", _vp), ("ln3_beta", _vp),
-                ("ln_eps", C.c_float), ("heads", C.c_int32), ("L", C.c_int32), ("tok2", _vp),
-                ("w32_hi", _vp), ("w32_lo", _vp), ("b32", _vp)]
-
-
-class WdDwArgs(C.Structure):
-    _fields_ = [("d_hi", _vp), ("d_lo", _vp), ("x_hi", _vp), ("x_lo", _vp), ("gather", _vp), ("grad", _vp), ("ws", _vp),
-                ("ws_floats", C.c_int64), ("d_ld", C.c_int32), ("x_ld", C.c_int32), ("grad_ld", C.c_int32), ("ntaps", C.c_int32),
-                ("hw_out", C.c_int32), ("hw_src", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("c", C.c_int32),
-                ("npass", C.c_int32), ("accumulate", C.c_int32), ("nslice", C.c_int32), ("dbg", C.c_int32), ("reserved", C.c_int32),
-                ("stamps", _vp), ("items", _vp), ("nitems", C.c_int32), ("reserved2", C.c_int32)]
-
-
-class WdDwItem(C.Structure):
-    _fields_ = [("d_hi", _vp), ("d_lo", _vp), ("x_hi", _vp), ("x_lo", _vp), ("grad", _vp), ("d_ld", C.c_int32), ("x_ld", C.c_int32),
-                ("grad_ld", C.c_int32), ("accumulate", C.c_int32)]
-
-
-_SIGS = {
-    "wd_gemm": (_i, [C.POINTER(WdGemmArgs), _vp]),
-    "wd_gemm_check": (_i, [C.POINTER(WdGemmArgs), C.POINTER(WdGemmArgs)]),
-    "wd_gemm_check_kernel": (C.c_char_p, [C.POINTER(WdGemmArgs)]),
-    "wd_dw": (_i, [C.POINTER(WdDwArgs), _vp]),
-    "wd_dw_supported": (_i, [_i, _i, _i, _i, _i]),
-    "wd_dw_slices": (_i, [_i, _i, _i, _i]),
-    "wd_dw_args_bytes": (_i, []),
-    "wd_dw_group": (_i, [C.POINTER(WdDwArgs), _vp, _vp, _i, _vp]),
-    "wd_dw_group_slices": (_i, [_i, _i, _i, _i, _i]),
-    "wd_dw_item_bytes": (_i, []),
-    "wd_gemm_auto_ksplit": (_i, [_i, _i, _i, C.c_int64]),
-    "wd_gemm_pack_w": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "wd_ff_fused": (_i, [C.POINTER(WdFfArgs), _vp]),
-    "wd_ff_supported": (_i, [_i, _i]),
-    "wd_ff_args_bytes": (_i, []),
-    "wd_gemm_args_bytes": (_i, []),
-    "wd_gemm_experimental": (_i, []),
-    "wd_gn_nchunk": (_i, [_i]),
-    "wd_gn_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "wd_gn_fold_chunks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "wd_gn_conv3x3_few_supported": (_i, [_i, _i, _i]),
-    "wd_gn_conv3x3_few": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _vp, _vp]),
-    "wd_gn_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "wd_gn_apply_dropout": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "wd_gn_apply2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _i, _vp,
-                          _vp, _vp, _vp]),
-    "wd_layernorm": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp]),
-    "wd_split": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "wd_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "wd_attention_packed_elems": (C.c_int64, [_i, _i, _i, _i]),
-    "wd_attention_pack_kv": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "wd_attention_packed": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "wd_timestep_embedding": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
-    "wd_embed_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
-    "wd_im2col3x3": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "wd_conv3x3_in_supported": (_i, [_i, _i, _i, _i]),
-    "wd_conv3x3_in_nchunk": (_i, [_i]),
-    "wd_conv3x3_in": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
-    "wd_nchw_to_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
-    "wd_tokens_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "wd_ddpm_step": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
-    "wd_advance_timestep": (_i, [_vp, _i, _vp, _i, _vp]),
-    "wd_randn": (_i, [_vp, _i, _i, _u64, _u64, C.c_uint32, _vp]),
-    "wd_vae_posterior": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _u64, _u64, _vp]),
-    "wd_posterior_sample": (_i, [_vp, _vp, _i, _i, _vp, _f, _vp, _u64, _u64, _vp]),
-    "wd_noise_images": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "wd_copy2d": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _vp]),
-    "wd_ema_update": (_i, [_vp, _vp, C.c_int64, C.c_double, _vp]),
-    "wd_adamw_table_entry_bytes": (_i, []),
-    "wd_adamw_chunk": (_i, []),
-    "wd_adamw_multi": (_i, [_vp, _i, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _i,
-                           C.c_double, _vp]),
-    "wd_mse_loss": (_i, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _vp]),
-    "wd_transpose_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "wd_repack_entry_bytes": (_i, []),
-    "wd_repack_tile": (_i, []),
-    "wd_repack_vchunk": (_i, []),
-    "wd_repack_multi": (_i, [_vp, _i, C.c_int64, _vp]),
-    "wd_attention_bwd_scratch_floats": (C.c_int64, [_i, _i, _i, _i]),
-    "wd_attention_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp]),
-    "wd_xattn_supported": (_i, [_i, _i, _i]),
-    "wd_xattn_fold": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "wd_xattn_fused": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp]),
-    "wd_dout_prep_rows": (_i, []),
-    "wd_dout_prep": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "wd_dout_prep_geglu": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "wd_colsum_finish": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, _vp]),
-    "wd_colsum_entry_bytes": (_i, []),
-    "wd_colsum_finish_multi": (_i, [_vp, _i, _i, _vp]),
-    "wd_emb_combine": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "wd_select_rows": (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),
-    "wd_emb_combine_mix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "wd_label_mix": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "wd_ddpm_step_cfg": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
-    "wd_ddim_step": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
-    "wd_next_timestep": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "wd_xattn_pair": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f,
-                           _vp, _vp, _i, _vp]),
-    "wd_xattn_planes": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f,
-                             _vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "wd_linear_fold": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "wd_add": (_i, [_vp, _vp, C.c_int64, _vp]),
-    "wd_permute_dw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "wd_colsum": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, C.c_int64, _vp]),
-    "wd_gn_bwd_nchunk": (_i, [_i]),
-    "wd_gn_bwd_stats": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp]),
-    "wd_gn_bwd_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp]),
-    "wd_gn_bwd_fused_supported": (_i, [_i, _i, _i]),
-    "wd_gn_bwd_fused": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp]),
-    "wd_gn_bwd_stats_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp]),
-    "wd_gn_bwd_apply_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "wd_gn_bwd_fused_dropout": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "wd_layernorm_bwd_nblk": (_i, [_i]),
-    "wd_layernorm_bwd": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _f, _vp, _i, _i, _vp, _vp]),
-    "wd_attention_bwd_small_nwg": (_i, [_i, _i, _i, _i]),
-    "wd_attention_bwd_small": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp,
-                                   C.POINTER(_i), _vp]),
-    "wd_geglu_fwd": (_i, [_vp, _i, C.c_int64, _i, _vp, _vp, _i, _vp]),
-    "wd_geglu_bwd": (_i, [_vp, _i, _vp, _i, C.c_int64, _i, _vp, _i, _vp]),
-    "wd_silu_bwd": (_i, [_vp, _vp, C.c_int64, _vp, _vp]),
-    "wd_pool2x2_sum": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "wd_embedding_bwd": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "wd_graph_begin": (_i, [_vp]),
-    "wd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
-    "wd_graph_launch": (_i, [_vp, _vp]),
-    "wd_graph_destroy": (_i, [_vp]),
-    "wd_prof_enable": (_i, [_i]),
-    "wd_prof_collect": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
-    "wd_prof_collect_flops": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
-    "wd_version": (C.c_char_p, []),
-    "wd_device_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.c_char_p, _i]),
-}
+# Struct-pointer parameters the callers pass as a raw address rather than byref(): the item records of wd_dw_group live in a
+# ctypes array on the host and in a tensor on the device.
+_RAW_ADDRESS = {"wd_dw_group": ("items_host", "items_dev")}
+assert all(p in dict(_PROTOS[f][1]) for f, ps in _RAW_ADDRESS.items() for p in ps)
+_SIGS = {f: (res, [C.c_void_p if p in _RAW_ADDRESS.get(f, ()) else t for p, t in params])
+         for f, (res, params) in _PROTOS.items()}
 
 
 def header_symbols() -> list:
     """Every function the public header declares (used by the CPU test that the .so exports them all)."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(wd_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(_PROTOS)
 
 
 class NativeError(RuntimeError):
@@ -215,18 +132,10 @@ def lib() -> C.CDLL:
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    if l.wd_gemm_args_bytes() != C.sizeof(WdGemmArgs):  # a stale library beside newer Python (or the reverse)
-        raise NativeError(f"{LIB_PATH}: wd_gemm_args is {l.wd_gemm_args_bytes()} bytes in the library, {C.sizeof(WdGemmArgs)} in "
-                          "worddiffusion_amd/_native.py - rebuild with `python -m worddiffusion_amd.build`")
-    if l.wd_ff_args_bytes() != C.sizeof(WdFfArgs):
-        raise NativeError(f"{LIB_PATH}: wd_ff_args is {l.wd_ff_args_bytes()} bytes in the library, {C.sizeof(WdFfArgs)} in "
-                          "worddiffusion_amd/_native.py - rebuild with `python -m worddiffusion_amd.build`")
-    if l.wd_dw_item_bytes() != C.sizeof(WdDwItem):
-        raise NativeError(f"{LIB_PATH}: wd_dw_item is {l.wd_dw_item_bytes()} bytes in the library, {C.sizeof(WdDwItem)} in "
-                          "worddiffusion_amd/_native.py - rebuild with `python -m worddiffusion_amd.build`")
-    if l.wd_dw_args_bytes() != C.sizeof(WdDwArgs):
-        raise NativeError(f"{LIB_PATH}: wd_dw_args is {l.wd_dw_args_bytes()} bytes in the library, {C.sizeof(WdDwArgs)} in "
-                          "worddiffusion_amd/_native.py - rebuild with `python -m worddiffusion_amd.build`")
+    for cname, cls in STRUCTS.items():  # a stale library beside a newer header (or the reverse)
+        if cname + "_bytes" in _SIGS and getattr(l, cname + "_bytes")() != C.sizeof(cls):
+            raise NativeError(f"{LIB_PATH}: {cname} is {getattr(l, cname + '_bytes')()} bytes in the library, {C.sizeof(cls)} in "
+                              "worddiffusion_amd/_native.py - rebuild with `python -m worddiffusion_amd.build`")
     _lib = l
     return l
 

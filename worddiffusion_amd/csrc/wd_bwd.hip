@@ -241,16 +241,9 @@ __global__ void __launch_bounds__(256) colsum_stage2(const float* __restrict__ p
 // The same finish for a whole list of (partial sums -> parameter gradient) pairs in one launch: grid (column tiles of the widest
 // entry, entries).  The training backward defers its bias-gradient finishes to one of these at its end (they are launch-bound:
 // ~45 launches of a few microseconds each otherwise).
-struct ColRef {
-    const float* part;
-    float* out;
-    int32_t nblk, c, ld, accumulate;
-    float scale;
-    int32_t pad;
-};
-__global__ void __launch_bounds__(256) colsum_multi_kernel(const ColRef* __restrict__ tab) {
+__global__ void __launch_bounds__(256) colsum_multi_kernel(const wd_colsum_entry* __restrict__ tab) {
     __shared__ double red[16][17];
-    const ColRef e = tab[blockIdx.y];
+    const wd_colsum_entry e = tab[blockIdx.y];
     if ((int)blockIdx.x * 16 >= e.c) return;
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
     const int col = blockIdx.x * 16 + cl;
@@ -1551,12 +1544,12 @@ extern "C" int wd_colsum_finish(const float* part, int nblk, int c, int nseg, fl
     return wd_check_launch();
 }
 
-extern "C" int wd_colsum_entry_bytes() { return (int)sizeof(ColRef); }
+extern "C" int wd_colsum_entry_bytes() { return (int)sizeof(wd_colsum_entry); }
 
 extern "C" int wd_colsum_finish_multi(const void* table, int n, int max_c, void* stream) {
     if (!table || n <= 0 || max_c <= 0) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
-    hipLaunchKernelGGL(colsum_multi_kernel, dim3((max_c + 15) / 16, n), dim3(256), 0, st, reinterpret_cast<const ColRef*>(table));
+    hipLaunchKernelGGL(colsum_multi_kernel, dim3((max_c + 15) / 16, n), dim3(256), 0, st, reinterpret_cast<const wd_colsum_entry*>(table));
     return wd_check_launch();
 }

@@ -7,17 +7,6 @@
 
 namespace {
 
-struct PackRef {        // one piece of one packed operand; built once by the host (engine.py)
-    const float* src0;  // [N][C][T] (T = 9 for 3x3 kernels, 1 for linears) or a vector of N floats
-    const float* src1;  // optional second addend (vectors only: conv bias + skip bias)
-    void* dst_hi;       // planes: bf16 hi plane, already offset to (row_off, col_off); vectors: fp32 destination
-    void* dst_lo;
-    int32_t N, C, T, mode;     // mode 0: forward planes, 1: data-gradient planes, 2: fp32 vector, 3: forward planes, fragment-major
-    int32_t npad, ld, g, ntile_c;
-    int64_t chunk0;     // index of this piece's first chunk (tile)
-    int32_t row_off, col_off;  // mode 3 only (dst_hi / dst_lo are the image's base there, ld = the matrix's row count)
-};
-
 constexpr int PT = 32;          // tile: 32 output channels x 32 input channels x T taps
 constexpr int VCHUNK = 8192;    // vector elements per workgroup
 
@@ -31,7 +20,7 @@ __device__ __forceinline__ int geglu_perm(int n, int N, int g) {
 }
 
 template <int T>
-__device__ __forceinline__ void repack_full_tile(const PackRef& e, float* s, const int n0, const int c0, const int tid) {
+__device__ __forceinline__ void repack_full_tile(const wd_repack_entry& e, float* s, const int n0, const int c0, const int tid) {
     constexpr int ROW = PT * T + 1;
     const int C = e.C, N = e.N;
     // load: for each output channel the (c, t) block of PT * T floats is contiguous in the OIHW source
@@ -88,7 +77,7 @@ __device__ __forceinline__ void repack_full_tile(const PackRef& e, float* s, con
     }
 }
 
-__global__ void __launch_bounds__(256) repack_multi_kernel(const PackRef* __restrict__ tab, int nentries) {
+__global__ void __launch_bounds__(256) repack_multi_kernel(const wd_repack_entry* __restrict__ tab, int nentries) {
     __shared__ float s[PT * (PT * 9 + 1)];
     int lo = 0, hi = nentries - 1;
     const int64_t ch = blockIdx.x;
@@ -97,7 +86,7 @@ __global__ void __launch_bounds__(256) repack_multi_kernel(const PackRef* __rest
         if (tab[mid].chunk0 <= ch) lo = mid;
         else hi = mid - 1;
     }
-    const PackRef e = tab[lo];
+    const wd_repack_entry e = tab[lo];
     const int64_t lc = ch - e.chunk0;
     const int tid = threadIdx.x;
     if (e.mode == 2) {
@@ -193,7 +182,7 @@ extern "C" int wd_linear_fold(const float* w3, const float* w2, const float* b2,
     return wd_check_launch();
 }
 
-extern "C" int wd_repack_entry_bytes(void) { return (int)sizeof(PackRef); }
+extern "C" int wd_repack_entry_bytes(void) { return (int)sizeof(wd_repack_entry); }
 extern "C" int wd_repack_tile(void) { return PT; }
 extern "C" int wd_repack_vchunk(void) { return VCHUNK; }
 
@@ -202,6 +191,6 @@ extern "C" int wd_repack_multi(const void* table, int nentries, int64_t total_ch
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(repack_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, st,
-                       reinterpret_cast<const PackRef*>(table), nentries);
+                       reinterpret_cast<const wd_repack_entry*>(table), nentries);
     return wd_check_launch();
 }

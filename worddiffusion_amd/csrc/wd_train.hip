@@ -9,19 +9,9 @@
 
 namespace {
 
-struct TensorRef {  // one entry of the device-side parameter table (built once by the host)
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    float* ema;        // may be NULL
-    int64_t n;
-    int64_t chunk0;    // index of this tensor's first chunk
-};
-
 constexpr int CHUNK = 8192;  // elements per workgroup
 
-__global__ void adamw_multi_kernel(const TensorRef* __restrict__ tab, int ntensor, float decay, float omb1, float b2,
+__global__ void adamw_multi_kernel(const wd_adamw_table_entry* __restrict__ tab, int ntensor, float decay, float omb1, float b2,
                                    float omb2, float step_size, float bc2_sqrt, float eps, int ema_mode, float ema_b,
                                    float ema_omb) {
     // binary search: which tensor owns chunk blockIdx.x
@@ -32,7 +22,7 @@ __global__ void adamw_multi_kernel(const TensorRef* __restrict__ tab, int ntenso
         if (tab[mid].chunk0 <= c) lo = mid;
         else hi = mid - 1;
     }
-    const TensorRef t = tab[lo];
+    const wd_adamw_table_entry t = tab[lo];
     const int64_t base = (c - t.chunk0) * CHUNK;
     const int64_t end = base + CHUNK < t.n ? base + CHUNK : t.n;
     if (!t.g) {
@@ -89,7 +79,7 @@ __global__ void mse_stage2(const double* __restrict__ partial, int nb, int64_t n
 
 }  // namespace
 
-extern "C" int wd_adamw_table_entry_bytes(void) { return (int)sizeof(TensorRef); }
+extern "C" int wd_adamw_table_entry_bytes(void) { return (int)sizeof(wd_adamw_table_entry); }
 extern "C" int wd_adamw_chunk(void) { return CHUNK; }
 
 extern "C" int wd_adamw_multi(const void* table, int ntensor, int64_t total_chunks, double lr, double beta1, double beta2,
@@ -102,7 +92,7 @@ extern "C" int wd_adamw_multi(const void* table, int ntensor, int64_t total_chun
                 omb2 = (float)(1.0 - beta2), step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, st,
-                       reinterpret_cast<const TensorRef*>(table), ntensor, decay, omb1, b2, omb2, step_size, bc2_sqrt,
+                       reinterpret_cast<const wd_adamw_table_entry*>(table), ntensor, decay, omb1, b2, omb2, step_size, bc2_sqrt,
                        (float)eps, ema_mode, (float)ema_beta, (float)(1.0 - ema_beta));
     return wd_check_launch();
 }

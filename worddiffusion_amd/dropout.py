@@ -10,19 +10,13 @@ One Philox4x32-10 draw covers four consecutive elements of a sample's token-majo
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict
 
 import numpy as np
 
-STREAM_DROPOUT0 = 0x100  # WD_STREAM_DROPOUT0 of include/wdiff_hip.h
+from ._native import STREAM_DROPOUT0, WdDropout  # noqa: F401  (wd_dropout and WD_STREAM_DROPOUT0 of include/wdiff_hip.h)
+
 _KEY = "out_layers.3.weight"
-
-
-class WdDropout(C.Structure):
-    """``wd_dropout`` of include/wdiff_hip.h."""
-    _fields_ = [("seed", C.c_uint64), ("row_base", C.c_uint64), ("row_base_dev", C.c_void_p), ("tag", C.c_uint32),
-                ("thr", C.c_uint32), ("scale", C.c_float)]
 
 
 def check_p(p: float) -> float:

@@ -263,8 +263,6 @@ class RecipeBook(dict):
     def device_table(self, lib, dst: Dict[str, torch.Tensor], dev, frag: Optional[Dict[str, torch.Tensor]] = None):
         """Serialises the pieces into the entry table of ``wd_repack_multi`` (include/wdiff_hip.h).  ``frag``: name -> the
         fragment-major image to write as well (mode 3) for the matrices ``frag_ok`` accepts."""
-        import struct
-        assert lib.wd_repack_entry_bytes() == 80
         tile, vchunk = lib.wd_repack_tile(), lib.wd_repack_vchunk()
         recs, c0 = [], 0
         for name, r in self.items():
@@ -280,15 +278,15 @@ class RecipeBook(dict):
                     hi, lo = d[0].data_ptr() + o, d[1].data_ptr() + o
                     ntc = (c + tile - 1) // tile
                     nch = (((npad if mode == 1 else n) + tile - 1) // tile) * ntc
-                recs.append(struct.pack("<QQQQiiiiiiiiqii", p.data_ptr(), p2.data_ptr() if p2 is not None else 0, hi, lo, n, c, t,
-                                        mode, npad, ld, g, ntc, c0, 0, 0))
+                recs.append(N.WdRepackEntry(p.data_ptr(), p2.data_ptr() if p2 is not None else 0, hi, lo, n, c, t,
+                                            mode, npad, ld, g, ntc, c0, 0, 0))
                 c0 += nch
                 if frag is not None and name in frag and self.frag_ok(r):
                     f = frag[name]
-                    recs.append(struct.pack("<QQQQiiiiiiiiqii", p.data_ptr(), 0, f[0].data_ptr(), f[1].data_ptr(), n, c, t, 3, 0,
-                                            r.rows, g, ntc, c0, row_off, col_off))
+                    recs.append(N.WdRepackEntry(p.data_ptr(), 0, f[0].data_ptr(), f[1].data_ptr(), n, c, t, 3, 0,
+                                                r.rows, g, ntc, c0, row_off, col_off))
                     c0 += nch
-        raw = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(dev)
+        raw = torch.frombuffer((N.WdRepackEntry * len(recs))(*recs), dtype=torch.uint8).to(dev)
         return raw, c0, len(recs)
 
 

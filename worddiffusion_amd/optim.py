@@ -4,7 +4,6 @@ launch updates every parameter (and the EMA copy) instead of the reference's ~26
 the next row of the plan."""
 from __future__ import annotations
 
-import struct
 from typing import Optional
 
 import torch
@@ -114,17 +113,16 @@ class FusedAdamW:
     def _build_table(self):
         lib = N.lib()
         chunk = lib.wd_adamw_chunk()
-        assert lib.wd_adamw_table_entry_bytes() == 56
         recs, c0 = [], 0
         self._grads = []
         for i, p in enumerate(self.params):
             g = p.grad.contiguous() if p.grad is not None else None  # None: torch.optim.AdamW skips the parameter
             self._grads.append(g)
             ema = self.ema_params[i].data_ptr() if self.ema_params is not None else 0
-            recs.append(struct.pack("<QQQQQqq", p.data_ptr(), g.data_ptr() if g is not None else 0, self.exp_avg[i].data_ptr(),
-                                    self.exp_avg_sq[i].data_ptr(), ema, p.numel(), c0))
+            recs.append(N.WdAdamwTableEntry(p.data_ptr(), g.data_ptr() if g is not None else 0, self.exp_avg[i].data_ptr(),
+                                            self.exp_avg_sq[i].data_ptr(), ema, p.numel(), c0))
             c0 += (p.numel() + chunk - 1) // chunk
-        raw = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
+        raw = torch.frombuffer((N.WdAdamwTableEntry * len(recs))(*recs), dtype=torch.uint8)
         self._table = raw.to(self.params[0].device)
         self._chunks = c0
         self._grad_ptrs = [g.data_ptr() if g is not None else 0 for g in self._grads]

@@ -245,14 +245,10 @@ class TrainEngine(UNetEngine):
         self._deferred[rnd].append((src_ptr, out_ptr, rows, c, ld, 1 if (rnd or acc) else 0, 1.0, 0))
 
     def _flush_deferred(self, P):
-        import struct
         for rnd, entries in enumerate(self._deferred):
             if not entries:
                 continue
-            rec = self.lib.wd_colsum_entry_bytes()
-            assert rec == 40, rec
-            blob = b"".join(struct.pack("<QQiiiifi", *e) for e in entries)
-            table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.device)
+            table = torch.frombuffer((N.WdColsumEntry * len(entries))(*entries), dtype=torch.uint8).to(self.device)
             P.keep.append(table)
             P.bwd.append((self.lib.wd_colsum_finish_multi, (table.data_ptr(), len(entries), max(e[3] for e in entries)),
                           f"parameter-gradient column sums: deferred finishes (round {rnd})"))
