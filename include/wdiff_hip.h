@@ -469,6 +469,26 @@ int wd_ddim_step(float* x, const float* eps, const float* second, float scale, f
                  const float* c1, const float* c2, const float* c3, const float* c4, const float* c5, const int32_t* k_dev,
                  const int32_t* t_dev, const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
 
+/* One DPM-Solver++(2M) update (Lu et al. 2022, algorithm 2: the data-prediction multistep solver) over a subsequence tau of S
+ * visited timesteps; k = *k_dev is the index of the current one.  With a = alpha_hat[tau[k]], p = alpha_hat of the predecessor
+ * (tau[k+1]; alpha_hat[0] after the last entry), lambda(v) = ln(v / (1-v)) / 2 and h_k = lambda(p) - lambda(a), the caller
+ * tabulates per k
+ *   c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt((1-p)/(1-a)), c4 = -sqrt(p) * expm1(-h_k), c5 = h_k / (2 h_{k-1})   (fp32 [S] each)
+ * with c5 = 0 where the step is first order (k = 0, the last step, every step at order 1), and the kernel evaluates, every
+ * operation rounded to fp32 on its own and in this order (no fma contraction),
+ *   x0 = (x - c1[k] * e) * c2[k];
+ *   D  = x0,  or  x0 + c5[k] * (x0 - x0_prev)  when c5[k] != 0;
+ *   x  = c3[k] * x + c4[k] * D;
+ *   x0_prev = x0   (always written).
+ * c5[k] == 0: x0_prev is NOT read (the first step sees an uninitialised buffer) and the term is omitted, not multiplied by
+ * zero.  e = eps, or torch.lerp(second, eps, scale) when second != NULL, formed as wd_ddim_step forms it; eps_out != NULL
+ * receives e.  x0_prev is a caller-owned buffer of x's shape that lives across the steps of one trajectory.
+ * WD_EINVAL: a required pointer (x, eps, x0_prev, c1..c5, k_dev) is NULL, n_per_sample % 4, or x / eps / second / eps_out /
+ * x0_prev is not 16-byte aligned. */
+int wd_dpmpp_step(float* x, const float* eps, const float* second, float scale, float* eps_out, float* x0_prev, int batch,
+                  int n_per_sample, const float* c1, const float* c2, const float* c3, const float* c4, const float* c5,
+                  const int32_t* k_dev, void* stream);
+
 /* The table-driven wd_advance_timestep: k = min(*k_dev + 1, S - 1); *k_dev = k; *t_dev = tau[k]; t64[b] = tau[k] for b < batch
  * (tau int32 [S]).  After the last visited step k stays at S - 1. */
 int wd_next_timestep(int32_t* k_dev, const int32_t* tau, int S, int32_t* t_dev, int64_t* t64, int batch, void* stream);

@@ -360,6 +360,52 @@ __global__ void ddim_step_kernel(float* __restrict__ x, const float* __restrict_
     }
 }
 
+// DPM-Solver++(2M) update (Lu et al. 2022, algorithm 2) on the step index k = *k_dev of the visited-timestep tables:
+//   x0 = (x - c1[k] * e) * c2[k];  D = x0, or x0 + c5[k] * (x0 - x0_prev) when c5[k] != 0;  x = c3[k] * x + c4[k] * D;
+//   x0_prev = x0,  every operation rounded on its own.  e as in ddim_step_kernel.  c5[k] == 0: x0_prev is written, not read.
+__global__ void dpmpp_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ second, float scale,
+                                  float* __restrict__ eps_out, float* __restrict__ x0_prev, int batch, int n4,
+                                  const float* __restrict__ c1, const float* __restrict__ c2, const float* __restrict__ c3,
+                                  const float* __restrict__ c4, const float* __restrict__ c5, const int32_t* __restrict__ k_dev) {
+    const int k = *k_dev;
+    const float a1 = c1[k], a2 = c2[k], a3 = c3[k], a4 = c4[k], r = c5[k];
+    const float oms = 1.0f - scale;
+    const bool high = fabsf(scale) >= 0.5f;
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        float4 ev = reinterpret_cast<const float4*>(eps)[i];
+        if (second) {
+            const float4 sv = reinterpret_cast<const float4*>(second)[i];
+            ev.x = lerp_guided(ev.x, sv.x, scale, oms, high);
+            ev.y = lerp_guided(ev.y, sv.y, scale, oms, high);
+            ev.z = lerp_guided(ev.z, sv.z, scale, oms, high);
+            ev.w = lerp_guided(ev.w, sv.w, scale, oms, high);
+        }
+        if (eps_out) reinterpret_cast<float4*>(eps_out)[i] = ev;
+        float4 x0;
+        x0.x = (xv.x - a1 * ev.x) * a2;
+        x0.y = (xv.y - a1 * ev.y) * a2;
+        x0.z = (xv.z - a1 * ev.z) * a2;
+        x0.w = (xv.w - a1 * ev.w) * a2;
+        float4 d = x0;
+        if (r != 0.0f) {
+            const float4 pv = reinterpret_cast<const float4*>(x0_prev)[i];
+            d.x = x0.x + r * (x0.x - pv.x);
+            d.y = x0.y + r * (x0.y - pv.y);
+            d.z = x0.z + r * (x0.z - pv.z);
+            d.w = x0.w + r * (x0.w - pv.w);
+        }
+        reinterpret_cast<float4*>(x0_prev)[i] = x0;
+        float4 o;
+        o.x = a3 * xv.x + a4 * d.x;
+        o.y = a3 * xv.y + a4 * d.y;
+        o.z = a3 * xv.z + a4 * d.z;
+        o.w = a3 * xv.w + a4 * d.w;
+        reinterpret_cast<float4*>(x)[i] = o;
+    }
+}
+
 // advance_kernel over a table of visited timesteps: k <- min(k + 1, S - 1), t <- tau[k]
 __global__ void next_timestep_kernel(int32_t* k_dev, const int32_t* __restrict__ tau, int S, int32_t* t_dev, int64_t* t64,
                                      int batch) {
@@ -677,6 +723,19 @@ extern "C" int wd_ddim_step(float* x, const float* eps, const float* second, flo
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, eps, second, scale,
                        eps_out, batch, n_per_sample / 4, c1, c2, c3, c4, c5, k_dev, t_dev, noise, seed, sample_offset);
+    return wd_check_launch();
+}
+
+extern "C" int wd_dpmpp_step(float* x, const float* eps, const float* second, float scale, float* eps_out, float* x0_prev, int batch,
+                             int n_per_sample, const float* c1, const float* c2, const float* c3, const float* c4, const float* c5,
+                             const int32_t* k_dev, void* stream) {
+    if (!x || !eps || !x0_prev || !c1 || !c2 || !c3 || !c4 || !c5 || !k_dev || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4)
+        return WD_EINVAL;
+    if (!aligned16(x) || !aligned16(eps) || !aligned16(second) || !aligned16(eps_out) || !aligned16(x0_prev)) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, eps, second, scale,
+                       eps_out, x0_prev, batch, n_per_sample / 4, c1, c2, c3, c4, c5, k_dev);
     return wd_check_launch();
 }
 

@@ -5,7 +5,8 @@ conditioning (word embedding, cross-attention K/V) is computed once, one denoisi
 update with on-device Philox noise + its timestep advance) is captured into a hipGraph and replayed once per visited step;
 there is no per-step host->device traffic.  What a sampler is to that loop is a ``_Sampler``, fixed on the host before
 anything is launched: ``_ddpm`` (``sampling``, ``train.py:221-236``: ``x <- 1/sqrt(a) (x - (1-a)/sqrt(1-ah) eps) + sqrt(b) z``
-at t = T-1 .. 1; ``sampling3`` skips the model on most of those steps) and ``_ddim`` (``sampling_ddim``: a subsequence).
+at t = T-1 .. 1; ``sampling3`` skips the model on most of those steps), ``_ddim`` (``sampling_ddim``: a subsequence) and
+``_dpmpp`` (``sampling_dpmpp``: a subsequence spaced in log-SNR, second-order multistep).
 
 Facts preserved from the reference: the method is ``sampling`` (``sample`` is provided as
 an alias because ``sampling.py:119`` calls it); index 0 of the schedule is never used; with ``cfg_scale > 0``
@@ -117,7 +118,7 @@ class EMA:
 
 
 class _Sampler(NamedTuple):
-    """What one sampler is to the reverse loop of ``Diffusion._denoise`` (built by ``Diffusion._ddpm`` / ``_ddim``, no GPU)."""
+    """What one sampler is to the reverse loop of ``Diffusion._denoise`` (built by ``Diffusion._ddpm`` / ``_ddim`` / ``_dpmpp``, no GPU)."""
     # per visited step, in loop order: (film_prepare argument = row of the pairs table, calls the model, index into ``noise`` or None)
     steps: list
     t_first: int  # the timestep of the first step
@@ -212,6 +213,54 @@ class Diffusion:
         c4 = torch.sqrt(torch.clamp(1 - p - sigma * sigma, min=0.0))
         return tuple(c.float().to(device).contiguous() for c in (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt(p), c4, sigma))
 
+    def dpmpp_timesteps(self, steps=None, spacing="logsnr", timesteps=None):
+        """The timesteps a DPM-Solver++ call visits, strictly decreasing ints in [1, T-1]: the explicit ``timesteps`` after the
+        validation of ``ddim_timesteps``; ``spacing="time"``: ``ddim_timesteps(steps)``; ``spacing="logsnr"``: ``steps`` of them
+        spread evenly in lambda_t = ln(alpha_hat_t / (1 - alpha_hat_t)) / 2 (float64, alpha_hat recomputed as in ``_ddim_tables``).
+        Target k of S is lambda_{T-1} + (lambda_1 - lambda_{T-1}) k / (S-1); its candidate is the index whose lambda is nearest
+        (the lowest on a tie), and tau[k] = max(min(candidate, tau[k-1] - 1), S - k) keeps the list strictly decreasing with
+        room for the entries still to come: always S entries, the first T-1, the last 1."""
+        T = self.noise_steps
+        if spacing not in ("logsnr", "time"):
+            raise ValueError(f"spacing must be 'logsnr' or 'time', not {spacing!r}")
+        if timesteps is not None or spacing == "time":
+            return self.ddim_timesteps(steps, timesteps)
+        S = int(steps)
+        if not 1 <= S <= T - 1:
+            raise ValueError(f"steps must be in [1, {T - 1}] for a schedule of {T} noise steps (got {steps})")
+        if S == 1:
+            return [T - 1]
+        ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
+        lam = 0.5 * torch.log(ah / (1 - ah))
+        target = lam[T - 1] + (lam[1] - lam[T - 1]) * torch.arange(S, dtype=torch.float64) / (S - 1)
+        # (one [S, T-1] argmin rather than S of them: this runs on the host in every call; the first of equal minima is returned)
+        cands = (1 + torch.argmin((lam[None, 1:] - target[:, None]).abs(), dim=1)).tolist()
+        tau = []
+        for k, cand in enumerate(cands):
+            if k:
+                cand = min(cand, tau[-1] - 1)
+            tau.append(max(cand, S - k))
+        return tau
+
+    def _dpmpp_tables(self, tau, order, device):
+        """The five per-step coefficients of ``wd_dpmpp_step`` (fp32 [S] each), with a = alpha_hat[tau[k]], p = alpha_hat of the
+        predecessor (alpha_hat[0] after the last entry, as in ``_ddim_tables``) and h_k = lambda(p) - lambda(a):
+        c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt((1-p)/(1-a)), c4 = -sqrt(p) expm1(-h_k), c5 = h_k / (2 h_{k-1}).  c5 = 0 makes a
+        step first order: k = 0, every k at ``order`` 1, and always the last step (no extrapolation into index 0).  Evaluated
+        in float64 from the fp32 betas and rounded to fp32 once."""
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, not {order!r}")
+        ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
+        tau = [int(t) for t in tau]
+        a = ah[tau]
+        p = ah[tau[1:] + [0]]
+        h = 0.5 * torch.log(p / (1 - p)) - 0.5 * torch.log(a / (1 - a))
+        c5 = torch.zeros_like(h)
+        if order == 2 and len(tau) > 2:
+            c5[1:-1] = h[1:-1] / (2 * h[:-2])
+        tabs = (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt((1 - p) / (1 - a)), -torch.sqrt(p) * torch.expm1(-h), c5)
+        return tuple(c.float().to(device).contiguous() for c in tabs)
+
     # --------------------------------------------------------------------------------------------------
     def _ddpm(self, calls_model=None, deterministic=False):
         """The DDPM family: t = T-1 .. 1 (train.py:221), the model called where ``calls_model(t)`` holds (None: everywhere; a
@@ -264,6 +313,32 @@ class Diffusion:
                                              P.t_in.data_ptr(), n, stream), "wd_next_timestep")
             return end_step
         stats = dict(sampler="ddim", steps=len(tau), eta=float(eta), timesteps=list(tau))
+        return _Sampler(steps, tau[0], list(tau), update, stats)
+
+    def _dpmpp(self, tau, order, spacing=None):
+        """DPM-Solver++(2M) over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows and pairs are indexed by k,
+        the model is called at every step and no step draws noise.  The previous data prediction lives in a buffer of the
+        update's own, written by every step and read only where c5[k] != 0.  A step ends with ``wd_dpmpp_step`` and
+        ``wd_next_timestep``."""
+        tabs = self._dpmpp_tables(tau, order, "cpu")
+        steps = [(k, True, None) for k in range(len(tau))]
+
+        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+            c = [t.to(device) for t in tabs]
+            tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
+            x0_prev = torch.empty_like(P.x_in)  # (the first step does not read it: c5[0] == 0)
+            P.k_dev.zero_()
+            n, npix = P.x_in.shape[0], P.x_in[0].numel()
+            scale, eps_g = guide or (0.0, None)
+
+            def end_step(stream):
+                N.check(lib.wd_dpmpp_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
+                                          scale, _dptr(eps_g), x0_prev.data_ptr(), n, npix, *(t.data_ptr() for t in c),
+                                          P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
+                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
+                                             P.t_in.data_ptr(), n, stream), "wd_next_timestep")
+            return end_step
+        stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
         return _Sampler(steps, tau[0], list(tau), update, stats)
 
     def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
@@ -488,6 +563,33 @@ class Diffusion:
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred)
+        finally:
+            model.train()  # as ``sampling`` (train.py:238)
+        return self._finish(x, vae, args)
+
+    @torch.no_grad()
+    def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
+                       mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
+                       record_pred=None, use_graph=True, underscore=None, style_pairs=None):
+        """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
+        ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
+        the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
+        step are always first order.  ``spacing="logsnr"`` spreads the timesteps evenly in log-SNR, where the solver's error
+        estimate holds on this schedule; ``"time"`` is DDIM's spacing.  Deterministic given x_T: ``seed`` only draws x_T (the
+        Philox key of ``sampling``), and there is no ``noise``.  The last step lands on index 0 of the schedule, as in
+        ``sampling_ddim``, and everything else follows it too: eval mode for the loop and TRAIN mode afterwards, ``vae=None``
+        returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
+        ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``."""
+        tau = self.dpmpp_timesteps(steps, spacing, timesteps)
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, not {order!r}")
+        device, tf, phosc = self._prepare("sampling_dpmpp", model, n, x_text, args, phoscLabels, underscore)
+        sampler = self._dpmpp(tau, order, None if timesteps is not None else spacing)
+        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
+        model.eval()
+        try:
+            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, seed=seed, sample_offset=sample_offset,
+                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)

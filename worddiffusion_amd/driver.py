@@ -94,17 +94,17 @@ def write_png(path: str, img: np.ndarray) -> None:
 
 
 def _check_sampler(sampler: str, skip_steps=False) -> None:
-    if sampler not in ("ddpm", "ddim"):
-        raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
-    if sampler == "ddim" and skip_steps:
-        raise ValueError("sampler='ddim' and skip_steps are two ways to run fewer steps: choose one")
+    if sampler not in ("ddpm", "ddim", "dpmpp"):
+        raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', not {sampler!r}")
+    if sampler != "ddpm" and skip_steps:
+        raise ValueError(f"sampler={sampler!r} and skip_steps are two ways to run fewer steps: choose one")
 
 
 @torch.no_grad()
 def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: Dict[str, int], args, vae=None,
                batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
                world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
-               ddim_steps: int = 50, eta: float = 0.0):
+               ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr"):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -112,7 +112,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``regenerateFromtrain2.py`` (``Diffusion.sampling3``); ``phosc_of(word) -> int tensor [769]`` supplies PHOSC vectors for
     ``UNetModelPhosc`` (``args.phosc == 1``).  ``mix_rate`` is handed to the sampler as ``full_sampling.py:171`` hands it: it has
     an effect on a model built with ``args.interpolation`` only.  ``sampler="ddim"``: ``Diffusion.sampling_ddim`` over
-    ``ddim_steps`` timesteps with ``eta`` instead of the full ``sampling`` loop."""
+    ``ddim_steps`` timesteps with ``eta`` instead of the full ``sampling`` loop; ``sampler="dpmpp"``: ``Diffusion.sampling_dpmpp``
+    over ``dpmpp_steps`` timesteps at ``dpmpp_order`` with ``dpmpp_spacing``."""
     _check_sampler(sampler, skip_steps)
     r0, w0, _ = env_rank_world()
     rank = r0 if rank is None else rank
@@ -130,6 +131,9 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         kw = dict(seed=seed, sample_offset=start + b0, mix_rate=mix_rate)
         if sampler == "ddim":
             res = diffusion.sampling_ddim(model, vae, len(chunk), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
+        elif sampler == "dpmpp":
+            res = diffusion.sampling_dpmpp(model, vae, len(chunk), words, labels, args, steps=dpmpp_steps, order=dpmpp_order,
+                                           spacing=dpmpp_spacing, phoscLabels=phosc, **kw)
         elif skip_steps:
             res = diffusion.sampling3(0, None, words, phosc, model, model, vae, 0, 1, len(chunk), words, labels, args, **kw)
             res = res if vae is None else res[2]
@@ -150,11 +154,13 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
 @torch.no_grad()
 def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, style_pair: Tuple[int, int], mix_steps: int = 8,
                 vae=None, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None,
-                phosc_of=None, sampler: str = "ddpm", ddim_steps: int = 50, eta: float = 0.0):
+                phosc_of=None, sampler: str = "ddpm", ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20,
+                dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr"):
     """One interpolation strip per gt row (this rank's shard of them): the row's word sampled ``mix_steps`` times in one call,
     sample j with the writer embedding ``(1 - m_j) * label[s1] + m_j * label[s2]``, ``m = linspace(0, 1, mix_steps)``
     (``Diffusion.sampling(..., style_pairs=)``, one forward per step; ``sampler="ddim"``: ``sampling_ddim`` over ``ddim_steps``
-    timesteps with ``eta``).  Sample j of row r is global sample ``r * mix_steps + j``
+    timesteps with ``eta``; ``sampler="dpmpp"``: ``sampling_dpmpp`` over ``dpmpp_steps`` timesteps at ``dpmpp_order`` with
+    ``dpmpp_spacing``).  Sample j of row r is global sample ``r * mix_steps + j``
     of the noise stream, whatever the sharding.
 
     Returns ``(start, [mix_steps, ...] tensor per row)``.  With ``out_dir``, ``<image>_interp.png`` is written per row: the
@@ -178,6 +184,9 @@ def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, st
         kw = dict(mix_rate=m, phoscLabels=phosc, seed=seed, sample_offset=r * mix_steps, style_pairs=tuple(int(s) for s in style_pair))
         if sampler == "ddim":
             res = diffusion.sampling_ddim(model, vae, mix_steps, word, labels, args, steps=ddim_steps, eta=eta, **kw).detach().cpu()
+        elif sampler == "dpmpp":
+            res = diffusion.sampling_dpmpp(model, vae, mix_steps, word, labels, args, steps=dpmpp_steps, order=dpmpp_order,
+                                           spacing=dpmpp_spacing, **kw).detach().cpu()
         else:
             res = diffusion.sampling(model, vae, mix_steps, word, labels, args, **kw).detach().cpu()
         outs.append(res)
@@ -216,10 +225,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--vocab_size", type=int, default=53, choices=[53, 54],
                     help="53: the 52-letter alphabet of train.py; 54: the '_' alphabet of trainModifyCondition.py:68")
     ap.add_argument("--skip_steps", type=int, default=0, help="1: regenerateFromtrain2.py's step-skipping sampler")
-    ap.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"],
-                    help="ddpm: every one of the noise_steps - 1 steps (train.py:221); ddim: --ddim_steps of them (Song et al. 2020)")
+    ap.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"],
+                    help="ddpm: every one of the noise_steps - 1 steps (train.py:221); ddim: --ddim_steps of them (Song et al. 2020); "
+                         "dpmpp: --dpmpp_steps of them with DPM-Solver++(2M) (Lu et al. 2022)")
     ap.add_argument("--ddim_steps", type=int, default=50, help="--sampler ddim: UNet evaluations per image")
     ap.add_argument("--eta", type=float, default=0.0, help="--sampler ddim: 0 deterministic .. 1 the DDPM posterior variance")
+    ap.add_argument("--dpmpp_steps", type=int, default=20, help="--sampler dpmpp: UNet evaluations per image")
+    ap.add_argument("--dpmpp_order", type=int, default=2, choices=[1, 2], help="--sampler dpmpp: 2 multistep; 1 is DDIM with eta 0")
+    ap.add_argument("--dpmpp_spacing", default="logsnr", choices=["logsnr", "time"],
+                    help="--sampler dpmpp: timesteps evenly spaced in log-SNR, or in t as --sampler ddim spaces them")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--interpolation", type=bool, nargs="?", const=True, default=False,
                     help="args.interpolation of the reference (sampling.py:64; any value is true, as there): with --mix_rate "
@@ -244,10 +258,12 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_args(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if a.sampler == "ddim" and a.skip_steps:
-        ap.error("--sampler ddim and --skip_steps 1 are two ways to run fewer steps: choose one")
+    if a.sampler != "ddpm" and a.skip_steps:
+        ap.error(f"--sampler {a.sampler} and --skip_steps 1 are two ways to run fewer steps: choose one")
     if a.sampler == "ddim" and not 1 <= a.ddim_steps <= a.noise_steps - 1:
         ap.error(f"--ddim_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.sampler == "dpmpp" and not 1 <= a.dpmpp_steps <= a.noise_steps - 1:
+        ap.error(f"--dpmpp_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
     return ap, a
 
 
@@ -296,12 +312,14 @@ def main(argv=None):
     if a.style_pair is not None:
         start, res = interpolate(ema_model, diffusion, rows, args, tuple(a.style_pair), a.mix_steps, vae=vae,
                                  out_dir=os.path.join(a.save_path, "images"), seed=a.seed, phosc_of=phosc_of, sampler=a.sampler,
-                                 ddim_steps=a.ddim_steps, eta=a.eta)
+                                 ddim_steps=a.ddim_steps, eta=a.eta, dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order,
+                                 dpmpp_spacing=a.dpmpp_spacing)
         print(f"[rank {rank}/{world}] strips of rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
         return
     start, res = regenerate(ema_model, diffusion, rows, wr, args, vae=vae, batch=a.batch_size,
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
-                            phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta)
+                            phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
+                            dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing)
     print(f"[rank {rank}/{world}] rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
 
 
