@@ -555,6 +555,29 @@ int wd_adamw_chunk(void);
 int wd_adamw_multi(const void* table, int ntensor, int64_t total_chunks, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int64_t step, int ema_mode, double ema_beta, void* stream);
 
+/* wd_adamw_multi on gradients scaled by a factor that lives on the device: every workgroup reads *gscale once and uses
+ * g = fp32(table.g[i] * *gscale), the product rounded on its own; everything after that is wd_adamw_multi's op order.  The
+ * gradient buffers are not written.  gscale is ctl + 1 of wd_grad_sqnorm_multi for global-norm clipping. */
+int wd_adamw_multi_scaled(const void* table, int ntensor, int64_t total_chunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, int64_t step, int ema_mode, double ema_beta, const float* gscale,
+                          void* stream);
+
+/* Global L2 norm of the gradients of a wd_adamw_multi table and the clip coefficient of torch.nn.utils.clip_grad_norm_, on
+ * the device (two launches, no atomics, fixed summation order: bit-identical from run to run).  Stage 1: one workgroup per
+ * chunk of the table sums (double)g * (double)g in double into partial[chunk] (entries with g == NULL give 0); stage 2: one
+ * workgroup adds the total_chunks partials in a fixed order and writes
+ *   ctl[0] = (float)sqrt(sum)                               the norm, one rounding of the double sum
+ *   ctl[1] = min(1.0f, max_norm / (ctl[0] + 1e-6f))         in fp32; a NaN quotient stays NaN (torch.clamp)
+ * max_norm = +inf gives ctl[1] = 1 for every finite norm: the norm is only measured.  partial: total_chunks doubles of
+ * scratch; ctl: 2 floats.  WD_EINVAL: a NULL pointer, max_norm <= 0 or NaN. */
+int wd_grad_sqnorm_multi(const void* table, int ntensor, int64_t total_chunks, double* partial, float max_norm, float* ctl,
+                         void* stream);
+
+/* dst[i] = scale * (overwrite ? src[i] : dst[i] + src[i]) over n fp32 elements, each operation rounded on its own.  With
+ * overwrite != 0 dst is never read (it may hold anything, NaN included).  16-byte accesses where dst and src reach a 16-byte
+ * boundary at the same element, scalar accesses for the ragged ends (or throughout).  dst and src must not overlap. */
+int wd_grad_accumulate(float* dst, const float* src, int64_t n, int overwrite, float scale, void* stream);
+
 /* Table-driven weight repack (one launch refreshes every packed operand after an optimiser step; the reference reads
  * its parameters in place, unet.py forward).  table: device array of nentries wd_repack_entry records (below), one per piece
  * of a packed operand.

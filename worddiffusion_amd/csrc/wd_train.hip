@@ -11,9 +11,24 @@ namespace {
 
 constexpr int CHUNK = 8192;  // elements per workgroup
 
+// which tensor owns chunk c (binary search over the running chunk0 sums; adamw_multi_kernel keeps its own copy of the loop -
+// through this helper the compiler swaps the operands of one scalar add, and that kernel's code is to stay what it was)
+__device__ __forceinline__ int chunk_owner(const wd_adamw_table_entry* __restrict__ tab, int ntensor, int64_t c) {
+    int lo = 0, hi = ntensor - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].chunk0 <= c) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// GS is empty (wd_adamw_multi: the plain kernel, its signature and code as they were) or one `const float*` (wd_adamw_multi_scaled):
+// a device-resident factor every gradient is multiplied by as it is loaded, the product rounded on its own.
+template <typename... GS>
 __global__ void adamw_multi_kernel(const wd_adamw_table_entry* __restrict__ tab, int ntensor, float decay, float omb1, float b2,
                                    float omb2, float step_size, float bc2_sqrt, float eps, int ema_mode, float ema_b,
-                                   float ema_omb) {
+                                   float ema_omb, const GS... gscale) {
     // binary search: which tensor owns chunk blockIdx.x
     int lo = 0, hi = ntensor - 1;
     const int64_t c = blockIdx.x;
@@ -32,8 +47,11 @@ __global__ void adamw_multi_kernel(const wd_adamw_table_entry* __restrict__ tab,
                 t.ema[i] = ema_mode == 1 ? t.p[i] : t.ema[i] * ema_b + ema_omb * t.p[i];
         return;
     }
+    float gs = 1.0f;
+    if constexpr (sizeof...(GS) > 0) gs = *(gscale, ...);  // one read per workgroup (uniform)
     for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
-        const float g = t.g[i];
+        float g = t.g[i];
+        if constexpr (sizeof...(GS) > 0) g = g * gs;  // the clipped gradient, as torch's grad.mul_(clip_coef) leaves it
         float p = t.p[i] * decay;                 // param.mul_(1 - lr * weight_decay)
         float m = t.m[i];
         m = m + omb1 * (g - m);                   // exp_avg.lerp_(grad, 1 - beta1)
@@ -77,6 +95,104 @@ __global__ void mse_stage2(const double* __restrict__ partial, int nb, int64_t n
     }
 }
 
+// ---- global gradient norm (clip_grad_norm_) and gradient accumulation: streaming passes over the flat gradient arena ----------
+// Sum of squares of one chunk of one tensor in double, one partial per workgroup.  16-byte loads where the address allows: a
+// scalar head up to the first 16-byte boundary of g + base, float4 body, scalar tail.  Every lane's order is fixed by (address,
+// length) alone and the LDS tree is fixed, so the partial is the same bits on every run.
+__global__ __launch_bounds__(256) void grad_sqnorm_stage1(const wd_adamw_table_entry* __restrict__ tab, int ntensor,
+                                                          double* __restrict__ partial) {
+    __shared__ double sh[256];
+    const int64_t c = blockIdx.x;
+    const wd_adamw_table_entry t = tab[chunk_owner(tab, ntensor, c)];
+    double acc = 0.0;
+    if (t.g) {
+        const int64_t base = (c - t.chunk0) * CHUNK;
+        const int len = (int)(base + CHUNK < t.n ? CHUNK : t.n - base);
+        const float* __restrict__ g = t.g + base;
+        int head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) >> 2);
+        if (head > len) head = len;
+        const int nvec = (len - head) >> 2;
+        if ((int)threadIdx.x < head) {
+            const double x = (double)g[threadIdx.x];
+            acc += x * x;
+        }
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + head);
+        for (int i = threadIdx.x; i < nvec; i += 256) {
+            const float4 q = g4[i];
+            acc += (double)q.x * (double)q.x;
+            acc += (double)q.y * (double)q.y;
+            acc += (double)q.z * (double)q.z;
+            acc += (double)q.w * (double)q.w;
+        }
+        const int tail0 = head + (nvec << 2);
+        if (tail0 + (int)threadIdx.x < len) {
+            const double x = (double)g[tail0 + threadIdx.x];
+            acc += x * x;
+        }
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[c] = sh[0];
+}
+
+// One workgroup: lane l adds partials l, l + 256, ... in index order, then the same LDS tree.  ctl[0] = the norm, ctl[1] = the
+// clip coefficient of torch.nn.utils.clip_grad_norm_, formed in fp32: clamp(max_norm / (norm + 1e-6), max = 1).  torch.clamp
+// passes NaN on, so a NaN quotient (a NaN norm, or inf / inf) stays NaN here too.
+__global__ __launch_bounds__(256) void grad_sqnorm_stage2(const double* __restrict__ partial, int64_t n, float max_norm,
+                                                          float* __restrict__ ctl) {
+    __shared__ double sh[256];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(sh[0]);
+        const float q = max_norm / (norm + 1e-6f);
+        ctl[0] = norm;
+        ctl[1] = q != q ? q : fminf(1.0f, q);
+    }
+}
+
+// dst = scale * (OVERWRITE ? src : dst + src); n4 float4s from 16-byte aligned pointers
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void grad_accumulate_vec(float4* __restrict__ dst, const float4* __restrict__ src, int64_t n4,
+                                                           float scale) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 s = src[i];
+        if (!OVERWRITE) {
+            const float4 d = dst[i];
+            s.x = d.x + s.x;
+            s.y = d.y + s.y;
+            s.z = d.z + s.z;
+            s.w = d.w + s.w;
+        }
+        s.x = scale * s.x;
+        s.y = scale * s.y;
+        s.z = scale * s.z;
+        s.w = scale * s.w;
+        dst[i] = s;
+    }
+}
+// the ragged ends (and everything, when dst and src are not aligned alike): elements [0, head) and [tail0, n)
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void grad_accumulate_scalar(float* __restrict__ dst, const float* __restrict__ src, int64_t head,
+                                                              int64_t tail0, int64_t n, float scale) {
+    const int64_t cnt = head + (n - tail0);
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < cnt; j += (int64_t)gridDim.x * 256) {
+        const int64_t i = j < head ? j : tail0 + (j - head);
+        const float s = src[i];
+        dst[i] = scale * (OVERWRITE ? s : dst[i] + s);
+    }
+}
+
 }  // namespace
 
 extern "C" int wd_adamw_table_entry_bytes(void) { return (int)sizeof(wd_adamw_table_entry); }
@@ -91,9 +207,71 @@ extern "C" int wd_adamw_multi(const void* table, int ntensor, int64_t total_chun
     const float decay = (float)(1.0 - lr * weight_decay), omb1 = (float)(1.0 - beta1), b2 = (float)beta2,
                 omb2 = (float)(1.0 - beta2), step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
     WdLaunchScope scope(WD_CLS_OTHER, st);
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, st,
+    hipLaunchKernelGGL(adamw_multi_kernel<>, dim3((unsigned)total_chunks), dim3(256), 0, st,
                        reinterpret_cast<const wd_adamw_table_entry*>(table), ntensor, decay, omb1, b2, omb2, step_size, bc2_sqrt,
                        (float)eps, ema_mode, (float)ema_beta, (float)(1.0 - ema_beta));
+    return wd_check_launch();
+}
+
+extern "C" int wd_adamw_multi_scaled(const void* table, int ntensor, int64_t total_chunks, double lr, double beta1, double beta2,
+                                     double eps, double weight_decay, int64_t step, int ema_mode, double ema_beta,
+                                     const float* gscale, void* stream) {
+    if (!table || !gscale || ntensor <= 0 || total_chunks <= 0 || step <= 0 || ema_mode < 0 || ema_mode > 2) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float decay = (float)(1.0 - lr * weight_decay), omb1 = (float)(1.0 - beta1), b2 = (float)beta2,
+                omb2 = (float)(1.0 - beta2), step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(adamw_multi_kernel<const float*>, dim3((unsigned)total_chunks), dim3(256), 0, st,
+                       reinterpret_cast<const wd_adamw_table_entry*>(table), ntensor, decay, omb1, b2, omb2, step_size, bc2_sqrt,
+                       (float)eps, ema_mode, (float)ema_beta, (float)(1.0 - ema_beta), gscale);
+    return wd_check_launch();
+}
+
+extern "C" int wd_grad_sqnorm_multi(const void* table, int ntensor, int64_t total_chunks, double* partial, float max_norm,
+                                    float* ctl, void* stream) {
+    if (!table || !partial || !ctl || ntensor <= 0 || total_chunks <= 0 || total_chunks > 0x7fffffff || !(max_norm > 0.0f))
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(grad_sqnorm_stage1, dim3((unsigned)total_chunks), dim3(256), 0, st,
+                       reinterpret_cast<const wd_adamw_table_entry*>(table), ntensor, partial);
+    hipLaunchKernelGGL(grad_sqnorm_stage2, dim3(1), dim3(256), 0, st, partial, total_chunks, max_norm, ctl);
+    return wd_check_launch();
+}
+
+extern "C" int wd_grad_accumulate(float* dst, const float* src, int64_t n, int overwrite, float scale, void* stream) {
+    if (!dst || !src || n <= 0) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uintptr_t da = reinterpret_cast<uintptr_t>(dst), sa = reinterpret_cast<uintptr_t>(src);
+    if ((da & 3u) || (sa & 3u)) return WD_EINVAL;
+    // float4 body where dst and src reach a 16-byte boundary at the same element; scalar head and tail (or everything)
+    int64_t head = n, n4 = 0;
+    if ((da & 15u) == (sa & 15u)) {
+        head = (int64_t)(((16u - (unsigned)(da & 15u)) & 15u) >> 2);
+        if (head > n) head = n;
+        n4 = (n - head) >> 2;
+    }
+    const int64_t tail0 = head + 4 * n4, nscalar = head + (n - tail0);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    if (n4 > 0) {
+        const int64_t want = (n4 + 255) / 256;
+        const unsigned nb = (unsigned)(want < 8192 ? want : 8192);
+        if (overwrite)
+            hipLaunchKernelGGL(grad_accumulate_vec<true>, dim3(nb), dim3(256), 0, st, reinterpret_cast<float4*>(dst + head),
+                               reinterpret_cast<const float4*>(src + head), n4, scale);
+        else
+            hipLaunchKernelGGL(grad_accumulate_vec<false>, dim3(nb), dim3(256), 0, st, reinterpret_cast<float4*>(dst + head),
+                               reinterpret_cast<const float4*>(src + head), n4, scale);
+    }
+    if (nscalar > 0) {
+        const int64_t want = (nscalar + 255) / 256;
+        const unsigned nb = (unsigned)(want < 8192 ? want : 8192);
+        if (overwrite)
+            hipLaunchKernelGGL(grad_accumulate_scalar<true>, dim3(nb), dim3(256), 0, st, dst, src, head, tail0, n, scale);
+        else
+            hipLaunchKernelGGL(grad_accumulate_scalar<false>, dim3(nb), dim3(256), 0, st, dst, src, head, tail0, n, scale);
+    }
     return wd_check_launch();
 }
 

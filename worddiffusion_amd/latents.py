@@ -250,7 +250,9 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
     (``training.TrainStep``: timesteps, noise, forward, loss, backward, gradient all-reduce, AdamW, EMA).
     ``max_batches=30`` reproduces the reference's ``if i == 30: break`` (``train.py:263-264``).  The loss stays on the
     device; it is read once at the end (the reference's per-batch ``loss.item()``, ``train.py:295``, is available through
-    ``on_batch``).  Returns the number of batches / images and the mean loss.
+    ``on_batch``).  Returns the number of batches / images and the mean loss.  With ``TrainStep(accumulate=A)`` every batch is
+    one micro-batch: a group the epoch leaves unfinished carries over into the next ``train_epoch`` call on the same ``step``
+    (checkpoint where ``step.micro_index == 0``).
 
     ``vae``: the dataset's batches carry pixels (``"images"``: float [B, 3, H, W] in [-1, 1]) instead of ``"latents"`` and every
     batch is encoded first, ``vae.encode(images).latent_dist.sample() * 0.18215`` (``train.py:277-278``), with the noise of an

@@ -30,13 +30,27 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, want_grad: bool = True):
 class FusedAdamW:
     """``optim.AdamW(model.parameters(), lr=1e-4)`` (train.py:405) + ``EMA(0.995).step_ema`` (train.py:294,410) in one
     multi-tensor launch.  ``ema_model`` is optional; with it ``step()`` reproduces ``ema.step_ema(ema_model, model)``
-    (plain copy for the first ``step_start_ema`` steps, then the moving average)."""
+    (plain copy for the first ``step_start_ema`` steps, then the moving average).
+
+    ``max_grad_norm`` (a float > 0, or ``inf`` to measure only; default ``None``: off, the launches above and nothing else) is
+    ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` folded into the step: ``step()`` first runs the norm pass
+    (``wd_grad_sqnorm_multi``: squares summed in double in a fixed order, rounded once to fp32) and then
+    ``wd_adamw_multi_scaled``, which multiplies every gradient by ``min(1, max_grad_norm / (norm + 1e-6))`` as it loads it.
+    Unlike torch the gradients are NOT scaled in place: ``param.grad`` still holds the unclipped values after ``step()``; the
+    coefficient lives in the kernel.  ``grad_norm`` is a device fp32 ``[1]`` tensor with the pre-clip norm of the last step;
+    nothing synchronises, the caller reads it when it wants to.  A non-finite norm propagates as in torch (the step is not
+    skipped)."""
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, ema_model=None, ema_beta=0.995,
-                 step_start_ema=2000):
+                 step_start_ema=2000, max_grad_norm=None):
         self.params = [p for p in params]
         if not self.params or not self.params[0].is_cuda:
             raise N.NativeError("FusedAdamW needs CUDA parameters (no CPU fallback)")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:  # (NaN fails the comparison too)
+                raise ValueError(f"max_grad_norm must be a positive number or inf, got {max_grad_norm}")
+        self.max_grad_norm = max_grad_norm
         # one group in torch.optim's layout: the source of truth for the hyper-parameters (LR schedulers write ``lr`` here)
         self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                                   maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
@@ -52,6 +66,11 @@ class FusedAdamW:
         self._grads = None
         self._grad_ptrs = None
         self._has_state = [False] * len(self.params)  # parameters that have been stepped (torch keeps state only for those)
+        # [norm, clip coefficient] of the last step, written by wd_grad_sqnorm_multi and read by wd_adamw_multi_scaled
+        # (allocated after the optimiser state, whose placement it therefore leaves alone)
+        self._clip_ctl = torch.zeros(2, dtype=torch.float32, device=self.params[0].device)
+        self.grad_norm = self._clip_ctl[:1]
+        self._partials = None
 
     lr = property(lambda self: self.param_groups[0]["lr"])
     betas = property(lambda self: self.param_groups[0]["betas"])
@@ -125,6 +144,8 @@ class FusedAdamW:
         raw = torch.frombuffer((N.WdAdamwTableEntry * len(recs))(*recs), dtype=torch.uint8)
         self._table = raw.to(self.params[0].device)
         self._chunks = c0
+        if self.max_grad_norm is not None:  # one double per chunk for the norm pass: allocated with the table, not per step
+            self._partials = torch.empty(c0, dtype=torch.float64, device=self.params[0].device)
         self._grad_ptrs = [g.data_ptr() if g is not None else 0 for g in self._grads]
         self._has_state = [h or g is not None for h, g in zip(self._has_state, self._grads)]
 
@@ -139,9 +160,16 @@ class FusedAdamW:
         else:
             mode = 1 if (self.step_count - 1) < self.step_start_ema else 2
         st = torch.cuda.current_stream(self.params[0].device).cuda_stream
-        N.check(lib.wd_adamw_multi(self._table.data_ptr(), len(self.params), self._chunks, float(self.lr),
-                                   float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                                   self.step_count, mode, float(self.ema_beta), st), "wd_adamw_multi")
+        hyper = (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                 self.step_count, mode, float(self.ema_beta))
+        if self.max_grad_norm is None:
+            N.check(lib.wd_adamw_multi(self._table.data_ptr(), len(self.params), self._chunks, *hyper, st), "wd_adamw_multi")
+        else:
+            ctl = self._clip_ctl.data_ptr()
+            N.check(lib.wd_grad_sqnorm_multi(self._table.data_ptr(), len(self.params), self._chunks, self._partials.data_ptr(),
+                                             self.max_grad_norm, ctl, st), "wd_grad_sqnorm_multi")
+            N.check(lib.wd_adamw_multi_scaled(self._table.data_ptr(), len(self.params), self._chunks, *hyper, ctl + 4, st),
+                    "wd_adamw_multi_scaled")
         # the kernel changed the parameters (and the EMA copy) behind autograd's back: the engines that packed operands from
         # them must repack before their next use
         from .engine import note_native_write

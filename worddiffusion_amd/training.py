@@ -12,6 +12,23 @@ backward pass finishes first; every segment is its own hipGraph and the all-redu
 second stream while the next segment computes, so only the last bucket's collective is exposed.  The same arithmetic is
 reachable piecewise through the reference's own call surface (``model(...)``, ``loss.backward()``, ``FusedAdamW.step``);
 this class only removes the per-step host work.
+
+Gradient accumulation (``accumulate=A``): an optimiser step happens on every A-th call.  A call that does not end its group runs
+the same captured graph and then adds the gradient arena into a second arena-sized buffer (``wd_grad_accumulate``; the first call
+of a group overwrites it) - no collective, no ``param.grad`` assignment, no optimiser step, no weight repack.  The last call folds
+the buffer back into the arena, scales by 1 / A (1 / (A * world) after the all-reduce) and goes on as a plain step, so
+``eng.grads()`` / ``param.grad`` then hold the MEAN gradient over the group, before any clipping, and the AdamW table keeps its
+pointers.  Data-parallel: collectives are issued on the last call only; in the bucketed form the fold of prefix [a0, a1) is queued
+on the compute stream behind segment j and in front of the event its all-reduce waits on, so the overlap is the plain step's.
+
+Keying invariant: ``step_index`` counts CALLS, with or without accumulation, and the eps rows and dropout masks of call c are keyed
+by the global row ``(c * world + rank) * B + b``.  So A calls of B rows draw exactly what one call of A * B rows draws.
+
+A partial group carries over from one call (and one ``train_epoch``) to the next - the buffer and ``micro_index`` belong to this
+object -, but neither is in a checkpoint: save at ``micro_index == 0``.
+
+Global-norm clipping belongs to the optimiser handed in (``FusedAdamW(max_grad_norm=...)``); ``last_grad_norm`` is its
+``grad_norm``, the norm of the mean gradient of the last optimiser step.
 """
 from __future__ import annotations
 
@@ -26,11 +43,18 @@ from .optim import FusedAdamW
 
 class TrainStep:
     def __init__(self, model, diffusion, optimizer: FusedAdamW, seed: int = 0, use_graph: bool = True,
-                 process_group=None, bucketed: Optional[bool] = None):
+                 process_group=None, bucketed: Optional[bool] = None, accumulate: int = 1):
         """``bucketed``: run the backward pass in segments with the gradient all-reduce of each segment's arena prefix
-        overlapped with the next segment (default: whenever world > 1; ``True`` at world 1 only cuts the graph - tests)."""
+        overlapped with the next segment (default: whenever world > 1; ``True`` at world 1 only cuts the graph - tests).
+        ``accumulate``: calls per optimiser step (module docstring); 1 is the plain step, launch for launch."""
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
         self.model, self.diffusion, self.opt = model, diffusion, optimizer
         self.seed, self.use_graph = seed, use_graph
+        self.accumulate = int(accumulate)
+        self.micro_index = 0      # position of the next call inside its group, 0 .. accumulate - 1
+        self.optimizer_steps = 0  # optimiser steps taken (step_index counts calls)
+        self._acc = None          # the accumulation buffer, arena-sized, allocated by the first call that needs it
         self._bucketed_arg = bucketed
         self.lib = N.lib()
         self.eng = model.train_engine
@@ -100,10 +124,26 @@ class TrainStep:
         N.check(rc, "wd_graph_end")
         return g
 
-    def _run_bucketed(self, st):
+    def _accumulate(self, st, a0, a1, fold: bool):
+        """fold False: acc[a0:a1] (+)= arena[a0:a1] (the first call of a group overwrites: the buffer is never cleared);
+        fold True: arena[a0:a1] = s * (arena[a0:a1] + acc[a0:a1]), s = 1 / accumulate in a single process and 1 in front of an
+        all-reduce (the sum over ranks is scaled once, by 1 / (accumulate * world))."""
+        arena = self.eng.grad_arena()
+        if self._acc is None or self._acc.numel() != arena.numel():
+            if self.micro_index != 0:
+                raise RuntimeError("the gradient arena changed size inside an accumulation group")
+            self._acc = torch.empty_like(arena)
+        if a1 <= a0:
+            return
+        dst, src = (arena, self._acc) if fold else (self._acc, arena)
+        scale = 1.0 / self.accumulate if fold and self.world == 1 else 1.0
+        N.check(self.lib.wd_grad_accumulate(dst[a0:a1].data_ptr(), src[a0:a1].data_ptr(), a1 - a0,
+                                            0 if fold or self.micro_index else 1, scale, st), "wd_grad_accumulate")
+
+    def _run_bucketed(self, st, final: bool = True):
         """Backward in segments; after segment j the arena prefix [a0, a1) is final: its all-reduce goes to the comm stream
         behind an event, the next segment runs meanwhile.  Returns after queueing everything; the compute stream waits for
-        the collectives before the optimiser."""
+        the collectives before the optimiser.  ``final`` False (a call inside an accumulation group): the segments only."""
         lib = self.lib
         arena = self.eng.grad_arena()
         if self.use_graph and self._seg_graphs is None:
@@ -113,21 +153,24 @@ class TrainStep:
                 N.check(lib.wd_graph_launch(self._seg_graphs[j], st), "wd_graph_launch")
             else:
                 self._body(st, j)
-            if self.world > 1 and a1 > a0:
+            if final and self.accumulate > 1:
+                self._accumulate(st, a0, a1, fold=True)  # in front of the event: the collective sums whole groups
+            if final and self.world > 1 and a1 > a0:
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
                 self._comm.wait_event(ev)
                 with torch.cuda.stream(self._comm):
                     torch.distributed.all_reduce(arena[a0:a1], group=self.pg)  # RCCL over xGMI (gloo in the one-GPU tests)
-        if self.world > 1:
+        if final and self.world > 1:
             self._stream.wait_stream(self._comm)
-            arena.mul_(1.0 / self.world)
+            arena.mul_(1.0 / (self.accumulate * self.world))
 
     def __call__(self, latents: torch.Tensor, text_features: torch.Tensor, labels: Optional[torch.Tensor],
                  t: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  phoscLabels: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
         """One optimisation step on a batch of latents [B, C, H, W]; returns the loss as a device tensor [1] (the
-        reference's ``loss.item()`` per step, train.py:295, is the caller's choice)."""
+        reference's ``loss.item()`` per step, train.py:295, is the caller's choice).  With ``accumulate > 1`` the batch is one
+        micro-batch of its group, the loss is this micro-batch's, and the optimiser steps on the group's last call."""
         if not latents.is_cuda:
             raise N.NativeError("TrainStep runs on the GPU only (no CPU fallback)")
         dev = latents.device
@@ -168,8 +211,9 @@ class TrainStep:
             else:
                 N.check(lib.wd_randn(self._eps.data_ptr(), B, self._eps[0].numel(), self.seed,
                                      (self.step_index * self.world + self.rank) * B, 2, st), "wd_randn")
+            final = self.micro_index == self.accumulate - 1  # this call ends its group: the optimiser steps
             if self.segments:
-                self._run_bucketed(st)
+                self._run_bucketed(st, final)
             else:
                 if self.use_graph:
                     if self._graph is None:
@@ -177,16 +221,32 @@ class TrainStep:
                     N.check(lib.wd_graph_launch(self._graph, st), "wd_graph_launch")
                 else:
                     self._body(st)
-                if self.world > 1:
+                if final and self.accumulate > 1:
+                    self._accumulate(st, 0, self.eng.grad_arena().numel(), fold=True)
+                if final and self.world > 1:
                     arena = self.eng.grad_arena()
                     torch.distributed.all_reduce(arena, group=self.pg)  # one all-reduce of the whole arena (WDIFF_GRAD_BUCKETS=1)
-                    arena.mul_(1.0 / self.world)
-            self.eng.assign_grads()
-            self.opt.step()
-            self.eng.refresh_weights()
+                    arena.mul_(1.0 / (self.accumulate * self.world))
+            if final:
+                self.eng.assign_grads()
+                self.opt.step()
+                self.eng.refresh_weights()
+            else:
+                self._accumulate(st, 0, self.eng.grad_arena().numel(), fold=False)
         cur.wait_stream(self._stream)
         for tns in (latents, text_features, labels, noise):
             if tns is not None and tns.is_cuda:
                 tns.record_stream(self._stream)
         self.step_index += 1
+        if final:
+            self.micro_index = 0
+            self.optimizer_steps += 1
+        else:
+            self.micro_index += 1
         return self._loss
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """The optimiser's ``grad_norm``: device fp32 [1], the global norm of the (mean) gradient of the last optimiser step,
+        before clipping (``FusedAdamW(max_grad_norm=...)``; zero while clipping is off)."""
+        return self.opt.grad_norm
