@@ -114,7 +114,10 @@ typedef struct wd_gemm_args {
                            * bias, rowvec, resid, out_f32 16-byte and out_hi / out_lo 8-byte aligned); not with GEGLU */
     int32_t stat_cpg;     /* channels per statistics group */
     int32_t dbg;          /* 0 in production.  0x400: take the two-workgroups-per-CU kernel (wd_gemm4_kernel) wherever it is
-                             legal, whatever the grid size (parity tests); other bits are timing experiments */
+                             legal, whatever the grid size (parity tests); 0x8000 / 0x10000: the 64 x 320 weights-to-registers
+                             kernel keeps the per-tap A path / takes the slab form where it is legal, whatever WDIFF_GEMMW_SLAB
+                             says (in the args wd_gemm_check returns, 0x10000 = the launch takes the slab form); other bits
+                             are timing experiments */
     int32_t* tickets;     /* NULL: split-K partials are combined by a second launch.  Else ntickets ints, ALL ZERO before the
                            * call and left all zero by it, not shared with a launch that may run concurrently: one arrival
                            * counter per output tile - the workgroup that finishes a tile's last K slice sums the slices from

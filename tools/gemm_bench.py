@@ -17,9 +17,11 @@ from worddiffusion_amd.engine import conv_gather_table, slab_order, slab_span  #
 DEV = "cuda:0"
 B = 64
 SHAPES = {
-    # name: (h, w, cin, cout, kind)   kind: conv3 | lin | conv3cat (640 -> 320 + skip) | geglu
+    # name: (h, w, cin, cout, kind)   kind: conv3 | conv3id (3x3 + a 640-channel identity source: the decoder's 1x1 skip) | lin | geglu
     "conv8x32": (8, 32, 320, 320, "conv3"),
     "conv8x32cat": (8, 32, 640, 320, "conv3"),
+    "conv8x32id": (8, 32, 320, 320, "conv3id"),
+    "conv8x32catid": (8, 32, 640, 320, "conv3id"),
     "conv4x16": (4, 16, 320, 320, "conv3"),
     "conv4x16cat": (4, 16, 640, 320, "conv3"),
     "lin8x32": (8, 32, 320, 320, "lin"),
@@ -50,6 +52,9 @@ def main():
     ap.add_argument("--stamps", type=int, default=0, help="1: per-stage cycle stamps of workgroup 0 (s_memtime)")
     ap.add_argument("--wdirect", type=int, default=0, help="1 / 2: fragment-major weights, 128 x 160 / 64 x 320 weights-to-registers kernel (w_layout 3); 3: the 64 x 80 whole-K kernel for 64-position samples (tile 64080); "
                     "the result is compared with the default kernel's first")
+    ap.add_argument("--gemmw-slab", type=int, default=-1, help="with --wdirect 2: 1 / 0 = the 64 x 320 kernel takes its slab form where "
+                    "legal / keeps the per-tap A path (wd_gemm_args.dbg 0x10000 / 0x8000), whatever WDIFF_GEMMW_SLAB says; the step's "
+                    "four layer shapes are conv8x32, conv8x32cat, conv8x32id, conv8x32catid (--slab is the experimental slab-ORDER kernel)")
     ap.add_argument("--cold", type=int, default=0, help="1: flush caches (1 GiB write) before every launch; "
                     "2: same, then read the weights once (emulates a prefetch) before the launch")
     ap.add_argument("--a32", type=int, default=0, help="1 (with --wdirect 2): src[0] is the fp32 map, GroupNorm + SiLU applied inside "
@@ -69,8 +74,9 @@ def main():
     for name in names:
         h, w, cin, cout, kind = SHAPES[name]
         hw, m = h * w, B * h * w
-        ntaps = 9 if kind == "conv3" else 1
-        ktot = ntaps * cin
+        ntaps = 9 if kind in ("conv3", "conv3id") else 1
+        c2 = 640 if kind == "conv3id" else 0
+        ktot = ntaps * cin + c2
         act = torch.randn(2, m, cin, device=DEV).to(torch.bfloat16)
         wt = (torch.randn(2, cout, ktot, device=DEV) / ktot ** 0.5).to(torch.bfloat16)
         bias = torch.randn(cout, device=DEV)
@@ -87,6 +93,11 @@ def main():
         s.ld, s.c, s.ntaps, s.hw_src = cin, cin, ntaps, hw
         g.src[0] = s
         g.nsrc, g.npass = 1, a.npass
+        if c2:
+            act2 = torch.randn(2, m, c2, device=DEV).to(torch.bfloat16)
+            s2 = N.WdSrc()
+            s2.hi, s2.lo, s2.ld, s2.c, s2.ntaps = act2[0].data_ptr(), act2[1].data_ptr(), c2, c2, 1
+            g.src[1], g.nsrc = s2, 2
         g.w_hi, g.w_lo = wt[0].data_ptr(), wt[1].data_ptr()
         g.m, g.n, g.ktot, g.hw_out = m, cout, ktot, hw
         g.bias = bias.data_ptr()
@@ -112,6 +123,8 @@ def main():
             N.check(lib.wd_gemm_pack_w(wt[0].data_ptr(), wt[1].data_ptr(), cout, ktot, wf[0].data_ptr(), wf[1].data_ptr(), st), "pack_w")
             g.w_hi, g.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
             g.w_layout, g.slab_rows, g.tile = 3, (w if ntaps == 9 else 0), (64320 if a.wdirect == 2 else 64080 if a.wdirect == 3 else 128160)
+            if a.gemmw_slab >= 0:
+                g.dbg = a.dbg = a.dbg | (0x10000 if a.gemmw_slab else 0x8000)
             if a.a32:
                 x32 = torch.randn(m, cin, device=DEV)
                 nchunk = lib.wd_gn_nchunk(hw)
@@ -190,7 +203,7 @@ def main():
             torch.cuda.synchronize()
             us = 1e3 * e0.elapsed_time(e1) / a.iters
         fl = 2.0 * m * cout * ktot
-        print(f"{name:12s} m={m:6d} n={cout:5d} k={ktot:5d} tile={a.tile:6d} npass={a.npass} slab={a.slab} ksplit={a.ksplit} cold={a.cold}: {us:8.1f} us  "
+        print(f"{name:12s} m={m:6d} n={cout:5d} k={ktot:5d} tile={a.tile:6d} npass={a.npass} slab={a.slab} gemmw_slab={a.gemmw_slab} ksplit={a.ksplit} cold={a.cold}: {us:8.1f} us  "
               f"{fl / us / 1e6:7.1f} TF/s algorithmic ({a.npass * fl / us / 1e6:7.1f} MFMA)", flush=True)
 
 

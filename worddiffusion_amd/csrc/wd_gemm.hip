@@ -2362,6 +2362,18 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         if (a.ksplit == 0) a.ksplit = a.ws ? wd_auto_ksplit(a.tile, a.m, a.n, nk64, a.ws_floats) : 1;
         if (a.ksplit > 1 && (nk64 < a.ksplit || (long)a.ksplit * a.m * a.n > a.ws_floats)) a.ksplit = 1;
         if (a.gn_gamma && a.ksplit <= 1) return WD_EINVAL;
+        {
+            // the slab form of the 64 x 320 kernel: src[0] a 3x3 / pad 1 / stride 1 source whose 64-row tiles are whole image rows of
+            // one sample, given as planes; an optional identity src[1]; no K cut.  Everything else takes the per-tap form.
+            // WDIFF_GEMMW_SLAB (default WD_GEMMW_SLAB_DEFAULT) is the switch; dbg WD_GEMMW_SLAB_OFF / _ON override it per call.
+            static const bool slab_env = getenv("WDIFF_GEMMW_SLAB") ? atoi(getenv("WDIFF_GEMMW_SLAB")) != 0 : WD_GEMMW_SLAB_DEFAULT;
+            const bool want = (a.dbg & WD_GEMMW_SLAB_OFF) ? false : (a.dbg & WD_GEMMW_SLAB_ON) ? true : slab_env;
+            const bool fits = a.tile == 64320 && a.npass == 3 && a.ksplit <= 1 && a.w_ngroups <= 1 && !a.a32 && !a.ln_gamma && same3 &&
+                              64 % a.slab_rows == 0 && a.hw_out % 64 == 0 && a.m % a.hw_out == 0 && q0.c % 64 == 0 &&
+                              (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
+            a.dbg &= ~(WD_GEMMW_SLAB_OFF | WD_GEMMW_SLAB_ON);
+            if (want && fits) a.dbg |= WD_GEMMW_SLAB_BIT;
+        }
         r.a = a, r.kernel = K_GEMMW;
         return WD_OK;
     }

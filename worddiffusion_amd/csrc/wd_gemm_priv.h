@@ -5,6 +5,11 @@
 // wd_gemmw.hip: the 64 x 320 "weights straight to registers" kernel (wd_gemm_args.w_layout == 3).  `a` has been validated and
 // its ksplit resolved by wd_gemm().
 int wd_gemmw_launch(const wd_gemm_args& a, hipStream_t st);
+// wd_gemm_args.dbg, the slab form of that kernel (the A operand of a 3x3 / pad 1 / stride 1 source from an LDS slab, see the kernel).
+// A caller's WD_GEMMW_SLAB_OFF / _ON overrides WDIFF_GEMMW_SLAB for this call (the engine's own switch, the parity tests); in
+// the RESOLVED args WD_GEMMW_SLAB_BIT says that the launch takes the slab form - wd_gemm_resolve alone decides that.
+constexpr bool WD_GEMMW_SLAB_DEFAULT = true;
+constexpr int WD_GEMMW_SLAB_OFF = 0x8000, WD_GEMMW_SLAB_ON = 0x10000, WD_GEMMW_SLAB_BIT = WD_GEMMW_SLAB_ON;
 // wd_gemm.hip: the split-K combine launch for slabs of a launch with bm-row tiles (statistics layout follows bm).
 int wd_gemm_launch_reduce(const wd_gemm_args& a, hipStream_t st, int bm);
 // wd_gemmq.hip: 64 x 80 tiles, all of K inside the workgroup (wd_gemm_args.tile == 64080: the 3x3 layers over 64-position samples).

@@ -38,9 +38,25 @@ __device__ __forceinline__ int w_lds_off(int row, int ch) { return row * 128 + (
 //      and normalises, activates and splits them between the load (issued a stage earlier) and the ds_write; the
 //      wd_gn_apply launch, its pass over the tensor and the planes it wrote disappear.  A tile's rows are one sample
 //      (hw_out % BM == 0): its 2 c scale / shift values are derived from the statistics partials once per workgroup.
-template <int NPASS, int RH, bool A32>
+// SLAB: src[0] is a 3x3 / pad 1 / stride 1 source over images slab_rows = W wide, W | 64 (wd_gemm checked: one tile = TR = 64 / W
+//      image rows of one sample).  The nine taps of a tile read shifted views of the same TR + 2 source image rows, so those rows
+//      are not gathered per tap (9 x 16 KB per 64-channel chunk through the vector-memory path) but copied ONCE per chunk into an LDS
+//      slab as wd_gemmq_kernel does: NR = TR + 2 rows of W + 2 tokens, a zero token at either end of a row (the padding), rows
+//      above / below the image filled through out-of-range offsets, both planes, the w_lds_off swizzle.  A tap is a constant
+//      shift of the slab row a lane reads its fragment from.  K runs CHUNK-major - stage (chunk, tap) multiplies the weight
+//      k-steps 2 (tap cpt + chunk) + half of the ordinary tap-major image - so a slab is live for nine stages: the loop has one
+//      workgroup barrier per chunk, not per stage, and the slab of chunk c + 1 is register-staged into the second buffer during the
+//      first stages of chunk c (one piece per thread and stage, both planes).  The stages that have no piece left to move issue NO
+//      load for it and wait for none - a uniform branch, against the rule below that every stage issues the same loads: with
+//      out-of-range loads in the idle slots the kernel ran 8-10 us per launch SLOWER than the per-tap form (every stage then
+//      begins with a vmcnt(0) for the store of a piece that is not there, and pays the address work of two loads), without them it
+//      runs level with it alone and 6 us per launch faster inside the step.  The 64-channel chunks of
+//      an identity src[1] (the decoder's 1x1 skip) follow as one-stage chunks through the same two buffers, one barrier per
+//      stage as in the per-tap form.  The K-half stagger is kept.
+template <int NPASS, int RH, bool A32, bool SLAB = false>
 __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, const int nbn, const int nbm) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(!SLAB || (NPASS == 3 && RH == 1 && !A32), "the slab form is the split-bf16 64 x 320 kernel over operand planes");
     constexpr int NPL = (NPASS == 1) ? 1 : 2;
     constexpr int BM = 64 * RH, BN = 320 / RH;
     constexpr int A_PL = BM * 128;  // one plane of one stage: BM rows x 64 bf16
@@ -48,6 +64,10 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
     constexpr uint32_t WD_OOB = 0x80000000u;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // SLAB geometry: image width, tile / slab image rows, slab tokens per image row, bytes of one plane / both planes of a chunk's slab
+    const int Wm = SLAB ? a.slab_rows : 1, wsh = __builtin_ctz(Wm);
+    const int TR = 64 >> wsh, NR = TR + 2, SW = Wm + 2;
+    const int CPL = NR * SW * 128, CHB = 2 * CPL;
     int* s_tab = reinterpret_cast<int*>(smem + 2 * STAGE);  // [ntaps0][BM] source row of src[0] per tap, -1 = zero row
 
     const int ntile = nbn * nbm;
@@ -71,8 +91,8 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
     const int cg = RH == 2 ? wave & 1 : wave & 3;
     const int l15 = lane & 15, lq = lane >> 4;
 
-    // ---- source-row table of src[0] for this row panel
-    {
+    // ---- source-row table of src[0] for this row panel (SLAB: src[0] needs none, src[1] is an identity source)
+    if constexpr (!SLAB) {
         const int nt0 = a.src[0].ntaps;
         const int32_t* g0 = a.src[0].gather;
         const int hw_src0 = a.src[0].hw_src;
@@ -128,7 +148,7 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
     // under kernel row 2): their operands are exact zeros and their 15 MFMAs per k-step are left out - a twelfth of the work of a
     // 3x3 convolution over 8 x 32 maps.  Bit 4 tap + i, from the table itself (any gather table, not only the arithmetic one).
     unsigned long long skipmask = 0;
-    if (RH == 1 && a.src[0].gather) {
+    if (!SLAB && RH == 1 && a.src[0].gather) {
         for (int t = 0; t < a.src[0].ntaps; ++t) {
             const unsigned long long oob = __ballot(s_tab[t * BM + lane] < 0);
 #pragma unroll
@@ -155,10 +175,10 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
     const int nk_all = a.ktot / 64;
     // (integer divisions run on the vector ALU: readfirstlane tells the compiler that their results are wave-uniform, else the
     // buffer descriptors and scalar offsets derived from them live in VGPRs and every load sits in a waterfall loop)
+    const int cpt0 = a.src[0].c >> 6, n0st = a.src[0].ntaps * cpt0;
     const int k_begin = __builtin_amdgcn_readfirstlane((int)((long)nk_all * sidx / a.ksplit));
     const int k_end = __builtin_amdgcn_readfirstlane((int)((long)nk_all * (sidx + 1) / a.ksplit));
-    const int nk = k_end - k_begin;
-    const int cpt0 = a.src[0].c >> 6, n0st = a.src[0].ntaps * cpt0;
+    const int nk = SLAB ? 0 : k_end - k_begin;   // (SLAB: no K cut, and every stage runs in the slab loop below)
     // (Every workgroup starts at the same stage on purpose: a rotated start - 32 CUs of an XCD reading 32 different slices of W
     // instead of the same one - measured 6-17 % SLOWER; the L2 serves a line that many CUs ask for at once cheaper than many lines.)
     int s = 0, tap = 0, kc = 0, left;  // left: stages of the current source still to load, this one included
@@ -198,7 +218,7 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
             else a_voff[j] = r >= 0 ? (uint32_t)r * (uint32_t)(cur_ld * 2) + (uint32_t)(ach * 16) : WD_OOB;
         }
     };
-    locate();
+    if constexpr (!SLAB) locate();
     auto kabs = [&]() { return s == 0 ? tap * cpt0 + kc : n0st + kc; };  // absolute stage (the W k-steps 2 kabs, 2 kabs + 1)
     auto advance = [&]() {  // (straight-line: an early return inside this lambda made hipcc treat s / kc as divergent - VGPR
         --left;             //  descriptors and scalar offsets, every load in a waterfall loop)
@@ -347,15 +367,175 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
         return __builtin_amdgcn_readfirstlane(sk);
     };
 
+    if constexpr (SLAB) {
+        // ---- src[0] through the LDS slab, chunk-major, then the 64-channel chunks of an identity src[1], one stage each, through the same
+        // two buffers.
+        const wd_src& q0 = a.src[0];
+        const int H = a.hw_out >> wsh;                 // image rows
+        const int bsm = m0 / a.hw_out;                 // sample of the tile
+        const int y0 = (m0 - bsm * a.hw_out) >> wsh;   // its first image row
+        const int ntok = NR * Wm;                      // real tokens of a slab
+        const int cpt1 = a.nsrc > 1 ? a.src[1].c >> 6 : 0, nch = cpt0 + cpt1;
+        const int nst = 9 * cpt0 + cpt1;
+        // skm0 / skm2: the row tiles whose source rows all lie above (kernel row 0) / below (kernel row 2) the image, bit i (a row tile of
+        // 16 positions spans the image rows y0 + (16 i >> wsh) ... y0 + ((16 i + 15) >> wsh)): exact zeros, their MFMAs are left out.
+        // ub[i]: position p = 16 i + (lane & 15) of row tile i reads, for tap (0, 0), slab row ub[i] + a per-lane row; 16 i is a multiple
+        // of W or W one of 16, so the uniform and the per-lane part of (p >> wsh) SW + (p & (W - 1)) separate.
+        int skm0 = 0, skm2 = 0;
+        int ub[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (y0 + ((16 * i + 15) >> wsh) < 1) skm0 |= 1 << i;
+            if (y0 + ((16 * i) >> wsh) + 1 >= H) skm2 |= 1 << i;
+            ub[i] = ((16 * i) >> wsh) * SW + ((16 * i) & (Wm - 1));
+        }
+        // fill: slot t of a thread is the 16-byte piece (tid & 7) of token (tid >> 3) + 64 t of the slab's real tokens, both planes; 64
+        // tokens on is TR image rows on at the same x.  Everything is re-derived from the lane index per use (as locate() does, and for
+        // its reason: the loop has no register to spare for values that only the fill needs).
+        // An identity chunk (src[1]) is the tile's own 64 rows in slab rows 0 ... 63 of the same buffers (it overwrites padding tokens
+        // that no later chunk reads: src[1] comes last), one stage per chunk.
+        const uint32_t frow_bytes = (uint32_t)(q0.ld * 2), frow1_bytes = (uint32_t)(a.src[1].ld * 2);
+        int fdst = -1;  // set by slab_piece: slab byte offset of the piece, -1: the slot holds none
+        auto slab_piece = [&](const int t, const int chunk, const bool live) -> uint32_t {   // -> its global byte offset (WD_OOB: zeros)
+            int ln;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            const int tq = wave * 8 + (ln >> 3) + 64 * t, fpc = ln & 7;
+            if (chunk >= cpt0) {   // (uniform)
+                const bool piece = live && tq < 64;   // (m % 64 == 0: every row of the tile is a real one)
+                fdst = piece ? w_lds_off(tq, fpc) : -1;
+                return piece ? (uint32_t)(m0 + tq) * frow1_bytes + (uint32_t)(fpc * 16) : WD_OOB;
+            }
+            const int fy = tq >> wsh, fx = tq & (Wm - 1);
+            const int gy = y0 - 1 + fy;   // source image row (rows outside the image read zeros)
+            const bool piece = live && tq < ntok;
+            fdst = piece ? w_lds_off(fy * SW + fx + 1, fpc) : -1;
+            return (piece && gy >= 0 && gy < H) ? (uint32_t)(bsm * q0.hw_src + gy * Wm + fx) * frow_bytes + (uint32_t)(fpc * 16) : WD_OOB;
+        };
+        auto slab_load = [&](const int t, const int chunk, const bool live) {
+            const uint32_t vo = slab_piece(t, chunk, live);
+            if (chunk < cpt0) {   // (a uniform branch between loop-constant descriptors, as in load_a; both sides issue the same loads)
+                ra[0][0] = __builtin_amdgcn_raw_buffer_load_b128(srd0_hi, vo, chunk * 128, 0);
+                ra[0][1] = __builtin_amdgcn_raw_buffer_load_b128(srd0_lo, vo, chunk * 128, 0);
+            } else {
+                ra[0][0] = __builtin_amdgcn_raw_buffer_load_b128(srd1_hi, vo, (chunk - cpt0) * 128, 0);
+                ra[0][1] = __builtin_amdgcn_raw_buffer_load_b128(srd1_lo, vo, (chunk - cpt0) * 128, 0);
+            }
+        };
+        auto slab_store = [&](char* buf, const int t, const int chunk, const bool live) {   // the piece slab_load(t, chunk, live) asked for
+            slab_piece(t, chunk, live);
+            if (fdst >= 0) {
+                *reinterpret_cast<w_u32x4*>(buf + fdst) = ra[0][0];
+                *reinterpret_cast<w_u32x4*>(buf + CPL + fdst) = ra[0][1];
+            }
+        };
+        // the padding tokens (either end of every slab image row) of both buffers and planes: written once, never overwritten
+        for (int i = tid; i < 2 * 2 * NR * 2 * 8; i += WNT) {
+            const int pc = i & 7, side = (i >> 3) & 1;
+            int rest = i >> 4;
+            const int ry = rest % NR;
+            rest /= NR;
+            const int pl = rest & 1, bf = rest >> 1;
+            *reinterpret_cast<w_u32x4*>(smem + bf * CHB + pl * CPL + w_lds_off(ry * SW + (side ? SW - 1 : 0), pc)) = w_u32x4{0u, 0u, 0u, 0u};
+        }
+        kb = 0;
+        load_b(xb, true);  // W(chunk 0, tap 0) is on its way while the first slab is filled
+        {   // slab of chunk 0: at most three pieces per thread and plane (ntok <= 198), all loads in flight before the first store
+            w_u32x4 v[3][2];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                slab_load(t, 0, true);
+                v[t][0] = ra[0][0], v[t][1] = ra[0][1];
+            }
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                ra[0][0] = v[t][0], ra[0][1] = v[t][1];
+                slab_store(smem, t, 0, true);
+            }
+        }
+        int st = 0, sc = 0;      // tap (0 in an identity chunk) and chunk of the stage whose memory phase runs
+        int pft = 0, pfc = -1;   // the slot and chunk that the previous stage's slab_load asked for (pfc < 0: nothing)
+        // Memory phase of stage (st, sc): store the piece loaded a stage ago, ask for W of the next stage and for this stage's piece of
+        // a later chunk, read this stage's A fragments.  Which piece a stage loads: a 3x3 chunk has nine stages, so stage t loads slot t
+        // of chunk sc + 1 (real pieces in slots 0 ... 2 at most; it goes into the buffer that nobody reads during chunk sc).  An identity
+        // chunk has one stage: like the per-tap form it loads TWO chunks ahead, stored after the next stage's barrier into the buffer
+        // just read; the last stage of the last 3x3 chunk does that for the second identity chunk.  A stage whose slot holds no piece
+        // (uniform) issues no load and stores nothing - see the SLAB note at the head of the kernel.
+        auto mem_phase = [&](const int kit, bf16x8 (&bnext)[5][NPL]) {
+            const bool conv = sc < cpt0;
+            if (pfc >= 0) slab_store(smem + (pfc & 1) * CHB, pft, pfc, true);   // (uniform)
+            int tn = st + 1, cn = sc;
+            if (tn == (conv ? 9 : 1)) tn = 0, cn = sc + 1;
+            kb = cn < cpt0 ? tn * cpt0 + cn : n0st + cn - cpt0;
+            load_b(bnext, kit + 1 < nst);
+            const bool two = !conv || (st == 8 && sc == cpt0 - 1);
+            const int fc = two ? sc + 2 : sc + 1, ft = two ? 0 : st;
+            const bool freal = fc < nch && 64 * ft < (fc < cpt0 ? ntok : 64);   // (uniform) the slot holds pieces
+            pfc = freal ? fc : -1, pft = ft;
+            if (freal) slab_load(ft, fc, true);
+            const int ky = (st * 11) >> 5;   // (= st / 3 below 9)
+            const int shift = ky * SW + (st - 3 * ky);
+            const char* cb = smem + (sc & 1) * CHB;
+            int ln;   // (the lane's fragment row re-derived per stage, as in slab_piece: no register held for it across the MFMAs)
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            const int f15 = ln & 15, ch = kh * 4 + (ln >> 4);
+            const int frow = conv ? shift + (f15 >> wsh) * SW + (f15 & (Wm - 1)) : f15;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int ao = w_lds_off((conv ? ub[i] : 16 * i) + frow, ch);
+#pragma unroll
+                for (int p = 0; p < NPL; ++p) xa[i][p] = *reinterpret_cast<const bf16x8*>(cb + p * CPL + ao);
+            }
+            int sk = !conv ? 0 : ky == 0 ? skm0 : ky == 2 ? skm2 : 0;
+            if (kit >= nst) sk = 15;         // the phantom stage of an odd stage count: W is all zero, and the slab is none
+            st = tn, sc = cn;
+            return __builtin_amdgcn_readfirstlane(sk);
+        };
+        // The K-half stagger of the per-tap form, kept: the second group multiplies a stage late, so on every SIMD one wave multiplies
+        // while the other is in its memory phase.  Both groups' stages start together at every barrier - the top of a chunk, and once
+        // more at stage 1, where the late group (which has nothing to multiply in stage 0) would otherwise run ahead into the early
+        // group's MFMA phase and stay there for the whole first chunk.
+        if (kh == 0) {
+            auto early_step = [&](const int kit, const bf16x8 (&bcur)[5][NPL], bf16x8 (&bnext)[5][NPL]) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (st == 0 || kit == 1) __syncthreads();   // (uniform) chunk sc is complete, every wave is done with chunk sc - 1
+                const int sk = mem_phase(kit, bnext);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_all(bcur, sk);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            for (int kit = 0; kit < nst; kit += 2) {
+                early_step(kit, xb, yb);
+                early_step(kit + 1, yb, xb);
+            }
+        } else {
+            int psk = 15;
+            auto late_step = [&](const int kit, bf16x8 (&bset)[5][NPL]) {   // bset: W(kit - 1) on entry, W(kit + 1) on exit
+                __builtin_amdgcn_sched_barrier(0);
+                if (st == 0 || kit == 1) __syncthreads();
+                mfma_all(bset, psk);   // stage kit - 1, on the fragments read before the barrier (kit = 0: nothing)
+                __builtin_amdgcn_sched_barrier(0);
+                psk = mem_phase(kit, bset);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            for (int kit = 0; kit < nst; kit += 2) {
+                late_step(kit, yb);
+                late_step(kit + 1, xb);
+            }
+            mfma_all(yb, psk);   // the last (possibly phantom) stage: index odd, set yb
+        }
+    }
+
     // ---- prologue: A(0) into buffer 0, A(1) on its way, W(0) on its way
-    kb = kabs();
-    load_a(nk > 0);
-    if (nk > 0) advance();
-    load_b(xb, nk > 0);
-    store_a(smem);
-    kb = kabs();
-    load_a(nk > 1);
-    if (nk > 1) advance();
+    if constexpr (!SLAB) {
+        kb = kabs();
+        load_a(nk > 0);
+        if (nk > 0) advance();
+        load_b(xb, nk > 0);
+        store_a(smem);
+        kb = kabs();
+        load_a(nk > 1);
+        if (nk > 1) advance();
+    }
     // The two K-half groups share the SIMDs pairwise (waves w and w + 4).  The second group multiplies one stage LATE - right
     // behind the barrier, on the fragments it read before it - so that on every SIMD one wave is in its MFMA phase while the
     // other is in its memory phase (vmcnt wait, ds_write, the load burst, the fragment reads).  The loads stay a BURST on purpose:
@@ -491,9 +671,35 @@ int launchw(const wd_gemm_args& a, hipStream_t st) {
     return wd_check_launch();
 }
 
+// the slab form (wd_gemm resolved dbg bit WD_GEMMW_SLAB_BIT): LDS = two slab buffers of (64 / W + 2) (W + 2) tokens x 2 planes x 128 B
+// (2 x 34.8 KB at W = 32, at most 2 x 50.7 KB: W = 64 or 1), or the epilogue image
+int launchw_slab(const wd_gemm_args& a, hipStream_t st) {
+    constexpr int red_smem = 64 * (320 + 4) * 4 + WD_STAT_SCRATCH;
+    constexpr int max_loop = 2 * 2 * 198 * 128;
+    constexpr int max_smem = max_loop > red_smem ? max_loop : red_smem;
+    static_assert(max_smem <= 160 * 1024, "LDS budget");
+    const int W = a.slab_rows;
+    const int loop_smem = 2 * 2 * (64 / W + 2) * (W + 2) * 128;
+    const int smem = loop_smem > red_smem ? loop_smem : red_smem;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wd_gemmw_kernel<3, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                max_smem) != hipSuccess)
+            return WD_ELAUNCH;
+        attr_done = true;
+    }
+    const int nbn = a.n / 320, nbm = a.m / 64;
+    {
+        WdLaunchScope scope(WD_CLS_GEMM_WDIRECT, st, 2.0 * (double)a.m * (double)a.n * (double)a.ktot);
+        hipLaunchKernelGGL((wd_gemmw_kernel<3, 1, false, true>), dim3(nbn * nbm), dim3(WNT), smem, st, a, nbn, nbm);
+    }
+    return wd_check_launch();
+}
+
 }  // namespace
 
 int wd_gemmw_launch(const wd_gemm_args& a, hipStream_t st) {
+    if (a.dbg & WD_GEMMW_SLAB_BIT) return launchw_slab(a, st);  // (wd_gemm checked the shape: see wd_gemm_resolve)
     if (a.a32) return launchw<3, 1, true>(a, st);  // (wd_gemm checked: npass 3, tile 64320, one sample per tile)
     if (a.tile == 128160) return a.npass == 3 ? launchw<3, 2>(a, st) : launchw<1, 2>(a, st);
     return a.npass == 3 ? launchw<3, 1>(a, st) : launchw<1, 1>(a, st);

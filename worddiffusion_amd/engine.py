@@ -362,6 +362,10 @@ class UNetEngine:
         # 64 x 320 tiles with the weights loaded straight into the MFMA operand registers (csrc/wd_gemmw.hip): the 320-column
         # layers whose grid fills the chip without a K cut
         self.use_wdirect = os.environ.get("WDIFF_GEMM_WDIRECT", "1") != "0"
+        # ... with the rows of a 3x3 / pad 1 / stride 1 source copied into an LDS slab once per 64-channel chunk instead of gathered per
+        # tap (wd_gemmw_kernel<..., SLAB>).  wd_gemm decides where that form is legal and reads the same variable for its default; an
+        # engine built while it is set passes its value with every launch (wd_gemm_args.dbg 0x10000 / 0x8000).
+        self.gemmw_slab = {None: None, "0": False}.get(os.environ.get("WDIFF_GEMMW_SLAB"), True)
         # Upsample as four 2x2 convolutions of the source map (one per output phase, 4 taps instead of 9; upsample_phase_tables)
         self.use_up_phases = os.environ.get("WDIFF_UPSAMPLE_PHASES", "1") != "0"
         self._derived: Dict[str, tuple] = {}   # name -> (persistent fp32 tensor, function that recomputes it from the parameters)
@@ -741,6 +745,8 @@ class UNetEngine:
         if wdirect or smallmap:
             wf = self._wfrag(wname)
             a.w_hi, a.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
+            if wdirect and self.gemmw_slab is not None:
+                a.dbg |= 0x10000 if self.gemmw_slab else 0x8000
         elif span:
             meta = (srcs[0].ntaps, srcs[0].c, srcs[1].c if len(srcs) > 1 else 0)
             if wname not in self._w3:
