@@ -83,6 +83,36 @@ def assert_untouched(buf, spec, name="buffer"):
                              f"element(s), first at {where}(row {r}, column {c}) = {val!r}")
 
 
+def row_windows(batch, stride, row0, rows, col0, cols):
+    """One window per sample, as the attention kernels place their output: rows b * stride + row0 .. + rows, columns col0 .. + cols."""
+    return [(b * stride + row0, rows, col0, cols) for b in range(batch)]
+
+
+def assert_untouched_windows(buf, windows, name="buffer"):
+    """assert_untouched for an output that is several windows of one buffer: everything outside ALL of them still holds the fill
+    pattern.  windows: a list of (row0, rows, col0, cols), or a boolean keep-mask over buf's last two dimensions (True = may
+    change; the same in every plane)."""
+    ints, k, pat = _ints(buf.detach().cpu())
+    if torch.is_tensor(windows):
+        assert windows.dtype == torch.bool and tuple(windows.shape) == tuple(buf.shape[-2:]), "keep-mask: bool [rows][ld]"
+        keep, what = windows.cpu(), f"the {int(windows.sum())} kept element(s)"
+    else:
+        keep = torch.zeros(buf.shape[-2:], dtype=torch.bool)
+        for row0, rows, col0, cols in windows:
+            assert 0 <= row0 and row0 + rows <= buf.shape[-2] and 0 <= col0 and col0 + cols <= buf.shape[-1], "window outside buf"
+            keep[row0:row0 + rows, col0:col0 + cols] = True
+        what = f"the {len(windows)} window(s)" + (f" of {windows[0][1]} x {windows[0][3]}, first at (row {windows[0][0]}, column "
+                                                  f"{windows[0][2]})" if windows else "")
+    bad = (ints != pat) & ~keep.repeat_interleave(k, dim=-1)
+    if bool(bad.any()):
+        idx = [int(v) for v in bad.nonzero()[0]]
+        r, c = idx[-2], idx[-1] // k
+        where = f"plane {idx[0]}, " if len(idx) == 3 else ""
+        val = buf[tuple(idx[:-2]) + (r, c)].item()
+        raise AssertionError(f"{name}: write outside {what}: {int(bad.sum())} element(s), first at {where}(row {r}, column {c}) "
+                             f"= {val!r}")
+
+
 def assert_finite(view, name="window"):
     """Every window value is finite (an unwritten element or a poisoned operand read shows as NaN)."""
     v = view.detach().float().cpu() if view.dtype == torch.bfloat16 else view.detach().cpu()

@@ -98,3 +98,61 @@ def test_a_window_as_wide_as_its_buffer_is_guarded_by_rows_alone():
     with pytest.raises(AssertionError, match=r"24 element\(s\), first at plane 0, \(row 1, column 0\)"):
         G.assert_untouched(buf[:1], (0, 0, 0, 0))
     G.assert_untouched(G.poisoned((2, 5, 8), torch.bfloat16), (0, 0, 0, 0))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16])
+@pytest.mark.parametrize("planes", [0, 2])
+def test_several_windows_report_a_write_between_them(dtype, planes):
+    """assert_untouched_windows: the attention output - one window of nq rows per sample at rows b * out_rows + out_row0 of one
+    pitched buffer - as a list of windows and as a keep-mask; a write into the rows between two samples' windows, beside a window
+    and past the last one is named by its position."""
+    B, nq, out_rows, row0, cols, ld, col0 = 3, 4, 7, 2, 6, 12, 4
+    lead = (planes,) if planes else ()
+    buf = G.poisoned(lead + (B * out_rows, ld), dtype)
+    wins = G.row_windows(B, out_rows, row0, nq, col0, cols)
+    assert wins == [(2, 4, 4, 6), (9, 4, 4, 6), (16, 4, 4, 6)]
+    mask = torch.zeros(B * out_rows, ld, dtype=torch.bool)
+    for r0, nr, c0, nc in wins:
+        mask[r0:r0 + nr, c0:c0 + nc] = True
+    G.assert_untouched_windows(buf, wins)
+    G.assert_untouched_windows(buf, mask)
+    for r0, nr, c0, nc in wins:  # every window may change, whole
+        buf[..., r0:r0 + nr, c0:c0 + nc] = 1
+    G.assert_untouched_windows(buf, wins)
+    G.assert_untouched_windows(buf, mask)
+    # the row after a sample's last query, the rows before the next sample's first, beside a window, the ends of the buffer
+    for r, c in [(6, 4), (7, 9), (8, 4), (13, 5), (9, 3), (12, 10), (0, 0), (20, 9), (20, 11)]:
+        b2 = buf.clone()
+        b2[..., r, c] = 3
+        for w in (wins, mask):
+            with pytest.raises(AssertionError, match=rf"out: write outside .*first at (plane 0, )?\(row {r}, column {c}\) = 3"):
+                G.assert_untouched_windows(b2, w, "out")
+    b2 = buf.clone()
+    b2[..., 6, 4] = 3
+    b2[..., 13, 4] = 3
+    with pytest.raises(AssertionError, match=r"element\(s\), first at (plane 0, )?\(row 6, column 4\)"):  # the first of the two
+        G.assert_untouched_windows(b2, wins)
+    if planes:
+        b2 = buf.clone()
+        b2[1, 15, 11] = 0
+        with pytest.raises(AssertionError, match=r"plane 1, \(row 15, column 11\)"):
+            G.assert_untouched_windows(b2, wins)
+    # one window: the same verdict as assert_untouched; no window: every element is guarded
+    G.assert_untouched_windows(G.poisoned((5, 8), dtype), [])
+    one = buf.clone()
+    with pytest.raises(AssertionError, match=r"first at (plane 0, )?\(row 9, column 4\)"):
+        G.assert_untouched_windows(one, wins[:1])
+    with pytest.raises(AssertionError, match=r"first at (plane 0, )?\(row 9, column 4\)"):
+        G.assert_untouched(one, wins[0])
+
+
+def test_several_windows_see_half_a_double_and_reject_a_bad_mask():
+    buf = G.poisoned((6, 4), torch.float64)
+    wins = [(0, 2, 1, 2), (3, 2, 1, 2)]
+    buf.view(torch.int32)[2, 3] = 0  # the high half of (row 2, column 1): between the windows
+    with pytest.raises(AssertionError, match=r"\(row 2, column 1\)"):
+        G.assert_untouched_windows(buf, wins)
+    with pytest.raises(AssertionError, match="keep-mask"):
+        G.assert_untouched_windows(buf, torch.zeros(6, 8, dtype=torch.bool))
+    with pytest.raises(AssertionError, match="window outside buf"):
+        G.assert_untouched_windows(buf, [(4, 3, 0, 1)])
