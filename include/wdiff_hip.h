@@ -517,6 +517,7 @@ int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sa
  * noise without sample, mean / logvar / sample / noise not 16-byte aligned.  Does not allocate or synchronise (capturable). */
 #define WD_VAE_MAX_LATENT 8
 #define WD_STREAM_VAE_POSTERIOR 3 /* stream ids taken so far: 0 x_T, 1 noise_images eps, 2 the training step's eps, 3 this one; */
+#define WD_STREAM_KNOWN 4         /* 4: the per-sample fixed eps of a known-region call (wd_known_blend below), via wd_randn; */
 #define WD_STREAM_DROPOUT0 0x100  /* 0x100 + layer: the training dropout mask of ResBlock `layer` (wd_dropout below) */
 int wd_vae_posterior(const float* moments_tok, int ld, const float* w, const float* bias, int batch, int L, int hw, float* mean,
                      float* logvar, float* sample, float scale, const float* noise, uint64_t seed, uint64_t sample_offset,
@@ -531,6 +532,29 @@ int wd_posterior_sample(const float* mean, const float* logvar, int batch, int n
  * sqrt(alpha_hat) and sqrt(1 - alpha_hat) are tabulated by the caller (fp32, reference op order). */
 int wd_noise_images(const float* x, const float* eps, const int64_t* t, const float* sqrt_ah, const float* sqrt_1m_ah,
                     int batch, int n_per_sample, float* out, void* stream);
+
+/* Known-region conditioning (inpainting as in RePaint, Lugmayr et al. 2022): after a sampler's update and BEFORE its timestep
+ * advance, x [batch][n_per_sample] is at the level of the predecessor p of the step just taken, read on the device so that a
+ * captured graph replays:
+ *   tau == NULL (DDPM form):  p = *t_dev - 1;
+ *   otherwise, k = *k_dev:    p = tau[k + 1] if k + 1 < S, else 0   (tau int32 [S], the visited timesteps of wd_next_timestep).
+ * Where the mask keeps, x is replaced by the known latent x0 noised to that level.  Per element, every operation rounded to
+ * fp32 on its own and in this order (no fma contraction):
+ *   kv = x0                                   when p == 0: the trajectory ends on the known latent itself, noise-free;
+ *   kv = sqrt_ah[p] * x0 + sqrt_1m_ah[p] * z  otherwise - the expression of wd_noise_images, bit for bit;
+ *   x  = x (its bits, untouched by arithmetic) where m == 0,  kv where m == 1,  x + m * (kv - x) otherwise.
+ * x0, mask (values in [0, 1], 1 = keep) and noise are fp32 [batch][n_per_sample]; the two tables are wd_noise_images'.
+ * z: read from noise when given (one fixed eps per sample, or the parity tests); else drawn from Philox4x32-10 keyed by seed
+ * with counter (element / 4, WD_TAG_KNOWN | p, sample_offset + sample index) - a tag family of its own, disjoint from the
+ * step kernels' bare timestep t (< 2^30) and from the 0x80000000 | stream_id tags of wd_randn, so a step that draws its own
+ * noise at level p and this blend never share a draw.  What is drawn for a group of four elements does not depend on the mask;
+ * at p == 0 neither noise is read nor anything drawn.
+ * WD_EINVAL (nothing launched): x, x0, mask or a table is NULL, n_per_sample % 4, x / x0 / mask / noise not 16-byte aligned,
+ * tau given with S < 1 or without k_dev, tau and t_dev both NULL.  Does not allocate or synchronise (capturable). */
+#define WD_TAG_KNOWN 0x40000000
+int wd_known_blend(float* x, const float* x0, const float* mask, int batch, int n_per_sample, const float* sqrt_ah,
+                   const float* sqrt_1m_ah, const int32_t* t_dev, const int32_t* k_dev, const int32_t* tau, int S,
+                   const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
 
 /* strided device-to-device copy (rows x width_bytes); used to materialise a channel concat (unet.py:1750) only when
  * GroupNorm groups straddle the concat boundary. */

@@ -1,7 +1,7 @@
 """worddiffusion_amd - MI355X-native UNet denoising hot path of WordDiffusion."""
 from .unet import UNetModel
 from .unetPhosc import UNetModelPhosc
-from .diffusion import EMA, Diffusion, label_padding
+from .diffusion import EMA, Diffusion, label_padding, latent_mask_from_pixels
 from .vae import AutoencoderKL
 
-__all__ = ["UNetModel", "UNetModelPhosc", "Diffusion", "EMA", "label_padding", "AutoencoderKL"]
+__all__ = ["UNetModel", "UNetModelPhosc", "Diffusion", "EMA", "label_padding", "latent_mask_from_pixels", "AutoencoderKL"]

@@ -95,6 +95,7 @@ WD_OK, WD_EINVAL, WD_ELAUNCH, WD_ESTATE = (DEFINES[n] for n in ("WD_OK", "WD_EIN
 ACT_NONE, ACT_SILU, ACT_GEGLU = (DEFINES[n] for n in ("WD_ACT_NONE", "WD_ACT_SILU", "WD_ACT_GEGLU"))
 VAE_MAX_LATENT, STREAM_VAE_POSTERIOR, STREAM_DROPOUT0, NCLASS = (
     DEFINES[n] for n in ("WD_VAE_MAX_LATENT", "WD_STREAM_VAE_POSTERIOR", "WD_STREAM_DROPOUT0", "WD_NCLASS"))
+STREAM_KNOWN, TAG_KNOWN = DEFINES["WD_STREAM_KNOWN"], DEFINES["WD_TAG_KNOWN"]
 CLASS_NAMES = ("gemm", "gn_stats", "gn_apply", "layernorm", "attention", "other", "gemm_other_tiles", "gemm_splitk_reduce",
                "gemm_two_per_cu", "gemm_weights_to_registers", "feed_forward_fused", "weight_gradient", "gemm_small_maps_whole_k")
 assert len(CLASS_NAMES) == NCLASS, "CLASS_NAMES must name every profiling class of the header (WD_NCLASS)"

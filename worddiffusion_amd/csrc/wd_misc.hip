@@ -427,6 +427,52 @@ __global__ void next_timestep_kernel(int32_t* k_dev, const int32_t* __restrict__
     }
 }
 
+// Known-region blend after a sampler's update, before its timestep advance: x is at the level of the predecessor p
+// (*t_dev - 1, or tau[*k_dev + 1], 0 after the last entry), and where the mask m keeps, it is replaced by the known latent x0
+// noised to that level:  kv = x0 at p == 0, else sa[p] * x0 + sb[p] * z (the expression of noise_images_kernel);
+//   x = x (m == 0, the bits it had),  kv (m == 1),  x + m * (kv - x) otherwise,  every operation rounded on its own.
+// z from ``noise`` or from the Philox stream under the tag WD_TAG_KNOWN | p; neither is touched at p == 0, and what is drawn
+// for a group of four does not depend on its mask.
+__global__ void known_blend_kernel(float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ mask, int batch,
+                                   int n4, const float* __restrict__ sa_tab, const float* __restrict__ sb_tab,
+                                   const int32_t* __restrict__ t_dev, const int32_t* __restrict__ k_dev,
+                                   const int32_t* __restrict__ tau, int S, const float* __restrict__ noise, uint64_t seed,
+                                   uint64_t sample_offset) {
+    int p;
+    if (tau) {
+        const int k = *k_dev;
+        p = (k >= -1 && k + 1 < S) ? tau[k + 1] : 0;
+    } else {
+        p = *t_dev - 1;
+    }
+    if (p < 0) p = 0;  // index 0 of the schedule is the last level there is
+    const float sa = sa_tab[p], sb = sb_tab[p];
+    const long total = (long)batch * n4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 m = reinterpret_cast<const float4*>(mask)[i];
+        float4 kv = reinterpret_cast<const float4*>(x0)[i];
+        if (p != 0) {
+            float4 z;
+            if (noise) z = reinterpret_cast<const float4*>(noise)[i];
+            else {
+                const int b = (int)(i / n4);
+                z = philox_normal4(seed, sample_offset + (uint64_t)b, (uint32_t)WD_TAG_KNOWN | (uint32_t)p, (uint32_t)(i - (long)b * n4));
+            }
+            kv.x = sa * kv.x + sb * z.x;
+            kv.y = sa * kv.y + sb * z.y;
+            kv.z = sa * kv.z + sb * z.z;
+            kv.w = sa * kv.w + sb * z.w;
+        }
+        float4 o;
+        o.x = m.x == 0.0f ? xv.x : (m.x == 1.0f ? kv.x : xv.x + m.x * (kv.x - xv.x));
+        o.y = m.y == 0.0f ? xv.y : (m.y == 1.0f ? kv.y : xv.y + m.y * (kv.y - xv.y));
+        o.z = m.z == 0.0f ? xv.z : (m.z == 1.0f ? kv.z : xv.z + m.z * (kv.z - xv.z));
+        o.w = m.w == 0.0f ? xv.w : (m.w == 1.0f ? kv.w : xv.w + m.w * (kv.w - xv.w));
+        reinterpret_cast<float4*>(x)[i] = o;
+    }
+}
+
 // ---- AutoencoderKL posterior (DiagonalGaussianDistribution of the encoder's moments) --------------------------------
 // One draw for four consecutive elements of a sample, shared by both kernels below:
 //   sample = scale * (mean + exp(0.5 * logvar) * z), every operation rounded on its own (no contraction in this file);
@@ -744,6 +790,19 @@ extern "C" int wd_next_timestep(int32_t* k_dev, const int32_t* tau, int S, int32
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(next_timestep_kernel, dim3(1), dim3(256), 0, st, k_dev, tau, S, t_dev, t64, batch);
+    return wd_check_launch();
+}
+
+extern "C" int wd_known_blend(float* x, const float* x0, const float* mask, int batch, int n_per_sample, const float* sqrt_ah,
+                              const float* sqrt_1m_ah, const int32_t* t_dev, const int32_t* k_dev, const int32_t* tau, int S,
+                              const float* noise, uint64_t seed, uint64_t sample_offset, void* stream) {
+    if (!x || !x0 || !mask || !sqrt_ah || !sqrt_1m_ah || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4) return WD_EINVAL;
+    if (tau ? (S < 1 || !k_dev) : !t_dev) return WD_EINVAL;
+    if (!aligned16(x) || !aligned16(x0) || !aligned16(mask) || !aligned16(noise)) return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(known_blend_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, x0, mask, batch,
+                       n_per_sample / 4, sqrt_ah, sqrt_1m_ah, t_dev, k_dev, tau, S, noise, seed, sample_offset);
     return wd_check_launch();
 }
 

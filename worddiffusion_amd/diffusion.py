@@ -123,8 +123,38 @@ class _Sampler(NamedTuple):
     steps: list
     t_first: int  # the timestep of the first step
     tau: Optional[list]  # the visited timesteps when FiLM rows and pairs are indexed by the step index; None: indexed by t
-    update: Callable  # update(lib, P, guide, zbuf, seed, sample_offset, device) -> end_step(stream), the launches that end a step
+    # update(lib, P, guide, zbuf, seed, sample_offset, device, known=None) -> end_step(stream), the launches that end a step;
+    # known = (x0, mask, eps or None, sqrt_ah, sqrt_1m_ah) on the device: ``wd_known_blend`` between the update and the advance
+    update: Callable
     stats: dict  # what ``last_stats`` reports of the sampler itself
+
+
+class _Known(NamedTuple):
+    """What a known-region / partial-noise call is to the reverse loop (built by ``Diffusion._known_setup``, no GPU)."""
+    x0: torch.Tensor  # the known latents, fp32 [n, C*h*w] on the host
+    mask: Optional[torch.Tensor]  # fp32 [n, C*h*w] on the host, 1 = keep; None: ``start`` alone, nothing is blended
+    start: Optional[int]  # the level the loop starts from (``x0`` noised to it); None: from x_T / noise as ever
+    tau: Optional[list]  # the retained visited timesteps of a DDIM / DPM++ call (None: DDPM)
+    mode: str  # "fresh": the blend draws its noise per step; "fixed": one eps per sample
+    eps: Optional[torch.Tensor]  # the caller's fixed eps, fp32 [n, C*h*w]; None: stream WD_STREAM_KNOWN of the call's seed
+
+
+def latent_mask_from_pixels(mask_px):
+    """A keep-mask over pixels [..., H, W] (H, W multiples of 8; nonzero / True = keep) -> the fp32 keep-mask [..., H/8, W/8] over
+    the latent cells of the 8x VAE: an 8x8 min-pool, so a latent cell is kept only if every pixel it covers is."""
+    m = torch.as_tensor(mask_px)
+    if m.dim() < 2 or m.shape[-2] % 8 or m.shape[-1] % 8 or not m.shape[-2] or not m.shape[-1]:
+        raise ValueError(f"a pixel mask must be [..., H, W] with H and W multiples of 8, got {tuple(m.shape)}")
+    m = (m != 0).to(torch.float32)
+    H, W = m.shape[-2:]
+    return m.reshape(*m.shape[:-2], H // 8, 8, W // 8, 8).amin(dim=(-3, -1)).contiguous()
+
+
+def _blend_known(lib, P, known, p_args, seed, sample_offset, stream):
+    """The ``wd_known_blend`` launch of a step's tail; p_args = (t_dev, k_dev, tau, S) as the kernel takes them."""
+    x0, mask, eps, sa, sb = known
+    N.check(lib.wd_known_blend(P.x_in.data_ptr(), x0.data_ptr(), mask.data_ptr(), P.x_in.shape[0], P.x_in[0].numel(), sa.data_ptr(),
+                               sb.data_ptr(), *p_args, _dptr(eps), seed, sample_offset, stream), "wd_known_blend")
 
 
 class Diffusion:
@@ -164,13 +194,17 @@ class Diffusion:
             eps = torch.empty_like(x)
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed
             N.check(lib.wd_randn(eps.data_ptr(), x.shape[0], n, seed, 0, 1, st), "wd_randn")
-        ah = self.alpha_hat.cpu()
-        sa, sb = torch.sqrt(ah).to(x.device), torch.sqrt(1 - ah).to(x.device)
+        sa, sb = self._noise_tables(x.device)
         out = torch.empty_like(x)
         t = t.to(x.device).long().contiguous()
         N.check(lib.wd_noise_images(x.data_ptr(), eps.data_ptr(), t.data_ptr(), sa.data_ptr(), sb.data_ptr(),
                                     x.shape[0], n, out.data_ptr(), st), "wd_noise_images")
         return out, eps
+
+    def _noise_tables(self, device):
+        """sqrt(alpha_hat) and sqrt(1 - alpha_hat), the two per-t scalars of ``train.py:190-194`` in the reference's fp32 op order."""
+        ah = self.alpha_hat.cpu()
+        return torch.sqrt(ah).to(device), torch.sqrt(1 - ah).to(device)
 
     def _step_tables(self, device):
         """ca = 1/sqrt(alpha), cb = (1-alpha)/sqrt(1-alpha_hat), cs = sqrt(beta): the three per-t scalars of
@@ -262,15 +296,16 @@ class Diffusion:
         return tuple(c.float().to(device).contiguous() for c in tabs)
 
     # --------------------------------------------------------------------------------------------------
-    def _ddpm(self, calls_model=None, deterministic=False):
-        """The DDPM family: t = T-1 .. 1 (train.py:221), the model called where ``calls_model(t)`` holds (None: everywhere; a
-        step that does not call it reuses the previous predicted noise) and one entry of ``noise`` per step while t > 1,
-        counted on skipped steps too.  A step ends with ``wd_ddpm_step`` (the guided ``wd_ddpm_step_cfg`` after two
-        forwards) and ``wd_advance_timestep``."""
-        T = self.noise_steps
-        steps = [(i, calls_model is None or bool(calls_model(i)), T - 1 - i if i > 1 else None) for i in reversed(range(1, T))]
+    def _ddpm(self, calls_model=None, deterministic=False, start=None):
+        """The DDPM family: t = T-1 .. 1 (train.py:221; ``start`` .. 1 for a call that begins at that level), the model called
+        where ``calls_model(t)`` holds (None: everywhere; a step that does not call it reuses the previous predicted noise) and
+        one entry of ``noise`` per step while t > 1, counted on skipped steps too.  A step ends with ``wd_ddpm_step`` (the
+        guided ``wd_ddpm_step_cfg`` after two forwards), ``wd_known_blend`` at the level t - 1 when a region is kept, and
+        ``wd_advance_timestep``."""
+        first = self.noise_steps - 1 if start is None else int(start)
+        steps = [(i, calls_model is None or bool(calls_model(i)), first - i if i > 1 else None) for i in reversed(range(1, first + 1))]
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
             ca, cb, cs = self._step_tables(device)
             if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
                 cs = torch.zeros_like(cs)
@@ -285,20 +320,22 @@ class Diffusion:
                     N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
                                              cs.data_ptr(), P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream),
                             "wd_ddpm_step")
+                if known is not None:
+                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), None, None, 0), seed, sample_offset, stream)
                 N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream),
                         "wd_advance_timestep")
             return end_step
         # (``steps`` is T - 1 even when steps skip the model: it counts the updates)
-        return _Sampler(steps, T - 1, None, update, dict(steps=T - 1))
+        return _Sampler(steps, first, None, update, dict(steps=first))
 
     def _ddim(self, tau, eta):
         """DDIM over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows, pairs and ``noise`` are indexed by k,
-        the model is called at every step and ``noise[k]`` is read only where c5[k] != 0.  A step ends with ``wd_ddim_step``
-        and ``wd_next_timestep``."""
+        the model is called at every step and ``noise[k]`` is read only where c5[k] != 0.  A step ends with ``wd_ddim_step``,
+        ``wd_known_blend`` at the level tau[k + 1] when a region is kept, and ``wd_next_timestep``."""
         tabs = self._ddim_tables(tau, eta, "cpu")
         steps = [(k, True, k if s != 0.0 else None) for k, s in enumerate(tabs[4].tolist())]  # (host tables: no device sync)
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
             c = [t.to(device) for t in tabs]
             tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
             P.k_dev.zero_()
@@ -309,6 +346,9 @@ class Diffusion:
                 N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
                                          scale, _dptr(eps_g), n, npix, *(t.data_ptr() for t in c), P.k_dev.data_ptr(),
                                          P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddim_step")
+                if known is not None:  # at the level of tau[k + 1] (index 0 after the last entry), read from k_dev
+                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau)), seed,
+                                 sample_offset, stream)
                 N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
                                              P.t_in.data_ptr(), n, stream), "wd_next_timestep")
             return end_step
@@ -318,12 +358,12 @@ class Diffusion:
     def _dpmpp(self, tau, order, spacing=None):
         """DPM-Solver++(2M) over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows and pairs are indexed by k,
         the model is called at every step and no step draws noise.  The previous data prediction lives in a buffer of the
-        update's own, written by every step and read only where c5[k] != 0.  A step ends with ``wd_dpmpp_step`` and
-        ``wd_next_timestep``."""
+        update's own, written by every step and read only where c5[k] != 0.  A step ends with ``wd_dpmpp_step``,
+        ``wd_known_blend`` as in ``_ddim`` and ``wd_next_timestep``."""
         tabs = self._dpmpp_tables(tau, order, "cpu")
         steps = [(k, True, None) for k in range(len(tau))]
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device):
+        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
             c = [t.to(device) for t in tabs]
             tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
             x0_prev = torch.empty_like(P.x_in)  # (the first step does not read it: c5[0] == 0)
@@ -335,20 +375,89 @@ class Diffusion:
                 N.check(lib.wd_dpmpp_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
                                           scale, _dptr(eps_g), x0_prev.data_ptr(), n, npix, *(t.data_ptr() for t in c),
                                           P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
+                if known is not None:  # (x0_prev keeps the model's own data prediction: the blend changes x alone)
+                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau)), seed,
+                                 sample_offset, stream)
                 N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
                                              P.t_in.data_ptr(), n, stream), "wd_next_timestep")
             return end_step
         stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
         return _Sampler(steps, tau[0], list(tau), update, stats)
 
+    def _known_setup(self, n, known, known_mask=None, start=None, known_noise="auto", x_T=None, *, draws_noise, tau=None):
+        """The ``known`` / ``known_mask`` / ``start`` / ``known_noise`` arguments of a sampler call, validated and settled on the
+        host (no device, no library): a ``_Known``, or None where the call passes none of them.
+
+        known        fp32 [n, C, h, w], latents as the model sees them (what ``LatentCache`` holds).
+        known_mask   None, or fp32 with values in [0, 1], 1 = keep, of shape [h, w], [n, 1, h, w] or [n, C, h, w]; expanded here,
+                     once, to [n, C*h*w].
+        start        an int in [1, T-1]: the loop begins from ``known`` noised to that level.  DDPM (``tau`` None) visits
+                     start .. 1; DDIM / DPM++ visit the entries of ``tau`` (their usual schedule) that are <= start, returned as
+                     ``_Known.tau``, and the level noised to, ``_Known.start``, is the first of them.
+        known_noise  "fresh": the blend draws its noise per step (RePaint); "fixed": one eps per sample, the one that noises to
+                     ``start``; a tensor [n, C, h, w]: fixed and given; "auto": "fresh" where the call draws step noise itself
+                     (``draws_noise``: DDPM, DDIM with eta > 0), "fixed" otherwise - a deterministic sampler stays one."""
+        T = self.noise_steps
+        if known is None:
+            if known_mask is not None or start is not None or not (isinstance(known_noise, str) and known_noise == "auto"):
+                raise ValueError("known_mask, start and known_noise need the known latents (known=)")
+            return None
+        if known_mask is None and start is None:
+            raise ValueError("known needs a known_mask (the region to keep), a start level, or both")
+        h, w = self.img_size[0] // 8, self.img_size[1] // 8
+        x0 = torch.as_tensor(known)
+        if not x0.is_floating_point() or x0.dim() != 4 or x0.shape[0] != n or tuple(x0.shape[2:]) != (h, w):
+            raise ValueError(f"known must be a float tensor [{n}, C, {h}, {w}], got {x0.dtype} {tuple(x0.shape)}")
+        shape = tuple(x0.shape)
+        C = shape[1]
+        x0 = x0.detach().to(torch.float32).cpu().reshape(n, -1).contiguous()
+        mask = None
+        if known_mask is not None:
+            mask = torch.as_tensor(known_mask)
+            if mask.dtype == torch.bool:
+                mask = mask.to(torch.float32)
+            if not mask.is_floating_point() or tuple(mask.shape) not in ((h, w), (n, 1, h, w), shape):
+                raise ValueError(f"known_mask must be a float tensor [{h}, {w}], [{n}, 1, {h}, {w}] or {list(shape)}, "
+                                 f"got {mask.dtype} {tuple(mask.shape)}")
+            mask = mask.detach().to(torch.float32).cpu()
+            if not bool(((mask >= 0) & (mask <= 1)).all()):
+                raise ValueError("known_mask values must lie in [0, 1] (1 = keep)")
+            mask = mask.expand(n, C, h, w).reshape(n, -1).contiguous()
+        if start is not None:
+            if x_T is not None:
+                raise ValueError("start begins the loop from the noised known latents: it cannot be combined with x_T")
+            if isinstance(start, bool) or int(start) != start or not 1 <= int(start) <= T - 1:
+                raise ValueError(f"start must be an int in [1, {T - 1}], not {start!r}")
+            start = int(start)
+            if tau is not None:
+                tau = [t for t in tau if t <= start]
+                if not tau:
+                    raise ValueError(f"start={start} lies below every visited timestep: no step is left")
+                start = tau[0]
+        eps = None
+        if isinstance(known_noise, str):
+            if known_noise not in ("auto", "fresh", "fixed"):
+                raise ValueError(f"known_noise must be 'auto', 'fresh', 'fixed' or a tensor {list(shape)}, not {known_noise!r}")
+            mode = known_noise if known_noise != "auto" else ("fresh" if draws_noise else "fixed")
+        else:
+            eps = torch.as_tensor(known_noise)
+            if not eps.is_floating_point() or tuple(eps.shape) != shape:
+                raise ValueError(f"known_noise must be a float tensor {list(shape)}, got {eps.dtype} {tuple(eps.shape)}")
+            eps = eps.detach().to(torch.float32).cpu().reshape(n, -1).contiguous()
+            mode = "fixed"
+        return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
+
     def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None):
+                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None):
         """The one reverse loop.  Per visited step of ``sampler`` (``_ddpm`` / ``_ddim``): this step's ``noise`` entry into
         the noise buffer if it has one, ``film_prepare`` and the forward(s) when the step calls the model, the sampler's update.
         mix = (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
         step, forward f of a step reading pairs[f, its film_prepare argument]; nf = 2 ends the step with the guided update.
         record_pred: a list that receives, per model-calling step, the predictions of its forwards (and, for nf = 2, the guided
-        one) - eager launches only, like ``record``."""
+        one) - eager launches only, like ``record``.
+        known: a ``_Known``.  Its fixed eps (the caller's, or stream WD_STREAM_KNOWN of ``seed`` at the global rows) noises the
+        known latents to ``known.start``, where the loop then begins, and with a mask every step's tail blends the kept region
+        back in at the level the step reached (``wd_known_blend``, inside the captured graph)."""
         lib = N.lib()
         eng = model.engine
         nf = 0 if mix is None else int(mix[0].shape[0])
@@ -367,12 +476,32 @@ class Diffusion:
         fps = nf or self.forwards_per_step
         ncalls = sum(fwd for _, fwd, _ in sampler.steps)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        npix = P.x_in[0].numel()
+        if known is not None and known.x0.shape[1] != npix:
+            raise ValueError(f"known holds {known.x0.shape[1]} values per sample, the model's latent {npix} {tuple(P.x_in.shape[1:])}")
 
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side):
             st = side.cuda_stream
-            if x_T is not None:
+            blend = None
+            if known is not None:
+                kx0 = known.x0.to(device)
+                sa, sb = self._noise_tables(device)
+                keps = None
+                if known.start is not None or (known.mask is not None and known.mode == "fixed"):
+                    if known.eps is not None:
+                        keps = known.eps.to(device)
+                    else:
+                        keps = torch.empty_like(kx0)
+                        N.check(lib.wd_randn(keps.data_ptr(), n, npix, seed, sample_offset, N.STREAM_KNOWN, st), "wd_randn")
+                if known.mask is not None:
+                    blend = (kx0, known.mask.to(device), keps if known.mode == "fixed" else None, sa, sb)
+            if known is not None and known.start is not None:
+                level = torch.full((n,), known.start, dtype=torch.int64, device=device)
+                N.check(lib.wd_noise_images(kx0.data_ptr(), keps.data_ptr(), level.data_ptr(), sa.data_ptr(), sb.data_ptr(), n, npix,
+                                            P.x_in.data_ptr(), st), "wd_noise_images")
+            elif x_T is not None:
                 P.x_in.copy_(x_T.to(device))
             else:
                 N.check(lib.wd_randn(P.x_in.data_ptr(), n, P.x_in[0].numel(), seed, sample_offset, 0, st), "wd_randn")
@@ -384,7 +513,8 @@ class Diffusion:
             P.t_dev.fill_(sampler.t_first)
             P.t_in.fill_(sampler.t_first)
             zbuf = torch.zeros_like(P.x_in) if noise is not None else None
-            end_step = sampler.update(lib, P, (float(mix[2]), eps_g) if nf == 2 else None, zbuf, seed, sample_offset, device)
+            end_step = sampler.update(lib, P, (float(mix[2]), eps_g) if nf == 2 else None, zbuf, seed, sample_offset, device,
+                                      known=blend)
             P.run_cond(st)
             P.run_film(st)  # time MLP of every timestep; the FiLM rows follow per chunk of timesteps (P.film_prepare)
             # before the capture: the captured step only reads the table (its rows are indexed by t, or by the DDIM step index)
@@ -435,7 +565,8 @@ class Diffusion:
             if gskip is not None:
                 lib.wd_graph_destroy(gskip)
         self.last_stats = dict(sampler.stats, forwards_per_step=fps, graph=gexec is not None, seed=seed,
-                               sample_offset=sample_offset, model_calls=ncalls * (nf or 1))
+                               sample_offset=sample_offset, model_calls=ncalls * (nf or 1), known=known is not None,
+                               start=None if known is None else known.start, known_noise=None if known is None else known.mode)
         return x
 
     def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, *, sampler=None):
@@ -515,7 +646,7 @@ class Diffusion:
     @torch.no_grad()
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
-                 style_pairs=None, record_pred=None):
+                 style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto"):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
@@ -527,15 +658,22 @@ class Diffusion:
         ``args.interpolation`` - then every forward blends a freshly drawn pair of writers and, with ``cfg_scale > 0``, a step
         is two forwards and ``torch.lerp(second, first, cfg_scale)`` (``last_stats["forwards_per_step"] == 2``) - or
         ``style_pairs`` is given: the writers to blend, the same at every step (one forward per step).  ``labels`` is unused
-        in both modes.  ``record_pred`` receives every step's predictions (eager launches)."""
+        in both modes.  ``record_pred`` receives every step's predictions (eager launches).
+
+        ``known`` / ``known_mask`` / ``start`` / ``known_noise`` (``_known_setup``): keep the masked region of the latents
+        ``known`` through the whole trajectory (every step ends by blending it back in at the level the step reached, the last
+        one noise-free, so the kept region of the result IS ``known``) and / or begin at the level ``start`` from ``known``
+        noised to it instead of from noise at T - 1; ``noise`` then holds one tensor per visited step with t > 1.
+        ``last_stats`` reports ``known``, ``start`` (the level noised to) and ``known_noise`` (the resolved mode)."""
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True)
         device, tf, phosc = self._prepare("sampling", model, n, x_text, args, phoscLabels, underscore)
-        sampler = self._ddpm()
+        sampler = self._ddpm(start=None if kn is None else kn.start)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
-                              record_pred=record_pred)
+                              record_pred=record_pred, known=kn)
         finally:
             model.train()  # train.py:238 (unconditional)
         return self._finish(x, vae, args)
@@ -543,7 +681,8 @@ class Diffusion:
     @torch.no_grad()
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
                       phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
-                      use_graph=True, underscore=None, style_pairs=None):
+                      use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None, start=None,
+                      known_noise="auto"):
         """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
         ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
         deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
@@ -552,8 +691,15 @@ class Diffusion:
         Everything else follows ``sampling``: eval mode for the loop and TRAIN mode afterwards, ``vae=None`` returns latents,
         ``phoscLabels`` for the PHOSC model, ``mix_rate`` / ``style_pairs`` as there (pairs are drawn for the visited steps
         only).  ``noise``: one tensor per visited step, read only where sigma != 0; ``record`` / ``record_pred`` as in
-        ``sampling``.  ``last_stats`` carries ``sampler="ddim"``, ``steps``, ``eta`` and ``timesteps``."""
+        ``sampling``.  ``last_stats`` carries ``sampler="ddim"``, ``steps``, ``eta`` and ``timesteps``.
+        ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling``; with ``start`` the call visits the entries of
+        its usual schedule that are <= start (``steps`` and ``timesteps`` of ``last_stats`` are the retained ones, FiLM rows,
+        pairs and ``noise`` are indexed by them) and the first of them is the level noised to.  With ``eta = 0`` the default
+        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``."""
         tau = self.ddim_timesteps(steps, timesteps)
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau)
+        if kn is not None:
+            tau = kn.tau
         if noise is not None and len(noise) != len(tau):
             raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
         device, tf, phosc = self._prepare("sampling_ddim", model, n, x_text, args, phoscLabels, underscore)
@@ -562,7 +708,8 @@ class Diffusion:
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
-                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred)
+                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
+                              known=kn)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
@@ -570,7 +717,8 @@ class Diffusion:
     @torch.no_grad()
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
                        mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
-                       record_pred=None, use_graph=True, underscore=None, style_pairs=None):
+                       record_pred=None, use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None,
+                       start=None, known_noise="auto"):
         """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
         ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
         the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
@@ -579,17 +727,22 @@ class Diffusion:
         Philox key of ``sampling``), and there is no ``noise``.  The last step lands on index 0 of the schedule, as in
         ``sampling_ddim``, and everything else follows it too: eval mode for the loop and TRAIN mode afterwards, ``vae=None``
         returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
-        ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``."""
+        ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``.
+        ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling_ddim`` (the default noise is the fixed eps: no
+        step draws); the first retained step is first order, like the first step of any call."""
         tau = self.dpmpp_timesteps(steps, spacing, timesteps)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=False, tau=tau)
+        if kn is not None:
+            tau = kn.tau
         device, tf, phosc = self._prepare("sampling_dpmpp", model, n, x_text, args, phoscLabels, underscore)
         sampler = self._dpmpp(tau, order, None if timesteps is not None else spacing)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, seed=seed, sample_offset=sample_offset,
-                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred)
+                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)

@@ -13,6 +13,8 @@ depend on the batch size or the number of ranks.  Host-side pieces restated from
   * ``regenerate``    - the loop; ``vae=None`` writes latents (``.npy``), a duck-typed VAE (``vae.decode(z).sample``) PNGs.
   * ``--encode_images`` - the other direction: the gt rows' images through the VAE encoder into a latent cache
                         (``latents.build_latent_cache``), then exit.
+  * ``--init_latents`` - regenerate FROM such a cache: ``--keep_cols A:B`` keeps those latent columns of every row's own latent
+                        and re-draws the rest, ``--start T`` begins from the latent noised to level T (``regenerate(known=...)``).
   * ``interpolate``   - one strip per gt row: the row's word in ``mix_steps`` styles from writer ``s1`` to writer ``s2``
                         (``sampling.py --interpolation --mix_rate`` renders one such blend of two random writers per call).
 """
@@ -93,6 +95,27 @@ def write_png(path: str, img: np.ndarray) -> None:
         f.write(png)
 
 
+def keep_cols_mask(keep_cols, h: int, w: int) -> torch.Tensor:
+    """fp32 [h, w] keep-mask of the latent columns ``a <= column < b`` (``keep_cols = (a, b)``, a half-open range within w)."""
+    try:
+        a, b = (int(v) for v in keep_cols)
+    except (TypeError, ValueError):
+        raise ValueError(f"keep_cols must be a pair (a, b) of latent columns, not {keep_cols!r}") from None
+    if not 0 <= a < b <= w:
+        raise ValueError(f"keep_cols must be a non-empty half-open range within the {w} latent columns, not {a}:{b}")
+    mask = torch.zeros(h, w, dtype=torch.float32)
+    mask[:, a:b] = 1.0
+    return mask
+
+
+def _known_latent(known, image: str) -> torch.Tensor:
+    """The cached latent of a gt row: under the image name itself or, as ``build_latent_cache`` writes it, with ``.png``."""
+    for key in (image, image + ".png"):
+        if key in known:
+            return known[key]
+    raise KeyError(f"no latent of gt row image {image!r} in the known-latent cache")
+
+
 def _check_sampler(sampler: str, skip_steps=False) -> None:
     if sampler not in ("ddpm", "ddim", "dpmpp"):
         raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', not {sampler!r}")
@@ -104,7 +127,8 @@ def _check_sampler(sampler: str, skip_steps=False) -> None:
 def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: Dict[str, int], args, vae=None,
                batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
                world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
-               ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr"):
+               ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
+               known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto"):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -113,14 +137,31 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``UNetModelPhosc`` (``args.phosc == 1``).  ``mix_rate`` is handed to the sampler as ``full_sampling.py:171`` hands it: it has
     an effect on a model built with ``args.interpolation`` only.  ``sampler="ddim"``: ``Diffusion.sampling_ddim`` over
     ``ddim_steps`` timesteps with ``eta`` instead of the full ``sampling`` loop; ``sampler="dpmpp"``: ``Diffusion.sampling_dpmpp``
-    over ``dpmpp_steps`` timesteps at ``dpmpp_order`` with ``dpmpp_spacing``."""
+    over ``dpmpp_steps`` timesteps at ``dpmpp_order`` with ``dpmpp_spacing``.
+
+    ``known`` (a ``LatentCache``, or any mapping image name -> latent [C, h, w]): every gt row is regenerated from its own cached
+    latent - ``keep_cols = (a, b)`` keeps the latent columns a <= column < b and re-draws the rest, ``start`` begins the loop
+    from the latent noised to that level, ``known_noise`` as in ``Diffusion.sampling``.  A row whose latent is missing raises
+    KeyError naming it, before anything is sampled.  Not with ``skip_steps``."""
     _check_sampler(sampler, skip_steps)
+    if known is None and (keep_cols is not None or start is not None):
+        raise ValueError("keep_cols and start need the known latents (known=)")
+    if known is not None:
+        if skip_steps:
+            raise ValueError("known latents are not supported by the step-skipping sampler (skip_steps)")
+        if keep_cols is None and start is None:
+            raise ValueError("known needs keep_cols (the latent columns to keep), a start level, or both")
     r0, w0, _ = env_rank_world()
     rank = r0 if rank is None else rank
     world = w0 if world is None else world
-    start, count = shard_range(len(rows), rank, world)
-    mine = rows[start:start + count]
+    first, count = shard_range(len(rows), rank, world)
+    mine = rows[first:first + count]
     outs = []
+    kmask = None
+    if known is not None:
+        if keep_cols is not None:
+            kmask = keep_cols_mask(keep_cols, diffusion.img_size[0] // 8, diffusion.img_size[1] // 8)
+        latents = [_known_latent(known, image) for _, image, _ in mine]  # (all of them first: a missing row fails up front)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
     for b0 in range(0, count, batch):
@@ -128,7 +169,9 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         words = [t for _, _, t in chunk]
         labels = torch.tensor([wr_dict[s] for s, _, _ in chunk], dtype=torch.int64)
         phosc = torch.stack([phosc_of(wd) for wd in words]) if phosc_of is not None else None
-        kw = dict(seed=seed, sample_offset=start + b0, mix_rate=mix_rate)
+        kw = dict(seed=seed, sample_offset=first + b0, mix_rate=mix_rate)
+        if known is not None:
+            kw.update(known=torch.stack(latents[b0:b0 + batch]), known_mask=kmask, start=start, known_noise=known_noise)
         if sampler == "ddim":
             res = diffusion.sampling_ddim(model, vae, len(chunk), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
         elif sampler == "dpmpp":
@@ -148,7 +191,7 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                 else:
                     arr = (item.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).numpy()
                     write_png(os.path.join(out_dir, f"{image}.png"), arr if arr.shape[2] == 3 else arr[:, :, 0])
-    return start, (torch.cat(outs) if outs else torch.empty(0))
+    return first, (torch.cat(outs) if outs else torch.empty(0))
 
 
 @torch.no_grad()
@@ -252,6 +295,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--latents_out", default=None, metavar="FILE", help="--encode_images: the container to write (.safetensors / .npz)")
     ap.add_argument("--latent_mode", default="sample", choices=["sample", "mode"],
                     help="--encode_images: a posterior draw per image (keyed by --seed and the row index) or the posterior mean")
+    ap.add_argument("--init_latents", default=None, metavar="FILE",
+                    help="a latent cache (--latents_out of an --encode_images run): every gt row is regenerated from its own latent, "
+                         "as --keep_cols and / or --start say")
+    ap.add_argument("--keep_cols", default=None, metavar="A:B",
+                    help="--init_latents: keep the latent columns A <= column < B of the 32 and re-draw the rest")
+    ap.add_argument("--start", type=int, default=None, metavar="T",
+                    help="--init_latents: begin from the latent noised to level T (1 .. noise_steps - 1) instead of from noise")
     return ap
 
 
@@ -264,6 +314,24 @@ def parse_args(argv=None):
         ap.error(f"--ddim_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
     if a.sampler == "dpmpp" and not 1 <= a.dpmpp_steps <= a.noise_steps - 1:
         ap.error(f"--dpmpp_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.init_latents is None and (a.keep_cols is not None or a.start is not None):
+        ap.error("--keep_cols and --start need --init_latents (the latents to start from)")
+    if a.init_latents is not None:
+        if a.skip_steps:
+            ap.error("--skip_steps 1 does not take --init_latents / --keep_cols / --start")
+        if a.style_pair is not None:
+            ap.error("--style_pair strips do not take --init_latents / --keep_cols / --start")
+        if a.keep_cols is None and a.start is None:
+            ap.error("--init_latents needs --keep_cols A:B, --start T, or both")
+        if a.start is not None and not 1 <= a.start <= a.noise_steps - 1:
+            ap.error(f"--start must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.keep_cols is not None:
+        parts = a.keep_cols.split(":")
+        if len(parts) != 2 or not all(p.strip().isdigit() for p in parts):
+            ap.error(f"--keep_cols takes A:B, two latent column indices, not {a.keep_cols!r}")
+        a.keep_cols = (int(parts[0]), int(parts[1]))
+        if not 0 <= a.keep_cols[0] < a.keep_cols[1] <= 32:
+            ap.error(f"--keep_cols must be a non-empty half-open range within the 32 latent columns, not {parts[0]}:{parts[1]}")
     return ap, a
 
 
@@ -316,10 +384,15 @@ def main(argv=None):
                                  dpmpp_spacing=a.dpmpp_spacing)
         print(f"[rank {rank}/{world}] strips of rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
         return
+    known = None
+    if a.init_latents:
+        from .latents import LatentCache
+        known = LatentCache(a.init_latents)
     start, res = regenerate(ema_model, diffusion, rows, wr, args, vae=vae, batch=a.batch_size,
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
                             phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
-                            dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing)
+                            dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing, known=known,
+                            keep_cols=a.keep_cols, start=a.start)
     print(f"[rank {rank}/{world}] rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
 
 
