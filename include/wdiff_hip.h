@@ -635,6 +635,27 @@ int wd_repack_multi(const void* table, int nentries, int64_t total_chunks, void*
 int wd_mse_loss(const float* pred, const float* target, int64_t n, float* grad, float* loss, double* scratch,
                 int scratch_len, void* stream);
 
+/* Weighted, masked per-sample squared error and its gradient (two launches, no atomics, fixed summation order: the same bits on
+ * every run).  pred, target, grad: fp32 [batch][n_per_sample]; mask: NULL, or fp32 [batch][n_per_sample] with values in [0, 1];
+ * t: int64 [batch] on the device; weights: NULL (w_b = 1), or fp32 [T] with w_b = weights[t_b].  No product is contracted:
+ *   d   = pred - target                                   in fp32
+ *   M_b = sum_i (double)m_bi                              (n_per_sample without a mask)
+ *   S_b = sum_i (double)m_bi * ((double)d * (double)d)    both sums in double
+ *   l_b = (float)(S_b / M_b)                              the UNWEIGHTED masked mean of sample b -> sample_loss[b] (optional)
+ *   c_b = (float)(2.0 * (double)w_b / ((double)batch * M_b))
+ *   grad = c_b * d without a mask, c_b * (m * d) with one, each product rounded on its own (grad may be NULL)
+ *   loss = (float)((sum_b (double)w_b * (S_b / M_b)) / batch), b ascending
+ * A sample with M_b == 0 contributes nothing: l_b = 0, its gradient row is 0 (not NaN) and the histogram skips it; otherwise NaN
+ * and inf propagate by plain arithmetic.  hist: NULL, or double [nbins][2] = (sum, count), ACCUMULATED INTO: for b ascending,
+ * bin = (t_b * nbins) / T in integers, hist[bin][0] += (double)l_b (the rounded fp32 value), hist[bin][1] += 1.
+ * scratch: >= 2 * batch doubles.  With weights == NULL and mask == NULL grad is wd_mse_loss's, bit for bit.
+ * t outside [0, T) is a precondition (the callers check host timesteps).  The function neither allocates nor synchronises.
+ * WD_EINVAL (nothing launched): pred, target, loss or scratch NULL; t NULL or T < 1 with weights or hist; nbins < 1 with hist;
+ * batch < 1; n_per_sample < 4 or not a multiple of 4; pred / target / mask / grad not 16-byte aligned. */
+int wd_weighted_mse_loss(const float* pred, const float* target, const float* mask, int batch, int n_per_sample,
+                         const int64_t* t, const float* weights, int T, float* grad, float* loss, float* sample_loss,
+                         double* hist, int nbins, double* scratch, void* stream);
+
 /* ---- backward building blocks (training step, train.py:290: loss.backward()).  Contractions reuse wd_gemm:
  *  d(input)  = wd_gemm over d(output) planes with the mirrored gather table and transposed weights;
  *  d(weight) = wd_gemm over the token dimension, operands = the transposed planes made by wd_transpose_planes. */

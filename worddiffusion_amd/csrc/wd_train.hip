@@ -193,6 +193,140 @@ __global__ __launch_bounds__(256) void grad_accumulate_scalar(float* __restrict_
     }
 }
 
+// ---- weighted, masked per-sample squared error (wd_weighted_mse_loss; specification in include/wdiff_hip.h) --------------------
+// Stage 1: one workgroup per sample.  With a mask the gradient scale needs M_b = sum(m) first, so the mask row is summed in a
+// pass of its own (the main pass reads it again from L2; a sample is 4 KB at the training shape).  Every lane's order is fixed by
+// n_per_sample alone and the LDS tree is fixed, so S_b and M_b are the same bits on every run.  out2[b] = S_b, out2[batch + b] = M_b.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void wmse_stage1(const float* __restrict__ pred, const float* __restrict__ target,
+                                                   const float* __restrict__ mask, int batch, int n4,
+                                                   const int64_t* __restrict__ t, const float* __restrict__ weights,
+                                                   float* __restrict__ grad, double* __restrict__ out2) {
+    __shared__ double sh[256];
+    const int b = blockIdx.x;
+    const int64_t row = (int64_t)b * n4;
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(pred) + row;
+    const float4* __restrict__ e4 = reinterpret_cast<const float4*>(target) + row;
+    const float4* __restrict__ m4 = MASKED ? reinterpret_cast<const float4*>(mask) + row : nullptr;
+    float4* __restrict__ g4 = grad ? reinterpret_cast<float4*>(grad) + row : nullptr;
+    double M = 4.0 * (double)n4;
+    if constexpr (MASKED) {
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const float4 m = m4[i];
+            acc += (double)m.x;
+            acc += (double)m.y;
+            acc += (double)m.z;
+            acc += (double)m.w;
+        }
+        sh[threadIdx.x] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+            __syncthreads();
+        }
+        M = sh[0];
+        __syncthreads();  // (sh is reused below)
+    }
+    const float w = weights ? weights[t[b]] : 1.0f;
+    // M == 0: the sample has no cell to learn from; its gradient row is 0 whatever pred holds
+    const bool live = M != 0.0;
+    const float c = live ? (float)(2.0 * (double)w / ((double)batch * M)) : 0.0f;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 p = p4[i], e = e4[i];
+        float4 d;
+        d.x = p.x - e.x;
+        d.y = p.y - e.y;
+        d.z = p.z - e.z;
+        d.w = p.w - e.w;
+        if constexpr (MASKED) {
+            const float4 m = m4[i];
+            acc += (double)m.x * ((double)d.x * (double)d.x);
+            acc += (double)m.y * ((double)d.y * (double)d.y);
+            acc += (double)m.z * ((double)d.z * (double)d.z);
+            acc += (double)m.w * ((double)d.w * (double)d.w);
+            d.x = m.x * d.x;
+            d.y = m.y * d.y;
+            d.z = m.z * d.z;
+            d.w = m.w * d.w;
+        } else {
+            acc += (double)d.x * (double)d.x;
+            acc += (double)d.y * (double)d.y;
+            acc += (double)d.z * (double)d.z;
+            acc += (double)d.w * (double)d.w;
+        }
+        if (g4) {
+            float4 g;
+            g.x = live ? c * d.x : 0.0f;
+            g.y = live ? c * d.y : 0.0f;
+            g.z = live ? c * d.z : 0.0f;
+            g.w = live ? c * d.w : 0.0f;
+            g4[i] = g;
+        }
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out2[b] = sh[0];
+        out2[batch + b] = M;
+    }
+}
+
+// Stage 2: one workgroup, 256 samples at a time.  Lane l forms sample base + l's mean, weighted term and bin; then lane 0 adds the
+// terms with b ascending, and lane j updates the bins j, j + 256, ... each walking the samples with b ascending - the bins do not
+// interact, so this is the recurrence "for b ascending: hist[bin_b] += (l_b, 1)" of the specification.
+__global__ __launch_bounds__(256) void wmse_stage2(const double* __restrict__ in2, int batch, const int64_t* __restrict__ t,
+                                                   const float* __restrict__ weights, int T, float* __restrict__ loss,
+                                                   float* __restrict__ sample_loss, double* __restrict__ hist, int nbins) {
+    __shared__ double term[256];
+    __shared__ float mean[256];
+    __shared__ int bin[256];  // -1: the sample has M_b == 0 and is skipped
+    double total = 0.0;
+    for (int base = 0; base < batch; base += 256) {
+        const int b = base + threadIdx.x;
+        const int cnt = batch - base < 256 ? batch - base : 256;
+        if (b < batch) {
+            const double S = in2[b], M = in2[batch + b];
+            const bool live = M != 0.0;
+            const double q = live ? S / M : 0.0;
+            const float l = (float)q;
+            int64_t tb = 0;
+            if (weights || hist) tb = t[b];
+            const float w = weights ? weights[tb] : 1.0f;
+            term[threadIdx.x] = (double)w * q;
+            mean[threadIdx.x] = l;
+            bin[threadIdx.x] = !live ? -1 : hist ? (int)((tb * (int64_t)nbins) / (int64_t)T) : 0;
+            if (sample_loss) sample_loss[b] = l;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < cnt; ++i)
+                if (bin[i] >= 0) total += term[i];
+        if (hist)
+            for (int k = threadIdx.x; k < nbins; k += 256) {
+                double s = hist[2 * (int64_t)k], c = hist[2 * (int64_t)k + 1];
+                bool hit = false;
+                for (int i = 0; i < cnt; ++i)
+                    if (bin[i] == k) {
+                        s += (double)mean[i];
+                        c += 1.0;
+                        hit = true;
+                    }
+                if (hit) {
+                    hist[2 * (int64_t)k] = s;
+                    hist[2 * (int64_t)k + 1] = c;
+                }
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = (float)(total / (double)batch);
+}
+
 }  // namespace
 
 extern "C" int wd_adamw_table_entry_bytes(void) { return (int)sizeof(wd_adamw_table_entry); }
@@ -284,5 +418,27 @@ extern "C" int wd_mse_loss(const float* pred, const float* target, int64_t n, fl
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(mse_stage1, dim3(nb), dim3(256), 0, st, pred, target, n, (float)(2.0 / (double)n), grad, scratch);
     hipLaunchKernelGGL(mse_stage2, dim3(1), dim3(64), 0, st, scratch, nb, n, loss);
+    return wd_check_launch();
+}
+
+extern "C" int wd_weighted_mse_loss(const float* pred, const float* target, const float* mask, int batch, int n_per_sample,
+                                    const int64_t* t, const float* weights, int T, float* grad, float* loss, float* sample_loss,
+                                    double* hist, int nbins, double* scratch, void* stream) {
+    if (!pred || !target || !loss || !scratch || batch < 1 || n_per_sample < 4 || (n_per_sample & 3)) return WD_EINVAL;
+    if ((weights || hist) && (!t || T < 1)) return WD_EINVAL;
+    if (hist && nbins < 1) return WD_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(mask) |
+         reinterpret_cast<uintptr_t>(grad)) & 15u)
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    const int n4 = n_per_sample >> 2;
+    if (mask)
+        hipLaunchKernelGGL(wmse_stage1<true>, dim3((unsigned)batch), dim3(256), 0, st, pred, target, mask, batch, n4, t, weights,
+                           grad, scratch);
+    else
+        hipLaunchKernelGGL(wmse_stage1<false>, dim3((unsigned)batch), dim3(256), 0, st, pred, target, mask, batch, n4, t, weights,
+                           grad, scratch);
+    hipLaunchKernelGGL(wmse_stage2, dim3(1), dim3(256), 0, st, scratch, batch, t, weights, T, loss, sample_loss, hist, nbins);
     return wd_check_launch();
 }

@@ -16,6 +16,7 @@ step is executed (``forwards_per_step = 2`` re-enables the literal behaviour for
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import random
 from typing import Callable, List, NamedTuple, Optional, Sequence
@@ -200,6 +201,50 @@ class Diffusion:
         N.check(lib.wd_noise_images(x.data_ptr(), eps.data_ptr(), t.data_ptr(), sa.data_ptr(), sb.data_ptr(),
                                     x.shape[0], n, out.data_ptr(), st), "wd_noise_images")
         return out, eps
+
+    def min_snr_weights(self, gamma=5.0):
+        """Min-SNR-gamma loss weights for eps-prediction (Hang et al. 2023): fp32 [noise_steps] on the host,
+        w_t = min(SNR_t, gamma) / SNR_t with SNR_t = alpha_hat_t / (1 - alpha_hat_t).  Evaluated in float64 from the fp32 betas
+        (alpha_hat recomputed in float64 as in ``_ddim_tables``) and rounded once; exactly 1 wherever SNR_t <= gamma."""
+        gamma = float(gamma)
+        if not (math.isfinite(gamma) and gamma > 0.0):
+            raise ValueError(f"gamma must be a finite number > 0, got {gamma!r}")
+        ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
+        snr = ah / (1.0 - ah)
+        return (torch.clamp(snr, max=gamma) / snr).float().contiguous()
+
+    @torch.no_grad()
+    def eval_loss(self, model, latents, text_features, labels, t, noise=None, seed=None, loss_mask=None, phoscLabels=None):
+        """Held-out loss: ``noise_images(latents, t)``, the model's inference forward, then the per-sample masked squared error
+        (``optim.weighted_mse_loss`` without a gradient) -> device fp32 [B], sample b's UNWEIGHTED mean over its mask (weights
+        are the caller's to apply: ``min_snr_weights()[t]``).  The model runs in ``eval()`` for the call and every module's
+        ``training`` flag is put back afterwards; no weight is updated and no generator is drawn from: the noise is ``noise``, or
+        the device Philox stream of ``seed`` (0 when neither is given, so a held-out set scores the same from call to call).
+        ``t``: an integer tensor [B] in [0, noise_steps); ``loss_mask``: the known-region shapes, values in [0, 1]."""
+        from .optim import check_timesteps, expand_loss_mask, weighted_mse_loss
+        if latents.dim() != 4:
+            raise ValueError(f"latents must be [B, C, h, w], got {tuple(latents.shape)}")
+        t = check_timesteps(t, latents.shape[0], self.noise_steps)
+        if loss_mask is not None:
+            loss_mask = expand_loss_mask(loss_mask, latents.shape).reshape(latents.shape)
+        if not latents.is_cuda:
+            raise N.NativeError("Diffusion.eval_loss runs on the GPU only (no CPU fallback)")
+        dev = latents.device
+        if noise is not None:
+            noise = noise.to(dev).contiguous().float()
+        x_t, eps = self.noise_images(latents, t, eps=noise, seed=0 if seed is None else int(seed))
+        flags = [(m, m.training) for m in model.modules()]
+        model.eval()
+        try:
+            kw = dict(timesteps=t.to(dev), context=text_features.to(dev), y=None if labels is None else labels.to(dev))
+            if getattr(model, "variant", "base") == "phosc":
+                pred = model(x_t, None if phoscLabels is None else phoscLabels.to(dev), **kw)
+            else:
+                pred = model(x_t, **kw)
+        finally:
+            for m, flag in flags:
+                m.training = flag
+        return weighted_mse_loss(pred, eps, mask=loss_mask, want_grad=False)[2]
 
     def _noise_tables(self, device):
         """sqrt(alpha_hat) and sqrt(1 - alpha_hat), the two per-t scalars of ``train.py:190-194`` in the reference's fp32 op order."""

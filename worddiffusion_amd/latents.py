@@ -157,22 +157,50 @@ class LatentCache:
         raise KeyError(name)
 
 
+def loss_mask_columns(width_px: int, h: int, w: int, pad_weight: float) -> torch.Tensor:
+    """The loss mask [1, h, w] of a word image whose content is ``width_px`` pixels wide and left-aligned, the rest padding: 1 over
+    the first ceil(width_px / 8) latent columns (a column that holds any content counts whole; at most w), ``pad_weight``
+    elsewhere."""
+    if isinstance(width_px, bool) or int(width_px) != width_px or width_px < 0:
+        raise ValueError(f"a content width must be an integer number of pixels >= 0, got {width_px!r}")
+    cols = min((int(width_px) + 7) // 8, w)
+    m = torch.full((1, h, w), float(pad_weight), dtype=torch.float32)
+    m[..., :cols] = 1.0
+    return m
+
+
 class CachedLatentDataset:
     """``rows``: gt rows ``(writer id, image name, transcription)`` (``driver.read_gt``); ``wr_dict``: writer id -> class index
     (``driver.writer_dict``); ``cache``: ``LatentCache``.  The image key is ``image + suffix`` with ``suffix='.png'`` as in
     ``train.py:378`` / the dictionary keys of the reference.  ``underscore`` selects the ``'_'`` alphabet of the
     ModifyCondition scripts.  Rows whose latent is missing are dropped up front when ``skip_missing`` (the reference would
-    raise KeyError from ``__getitem__`` in the middle of an epoch)."""
+    raise KeyError from ``__getitem__`` in the middle of an epoch).
+
+    ``width_of(image name) -> content width in pixels``: every item and batch then carries a ``"loss_mask"`` ([1, h, w] /
+    [B, 1, h, w], ``loss_mask_columns``) that ``train_epoch`` hands to the step: 1 over the latent columns the word covers,
+    ``pad_weight`` over the blank padding to its right.  ``pad_weight`` in [0, 1] is then required and has no default: 0 leaves
+    the padding unconstrained, so samples may put ink there, and which value trains best has not been measured."""
 
     def __init__(self, rows: Sequence[Tuple[str, str, str]], wr_dict: Mapping[str, int], cache: LatentCache,
                  suffix: str = ".png", underscore: bool = False, phosc_of: Optional[Callable[[str], torch.Tensor]] = None,
-                 skip_missing: bool = False, max_items: Optional[int] = None):
+                 skip_missing: bool = False, max_items: Optional[int] = None,
+                 width_of: Optional[Callable[[str], int]] = None, pad_weight: Optional[float] = None):
+        if width_of is not None:
+            if pad_weight is None:
+                raise ValueError("width_of needs pad_weight, the loss weight of the padding in [0, 1] (there is no default: 0 "
+                                 "leaves the padding unconstrained, and no value has been measured to train best)")
+            if isinstance(pad_weight, bool) or not 0.0 <= float(pad_weight) <= 1.0:
+                raise ValueError(f"pad_weight must lie in [0, 1], got {pad_weight!r}")
+        elif pad_weight is not None:
+            raise ValueError("pad_weight weighs the padding that width_of locates: pass width_of too")
+        self.width_of, self.pad_weight = width_of, None if pad_weight is None else float(pad_weight)
         self.cache, self.wr_dict, self.suffix, self.phosc_of = cache, wr_dict, suffix, phosc_of
         self._pad = label_padding_underscore if underscore else label_padding
         rows = list(rows[:max_items] if max_items is not None else rows)  # train.py:369 keeps the first 1000 lines
         if skip_missing:
             rows = [r for r in rows if (r[1] + suffix) in cache]
         self.rows = rows
+        self._pre_mask = None  # loss masks [N,1,h,w] once preloaded (width_of)
         self._pre = None  # (latents [N,C,H,W], words [N,L], s_id [N][, phosc [N,P]]) once preloaded
 
     def preload(self, max_bytes: int = 2 << 30) -> bool:
@@ -191,6 +219,7 @@ class CachedLatentDataset:
                torch.tensor([it["s_id"] for it in items], dtype=torch.int64)]
         if self.phosc_of is not None:
             pre.append(torch.stack([it["phosc"] for it in items]))
+        self._pre_mask = torch.stack([it["loss_mask"] for it in items]) if self.width_of is not None else None
         self._pre = pre
         return True
 
@@ -205,6 +234,9 @@ class CachedLatentDataset:
                     s_id=int(self.wr_dict[s_id]), label=label)
         if self.phosc_of is not None:
             item["phosc"] = torch.as_tensor(self.phosc_of(label)).to(torch.int64)
+        if self.width_of is not None:
+            item["loss_mask"] = loss_mask_columns(self.width_of(name), item["latent"].shape[-2], item["latent"].shape[-1],
+                                                  self.pad_weight)
         return item
 
     def batches(self, batch_size: int, shuffle: bool = True, seed: int = 0, epoch: int = 0, rank: int = 0, world: int = 1,
@@ -229,6 +261,8 @@ class CachedLatentDataset:
                            s_id=self._pre[2].index_select(0, sel))
                 if self.phosc_of is not None:
                     out["phosc"] = self._pre[3].index_select(0, sel)
+                if self._pre_mask is not None:
+                    out["loss_mask"] = self._pre_mask.index_select(0, sel)
             else:
                 items = [self[int(i)] for i in idx]
                 out = dict(image_names=[it["image_name"] for it in items], labels=[it["label"] for it in items],
@@ -236,8 +270,10 @@ class CachedLatentDataset:
                            s_id=torch.tensor([it["s_id"] for it in items], dtype=torch.int64))
                 if self.phosc_of is not None:
                     out["phosc"] = torch.stack([it["phosc"] for it in items])
+                if self.width_of is not None:
+                    out["loss_mask"] = torch.stack([it["loss_mask"] for it in items])
             if pin and torch.cuda.is_available():
-                for k in ("latents", "words", "s_id", "phosc"):
+                for k in ("latents", "words", "s_id", "phosc", "loss_mask"):
                     if k in out:
                         out[k] = out[k].pin_memory()
             yield out
@@ -256,7 +292,11 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
 
     ``vae``: the dataset's batches carry pixels (``"images"``: float [B, 3, H, W] in [-1, 1]) instead of ``"latents"`` and every
     batch is encoded first, ``vae.encode(images).latent_dist.sample() * 0.18215`` (``train.py:277-278``), with the noise of an
-    image keyed by ``(seed, position in the epoch's global image sequence)``."""
+    image keyed by ``(seed, position in the epoch's global image sequence)``.
+
+    A batch that carries a ``"loss_mask"`` (``CachedLatentDataset(width_of=..., pad_weight=...)``) hands it to the step
+    (``TrainStep.__call__(loss_mask=...)``); with ``TrainStep(loss_bins > 0)`` the result also holds ``loss_by_timestep``, the
+    step's histogram as it stands at the end of the epoch (it is the step's: ``reset_loss_by_timestep()`` empties it)."""
     import queue
     import threading
     if hasattr(dataset, "preload"):
@@ -274,6 +314,9 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
                     break
                 if eng is not None:
                     eng.check_ids(b["words"], b["s_id"], b.get("phosc"))
+                    m = b.get("loss_mask")
+                    if m is not None and not bool(((m >= 0) & (m <= 1)).all()):
+                        raise ValueError("loss_mask values must lie in [0, 1]")
                 q.put(b)
             q.put(None)
         except BaseException as e:  # surfaced in the consumer
@@ -296,7 +339,10 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
         words = b["words"].to(device, non_blocking=True)
         s_id = b["s_id"].to(device, non_blocking=True)
         ph = b["phosc"].to(device, non_blocking=True) if "phosc" in b else None
-        loss = step(lat, words, s_id, phoscLabels=ph, **({"check": False} if eng is not None else {}))
+        kw = {"check": False} if eng is not None else {}
+        if b.get("loss_mask") is not None:
+            kw["loss_mask"] = b["loss_mask"].to(device, non_blocking=True)
+        loss = step(lat, words, s_id, phoscLabels=ph, **kw)
         total = loss.clone() if total is None else total + loss
         nb += 1
         if on_batch is not None:
@@ -304,4 +350,7 @@ def train_epoch(step, dataset: CachedLatentDataset, batch_size: int, device, epo
         i += 1
     th.join()
     mean = float(total.item()) / nb if nb else float("nan")
-    return dict(batches=nb, images=nb * batch_size, mean_loss=mean)
+    out = dict(batches=nb, images=nb * batch_size, mean_loss=mean)
+    if getattr(step, "loss_bins", 0) > 0:
+        out["loss_by_timestep"] = step.loss_by_timestep()
+    return out

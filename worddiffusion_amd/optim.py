@@ -27,6 +27,101 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, want_grad: bool = True):
     return loss, grad
 
 
+def expand_loss_mask(mask, shape, check_values: bool = True) -> torch.Tensor:
+    """A loss mask under the known-region rules (``Diffusion._known_setup``): a float (or bool) tensor of shape ``[h, w]``,
+    ``[B, 1, h, w]`` or ``[B, C, h, w]`` for predictions of ``shape = (B, C, h, w)``, values in [0, 1] -> fp32 ``[B, C*h*w]`` on the
+    mask's own device.  Host arithmetic only (``check_values`` on a device tensor costs one small synchronisation)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 4:
+        raise ValueError(f"a loss mask needs predictions of shape [B, C, h, w], got {list(shape)}")
+    B, C, h, w = shape
+    mask = torch.as_tensor(mask)
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.float32)
+    if not mask.is_floating_point() or tuple(mask.shape) not in ((h, w), (B, 1, h, w), shape):
+        raise ValueError(f"loss_mask must be a float tensor [{h}, {w}], [{B}, 1, {h}, {w}] or {list(shape)}, "
+                         f"got {mask.dtype} {tuple(mask.shape)}")
+    mask = mask.detach().to(torch.float32)
+    if check_values and not bool(((mask >= 0) & (mask <= 1)).all()):  # (NaN fails both comparisons)
+        raise ValueError("loss_mask values must lie in [0, 1]")
+    return mask.expand(B, C, h, w).reshape(B, -1).contiguous()
+
+
+def check_loss_weights(weights, noise_steps: int) -> torch.Tensor:
+    """A per-timestep weight table: a float tensor ``[noise_steps]``, every value finite and >= 0 -> fp32 on the host."""
+    w = torch.as_tensor(weights)
+    if not w.is_floating_point() or tuple(w.shape) != (int(noise_steps),):
+        raise ValueError(f"loss weights must be a float tensor [{int(noise_steps)}], got {w.dtype} {tuple(w.shape)}")
+    w = w.detach().to(torch.float32).cpu().contiguous()
+    if not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError("loss weights must be finite and >= 0")
+    return w
+
+
+def check_timesteps(t, batch: int, noise_steps: int) -> torch.Tensor:
+    """Timesteps that index a per-timestep table: an integer tensor ``[batch]`` with every value in [0, noise_steps)."""
+    t = torch.as_tensor(t)
+    if t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != (int(batch),):
+        raise ValueError(f"t must be an integer tensor [{int(batch)}], got {t.dtype} {tuple(t.shape)}")
+    if not bool(((t >= 0) & (t < int(noise_steps))).all()):
+        raise ValueError(f"every timestep must lie in [0, {int(noise_steps)})")
+    return t
+
+
+def weighted_mse_loss(pred: torch.Tensor, target: torch.Tensor, t: Optional[torch.Tensor] = None,
+                      weights: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, want_grad: bool = True):
+    """Per-sample weighted, masked squared error (``wd_weighted_mse_loss``; DESIGN.md "Weighted training loss"):
+
+        loss = mean_b weights[t_b] * sum_i m_bi (pred - target)_bi^2 / sum_i m_bi
+
+    -> (loss [1], d loss / d pred or None, sample_loss [B]): device tensors, ``sample_loss`` the UNWEIGHTED masked mean of every
+    sample.  ``pred`` / ``target``: [B, ...] with a multiple of 4 elements per sample; ``weights``: a float tensor [T], finite and
+    >= 0, indexed by ``t`` (an integer tensor [B] in [0, T), required with it); ``mask``: the known-region shapes ([h, w],
+    [B, 1, h, w] or pred's own) with values in [0, 1] - a sample whose mask is all zero has loss 0 and a zero gradient row.
+    Arguments are validated before anything touches the device; the kernel runs on the GPU only."""
+    if pred.dim() < 2 or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"pred and target must share a shape [B, ...], got {tuple(pred.shape)} and {tuple(target.shape)}")
+    B = pred.shape[0]
+    n = pred[0].numel() if B else 0
+    if B < 1 or n < 4 or n % 4:
+        raise ValueError(f"weighted_mse_loss needs B >= 1 and a multiple of 4 elements per sample, got {tuple(pred.shape)}")
+    T = 0
+    if weights is not None:
+        if t is None:
+            raise ValueError("weights are indexed by the timesteps: pass t")
+        weights = check_loss_weights(weights, torch.as_tensor(weights).numel())
+        T = weights.numel()
+        t = check_timesteps(t, B, T)
+    else:
+        t = None  # (nothing reads it)
+    if mask is not None:
+        if pred.dim() == 4:
+            mask = expand_loss_mask(mask, pred.shape)
+        else:  # any other [B, ...]: only a mask of pred's own shape has a meaning
+            mask = torch.as_tensor(mask)
+            if tuple(mask.shape) != tuple(pred.shape):
+                raise ValueError(f"loss_mask must have pred's shape {list(pred.shape)}, got {tuple(mask.shape)}")
+            mask = expand_loss_mask(mask.reshape(B, 1, 1, n), (B, 1, 1, n))
+    if not pred.is_cuda:
+        raise N.NativeError("weighted_mse_loss runs on the GPU only (no CPU fallback)")
+    lib, dev = N.lib(), pred.device
+    pred, target = pred.contiguous().float(), target.contiguous().float()
+    if mask is not None:
+        mask = mask.to(dev)
+    if weights is not None:
+        weights, t = weights.to(dev), t.to(dev).long().contiguous()
+    grad = torch.empty_like(pred) if want_grad else None
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    sample_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    scratch = torch.empty(2 * B, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    N.check(lib.wd_weighted_mse_loss(pred.data_ptr(), target.data_ptr(), mask.data_ptr() if mask is not None else None, B, n,
+                                     t.data_ptr() if t is not None else None, weights.data_ptr() if weights is not None else None,
+                                     T, grad.data_ptr() if want_grad else None, loss.data_ptr(), sample_loss.data_ptr(), None, 0,
+                                     scratch.data_ptr(), st), "wd_weighted_mse_loss")
+    return loss, grad, sample_loss
+
+
 class FusedAdamW:
     """``optim.AdamW(model.parameters(), lr=1e-4)`` (train.py:405) + ``EMA(0.995).step_ema`` (train.py:294,410) in one
     multi-tensor launch.  ``ema_model`` is optional; with it ``step()`` reproduces ``ema.step_ema(ema_model, model)``

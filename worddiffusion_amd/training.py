@@ -29,6 +29,12 @@ object -, but neither is in a checkpoint: save at ``micro_index == 0``.
 
 Global-norm clipping belongs to the optimiser handed in (``FusedAdamW(max_grad_norm=...)``); ``last_grad_norm`` is its
 ``grad_norm``, the norm of the mean gradient of the last optimiser step.
+
+Weighted loss (``loss_weights`` / ``loss_bins`` / ``loss_mask``; DESIGN.md "Weighted training loss"): the step's loss launch becomes
+``wd_weighted_mse_loss`` - loss = mean_b w[t_b] * sum_i m_bi (pred - eps)_bi^2 / sum_i m_bi -, which also writes the per-sample
+losses and adds them to a per-timestep histogram, inside the captured body.  Accumulation, clipping and data-parallel need no
+change: the gradient is still d loss / d pred of a per-rank mean over B, so the arena holds what it always held.  A step built
+without the new arguments, and never handed a mask, launches ``wd_mse_loss`` as before and allocates nothing new.
 """
 from __future__ import annotations
 
@@ -38,17 +44,36 @@ from typing import Optional
 import torch
 
 from . import _native as N
-from .optim import FusedAdamW
+from .optim import FusedAdamW, check_loss_weights, check_timesteps, expand_loss_mask
 
 
 class TrainStep:
     def __init__(self, model, diffusion, optimizer: FusedAdamW, seed: int = 0, use_graph: bool = True,
-                 process_group=None, bucketed: Optional[bool] = None, accumulate: int = 1):
+                 process_group=None, bucketed: Optional[bool] = None, accumulate: int = 1, loss_weights=None,
+                 snr_gamma: float = 5.0, loss_bins: int = 0):
         """``bucketed``: run the backward pass in segments with the gradient all-reduce of each segment's arena prefix
         overlapped with the next segment (default: whenever world > 1; ``True`` at world 1 only cuts the graph - tests).
-        ``accumulate``: calls per optimiser step (module docstring); 1 is the plain step, launch for launch."""
+        ``accumulate``: calls per optimiser step (module docstring); 1 is the plain step, launch for launch.
+        ``loss_weights``: ``None``, ``"min_snr"`` (``diffusion.min_snr_weights(snr_gamma)``) or a float tensor [noise_steps],
+        finite and >= 0: the weight of a sample drawn at timestep t; the returned loss is the weighted one.
+        ``loss_bins``: > 0 keeps a histogram of the UNWEIGHTED per-sample losses over that many equal timestep ranges
+        (``loss_by_timestep()``), updated on the device by the loss launch itself."""
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
+        if isinstance(loss_bins, bool) or int(loss_bins) != loss_bins or loss_bins < 0:
+            raise ValueError(f"loss_bins must be an integer >= 0, got {loss_bins!r}")
+        if loss_weights is None:
+            self._wtab_host = None
+        elif isinstance(loss_weights, str):
+            if loss_weights != "min_snr":
+                raise ValueError(f"loss_weights must be None, 'min_snr' or a float tensor [noise_steps], not {loss_weights!r}")
+            self._wtab_host = check_loss_weights(diffusion.min_snr_weights(snr_gamma), diffusion.noise_steps)
+        else:
+            self._wtab_host = check_loss_weights(loss_weights, diffusion.noise_steps)
+        self.loss_bins = int(loss_bins)
+        self._weighted = self._wtab_host is not None or self.loss_bins > 0  # the loss launch is wd_weighted_mse_loss even unmasked
+        self._wtab = self._hist = self._sample_loss = self._wscratch = self._mask = None  # made by the first call that needs them
+        self._mgraph = self._mseg_graphs = None  # the captured bodies of masked calls (``_graph`` / ``_seg_graphs``: unmasked)
         self.model, self.diffusion, self.opt = model, diffusion, optimizer
         self.seed, self.use_graph = seed, use_graph
         self.accumulate = int(accumulate)
@@ -85,19 +110,37 @@ class TrainStep:
         self._P = P
         self._stream = torch.cuda.Stream(device=dev)
         self._comm = torch.cuda.Stream(device=dev)
-        for g in ([self._graph] if self._graph is not None else []) + list(getattr(self, "_seg_graphs", []) or []):
+        for g in [self._graph, self._mgraph] + list(getattr(self, "_seg_graphs", []) or []) + list(self._mseg_graphs or []):
             if g is not None:
                 self.lib.wd_graph_destroy(g)
-        self._graph = None
-        self._seg_graphs = None
+        self._graph = self._mgraph = None
+        self._seg_graphs = self._mseg_graphs = None
+        self._sample_loss = self._wscratch = self._mask = None  # sized by the batch (the histogram and the table are not)
         self.bucketed = (self.world > 1) if self._bucketed_arg is None else bool(self._bucketed_arg)
         self.segments = list(getattr(P, "bwd_segments", [])) if self.bucketed else []
         if len(self.segments) <= 1:
             self.segments = []
 
-    def _body(self, st, seg: Optional[int] = None):
+    def _ensure_weighted(self, masked: bool):
+        """The buffers of the weighted loss launch, allocated by the first call that runs it (never by a plain step)."""
+        P = self._P
+        dev, B = P.x_in.device, P.x_in.shape[0]
+        if self._sample_loss is None:
+            for name, buf in (("out", P.out), ("dout", P.dout), ("eps", self._eps)):  # [B][C*h*w] rows, as the flat MSE assumes
+                if tuple(buf.shape) != tuple(P.x_in.shape) or not buf.is_contiguous():
+                    raise N.NativeError(f"the training plan's {name} does not share the layout of its input")
+            self._sample_loss = torch.zeros(B, dtype=torch.float32, device=dev)
+            self._wscratch = torch.zeros(2 * B, dtype=torch.float64, device=dev)
+        if self._wtab_host is not None and (self._wtab is None or self._wtab.device != dev):
+            self._wtab = self._wtab_host.to(dev)
+        if self.loss_bins and (self._hist is None or self._hist.device != dev):
+            self._hist = torch.zeros(self.loss_bins, 2, dtype=torch.float64, device=dev)
+        if masked and self._mask is None:
+            self._mask = torch.zeros(B, P.x_in[0].numel(), dtype=torch.float32, device=dev)
+
+    def _body(self, st, seg: Optional[int] = None, masked: bool = False):
         """The whole step body (seg None), or segment ``seg`` of it: segment 0 = noise + forward + loss + the first part of the
-        backward list, the others = the following parts."""
+        backward list, the others = the following parts.  ``masked``: the loss launch reads the step's mask buffer."""
         lib, P = self.lib, self._P
         if seg is None or seg == 0:
             n = P.x_in[0].numel()
@@ -105,20 +148,27 @@ class TrainStep:
             N.check(lib.wd_noise_images(self._x0.data_ptr(), self._eps.data_ptr(), P.t_in.data_ptr(), self._sa.data_ptr(),
                                         self._sb.data_ptr(), B, n, P.x_in.data_ptr(), st), "wd_noise_images")
             P.run_step(st)
-            N.check(lib.wd_mse_loss(P.out.data_ptr(), self._eps.data_ptr(), P.out.numel(), P.dout.data_ptr(),
-                                    self._loss.data_ptr(), self._scratch.data_ptr(), 1024, st), "wd_mse_loss")
+            if self._weighted or masked:
+                N.check(lib.wd_weighted_mse_loss(P.out.data_ptr(), self._eps.data_ptr(), self._mask.data_ptr() if masked else None,
+                                                 B, n, P.t_in.data_ptr(), None if self._wtab is None else self._wtab.data_ptr(),
+                                                 self.diffusion.noise_steps, P.dout.data_ptr(), self._loss.data_ptr(),
+                                                 self._sample_loss.data_ptr(), None if self._hist is None else self._hist.data_ptr(),
+                                                 self.loss_bins, self._wscratch.data_ptr(), st), "wd_weighted_mse_loss")
+            else:
+                N.check(lib.wd_mse_loss(P.out.data_ptr(), self._eps.data_ptr(), P.out.numel(), P.dout.data_ptr(),
+                                        self._loss.data_ptr(), self._scratch.data_ptr(), 1024, st), "wd_mse_loss")
         if seg is None:
             P.run_bwd(st)
         else:
             b0, b1, _, _ = self.segments[seg]
             P.run_bwd(st, b0, b1)
 
-    def _capture(self, st, seg=None):
+    def _capture(self, st, seg=None, masked=False):
         lib = self.lib
         N.check(lib.wd_graph_begin(st), "wd_graph_begin")
         g = C.c_void_p()
         try:
-            self._body(st, seg)
+            self._body(st, seg, masked)
         finally:
             rc = lib.wd_graph_end(st, C.byref(g))
         N.check(rc, "wd_graph_end")
@@ -140,19 +190,26 @@ class TrainStep:
         N.check(self.lib.wd_grad_accumulate(dst[a0:a1].data_ptr(), src[a0:a1].data_ptr(), a1 - a0,
                                             0 if fold or self.micro_index else 1, scale, st), "wd_grad_accumulate")
 
-    def _run_bucketed(self, st, final: bool = True):
+    def _run_bucketed(self, st, final: bool = True, masked: bool = False):
         """Backward in segments; after segment j the arena prefix [a0, a1) is final: its all-reduce goes to the comm stream
         behind an event, the next segment runs meanwhile.  Returns after queueing everything; the compute stream waits for
         the collectives before the optimiser.  ``final`` False (a call inside an accumulation group): the segments only."""
         lib = self.lib
         arena = self.eng.grad_arena()
-        if self.use_graph and self._seg_graphs is None:
-            self._seg_graphs = [self._capture(st, j) for j in range(len(self.segments))]
+        graphs = None
+        if self.use_graph:  # one list of segment graphs per variant of the body; only segment 0, which holds the loss, differs
+            if (self._mseg_graphs if masked else self._seg_graphs) is None:
+                made = [self._capture(st, j, masked) for j in range(len(self.segments))]
+                if masked:
+                    self._mseg_graphs = made
+                else:
+                    self._seg_graphs = made
+            graphs = self._mseg_graphs if masked else self._seg_graphs
         for j, (_, _, a0, a1) in enumerate(self.segments):
             if self.use_graph:
-                N.check(lib.wd_graph_launch(self._seg_graphs[j], st), "wd_graph_launch")
+                N.check(lib.wd_graph_launch(graphs[j], st), "wd_graph_launch")
             else:
-                self._body(st, j)
+                self._body(st, j, masked)
             if final and self.accumulate > 1:
                 self._accumulate(st, a0, a1, fold=True)  # in front of the event: the collective sums whole groups
             if final and self.world > 1 and a1 > a0:
@@ -167,10 +224,18 @@ class TrainStep:
 
     def __call__(self, latents: torch.Tensor, text_features: torch.Tensor, labels: Optional[torch.Tensor],
                  t: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                 phoscLabels: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+                 phoscLabels: Optional[torch.Tensor] = None, check: bool = True,
+                 loss_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimisation step on a batch of latents [B, C, H, W]; returns the loss as a device tensor [1] (the
         reference's ``loss.item()`` per step, train.py:295, is the caller's choice).  With ``accumulate > 1`` the batch is one
-        micro-batch of its group, the loss is this micro-batch's, and the optimiser steps on the group's last call."""
+        micro-batch of its group, the loss is this micro-batch's, and the optimiser steps on the group's last call.
+
+        ``loss_mask``: a weight in [0, 1] per latent cell, of shape [h, w], [B, 1, h, w] or [B, C, h, w] (the known-region
+        convention); sample b's loss is then the mask-weighted mean over its cells, and a sample whose mask is all zero adds
+        nothing.  The mask is copied into a buffer of the step before the graph runs.  Masked and unmasked calls are two captured
+        bodies, each kept once it exists.  ``check`` also covers the mask's values and a host ``t`` (every value in
+        [0, noise_steps): the loss launch indexes its tables with it); a mask on the device costs one small synchronisation
+        there, so a loader that has checked its host tensors passes ``check=False``."""
         if not latents.is_cuda:
             raise N.NativeError("TrainStep runs on the GPU only (no CPU fallback)")
         dev = latents.device
@@ -183,6 +248,13 @@ class TrainStep:
         lib, P = self.lib, self._P
         if check:  # out-of-range ids raise here instead of faulting a kernel (device tensors: one small sync; a loader that has
             self.eng.check_ids(text_features, labels, phoscLabels)  # checked its host tensors passes check=False)
+            if t is not None and not t.is_cuda:
+                check_timesteps(t, B, self.diffusion.noise_steps)
+        masked = loss_mask is not None
+        if masked:
+            loss_mask = expand_loss_mask(loss_mask, latents.shape, check_values=check)
+        if masked or self._weighted:
+            self._ensure_weighted(masked)
         if t is None:
             if self._tgen is None:
                 t = self.diffusion.sample_timesteps(B)  # host RNG like the reference (train.py:281)
@@ -206,6 +278,8 @@ class TrainStep:
             if labels is not None:
                 P.y_in.copy_(labels, non_blocking=True)
             self._x0.copy_(latents, non_blocking=True)
+            if masked:
+                self._mask.copy_(loss_mask, non_blocking=True)
             if noise is not None:
                 self._eps.copy_(noise, non_blocking=True)
             else:
@@ -213,14 +287,16 @@ class TrainStep:
                                      (self.step_index * self.world + self.rank) * B, 2, st), "wd_randn")
             final = self.micro_index == self.accumulate - 1  # this call ends its group: the optimiser steps
             if self.segments:
-                self._run_bucketed(st, final)
+                self._run_bucketed(st, final, masked)
             else:
                 if self.use_graph:
-                    if self._graph is None:
+                    if masked and self._mgraph is None:
+                        self._mgraph = self._capture(st, None, True)
+                    elif not masked and self._graph is None:
                         self._graph = self._capture(st)
-                    N.check(lib.wd_graph_launch(self._graph, st), "wd_graph_launch")
+                    N.check(lib.wd_graph_launch(self._mgraph if masked else self._graph, st), "wd_graph_launch")
                 else:
-                    self._body(st)
+                    self._body(st, None, masked)
                 if final and self.accumulate > 1:
                     self._accumulate(st, 0, self.eng.grad_arena().numel(), fold=True)
                 if final and self.world > 1:
@@ -234,7 +310,7 @@ class TrainStep:
             else:
                 self._accumulate(st, 0, self.eng.grad_arena().numel(), fold=False)
         cur.wait_stream(self._stream)
-        for tns in (latents, text_features, labels, noise):
+        for tns in (latents, text_features, labels, noise, loss_mask):
             if tns is not None and tns.is_cuda:
                 tns.record_stream(self._stream)
         self.step_index += 1
@@ -250,3 +326,38 @@ class TrainStep:
         """The optimiser's ``grad_norm``: device fp32 [1], the global norm of the (mean) gradient of the last optimiser step,
         before clipping (``FusedAdamW(max_grad_norm=...)``; zero while clipping is off)."""
         return self.opt.grad_norm
+
+    @property
+    def last_sample_losses(self) -> torch.Tensor:
+        """Device fp32 [B]: the UNWEIGHTED (masked) mean squared error of every sample of the last call, written by the loss launch;
+        nothing synchronises.  Only the weighted loss launch computes it (``loss_weights``, ``loss_bins`` or a ``loss_mask``)."""
+        if self._sample_loss is None:
+            raise RuntimeError("last_sample_losses: no call has run the weighted loss (loss_weights, loss_bins or a loss_mask)")
+        return self._sample_loss
+
+    def _bin_edges(self):
+        T, nb = self.diffusion.noise_steps, self.loss_bins
+        return [-((-k * T) // nb) for k in range(nb)] + [T]  # bin k holds the t with (t * nb) // T == k: from ceil(k T / nb) on
+
+    def loss_by_timestep(self):
+        """The histogram ``loss_bins`` asked for, as numpy arrays: ``edges`` int64 [loss_bins + 1] (bin k holds the timesteps
+        edges[k] <= t < edges[k + 1]), ``mean`` float64 [loss_bins] (the mean unweighted per-sample loss of the calls since the
+        last reset; NaN for a bin no sample fell in) and ``count`` int64 [loss_bins].  Synchronises once, here and nowhere else."""
+        import numpy as np
+        if not self.loss_bins:
+            raise RuntimeError("loss_by_timestep needs TrainStep(loss_bins > 0)")
+        if self._hist is None:
+            h = np.zeros((self.loss_bins, 2))
+        else:
+            h = self._hist.cpu().numpy()  # (the one synchronisation; ordered after the step, which the caller's stream waits for)
+        count = h[:, 1].astype(np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(count > 0, h[:, 0] / h[:, 1], np.nan)
+        return dict(edges=np.asarray(self._bin_edges(), dtype=np.int64), mean=mean, count=count)
+
+    def reset_loss_by_timestep(self) -> None:
+        """Empties the histogram (a device memset queued behind the last step; no synchronisation)."""
+        if not self.loss_bins:
+            raise RuntimeError("reset_loss_by_timestep needs TrainStep(loss_bins > 0)")
+        if self._hist is not None:
+            self._hist.zero_()
