@@ -404,6 +404,22 @@ int wd_xattn_planes(const float* x, int ld, int batch, int hw, int c, float eps,
                     const float* gamma2, const float* beta2, float eps2, wd_bf16* n_hi, wd_bf16* n_lo, int n_ld, wd_bf16* r_hi,
                     wd_bf16* r_lo, int r_ld, void* stream);
 
+/* Per-character attention maps: the head sum of the softmax of one folded cross-attention (the reference's --attentionMaps 1
+ * outputs attn1 / attn2 / attn3, unet.py:203-279 (CrossAttention keeps its softmax), 337-345, 405-410, 1645-1832; :1757 sums the
+ * heads).  Per token row r of sample b, with A as in wd_xattn_pair:
+ *     xa = x[r] (mq_pl_a == NULL: gamma_a .. bias_a unused)   or   xa = A(x[r]) (the attention before the tapped one)
+ *     p[h][j] = softmax_j(LN(xa; gamma_b, beta_b, eps) . Mq_b[b][h*L + j]),   m[j] = sum_h p[h][j]
+ *     maps[r][j] = m[j]  (wtab == NULL)   or   maps[r][j] + wtab[*k_dev] * m[j]  (product and sum rounded separately, no fma;
+ *                                               *k_dev outside [0, wtab_n) counts as weight 0)
+ * The same LayerNorm, planes and MFMA score products as wd_xattn_pair / wd_xattn_planes, so p is what the sampling step itself
+ * multiplies with Mo; no output product, Mo_b is not read.  maps is fp32 [batch*hw][maps_ld >= L].  k_dev is a device index
+ * (the samplers' step index or timestep), so one captured graph serves every step.  Shapes: wd_xattn_supported(c, heads, L);
+ * wtab and k_dev come together. */
+int wd_xattn_maps(const float* x, int ld, int batch, int hw, int c, float eps, int heads, int L, const float* gamma_a,
+                  const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a, const float* gamma_b,
+                  const float* beta_b, const wd_bf16* mq_pl_b, float* maps, int maps_ld, const float* wtab, int wtab_n,
+                  const int32_t* k_dev, void* stream);
+
 /* Two linear layers with nothing between them as one: w32 [c][ffi] = w3 [c][inner] . w2 [inner][ffi] and b32 [c] = w3 . b2 + b3
  * (b2 / b3 may be NULL: zeros).  fp64 products summed in ascending k and rounded once to fp32; no library GEMM.  The folded tail
  * of wd_ff_fused and the two-source ff2 + proj_out GEMM of the SpatialTransformer read the result (unet.py:145,406-412). */

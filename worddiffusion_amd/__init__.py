@@ -1,7 +1,9 @@
 """worddiffusion_amd - MI355X-native UNet denoising hot path of WordDiffusion."""
 from .unet import UNetModel
+from .model import remap_attention_maps_state_dict, to_attention_maps_state_dict
 from .unetPhosc import UNetModelPhosc
 from .diffusion import EMA, Diffusion, label_padding, latent_mask_from_pixels
 from .vae import AutoencoderKL
 
-__all__ = ["UNetModel", "UNetModelPhosc", "Diffusion", "EMA", "label_padding", "latent_mask_from_pixels", "AutoencoderKL"]
+__all__ = ["UNetModel", "UNetModelPhosc", "Diffusion", "EMA", "label_padding", "latent_mask_from_pixels", "AutoencoderKL",
+           "remap_attention_maps_state_dict", "to_attention_maps_state_dict"]

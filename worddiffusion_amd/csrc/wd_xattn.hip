@@ -572,7 +572,307 @@ int launch16(const float* x, int ld, int batch, int hw, const XaLayer& la, const
     return wd_check_launch();
 }
 
+// ---- Per-character attention maps (unet.py:203-279,1645-1832: the head sum of softmax(q k^T) of one cross-attention): the
+// kernel above with its tail replaced.  PAIR: the first attention runs in full, line for line as in xattn16_kernel<NI, 2, .> (its
+// result is the residual stream the tapped attention reads); the tapped attention stops after the softmax: no probability planes,
+// no second product, Mo is never loaded.  The phases are copies, not calls: hoisting them out of xattn16_kernel moves its
+// registers, and its outputs are compared bit for bit.  Tail: probabilities in place in the score tile, then thread (token, key)
+// sums the heads and stores - L consecutive floats per row, rows of a tile consecutive where maps_ld == L.
+//   wtab == NULL: maps = m;   else: maps = maps + wtab[*k_dev] * m, product and sum each rounded on its own (weight 0 for an
+//   index outside [0, wtab_n)).
+// acc + w * m, the product and the sum rounded one after the other: parsed with contraction off, so neither carries the `contract`
+// flag and they cannot fuse once inlined (the __fmul_rn / __fadd_rn intrinsics are inline functions parsed with contraction allowed
+// and do fuse; as wd_dropout_apply in wd_philox.h).  A host fp32 replay is then bit-exact.
+__device__ __forceinline__ float xa_accumulate(float acc, float w, float m) {
+#pragma clang fp contract(off)
+    const float p = w * m;
+    return acc + p;
+}
+
+template <int NI, bool PAIR, int LL>
+__global__ void __launch_bounds__(256, 3) xattn_maps_kernel(const float* __restrict__ x, int ld, int hw, const XaLayer la,
+                                                         const XaLayer lb, float eps, int heads, int L, float* __restrict__ maps,
+                                                         int maps_ld, const float* __restrict__ wtab, int wtab_n,
+                                                         const int32_t* __restrict__ k_dev) {
+    constexpr int XT = 16, NTH = 256, NP = PAIR ? 2 : 1;
+    constexpr int C = NI * 32, XP = C + 8, OP = C + 4, SP = 65, PP = 72, NT = NI / 2, KS32 = C / 32;
+    static_assert(NI % 2 == 0, "column tiles per wave");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    wd_bf16* sX = reinterpret_cast<wd_bf16*>(smem);                              // [2][XT][XP] normalised tokens (planes)
+    float* sO = reinterpret_cast<float*>(smem);                                   // [XT][OP] output image (overlays sX)
+    constexpr size_t XBYTES = (size_t)2 * XT * XP * 2 > (size_t)XT * OP * 4 ? (size_t)2 * XT * XP * 2 : (size_t)XT * OP * 4;
+    float* sS = reinterpret_cast<float*>(smem + XBYTES);                          // [XT][SP] scores, then probabilities
+    wd_bf16* sP = reinterpret_cast<wd_bf16*>(smem + XBYTES + (size_t)XT * SP * 4);  // [2][XT][PP] probabilities (planes), PAIR
+    float* sV = reinterpret_cast<float*>(smem + XBYTES + (size_t)XT * SP * 4 + (size_t)2 * XT * PP * 2);  // [3][C], PAIR
+    const int b = blockIdx.x, t0 = blockIdx.y * XT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int HJ = heads * L;
+    const long row0 = (long)b * hw + t0;
+    const int ntok = min(XT, hw - t0);
+    constexpr int FI = NI / 2;
+    const int qd = lane >> 4, l15 = lane & 15;
+    const int trow = wave * 4 + qd;
+    const bool ok = trow < ntok;
+    float4 xr[FI];
+#pragma unroll
+    for (int i = 0; i < FI; ++i) {
+        xr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) xr[i] = *reinterpret_cast<const float4*>(x + (row0 + trow) * ld + (l15 + 16 * i) * 4);
+    }
+    const bool row_live = wave * 16 + l15 < HJ;
+    const long pq = (long)XHJ * C;
+    xa_bf16x8 bh[KS32], bl[KS32];
+    auto request_scores = [&](const XaLayer& ly) {
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(ly.mq_pl + (long)b * 2 * pq), 0,
+                                                                            (int)(2 * pq * 2), 0x00020000);
+        const unsigned vo = row_live ? lane * 16u : 0x80000000u;
+#pragma unroll
+        for (int ks = 0; ks < KS32; ++ks) {
+            bh[ks] = xa_bload(rq, vo, (unsigned)((wave * KS32 + ks) << 10));
+            bl[ks] = xa_bload(rq, vo, (unsigned)(((wave * KS32 + ks) << 10) + pq * 2));
+        }
+    };
+    if (PAIR) {
+        for (int e = tid; e < 2 * XT * PP / 2; e += NTH) reinterpret_cast<uint32_t*>(sP)[e] = 0u;  // padding columns stay zero
+        for (int e = tid; e < 3 * (C / 4); e += NTH) {  // [0] la.bias [1] lb.gamma [2] lb.beta
+            const int v = e / (C / 4), i = e - v * (C / 4);
+            const float* src = v == 0 ? la.bias : v == 1 ? lb.gamma : lb.beta;
+            reinterpret_cast<float4*>(sV)[e] = reinterpret_cast<const float4*>(src)[i];
+        }
+    }
+#pragma unroll
+    for (int ps = 0; ps < NP; ++ps) {
+    const XaLayer& ly = ps == 0 ? la : lb;
+    const float* gamma = ps == 0 ? la.gamma : sV + C;
+    const float* beta = ps == 0 ? la.beta : sV + 2 * C;
+    const bool last = ps == NP - 1;
+    // ---- LayerNorm -> split planes in LDS
+    {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < FI; ++i) s += (xr[i].x + xr[i].y) + (xr[i].z + xr[i].w);
+        const float mean = wd_row16_sum(s) / (float)C;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < FI; ++i) {
+            const float a0 = xr[i].x - mean, a1 = xr[i].y - mean, a2 = xr[i].z - mean, a3 = xr[i].w - mean;
+            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+        }
+        const float rstd = 1.0f / sqrtf(wd_row16_sum(q) / (float)C + eps);
+#pragma unroll
+        for (int i = 0; i < FI; ++i) {
+            const float4 ga = *reinterpret_cast<const float4*>(gamma + (l15 + 16 * i) * 4);
+            const float4 be = *reinterpret_cast<const float4*>(beta + (l15 + 16 * i) * 4);
+            float4 o;
+            o.x = (xr[i].x - mean) * rstd * ga.x + be.x; o.y = (xr[i].y - mean) * rstd * ga.y + be.y;
+            o.z = (xr[i].z - mean) * rstd * ga.z + be.z; o.w = (xr[i].w - mean) * rstd * ga.w + be.w;
+            uint2 hi, lo;
+            wd_split4(o, hi, lo);
+            *reinterpret_cast<uint2*>(sX + (long)trow * XP + (l15 + 16 * i) * 4) = hi;
+            *reinterpret_cast<uint2*>(sX + (long)(XT + trow) * XP + (l15 + 16 * i) * 4) = lo;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    request_scores(ly);
+    __syncthreads();
+
+    // ---- scores S[token][hj] = Xn . Mq^T
+    if (wave * 16 < HJ) {
+        xa_f32x4 a_lh = {0.f, 0.f, 0.f, 0.f}, a_hl = a_lh, a_hh = a_lh;
+        const wd_bf16* ax = sX + (long)l15 * XP + qd * 8;
+#pragma unroll
+        for (int ks = 0; ks < KS32; ++ks) {
+            const xa_bf16x8 ah = *reinterpret_cast<const xa_bf16x8*>(ax + ks * 32);
+            const xa_bf16x8 al = *reinterpret_cast<const xa_bf16x8*>(ax + (long)XT * XP + ks * 32);
+            a_lh = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[ks], a_lh, 0, 0, 0);
+            a_hl = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[ks], a_hl, 0, 0, 0);
+            a_hh = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[ks], a_hh, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sS[(4 * qd + r) * SP + wave * 16 + l15] = (a_lh[r] + a_hl[r]) + a_hh[r];
+    }
+    if (last) {
+        // ---- the tapped attention: softmax per (token, head) in place (fp32: the value the step's kernel splits into planes)
+        __syncthreads();
+        for (int idx = tid; idx < XT * heads; idx += NTH) {
+            const int t = idx / heads, h = idx - t * heads;
+            float* pr = sS + t * SP + h * L;
+            if (LL > 0) {
+                constexpr int LN_ = LL > 0 ? LL : 1;
+                float v[LN_];
+#pragma unroll
+                for (int j = 0; j < LN_; ++j) v[j] = pr[j];
+                float mx = v[0];
+#pragma unroll
+                for (int j = 1; j < LN_; ++j) mx = fmaxf(mx, v[j]);
+                float sum = 0.f;
+#pragma unroll
+                for (int j = 0; j < LN_; ++j) {
+                    v[j] = __expf(v[j] - mx);
+                    sum += v[j];
+                }
+                const float inv = __fdividef(1.f, sum);
+#pragma unroll
+                for (int j = 0; j < LN_; ++j) pr[j] = v[j] * inv;
+            } else {
+                float mx = -3.4e38f;
+                for (int j = 0; j < L; ++j) mx = fmaxf(mx, pr[j]);
+                float sum = 0.f;
+                for (int j = 0; j < L; ++j) sum += __expf(pr[j] - mx);
+                const float inv = __fdividef(1.f, sum);
+                for (int j = 0; j < L; ++j) pr[j] = __expf(pr[j] - mx) * inv;
+            }
+        }
+        __syncthreads();
+        // ---- head sum (unet.py:1757) and store
+        float w = 0.f;
+        if (wtab) {
+            const int k = *k_dev;
+            if (k >= 0 && k < wtab_n) w = wtab[k];  // (an index outside the table adds nothing)
+        }
+        for (int idx = tid; idx < ntok * L; idx += NTH) {
+            const int t = idx / L, j = idx - t * L;
+            float m = sS[t * SP + j];
+            for (int h = 1; h < heads; ++h) m += sS[t * SP + h * L + j];
+            float* dst = maps + (row0 + t) * maps_ld + j;
+            *dst = wtab ? xa_accumulate(*dst, w, m) : m;
+        }
+        return;
+    }
+    // ---- the first attention of a pair, as in xattn16_kernel: output product, + bias + residual -> the rows the tap reads
+    __builtin_amdgcn_sched_barrier(0);
+    xa_bf16x8 mh[2][NT], ml[2][NT];
+    {
+        const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<wd_bf16*>(ly.mot_pl + (long)b * 2 * pq), 0,
+                                                                            (int)(2 * pq * 2), 0x00020000);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const unsigned vo = ks * 32 + qd * 8 < HJ ? lane * 16u : 0x80000000u;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                mh[ks][t] = xa_bload(rm, vo, (unsigned)((((wave * NT + t) * 2 + ks) << 10)));
+                ml[ks][t] = xa_bload(rm, vo, (unsigned)((((wave * NT + t) * 2 + ks) << 10) + pq * 2));
+            }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < XT * heads; idx += NTH) {
+        const int t = idx / heads, h = idx - t * heads;
+        const float* pr = sS + t * SP + h * L;
+        wd_bf16* ph = sP + (long)t * PP + h * L;
+        if (LL > 0) {
+            constexpr int LN_ = LL > 0 ? LL : 1;
+            float v[LN_];
+#pragma unroll
+            for (int j = 0; j < LN_; ++j) v[j] = pr[j];
+            float mx = v[0];
+#pragma unroll
+            for (int j = 1; j < LN_; ++j) mx = fmaxf(mx, v[j]);
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < LN_; ++j) {
+                v[j] = __expf(v[j] - mx);
+                sum += v[j];
+            }
+            const float inv = __fdividef(1.f, sum);
+#pragma unroll
+            for (int j = 0; j < LN_; ++j) {
+                uint32_t hi, lo;
+                wd_split1(v[j] * inv, hi, lo);
+                ph[j] = (wd_bf16)hi;
+                ph[(long)XT * PP + j] = (wd_bf16)lo;
+            }
+        } else {
+            float mx = -3.4e38f;
+            for (int j = 0; j < L; ++j) mx = fmaxf(mx, pr[j]);
+            float sum = 0.f;
+            for (int j = 0; j < L; ++j) sum += __expf(pr[j] - mx);
+            const float inv = __fdividef(1.f, sum);
+            for (int j = 0; j < L; ++j) {
+                uint32_t hi, lo;
+                wd_split1(__expf(pr[j] - mx) * inv, hi, lo);
+                ph[j] = (wd_bf16)hi;
+                ph[(long)XT * PP + j] = (wd_bf16)lo;
+            }
+        }
+    }
+    __syncthreads();
+    {
+        xa_f32x4 o[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) o[t] = xa_f32x4{0.f, 0.f, 0.f, 0.f};
+        const wd_bf16* ap = sP + (long)l15 * PP + qd * 8;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const xa_bf16x8 ah = *reinterpret_cast<const xa_bf16x8*>(ap + ks * 32);
+            const xa_bf16x8 al = *reinterpret_cast<const xa_bf16x8*>(ap + (long)XT * PP + ks * 32);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, mh[ks][t], o[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, ml[ks][t], o[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, mh[ks][t], o[t], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sO[(4 * qd + r) * OP + (wave * NT + t) * 16 + l15] = o[t][r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < FI; ++i) {
+        const int n = (l15 + 16 * i) * 4;
+        const float4 bi = *reinterpret_cast<const float4*>(sV + n);
+        const float4 at = *reinterpret_cast<const float4*>(sO + trow * OP + n);
+        xr[i] = make_float4(at.x + bi.x + xr[i].x, at.y + bi.y + xr[i].y, at.z + bi.z + xr[i].z, at.w + bi.w + xr[i].w);
+    }
+    __syncthreads();  // the output image is consumed before the tapped attention overwrites the token planes
+    }
+}
+
+template <int NI, bool PAIR>
+int launch_maps(const float* x, int ld, int batch, int hw, const XaLayer& la, const XaLayer& lb, float eps, int heads, int L,
+                float* maps, int maps_ld, const float* wtab, int wtab_n, const int32_t* k_dev, hipStream_t st) {
+    constexpr int C = NI * 32, XTM = 16;
+    constexpr size_t xb = (size_t)2 * XTM * (C + 8) * 2 > (size_t)XTM * (C + 4) * 4 ? (size_t)2 * XTM * (C + 8) * 2 : (size_t)XTM * (C + 4) * 4;
+    constexpr size_t smem = xb + (size_t)XTM * 65 * 4 + (size_t)2 * XTM * 72 * 2 + (size_t)3 * C * 4;
+    static_assert(smem <= 48 * 1024, "static LDS limit");
+    WdLaunchScope scope(WD_CLS_ATTN, st);
+    const dim3 grid(batch, (hw + XTM - 1) / XTM);
+    if (L == 10)
+        hipLaunchKernelGGL((xattn_maps_kernel<NI, PAIR, 10>), grid, dim3(256), smem, st, x, ld, hw, la, lb, eps, heads, L, maps,
+                           maps_ld, wtab, wtab_n, k_dev);
+    else
+        hipLaunchKernelGGL((xattn_maps_kernel<NI, PAIR, 0>), grid, dim3(256), smem, st, x, ld, hw, la, lb, eps, heads, L, maps,
+                           maps_ld, wtab, wtab_n, k_dev);
+    return wd_check_launch();
+}
+
 }  // namespace
+
+extern "C" int wd_xattn_maps(const float* x, int ld, int batch, int hw, int c, float eps, int heads, int L, const float* gamma_a,
+                             const float* beta_a, const wd_bf16* mq_pl_a, const wd_bf16* mot_pl_a, const float* bias_a,
+                             const float* gamma_b, const float* beta_b, const wd_bf16* mq_pl_b, float* maps, int maps_ld,
+                             const float* wtab, int wtab_n, const int32_t* k_dev, void* stream) {
+    if (!x || !maps || !gamma_b || !beta_b || !mq_pl_b || batch <= 0 || hw <= 0) return WD_EINVAL;
+    const bool pair = mq_pl_a != nullptr;
+    if (pair && (!gamma_a || !beta_a || !mot_pl_a || !bias_a)) return WD_EINVAL;
+    if (!wd_xattn_supported(c, heads, L) || ld % 4 || ld < c || maps_ld < L || (wtab != nullptr) != (k_dev != nullptr) ||
+        (wtab && wtab_n <= 0))
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const XaLayer lb = {gamma_b, beta_b, mq_pl_b, nullptr, nullptr};
+    const XaLayer la = pair ? XaLayer{gamma_a, beta_a, mq_pl_a, mot_pl_a, bias_a} : lb;
+#define WD_XM(NI_, PAIR_) return launch_maps<NI_, PAIR_>(x, ld, batch, hw, la, lb, eps, heads, L, maps, maps_ld, wtab, wtab_n, k_dev, st)
+    if (c == 320) {
+        if (pair) WD_XM(10, true);
+        WD_XM(10, false);
+    }
+    if (pair) WD_XM(2, true);
+    WD_XM(2, false);
+#undef WD_XM
+}
 
 extern "C" int wd_xattn_supported(int c, int heads, int L) {
     return (c == 64 || c == 320) && heads > 0 && L > 0 && heads * L <= 40 && c % heads == 0;

@@ -175,6 +175,7 @@ class Diffusion:
         self.forwards_per_step = 1
         self.tabulate_film = os.environ.get("WDIFF_FILM_TABLE", "1") != "0"
         self.last_stats = {}
+        self.last_attention = None  # the maps of the last sampler call that asked for them (``attention=``)
 
     def prepare_noise_schedule(self):
         return torch.linspace(self.beta_start, self.beta_end, self.noise_steps)
@@ -429,6 +430,34 @@ class Diffusion:
         stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
         return _Sampler(steps, tau[0], list(tau), update, stats)
 
+    def _attention_setup(self, model, sampler, attention):
+        """The ``attention`` argument of a sampler call, settled on the host (no device, no library): None, or (weights, N) - the
+        fp32 table the steps' ``wd_xattn_maps`` launches read, 1/N at the N model-calling steps whose timestep lies in the window
+        and 0 elsewhere, indexed as the sampler's FiLM rows are (by t, [noise_steps], or by the step index of its ``tau``).
+        attention: None / False (off), True (every model-calling step) or (t_hi, t_lo), both ends included."""
+        if attention is None or attention is False:
+            return None
+        if attention is True:
+            hi, lo = self.noise_steps, 0
+        else:
+            try:
+                hi, lo = attention
+                ok = all(not isinstance(v, bool) and int(v) == v for v in (hi, lo))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok or int(lo) > int(hi):
+                raise ValueError(f"attention must be True or a timestep window (t_hi, t_lo) with t_hi >= t_lo, not {attention!r}")
+            hi, lo = int(hi), int(lo)
+        if getattr(model, "variant", "base") == "phosc":
+            raise NotImplementedError("attention= with the PHOSC model: it has no per-character attention maps")
+        tau = sampler.tau
+        rows = [row for row, fwd, _ in sampler.steps if fwd and lo <= (row if tau is None else tau[row]) <= hi]
+        if not rows:
+            raise ValueError(f"attention window ({hi}, {lo}) selects none of the steps that call the model")
+        w = torch.zeros(self.noise_steps if tau is None else len(tau), dtype=torch.float32)
+        w[rows] = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(len(rows)), dtype=torch.float32)
+        return w, len(rows)
+
     def _known_setup(self, n, known, known_mask=None, start=None, known_noise="auto", x_T=None, *, draws_noise, tau=None):
         """The ``known`` / ``known_mask`` / ``start`` / ``known_noise`` arguments of a sampler call, validated and settled on the
         host (no device, no library): a ``_Known``, or None where the call passes none of them.
@@ -493,7 +522,7 @@ class Diffusion:
         return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
 
     def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None):
+                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None, attention=None):
         """The one reverse loop.  Per visited step of ``sampler`` (``_ddpm`` / ``_ddim``): this step's ``noise`` entry into
         the noise buffer if it has one, ``film_prepare`` and the forward(s) when the step calls the model, the sampler's update.
         mix = (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
@@ -502,7 +531,10 @@ class Diffusion:
         one) - eager launches only, like ``record``.
         known: a ``_Known``.  Its fixed eps (the caller's, or stream WD_STREAM_KNOWN of ``seed`` at the global rows) noises the
         known latents to ``known.start``, where the loop then begins, and with a mask every step's tail blends the kept region
-        back in at the level the step reached (``wd_known_blend``, inside the captured graph)."""
+        back in at the level the step reached (``wd_known_blend``, inside the captured graph).
+        attention: what ``_attention_setup`` returned.  The plan then holds three map accumulators, zeroed here, and every
+        model-calling step adds its weight times its maps (``wd_xattn_maps`` inside the captured step, the first forward of a
+        step only); the weighted mean lands in ``last_attention``."""
         lib = N.lib()
         eng = model.engine
         nf = 0 if mix is None else int(mix[0].shape[0])
@@ -517,7 +549,9 @@ class Diffusion:
         # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
         film_steps = self.noise_steps if (self.tabulate_film or nf) else 0
         P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
-                     film_timesteps=tuple(sampler.tau) if (film_steps and sampler.tau is not None) else None)
+                     film_timesteps=tuple(sampler.tau) if (film_steps and sampler.tau is not None) else None,
+                     **(dict(attn_maps=True, attn_rows=attention[0].numel(), attn_by_step=sampler.tau is not None)
+                        if attention is not None else {}))
         fps = nf or self.forwards_per_step
         ncalls = sum(fwd for _, fwd, _ in sampler.steps)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
@@ -554,6 +588,10 @@ class Diffusion:
                             phosc.to(device) if phosc is not None else None, check=False)
             if nf:
                 eng.load_mix(P, mix[0].to(device), mix[1].to(device), check=False)
+            if attention is not None:
+                P.map_w.copy_(attention[0])
+                for acc in P.maps:
+                    acc.zero_()
             eps_g = torch.empty_like(P.out) if (nf == 2 and record_pred is not None) else None
             P.t_dev.fill_(sampler.t_first)
             P.t_in.fill_(sampler.t_first)
@@ -603,6 +641,10 @@ class Diffusion:
                 if record_pred is not None and fwd:
                     record_pred.append((P.out.clone(),) if nf != 2 else (P.out.clone(), P.out1.clone(), eps_g.clone()))
             x = P.x_in.clone()
+            self.last_attention = None
+            if attention is not None:
+                self.last_attention = {k: acc.clone().reshape(n, mh, mw, -1)
+                                       for k, acc, (mh, mw) in zip(("input", "middle", "output"), P.maps, P.map_hw)}
         torch.cuda.current_stream(device).wait_stream(side)
         if gexec is not None:
             side.synchronize()
@@ -612,6 +654,8 @@ class Diffusion:
         self.last_stats = dict(sampler.stats, forwards_per_step=fps, graph=gexec is not None, seed=seed,
                                sample_offset=sample_offset, model_calls=ncalls * (nf or 1), known=known is not None,
                                start=None if known is None else known.start, known_noise=None if known is None else known.mode)
+        if attention is not None:
+            self.last_stats["attention_steps"] = attention[1]
         return x
 
     def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, *, sampler=None):
@@ -691,7 +735,7 @@ class Diffusion:
     @torch.no_grad()
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
-                 style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto"):
+                 style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto", attention=None):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
@@ -709,16 +753,22 @@ class Diffusion:
         ``known`` through the whole trajectory (every step ends by blending it back in at the level the step reached, the last
         one noise-free, so the kept region of the result IS ``known``) and / or begin at the level ``start`` from ``known``
         noised to it instead of from noise at T - 1; ``noise`` then holds one tensor per visited step with t > 1.
-        ``last_stats`` reports ``known``, ``start`` (the level noised to) and ``known_noise`` (the resolved mode)."""
+        ``last_stats`` reports ``known``, ``start`` (the level noised to) and ``known_noise`` (the resolved mode).
+
+        ``attention=True | (t_hi, t_lo)``: the per-character cross-attention maps of the call (the reference's --attentionMaps 1
+        outputs, unet.py:1645-1832), averaged over the model-calling steps (those with t_lo <= t <= t_hi), are left in
+        ``last_attention = {"input", "middle", "output"}``, fp32 [n, h, w, L] at latent resolution; ``last_stats`` gains
+        ``attention_steps``.  Base model only."""
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True)
         device, tf, phosc = self._prepare("sampling", model, n, x_text, args, phoscLabels, underscore)
         sampler = self._ddpm(start=None if kn is None else kn.start)
+        att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
-                              record_pred=record_pred, known=kn)
+                              record_pred=record_pred, known=kn, attention=att)
         finally:
             model.train()  # train.py:238 (unconditional)
         return self._finish(x, vae, args)
@@ -727,7 +777,7 @@ class Diffusion:
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
                       phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
                       use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None, start=None,
-                      known_noise="auto"):
+                      known_noise="auto", attention=None):
         """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
         ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
         deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
@@ -740,7 +790,8 @@ class Diffusion:
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling``; with ``start`` the call visits the entries of
         its usual schedule that are <= start (``steps`` and ``timesteps`` of ``last_stats`` are the retained ones, FiLM rows,
         pairs and ``noise`` are indexed by them) and the first of them is the level noised to.  With ``eta = 0`` the default
-        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``."""
+        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention`` as in
+        ``sampling``."""
         tau = self.ddim_timesteps(steps, timesteps)
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau)
         if kn is not None:
@@ -749,12 +800,13 @@ class Diffusion:
             raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
         device, tf, phosc = self._prepare("sampling_ddim", model, n, x_text, args, phoscLabels, underscore)
         sampler = self._ddim(tau, eta)
+        att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
-                              known=kn)
+                              known=kn, attention=att)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
@@ -763,7 +815,7 @@ class Diffusion:
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
                        mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
                        record_pred=None, use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None,
-                       start=None, known_noise="auto"):
+                       start=None, known_noise="auto", attention=None):
         """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
         ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
         the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
@@ -774,7 +826,7 @@ class Diffusion:
         returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
         ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``.
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling_ddim`` (the default noise is the fixed eps: no
-        step draws); the first retained step is first order, like the first step of any call."""
+        step draws); the first retained step is first order, like the first step of any call.  ``attention`` as in ``sampling``."""
         tau = self.dpmpp_timesteps(steps, spacing, timesteps)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
@@ -783,11 +835,12 @@ class Diffusion:
             tau = kn.tau
         device, tf, phosc = self._prepare("sampling_dpmpp", model, n, x_text, args, phoscLabels, underscore)
         sampler = self._dpmpp(tau, order, None if timesteps is not None else spacing)
+        att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, seed=seed, sample_offset=sample_offset,
-                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn)
+                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn, attention=att)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
@@ -804,7 +857,7 @@ class Diffusion:
     @torch.no_grad()
     def sampling3(self, epoch, x_t, words, phoscLabels, model, model1, vae, emaOld, noiseInput, n, x_text, labels, args,
                   mix_rate=None, cfg_scale=3, seed=None, sample_offset=0, use_graph=True, x_T=None, noise=None, record=None, *,
-                  style_pairs=None):
+                  style_pairs=None, attention=None):
         """Bulk-regeneration sampler of ``regenerateFromtrain2.py:465-648`` (same argument order): the predicted noise is
         refreshed only on the steps of ``sampling3_calls_model`` (1 in 5) and reused in between, and unless
         ``args.fullSampling`` the update is deterministic (no ``sqrt(beta) * noise`` term, ``:618``).  ``noiseInput == 0``
@@ -815,7 +868,9 @@ class Diffusion:
         (``tests/golden/ddpm_traj_sampling3.npz``, ``oracle/make_golden_sampling3.py``).  ``mix_rate`` / ``style_pairs`` as in
         ``sampling``; this loop calls the model once per model-calling step, so with ``args.interpolation`` one pair is drawn for
         each of those steps and none for the others.  (The reference's own loop accepts ``mix_rate`` and does not hand it to
-        the model, ``:587,591``: there the argument has no effect; here it selects the blend, as it does in ``sampling``.)"""
+        the model, ``:587,591``: there the argument has no effect; here it selects the blend, as it does in ``sampling``.)
+        ``attention`` as in ``sampling``: the steps that reuse the previous prediction run no forward and add nothing, and
+        ``attention_steps`` counts the model-calling steps of the window only."""
         if emaOld == 1:
             model = model1
         model.eval()  # and it stays in eval mode: ``#model.train()`` is commented out at regenerateFromtrain2.py:622
@@ -827,9 +882,10 @@ class Diffusion:
         full = bool(getattr(args, "fullSampling", False))
         sampler = self._ddpm(None if full else (lambda i: self.sampling3_calls_model(i, self.noise_steps, epoch)),
                              deterministic=not full)
+        att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, 0, sampler=sampler)  # (one forward per step: no guidance here)
         x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_t if noiseInput == 0 else x_T, noise=noise,
-                          seed=seed, sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix)
+                          seed=seed, sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, attention=att)
         if vae is None:
             return x
         image = self._finish(x, vae, args)

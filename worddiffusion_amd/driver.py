@@ -128,7 +128,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
                world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
                ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
-               known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto"):
+               known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto",
+               attention=None, attn_out: Optional[str] = None):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -142,7 +143,14 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``known`` (a ``LatentCache``, or any mapping image name -> latent [C, h, w]): every gt row is regenerated from its own cached
     latent - ``keep_cols = (a, b)`` keeps the latent columns a <= column < b and re-draws the rest, ``start`` begins the loop
     from the latent noised to that level, ``known_noise`` as in ``Diffusion.sampling``.  A row whose latent is missing raises
-    KeyError naming it, before anything is sampled.  Not with ``skip_steps``."""
+    KeyError naming it, before anything is sampled.  Not with ``skip_steps``.
+
+    ``attention`` (True or a timestep window ``(t_hi, t_lo)``, as in ``Diffusion.sampling``): every call also leaves its
+    per-character cross-attention maps; ``attn_out`` (a ``.npz`` path; a relative one lands in ``out_dir``, beside the images)
+    receives them for the shard: ``input`` / ``middle`` / ``output`` fp32 [rows, h, w, 10], row i belonging to ``images[i]`` /
+    ``words[i]``.  ``attn_out`` alone means ``attention=True``."""
+    if attn_out is not None and attention is None:
+        attention = True
     _check_sampler(sampler, skip_steps)
     if known is None and (keep_cols is not None or start is not None):
         raise ValueError("keep_cols and start need the known latents (known=)")
@@ -156,7 +164,7 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     world = w0 if world is None else world
     first, count = shard_range(len(rows), rank, world)
     mine = rows[first:first + count]
-    outs = []
+    outs, maps = [], []
     kmask = None
     if known is not None:
         if keep_cols is not None:
@@ -170,6 +178,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         labels = torch.tensor([wr_dict[s] for s, _, _ in chunk], dtype=torch.int64)
         phosc = torch.stack([phosc_of(wd) for wd in words]) if phosc_of is not None else None
         kw = dict(seed=seed, sample_offset=first + b0, mix_rate=mix_rate)
+        if attention is not None:
+            kw.update(attention=attention)
         if known is not None:
             kw.update(known=torch.stack(latents[b0:b0 + batch]), known_mask=kmask, start=start, known_noise=known_noise)
         if sampler == "ddim":
@@ -184,6 +194,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
             res = diffusion.sampling(model, vae, len(chunk), words, labels, args, phoscLabels=phosc, **kw)
         res = res.detach().cpu()
         outs.append(res)
+        if attention is not None:
+            maps.append({k: v.cpu() for k, v in diffusion.last_attention.items()})
         if out_dir is not None:
             for (_, image, _), item in zip(chunk, res):
                 if vae is None:
@@ -191,6 +203,10 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                 else:
                     arr = (item.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).numpy()
                     write_png(os.path.join(out_dir, f"{image}.png"), arr if arr.shape[2] == 3 else arr[:, :, 0])
+    if attn_out is not None and maps:
+        path = attn_out if (os.path.isabs(attn_out) or out_dir is None) else os.path.join(out_dir, attn_out)
+        np.savez_compressed(path, images=np.array([image for _, image, _ in mine]), words=np.array([t for _, _, t in mine]),
+                            **{k: torch.cat([m[k] for m in maps]).numpy() for k in maps[0]})
     return first, (torch.cat(outs) if outs else torch.empty(0))
 
 
@@ -302,6 +318,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--init_latents: keep the latent columns A <= column < B of the 32 and re-draw the rest")
     ap.add_argument("--start", type=int, default=None, metavar="T",
                     help="--init_latents: begin from the latent noised to level T (1 .. noise_steps - 1) instead of from noise")
+    ap.add_argument("--attn_maps", default=None, metavar="FILE",
+                    help="also save the per-character cross-attention maps of every generated row (.npz beside the images: input / "
+                         "middle / output [rows, h, w, 10], images, words); base model only")
+    ap.add_argument("--attn_window", default=None, metavar="HI:LO",
+                    help="--attn_maps: average over the model-calling steps with LO <= t <= HI only (default: all of them)")
     return ap
 
 
@@ -325,6 +346,20 @@ def parse_args(argv=None):
             ap.error("--init_latents needs --keep_cols A:B, --start T, or both")
         if a.start is not None and not 1 <= a.start <= a.noise_steps - 1:
             ap.error(f"--start must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.attn_window is not None:
+        if a.attn_maps is None:
+            ap.error("--attn_window needs --attn_maps (the file to write)")
+        parts = a.attn_window.split(":")
+        if len(parts) != 2 or not all(p.strip().isdigit() for p in parts) or int(parts[0]) < int(parts[1]):
+            ap.error(f"--attn_window takes HI:LO, two timesteps with HI >= LO, not {a.attn_window!r}")
+        a.attn_window = (int(parts[0]), int(parts[1]))
+    if a.attn_maps is not None:
+        if a.phosc:
+            ap.error("--attn_maps: the PHOSC model has no per-character attention maps")
+        if a.style_pair is not None:
+            ap.error("--style_pair strips do not take --attn_maps")
+        if not a.attn_maps.endswith(".npz"):
+            a.attn_maps += ".npz"
     if a.keep_cols is not None:
         parts = a.keep_cols.split(":")
         if len(parts) != 2 or not all(p.strip().isdigit() for p in parts):
@@ -392,7 +427,10 @@ def main(argv=None):
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
                             phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
                             dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing, known=known,
-                            keep_cols=a.keep_cols, start=a.start)
+                            keep_cols=a.keep_cols, start=a.start,
+                            attention=None if a.attn_maps is None else (a.attn_window or True),
+                            attn_out=None if a.attn_maps is None else
+                            (a.attn_maps if world == 1 else a.attn_maps[:-4] + f".rank{rank}.npz"))
     print(f"[rank {rank}/{world}] rows {start}..{start + len(res)} of {len(rows)} written to {a.save_path}/images")
 
 

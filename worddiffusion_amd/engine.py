@@ -309,6 +309,12 @@ class Plan:
         self.step: List[tuple] = []
         self.keep: List[object] = []
         self.out: Optional[torch.Tensor] = None
+        # attention maps (UNetEngine.plan attn_maps): the tapped SpatialTransformers, their buffers fp32 [B, h*w, L] and (h, w),
+        # the accumulate form's weight table
+        self.map_taps: tuple = ()
+        self.maps: List[torch.Tensor] = []
+        self.map_hw: List[tuple] = []
+        self.map_w: Optional[torch.Tensor] = None
 
     @staticmethod
     def _run(ops, stream):
@@ -1084,7 +1090,8 @@ class UNetEngine:
         heads, d = mod.heads, mod.d_head
         inner = heads * d
         L = self._ctx_len
-        if (self.fuse_st and self.variant != "phosc" and len(mod.transformer_blocks) == 1 and inner == c == 320 and
+        tap = name in P.map_taps  # its attn2 softmax is read back (attention maps): the chained form, plus one wd_xattn_maps
+        if (self.fuse_st and not tap and self.variant != "phosc" and len(mod.transformer_blocks) == 1 and inner == c == 320 and
                 self.npass == 3 and self.fuse_xattn and self.fuse_xattn_pair and self.fuse_ff and self.fuse_proj and
                 bool(self.lib.wd_xattn_supported(inner, heads, L)) and (M + 63) // 64 >= 192 and hw % 64 == 0 and
                 (name + ".tb0.ff1f.w") in self._w and
@@ -1103,11 +1110,28 @@ class UNetEngine:
         n1_pre = g_in._ln_pl
         xpl = None
         fuse = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))
+        folds = {}  # tag -> (mq_pl, mot_pl) of the block being planned
+
+        def maps(p, x_in, first):
+            """The attn2 softmax of block ``p`` summed over heads into this tap's map buffer: x_in is what the attention launch
+            just before read - the rows attn1 reads (first = "a1": the pair form runs attn1 again) or attn2's own input."""
+            g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
+            a = (g2, b2, folds["a1"][0].data_ptr(), folds["a1"][1].data_ptr(), self._w[f"{p}.a1.o.b"].data_ptr()) if first else \
+                (None,) * 5
+            buf = torch.zeros((B, hw, L), dtype=torch.float32, device=self.device)
+            P.maps.append(buf)
+            P.map_hw.append((h, w))
+            wt = P.map_w
+            ops.append((self.lib.wd_xattn_maps,
+                        (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, *a, g2, b2, folds["a2"][0].data_ptr(),
+                         buf.data_ptr(), L, _ptr(wt), wt.numel() if wt is not None else 0,
+                         P.map_k.data_ptr() if wt is not None else None), f"{p}.a2:maps"))
 
         def folded(tag, p, x_in, x_out, ln_name, next_ln=None, raw=None):
             """x_out = x_in + to_out(attention(to_q(LN(x_in)), K, V)) in one launch.  next_ln: also emit the following
             LayerNorm as operand planes.  raw: planes that take x_out itself (wd_xattn_planes)."""
             mq, mo, mq_pl, mot_pl = self._xattn_fold(P, f"{p}.{tag}", heads, d)
+            folds[tag] = (mq_pl, mot_pl)
             npl = self._planes(P, M, inner) if next_ln else None
             if raw is not None:
                 ops.append((self.lib.wd_xattn_planes,
@@ -1133,6 +1157,7 @@ class UNetEngine:
             planes that take x_out itself (wd_xattn_planes)."""
             _, _, qa, oa = self._xattn_fold(P, p + ".a1", heads, d)
             _, _, qb, ob = self._xattn_fold(P, p + ".a2", heads, d)
+            folds["a1"], folds["a2"] = (qa, oa), (qb, ob)
             npl = self._planes(P, M, inner)
             g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
             args = (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, g2, b2, qa.data_ptr(), oa.data_ptr(),
@@ -1162,6 +1187,8 @@ class UNetEngine:
             if fuse and self.variant != "phosc" and self.fuse_xattn_pair:
                 tok2 = self._f32(P, M, inner)
                 n3 = folded_pair(p, tok, tok2, raw=tok2pl)
+                if tap:
+                    maps(p, tok, "a1")
             tok1 = self._f32(P, M, inner) if n3 is None else None
             if n3 is not None:
                 pass
@@ -1194,6 +1221,8 @@ class UNetEngine:
             elif fuse:
                 tok2 = self._f32(P, M, inner)
                 n3 = folded("a2", p, tok1, tok2, "norm2", next_ln="norm3", raw=tok2pl)
+                if tap:
+                    maps(p, tok1, None)
             else:
                 tok2 = self._f32(P, M, inner)
                 n2 = n2_pre if (self.variant == "phosc" and n2_pre is not None) else \
@@ -1406,6 +1435,35 @@ class UNetEngine:
                         out_ld=cout, want_stats=want_stats, tile=tile)
         return Act(h0, cout, H, W, g0._stats), xin
 
+    def _map_taps(self, L: int) -> tuple:
+        """The three SpatialTransformers whose attn2 softmax the reference returns with --attentionMaps 1 (unet.py:1645-1832: the
+        last one of the input blocks, the middle one, the last one of the output blocks), by the names ``_trunk`` gives them.
+        Raises NotImplementedError where one of them does not run on the folded MFMA cross-attention - the only form whose
+        probabilities ``wd_xattn_maps`` reproduces."""
+        m = self.model
+        if self.variant == "phosc":
+            raise NotImplementedError("attention maps: the PHOSC model's cross-attention has ctx + PHOSC keys, and the reference "
+                                      "keeps a map only where it has 10 (unetPhosc.py: attn.shape[-1] == 10 is false)")
+        if not self.fuse_xattn or os.environ.get("WDIFF_XATTN_VALU"):
+            raise NotImplementedError("attention maps need the folded MFMA cross-attention (WDIFF_FUSE_XATTN=0 / WDIFF_XATTN_VALU "
+                                      "select forms that do not keep the probabilities wd_xattn_maps reports)")
+        taps = []
+        for prefix, blocks in (("in", list(enumerate(m.input_blocks))[1:]), ("mid", [(None, m.middle_block)]),
+                               ("out", list(enumerate(m.output_blocks)))):
+            found = [(f"{prefix}{'' if i is None else i}.{j}", mod) for i, blk in blocks for j, mod in enumerate(blk)
+                     if isinstance(mod, SpatialTransformerParams)]
+            if not found:
+                raise NotImplementedError(f"attention maps: no SpatialTransformer in the {prefix} blocks")
+            name, mod = found[-1]
+            if len(mod.transformer_blocks) != 1:
+                raise NotImplementedError("attention maps with transformer_depth > 1 (the reference keeps the last block's map; "
+                                          "not planned here)")
+            if not self.lib.wd_xattn_supported(mod.heads * mod.d_head, mod.heads, L):
+                raise NotImplementedError(f"attention maps: {name} ({mod.heads * mod.d_head} channels, {mod.heads} heads, {L} "
+                                          "keys) is outside wd_xattn_supported")
+            taps.append(name)
+        return tuple(taps)
+
     def _trunk(self, P: Plan, cur: Act) -> Act:
         """Input blocks after the first convolution, middle block, output blocks over the skip stack."""
         m = self.model
@@ -1450,7 +1508,8 @@ class UNetEngine:
         return g, otok
 
     def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0,
-             film_timesteps: Optional[tuple] = None) -> Plan:
+             film_timesteps: Optional[tuple] = None, attn_maps: bool = False, attn_rows: int = 0,
+             attn_by_step: bool = False) -> Plan:
         """film_steps = T > 0 (the DDPM sampler): the whole time / writer embedding path (timestep_embedding, time_embed,
         label_emb, SiLU, every emb_layers) is tabulated for all T timesteps by ``P.film`` ops - one large GEMM per
         ``sampling()`` call instead of three 64-row GEMMs per step - and each step copies its rows (``wd_select_rows``).
@@ -1462,8 +1521,16 @@ class UNetEngine:
 
         film_timesteps = tau (the DDIM sampler, with film_steps = T): the table covers the S visited timesteps only - row k is
         timestep tau[k], ``P.film_prepare`` takes the step index k, ``wd_select_rows`` reads it from ``P.k_dev`` and the pairs
-        of the interpolation path are indexed (forward, k, b)."""
+        of the interpolation path are indexed (forward, k, b).
+
+        attn_maps: the three tapped SpatialTransformers (``_map_taps``) run as the chained launches (never the one-launch form)
+        and each gains one ``wd_xattn_maps`` launch after its attention launch, into ``P.maps[i]`` fp32 [B, h_i*w_i, L].  Every
+        other launch is the default plan's with WDIFF_FUSE_ST=0 for those three blocks.  attn_rows = 0: a step overwrites the
+        maps.  attn_rows = R > 0 (the samplers): a step adds ``P.map_w[row] * map``, ``P.map_w`` fp32 [R] filled by the caller,
+        row = ``P.k_dev`` if attn_by_step else ``P.t_dev``; with mix = 2 only the first forward of a step adds."""
         key = (B, H, W, ctx_len, phosc_len, self.npass, film_steps) + ((("mix", mix),) if mix else ())
+        if attn_maps:
+            key += (("maps", int(attn_rows), bool(attn_by_step)),)
         if film_timesteps is not None:
             film_timesteps = tuple(int(t) for t in film_timesteps)
             if not film_steps or not film_timesteps or min(film_timesteps) < 0 or max(film_timesteps) >= film_steps:
@@ -1476,11 +1543,13 @@ class UNetEngine:
         lib = self.lib
         if ctx_len + phosc_len == 0:
             raise NotImplementedError("context=None: every reference script conditions on the word (unet.py:1605)")
+        taps = self._map_taps(ctx_len + phosc_len) if attn_maps else ()  # (raises before anything is built or launched)
         P = self._begin_plan(Plan(), B)
         dev = self.device
         mc = m.model_channels
         ted = 4 * mc
         self._inputs(P, H, W, ctx_len, phosc_len)
+        P.map_taps = taps
         # step-invariant: run once per call (P.cond)
         self._conditioning(P, P.cond, ctx_len, phosc_len)
 
@@ -1497,6 +1566,9 @@ class UNetEngine:
         self._film = self._f32(P, B, self.film_total)
         P.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
         P.k_dev = torch.zeros((1,), dtype=torch.int32, device=dev)  # index into film_timesteps (the table-driven loop)
+        if attn_maps and attn_rows:
+            P.map_w = torch.zeros((int(attn_rows),), dtype=torch.float32, device=dev)
+            P.map_k = P.k_dev if attn_by_step else P.t_dev
         P.film = []
         if film_steps:
             # the table holds ``chunk`` consecutive timesteps (rows (t % chunk) * B + b), not all T: T*B*film_total fp32 was
@@ -1620,7 +1692,9 @@ class UNetEngine:
             fn, args, what = step[-1]
             assert args[-1] == P.out.data_ptr(), what
             P.out1 = torch.empty_like(P.out)
-            P.step1 = [select1] + step[1:-1] + [(fn, args[:-1] + (P.out1.data_ptr(),), what)]
+            # (the attention maps accumulate over the first forward alone)
+            P.step1 = [select1] + [op for op in step[1:-1] if op[0] is not lib.wd_xattn_maps] + \
+                [(fn, args[:-1] + (P.out1.data_ptr(),), what)]
         self._plans[key] = P
         return P
 
@@ -1685,9 +1759,10 @@ class UNetEngine:
         if phosc is not None:
             P.phosc_in.copy_(phosc.to(torch.int32) if phosc.dtype != torch.int32 else phosc, non_blocking=True)
 
-    def forward(self, x, t, context, y, phosc=None, mix=None):
+    def forward(self, x, t, context, y, phosc=None, mix=None, attn_maps=False):
         """mix = (int pairs [B, 2], fp32 mix rates [B]): the writer term is the blend of each sample's pair and ``y`` is unused
-        (unet.py:1558-1573)."""
+        (unet.py:1558-1573).  attn_maps: returns (eps, [m_in, m_mid, m_out]), m_i fp32 [B, h_i, w_i, L]: the per-character
+        attention maps of the three tapped SpatialTransformers (``plan``)."""
         self.refresh_weights()
         B, _, H, W = x.shape
         ctx_len = 0 if context is None else context.shape[1]
@@ -1695,7 +1770,7 @@ class UNetEngine:
         if mix is not None:
             self.check_pairs(mix[0])
             y = None
-        P = self.plan(B, H, W, ctx_len, phosc_len, mix=1 if mix is not None else 0)
+        P = self.plan(B, H, W, ctx_len, phosc_len, mix=1 if mix is not None else 0, attn_maps=bool(attn_maps))
         self.check_ids(context, y, phosc, need_y=mix is None)
         self.load_inputs(P, x, t, context, y, phosc, check=False)
         if mix is not None:
@@ -1703,4 +1778,6 @@ class UNetEngine:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         P.run_cond(stream)
         P.run_step(stream)
+        if attn_maps:
+            return P.out.clone(), [mp.clone().reshape(B, mh, mw, -1) for mp, (mh, mw) in zip(P.maps, P.map_hw)]
         return P.out.clone()

@@ -48,7 +48,12 @@ class UNetBase(nn.Module):
             raise NotImplementedError("n_embed (codebook id prediction) is not on the accelerated path")
         if isinstance(context_dim, (list, tuple)):
             context_dim = list(context_dim)[0]
-        for flag in ("charImages", "attentionMaps", "ocrTraining", "wrdChrWrStyl"):
+        if _arg(args, "attentionMaps", 0):
+            # (with the flag the reference also registers the middle block under other names, unet.py:1336-1364)
+            raise NotImplementedError("args.attentionMaps=1: build the model with attentionMaps=0 and ask a forward for the maps "
+                                      "with return_attention= (samplers: attention=); a checkpoint saved by an attentionMaps=1 run "
+                                      "loads after remap_attention_maps_state_dict(state_dict)")
+        for flag in ("charImages", "ocrTraining", "wrdChrWrStyl"):
             if _arg(args, flag, 0):
                 raise NotImplementedError(f"args.{flag}=1 selects an auxiliary head / debugging output that is "
                                           "outside the accelerated denoising path (SURVEY.md 8b)")
@@ -212,8 +217,10 @@ class UNetBase(nn.Module):
         eng.dropout_seed, eng.dropout_row_base = int(seed), int(row_base)
         return self
 
-    def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None):
+    def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None, return_attention=False):
         autograd = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if return_attention is not False:
+            return self._run_attention(x, timesteps, context, y, phosc, mix_rate, return_attention, autograd)
         if self.training and not autograd and float(self.dropout) > 0:
             # the inference engine has no dropout: running it here would silently skip the layer train mode asks for
             raise NotImplementedError(f"train mode with dropout={self.dropout} outside autograd: the HIP inference path applies "
@@ -239,12 +246,71 @@ class UNetBase(nn.Module):
         out = self.engine.forward(x.float(), timesteps, context, y, phosc)
         return out.type(x.dtype)
 
+    def _run_attention(self, x, timesteps, context, y, phosc, mix_rate, mode, autograd):
+        """``forward(..., return_attention=True | "reference")``: the predicted noise and the per-character attention maps of the
+        three SpatialTransformers the reference taps with --attentionMaps 1 (unet.py:1645-1832), each the softmax of the block's
+        attn2 summed over heads.  True: ``(eps, attn1, attn2, attn3)``, fp32 [B, h_i, w_i, L] at latent resolution.
+        "reference": ``(eps, attn1, attn2, attn3, context)`` as the reference returns them - the maps replicated x8 / x16 / x8
+        (its nearest-neighbour F.interpolate, unet.py:1761-1778) and the word encoder's output [B, L, context_dim]."""
+        if mode is not True and mode != "reference":
+            raise ValueError(f"return_attention must be False, True or 'reference', not {mode!r}")
+        if autograd:
+            raise NotImplementedError("return_attention under autograd: the attention maps are an inference-only output")
+        if self.interpolation and mix_rate is not None:
+            raise NotImplementedError("return_attention together with mix_rate")
+        if self.training and float(self.dropout) > 0:
+            raise NotImplementedError(f"train mode with dropout={self.dropout} outside autograd: call model.eval() first")
+        eng = self.engine
+        out, maps = eng.forward(x.float(), timesteps, context, y, phosc, attn_maps=True)
+        out = out.type(x.dtype)
+        if mode is True:
+            return (out, *maps)
+        B, L = x.shape[0], maps[0].shape[-1]
+        P = eng.plan(B, x.shape[2], x.shape[3], L, 0, attn_maps=True)  # (the plan that just ran: its word-encoder planes)
+        # (held as split-bf16 operand planes, hi + lo: 16 significant bits of the reference's fp32 tensor)
+        ctx = (P.ctx_pl[0].float() + P.ctx_pl[1].float() if eng.npass == 3 else P.ctx_pl[0].float()).reshape(B, L, -1)
+        big = [m.repeat_interleave(f, 1).repeat_interleave(f, 2) for m, f in zip(maps, (8, 16, 8))]
+        return (out, *big, ctx)
+
     def _grad_anchor(self, device):
         a = self.__dict__.get("_anchor")
         if a is None or a.device != device:
             a = torch.zeros(1, device=device, requires_grad=True)
             self.__dict__["_anchor"] = a
         return a
+
+
+_MAPS_KEYS = (("middle_block1.0.0.", "middle_block.0."), ("middle_block1.0.1.", "middle_block.1."),
+              ("middle_block1.1.0.", "middle_block.2."))
+
+
+def _rename_keys(sd, pairs):
+    out = type(sd)()
+    if hasattr(sd, "_metadata"):
+        out._metadata = sd._metadata
+    for k, v in sd.items():
+        for old, new in pairs:
+            if k.startswith(old):
+                k = new + k[len(old):]
+                break
+        if k in out:
+            raise KeyError(f"two keys map to {k!r}")
+        out[k] = v
+    return out
+
+
+def remap_attention_maps_state_dict(sd):
+    """A state dict saved by a reference model built with ``--attentionMaps 1`` -> the keys of this package's models (and of the
+    reference without the flag): with the flag the reference registers the middle block as ``middle_block1`` =
+    ``[[ResBlock, SpatialTransformer], [ResBlock]]`` (unet.py:1336-1364), so ``middle_block1.0.0.`` -> ``middle_block.0.``,
+    ``middle_block1.0.1.`` -> ``middle_block.1.``, ``middle_block1.1.0.`` -> ``middle_block.2.``.  Every other key, and every
+    tensor, is passed through; the order is kept."""
+    return _rename_keys(sd, _MAPS_KEYS)
+
+
+def to_attention_maps_state_dict(sd):
+    """The inverse of ``remap_attention_maps_state_dict``: this package's keys -> those an ``--attentionMaps 1`` reference loads."""
+    return _rename_keys(sd, tuple((new, old) for old, new in _MAPS_KEYS))
 
 
 class _HipUNetStep(torch.autograd.Function):

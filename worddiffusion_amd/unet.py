@@ -27,12 +27,16 @@ class UNetModel(UNetBase):
         self.res = ResBlockConditionalParams()  # unet.py:1472 - dead parameters kept for checkpoint parity
 
     def forward(self, x, wrdChrWrStyl=None, original_images=None, timesteps=None, context=None, y=None,
-                charContextImages=None, original_context=None, or_images=None, mix_rate=None, **kwargs):
-        """Predicted noise [B, out_channels, H, W] (``unet.py:1499``; returns ``h`` as at ``:1821/:1836``)."""
+                charContextImages=None, original_context=None, or_images=None, mix_rate=None, return_attention=False,
+                **kwargs):
+        """Predicted noise [B, out_channels, H, W] (``unet.py:1499``; returns ``h`` as at ``:1821/:1836``).
+        ``return_attention=True``: ``(eps, attn1, attn2, attn3)``, the per-character cross-attention maps fp32 [B, h, w, L] of
+        the last input, the middle and the last output SpatialTransformer; ``"reference"``: the tuple the reference returns with
+        ``--attentionMaps 1`` (``UNetBase._run_attention``).  Inference only."""
         self._check_common(x, timesteps, mix_rate)
         self._check_context(context)
         if self.num_classes is not None:
             if _arg(self.args, "imgConditioned", 0) == 1:
                 raise NotImplementedError("args.imgConditioned=1 drops the writer embedding (unet.py:1578-1579)")
             assert y is not None and tuple(y.shape) == (x.shape[0],), "y must be [B] (unet.py:1555)"
-        return self._run(x, timesteps, context, y, mix_rate=mix_rate)
+        return self._run(x, timesteps, context, y, mix_rate=mix_rate, return_attention=return_attention)

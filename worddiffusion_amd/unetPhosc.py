@@ -14,8 +14,12 @@ from .model import UNetBase, _arg
 class UNetModelPhosc(UNetBase):
     variant = "phosc"
 
-    def forward(self, x, phoscLabels=None, timesteps=None, context=None, y=None, mix_rate=None, **kwargs):
+    def forward(self, x, phoscLabels=None, timesteps=None, context=None, y=None, mix_rate=None, return_attention=False,
+                **kwargs):
         self._check_common(x, timesteps, mix_rate)
+        if return_attention is not False:
+            # the reference keeps a map only where the attention has 10 keys; this model's has the PHOSC keys as well
+            raise NotImplementedError("return_attention: the PHOSC model has no per-character attention maps")
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"  # unetPhosc.py:1079-1081
         if y is not None and y.shape[0] != x.shape[0]:
