@@ -29,7 +29,7 @@ def test_select_rows_behind_guard_bands(B, row_floats):
     one resident chunk serves all timesteps), nothing written outside out, nothing read outside the table (its pads are NaN).
 
     A negative *t_dev cannot reach the kernel (C's % would keep the sign and the read start before the table): the index is
-    P.t_dev or P.k_dev (engine.py plan()); diffusion.py fills t_dev with the sampler's first timestep (>= 0) and steps it down by
+    P.t_dev or P.k_dev (engine.py _film_table); diffusion.py fills t_dev with the sampler's first timestep (>= 0) and steps it down by
     one after each step of the DDPM loop, whose last selecting step is t = 1; k_dev starts at zero and wd_next_timestep clamps it
     to [0, S - 1]."""
     lib = N.lib()

@@ -14,8 +14,8 @@ dense launch, nothing written outside, and the same bits in the planes that rema
 heads * L takes 1 (a softmax of one key), 16, 17, 32, 33 and 40: the borders of the three 16-row score tiles and of the two 32-pair
 output k-steps of xattn16_kernel; hw takes 1, 15, 16, 17 and 70 (its 16-token tiles, the 64-token tiles of xattn_fused_kernel).
 
-out == x is not a case: the engine never passes it (engine.py _transformer: folded() and folded_pair() write tok1 / tok2, fresh
-buffers, from tok; _transformer_fused does not call these entry points at all).
+out == x is not a case: the engine never passes it (engine.py: _st_attn_folded and _st_attn_pair write fresh buffers from the
+rows they read; _transformer_fused does not call these entry points at all).
 
 Largest max_rel against fp64 seen on an MI355X (out / LayerNorm planes; tolerances 2e-5 / 3e-5):
   xattn_fold_kernel        the seven shapes: mq 6.3e-07, mo 5.9e-07

@@ -16,6 +16,7 @@ Torch is used for device memory, the weight repack at load time and stream handl
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -301,6 +302,16 @@ class Act:
         self.stats = stats  # (part tensor [B, nchunk, c / part_cpg, 2] f64, nchunk, part_cpg) once known
         self.prod = prod    # the WdGemmArgs of the GEMM whose epilogue writes ``t``: a consumer that wants the operand planes of
         #                     this very tensor asks that epilogue for them instead of launching wd_split
+
+
+# How one SpatialTransformer is launched (UNetEngine._st_form) and what every stage of it needs to know:
+#   form   "one-launch" (GroupNorm to proj_out in one launch), else how the chain runs attn1 / attn2: "pair" | "folded" | "phosc" | "plain"
+#   tail   how the last block's feed-forward meets proj_out: "ff+proj" | "two-source" | "proj_out"
+#   M = B * hw token rows of inner = heads * d channels (the map has c), L context keys
+#   tap    an attention-map tap of the plan: one wd_xattn_maps launch behind the attentions
+#   gn_in  proj_in applies the GroupNorm itself while it stages the fp32 map (no wd_gn_apply launch)
+#   xfold  the cross-attentions run folded (wd_xattn_fold): one launch each, or one for the pair
+StForm = collections.namedtuple("StForm", "form tail B h w c hw M heads d inner L tap gn_in xfold")
 
 
 class Plan:
@@ -1082,212 +1093,255 @@ class UNetEngine:
                         mq.data_ptr(), mo.data_ptr(), mq_pl.data_ptr(), mot_pl.data_ptr()), at + ":fold"))
         return mq, mo, mq_pl, mot_pl
 
-    def _transformer(self, P, name, mod: SpatialTransformerParams, x: Act) -> Act:
-        ops = P.step
-        B = self._B
-        h, w, c = x.h, x.w, x.c
+    def _xattn_mfma(self) -> bool:
+        """Do the folded cross-attention launches run on the MFMA units?  WDIFF_XATTN_VALU selects their fp32 VALU form, which writes
+        no operand planes of its result and is not the arithmetic wd_xattn_maps repeats.  Read at plan time, not in __init__: the C
+        side reads the variable at every call."""
+        return not os.environ.get("WDIFF_XATTN_VALU")
+
+    def _ff_fills_chip(self, p, M) -> bool:
+        """Does block ``p`` run its feed-forward as wd_ff_fused?  One workgroup per 64 tokens: worth it once they fill the chip (the
+        8 x 32 level at batch >= 48)."""
+        return self.fuse_ff and (p + ".ff1f.w") in self._w and (M + 63) // 64 >= 192
+
+    def _st_form(self, P, name, mod: SpatialTransformerParams, x: Act) -> StForm:
+        """The launch form of SpatialTransformer ``name`` reading the map ``x`` under this engine's switches, with the sizes every
+        stage needs (DESIGN.md "SpatialTransformer launch forms" is this function as a table)."""
+        B, h, w, c = self._B, x.h, x.w, x.c
         hw, M = h * w, B * h * w
-        heads, d = mod.heads, mod.d_head
+        heads, d, L = mod.heads, mod.d_head, self._ctx_len
         inner = heads * d
-        L = self._ctx_len
-        tap = name in P.map_taps  # its attn2 softmax is read back (attention maps): the chained form, plus one wd_xattn_maps
-        if (self.fuse_st and not tap and self.variant != "phosc" and len(mod.transformer_blocks) == 1 and inner == c == 320 and
-                self.npass == 3 and self.fuse_xattn and self.fuse_xattn_pair and self.fuse_ff and self.fuse_proj and
-                bool(self.lib.wd_xattn_supported(inner, heads, L)) and (M + 63) // 64 >= 192 and hw % 64 == 0 and
-                (name + ".tb0.ff1f.w") in self._w and
-                self._gn_in_consumer(P, ops, name + ".gn", [x], False, M, hw, inner)):
-            return self._transformer_fused(P, name, mod, x)
-        tok = self._f32(P, M, inner)
-        # (PHOSC variant: the first block's norm1 planes come out of proj_in's epilogue where its tiles hold whole rows)
-        ln1 = f"{name}.tb0.norm1" if self.variant == "phosc" else None
-        if self._gn_in_consumer(P, ops, name + ".gn", [x], False, M, hw, inner):
-            g_in = self._gemm(ops, name + ".proj_in", [self._src32(x, hw_src=hw)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
-                              out_f32=tok, out_ld=inner, a32=(x, name + ".gn", 1e-6, False), ln=ln1)
+        nblk = len(mod.transformer_blocks)
+        tap = name in P.map_taps
+        xfold = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))  # K/V/to_q/to_out folded per sample (<= 10 keys)
+        # asked once, before anything of the block is planned: where ``x`` has no statistics yet the question appends their
+        # wd_gn_stats launch, which is the block's first op in every form
+        gn_in = self._gn_in_consumer(P, P.step, name + ".gn", [x], False, M, hw, inner)
+        one_launch = (
+            self.fuse_st and                          # WDIFF_FUSE_ST=0: the tests' reference for this form
+            not tap and                               # its attn2 softmax is read back (attention maps): needs attn2's input in memory
+            self.variant != "phosc" and               # the front runs two cross-attentions; PHOSC blocks start with self-attention
+            nblk == 1 and                             # the front feeds the feed-forward and proj_out tail of the same block
+            inner == c == 320 and                     # the kernel is built for 320-channel rows
+            self.npass == 3 and                       # ... and for split-bf16 operands
+            xfold and self.fuse_xattn_pair and        # it is the pair form kept on chip: each switch that undoes that undoes this
+            self.fuse_ff and self.fuse_proj and       # the front only comes with the feed-forward + proj_out tail
+            (M + 63) // 64 >= 192 and                 # one workgroup per 64-token panel: they must fill the chip
+            hw % 64 == 0 and                          # a panel must not straddle two samples
+            (name + ".tb0.ff1f.w") in self._w and     # wd_ff_supported(inner, hidden width): the weights were packed for it
+            gn_in)                                    # the front normalises the fp32 map as proj_in's own staging would
+        if one_launch:
+            form = "one-launch"
+        elif xfold and self.variant != "phosc" and self.fuse_xattn_pair:
+            form = "pair"
+        elif self.variant == "phosc":
+            form = "phosc"
         else:
-            g, _ = self._gn(P, ops, name + ".gn", [x], name + ".gn", 1e-6, False)
-            g_in = self._gemm(ops, name + ".proj_in", [self._src(g, c)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
-                              out_f32=tok, out_ld=inner, ln=ln1)
-        n1_pre = g_in._ln_pl
-        xpl = None
-        fuse = self.fuse_xattn and bool(self.lib.wd_xattn_supported(inner, heads, L))
-        folds = {}  # tag -> (mq_pl, mot_pl) of the block being planned
+            form = "folded" if xfold else "plain"
+        ff_fused = self._ff_fills_chip(f"{name}.tb{nblk - 1}", M)
+        if ff_fused and self.fuse_proj and inner == c:
+            tail = "ff+proj"
+        elif (not ff_fused and self.fold_proj and self.npass == 3 and (name + ".po32.w") in self._w and
+              xfold and self._xattn_mfma()):   # (tok2 as operand planes: the MFMA form of the folded cross-attention writes them)
+            tail = "two-source"
+        else:
+            tail = "proj_out"
+        return StForm(form, tail, B, h, w, c, hw, M, heads, d, inner, L, tap, gn_in, xfold)
 
-        def maps(p, x_in, first):
-            """The attn2 softmax of block ``p`` summed over heads into this tap's map buffer: x_in is what the attention launch
-            just before read - the rows attn1 reads (first = "a1": the pair form runs attn1 again) or attn2's own input."""
-            g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
-            a = (g2, b2, folds["a1"][0].data_ptr(), folds["a1"][1].data_ptr(), self._w[f"{p}.a1.o.b"].data_ptr()) if first else \
-                (None,) * 5
-            buf = torch.zeros((B, hw, L), dtype=torch.float32, device=self.device)
-            P.maps.append(buf)
-            P.map_hw.append((h, w))
-            wt = P.map_w
-            ops.append((self.lib.wd_xattn_maps,
-                        (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, *a, g2, b2, folds["a2"][0].data_ptr(),
-                         buf.data_ptr(), L, _ptr(wt), wt.numel() if wt is not None else 0,
-                         P.map_k.data_ptr() if wt is not None else None), f"{p}.a2:maps"))
+    def _transformer(self, P, name, mod: SpatialTransformerParams, x: Act) -> Act:
+        f = self._st_form(P, name, mod, x)
+        if f.form == "one-launch":
+            return self._transformer_fused(P, f, name, mod, x)
+        return self._transformer_chain(P, f, name, mod, x)
 
-        def folded(tag, p, x_in, x_out, ln_name, next_ln=None, raw=None):
-            """x_out = x_in + to_out(attention(to_q(LN(x_in)), K, V)) in one launch.  next_ln: also emit the following
-            LayerNorm as operand planes.  raw: planes that take x_out itself (wd_xattn_planes)."""
-            mq, mo, mq_pl, mot_pl = self._xattn_fold(P, f"{p}.{tag}", heads, d)
-            folds[tag] = (mq_pl, mot_pl)
-            npl = self._planes(P, M, inner) if next_ln else None
-            if raw is not None:
-                ops.append((self.lib.wd_xattn_planes,
-                            (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, self._w[f"{p}.{ln_name}.g"].data_ptr(),
-                             self._w[f"{p}.{ln_name}.b"].data_ptr(), mq_pl.data_ptr(), mot_pl.data_ptr(),
-                             self._w[f"{p}.{tag}.o.b"].data_ptr(), None, None, None, None, None, x_out.data_ptr(), inner,
-                             self._w[f"{p}.{next_ln}.g"].data_ptr() if next_ln else None,
-                             self._w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5, *self._hilo(npl), inner,
-                             *self._hilo(raw), inner), f"{p}.{tag}:folded + planes"))
-                return npl
-            ops.append((self.lib.wd_xattn_fused,
-                        (x_in.data_ptr(), inner, B, hw, inner, self._w[f"{p}.{ln_name}.g"].data_ptr(),
-                         self._w[f"{p}.{ln_name}.b"].data_ptr(), 1e-5, mq.data_ptr(), mo.data_ptr(), heads, L,
-                         self._w[f"{p}.{tag}.o.b"].data_ptr(), x_out.data_ptr(), inner,
-                         self._w[f"{p}.{next_ln}.g"].data_ptr() if next_ln else None,
-                         self._w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5, *self._hilo(npl), inner,
-                         mq_pl.data_ptr(), mot_pl.data_ptr()),
-                        f"{p}.{tag}:folded"))
-            return npl
-
-        def folded_pair(p, x_in, x_out, raw=None):
-            """Both cross-attentions of a base-model block (each behind norm2, unet.py:337-345) and norm3 in one launch.  raw:
-            planes that take x_out itself (wd_xattn_planes)."""
-            _, _, qa, oa = self._xattn_fold(P, p + ".a1", heads, d)
-            _, _, qb, ob = self._xattn_fold(P, p + ".a2", heads, d)
-            folds["a1"], folds["a2"] = (qa, oa), (qb, ob)
-            npl = self._planes(P, M, inner)
-            g2, b2 = self._w[f"{p}.norm2.g"].data_ptr(), self._w[f"{p}.norm2.b"].data_ptr()
-            args = (x_in.data_ptr(), inner, B, hw, inner, 1e-5, heads, L, g2, b2, qa.data_ptr(), oa.data_ptr(),
-                    self._w[f"{p}.a1.o.b"].data_ptr(), g2, b2, qb.data_ptr(), ob.data_ptr(),
-                    self._w[f"{p}.a2.o.b"].data_ptr(), x_out.data_ptr(), inner, self._w[f"{p}.norm3.g"].data_ptr(),
-                    self._w[f"{p}.norm3.b"].data_ptr(), 1e-5, *self._hilo(npl), inner)
-            if raw is not None:
-                ops.append((self.lib.wd_xattn_planes, args + (*self._hilo(raw), inner), f"{p}.a1+a2:folded + planes"))
-            else:
-                ops.append((self.lib.wd_xattn_pair, args, f"{p}.a1+a2:folded"))
-            return npl
-
+    def _transformer_chain(self, P, f: StForm, name, mod: SpatialTransformerParams, x: Act) -> Act:
+        """proj_in, then per block the attentions of ``f.form`` and the feed-forward; the last block ends in the tail ``f.tail``."""
+        tok, n1 = self._st_proj_in(P, f, name, x)
         for di, tb in enumerate(mod.transformer_blocks):
             p = f"{name}.tb{di}"
-            scale = d ** -0.5
-            n3 = None
             last = di == len(mod.transformer_blocks) - 1
             ffi = tb.ff.net[2].in_features
-            ff_fused = self.fuse_ff and (p + ".ff1f.w") in self._w and (M + 63) // 64 >= 192
-            # the unfused tail folded (ff2 + proj_out as one two-source GEMM): it reads tok2 as operand planes, which the MFMA form
-            # of the folded cross-attention writes beside the fp32 rows
-            tok2pl = None
-            if (last and not ff_fused and self.fold_proj and self.npass == 3 and fuse and (name + ".po32.w") in self._w and
-                    not os.environ.get("WDIFF_XATTN_VALU")):
-                tok2pl = self._planes(P, M, inner)
-            # ---- attn1
-            if fuse and self.variant != "phosc" and self.fuse_xattn_pair:
-                tok2 = self._f32(P, M, inner)
-                n3 = folded_pair(p, tok, tok2, raw=tok2pl)
-                if tap:
-                    maps(p, tok, "a1")
-            tok1 = self._f32(P, M, inner) if n3 is None else None
-            if n3 is not None:
-                pass
-            elif self.variant == "phosc":
-                n1 = n1_pre if (di == 0 and n1_pre is not None) else self._ln(P, ops, p + ".norm1", tok, M, inner, p + ".norm1")
-                qkv = self._f32(P, M, 3 * inner)
-                self._gemm(ops, p + ".a1.qkv", [self._src(n1, inner)], p + ".a1.qkv.w", M, hw, out_f32=qkv,
-                           out_ld=3 * inner)
-                o1 = self._planes(P, M, inner)
-                self._attention(ops, p + ".a1", qkv.data_ptr(), 3 * inner, qkv.data_ptr() + 4 * inner, 3 * inner,
-                                qkv.data_ptr() + 8 * inner, 3 * inner, heads, hw, hw, d, scale, o1)
-                n2_pre = self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
-                                    resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner,
-                                    ln=None if fuse else p + ".norm2")._ln_pl
-            elif fuse:
-                folded("a1", p, tok, tok1, "norm2")  # the base model reads norm2 for both attentions (unet.py:337-345)
-            else:
-                n1 = self._ln(P, ops, p + ".norm2a", tok, M, inner, p + ".norm2")
-                q1 = self._f32(P, M, inner)
-                self._gemm(ops, p + ".a1.q", [self._src(n1, inner)], p + ".a1.q.w", M, hw, out_f32=q1, out_ld=inner)
-                ko = self.kv_off[p + ".a1"]
-                o1 = self._planes(P, M, inner)
-                self._attention(ops, p + ".a1", q1.data_ptr(), inner, self._kv.data_ptr() + 4 * ko, self.kv_total,
-                                self._kv.data_ptr() + 4 * (ko + inner), self.kv_total, heads, hw, L, d, scale, o1)
-                self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
-                           resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner)
-            # ---- attn2 (cross)
-            if n3 is not None:
-                pass
-            elif fuse:
-                tok2 = self._f32(P, M, inner)
-                n3 = folded("a2", p, tok1, tok2, "norm2", next_ln="norm3", raw=tok2pl)
-                if tap:
-                    maps(p, tok1, None)
-            else:
-                tok2 = self._f32(P, M, inner)
-                n2 = n2_pre if (self.variant == "phosc" and n2_pre is not None) else \
-                    self._ln(P, ops, p + ".norm2", tok1, M, inner, p + ".norm2")
-                q2 = self._f32(P, M, inner)
-                self._gemm(ops, p + ".a2.q", [self._src(n2, inner)], p + ".a2.q.w", M, hw, out_f32=q2, out_ld=inner)
-                ko = self.kv_off[p + ".a2"]
-                o2 = self._planes(P, M, inner)
-                kp, vp = self._kv.data_ptr() + 4 * ko, self._kv.data_ptr() + 4 * (ko + inner)
-                nimg = self.lib.wd_attention_packed_elems(B, heads, L, d) if self.pack_kv else 0
-                if nimg > 0:
-                    # the context's keys / values do not change during a sampling call: their split-bf16 LDS images are built
-                    # once per call (P.cond, after the K/V projection) and every step's attention copies them 16 bytes at a time
-                    img = torch.empty(nimg, dtype=torch.bfloat16, device=self.device)
-                    P.keep.append(img)
-                    P.cond.append((self.lib.wd_attention_pack_kv,
-                                   (kp, self.kv_total, vp, self.kv_total, B, heads, L, d, img.data_ptr()), p + ".a2:pack kv"))
-                    ops.append((self.lib.wd_attention_packed,
-                                (q2.data_ptr(), inner, img.data_ptr(), B, heads, hw, L, d, float(scale), None, *self._hilo(o2), inner,
-                                 hw, 0), p + ".a2"))
-                else:
-                    self._attention(ops, p + ".a2", q2.data_ptr(), inner, kp, self.kv_total, vp, self.kv_total, heads, hw, L, d,
-                                    scale, o2)
-                n3 = self._gemm(ops, p + ".a2.out", [self._src(o2, inner)], p + ".a2.o.w", M, hw, bias=self._w[p + ".a2.o.b"],
-                                resid=tok1.data_ptr(), resid_ld=inner, out_f32=tok2, out_ld=inner, ln=p + ".norm3")._ln_pl
-            # ---- GEGLU feed-forward
+            tok2pl = self._planes(P, f.M, f.inner) if last and f.tail == "two-source" else None
+            tok2, n3, tapped = self._st_attention(P, f, p, tok, n1 if di == 0 else None, tok2pl)
+            if f.tap:
+                self._st_maps(P, f, p, *tapped)
             if n3 is None:
-                n3 = self._ln(P, ops, p + ".norm3", tok2, M, inner, p + ".norm3")
-            if tok2pl is not None:
-                ffh = self._planes(P, M, ffi)
-                self._gemm(ops, p + ".ff1", [self._src(n3, inner)], p + ".ff1.w", M, hw, bias=self._w[p + ".ff1.b"],
-                           act=N.ACT_GEGLU, out_pl=ffh, tile=geglu_tile(ffi))
-                out = self._f32(P, M, c)
-                gg = self._gemm(ops, name + ".ff2 + proj_out", [self._src(ffh, ffi), self._src(tok2pl, inner)], name + ".po32.w", M, hw,
-                                bias=self._w[name + ".b32"], resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True)
-                return Act(out, c, h, w, gg._stats, prod=gg)
-            tok = self._f32(P, M, inner)
-            xpl = self._planes(P, M, inner) if last else None
-            if ff_fused:
-                # one workgroup per 64 tokens: worth it once they fill the chip (the 8 x 32 level at batch >= 48)
-                if last and self.fuse_proj and inner == c:
-                    out = self._f32(P, M, c)
-                    fa = self._ff_fused(ops, p, n3, tok2, M, inner, ffi, out, None,
-                                        proj=(name + ".po.w", self._w[name + ".po.b"], x.t, hw))
-                    return Act(out, c, h, w, fa._stats, prod=fa)
-                self._ff_fused(ops, p, n3, tok2, M, inner, ffi, None if last else tok, xpl)
-            else:
-                ffh = self._planes(P, M, ffi)
-                self._gemm(ops, p + ".ff1", [self._src(n3, inner)], p + ".ff1.w", M, hw, bias=self._w[p + ".ff1.b"],
-                           act=N.ACT_GEGLU, out_pl=ffh, tile=geglu_tile(ffi))
-                self._gemm(ops, p + ".ff2", [self._src(ffh, ffi)], p + ".ff2.w", M, hw, bias=self._w[p + ".ff2.b"],
-                           resid=tok2.data_ptr(), resid_ld=inner, out_f32=None if last else tok, out_ld=inner,
-                           out_pl=xpl)
-        out = self._f32(P, M, c)
-        gg = self._gemm(ops, name + ".proj_out", [self._src(xpl, inner)], name + ".po.w", M, hw,
-                        bias=self._w[name + ".po.b"], resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c,
-                        want_stats=True)
-        return Act(out, c, h, w, gg._stats, prod=gg)
+                n3 = self._ln(P, P.step, p + ".norm3", tok2, f.M, f.inner, p + ".norm3")
+            if last:
+                return self._st_tail(P, f, name, p, ffi, n3, tok2, tok2pl, x)
+            tok = self._f32(P, f.M, f.inner)
+            self._st_ff(P, f, p, ffi, n3, tok2, tok, None)
 
-    def _transformer_fused(self, P, name, mod: SpatialTransformerParams, x: Act) -> Act:
+    def _st_proj_in(self, P, f: StForm, name, x: Act):
+        """GroupNorm + proj_in -> the token rows [M, inner]; f.gn_in: the GEMM normalises the fp32 map itself while it stages it.
+        Also returns the first block's norm1 planes where proj_in's epilogue wrote them (PHOSC variant, tiles that hold whole rows)."""
+        tok = self._f32(P, f.M, f.inner)
+        if f.gn_in:
+            src, a32 = self._src32(x, hw_src=f.hw), (x, name + ".gn", 1e-6, False)
+        else:
+            g, _ = self._gn(P, P.step, name + ".gn", [x], name + ".gn", 1e-6, False)
+            src, a32 = self._src(g, f.c), None
+        g_in = self._gemm(P.step, name + ".proj_in", [src], name + ".pi.w", f.M, f.hw, bias=self._w[name + ".pi.b"], out_f32=tok,
+                          out_ld=f.inner, a32=a32, ln=f"{name}.tb0.norm1" if self.variant == "phosc" else None)
+        return tok, g_in._ln_pl
+
+    def _st_attention(self, P, f: StForm, p, tok, n1, tok2pl):
+        """attn1 and attn2 of block ``p`` as ``f.form`` plans them -> (tok2, norm3 planes or None, what a maps tap reads).
+        n1: norm1 planes already made (PHOSC).  tok2pl: planes that also take tok2 itself."""
+        if f.form == "pair":
+            return self._st_attn_pair(P, f, p, tok, tok2pl)
+        n2 = None
+        if f.form == "phosc":
+            tok1, n2 = self._st_attn_self(P, f, p, tok, n1)
+        elif f.form == "folded":
+            tok1, _, _ = self._st_attn_folded(P, f, p, "a1", tok)
+        else:  # (the base model reads norm2 for both attentions, unet.py:337-345)
+            tok1, _ = self._st_attn_plain(P, f, p, "a1", tok, self._ln(P, P.step, p + ".norm2a", tok, f.M, f.inner, p + ".norm2"))
+        if f.xfold:
+            tok2, n3, fold = self._st_attn_folded(P, f, p, "a2", tok1, next_ln="norm3", raw=tok2pl)
+            return tok2, n3, (tok1, None, fold)
+        if n2 is None:
+            n2 = self._ln(P, P.step, p + ".norm2", tok1, f.M, f.inner, p + ".norm2")
+        return (*self._st_attn_plain(P, f, p, "a2", tok1, n2, next_ln="norm3", pack=self.pack_kv), None)
+
+    def _st_attn_pair(self, P, f: StForm, p, x_in, raw=None):
+        """Both cross-attentions of a base-model block (each behind norm2, unet.py:337-345) and norm3 in one launch.  raw: planes
+        that take the result itself (wd_xattn_planes)."""
+        w, inner = self._w, f.inner
+        fa, fb = (self._xattn_fold(P, f"{p}.{tag}", f.heads, f.d)[2:] for tag in ("a1", "a2"))
+        x_out, npl = self._f32(P, f.M, inner), self._planes(P, f.M, inner)
+        g2, b2 = w[f"{p}.norm2.g"].data_ptr(), w[f"{p}.norm2.b"].data_ptr()
+        args = (x_in.data_ptr(), inner, f.B, f.hw, inner, 1e-5, f.heads, f.L, g2, b2, fa[0].data_ptr(), fa[1].data_ptr(),
+                w[f"{p}.a1.o.b"].data_ptr(), g2, b2, fb[0].data_ptr(), fb[1].data_ptr(), w[f"{p}.a2.o.b"].data_ptr(),
+                x_out.data_ptr(), inner, w[f"{p}.norm3.g"].data_ptr(), w[f"{p}.norm3.b"].data_ptr(), 1e-5, *self._hilo(npl), inner)
+        if raw is not None:
+            P.step.append((self.lib.wd_xattn_planes, args + (*self._hilo(raw), inner), f"{p}.a1+a2:folded + planes"))
+        else:
+            P.step.append((self.lib.wd_xattn_pair, args, f"{p}.a1+a2:folded"))
+        return x_out, npl, (x_in, fa, fb)
+
+    def _st_attn_folded(self, P, f: StForm, p, tag, x_in, next_ln=None, raw=None):
+        """x_out = x_in + to_out(attention(to_q(norm2(x_in)), K, V)) in one launch.  next_ln: also emit the following LayerNorm as
+        operand planes.  raw: planes that take x_out itself (wd_xattn_planes).  Returns (x_out, those LayerNorm planes, the fold)."""
+        w, inner = self._w, f.inner
+        mq, mo, mq_pl, mot_pl = self._xattn_fold(P, f"{p}.{tag}", f.heads, f.d)
+        x_out = self._f32(P, f.M, inner)
+        npl = self._planes(P, f.M, inner) if next_ln else None
+        src = (x_in.data_ptr(), inner, f.B, f.hw, inner)
+        ln = (w[f"{p}.norm2.g"].data_ptr(), w[f"{p}.norm2.b"].data_ptr())
+        bias = w[f"{p}.{tag}.o.b"].data_ptr()
+        dst = (x_out.data_ptr(), inner, w[f"{p}.{next_ln}.g"].data_ptr() if next_ln else None,
+               w[f"{p}.{next_ln}.b"].data_ptr() if next_ln else None, 1e-5, *self._hilo(npl), inner)
+        if raw is not None:  # (the pair entry point with no second attention)
+            P.step.append((self.lib.wd_xattn_planes,
+                           (*src, 1e-5, f.heads, f.L, *ln, mq_pl.data_ptr(), mot_pl.data_ptr(), bias, None, None, None, None, None,
+                            *dst, *self._hilo(raw), inner), f"{p}.{tag}:folded + planes"))
+        else:
+            P.step.append((self.lib.wd_xattn_fused,
+                           (*src, *ln, 1e-5, mq.data_ptr(), mo.data_ptr(), f.heads, f.L, bias, *dst, mq_pl.data_ptr(),
+                            mot_pl.data_ptr()), f"{p}.{tag}:folded"))
+        return x_out, npl, (mq_pl, mot_pl)
+
+    def _st_attn_self(self, P, f: StForm, p, tok, n1):
+        """attn1 of a PHOSC block: self-attention over the hw tokens of a sample as wd_gemm (q, k, v) -> wd_attention -> wd_gemm.
+        Returns (tok1, norm2 planes or None): the planes come out of the last epilogue where a plain attn2 would read them."""
+        ops, M, hw, inner = P.step, f.M, f.hw, f.inner
+        if n1 is None:
+            n1 = self._ln(P, ops, p + ".norm1", tok, M, inner, p + ".norm1")
+        qkv = self._f32(P, M, 3 * inner)
+        self._gemm(ops, p + ".a1.qkv", [self._src(n1, inner)], p + ".a1.qkv.w", M, hw, out_f32=qkv, out_ld=3 * inner)
+        o1 = self._planes(P, M, inner)
+        self._attention(ops, p + ".a1", qkv.data_ptr(), 3 * inner, qkv.data_ptr() + 4 * inner, 3 * inner,
+                        qkv.data_ptr() + 8 * inner, 3 * inner, f.heads, hw, hw, f.d, f.d ** -0.5, o1)
+        tok1 = self._f32(P, M, inner)
+        g = self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
+                       resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner, ln=None if f.xfold else p + ".norm2")
+        return tok1, g._ln_pl
+
+    def _st_attn_plain(self, P, f: StForm, p, tag, x_in, n_in, next_ln=None, pack=False):
+        """x_out = x_in + to_out(attention(to_q(n_in), K, V)) over the context's keys as wd_gemm -> wd_attention -> wd_gemm.  n_in:
+        the LayerNorm planes of x_in.  next_ln: the last epilogue also writes that LayerNorm of x_out where it can.  pack: a long
+        context's keys / values as LDS images.  Returns (x_out, the next_ln planes or None)."""
+        ops, M, hw, inner, heads, L, d = P.step, f.M, f.hw, f.inner, f.heads, f.L, f.d
+        q = self._f32(P, M, inner)
+        self._gemm(ops, f"{p}.{tag}.q", [self._src(n_in, inner)], f"{p}.{tag}.q.w", M, hw, out_f32=q, out_ld=inner)
+        ko = self.kv_off[f"{p}.{tag}"]
+        o = self._planes(P, M, inner)
+        kp, vp = self._kv.data_ptr() + 4 * ko, self._kv.data_ptr() + 4 * (ko + inner)
+        nimg = self.lib.wd_attention_packed_elems(f.B, heads, L, d) if pack else 0
+        if nimg > 0:
+            # the context's keys / values do not change during a sampling call: their split-bf16 LDS images are built
+            # once per call (P.cond, after the K/V projection) and every step's attention copies them 16 bytes at a time
+            img = torch.empty(nimg, dtype=torch.bfloat16, device=self.device)
+            P.keep.append(img)
+            P.cond.append((self.lib.wd_attention_pack_kv,
+                           (kp, self.kv_total, vp, self.kv_total, f.B, heads, L, d, img.data_ptr()), f"{p}.{tag}:pack kv"))
+            ops.append((self.lib.wd_attention_packed,
+                        (q.data_ptr(), inner, img.data_ptr(), f.B, heads, hw, L, d, float(d ** -0.5), None, *self._hilo(o), inner,
+                         hw, 0), f"{p}.{tag}"))
+        else:
+            self._attention(ops, f"{p}.{tag}", q.data_ptr(), inner, kp, self.kv_total, vp, self.kv_total, heads, hw, L, d,
+                            d ** -0.5, o)
+        x_out = self._f32(P, M, inner)
+        g = self._gemm(ops, f"{p}.{tag}.out", [self._src(o, inner)], f"{p}.{tag}.o.w", M, hw, bias=self._w[f"{p}.{tag}.o.b"],
+                       resid=x_in.data_ptr(), resid_ld=inner, out_f32=x_out, out_ld=inner, ln=f"{p}.{next_ln}" if next_ln else None)
+        return x_out, g._ln_pl
+
+    def _st_maps(self, P, f: StForm, p, x_in, fa, fb):
+        """The attn2 softmax of block ``p`` summed over heads into this tap's map buffer.  x_in is what the attention launch just
+        before read: the rows attn1 reads (fa: attn1's fold - the pair form runs attn1 again) or attn2's own input (fa None)."""
+        w = self._w
+        g2, b2 = w[f"{p}.norm2.g"].data_ptr(), w[f"{p}.norm2.b"].data_ptr()
+        first = (g2, b2, fa[0].data_ptr(), fa[1].data_ptr(), w[f"{p}.a1.o.b"].data_ptr()) if fa is not None else (None,) * 5
+        buf = torch.zeros((f.B, f.hw, f.L), dtype=torch.float32, device=self.device)
+        P.maps.append(buf)
+        P.map_hw.append((f.h, f.w))
+        wt = P.map_w
+        P.step.append((self.lib.wd_xattn_maps,
+                       (x_in.data_ptr(), f.inner, f.B, f.hw, f.inner, 1e-5, f.heads, f.L, *first, g2, b2, fb[0].data_ptr(),
+                        buf.data_ptr(), f.L, _ptr(wt), wt.numel() if wt is not None else 0,
+                        P.map_k.data_ptr() if wt is not None else None), f"{p}.a2:maps"))
+
+    def _st_ff1(self, P, f: StForm, p, ffi, n3):
+        """The GEGLU projection of block ``p`` as a GEMM -> the hidden activations as operand planes [M, ffi]."""
+        ffh = self._planes(P, f.M, ffi)
+        self._gemm(P.step, p + ".ff1", [self._src(n3, f.inner)], p + ".ff1.w", f.M, f.hw, bias=self._w[p + ".ff1.b"],
+                   act=N.ACT_GEGLU, out_pl=ffh, tile=geglu_tile(ffi))
+        return ffh
+
+    def _st_ff(self, P, f: StForm, p, ffi, n3, tok2, out_f32, out_pl):
+        """tok2 + FeedForward(n3) into fp32 rows and / or operand planes: one wd_ff_fused launch where that fills the chip, else the
+        GEGLU GEMM and ff2."""
+        if self._ff_fills_chip(p, f.M):
+            self._ff_fused(P.step, p, n3, tok2, f.M, f.inner, ffi, out_f32, out_pl)
+            return
+        ffh = self._st_ff1(P, f, p, ffi, n3)
+        self._gemm(P.step, p + ".ff2", [self._src(ffh, ffi)], p + ".ff2.w", f.M, f.hw, bias=self._w[p + ".ff2.b"],
+                   resid=tok2.data_ptr(), resid_ld=f.inner, out_f32=out_f32, out_ld=f.inner, out_pl=out_pl)
+
+    def _st_tail(self, P, f: StForm, name, p, ffi, n3, tok2, tok2pl, x: Act) -> Act:
+        """The last block's feed-forward, proj_out and the transformer's residual as ``f.tail`` plans them -> the output map, with
+        the statistics of the next ResBlock's GroupNorm where the last launch gives them."""
+        ops, M, hw, c = P.step, f.M, f.hw, f.c
+        out = self._f32(P, M, c)
+        if f.tail == "ff+proj":
+            g = self._ff_fused(ops, p, n3, tok2, M, f.inner, ffi, out, None, proj=(name, x.t, hw))
+        elif f.tail == "two-source":  # ff2 and proj_out folded: out = [h | tok2] [W32 | W3]^T + b32 + x
+            ffh = self._st_ff1(P, f, p, ffi, n3)
+            g = self._gemm(ops, name + ".ff2 + proj_out", [self._src(ffh, ffi), self._src(tok2pl, f.inner)], name + ".po32.w", M, hw,
+                           bias=self._w[name + ".b32"], resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True)
+        else:
+            xpl = self._planes(P, M, f.inner)
+            self._st_ff(P, f, p, ffi, n3, tok2, None, xpl)
+            g = self._gemm(ops, name + ".proj_out", [self._src(xpl, f.inner)], name + ".po.w", M, hw, bias=self._w[name + ".po.b"],
+                           resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True)
+        return Act(out, c, f.h, f.w, g._stats, prod=g)
+
+    def _transformer_fused(self, P, f: StForm, name, mod: SpatialTransformerParams, x: Act) -> Act:
         """The SpatialTransformer (unet.py:398-412, one base-model block) as ONE wd_ff_fused launch with the transformer front
         (wd_ff_args.x_in): GroupNorm + proj_in, both folded cross-attentions, norm3, the GEGLU feed-forward and proj_out + residual
         per 64-token panel; the GroupNorm statistics of the result for the next ResBlock come out of its epilogue."""
-        M, hw, c = self._B * x.h * x.w, x.h * x.w, x.c
-        heads, d, L = mod.heads, mod.d_head, self._ctx_len
+        M, hw, c, heads, d, L = f.M, f.hw, f.c, f.heads, f.d, f.L
         p = name + ".tb0"
         folds = [self._xattn_fold(P, f"{p}.{tag}", heads, d)[2:] for tag in ("a1", "a2")]
         # (folded tail: the kernel keeps tok2 on chip - no scratch)
@@ -1304,8 +1358,7 @@ class UNetEngine:
                      ln3_gamma=self._w[p + ".norm3.g"].data_ptr(), ln3_beta=self._w[p + ".norm3.b"].data_ptr(), ln_eps=1e-5,
                      heads=heads, L=L, tok2=_ptr(tok2))
         ffi = mod.transformer_blocks[0].ff.net[2].in_features
-        fa = self._ff_fused(P.step, p, None, tok2, M, c, ffi, out, None, proj=(name + ".po.w", self._w[name + ".po.b"], x.t, hw),
-                            front=front)
+        fa = self._ff_fused(P.step, p, None, tok2, M, c, ffi, out, None, proj=(name, x.t, hw), front=front)
         return Act(out, c, x.h, x.w, fa._stats, prod=fa)
 
     def _fold_fused(self, name) -> bool:
@@ -1321,8 +1374,8 @@ class UNetEngine:
         return self._wf[wname]
 
     def _ff_fused(self, ops, p, n3, resid, M, inner, ffi, out_f32, out_pl, proj=None, front=None):
-        """x + FeedForward(LN3(x)) (unet.py:343-344, :122-149) as one wd_ff_fused launch.  proj = (weight name, bias, residual
-        tensor, hw): the SpatialTransformer's proj_out + residual (unet.py:406-412) in the same launch, with the GroupNorm statistics
+        """x + FeedForward(LN3(x)) (unet.py:343-344, :122-149) as one wd_ff_fused launch.  proj = (SpatialTransformer name, residual
+        tensor, hw): that transformer's proj_out + residual (unet.py:406-412) in the same launch, with the GroupNorm statistics
         of the result for the next ResBlock; returns the statistics tuple then.  front: the wd_ff_args fields of the transformer
         front (n3 is None then: the launch makes the norm3 rows itself)."""
         a = N.WdFfArgs()
@@ -1343,13 +1396,13 @@ class UNetEngine:
         a.hw_out, a.npass = 1, self.npass
         stats = None
         if proj is not None:
-            wname, b3, x_in, hw = proj
-            w3 = self._wfrag(wname)
-            a.w3_hi, a.w3_lo, a.b3 = w3[0].data_ptr(), w3[1].data_ptr(), b3.data_ptr()
+            name, x_in, hw = proj
+            w3 = self._wfrag(name + ".po.w")
+            a.w3_hi, a.w3_lo, a.b3 = w3[0].data_ptr(), w3[1].data_ptr(), self._w[name + ".po.b"].data_ptr()
             a.resid3, a.resid3_ld = x_in.data_ptr(), inner
-            if self._fold_fused(wname[:-len(".po.w")]):
-                w32 = self._wfrag(wname[:-len(".po.w")] + ".w32.w")
-                a.w32_hi, a.w32_lo, a.b32 = w32[0].data_ptr(), w32[1].data_ptr(), self._w[wname[:-len(".po.w")] + ".b32"].data_ptr()
+            if self._fold_fused(name):
+                w32 = self._wfrag(name + ".w32.w")
+                a.w32_hi, a.w32_lo, a.b32 = w32[0].data_ptr(), w32[1].data_ptr(), self._w[name + ".b32"].data_ptr()
             if self.fuse_stats and inner % 32 == 0 and hw % 64 == 0:
                 nchunk = hw // 64
                 part = torch.zeros((M // hw, nchunk, 32, 2), dtype=torch.float64, device=self.device)
@@ -1444,7 +1497,7 @@ class UNetEngine:
         if self.variant == "phosc":
             raise NotImplementedError("attention maps: the PHOSC model's cross-attention has ctx + PHOSC keys, and the reference "
                                       "keeps a map only where it has 10 (unetPhosc.py: attn.shape[-1] == 10 is false)")
-        if not self.fuse_xattn or os.environ.get("WDIFF_XATTN_VALU"):
+        if not self.fuse_xattn or not self._xattn_mfma():
             raise NotImplementedError("attention maps need the folded MFMA cross-attention (WDIFF_FUSE_XATTN=0 / WDIFF_XATTN_VALU "
                                       "select forms that do not keep the probabilities wd_xattn_maps reports)")
         taps = []
@@ -1539,27 +1592,18 @@ class UNetEngine:
         P = self._cached_plan(self._plans, key, room=max(1, PLAN_CACHE_SIZE))
         if P is not None:
             return P
-        m = self.model
-        lib = self.lib
         if ctx_len + phosc_len == 0:
             raise NotImplementedError("context=None: every reference script conditions on the word (unet.py:1605)")
-        taps = self._map_taps(ctx_len + phosc_len) if attn_maps else ()  # (raises before anything is built or launched)
-        P = self._begin_plan(Plan(), B)
-        dev = self.device
-        mc = m.model_channels
-        ted = 4 * mc
-        self._inputs(P, H, W, ctx_len, phosc_len)
-        P.map_taps = taps
-        # step-invariant: run once per call (P.cond)
-        self._conditioning(P, P.cond, ctx_len, phosc_len)
-
-        # ---- per-step: time/label embedding (unet.py:1550-1581) + all emb_layers at once (unet.py:609-615,660)
-        step = P.step
-        has_lab = m.num_classes is not None
-        if mix and not has_lab:
+        if mix and self.model.num_classes is None:
             raise ValueError("writer-style interpolation needs a class-conditional model (num_classes)")
         if mix not in (0, 1, 2) or (mix == 2 and not film_steps):
             raise ValueError(f"mix = {mix}: 1 or 2 forwards per step with the table, 1 without")
+        taps = self._map_taps(ctx_len + phosc_len) if attn_maps else ()  # (raises before anything is built or launched)
+        P = self._begin_plan(Plan(), B)
+        dev = self.device
+        self._inputs(P, H, W, ctx_len, phosc_len)
+        P.map_taps = taps
+        self._conditioning(P, P.cond, ctx_len, phosc_len)  # step-invariant: run once per call (P.cond)
         P.mix = mix
         if mix:
             P.mix_m = torch.zeros((B,), dtype=torch.float32, device=dev)
@@ -1570,133 +1614,166 @@ class UNetEngine:
             P.map_w = torch.zeros((int(attn_rows),), dtype=torch.float32, device=dev)
             P.map_k = P.k_dev if attn_by_step else P.t_dev
         P.film = []
-        if film_steps:
-            # the table holds ``chunk`` consecutive timesteps (rows (t % chunk) * B + b), not all T: T*B*film_total fp32 was
-            # 655 MB + 328 MB of operand planes at B = 64 and grew with B and T; a chunk of ~8192 rows is 84 + 42 MB at any
-            # B.  The time MLP (T rows, cheap) is still evaluated for every t once per call (P.film); the SiLU(time + label)
-            # planes and the emb_layers GEMM of a chunk run when the loop enters it (P.film_prepare, same stream, a fraction
-            # of one step each).
-            T = film_steps if film_timesteps is None else len(film_timesteps)  # rows of the table: all t, or the visited ones
-            nf = max(1, mix)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
-            # (a table over all t keeps at least 8 timesteps resident; one over the visited steps is cut by rows alone)
-            chunk = min(T, max(8 if film_timesteps is None else 1, FILM_CHUNK_ROWS // (B * nf)))
-            nchunks = (T + chunk - 1) // chunk
-            Tp = nchunks * chunk
-            film = P.film
-            if film_timesteps is None:
-                tt = torch.arange(Tp, dtype=torch.int64, device=dev)
-            else:  # row k holds timestep tau[k]; the padding rows repeat the last one and are never selected
-                tt = torch.tensor(film_timesteps + (film_timesteps[-1],) * (Tp - T), dtype=torch.int64, device=dev)
-            P.keep.append(tt)
-            te = self._planes(P, Tp, mc)
-            film.append((lib.wd_timestep_embedding, (tt.data_ptr(), Tp, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
-                         "timestep_embedding[all t]"))
-            e1 = self._planes(P, Tp, ted)
-            self._gemm(film, "time_embed.0[all t]", [self._src(te, mc)], "te0.w", Tp, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
-                       out_pl=e1)
-            tm = self._f32(P, Tp, ted)
-            self._gemm(film, "time_embed.2[all t]", [self._src(e1, ted)], "te2.w", Tp, 1, bias=self._w["te2.b"], out_f32=tm,
-                       out_ld=ted)
-            e2 = self._planes(P, nf * chunk * B, ted)
-            P.film_table = self._f32(P, nf * chunk * B, self.film_total)
-            P.film_chunk, P.film_nchunks, P.film_loaded = chunk, nchunks, -1
-            if mix:
-                P.pairs = torch.zeros((nf, Tp, B, 2), dtype=torch.int32, device=dev)
-            chunk_gemm = []
-            self._gemm(chunk_gemm, "emb_layers(all)[chunk of t]", [self._src(e2, ted)], "film.w", nf * chunk * B, 1,
-                       bias=self._w["film.b"], out_f32=P.film_table, out_ld=self.film_total)
-            lab = self._w["label"].data_ptr() if has_lab else None
-            yin = P.y_in.data_ptr() if has_lab else None
-            ncls = m.num_classes if has_lab else 0
-
-            def film_prepare(t, stream, P=P, tm=tm, e2=e2, chunk=chunk, B=B):
-                """Makes the FiLM rows of timestep ``t`` resident: (re)computes the chunk ``t // chunk`` unless it is loaded."""
-                c = int(t) // chunk
-                if c == P.film_loaded:
-                    return False
-                if mix:
-                    for f in range(nf):  # table f: rows f*chunk*B.. of the planes, pairs[f][c*chunk..]
-                        N.check(lib.wd_emb_combine_mix(tm.data_ptr() + 4 * c * chunk * ted, lab, P.pairs[f, c * chunk].data_ptr(),
-                                                       P.mix_m.data_ptr(), ncls, chunk, B, ted,
-                                                       *self._hilo(e2, 2 * f * chunk * B * ted), ted, stream),
-                                "SiLU(time + blended label)[chunk of t]")
-                else:
-                    N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, *self._hilo(e2), ted,
-                                               stream), "SiLU(time + label)[chunk of t]")
-                Plan._run(chunk_gemm, stream)
-                P.film_loaded = c
-                return True
-
-            P.film_prepare = film_prepare
-            row_dev = P.t_dev if film_timesteps is None else P.k_dev
-            step.append((lib.wd_select_rows, (P.film_table.data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
-                                              self._film.data_ptr()), "film rows of step t"))
-            if mix == 2:
-                select1 = (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
-                                                self._film.data_ptr()), "film rows of step t, second forward")
-        else:
-            if mix:
-                # the blended rows [B, ted] (wd_label_mix) are the residual of the time_embed.2 GEMM, row b for sample b
-                P.pairs = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-                lab_rows = self._f32(P, B, ted)
-                id_rows = torch.arange(B, dtype=torch.int64, device=dev)
-                P.keep.append(id_rows)
-                step.append((lib.wd_label_mix, (self._w["label"].data_ptr(), P.pairs.data_ptr(), P.mix_m.data_ptr(), m.num_classes,
-                                                B, ted, lab_rows.data_ptr()), "blended label rows"))
-            te = self._planes(P, B, mc)
-            step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
-                         "timestep_embedding"))
-            e1 = self._planes(P, B, ted)
-            self._gemm(step, "time_embed.0", [self._src(te, mc)], "te0.w", B, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
-                       out_pl=e1)
-            e2 = self._planes(P, B, ted)  # SiLU(emb): the only form any consumer reads (emb_layers start with SiLU)
-            self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
-                       resid=(lab_rows if mix else self._w["label"]).data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
-                       resid_rows=(id_rows if mix else P.y_in).data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
-            self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"],
-                       out_f32=self._film, out_ld=self.film_total)
-
-        # ---- head: the first convolution
-        if self.fuse_in and self.variant != "phosc" and lib.wd_conv3x3_in_supported(m.in_channels, H, W, mc) and mc % 32 == 0:
-            # the 4-channel 3x3 as a direct fp32 convolution: no im2col planes, and the statistics partials of the consumer's
-            # GroupNorm (32 groups) in the layout the GEMM's epilogue gives them
-            h0 = self._f32(P, B * H * W, mc)
-            stats = None
-            if self.fuse_stats:
-                nchunk = lib.wd_conv3x3_in_nchunk(H * W)
-                part = torch.zeros((B, nchunk, 32, 2), dtype=torch.float64, device=dev)
-                P.keep.append(part)
-                stats = (part, nchunk, mc // 32)
-            step.append((lib.wd_conv3x3_in, (P.x_in.data_ptr(), B, m.in_channels, H, W, self._w["in.w.f32"].data_ptr(),
-                                             self._w["in.b"].data_ptr(), mc, h0.data_ptr(), mc,
-                                             stats[0].data_ptr() if stats else None, mc // 32), "input_blocks.0: conv3x3 from NCHW"))
-            cur = Act(h0, mc, H, W, stats)
-        else:
-            cur, _ = self._head_gemm(P, step, "input_blocks.0", P.x_in, "in")
+        # per step: time / label embedding (unet.py:1550-1581) + all emb_layers at once (unet.py:609-615,660) into self._film, ...
+        select1 = self._film_table(P, film_steps, film_timesteps) if film_steps else self._film_per_step(P)
+        # ... the first convolution, the blocks, the output convolution into P.out
+        cur = self._head(P, H, W)
         cur = self._trunk(P, cur)
-        # ---- tail
-        oc = m.out_channels
-        P.out = torch.empty((B, oc, cur.h, cur.w), dtype=torch.float32, device=dev)
-        if self.fuse_out and lib.wd_gn_conv3x3_few_supported(cur.c, cur.w, oc) and cur.c % 32 == 0:
-            # GroupNorm + SiLU + the 320 -> 4 convolution + NCHW in one fp32 launch (as a GEMM it fills 4 of 64 tile columns)
-            part, nchunk, pc = self._gn_stats(P, step, "out.gn", cur)
-            step.append((lib.wd_gn_conv3x3_few,
-                         (cur.t.data_ptr(), cur.c, B, cur.h, cur.w, cur.c, cur.c // 32, part.data_ptr(), nchunk, pc,
-                          self._w["out.gn.g"].data_ptr(), self._w["out.gn.b"].data_ptr(), 1e-5, 1,
-                          self._w["out.w.f32"].data_ptr(), self._w["out.b"].data_ptr(), oc, P.out.data_ptr()),
-                         "out: GroupNorm + SiLU + conv3x3 -> NCHW"))
-        else:
-            self._tail_gemm(P, step, "out.conv", cur, 1e-5, nchw=P.out)
+        self._tail(P, cur)
         if mix == 2:
-            # the second forward of a step: its own FiLM rows, the same launches, the prediction kept beside the first one
-            fn, args, what = step[-1]
-            assert args[-1] == P.out.data_ptr(), what
-            P.out1 = torch.empty_like(P.out)
-            # (the attention maps accumulate over the first forward alone)
-            P.step1 = [select1] + [op for op in step[1:-1] if op[0] is not lib.wd_xattn_maps] + \
-                [(fn, args[:-1] + (P.out1.data_ptr(),), what)]
+            self._second_forward(P, select1)
         self._plans[key] = P
         return P
+
+    def _film_table(self, P: Plan, film_steps: int, film_timesteps: Optional[tuple]):
+        """The tabulated FiLM path (``plan`` film_steps / film_timesteps): ``P.film`` evaluates the time MLP of every table row once
+        per call, ``P.film_prepare`` makes the chunk of rows a step reads resident, and the step begins by selecting its rows.
+        Returns the select op a second forward begins with (mix = 2), else None."""
+        lib, dev, B, mix, film = self.lib, self.device, self._B, P.mix, P.film
+        mc = self.model.model_channels
+        ted = 4 * mc
+        # the table holds ``chunk`` consecutive timesteps (rows (t % chunk) * B + b), not all T: T*B*film_total fp32 was
+        # 655 MB + 328 MB of operand planes at B = 64 and grew with B and T; a chunk of ~8192 rows is 84 + 42 MB at any
+        # B.  The time MLP (T rows, cheap) is still evaluated for every t once per call (P.film); the SiLU(time + label)
+        # planes and the emb_layers GEMM of a chunk run when the loop enters it (P.film_prepare, same stream, a fraction
+        # of one step each).
+        T = film_steps if film_timesteps is None else len(film_timesteps)  # rows of the table: all t, or the visited ones
+        nf = max(1, mix)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
+        # (a table over all t keeps at least 8 timesteps resident; one over the visited steps is cut by rows alone)
+        chunk = min(T, max(8 if film_timesteps is None else 1, FILM_CHUNK_ROWS // (B * nf)))
+        nchunks = (T + chunk - 1) // chunk
+        Tp = nchunks * chunk
+        if film_timesteps is None:
+            tt = torch.arange(Tp, dtype=torch.int64, device=dev)
+        else:  # row k holds timestep tau[k]; the padding rows repeat the last one and are never selected
+            tt = torch.tensor(film_timesteps + (film_timesteps[-1],) * (Tp - T), dtype=torch.int64, device=dev)
+        P.keep.append(tt)
+        te = self._planes(P, Tp, mc)
+        film.append((lib.wd_timestep_embedding, (tt.data_ptr(), Tp, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
+                     "timestep_embedding[all t]"))
+        e1 = self._planes(P, Tp, ted)
+        self._gemm(film, "time_embed.0[all t]", [self._src(te, mc)], "te0.w", Tp, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
+                   out_pl=e1)
+        tm = self._f32(P, Tp, ted)
+        self._gemm(film, "time_embed.2[all t]", [self._src(e1, ted)], "te2.w", Tp, 1, bias=self._w["te2.b"], out_f32=tm,
+                   out_ld=ted)
+        e2 = self._planes(P, nf * chunk * B, ted)
+        P.film_table = self._f32(P, nf * chunk * B, self.film_total)
+        P.film_chunk, P.film_nchunks, P.film_loaded = chunk, nchunks, -1
+        if mix:
+            P.pairs = torch.zeros((nf, Tp, B, 2), dtype=torch.int32, device=dev)
+        chunk_gemm = []
+        self._gemm(chunk_gemm, "emb_layers(all)[chunk of t]", [self._src(e2, ted)], "film.w", nf * chunk * B, 1,
+                   bias=self._w["film.b"], out_f32=P.film_table, out_ld=self.film_total)
+        P.film_prepare = self._film_prepare(P, tm, e2, chunk, nf, chunk_gemm)
+        row_dev = P.t_dev if film_timesteps is None else P.k_dev
+        P.step.append((lib.wd_select_rows, (P.film_table.data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
+                                            self._film.data_ptr()), "film rows of step t"))
+        if mix != 2:
+            return None
+        return (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
+                                     self._film.data_ptr()), "film rows of step t, second forward")
+
+    def _film_prepare(self, P: Plan, tm, e2, chunk, nf, chunk_gemm):
+        """``P.film_prepare`` of a tabulated plan, a closure over it: tm fp32 [rows, ted] the time MLP's output, e2 the planes that
+        take SiLU(time + label) of the resident chunk, chunk_gemm the emb_layers GEMM over them."""
+        lib, B, mix, ted = self.lib, self._B, P.mix, tm.shape[1]
+        has_lab = self.model.num_classes is not None
+        lab = self._w["label"].data_ptr() if has_lab else None
+        yin = P.y_in.data_ptr() if has_lab else None
+        ncls = self.model.num_classes if has_lab else 0
+
+        def film_prepare(t, stream):
+            """Makes the FiLM rows of timestep ``t`` resident: (re)computes the chunk ``t // chunk`` unless it is loaded."""
+            c = int(t) // chunk
+            if c == P.film_loaded:
+                return False
+            if mix:
+                for f in range(nf):  # table f: rows f*chunk*B.. of the planes, pairs[f][c*chunk..]
+                    N.check(lib.wd_emb_combine_mix(tm.data_ptr() + 4 * c * chunk * ted, lab, P.pairs[f, c * chunk].data_ptr(),
+                                                   P.mix_m.data_ptr(), ncls, chunk, B, ted,
+                                                   *self._hilo(e2, 2 * f * chunk * B * ted), ted, stream),
+                            "SiLU(time + blended label)[chunk of t]")
+            else:
+                N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, *self._hilo(e2), ted,
+                                           stream), "SiLU(time + label)[chunk of t]")
+            Plan._run(chunk_gemm, stream)
+            P.film_loaded = c
+            return True
+
+        return film_prepare
+
+    def _film_per_step(self, P: Plan):
+        """The embedding path evaluated in every step (no table): three B-row GEMMs into ``self._film``.  mix: the label term is
+        the blend of each sample's pair of writers."""
+        m, lib, dev, B, mix, step = self.model, self.lib, self.device, self._B, P.mix, P.step
+        mc = m.model_channels
+        ted = 4 * mc
+        has_lab = m.num_classes is not None
+        if mix:
+            # the blended rows [B, ted] (wd_label_mix) are the residual of the time_embed.2 GEMM, row b for sample b
+            P.pairs = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+            lab_rows = self._f32(P, B, ted)
+            id_rows = torch.arange(B, dtype=torch.int64, device=dev)
+            P.keep.append(id_rows)
+            step.append((lib.wd_label_mix, (self._w["label"].data_ptr(), P.pairs.data_ptr(), P.mix_m.data_ptr(), m.num_classes,
+                                            B, ted, lab_rows.data_ptr()), "blended label rows"))
+        te = self._planes(P, B, mc)
+        step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
+                     "timestep_embedding"))
+        e1 = self._planes(P, B, ted)
+        self._gemm(step, "time_embed.0", [self._src(te, mc)], "te0.w", B, 1, bias=self._w["te0.b"], act=N.ACT_SILU,
+                   out_pl=e1)
+        e2 = self._planes(P, B, ted)  # SiLU(emb): the only form any consumer reads (emb_layers start with SiLU)
+        self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
+                   resid=(lab_rows if mix else self._w["label"]).data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
+                   resid_rows=(id_rows if mix else P.y_in).data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
+        self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"],
+                   out_f32=self._film, out_ld=self.film_total)
+
+    def _head(self, P: Plan, H, W) -> Act:
+        """The first convolution of the step, from ``P.x_in``."""
+        m, lib, B = self.model, self.lib, self._B
+        mc = m.model_channels
+        if not (self.fuse_in and self.variant != "phosc" and lib.wd_conv3x3_in_supported(m.in_channels, H, W, mc) and mc % 32 == 0):
+            return self._head_gemm(P, P.step, "input_blocks.0", P.x_in, "in")[0]
+        # the 4-channel 3x3 as a direct fp32 convolution: no im2col planes, and the statistics partials of the consumer's
+        # GroupNorm (32 groups) in the layout the GEMM's epilogue gives them
+        h0 = self._f32(P, B * H * W, mc)
+        stats = None
+        if self.fuse_stats:
+            nchunk = lib.wd_conv3x3_in_nchunk(H * W)
+            part = torch.zeros((B, nchunk, 32, 2), dtype=torch.float64, device=self.device)
+            P.keep.append(part)
+            stats = (part, nchunk, mc // 32)
+        P.step.append((lib.wd_conv3x3_in, (P.x_in.data_ptr(), B, m.in_channels, H, W, self._w["in.w.f32"].data_ptr(),
+                                           self._w["in.b"].data_ptr(), mc, h0.data_ptr(), mc,
+                                           stats[0].data_ptr() if stats else None, mc // 32), "input_blocks.0: conv3x3 from NCHW"))
+        return Act(h0, mc, H, W, stats)
+
+    def _tail(self, P: Plan, cur: Act):
+        """GroupNorm + SiLU + the output convolution of the step, into ``P.out`` (NCHW)."""
+        lib, B, oc = self.lib, self._B, self.model.out_channels
+        P.out = torch.empty((B, oc, cur.h, cur.w), dtype=torch.float32, device=self.device)
+        if not (self.fuse_out and lib.wd_gn_conv3x3_few_supported(cur.c, cur.w, oc) and cur.c % 32 == 0):
+            self._tail_gemm(P, P.step, "out.conv", cur, 1e-5, nchw=P.out)
+            return
+        # GroupNorm + SiLU + the 320 -> 4 convolution + NCHW in one fp32 launch (as a GEMM it fills 4 of 64 tile columns)
+        part, nchunk, pc = self._gn_stats(P, P.step, "out.gn", cur)
+        P.step.append((lib.wd_gn_conv3x3_few,
+                       (cur.t.data_ptr(), cur.c, B, cur.h, cur.w, cur.c, cur.c // 32, part.data_ptr(), nchunk, pc,
+                        self._w["out.gn.g"].data_ptr(), self._w["out.gn.b"].data_ptr(), 1e-5, 1,
+                        self._w["out.w.f32"].data_ptr(), self._w["out.b"].data_ptr(), oc, P.out.data_ptr()),
+                       "out: GroupNorm + SiLU + conv3x3 -> NCHW"))
+
+    def _second_forward(self, P: Plan, select1):
+        """``P.step1`` (mix = 2), the second forward of a step: its own FiLM rows, the same launches, the prediction kept beside
+        the first one in ``P.out1``.  The attention maps accumulate over the first forward alone."""
+        fn, args, what = P.step[-1]
+        assert args[-1] == P.out.data_ptr(), what
+        P.out1 = torch.empty_like(P.out)
+        P.step1 = [select1] + [op for op in P.step[1:-1] if op[0] is not self.lib.wd_xattn_maps] + \
+            [(fn, args[:-1] + (P.out1.data_ptr(),), what)]
 
     # ------------------------------------------------------------------------------------------ run
     def check_ids(self, context=None, y=None, phosc=None, need_y=True):
