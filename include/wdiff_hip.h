@@ -535,6 +535,7 @@ int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sa
 #define WD_STREAM_VAE_POSTERIOR 3 /* stream ids taken so far: 0 x_T, 1 noise_images eps, 2 the training step's eps, 3 this one; */
 #define WD_STREAM_KNOWN 4         /* 4: the per-sample fixed eps of a known-region call (wd_known_blend below), via wd_randn; */
 #define WD_STREAM_DROPOUT0 0x100  /* 0x100 + layer: the training dropout mask of ResBlock `layer` (wd_dropout below) */
+#define WD_STREAM_LABEL_DROP 5    /* 5: the per-sample writer dropout of a training step (wd_label_rows_keep below) */
 int wd_vae_posterior(const float* moments_tok, int ld, const float* w, const float* bias, int batch, int L, int hw, float* mean,
                      float* logvar, float* sample, float scale, const float* noise, uint64_t seed, uint64_t sample_offset,
                      void* stream);
@@ -779,6 +780,25 @@ typedef struct {
     uint32_t tag, thr;
     float scale;
 } wd_dropout;
+/* Writer-free guidance (classifier-free guidance on the writer; the reference's imgConditioned == 1 branch, unet.py:1578-1579,
+ * made per sample): a sample either keeps its label term or runs without it - the term is left out, not multiplied by zero.
+ * wd_emb_combine_keep: wd_emb_combine with keep uint8 [B].  Row t*B + b is SiLU(time[t] + label[y_b]) where keep[b] != 0, bit
+ * for bit wd_emb_combine's row, and SiLU(time[t]) where keep[b] == 0: bit for bit wd_emb_combine's row on an all-zero label
+ * table wherever time holds no exact zero.  keep == NULL: no sample keeps its writer; label and y may then be NULL.
+ * wd_label_rows_keep: the writer rows of a batch, out fp32 [B][ted] (16-byte aligned; the residual rows of the time_embed.2 GEMM,
+ * as wd_label_mix's): out[b] = label[y_b] bit for bit where sample b keeps its writer, exact zeros where it does not.  The
+ * decision is keep_in[b] != 0 (uint8 [B]) when d == NULL.  Otherwise it is drawn: one Philox4x32-10 call with
+ *   counter = (0, d->tag, row & 0xffffffff, row >> 32), key = (seed & 0xffffffff, seed >> 32), row = row_base (+ *row_base_dev) + b,
+ * kept iff output word 0 >= d->thr; d->scale is ignored.  A training step passes tag = 0x80000000 | WD_STREAM_LABEL_DROP, which
+ * no ResBlock mask (0x80000000 | (0x100 + layer)), WD_TAG_KNOWN draw or bare timestep uses.  NULL or: y_eff int64 [B] receives
+ * y_b where kept and -1 where dropped (the ids to hand wd_embedding_bwd, which skips ids outside [0, vocab)); keep_out uint8 [B]
+ * receives the decision.  y_b is clamped to [0, num_classes) for the read - the host range-checks it.
+ * Both: WD_EINVAL (nothing launched) for a NULL required pointer, ted % 4, out_ld % 4 or < ted; they neither allocate nor
+ * synchronise (capturable). */
+int wd_emb_combine_keep(const float* time, const float* label, const int64_t* y, const uint8_t* keep, int num_classes, int T, int B,
+                        int ted, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream);
+int wd_label_rows_keep(const float* label, const int64_t* y, int num_classes, int B, int ted, const wd_dropout* d,
+                       const uint8_t* keep_in, float* out, int64_t* y_eff, uint8_t* keep_out, void* stream);
 /* wd_gn_apply with the mask on the normalised(+SiLU) planes (the raw planes carry none). */
 int wd_gn_apply_dropout(const float* x, int ld, int batch, int hw, int c, int cpg, const double* part, int nchunk, int part_cpg,
                         const float* gamma, const float* beta, float eps, int silu,
@@ -864,7 +884,8 @@ int wd_geglu_bwd(const float* u, int ld, const float* dh, int dh_ld, int64_t row
 int wd_silu_bwd(const float* pre, const float* dact, int64_t n, float* dpre, void* stream);
 /* backward of F.interpolate(scale_factor=2, mode="nearest") (Upsample.forward, unet.py:497): in [B][2h][2w][c] -> out [B][h][w][c], 2x2 block sums */
 int wd_pool2x2_sum(const float* in, int batch, int h, int w, int c, float* out, void* stream);
-/* nn.Embedding backward (CharacterEncoder.embedding unet.py:845, label_emb :1245): dtable[v][:] (+)= sum of d[r][:] over rows with ids[r] == v (deterministic) */
+/* nn.Embedding backward (CharacterEncoder.embedding unet.py:845, label_emb :1245): dtable[v][:] (+)= sum of d[r][:] over rows with ids[r] == v (deterministic);
+ * a row whose id lies outside [0, vocab) contributes to no table row: ids of -1 mask rows out (wd_label_rows_keep's y_eff) */
 int wd_embedding_bwd(const void* ids, int ids_are_i64, int rows, const float* d, int ld, int vocab, int c, float* dtable,
                      int accumulate, void* stream);
 

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("WDIFF_LIB") or os.path.join(_HERE, "libwdiff_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "wdiff_hip.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
-            "uint16_t": C.c_uint16, "float": C.c_float, "double": C.c_double, "char": C.c_char}
+            "uint16_t": C.c_uint16, "uint8_t": C.c_uint8, "float": C.c_float, "double": C.c_double, "char": C.c_char}
 _DECL = re.compile(r"(?:const\s+)?(\w+)(?:\s*(\*+)\s*|\s+)(\w+)((?:\s*,\s*\w+)*)\s*(?:\[(\d+)\])?")
 _ITEMS = [re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;\s*"),  # struct: (body, name)
           re.compile(r"typedef\s+(\w+)\s+(\w+)\s*;\s*"),                        # alias: (known type, name)
@@ -96,6 +96,7 @@ ACT_NONE, ACT_SILU, ACT_GEGLU = (DEFINES[n] for n in ("WD_ACT_NONE", "WD_ACT_SIL
 VAE_MAX_LATENT, STREAM_VAE_POSTERIOR, STREAM_DROPOUT0, NCLASS = (
     DEFINES[n] for n in ("WD_VAE_MAX_LATENT", "WD_STREAM_VAE_POSTERIOR", "WD_STREAM_DROPOUT0", "WD_NCLASS"))
 STREAM_KNOWN, TAG_KNOWN = DEFINES["WD_STREAM_KNOWN"], DEFINES["WD_TAG_KNOWN"]
+STREAM_LABEL_DROP = DEFINES["WD_STREAM_LABEL_DROP"]
 CLASS_NAMES = ("gemm", "gn_stats", "gn_apply", "layernorm", "attention", "other", "gemm_other_tiles", "gemm_splitk_reduce",
                "gemm_two_per_cu", "gemm_weights_to_registers", "feed_forward_fused", "weight_gradient", "gemm_small_maps_whole_k")
 assert len(CLASS_NAMES) == NCLASS, "CLASS_NAMES must name every profiling class of the header (WD_NCLASS)"

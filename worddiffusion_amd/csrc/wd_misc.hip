@@ -262,6 +262,68 @@ __global__ void label_mix_kernel(const float* __restrict__ label, const int32_t*
     }
 }
 
+// ---- writer-free guidance ---------------------------------------------------------------------------------------------------
+// emb_combine_kernel with the label term per sample: where keep[b] == 0 (or keep == NULL) the row is SiLU(time[t]) - the term is
+// left out, not multiplied by zero (the reference's imgConditioned == 1 branch, unet.py:1578-1579).  Kept rows run
+// emb_combine_kernel's operations in its order.
+__global__ void emb_combine_keep_kernel(const float* __restrict__ time, const float* __restrict__ label, const int64_t* __restrict__ y,
+                                        const uint8_t* __restrict__ keep, int num_classes, int T, int B, int ted,
+                                        wd_bf16* __restrict__ out_hi, wd_bf16* __restrict__ out_lo, int out_ld) {
+    const int t4 = ted >> 2;
+    const long total = (long)T * B * t4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / t4;
+        const int cx = (int)(i - row * t4) * 4;
+        const int t = (int)(row / B), b = (int)(row - (long)t * B);
+        float4 v = *reinterpret_cast<const float4*>(time + (long)t * ted + cx);
+        if (keep && keep[b]) {
+            long yb = y[b];
+            yb = yb < 0 ? 0 : (yb >= num_classes ? num_classes - 1 : yb);
+            const float4 l = *reinterpret_cast<const float4*>(label + yb * ted + cx);
+            v.x += l.x; v.y += l.y; v.z += l.z; v.w += l.w;
+        }
+        v.x = wd_silu(v.x); v.y = wd_silu(v.y); v.z = wd_silu(v.z); v.w = wd_silu(v.w);
+        uint2 hi, lo;
+        wd_split4(v, hi, lo);
+        *reinterpret_cast<uint2*>(out_hi + row * out_ld + cx) = hi;
+        if (out_lo) *reinterpret_cast<uint2*>(out_lo + row * out_ld + cx) = lo;
+    }
+}
+
+// out[b][:] = label[y_b][:] where sample b keeps its writer, zeros where it does not.  The decision is keep_in[b], or (DRAW) word 0
+// of one Philox4x32-10 call with counter (0, d.tag, row) >= d.thr, row the global sample row of wd_dropout_row: every lane of a
+// row recomputes it, the lane of the row's first four columns also writes y_eff[b] (y_b, or -1 when dropped) and keep_out[b].
+template <bool DRAW>
+__global__ void label_rows_keep_kernel(const float* __restrict__ label, const int64_t* __restrict__ y, int num_classes, int B, int ted,
+                                       const wd_dropout d, const uint8_t* __restrict__ keep_in, float* __restrict__ out,
+                                       int64_t* __restrict__ y_eff, uint8_t* __restrict__ keep_out) {
+    const int t4 = ted >> 2;
+    const long total = (long)B * t4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / t4), cx = (int)(i - (long)b * t4) * 4;
+        bool keep;
+        if constexpr (DRAW) {
+            const uint64_t row = wd_dropout_row(d, b);
+            uint32_t w[4] = {0u, d.tag, (uint32_t)row, (uint32_t)(row >> 32)};
+            philox4x32_10(w, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+            keep = w[0] >= d.thr;
+        } else {
+            keep = keep_in[b] != 0;
+        }
+        const long yb = y[b];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (keep) {
+            const long yc = yb < 0 ? 0 : (yb >= num_classes ? num_classes - 1 : yb);  // range-checked on the host, as above
+            v = *reinterpret_cast<const float4*>(label + yc * ted + cx);
+        }
+        *reinterpret_cast<float4*>(out + (long)b * ted + cx) = v;
+        if (cx == 0) {
+            if (y_eff) y_eff[b] = keep ? (int64_t)yb : (int64_t)-1;
+            if (keep_out) keep_out[b] = keep ? 1 : 0;
+        }
+    }
+}
+
 // torch.lerp(second, first, s) as ATen evaluates it: the weight >= 0.5 form is first - (first - second) * (1 - s)
 __device__ __forceinline__ float lerp_cfg(float first, float second, float s, float oms, bool high) {
     const float d = first - second;
@@ -743,6 +805,34 @@ extern "C" int wd_label_mix(const float* label, const int32_t* pairs, const floa
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(label_mix_kernel, dim3(grid_for((long)B * (ted / 4))), dim3(256), 0, st, label, pairs, mix, num_classes, B, ted,
                        out);
+    return wd_check_launch();
+}
+
+extern "C" int wd_emb_combine_keep(const float* time, const float* label, const int64_t* y, const uint8_t* keep, int num_classes, int T,
+                                   int B, int ted, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream) {
+    if (!time || !out_hi || T <= 0 || B <= 0 || ted <= 0 || ted % 4 || out_ld % 4 || out_ld < ted ||
+        (keep && (!label || !y || num_classes <= 0)))
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(emb_combine_keep_kernel, dim3(grid_for((long)T * B * (ted / 4))), dim3(256), 0, st, time, label, y, keep,
+                       num_classes, T, B, ted, out_hi, out_lo, out_ld);
+    return wd_check_launch();
+}
+
+extern "C" int wd_label_rows_keep(const float* label, const int64_t* y, int num_classes, int B, int ted, const wd_dropout* d,
+                                  const uint8_t* keep_in, float* out, int64_t* y_eff, uint8_t* keep_out, void* stream) {
+    if (!label || !y || !out || num_classes <= 0 || B <= 0 || ted <= 0 || ted % 4 || (!d && !keep_in) || ((uintptr_t)out & 15))
+        return WD_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    const dim3 grid(grid_for((long)B * (ted / 4)));
+    if (d)
+        hipLaunchKernelGGL(label_rows_keep_kernel<true>, grid, dim3(256), 0, st, label, y, num_classes, B, ted, *d, keep_in, out, y_eff,
+                           keep_out);
+    else
+        hipLaunchKernelGGL(label_rows_keep_kernel<false>, grid, dim3(256), 0, st, label, y, num_classes, B, ted, wd_dropout{}, keep_in,
+                           out, y_eff, keep_out);
     return wd_check_launch();
 }
 

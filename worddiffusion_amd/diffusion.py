@@ -215,13 +215,15 @@ class Diffusion:
         return (torch.clamp(snr, max=gamma) / snr).float().contiguous()
 
     @torch.no_grad()
-    def eval_loss(self, model, latents, text_features, labels, t, noise=None, seed=None, loss_mask=None, phoscLabels=None):
+    def eval_loss(self, model, latents, text_features, labels, t, noise=None, seed=None, loss_mask=None, phoscLabels=None,
+                  writer_keep=None):
         """Held-out loss: ``noise_images(latents, t)``, the model's inference forward, then the per-sample masked squared error
         (``optim.weighted_mse_loss`` without a gradient) -> device fp32 [B], sample b's UNWEIGHTED mean over its mask (weights
         are the caller's to apply: ``min_snr_weights()[t]``).  The model runs in ``eval()`` for the call and every module's
         ``training`` flag is put back afterwards; no weight is updated and no generator is drawn from: the noise is ``noise``, or
         the device Philox stream of ``seed`` (0 when neither is given, so a held-out set scores the same from call to call).
-        ``t``: an integer tensor [B] in [0, noise_steps); ``loss_mask``: the known-region shapes, values in [0, 1]."""
+        ``t``: an integer tensor [B] in [0, noise_steps); ``loss_mask``: the known-region shapes, values in [0, 1].
+        ``writer_keep``: handed to the model's forward - ``False`` scores the writer-free branch a guided sampler runs."""
         from .optim import check_timesteps, expand_loss_mask, weighted_mse_loss
         if latents.dim() != 4:
             raise ValueError(f"latents must be [B, C, h, w], got {tuple(latents.shape)}")
@@ -238,6 +240,8 @@ class Diffusion:
         model.eval()
         try:
             kw = dict(timesteps=t.to(dev), context=text_features.to(dev), y=None if labels is None else labels.to(dev))
+            if writer_keep is not None:
+                kw["writer_keep"] = writer_keep
             if getattr(model, "variant", "base") == "phosc":
                 pred = model(x_t, None if phoscLabels is None else phoscLabels.to(dev), **kw)
             else:
@@ -522,7 +526,8 @@ class Diffusion:
         return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
 
     def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None, attention=None):
+                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None, attention=None,
+                 writer_free=None):
         """The one reverse loop.  Per visited step of ``sampler`` (``_ddpm`` / ``_ddim``): this step's ``noise`` entry into
         the noise buffer if it has one, ``film_prepare`` and the forward(s) when the step calls the model, the sampler's update.
         mix = (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
@@ -534,10 +539,14 @@ class Diffusion:
         back in at the level the step reached (``wd_known_blend``, inside the captured graph).
         attention: what ``_attention_setup`` returned.  The plan then holds three map accumulators, zeroed here, and every
         model-calling step adds its weight times its maps (``wd_xattn_maps`` inside the captured step, the first forward of a
-        step only); the weighted mean lands in ``last_attention``."""
+        step only); the weighted mean lands in ``last_attention``.
+        writer_free: None, or the guidance scale of a writer-free guided call (``_guidance_setup``): a step is the conditional
+        forward, the forward without the writer term (``engine.plan`` guide = 2) and the guided update
+        ``torch.lerp(free, cond, scale)`` - the two-forward step of the interpolation mode with other FiLM rows."""
         lib = N.lib()
         eng = model.engine
         nf = 0 if mix is None else int(mix[0].shape[0])
+        two = nf == 2 or writer_free is not None  # forwards per step with predictions of their own, lerped by the update
         if nf:
             eng.check_pairs(mix[0])  # first: nothing is launched for an id that does not fit the table
             labels = None  # unused in this mode (unet.py:1558-1573)
@@ -547,12 +556,13 @@ class Diffusion:
         ctx_len = text_features.shape[1]
         phosc_len = 0 if phosc is None else phosc.shape[1]
         # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
-        film_steps = self.noise_steps if (self.tabulate_film or nf) else 0
+        film_steps = self.noise_steps if (self.tabulate_film or nf or writer_free is not None) else 0
         P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
                      film_timesteps=tuple(sampler.tau) if (film_steps and sampler.tau is not None) else None,
                      **(dict(attn_maps=True, attn_rows=attention[0].numel(), attn_by_step=sampler.tau is not None)
-                        if attention is not None else {}))
-        fps = nf or self.forwards_per_step
+                        if attention is not None else {}),
+                     **(dict(guide=2) if writer_free is not None else {}))
+        fps = nf or (2 if writer_free is not None else self.forwards_per_step)
         ncalls = sum(fwd for _, fwd, _ in sampler.steps)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
         npix = P.x_in[0].numel()
@@ -592,12 +602,12 @@ class Diffusion:
                 P.map_w.copy_(attention[0])
                 for acc in P.maps:
                     acc.zero_()
-            eps_g = torch.empty_like(P.out) if (nf == 2 and record_pred is not None) else None
+            eps_g = torch.empty_like(P.out) if (two and record_pred is not None) else None
             P.t_dev.fill_(sampler.t_first)
             P.t_in.fill_(sampler.t_first)
             zbuf = torch.zeros_like(P.x_in) if noise is not None else None
-            end_step = sampler.update(lib, P, (float(mix[2]), eps_g) if nf == 2 else None, zbuf, seed, sample_offset, device,
-                                      known=blend)
+            scale = None if not two else float(mix[2]) if nf else float(writer_free)
+            end_step = sampler.update(lib, P, (scale, eps_g) if two else None, zbuf, seed, sample_offset, device, known=blend)
             P.run_cond(st)
             P.run_film(st)  # time MLP of every timestep; the FiLM rows follow per chunk of timesteps (P.film_prepare)
             # before the capture: the captured step only reads the table (its rows are indexed by t, or by the DDIM step index)
@@ -606,9 +616,9 @@ class Diffusion:
 
             def one_step(stream, forward=True):
                 if forward:
-                    for _ in range(1 if nf else fps):
+                    for _ in range(1 if two or nf else fps):
                         P.run_step(stream)
-                    if nf == 2:  # train.py:223-228 with two different pairs: lerp(second, first, cfg_scale) feeds the update
+                    if two:  # train.py:223-228 with two different forwards: lerp(second, first, cfg_scale) feeds the update
                         P.run_step1(stream)
                 end_step(stream)
 
@@ -639,7 +649,7 @@ class Diffusion:
                 else:
                     one_step(st, fwd)
                 if record_pred is not None and fwd:
-                    record_pred.append((P.out.clone(),) if nf != 2 else (P.out.clone(), P.out1.clone(), eps_g.clone()))
+                    record_pred.append((P.out.clone(),) if not two else (P.out.clone(), P.out1.clone(), eps_g.clone()))
             x = P.x_in.clone()
             self.last_attention = None
             if attention is not None:
@@ -652,11 +662,32 @@ class Diffusion:
             if gskip is not None:
                 lib.wd_graph_destroy(gskip)
         self.last_stats = dict(sampler.stats, forwards_per_step=fps, graph=gexec is not None, seed=seed,
-                               sample_offset=sample_offset, model_calls=ncalls * (nf or 1), known=known is not None,
+                               sample_offset=sample_offset, model_calls=ncalls * (2 if two else nf or 1), known=known is not None,
                                start=None if known is None else known.start, known_noise=None if known is None else known.mode)
         if attention is not None:
             self.last_stats["attention_steps"] = attention[1]
+        if writer_free is not None:
+            self.last_stats["guidance"] = "writer_free"
         return x
+
+    def _guidance_setup(self, model, guidance, cfg_scale, mix):
+        """The ``guidance`` argument of a sampler call, settled on the host: the ``writer_free`` argument of ``_denoise`` - None,
+        or the scale of the guided update.  ``guidance="writer_free"`` with ``cfg_scale > 0`` runs, per model-calling step, the
+        conditional forward, the forward without the writer term and ``torch.lerp(free, cond, cfg_scale)``; with ``cfg_scale == 0``
+        one forward runs, as behind the reference's ``if cfg_scale > 0`` (train.py:223), and the call is the plain one."""
+        if guidance is None:
+            return None
+        if guidance != "writer_free":
+            raise ValueError(f"guidance must be None or 'writer_free', not {guidance!r}")
+        if mix is not None:
+            raise ValueError("guidance='writer_free' cannot be combined with writer-style interpolation (args.interpolation "
+                             "with a mix_rate, or style_pairs)")
+        if getattr(model, "num_classes", None) is None:
+            raise ValueError("guidance='writer_free' needs a class-conditional model (num_classes)")
+        s = float(cfg_scale)
+        if not math.isfinite(s) or s < 0:
+            raise ValueError(f"cfg_scale must be a finite number >= 0, got {cfg_scale!r}")
+        return s if s > 0 else None
 
     def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, *, sampler=None):
         """The ``mix`` argument of ``_denoise`` for a sampler call, or None where the call does not interpolate.
@@ -735,7 +766,8 @@ class Diffusion:
     @torch.no_grad()
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
-                 style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto", attention=None):
+                 style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto", attention=None,
+                 guidance=None):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
@@ -758,17 +790,25 @@ class Diffusion:
         ``attention=True | (t_hi, t_lo)``: the per-character cross-attention maps of the call (the reference's --attentionMaps 1
         outputs, unet.py:1645-1832), averaged over the model-calling steps (those with t_lo <= t <= t_hi), are left in
         ``last_attention = {"input", "middle", "output"}``, fp32 [n, h, w, L] at latent resolution; ``last_stats`` gains
-        ``attention_steps``.  Base model only."""
+        ``attention_steps``.  Base model only.
+
+        ``guidance="writer_free"`` (``_guidance_setup``; DESIGN.md "Writer-free guidance"): classifier-free guidance on the writer.
+        With ``cfg_scale > 0`` every model-calling step runs the conditional forward, the forward without the writer term and the
+        guided update ``torch.lerp(free, cond, cfg_scale)``; ``last_stats`` reports ``forwards_per_step == 2`` and
+        ``guidance``, ``record_pred`` receives (cond, free, guided) and ``attention`` reads the conditional forward.  With
+        ``cfg_scale == 0`` the call is the plain one.  Without the argument ``cfg_scale`` stays inert outside interpolation mode,
+        as in the reference, whose two forwards are identical (train.py:224-228).  Not together with the interpolation modes."""
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True)
         device, tf, phosc = self._prepare("sampling", model, n, x_text, args, phoscLabels, underscore)
         sampler = self._ddpm(start=None if kn is None else kn.start)
         att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
+        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
-                              record_pred=record_pred, known=kn, attention=att)
+                              record_pred=record_pred, known=kn, attention=att, writer_free=wf)
         finally:
             model.train()  # train.py:238 (unconditional)
         return self._finish(x, vae, args)
@@ -777,7 +817,7 @@ class Diffusion:
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
                       phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
                       use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None, start=None,
-                      known_noise="auto", attention=None):
+                      known_noise="auto", attention=None, guidance=None):
         """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
         ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
         deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
@@ -790,8 +830,8 @@ class Diffusion:
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling``; with ``start`` the call visits the entries of
         its usual schedule that are <= start (``steps`` and ``timesteps`` of ``last_stats`` are the retained ones, FiLM rows,
         pairs and ``noise`` are indexed by them) and the first of them is the level noised to.  With ``eta = 0`` the default
-        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention`` as in
-        ``sampling``."""
+        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention`` and
+        ``guidance`` as in ``sampling``."""
         tau = self.ddim_timesteps(steps, timesteps)
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau)
         if kn is not None:
@@ -802,11 +842,12 @@ class Diffusion:
         sampler = self._ddim(tau, eta)
         att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
+        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
                               sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
-                              known=kn, attention=att)
+                              known=kn, attention=att, writer_free=wf)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)
@@ -815,7 +856,7 @@ class Diffusion:
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
                        mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
                        record_pred=None, use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None,
-                       start=None, known_noise="auto", attention=None):
+                       start=None, known_noise="auto", attention=None, guidance=None):
         """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
         ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
         the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
@@ -826,7 +867,8 @@ class Diffusion:
         returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
         ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``.
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling_ddim`` (the default noise is the fixed eps: no
-        step draws); the first retained step is first order, like the first step of any call.  ``attention`` as in ``sampling``."""
+        step draws); the first retained step is first order, like the first step of any call.  ``attention`` and ``guidance`` as in
+        ``sampling``."""
         tau = self.dpmpp_timesteps(steps, spacing, timesteps)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
@@ -837,10 +879,12 @@ class Diffusion:
         sampler = self._dpmpp(tau, order, None if timesteps is not None else spacing)
         att = self._attention_setup(model, sampler, attention)
         mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
+        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
         model.eval()
         try:
             x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, seed=seed, sample_offset=sample_offset,
-                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn, attention=att)
+                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn, attention=att,
+                              writer_free=wf)
         finally:
             model.train()  # as ``sampling`` (train.py:238)
         return self._finish(x, vae, args)

@@ -129,7 +129,7 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
                ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
                known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto",
-               attention=None, attn_out: Optional[str] = None):
+               attention=None, attn_out: Optional[str] = None, guidance: Optional[str] = None, cfg_scale: float = 3.0):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -148,7 +148,12 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``attention`` (True or a timestep window ``(t_hi, t_lo)``, as in ``Diffusion.sampling``): every call also leaves its
     per-character cross-attention maps; ``attn_out`` (a ``.npz`` path; a relative one lands in ``out_dir``, beside the images)
     receives them for the shard: ``input`` / ``middle`` / ``output`` fp32 [rows, h, w, 10], row i belonging to ``images[i]`` /
-    ``words[i]``.  ``attn_out`` alone means ``attention=True``."""
+    ``words[i]``.  ``attn_out`` alone means ``attention=True``.
+
+    ``guidance="writer_free"`` with ``cfg_scale`` (``Diffusion.sampling``): classifier-free guidance on the writer, two forwards
+    per step.  Not with ``skip_steps``, whose sampler has no guidance."""
+    if guidance is not None and skip_steps:
+        raise ValueError("guidance is not supported by the step-skipping sampler (skip_steps)")
     if attn_out is not None and attention is None:
         attention = True
     _check_sampler(sampler, skip_steps)
@@ -180,6 +185,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         kw = dict(seed=seed, sample_offset=first + b0, mix_rate=mix_rate)
         if attention is not None:
             kw.update(attention=attention)
+        if guidance is not None:
+            kw.update(guidance=guidance, cfg_scale=cfg_scale)
         if known is not None:
             kw.update(known=torch.stack(latents[b0:b0 + batch]), known_mask=kmask, start=start, known_noise=known_noise)
         if sampler == "ddim":
@@ -302,6 +309,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="two writer class indices: one strip per gt row from S1 to S2 in --mix_steps samples is written "
                          "instead of the rows themselves")
     ap.add_argument("--mix_steps", type=int, default=8)
+    ap.add_argument("--guidance", default=None, choices=["writer_free"],
+                    help="writer_free: classifier-free guidance on the writer - every step also runs the model without the writer "
+                         "embedding and extrapolates by --cfg_scale (for a model trained with label dropout)")
+    ap.add_argument("--cfg_scale", type=float, default=3.0, help="--guidance: the guidance scale (train.py:200); 0 turns it off")
     ap.add_argument("--stable_dif_path", default=None,
                     help="local Stable-Diffusion checkout in diffusers layout (its vae/ subfolder is read; train.py:415): with it "
                          "the rows are decoded and written as PNGs, without it as latents (.npy)")
@@ -335,6 +346,8 @@ def parse_args(argv=None):
         ap.error(f"--ddim_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
     if a.sampler == "dpmpp" and not 1 <= a.dpmpp_steps <= a.noise_steps - 1:
         ap.error(f"--dpmpp_steps must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.guidance is not None and (a.skip_steps or a.style_pair is not None or (a.interpolation and a.mix_rate is not None)):
+        ap.error("--guidance cannot be combined with --skip_steps 1, --style_pair or --interpolation with a --mix_rate")
     if a.init_latents is None and (a.keep_cols is not None or a.start is not None):
         ap.error("--keep_cols and --start need --init_latents (the latents to start from)")
     if a.init_latents is not None:
@@ -428,6 +441,7 @@ def main(argv=None):
                             phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
                             dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing, known=known,
                             keep_cols=a.keep_cols, start=a.start,
+                            guidance=a.guidance, cfg_scale=a.cfg_scale,
                             attention=None if a.attn_maps is None else (a.attn_window or True),
                             attn_out=None if a.attn_maps is None else
                             (a.attn_maps if world == 1 else a.attn_maps[:-4] + f".rank{rank}.npz"))

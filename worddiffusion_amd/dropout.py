@@ -7,6 +7,9 @@ One Philox4x32-10 draw covers four consecutive elements of a sample's token-majo
     idx = token * c + ch,  e4 = idx >> 2,  element idx reads output word idx & 3 and is kept iff word >= threshold(p)
 
 ``row`` is the global sample row, ``tag = tag(layer)`` and a kept element is multiplied by ``scale(p)``.
+
+The writer dropout of a training step (DESIGN.md "Writer-free guidance") is one such draw per sample: counter (0, label_tag(), row),
+the same key, word 0 against ``threshold(p)``; nothing is scaled.
 """
 from __future__ import annotations
 
@@ -14,7 +17,7 @@ from typing import Dict
 
 import numpy as np
 
-from ._native import STREAM_DROPOUT0, WdDropout  # noqa: F401  (wd_dropout and WD_STREAM_DROPOUT0 of include/wdiff_hip.h)
+from ._native import STREAM_DROPOUT0, STREAM_LABEL_DROP, WdDropout  # noqa: F401  (wd_dropout, WD_STREAM_* of include/wdiff_hip.h)
 
 _KEY = "out_layers.3.weight"
 
@@ -38,6 +41,12 @@ def scale(p: float) -> np.float32:
 
 def tag(layer: int) -> int:
     return 0x80000000 | (STREAM_DROPOUT0 + int(layer))
+
+
+def label_tag() -> int:
+    """The tag of the writer dropout (``wd_label_rows_keep``): one draw per global sample row with counter (0, tag, row), the
+    sample keeps its writer iff word 0 >= threshold(p).  Disjoint from every ``tag(layer)``, WD_TAG_KNOWN and the bare timesteps."""
+    return 0x80000000 | STREAM_LABEL_DROP
 
 
 def layer_ids(model) -> Dict[str, int]:

@@ -355,6 +355,14 @@ class Plan:
         self._run(self.step1, stream)
 
 
+def check_writer_keep(writer_keep, B: int) -> torch.Tensor:
+    """The ``writer_keep`` argument as a uint8 tensor [B] (1: the sample keeps its writer term); raises for anything else."""
+    k = torch.as_tensor(writer_keep)
+    if k.dtype not in (torch.bool, torch.uint8) or tuple(k.shape) != (B,):
+        raise ValueError(f"writer_keep must be a bool / uint8 tensor [{B}], False or None, got {k.dtype} {tuple(k.shape)}")
+    return (k != 0).to(torch.uint8)
+
+
 def _ptr(t: Optional[torch.Tensor], byte_off: int = 0):
     return None if t is None else t.data_ptr() + byte_off
 
@@ -1562,7 +1570,7 @@ class UNetEngine:
 
     def plan(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int, film_steps: int = 0, mix: int = 0,
              film_timesteps: Optional[tuple] = None, attn_maps: bool = False, attn_rows: int = 0,
-             attn_by_step: bool = False) -> Plan:
+             attn_by_step: bool = False, guide: int = 0, writer_keep: bool = False) -> Plan:
         """film_steps = T > 0 (the DDPM sampler): the whole time / writer embedding path (timestep_embedding, time_embed,
         label_emb, SiLU, every emb_layers) is tabulated for all T timesteps by ``P.film`` ops - one large GEMM per
         ``sampling()`` call instead of three 64-row GEMMs per step - and each step copies its rows (``wd_select_rows``).
@@ -1580,8 +1588,18 @@ class UNetEngine:
         and each gains one ``wd_xattn_maps`` launch after its attention launch, into ``P.maps[i]`` fp32 [B, h_i*w_i, L].  Every
         other launch is the default plan's with WDIFF_FUSE_ST=0 for those three blocks.  attn_rows = 0: a step overwrites the
         maps.  attn_rows = R > 0 (the samplers): a step adds ``P.map_w[row] * map``, ``P.map_w`` fp32 [R] filled by the caller,
-        row = ``P.k_dev`` if attn_by_step else ``P.t_dev``; with mix = 2 only the first forward of a step adds."""
+        row = ``P.k_dev`` if attn_by_step else ``P.t_dev``; with mix = 2 only the first forward of a step adds.
+
+        guide = 2 (writer-free guidance, with the table): a two-forward plan built as mix = 2 is - ``P.step`` reads the rows of
+        forward 0, SiLU(time + label[y]), ``P.step1`` those of forward 1, SiLU(time) (``wd_emb_combine_keep`` without a keep
+        mask), and writes ``P.out1``.  Not together with mix.
+        writer_keep (without the table): the writer term per sample - ``wd_label_rows_keep`` turns ``P.keep_in`` (uint8 [B],
+        filled by ``load_keep``) into the residual rows of the time_embed.2 GEMM, label[y_b] or zeros."""
         key = (B, H, W, ctx_len, phosc_len, self.npass, film_steps) + ((("mix", mix),) if mix else ())
+        if guide:
+            key += (("guide", guide),)
+        if writer_keep:
+            key += (("writer_keep",),)
         if attn_maps:
             key += (("maps", int(attn_rows), bool(attn_by_step)),)
         if film_timesteps is not None:
@@ -1598,15 +1616,22 @@ class UNetEngine:
             raise ValueError("writer-style interpolation needs a class-conditional model (num_classes)")
         if mix not in (0, 1, 2) or (mix == 2 and not film_steps):
             raise ValueError(f"mix = {mix}: 1 or 2 forwards per step with the table, 1 without")
+        if (guide or writer_keep) and mix:
+            raise NotImplementedError("writer-free guidance on top of writer-style interpolation (guide / writer_keep with mix)")
+        if (guide or writer_keep) and self.model.num_classes is None:
+            raise ValueError("writer-free guidance needs a class-conditional model (num_classes)")
+        if guide not in (0, 2) or (guide and not film_steps) or (writer_keep and (film_steps or guide)):
+            raise ValueError(f"guide = {guide}: two forwards per step with the table; writer_keep: the plan without the table")
         taps = self._map_taps(ctx_len + phosc_len) if attn_maps else ()  # (raises before anything is built or launched)
         P = self._begin_plan(Plan(), B)
         dev = self.device
         self._inputs(P, H, W, ctx_len, phosc_len)
         P.map_taps = taps
         self._conditioning(P, P.cond, ctx_len, phosc_len)  # step-invariant: run once per call (P.cond)
-        P.mix = mix
+        P.mix, P.guide = mix, guide
         if mix:
             P.mix_m = torch.zeros((B,), dtype=torch.float32, device=dev)
+        P.keep_in = torch.ones((B,), dtype=torch.uint8, device=dev) if writer_keep else None
         self._film = self._f32(P, B, self.film_total)
         P.t_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
         P.k_dev = torch.zeros((1,), dtype=torch.int32, device=dev)  # index into film_timesteps (the table-driven loop)
@@ -1620,7 +1645,7 @@ class UNetEngine:
         cur = self._head(P, H, W)
         cur = self._trunk(P, cur)
         self._tail(P, cur)
-        if mix == 2:
+        if mix == 2 or guide == 2:
             self._second_forward(P, select1)
         self._plans[key] = P
         return P
@@ -1628,7 +1653,7 @@ class UNetEngine:
     def _film_table(self, P: Plan, film_steps: int, film_timesteps: Optional[tuple]):
         """The tabulated FiLM path (``plan`` film_steps / film_timesteps): ``P.film`` evaluates the time MLP of every table row once
         per call, ``P.film_prepare`` makes the chunk of rows a step reads resident, and the step begins by selecting its rows.
-        Returns the select op a second forward begins with (mix = 2), else None."""
+        Returns the select op a second forward begins with (mix = 2 or guide = 2), else None."""
         lib, dev, B, mix, film = self.lib, self.device, self._B, P.mix, P.film
         mc = self.model.model_channels
         ted = 4 * mc
@@ -1638,7 +1663,7 @@ class UNetEngine:
         # planes and the emb_layers GEMM of a chunk run when the loop enters it (P.film_prepare, same stream, a fraction
         # of one step each).
         T = film_steps if film_timesteps is None else len(film_timesteps)  # rows of the table: all t, or the visited ones
-        nf = max(1, mix)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
+        nf = max(1, mix, P.guide)  # tables (forwards per step with FiLM rows of their own); the resident rows are shared between them
         # (a table over all t keeps at least 8 timesteps resident; one over the visited steps is cut by rows alone)
         chunk = min(T, max(8 if film_timesteps is None else 1, FILM_CHUNK_ROWS // (B * nf)))
         nchunks = (T + chunk - 1) // chunk
@@ -1669,7 +1694,7 @@ class UNetEngine:
         row_dev = P.t_dev if film_timesteps is None else P.k_dev
         P.step.append((lib.wd_select_rows, (P.film_table.data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
                                             self._film.data_ptr()), "film rows of step t"))
-        if mix != 2:
+        if nf != 2:
             return None
         return (lib.wd_select_rows, (P.film_table[chunk * B].data_ptr(), row_dev.data_ptr(), B, self.film_total, chunk,
                                      self._film.data_ptr()), "film rows of step t, second forward")
@@ -1697,6 +1722,10 @@ class UNetEngine:
             else:
                 N.check(lib.wd_emb_combine(tm.data_ptr() + 4 * c * chunk * ted, lab, yin, ncls, chunk, B, ted, *self._hilo(e2), ted,
                                            stream), "SiLU(time + label)[chunk of t]")
+                if P.guide:  # table 1: the writer-free rows, SiLU(time) (no keep mask: no sample keeps its writer)
+                    N.check(lib.wd_emb_combine_keep(tm.data_ptr() + 4 * c * chunk * ted, None, None, None, 0, chunk, B, ted,
+                                                    *self._hilo(e2, 2 * chunk * B * ted), ted, stream),
+                            "SiLU(time)[chunk of t]")
             Plan._run(chunk_gemm, stream)
             P.film_loaded = c
             return True
@@ -1705,11 +1734,12 @@ class UNetEngine:
 
     def _film_per_step(self, P: Plan):
         """The embedding path evaluated in every step (no table): three B-row GEMMs into ``self._film``.  mix: the label term is
-        the blend of each sample's pair of writers."""
+        the blend of each sample's pair of writers.  ``P.keep_in``: it is label[y_b] or zeros, per sample."""
         m, lib, dev, B, mix, step = self.model, self.lib, self.device, self._B, P.mix, P.step
         mc = m.model_channels
         ted = 4 * mc
         has_lab = m.num_classes is not None
+        own_rows = bool(mix) or P.keep_in is not None  # the writer rows of this batch are computed, not gathered from the table by y
         if mix:
             # the blended rows [B, ted] (wd_label_mix) are the residual of the time_embed.2 GEMM, row b for sample b
             P.pairs = torch.zeros((B, 2), dtype=torch.int32, device=dev)
@@ -1718,6 +1748,13 @@ class UNetEngine:
             P.keep.append(id_rows)
             step.append((lib.wd_label_mix, (self._w["label"].data_ptr(), P.pairs.data_ptr(), P.mix_m.data_ptr(), m.num_classes,
                                             B, ted, lab_rows.data_ptr()), "blended label rows"))
+        if P.keep_in is not None:  # the same residual form: rows [B, ted] read with identity row ids
+            lab_rows = self._f32(P, B, ted)
+            id_rows = torch.arange(B, dtype=torch.int64, device=dev)
+            P.keep.append(id_rows)
+            step.append((lib.wd_label_rows_keep, (self._w["label"].data_ptr(), P.y_in.data_ptr(), m.num_classes, B, ted, None,
+                                                  P.keep_in.data_ptr(), lab_rows.data_ptr(), None, None),
+                         "kept label rows"))
         te = self._planes(P, B, mc)
         step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
                      "timestep_embedding"))
@@ -1726,8 +1763,8 @@ class UNetEngine:
                    out_pl=e1)
         e2 = self._planes(P, B, ted)  # SiLU(emb): the only form any consumer reads (emb_layers start with SiLU)
         self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
-                   resid=(lab_rows if mix else self._w["label"]).data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
-                   resid_rows=(id_rows if mix else P.y_in).data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
+                   resid=(lab_rows if own_rows else self._w["label"]).data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
+                   resid_rows=(id_rows if own_rows else P.y_in).data_ptr() if has_lab else None, act=N.ACT_SILU, out_pl=e2)
         self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"],
                    out_f32=self._film, out_ld=self.film_total)
 
@@ -1767,8 +1804,8 @@ class UNetEngine:
                        "out: GroupNorm + SiLU + conv3x3 -> NCHW"))
 
     def _second_forward(self, P: Plan, select1):
-        """``P.step1`` (mix = 2), the second forward of a step: its own FiLM rows, the same launches, the prediction kept beside
-        the first one in ``P.out1``.  The attention maps accumulate over the first forward alone."""
+        """``P.step1`` (mix = 2 or guide = 2), the second forward of a step: its own FiLM rows, the same launches, the prediction kept
+        beside the first one in ``P.out1``.  The attention maps accumulate over the first forward alone."""
         fn, args, what = P.step[-1]
         assert args[-1] == P.out.data_ptr(), what
         P.out1 = torch.empty_like(P.out)
@@ -1822,6 +1859,13 @@ class UNetEngine:
             P.pairs.copy_(pairs, non_blocking=True)
         P.mix_m.copy_(mix_rate, non_blocking=True)
 
+    def load_keep(self, P: Plan, writer_keep):
+        """writer_keep: bool / uint8 [B] (nonzero: the sample keeps its writer term), or False: no sample does."""
+        if writer_keep is False:
+            P.keep_in.zero_()
+        else:
+            P.keep_in.copy_(check_writer_keep(writer_keep, P.keep_in.shape[0]), non_blocking=True)
+
     def load_inputs(self, P: Plan, x=None, t=None, context=None, y=None, phosc=None, check=True):
         if check:
             self.check_ids(context, y, phosc, need_y=False)
@@ -1836,8 +1880,9 @@ class UNetEngine:
         if phosc is not None:
             P.phosc_in.copy_(phosc.to(torch.int32) if phosc.dtype != torch.int32 else phosc, non_blocking=True)
 
-    def forward(self, x, t, context, y, phosc=None, mix=None, attn_maps=False):
-        """mix = (int pairs [B, 2], fp32 mix rates [B]): the writer term is the blend of each sample's pair and ``y`` is unused
+    def forward(self, x, t, context, y, phosc=None, mix=None, attn_maps=False, writer_keep=None):
+        """writer_keep (``load_keep``): the writer term per sample; None: every sample keeps it, the plan without the argument.
+        mix = (int pairs [B, 2], fp32 mix rates [B]): the writer term is the blend of each sample's pair and ``y`` is unused
         (unet.py:1558-1573).  attn_maps: returns (eps, [m_in, m_mid, m_out]), m_i fp32 [B, h_i, w_i, L]: the per-character
         attention maps of the three tapped SpatialTransformers (``plan``)."""
         self.refresh_weights()
@@ -1847,9 +1892,17 @@ class UNetEngine:
         if mix is not None:
             self.check_pairs(mix[0])
             y = None
-        P = self.plan(B, H, W, ctx_len, phosc_len, mix=1 if mix is not None else 0, attn_maps=bool(attn_maps))
+        if writer_keep is not None:
+            if mix is not None or attn_maps:
+                raise ValueError("writer_keep cannot be combined with writer-style interpolation (mix_rate) or return_attention")
+            if writer_keep is not False:
+                writer_keep = check_writer_keep(writer_keep, B)
+        P = self.plan(B, H, W, ctx_len, phosc_len, mix=1 if mix is not None else 0, attn_maps=bool(attn_maps),
+                      **(dict(writer_keep=True) if writer_keep is not None else {}))
         self.check_ids(context, y, phosc, need_y=mix is None)
         self.load_inputs(P, x, t, context, y, phosc, check=False)
+        if writer_keep is not None:
+            self.load_keep(P, writer_keep)
         if mix is not None:
             self.load_mix(P, mix[0], mix[1], check=False)
         stream = torch.cuda.current_stream(self.device).cuda_stream

@@ -217,8 +217,17 @@ class UNetBase(nn.Module):
         eng.dropout_seed, eng.dropout_row_base = int(seed), int(row_base)
         return self
 
-    def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None, return_attention=False):
+    def _run(self, x, timesteps, context, y, phosc=None, mix_rate=None, return_attention=False, writer_keep=None):
+        """writer_keep: None, a bool / uint8 tensor [B] (nonzero: the sample keeps its writer term) or False (no sample does: the
+        reference's ``args.imgConditioned == 1`` forward, unet.py:1578-1579)."""
         autograd = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if writer_keep is not None:
+            if self.num_classes is None:
+                raise ValueError("writer_keep needs a class-conditional model (num_classes)")
+            if return_attention is not False:
+                raise NotImplementedError("writer_keep together with return_attention")
+            if self.interpolation and mix_rate is not None:
+                raise NotImplementedError("writer_keep together with mix_rate in interpolation mode")
         if return_attention is not False:
             return self._run_attention(x, timesteps, context, y, phosc, mix_rate, return_attention, autograd)
         if self.training and not autograd and float(self.dropout) > 0:
@@ -242,8 +251,9 @@ class UNetBase(nn.Module):
             # ``predicted_noise = model(...)`` inside the training loop (train.py:287): the result carries a grad_fn whose
             # backward runs the HIP backward list and fills ``param.grad`` (reference layouts), so ``loss.backward()``,
             # ``optimizer.step()`` and ``ema.step_ema`` of the reference loop work unchanged.
-            return _HipUNetStep.apply(self, x, timesteps, context, y, phosc, self._grad_anchor(x.device)).type(x.dtype)
-        out = self.engine.forward(x.float(), timesteps, context, y, phosc)
+            return _HipUNetStep.apply(self, x, timesteps, context, y, phosc, self._grad_anchor(x.device),
+                                      writer_keep).type(x.dtype)
+        out = self.engine.forward(x.float(), timesteps, context, y, phosc, writer_keep=writer_keep)
         return out.type(x.dtype)
 
     def _run_attention(self, x, timesteps, context, y, phosc, mix_rate, mode, autograd):
@@ -320,12 +330,12 @@ class _HipUNetStep(torch.autograd.Function):
     asks for one)."""
 
     @staticmethod
-    def forward(ctx, model, x, timesteps, context, y, phosc, anchor):
+    def forward(ctx, model, x, timesteps, context, y, phosc, anchor, writer_keep=None):
         eng = model.train_engine
         ctx.eng = eng
-        return eng.forward_train(x.float(), timesteps, context, y, phosc).clone()
+        return eng.forward_train(x.float(), timesteps, context, y, phosc, writer_keep=writer_keep).clone()
 
     @staticmethod
     def backward(ctx, gout):
         ctx.eng.backward(gout.contiguous().float())
-        return None, None, None, None, None, None, torch.zeros_like(ctx.eng.model._anchor)
+        return None, None, None, None, None, None, torch.zeros_like(ctx.eng.model._anchor), None

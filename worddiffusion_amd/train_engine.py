@@ -28,7 +28,7 @@ import torch
 from . import _native as N
 from . import dropout as DO
 from .backward import conv_bwd_table
-from .engine import Act, Plan, UNetEngine, _ptr
+from .engine import Act, Plan, UNetEngine, _ptr, check_writer_keep
 from .layers import DownsampleParams, ResBlockParams, SpatialTransformerParams, UpsampleParams
 
 
@@ -50,6 +50,9 @@ class TrainPlan(Plan):
         # row base they all point to - uint64 [1] kept as int64 bits -, so a captured step draws new masks when replayed
         self.dropouts: List[DO.WdDropout] = []
         self.row_base: Optional[torch.Tensor] = None
+        # writer dropout (plan_train label_drop): the decision of the last forward, uint8 [B], written by wd_label_rows_keep; a
+        # drawn one is keyed by a wd_dropout of its own in ``dropouts`` (same seed, same row base, the tag of dropout.label_tag)
+        self.writer_keep: Optional[torch.Tensor] = None
 
     def set_dropout_seed(self, seed: int):
         for d in self.dropouts:
@@ -876,10 +879,22 @@ class TrainEngine(UNetEngine):
         if self._ws is None or self._ws.numel() < 8 * 2 * cmax * 9 * cmax:
             self._ws = torch.empty(max(128 * 128 * 160 * 8, 8 * 2 * cmax * 9 * cmax), dtype=torch.float32, device=self.device)
 
-    def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0) -> TrainPlan:
+    def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0, label_drop=None) -> TrainPlan:
+        """label_drop: None - every sample keeps its writer term, the plan without the argument; "mask" - the term per sample from
+        ``P.keep_in`` (uint8 [B], ``load_keep``); a float p in (0, 1) - dropped with probability p, drawn on the device per
+        global sample row (``wd_label_rows_keep``).  Either way the rows the kernel writes are the residual of the time_embed.2
+        GEMM and label_emb's backward reads the ids it writes (-1 for a dropped sample: no gradient row)."""
         # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1): refused before any device work; a plan is built for its p's
         drops = tuple(DO.check_p(mod.out_layers[2].p) for _, mod in self._walk() if isinstance(mod, ResBlockParams))
         key = (B, H, W, ctx_len, phosc_len, self.npass) + ((drops,) if any(drops) else ())
+        if label_drop is not None:
+            if label_drop != "mask":
+                label_drop = DO.check_p(label_drop)
+                if label_drop == 0.0:
+                    raise ValueError("label_drop = 0 is the plan without the argument: pass None")
+            if self.model.num_classes is None:
+                raise ValueError("writer dropout needs a class-conditional model (num_classes)")
+            key += (("label_drop", label_drop),)
         P = self._cached_plan(self._tplans, key)
         if P is not None:
             return P
@@ -921,10 +936,30 @@ class TrainEngine(UNetEngine):
         e1 = self._planes(P, B, ted)
         step.append((lib.wd_split, (pre1.data_ptr(), ted, B, ted, 1, *self._hilo(e1), ted), "time_embed.1(SiLU)"))
         has_lab = m.num_classes is not None
+        lab, lab_rows, y_bwd = (self._w["label"], P.y_in, P.y_in) if has_lab else (None, None, None)
+        if label_drop is not None:
+            # the writer rows of the batch, label[y_b] or zeros, read with identity row ids (the residual form of wd_label_mix)
+            lab = self._f32(P, B, ted)
+            lab_rows = torch.arange(B, dtype=torch.int64, device=dev)
+            y_bwd = torch.zeros((B,), dtype=torch.int64, device=dev)
+            P.writer_keep = torch.ones((B,), dtype=torch.uint8, device=dev)
+            P.keep += [lab_rows, y_bwd]
+            d = None
+            if label_drop == "mask":
+                P.keep_in = torch.ones((B,), dtype=torch.uint8, device=dev)
+            else:
+                d = DO.WdDropout()
+                d.seed, d.row_base, d.row_base_dev = 0, 0, P.row_base.data_ptr()
+                d.tag, d.thr, d.scale = DO.label_tag(), DO.threshold(label_drop), 1.0
+                P.dropouts.append(d)
+            step.append((lib.wd_label_rows_keep, (self._w["label"].data_ptr(), P.y_in.data_ptr(), m.num_classes, B, ted,
+                                                  C.byref(d) if d is not None else None,
+                                                  P.keep_in.data_ptr() if d is None else None, lab.data_ptr(), y_bwd.data_ptr(),
+                                                  P.writer_keep.data_ptr()), "kept label rows"))
         pre2 = self._f32(P, B, ted)
         self._gemm(step, "time_embed.2+label", [self._src(e1, ted)], "te2.w", B, 1, bias=self._w["te2.b"],
-                   resid=self._w["label"].data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
-                   resid_rows=P.y_in.data_ptr() if has_lab else None, out_f32=pre2, out_ld=ted)
+                   resid=lab.data_ptr() if has_lab else None, resid_ld=ted if has_lab else 0,
+                   resid_rows=lab_rows.data_ptr() if has_lab else None, out_f32=pre2, out_ld=ted)
         e2 = self._planes(P, B, ted)
         step.append((lib.wd_split, (pre2.data_ptr(), ted, B, ted, 1, *self._hilo(e2), ted), "emb_layers.0(SiLU)"))
         self._film = self._f32(P, B, self.film_total)
@@ -1001,7 +1036,7 @@ class TrainEngine(UNetEngine):
         bops.append((lib.wd_silu_bwd, (pre2.data_ptr(), de2.data_ptr(), B * ted, dpre2.data_ptr()), "emb SiLU:bwd"))
         if has_lab:
             dl = self._pgrad(m.label_emb.weight)
-            bops.append((lib.wd_embedding_bwd, (P.y_in.data_ptr(), 1, B, dpre2.data_ptr(), ted, m.num_classes, ted, dl.data_ptr(),
+            bops.append((lib.wd_embedding_bwd, (y_bwd.data_ptr(), 1, B, dpre2.data_ptr(), ted, m.num_classes, ted, dl.data_ptr(),
                                                 self._pacc(dl)), "label_emb:bwd"))
         de1 = self._f32(P, B, ted)
         self._bwd_linear(P, "time_embed.2", dpre2, B, ted, 1,
@@ -1065,15 +1100,22 @@ class TrainEngine(UNetEngine):
         return P
 
     # ------------------------------------------------------------------------------------------ run
-    def forward_train(self, x, t, context, y, phosc=None):
-        """Training forward: keeps every intermediate for ``backward``.  Returns the plan's output buffer (no copy)."""
+    def forward_train(self, x, t, context, y, phosc=None, writer_keep=None):
+        """Training forward: keeps every intermediate for ``backward``.  Returns the plan's output buffer (no copy).
+        writer_keep: bool / uint8 [B] or False (``UNetEngine.load_keep``) - the writer term per sample, in the forward and in
+        label_emb's gradient."""
         self.refresh_weights()
         B, _, H, W = x.shape
         if context is None:
             raise NotImplementedError("context=None")
         self.check_ids(context, y, phosc)
-        P = self.plan_train(B, H, W, context.shape[1], 0 if phosc is None else phosc.shape[1])
+        if writer_keep is not None and writer_keep is not False:
+            writer_keep = check_writer_keep(writer_keep, B)
+        P = self.plan_train(B, H, W, context.shape[1], 0 if phosc is None else phosc.shape[1],
+                            **(dict(label_drop="mask") if writer_keep is not None else {}))
         self.load_inputs(P, x, t, context, y, phosc, check=False)
+        if writer_keep is not None:
+            self.load_keep(P, writer_keep)
         if P.dropouts:
             P.set_dropout_seed(self.dropout_seed)
             P.set_row_base(self.dropout_row_base)

@@ -21,8 +21,9 @@ the buffer back into the arena, scales by 1 / A (1 / (A * world) after the all-r
 pointers.  Data-parallel: collectives are issued on the last call only; in the bucketed form the fold of prefix [a0, a1) is queued
 on the compute stream behind segment j and in front of the event its all-reduce waits on, so the overlap is the plain step's.
 
-Keying invariant: ``step_index`` counts CALLS, with or without accumulation, and the eps rows and dropout masks of call c are keyed
-by the global row ``(c * world + rank) * B + b``.  So A calls of B rows draw exactly what one call of A * B rows draws.
+Keying invariant: ``step_index`` counts CALLS, with or without accumulation, and the eps rows, the dropout masks and the writer
+dropout (``label_dropout``) of call c are keyed by the global row ``(c * world + rank) * B + b``.  So A calls of B rows draw
+exactly what one call of A * B rows draws.
 
 A partial group carries over from one call (and one ``train_epoch``) to the next - the buffer and ``micro_index`` belong to this
 object -, but neither is in a checkpoint: save at ``micro_index == 0``.
@@ -44,20 +45,25 @@ from typing import Optional
 import torch
 
 from . import _native as N
+from .dropout import check_p
 from .optim import FusedAdamW, check_loss_weights, check_timesteps, expand_loss_mask
 
 
 class TrainStep:
     def __init__(self, model, diffusion, optimizer: FusedAdamW, seed: int = 0, use_graph: bool = True,
                  process_group=None, bucketed: Optional[bool] = None, accumulate: int = 1, loss_weights=None,
-                 snr_gamma: float = 5.0, loss_bins: int = 0):
+                 snr_gamma: float = 5.0, loss_bins: int = 0, label_dropout: float = 0.0):
         """``bucketed``: run the backward pass in segments with the gradient all-reduce of each segment's arena prefix
         overlapped with the next segment (default: whenever world > 1; ``True`` at world 1 only cuts the graph - tests).
         ``accumulate``: calls per optimiser step (module docstring); 1 is the plain step, launch for launch.
         ``loss_weights``: ``None``, ``"min_snr"`` (``diffusion.min_snr_weights(snr_gamma)``) or a float tensor [noise_steps],
         finite and >= 0: the weight of a sample drawn at timestep t; the returned loss is the weighted one.
         ``loss_bins``: > 0 keeps a histogram of the UNWEIGHTED per-sample losses over that many equal timestep ranges
-        (``loss_by_timestep()``), updated on the device by the loss launch itself."""
+        (``loss_by_timestep()``), updated on the device by the loss launch itself.
+        ``label_dropout``: p in [0, 1) - every sample runs without its writer term with probability p (the training half of
+        writer-free guidance), drawn on the device inside the captured body under the keying invariant of the module docstring;
+        ``last_writer_keep`` holds the decisions of the last call.  0 is the step without the argument, launch for launch."""
+        self.label_dropout = check_p(label_dropout)
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
         if isinstance(loss_bins, bool) or int(loss_bins) != loss_bins or loss_bins < 0:
@@ -100,7 +106,7 @@ class TrainStep:
     def _prepare(self, B, H, W, L, dev, phosc_len=0):
         eng = self.eng
         eng.refresh_weights()
-        P = eng.plan_train(B, H, W, L, phosc_len)
+        P = eng.plan_train(B, H, W, L, phosc_len, **(dict(label_drop=self.label_dropout) if self.label_dropout > 0 else {}))
         ah = self.diffusion.alpha_hat.cpu()
         self._sa, self._sb = torch.sqrt(ah).to(dev).contiguous(), torch.sqrt(1 - ah).to(dev).contiguous()
         self._x0 = torch.zeros_like(P.x_in)
@@ -326,6 +332,14 @@ class TrainStep:
         """The optimiser's ``grad_norm``: device fp32 [1], the global norm of the (mean) gradient of the last optimiser step,
         before clipping (``FusedAdamW(max_grad_norm=...)``; zero while clipping is off)."""
         return self.opt.grad_norm
+
+    @property
+    def last_writer_keep(self) -> torch.Tensor:
+        """Device uint8 [B]: 1 where the sample of the last call kept its writer term, written by the step itself; nothing
+        synchronises.  Only a step built with ``label_dropout > 0`` draws it."""
+        if not self.label_dropout or self._key is None:
+            raise RuntimeError("last_writer_keep: no call has drawn a writer dropout (TrainStep(label_dropout > 0))")
+        return self._P.writer_keep
 
     @property
     def last_sample_losses(self) -> torch.Tensor:

@@ -28,15 +28,18 @@ class UNetModel(UNetBase):
 
     def forward(self, x, wrdChrWrStyl=None, original_images=None, timesteps=None, context=None, y=None,
                 charContextImages=None, original_context=None, or_images=None, mix_rate=None, return_attention=False,
-                **kwargs):
+                writer_keep=None, **kwargs):
         """Predicted noise [B, out_channels, H, W] (``unet.py:1499``; returns ``h`` as at ``:1821/:1836``).
         ``return_attention=True``: ``(eps, attn1, attn2, attn3)``, the per-character cross-attention maps fp32 [B, h, w, L] of
         the last input, the middle and the last output SpatialTransformer; ``"reference"``: the tuple the reference returns with
-        ``--attentionMaps 1`` (``UNetBase._run_attention``).  Inference only."""
+        ``--attentionMaps 1`` (``UNetBase._run_attention``).  Inference only.
+        ``writer_keep``: a bool / uint8 tensor [B] - sample b runs with its writer term where nonzero and without it elsewhere -
+        or ``False`` for no sample (the reference's ``args.imgConditioned == 1`` forward); eval and autograd."""
         self._check_common(x, timesteps, mix_rate)
         self._check_context(context)
         if self.num_classes is not None:
             if _arg(self.args, "imgConditioned", 0) == 1:
-                raise NotImplementedError("args.imgConditioned=1 drops the writer embedding (unet.py:1578-1579)")
+                raise NotImplementedError("args.imgConditioned=1 drops the writer embedding for every call (unet.py:1578-1579): "
+                                          "build the model without it and pass writer_keep=False to forward")
             assert y is not None and tuple(y.shape) == (x.shape[0],), "y must be [B] (unet.py:1555)"
-        return self._run(x, timesteps, context, y, mix_rate=mix_rate, return_attention=return_attention)
+        return self._run(x, timesteps, context, y, mix_rate=mix_rate, return_attention=return_attention, writer_keep=writer_keep)

@@ -15,7 +15,8 @@ class UNetModelPhosc(UNetBase):
     variant = "phosc"
 
     def forward(self, x, phoscLabels=None, timesteps=None, context=None, y=None, mix_rate=None, return_attention=False,
-                **kwargs):
+                writer_keep=None, **kwargs):
+        """``writer_keep`` as in ``UNetModel.forward``: the writer term per sample, or ``False`` for none."""
         self._check_common(x, timesteps, mix_rate)
         if return_attention is not False:
             # the reference keeps a map only where the attention has 10 keys; this model's has the PHOSC keys as well
@@ -29,4 +30,4 @@ class UNetModelPhosc(UNetBase):
             if phoscLabels is None:
                 raise ValueError("args.phosc/phos is set: phoscLabels [B, n] is required (unetPhosc.py:1120-1123)")
             phosc = phoscLabels.int()
-        return self._run(x, timesteps, context, y, phosc, mix_rate=mix_rate)
+        return self._run(x, timesteps, context, y, phosc, mix_rate=mix_rate, writer_keep=writer_keep)
