@@ -1,0 +1,138 @@
+"""The kernel forms of a launch plan, without anything that merely grows with the batch: ``signature(engine, P)`` is one entry per
+op of ``P.cond`` and ``P.step`` (the FiLM table ops, ``P.film`` and the closure of ``P.film_prepare``, are left out), ``diff`` says in
+one line how two signatures differ.  Two batch sizes whose plans launch the same kernel forms in the same order have equal
+signatures; tools/plan_thresholds.py scans the batch sizes at which they stop being equal.
+
+An entry is (section, function name, ``what``, form).  The form is a readable string:
+  wd_gemm       what wd_gemm_check resolves for the op's args - the launch family (wd_gemm_check_kernel), w_layout, tile, ksplit, nsrc -
+                and which options are on: tickets (in-launch combine), slab (the slab form of the 64 x 320 kernel), slab_rows (the
+                computed source rows), a32 (GroupNorm while staging), ln, gn, stat (GroupNorm statistics), f32 / planes (outputs)
+  wd_ff_fused   front / no front, how proj_out rides along (folded / proj_out / none), whether tok2 is written, stat
+  anything else the empty string: the function and its ``what`` are the form
+No address, row count, pitch or byte count enters."""
+import ctypes as C
+
+from worddiffusion_amd import _native as N
+
+SLAB_BIT = 0x10000  # wd_gemm_args.dbg of the RESOLVED args: the launch takes the slab form (include/wdiff_hip.h)
+
+
+def _struct(args):
+    """The structure an op passes by reference as its only argument."""
+    return getattr(args[0], "_obj", args[0])
+
+
+def gemm_form(lib, a) -> str:
+    r = N.WdGemmArgs()
+    if lib.wd_gemm_check(C.byref(a), C.byref(r)) != N.WD_OK:
+        return "REFUSED by wd_gemm_check"
+    kern = lib.wd_gemm_check_kernel(C.byref(a)).decode()
+    flags = [name for name, on in (("tickets", r.tickets), ("slab", r.dbg & SLAB_BIT), ("slab_rows", r.slab_rows), ("a32", r.a32),
+                                   ("ln", r.ln_gamma), ("gn", r.gn_gamma), ("stat", r.stat_part), ("f32", r.out_f32),
+                                   ("planes", r.out_hi)) if on]
+    return f"{kern} w_layout={r.w_layout} tile={r.tile} ksplit={r.ksplit} nsrc={r.nsrc} [{' '.join(flags)}]"
+
+
+def ff_form(a) -> str:
+    proj = "proj_out folded" if a.w32_hi else "proj_out" if a.w3_hi else "no proj_out"
+    flags = ["front" if a.x_in else "no front", proj] + (["tok2 written"] if a.tok2 else []) + (["stat"] if a.stat_part else [])
+    return ", ".join(flags)
+
+
+def signature(engine, P) -> tuple:
+    lib = engine.lib
+    sig = []
+    for section in ("cond", "step"):
+        for fn, args, what in getattr(P, section):
+            name = fn.__name__
+            if name == "wd_gemm":
+                form = gemm_form(lib, _struct(args))
+            elif name == "wd_ff_fused":
+                form = ff_form(_struct(args))
+            else:
+                form = ""
+            sig.append((section, name, what, form))
+    return tuple(sig)
+
+
+def _keyed(sig) -> dict:
+    """(section, what, occurrence) -> (function, form), in plan order: a ``what`` may repeat (one word_emb chain per token group)."""
+    out, seen = {}, {}
+    for section, name, what, form in sig:
+        n = seen[(section, what)] = seen.get((section, what), 0) + 1
+        out[(section, what, n)] = (name, form)
+    return out
+
+
+def _label(key) -> str:
+    section, what, n = key
+    return ("cond: " if section == "cond" else "") + what + (f" #{n}" if n > 1 else "")
+
+
+def _names(keys) -> str:
+    keys = list(keys)
+    return ", ".join(_label(k) for k in keys[:3]) + (f" (+{len(keys) - 3} more)" if len(keys) > 3 else "")
+
+
+def _show(entry) -> str:
+    name, form = entry
+    return f"{name} {form}" if form else name
+
+
+def diff(sig_a, sig_b) -> str:
+    """One line: the ops whose form changed grouped by (old form -> new form), then the ops only ``sig_a`` has (-) and the ops only
+    ``sig_b`` has (+), grouped by function.  A group names its first three ops and counts the rest.  '' for equal signatures."""
+    if tuple(sig_a) == tuple(sig_b):
+        return ""
+    ka, kb = _keyed(sig_a), _keyed(sig_b)
+    changed, gone, new = {}, {}, {}
+    for k, e in ka.items():
+        if k not in kb:
+            gone.setdefault(e[0], []).append(k)
+        elif kb[k] != e:
+            changed.setdefault((_show(e), _show(kb[k])), []).append(k)
+    for k, e in kb.items():
+        if k not in ka:
+            new.setdefault(e[0], []).append(k)
+    parts = [f"{_names(ks)}: {old} -> {to}" for (old, to), ks in changed.items()]
+    parts += [f"- {fn} x{len(ks)}: {_names(ks)}" for fn, ks in gone.items()]
+    parts += [f"+ {fn} x{len(ks)}: {_names(ks)}" for fn, ks in new.items()]
+    if not parts:
+        parts = ["same ops in another order"]
+    return "; ".join(parts)
+
+
+def read_scan(path) -> dict:
+    """A scan file of tools/plan_thresholds.py -> {B: summary of the difference to B - 1}, in file order ('#' lines are comments)."""
+    out = {}
+    with open(path) as f:
+        for line in f:
+            line = line.rstrip("\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            head, sep, text = line.partition(": ")
+            if not (head.startswith("B=") and head[2:].isdigit() and sep and text):
+                raise ValueError(f"{path}: not a threshold line: {line[:80]!r}")
+            if int(head[2:]) in out:
+                raise ValueError(f"{path}: B = {head[2:]} is listed twice")
+            out[int(head[2:])] = text
+    return out
+
+
+def release(engine):
+    """Drops every plan the engine holds and returns their buffers to the device (a B = 48 plan holds about 1 GB)."""
+    import gc
+
+    import torch
+    engine._plans.clear()
+    engine._cur_plan = None
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def signature_at(engine, B, phosc_len=0, h=8, w=32, ctx_len=10) -> tuple:
+    """The signature of the forward's plan at batch ``B`` (plans only: nothing but ``refresh_weights`` launches); the plan is released."""
+    engine.refresh_weights()
+    sig = signature(engine, engine.plan(B, h, w, ctx_len, phosc_len))
+    release(engine)
+    return sig
