@@ -496,3 +496,34 @@ def test_wd_gemm_check_statistics_need_the_vector_epilogue(field, off):
     assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_EINVAL
     a.stat_part = None  # the same launch without statistics is legal: it takes the scalar epilogue
     assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_OK
+
+
+def test_backward_segment_constructors():
+    """The two constructors of the training planner's segments give the fields its call sites used to write out by hand."""
+    from worddiffusion_amd.train_engine import Dx, conv3_seg, linear_seg
+    planes, wgrad, d, (k, hw, m) = object(), object(), object(), (320, 256, 512)
+    s = linear_seg(planes, k, hw, "B:x.w", wgrad, d, m)
+    assert s.planes is planes and s.wgrad is wgrad and s.wb == "B:x.w" and s.c == k and s.ntaps == 1
+    assert s.dx == [(d, k, 0, 0, k)] and s.dx[0].t is d and s.dx_rows == m and s.dx_hw == s.hw_src == hw
+    assert s.ftab is None and s.btab is None and s.wgrad_packed is None
+    ftab, btab = object(), object()
+    s = conv3_seg(planes, k, ftab, btab, hw // 4, "B:c.w", wgrad, Dx(d, k, 1, 0, k), m, hw)
+    assert s.ntaps == 9 and s.ftab is ftab and s.btab is btab and (s.hw_src, s.dx_rows, s.dx_hw) == (hw // 4, m, hw)
+    assert s.dx == [(d, k, 1, 0, k)] and s.wgrad_packed is None
+    with pytest.raises(AttributeError):
+        s.col_off = 0  # slotted: a key no one reads cannot be set
+
+
+def test_plan_train_refuses_before_any_device_work():
+    """What the training plan cannot do is refused from the arguments and the model alone (these models never saw a device)."""
+    eng = UNetModel(args=make_args(), **SMALL).train().train_engine
+    with pytest.raises(NotImplementedError):
+        eng.plan_train(2, 4, 8, 0)       # context=None
+    with pytest.raises(ValueError):
+        eng.plan_train(2, 4, 8, 10, 5)   # phoscLabels on the base model
+    with pytest.raises(ValueError):
+        eng.plan_train(2, 4, 8, 10, label_drop=1.0)
+    wide = UNetModel(args=make_args(), **dict(SMALL, out_channels=40)).train().train_engine
+    with pytest.raises(NotImplementedError, match="out_channels"):
+        wide.plan_train(2, 4, 8, 10)
+    assert not eng._tplans and not wide._tplans

@@ -19,9 +19,9 @@ them.  Forward + backward replay as one hipGraph.  Scope: the base ``unet.UNetMo
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
-
 import os
+from collections import namedtuple
+from typing import Callable, Dict, List, Optional
 
 import torch
 
@@ -72,6 +72,59 @@ def _rup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+# One destination of a data-gradient GEMM: t [rows, ld] (+)= d(out) . W[w_row_off : w_row_off + nrows]
+Dx = namedtuple("Dx", "t ld acc w_row_off nrows")
+# How a segment's weight gradient runs (_dw_form): dw - wd_dw, else transposed planes + wd_gemm; defer - in the grouped launch of
+# its shape (_flush_dw); hw_out / hw_src - the positions per sample wd_dw is given.  DwItem: one waiting for that launch.
+DwForm = namedtuple("DwForm", "dw defer hw_out hw_src")
+DwItem = namedtuple("DwItem", "what dpl d_ld planes wg out_ld ftab")
+# What _transformer keeps for its backward.  An attention: x the residual stream it read, n the planes of LayerNorm ``ln``, q the
+# query rows (q | k | v rows of the spatial self-attention), o the attention's output planes, ko the offset of its K | V columns.
+# A block: its attentions, then the feed-forward's input stream x3, norm3 planes, GEGLU pre-activation u, hidden planes ffh (ffi
+# wide) and output planes xpl.  The transformer: input x, output, GroupNorm planes gpl, M tokens (hw per sample), inner channels.
+_AttnRec = namedtuple("_AttnRec", "tag at x n q o ko self_attn ln")
+_BlockRec = namedtuple("_BlockRec", "tb p attns x3 n3 u ffh ffi xpl")
+_STRec = namedtuple("_STRec", "name mod x out gpl M hw inner blocks")
+
+
+class BwdSeg:
+    """One operand of out = sum_seg gather(planes_seg) . W_seg^T as ``_bwd_linear`` differentiates it: planes [2, rows, ld] of ``c``
+    channels read through ``ntaps`` taps of the forward table ``ftab`` (None: row for row) over ``hw_src`` source positions per
+    sample; ``wgrad`` [n, c * ntaps] in OIHW order or None (``wgrad_packed`` = (packed [n, ld_k], OIHW destination, c_in) for the
+    im2col input convolution); ``wb`` names the data-gradient weight of the ``dx`` destinations (Dx), whose rows are ``dx_rows``
+    output positions (``dx_hw`` per sample) through the inverse table ``btab``."""
+    __slots__ = ("planes", "c", "ntaps", "hw_src", "ftab", "btab", "wb", "wgrad", "wgrad_packed", "dx", "dx_rows", "dx_hw")
+
+    def __init__(self, planes, c, ntaps, hw_src, ftab=None, btab=None, wb=None, wgrad=None, wgrad_packed=None, dx=(), dx_rows=0,
+                 dx_hw=0):
+        self.planes, self.c, self.ntaps, self.hw_src, self.ftab, self.btab = planes, c, ntaps, hw_src, ftab, btab
+        self.wb, self.wgrad, self.wgrad_packed, self.dx, self.dx_rows, self.dx_hw = wb, wgrad, wgrad_packed, dx, dx_rows, dx_hw
+
+
+def linear_seg(planes, k: int, hw: int, wb: str, wgrad, d, m: int) -> BwdSeg:
+    """A linear layer (one tap) over ``m`` rows of ``k`` channels whose data gradient goes to ``d`` [m, k]."""
+    return BwdSeg(planes, k, 1, hw, wb=wb, wgrad=wgrad, dx=[Dx(d, k, 0, 0, k)], dx_rows=m, dx_hw=hw)
+
+
+def conv3_seg(planes, c: int, ftab, btab, hw_src: int, wb: str, wgrad, dx: Dx, dx_rows: int, dx_hw: int) -> BwdSeg:
+    """A 3x3 convolution read through the gather table ``ftab``; ``dx`` is written through ``btab``."""
+    return BwdSeg(planes, c, 9, hw_src, ftab=ftab, btab=btab, wb=wb, wgrad=wgrad, dx=[dx], dx_rows=dx_rows, dx_hw=dx_hw)
+
+
+class _Build:
+    """What one ``plan_train`` build collects on its way: made when the build starts, dropped when it ends or raises."""
+
+    def __init__(self):
+        self.tape: List[Callable] = []          # the backward of every block, in forward order
+        self.pw = set()                         # parameter-gradient buffers the backward list has written (_pacc)
+        self.deferred, self.deferred_outs = [], {}  # wd_colsum_finish_multi entries per round; rounds taken per buffer
+        self.gn_names: Dict[int, str] = {}      # id(GroupNorm) -> name of its packed weights
+        self.done_at: Dict[int, int] = {}       # gradient buffer data_ptr -> index of the last closure that writes it
+        self.closure = 0
+        self.dkv = self.dfilm = None            # d(K | V of every cross-attention), d(FiLM rows)
+        self.dw_pending: Dict[tuple, List[DwItem]] = {}  # weight gradients waiting for their group, by shape
+
+
 class TrainEngine(UNetEngine):
     def __init__(self, model, variant: str):
         super().__init__(model, variant)
@@ -88,7 +141,7 @@ class TrainEngine(UNetEngine):
         self.fuse_geglu_bwd = os.environ.get("WDIFF_FUSE_GEGLU_BWD", "1") != "0"  # GEGLU backward inside the d(out) preparation of ff1
         self.fuse_gn_bwd = os.environ.get("WDIFF_FUSE_GN_BWD", "1") != "0"  # GroupNorm backward in one pass (wd_gn_bwd_fused)
         self.dw_group_max = int(os.environ.get("WDIFF_DW_GROUP", "8"))  # single-tap layers of one shape per grouped launch (1: off)
-        self._dw_pending: Dict[tuple, list] = {}
+        self._bs: Optional[_Build] = None            # the plan build in progress
         self._tplans: Dict[tuple, TrainPlan] = {}
         self._grad: Dict[int, torch.Tensor] = {}     # id(param) -> gradient buffer (possibly a view into a group)
         self._params: Dict[int, torch.nn.Parameter] = {}
@@ -97,14 +150,11 @@ class TrainEngine(UNetEngine):
         self._arena = None
         self._arena_used = 0
         self.defer_bias_sums = os.environ.get("WDIFF_DEFER_BIAS", "1") != "0"
-        self._deferred, self._deferred_outs = [], {}
         # data-parallel overlap: the backward list is cut into NBUCKETS segments such that after segment j a PREFIX of the
         # gradient arena is final (the arena is carved in the order the backward list first writes the gradients, so a prefix
         # = the layers nearest the output) - TrainStep all-reduces that prefix while the next segment runs
         self.nbuckets = int(os.environ.get("WDIFF_GRAD_BUCKETS", "3"))
         self._carve_order: List[tuple] = []          # (data_ptr, arena offset, rounded numel) in carve order
-        self._done_at: Dict[int, int] = {}           # gradient buffer data_ptr -> index of the last closure that writes it
-        self._closure = 0
         self._cut_closures: Optional[List[int]] = None  # closures after which a bucket ends (fixed by the first plan)
         # training dropout through model(...) under autograd: the mask key, and the global row of the next forward's sample 0
         # (advanced by the batch after every training forward); TrainStep keys its own steps (training.py)
@@ -226,43 +276,38 @@ class TrainEngine(UNetEngine):
         """All parameter gradients as one flat fp32 tensor (views of it are the ``param.grad``s)."""
         return self._arena[: self._arena_used]
 
-    def _bias_finish(self, ops, what, colpart, nblk, n, b):
-        """Bias gradient = sum over the 64-row blocks of ``colpart``."""
-        self._param_colsum(ops, what, colpart.data_ptr(), n, nblk, n, b.data_ptr(), self._pacc(b), key=b.data_ptr())
-
-    def _param_colsum(self, ops, what, src_ptr, ld, rows, c, out_ptr, acc, key=None):
+    def _param_colsum(self, ops, what, src_ptr, ld, rows, c, out_ptr, acc):
         """out[0..c) (+)= column sums of src[rows, c] (row pitch ld) where ``out`` is a PARAMETER gradient, so nothing in the
         backward list reads it: deferred to the batched launches at the end of the list (``wd_colsum_finish_multi``), one
         launch per round.  A gradient with several writers (a norm shared by two attentions, the word encoder's projections
         run once per token group in the PHOSC variant) gets one entry per writer, in successive rounds.  ``src`` must stay
         intact until the end of the list (a plan-owned buffer, not a shared scratch)."""
-        key = out_ptr if key is None else key
-        rnd = self._deferred_outs.get(key, 0)
+        rnd = self._bs.deferred_outs.get(out_ptr, 0)
         if not self.defer_bias_sums or rows > 1024 or (acc and rnd == 0):
             # (acc and rnd == 0: an earlier, non-deferred op of this list already wrote the row - keep program order)
             self._colsum(ops, what, src_ptr, ld, rows, c, rows, out_ptr, c, acc)
             return
-        self._deferred_outs[key] = rnd + 1
-        while len(self._deferred) <= rnd:
-            self._deferred.append([])
-        self._deferred[rnd].append((src_ptr, out_ptr, rows, c, ld, 1 if (rnd or acc) else 0, 1.0, 0))
+        self._bs.deferred_outs[out_ptr] = rnd + 1
+        while len(self._bs.deferred) <= rnd:
+            self._bs.deferred.append([])
+        self._bs.deferred[rnd].append((src_ptr, out_ptr, rows, c, ld, 1 if (rnd or acc) else 0, 1.0, 0))
 
     def _flush_deferred(self, P):
-        for rnd, entries in enumerate(self._deferred):
+        for rnd, entries in enumerate(self._bs.deferred):
             if not entries:
                 continue
             table = torch.frombuffer((N.WdColsumEntry * len(entries))(*entries), dtype=torch.uint8).to(self.device)
             P.keep.append(table)
             P.bwd.append((self.lib.wd_colsum_finish_multi, (table.data_ptr(), len(entries), max(e[3] for e in entries)),
                           f"parameter-gradient column sums: deferred finishes (round {rnd})"))
-        self._deferred, self._deferred_outs = [], {}
+        self._bs.deferred, self._bs.deferred_outs = [], {}
 
     def _pacc(self, t: torch.Tensor) -> int:
         """1 if the backward list has already written this parameter-gradient buffer (shared norm2), else 0."""
         k = t.data_ptr()
-        acc = k in self._pw
-        self._pw.add(k)
-        self._done_at[k] = self._closure  # (a buffer with several writers is final after the last one)
+        acc = k in self._bs.pw
+        self._bs.pw.add(k)
+        self._bs.done_at[k] = self._bs.closure  # (a buffer with several writers is final after the last one)
         return int(acc)
 
     def _gacc(self, P, act: TAct):
@@ -271,6 +316,14 @@ class TrainEngine(UNetEngine):
         acc = act.gw
         act.gw = True
         return act.g, int(acc)
+
+    def _dresid(self, P, name, x: TAct, dO: torch.Tensor, M):
+        """The identity branch of out = f(x) + x: d(out) added to x's gradient, or copied where it is the first to write it."""
+        g, acc = self._gacc(P, x)
+        if acc:
+            P.bwd.append((self.lib.wd_add, (g.data_ptr(), dO.data_ptr(), g.numel()), name + ":dresid"))
+        else:
+            P.bwd.append((self.lib.wd_copy2d, (g.data_ptr(), 4 * x.c, dO.data_ptr(), 4 * x.c, 4 * x.c, M), name + ":dresid"))
 
     def _scratch(self, key: str, numel: int, dtype) -> torch.Tensor:
         cur = self._scr.get(key)
@@ -327,22 +380,22 @@ class TrainEngine(UNetEngine):
 
     def _flush_dw(self, P):
         """Emits the weight-gradient launches put off by _bwd_linear: layers of one shape as ONE grouped wd_dw_group launch."""
-        pend, self._dw_pending = self._dw_pending, {}
+        pend, self._bs.dw_pending = self._bs.dw_pending, {}
         for (M, n, c, hw, ntaps, hw_src, _), items in pend.items():
-            ftab = items[0]["ftab"]
+            ftab = items[0].ftab
             for lo in range(0, len(items), self.dw_group_max):
                 grp = items[lo:lo + self.dw_group_max]
                 if len(grp) == 1:
                     it = grp[0]
-                    self._dw(P.bwd, it["what"], it["dpl"], it["d_ld"], it["planes"], it["col_off"], c, ftab, ntaps, hw, hw_src, M, n,
-                             it["wg"], it["out_ld"], self._pacc(it["wg"]))
+                    self._dw(P.bwd, it.what, it.dpl, it.d_ld, it.planes, 0, c, ftab, ntaps, hw, hw_src, M, n, it.wg, it.out_ld,
+                             self._pacc(it.wg))
                     continue
                 arr = (N.WdDwItem * len(grp))()
                 for i, it in enumerate(grp):
-                    arr[i].d_hi, arr[i].d_lo = self._hilo(it["dpl"])
-                    arr[i].x_hi, arr[i].x_lo = self._hilo(it["planes"], 2 * it["col_off"])
-                    arr[i].grad, arr[i].grad_ld = it["wg"].data_ptr(), it["out_ld"]
-                    arr[i].d_ld, arr[i].x_ld, arr[i].accumulate = it["d_ld"], it["planes"].shape[2], self._pacc(it["wg"])
+                    arr[i].d_hi, arr[i].d_lo = self._hilo(it.dpl)
+                    arr[i].x_hi, arr[i].x_lo = self._hilo(it.planes)
+                    arr[i].grad, arr[i].grad_ld = it.wg.data_ptr(), it.out_ld
+                    arr[i].d_ld, arr[i].x_ld, arr[i].accumulate = it.d_ld, it.planes.shape[2], self._pacc(it.wg)
                 dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
                 a = N.WdDwArgs()
                 a.ws, a.ws_floats = self._ws.data_ptr(), self._ws.numel()
@@ -350,53 +403,57 @@ class TrainEngine(UNetEngine):
                 a.ntaps, a.hw_out, a.hw_src, a.m, a.n, a.c, a.npass, a.nslice = ntaps, hw, hw_src, M, n, c, self.npass, 0
                 P.keep += [arr, dev, a]
                 P.bwd.append((self.lib.wd_dw_group, (C.byref(a), C.cast(arr, C.c_void_p), dev.data_ptr(), len(grp)),
-                              "dW group: " + ", ".join(it["what"] for it in grp)))
+                              "dW group: " + ", ".join(it.what for it in grp)))
 
-    def _bwd_linear(self, P, what, dout: torch.Tensor, M, n, hw_out, segs, bias=(), film_off=None, npad=None, geglu=None):
-        """Backward of out[M, n] = sum_seg gather(planes_seg) . W_seg^T + bias (+ FiLM row vector).
-
-        seg keys: planes [2, rows, ld], c, ntaps, ftab (forward table or None), hw_src (forward source positions per
-        sample), wgrad (tensor [n, c*ntaps] in OIHW order, or None), wgrad_packed (tensor [n, ld_k] for the im2col input
-        conv), wb (name of the data-gradient weight) and dx: list of (tensor, ld, acc, w_row_off, nrows) written by the
-        data-gradient GEMM whose rows are dx_rows output positions (dx_hw per sample) through btab."""
-        ops = P.bwd
-        lib = self.lib
+    def _bwd_linear(self, P, what, dout: torch.Tensor, M, n, hw_out, segs: List[BwdSeg], bias=(), film_off=None, npad=None,
+                    geglu=None):
+        """Backward of out[M, n] = sum_seg gather(planes_seg) . W_seg^T + bias (+ FiLM row vector), appended to ``P.bwd``: the pass
+        over d(out), then per segment its data-gradient GEMMs and its weight gradient, then the bias / FiLM sums.
+        geglu = (u, dh, inner): d(output) is the GEGLU projection's and is NOT materialised - wd_dout_prep_geglu derives its planes
+        and column sums from the saved pre-activation and the gradient of the activation's output (dout is None then)."""
         npad = n if npad is None else npad
-        # geglu = (u, dh, inner): d(output) is the GEGLU projection's and is NOT materialised - wd_dout_prep_geglu derives its planes
-        # and column sums from the saved pre-activation and the gradient of the activation's output (dout is None then)
-        ldd = dout.shape[1] if dout is not None else n
-        mpad = _rup(M, 64)
-        need_dx = any(s.get("dx") for s in segs)
-        # weight gradients straight from the row-major planes (wd_dw: transposed LDS reads) wherever the shape allows; the rest goes
-        # through transposed copies of both operands and wd_gemm
+        forms = [self._dw_form(s, M, n, npad, hw_out) for s in segs]
+        dpl, doutT, colpart = self._stage_dout(P, what, dout, M, n, npad, hw_out, segs, forms, bias, film_off, geglu)
+        for si, (s, form) in enumerate(zip(segs, forms)):
+            self._emit_dx(P.bwd, f"{what}:dX{si}", s, dpl, npad, hw_out)
+            if s.wgrad is not None or s.wgrad_packed is not None:
+                self._emit_dw(P.bwd, what, si, s, form, dpl, doutT, M, n, npad)
+        self._emit_sums(P.bwd, what, dout, M, n, hw_out, colpart, bias, film_off)
+
+    def _dw_form(self, s: BwdSeg, M, n, npad, hw_out) -> DwForm:
+        """Weight gradients straight from the row-major planes (wd_dw: transposed LDS reads) wherever the shape allows; the rest goes
+        through transposed copies of both operands and wd_gemm.  Single-tap layers wait for the others of their shape (one grouped
+        launch at the end of the block's backward, _flush_dw); 3x3 layers join a group only where a launch of their own would run
+        short token slices - the 4 x 16 level: < 16 units of 64 tokens per slice -; the two convolutions of a ResBlock there share
+        a launch."""
+        lib, taps, ws = self.lib, s.ntaps, self._ws.numel()
         hw_dw = hw_out if (hw_out % 64 == 0 and M % hw_out == 0) else 64
-        for s in segs:
-            s["_dw"] = bool(self.use_dw and s.get("wgrad") is not None and npad % 8 == 0 and s["planes"].shape[2] % 8 == 0 and
-                            s.get("col_off", 0) % 8 == 0 and (s.get("ftab") is not None or s["ntaps"] == 1) and
-                            lib.wd_dw_supported(M, n, s["c"], s["ntaps"], hw_out if s.get("ftab") is not None else hw_dw) and
-                            lib.wd_dw_slices(M, n, s["c"], s["ntaps"]) * n * s["c"] * s["ntaps"] <= self._ws.numel())
-        need_dw = any((s.get("wgrad") is not None and not s["_dw"]) or s.get("wgrad_packed") is not None for s in segs)
-        need_dpl = need_dx or any(s["_dw"] for s in segs)
-        # single-tap layers wait for the others of their shape (one grouped launch at the end of the block's backward, _flush_dw):
-        # their d(out) planes then need a buffer of their own
-        # (3x3 layers join a group only where a launch of their own would run short token slices - the 4 x 16 level: < 16 units of 64
-        # tokens per slice -; the two convolutions of a ResBlock there share a launch)
-        for s in segs:
-            taps = s["ntaps"]
-            short = taps == 1 or (M // 64) // max(1, self.lib.wd_dw_slices(M, n, s["c"], taps)) < 16
-            s["_defer"] = bool(s["_dw"] and self.dw_group_max > 1 and short and (taps == 1) == (s.get("ftab") is None) and
-                               self.lib.wd_dw_group_slices(M, n, s["c"], taps, 2) * 2 * n * s["c"] * taps <= self._ws.numel())
+        hw, hw_src = (hw_out, s.hw_src) if s.ftab is not None else (hw_dw, hw_dw)
+        dw = bool(self.use_dw and s.wgrad is not None and npad % 8 == 0 and s.planes.shape[2] % 8 == 0 and
+                  (s.ftab is not None or taps == 1) and lib.wd_dw_supported(M, n, s.c, taps, hw) and
+                  lib.wd_dw_slices(M, n, s.c, taps) * n * s.c * taps <= ws)
+        short = taps == 1 or (M // 64) // max(1, lib.wd_dw_slices(M, n, s.c, taps)) < 16
+        defer = bool(dw and self.dw_group_max > 1 and short and (taps == 1) == (s.ftab is None) and
+                     lib.wd_dw_group_slices(M, n, s.c, taps, 2) * 2 * n * s.c * taps <= ws)
+        return DwForm(dw, defer, hw, hw_src)
+
+    def _stage_dout(self, P, what, dout, M, n, npad, hw_out, segs, forms, bias, film_off, geglu):
+        """One pass over d(output), appended to ``P.bwd``: row-major planes ``dpl`` (data gradient, wd_dw), transposed planes
+        ``doutT`` (wd_gemm weight gradient), per-64-row column sums ``colpart`` (bias / FiLM gradients, whenever the segments line
+        up).  Returns the three buffers, None for what no one reads."""
+        lib, mpad = self.lib, _rup(M, 64)
+        need_dw = any((s.wgrad is not None and not f.dw) or s.wgrad_packed is not None for s, f in zip(segs, forms))
+        need_dpl = any(s.dx for s in segs) or any(f.dw for f in forms)
         dpl = doutT = colpart = None
-        if need_dpl and any(s["_defer"] for s in segs):
+        if need_dpl and any(f.defer for f in forms):
+            # the planes of a deferred weight gradient are read at the end of the block's backward: a buffer of their own
             dpl = torch.empty(2, M, npad, dtype=torch.bfloat16, device=self.device)
             P.keep.append(dpl)
         elif need_dpl:
             dpl = self._scratch("dpl", 2 * self._max_dpl, torch.bfloat16)[: 2 * M * npad].view(2, M, npad)
         if need_dw:
             doutT = self._scratch("doutT", 2 * self._max_doutT, torch.bfloat16)[: 2 * n * mpad].view(2, n, mpad)
-        # bias / FiLM gradients come out of the same pass as per-64-row column sums whenever the segments line up
-        fuse_cs = (bool(bias) or film_off is not None) and (film_off is None or hw_out % 64 == 0)
-        if fuse_cs:
+        if (bool(bias) or film_off is not None) and (film_off is None or hw_out % 64 == 0):
             if bias and self.defer_bias_sums:
                 # the bias-gradient finish of this layer runs in the one batched launch at the end of the backward list, so
                 # its partial sums need a buffer of their own
@@ -405,76 +462,68 @@ class TrainEngine(UNetEngine):
             else:
                 colpart = self._scratch("colpart", self._max_colpart, torch.float32)
             assert (mpad // 64) * n <= colpart.numel(), what
+        outs = (*self._hilo(dpl), _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None, _ptr(colpart))
         if geglu is not None:
             u, dh, inner = geglu
-            assert dout is None and n == 2 * inner and npad == n and fuse_cs and film_off is None, what
-            ops.append((lib.wd_dout_prep_geglu, (u.data_ptr(), u.shape[1], dh.data_ptr(), dh.shape[1], M, inner, mpad, *self._hilo(dpl),
-                                                 _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None,
-                                                 _ptr(colpart)), what + ":prep(geglu bwd)"))
-        elif need_dpl or need_dw or fuse_cs:
-            # one pass over d(output): row-major planes (data gradient, wd_dw), transposed planes (wd_gemm weight gradient), column sums
-            ops.append((lib.wd_dout_prep, (dout.data_ptr(), ldd, M, n, npad, mpad, *self._hilo(dpl),
-                                           _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None,
-                                           _ptr(colpart)), what + ":prep(dout)"))
-        for si, s in enumerate(segs):
-            c, ntaps = s["c"], s["ntaps"]
-            planes = s["planes"]
-            for (dx, dx_ld, acc, roff, nrows) in s.get("dx") or ():
-                src = self._src(dpl, npad, ntaps, s.get("btab"), hw_out if s.get("btab") is not None else 0)
-                self._gemm(ops, f"{what}:dX{si}", [src], s["wb"], s["dx_rows"], s["dx_hw"],
-                           resid=dx.data_ptr() if acc else None, resid_ld=dx_ld if acc else 0, out_f32=dx, out_ld=dx_ld,
-                           n=nrows, w_row_off=roff)
-            wg, wgp = s.get("wgrad"), s.get("wgrad_packed")
-            if wg is None and wgp is None:
-                continue
-            k = ntaps * c
-            ftab = s.get("ftab")
-            if s["_defer"]:
-                key = (M, n, c, hw_out if ftab is not None else hw_dw, ntaps, s["hw_src"] if ftab is not None else hw_dw,
-                       ftab.data_ptr() if ftab is not None else 0)
-                self._dw_pending.setdefault(key, []).append(
-                    dict(what=f"{what}:dW{si}", dpl=dpl, d_ld=npad, planes=planes, col_off=s.get("col_off", 0), wg=wg, out_ld=k,
-                         ftab=ftab))
-                continue
-            if s["_dw"]:
-                self._dw(ops, f"{what}:dW{si}", dpl, npad, planes, s.get("col_off", 0), c, ftab, ntaps,
-                         hw_out if ftab is not None else hw_dw, s["hw_src"] if ftab is not None else hw_dw, M, n, wg, k,
-                         self._pacc(wg))
-                continue
-            xT = self._scratch("xT", 2 * self._max_xT, torch.bfloat16)[: 2 * k * mpad].view(2, k, mpad)
-            ops.append((lib.wd_transpose_planes,
-                        (planes[0].data_ptr() + 2 * s.get("col_off", 0), planes[1].data_ptr() + 2 * s.get("col_off", 0), 0,
-                         planes.shape[2], c, _ptr(ftab), ntaps, hw_out if ftab is not None else 0,
-                         s["hw_src"] if ftab is not None else 0, M, mpad, 1 if wgp is None else 0, xT[0].data_ptr(),
-                         xT[1].data_ptr()), f"{what}:T(x{si})"))
-            if wgp is not None:
-                packed, dst, cin = wgp
-                self._gemm_dw(ops, f"{what}:dW{si}", doutT, n, xT, k, mpad, packed, k, 0)
-                ops.append((lib.wd_permute_dw, (packed.data_ptr(), k, n, cin, 9, dst.data_ptr()), f"{what}:dW{si}:oihw"))
-                self._pacc(dst)
-            else:
-                self._gemm_dw(ops, f"{what}:dW{si}", doutT, n, xT, k, mpad, wg, k, self._pacc(wg))
-        if film_off is not None:
-            # per-sample column sums are the FiLM gradient; summing those over the batch is the bias gradient
-            B = M // hw_out
-            if fuse_cs:
-                ops.append((lib.wd_colsum_finish, (colpart.data_ptr(), hw_out // 64, n, B, self._dfilm.data_ptr() + 4 * film_off,
-                                                   self.film_total, 0, 1.0), what + ":dfilm"))
-            else:
-                self._colsum(ops, what + ":dfilm", dout.data_ptr(), ldd, M, n, hw_out,
-                             self._dfilm.data_ptr() + 4 * film_off, self.film_total, 0)
-            for b in bias:
-                if fuse_cs:
-                    self._bias_finish(ops, what + ":dbias", colpart, mpad // 64, n, b)
-                else:
-                    self._colsum(ops, what + ":dbias", self._dfilm.data_ptr() + 4 * film_off, self.film_total, B, n, B,
-                                 b.data_ptr(), n, self._pacc(b))
+            assert dout is None and n == 2 * inner and npad == n and colpart is not None and film_off is None, what
+            P.bwd.append((lib.wd_dout_prep_geglu, (u.data_ptr(), u.shape[1], dh.data_ptr(), dh.shape[1], M, inner, mpad, *outs),
+                          what + ":prep(geglu bwd)"))
+        elif need_dpl or need_dw or colpart is not None:
+            P.bwd.append((lib.wd_dout_prep, (dout.data_ptr(), dout.shape[1], M, n, npad, mpad, *outs), what + ":prep(dout)"))
+        return dpl, doutT, colpart
+
+    def _emit_dx(self, ops, what, s: BwdSeg, dpl, npad, hw_out):
+        """The data-gradient GEMMs of one segment: d(out) planes through the inverse table times the repacked weight."""
+        for dx in s.dx:
+            src = self._src(dpl, npad, s.ntaps, s.btab, hw_out if s.btab is not None else 0)
+            self._gemm(ops, what, [src], s.wb, s.dx_rows, s.dx_hw, resid=dx.t.data_ptr() if dx.acc else None,
+                       resid_ld=dx.ld if dx.acc else 0, out_f32=dx.t, out_ld=dx.ld, n=dx.nrows, w_row_off=dx.w_row_off)
+
+    def _emit_dw(self, ops, what, si, s: BwdSeg, form: DwForm, dpl, doutT, M, n, npad):
+        """The weight gradient of one segment in the form ``_dw_form`` chose: queued for its group, wd_dw, or transposed planes +
+        wd_gemm (+ the OIHW permutation of the im2col input convolution)."""
+        c, ntaps, ftab, planes, wg = s.c, s.ntaps, s.ftab, s.planes, s.wgrad
+        k, mpad = ntaps * c, _rup(M, 64)
+        if form.defer:
+            key = (M, n, c, form.hw_out, ntaps, form.hw_src, ftab.data_ptr() if ftab is not None else 0)
+            self._bs.dw_pending.setdefault(key, []).append(DwItem(f"{what}:dW{si}", dpl, npad, planes, wg, k, ftab))
+            return
+        if form.dw:
+            self._dw(ops, f"{what}:dW{si}", dpl, npad, planes, 0, c, ftab, ntaps, form.hw_out, form.hw_src, M, n, wg, k,
+                     self._pacc(wg))
+            return
+        xT = self._scratch("xT", 2 * self._max_xT, torch.bfloat16)[: 2 * k * mpad].view(2, k, mpad)
+        hw_out = form.hw_out if ftab is not None else 0
+        ops.append((self.lib.wd_transpose_planes,
+                    (planes[0].data_ptr(), planes[1].data_ptr(), 0, planes.shape[2], c, _ptr(ftab), ntaps, hw_out,
+                     s.hw_src if ftab is not None else 0, M, mpad, 1 if s.wgrad_packed is None else 0, xT[0].data_ptr(),
+                     xT[1].data_ptr()), f"{what}:T(x{si})"))
+        if s.wgrad_packed is not None:
+            packed, dst, cin = s.wgrad_packed
+            self._gemm_dw(ops, f"{what}:dW{si}", doutT, n, xT, k, mpad, packed, k, 0)
+            ops.append((self.lib.wd_permute_dw, (packed.data_ptr(), k, n, cin, 9, dst.data_ptr()), f"{what}:dW{si}:oihw"))
+            self._pacc(dst)
         else:
-            for b in bias:
-                if fuse_cs:
-                    self._bias_finish(ops, what + ":dbias", colpart, mpad // 64, n, b)
-                else:
-                    self._colsum(ops, what + ":dbias", dout.data_ptr(), ldd, M, n, M, b.data_ptr(), n, self._pacc(b))
+            self._gemm_dw(ops, f"{what}:dW{si}", doutT, n, xT, k, mpad, wg, k, self._pacc(wg))
+
+    def _emit_sums(self, ops, what, dout, M, n, hw_out, colpart, bias, film_off):
+        """FiLM gradient (per-sample column sums of d(out), read by the embedding path's backward) and bias gradients (their sum
+        over the batch): finishes of ``colpart`` where the pass over d(out) left it, column sums otherwise."""
+        src, ld, rows = (dout.data_ptr(), dout.shape[1], M) if dout is not None else (None, n, M)
+        if film_off is not None:
+            B = M // hw_out
+            dfilm = self._bs.dfilm.data_ptr() + 4 * film_off
+            if colpart is not None:
+                ops.append((self.lib.wd_colsum_finish, (colpart.data_ptr(), hw_out // 64, n, B, dfilm, self.film_total, 0, 1.0),
+                            what + ":dfilm"))
+            else:
+                self._colsum(ops, what + ":dfilm", src, ld, M, n, hw_out, dfilm, self.film_total, 0)
+            src, ld, rows = dfilm, self.film_total, B
+        for b in bias:
+            if colpart is not None:  # the sum over its 64-row blocks
+                self._param_colsum(ops, what + ":dbias", colpart.data_ptr(), n, _rup(M, 64) // 64, n, b.data_ptr(), self._pacc(b))
+            else:
+                self._colsum(ops, what + ":dbias", src, ld, rows, n, rows, b.data_ptr(), n, self._pacc(b))
 
     def _dropout_args(self, P, mod: ResBlockParams, p: float) -> DO.WdDropout:
         """The wd_dropout of ResBlock ``mod``: layer tag, threshold and scale fixed here, the seed set before every launch or
@@ -497,7 +546,7 @@ class TrainEngine(UNetEngine):
         ctot = sum(s.c for s in srcs)
         cpg = ctot // 32
         gam, bet = gn.weight, gn.bias
-        gw, gb = self._w[self._gn_names[id(gn)] + ".g"], self._w[self._gn_names[id(gn)] + ".b"]
+        gw, gb = self._w[self._bs.gn_names[id(gn)] + ".g"], self._w[self._bs.gn_names[id(gn)] + ".b"]
         pair = self._ppair(bet, gam)  # [d beta | d gamma], the order of the planar sums
         dbet, dgam = pair[0], pair[1]
         # one pass (the workgroup keeps its tile of dy / xhat in LDS) where the shape allows, else statistics pass + apply pass
@@ -612,8 +661,8 @@ class TrainEngine(UNetEngine):
                             bias=self._w[name + ".c2.b"], resid=srcs[0].t.data_ptr(), resid_ld=cout, out_f32=outt,
                             out_ld=cout, want_stats=True)
         out = TAct(outt, cout, h, w, g2._stats)
-        self._gn_names[id(mod.in_layers[0])] = name + ".gn1"
-        self._gn_names[id(mod.out_layers[0])] = name + ".gn2"
+        self._bs.gn_names[id(mod.in_layers[0])] = name + ".gn1"
+        self._bs.gn_names[id(mod.out_layers[0])] = name + ".gn2"
 
         def bwd():
             bops = P.bwd
@@ -621,33 +670,26 @@ class TrainEngine(UNetEngine):
             dO = out.g
             btab = self._btable(h, w, "same")
             da2 = self._f32(P, M, cout)
-            segs = [dict(planes=a2, c=cout, ntaps=9, ftab=tab, btab=btab, hw_src=hw, wb="B:" + name + ".c2.w",
-                         wgrad=self._pgrad(mod.out_layers[3].weight).view(cout, -1), dx=[(da2, cout, 0, 0, cout)],
-                         dx_rows=M, dx_hw=hw)]
+            segs = [conv3_seg(a2, cout, tab, btab, hw, "B:" + name + ".c2.w", self._pgrad(mod.out_layers[3].weight).view(cout, -1),
+                              Dx(da2, cout, 0, 0, cout), M, hw)]
             biases = [self._pgrad(mod.out_layers[3].bias)]
             if need_raw:
                 dxs, coff = [], 0
                 for s in srcs:
                     g, acc = self._gacc(P, s)
-                    dxs.append((g, s.c, acc, coff, s.c))
+                    dxs.append(Dx(g, s.c, acc, coff, s.c))
                     coff += s.c
-                segs.append(dict(planes=raw, c=cin, ntaps=1, hw_src=hw, wb="B:" + name + ".skip.w",
-                                 wgrad=self._pgrad(mod.skip_connection.weight).view(cout, cin), dx=dxs, dx_rows=M, dx_hw=hw))
+                segs.append(BwdSeg(raw, cin, 1, hw, wb="B:" + name + ".skip.w",
+                                   wgrad=self._pgrad(mod.skip_connection.weight).view(cout, cin), dx=dxs, dx_rows=M, dx_hw=hw))
                 biases.append(self._pgrad(mod.skip_connection.bias))
             else:
-                g, acc = self._gacc(P, srcs[0])
-                if acc:
-                    bops.append((self.lib.wd_add, (g.data_ptr(), dO.data_ptr(), g.numel()), name + ":dresid"))
-                else:
-                    bops.append((self.lib.wd_copy2d, (g.data_ptr(), 4 * cout, dO.data_ptr(), 4 * cout, 4 * cout, M),
-                                 name + ":dresid"))
+                self._dresid(P, name, srcs[0], dO, M)
             self._bwd_linear(P, name + ".conv2", dO, M, cout, hw, segs, bias=biases)
             self._gn_bwd(P, name + ".gn2", [h1], mod.out_layers[0], 1e-5, True, da2, dropout=drop)
             da1 = self._f32(P, M, cin)
             self._bwd_linear(P, name + ".conv1", h1.g, M, cout, hw,
-                             [dict(planes=a1, c=cin, ntaps=9, ftab=tab, btab=btab, hw_src=hw, wb="B:" + name + ".c1.w",
-                                   wgrad=self._pgrad(mod.in_layers[2].weight).view(cout, -1), dx=[(da1, cin, 0, 0, cin)],
-                                   dx_rows=M, dx_hw=hw)],
+                             [conv3_seg(a1, cin, tab, btab, hw, "B:" + name + ".c1.w",
+                                        self._pgrad(mod.in_layers[2].weight).view(cout, -1), Dx(da1, cin, 0, 0, cin), M, hw)],
                              bias=[self._pgrad(mod.in_layers[2].bias)], film_off=self.film_off[name])
             self._gn_bwd(P, name + ".gn1", srcs, mod.in_layers[0], 1e-5, True, da1)
             if parts is not None:
@@ -661,7 +703,7 @@ class TrainEngine(UNetEngine):
                         bops.append((self.lib.wd_add, (g.data_ptr(), dst.data_ptr(), g.numel()), name + ":d(concat)+"))
                     coff += s.c
 
-        self._tape.append(bwd)
+        self._bs.tape.append(bwd)
         return out
 
     def _resample(self, P, name, mod, x: TAct, mode: str) -> TAct:
@@ -684,14 +726,14 @@ class TrainEngine(UNetEngine):
             g, acc = self._gacc(P, x)
             if mode == "down":
                 btab = self._btable(x.h, x.w, "down")
-                dx, dx_rows, dx_hw = [(g, x.c, acc, 0, x.c)], M_in, hw_in
+                dx, dx_rows, dx_hw = Dx(g, x.c, acc, 0, x.c), M_in, hw_in
             else:  # nearest x2: data gradient at the upsampled resolution, then 2x2 sums
                 btab = self._btable(ho, wo, "same")
                 du = self._f32(P, M_out, x.c)
-                dx, dx_rows, dx_hw = [(du, x.c, 0, 0, x.c)], M_out, hw_out
+                dx, dx_rows, dx_hw = Dx(du, x.c, 0, 0, x.c), M_out, hw_out
             self._bwd_linear(P, name + ".conv", out.g, M_out, mod.cout, hw_out,
-                             [dict(planes=pl, c=x.c, ntaps=9, ftab=tab, btab=btab, hw_src=hw_in, wb="B:" + name + ".w",
-                                   wgrad=self._pgrad(conv.weight).view(mod.cout, -1), dx=dx, dx_rows=dx_rows, dx_hw=dx_hw)],
+                             [conv3_seg(pl, x.c, tab, btab, hw_in, "B:" + name + ".w", self._pgrad(conv.weight).view(mod.cout, -1),
+                                        dx, dx_rows, dx_hw)],
                              bias=[self._pgrad(conv.bias)])
             if mode == "up":
                 if acc:
@@ -701,7 +743,7 @@ class TrainEngine(UNetEngine):
                 else:
                     bops.append((self.lib.wd_pool2x2_sum, (du.data_ptr(), B, x.h, x.w, x.c, g.data_ptr()), name + ":pool"))
 
-        self._tape.append(bwd)
+        self._bs.tape.append(bwd)
         return out
 
     def _transformer(self, P, name, mod: SpatialTransformerParams, x: TAct) -> TAct:
@@ -715,15 +757,15 @@ class TrainEngine(UNetEngine):
         L = self._ctx_len
         scale = d ** -0.5
         gpl, _ = self._gn(P, ops, name + ".gn", [x], name + ".gn", 1e-6, False)
-        self._gn_names[id(mod.norm)] = name + ".gn"
+        self._bs.gn_names[id(mod.norm)] = name + ".gn"
         tok = self._f32(P, M, inner)
         self._gemm(ops, name + ".proj_in", [self._src(gpl, c)], name + ".pi.w", M, hw, bias=self._w[name + ".pi.b"],
                    out_f32=tok, out_ld=inner)
-        saved = []
+        blocks = []
         cur = tok
         for di, tb in enumerate(mod.transformer_blocks):
             p = f"{name}.tb{di}"
-            rec = dict(tb=tb, p=p, tok=cur)
+            attns = []
             # base model: both attentions are cross-attentions reading norm2 (unet.py:337-345); PHOSC model: attn1 is the
             # spatial self-attention behind norm1 (unetPhosc.py:241-246)
             for tag, at in (("a1", tb.attn1), ("a2", tb.attn2)):
@@ -737,14 +779,14 @@ class TrainEngine(UNetEngine):
                                out_ld=3 * inner)
                     self._attention(ops, p + ".a1", qkv.data_ptr(), 3 * inner, qkv.data_ptr() + 4 * inner, 3 * inner,
                                     qkv.data_ptr() + 8 * inner, 3 * inner, heads, hw, hw, d, scale, o)
-                    rec[tag] = dict(at=at, x=cur, n=n_pl, qkv=qkv, o=o, self_attn=True, ln=ln)
+                    attns.append(_AttnRec(tag, at, cur, n_pl, qkv, o, 0, True, ln))
                 else:
                     q = self._f32(P, M, inner)
                     self._gemm(ops, f"{p}.{tag}.q", [self._src(n_pl, inner)], f"{p}.{tag}.q.w", M, hw, out_f32=q, out_ld=inner)
                     ko = self.kv_off[f"{p}.{tag}"]
                     self._attention(ops, f"{p}.{tag}", q.data_ptr(), inner, self._kv.data_ptr() + 4 * ko, self.kv_total,
                                     self._kv.data_ptr() + 4 * (ko + inner), self.kv_total, heads, hw, L, d, scale, o)
-                    rec[tag] = dict(at=at, x=cur, n=n_pl, q=q, o=o, ko=ko, self_attn=False, ln=ln)
+                    attns.append(_AttnRec(tag, at, cur, n_pl, q, o, ko, False, ln))
                 nxt = self._f32(P, M, inner)
                 self._gemm(ops, f"{p}.{tag}.out", [self._src(o, inner)], f"{p}.{tag}.o.w", M, hw,
                            bias=self._w[f"{p}.{tag}.o.b"], resid=cur.data_ptr(), resid_ld=inner, out_f32=nxt, out_ld=inner)
@@ -760,91 +802,92 @@ class TrainEngine(UNetEngine):
             xpl = self._planes(P, M, inner)
             self._gemm(ops, p + ".ff2", [self._src(ffh, ffi)], p + ".ff2.w", M, hw, bias=self._w[p + ".ff2.b"],
                        resid=cur.data_ptr(), resid_ld=inner, out_f32=nxt, out_ld=inner, out_pl=xpl)
-            rec.update(x3=cur, n3=n3, u=u, ffh=ffh, ffi=ffi, out=nxt, xpl=xpl)
-            saved.append(rec)
+            blocks.append(_BlockRec(tb, p, attns, cur, n3, u, ffh, ffi, xpl))
             cur = nxt
         outt = self._f32(P, M, c)
-        gg = self._gemm(ops, name + ".proj_out", [self._src(saved[-1]["xpl"], inner)], name + ".po.w", M, hw,
+        gg = self._gemm(ops, name + ".proj_out", [self._src(blocks[-1].xpl, inner)], name + ".po.w", M, hw,
                         bias=self._w[name + ".po.b"], resid=x.t.data_ptr(), resid_ld=c, out_f32=outt, out_ld=c,
                         want_stats=True)
         out = TAct(outt, c, h, w, gg._stats)
 
-        def bwd():
-            bops = P.bwd
-            assert out.gw, name
-            dO = out.g
-            g, acc = self._gacc(P, x)
-            if acc:
-                bops.append((lib.wd_add, (g.data_ptr(), dO.data_ptr(), g.numel()), name + ":dresid"))
-            else:
-                bops.append((lib.wd_copy2d, (g.data_ptr(), 4 * c, dO.data_ptr(), 4 * c, 4 * c, M), name + ":dresid"))
-            dcur = self._f32(P, M, inner)  # gradient of the running token stream (residual adds share it)
-            self._bwd_linear(P, name + ".proj_out", dO, M, c, hw,
-                             [dict(planes=saved[-1]["xpl"], c=inner, ntaps=1, hw_src=hw, wb="B:" + name + ".po.w",
-                                   wgrad=self._pgrad(mod.proj_out.weight).view(c, inner), dx=[(dcur, inner, 0, 0, inner)],
-                                   dx_rows=M, dx_hw=hw)], bias=[self._pgrad(mod.proj_out.bias)])
-            for rec in reversed(saved):
-                tb, p, ffi = rec["tb"], rec["p"], rec["ffi"]
-                # ---- feed-forward: out = ff2(geglu(ff1(LN3(x3)))) + x3
-                dffh = self._f32(P, M, ffi)
-                self._bwd_linear(P, p + ".ff2", dcur, M, inner, hw,
-                                 [dict(planes=rec["ffh"], c=ffi, ntaps=1, hw_src=hw, wb="B:" + p + ".ff2.w",
-                                       wgrad=self._pgrad(tb.ff.net[2].weight), dx=[(dffh, ffi, 0, 0, ffi)], dx_rows=M,
-                                       dx_hw=hw)], bias=[self._pgrad(tb.ff.net[2].bias)])
-                dn3 = self._f32(P, M, inner)
-                ff1_seg = [dict(planes=rec["n3"], c=inner, ntaps=1, hw_src=hw, wb="B:" + p + ".ff1.w",
-                                wgrad=self._pgrad(tb.ff.net[0].proj.weight), dx=[(dn3, inner, 0, 0, inner)], dx_rows=M, dx_hw=hw)]
-                if self.fuse_geglu_bwd and ffi % 64 == 0:
-                    # d(GEGLU pre-activation) goes straight to operand planes + bias column sums (never written as fp32)
-                    self._bwd_linear(P, p + ".ff1", None, M, 2 * ffi, hw, ff1_seg, bias=[self._pgrad(tb.ff.net[0].proj.bias)],
-                                     geglu=(rec["u"], dffh, ffi))
-                else:
-                    du = self._f32(P, M, 2 * ffi)
-                    bops.append((lib.wd_geglu_bwd, (rec["u"].data_ptr(), 2 * ffi, dffh.data_ptr(), ffi, M, ffi, du.data_ptr(), 2 * ffi),
-                                 p + ".geglu:bwd"))
-                    self._bwd_linear(P, p + ".ff1", du, M, 2 * ffi, hw, ff1_seg, bias=[self._pgrad(tb.ff.net[0].proj.bias)])
-                self._ln_bwd(P, p + ".norm3:bwd", rec["x3"], M, inner, tb.norm3, p + ".norm3", dn3, dcur, 1)
-                # ---- the two cross-attentions, last first
-                for tag in ("a2", "a1"):
-                    r = rec[tag]
-                    at = r["at"]
-                    do = self._f32(P, M, inner)
-                    self._bwd_linear(P, f"{p}.{tag}.out", dcur, M, inner, hw,
-                                     [dict(planes=r["o"], c=inner, ntaps=1, hw_src=hw, wb=f"B:{p}.{tag}.o.w",
-                                           wgrad=self._pgrad(at.to_out[0].weight), dx=[(do, inner, 0, 0, inner)], dx_rows=M,
-                                           dx_hw=hw)], bias=[self._pgrad(at.to_out[0].bias)])
-                    dn = self._f32(P, M, inner)
-                    if r["self_attn"]:
-                        qkv = r["qkv"]
-                        dqkv = self._f32(P, M, 3 * inner)
-                        self._attn_bwd(P, f"{p}.a1:bwd", qkv.data_ptr(), 3 * inner, qkv.data_ptr() + 4 * inner, 3 * inner,
-                                       qkv.data_ptr() + 8 * inner, 3 * inner, do, heads, hw, hw, d, scale, dqkv.data_ptr(),
-                                       3 * inner, dqkv.data_ptr() + 4 * inner, 3 * inner)
-                        self._bwd_linear(P, p + ".a1.qkv", dqkv, M, 3 * inner, hw,
-                                         [dict(planes=r["n"], c=inner, ntaps=1, hw_src=hw, wb=f"B:{p}.a1.qkv.w",
-                                               wgrad=self._pgroup([at.to_q.weight, at.to_k.weight, at.to_v.weight]),
-                                               dx=[(dn, inner, 0, 0, inner)], dx_rows=M, dx_hw=hw)])
-                    else:
-                        dq = self._f32(P, M, inner)
-                        ko = r["ko"]
-                        self._attn_bwd(P, f"{p}.{tag}:bwd", r["q"].data_ptr(), inner, self._kv.data_ptr() + 4 * ko,
-                                       self.kv_total, self._kv.data_ptr() + 4 * (ko + inner), self.kv_total, do, heads, hw, L, d,
-                                       scale, dq.data_ptr(), inner, self._dkv.data_ptr() + 4 * ko, self.kv_total)
-                        self._bwd_linear(P, f"{p}.{tag}.q", dq, M, inner, hw,
-                                         [dict(planes=r["n"], c=inner, ntaps=1, hw_src=hw, wb=f"B:{p}.{tag}.q.w",
-                                               wgrad=self._pgrad(at.to_q.weight), dx=[(dn, inner, 0, 0, inner)], dx_rows=M,
-                                               dx_hw=hw)])
-                    self._ln_bwd(P, f"{p}.{r['ln']}({tag}):bwd", r["x"], M, inner, getattr(tb, r["ln"]), f"{p}.{r['ln']}", dn,
-                                 dcur, 1)
-            dg = self._f32(P, M, c)
-            self._bwd_linear(P, name + ".proj_in", dcur, M, inner, hw,
-                             [dict(planes=gpl, c=c, ntaps=1, hw_src=hw, wb="B:" + name + ".pi.w",
-                                   wgrad=self._pgrad(mod.proj_in.weight).view(inner, c), dx=[(dg, c, 0, 0, c)], dx_rows=M,
-                                   dx_hw=hw)], bias=[self._pgrad(mod.proj_in.bias)])
-            self._gn_bwd(P, name + ".gn", [x], mod.norm, 1e-6, False, dg)
+        st = _STRec(name, mod, x, out, gpl, M, hw, inner, blocks)
 
-        self._tape.append(bwd)
+        def bwd():
+            dcur = self._st_out_bwd(P, st)
+            for blk in reversed(blocks):
+                self._ff_bwd(P, st, blk, dcur)
+                for a in reversed(blk.attns):
+                    self._attn_layer_bwd(P, st, blk, a, dcur)
+            self._st_in_bwd(P, st, dcur)
+
+        self._bs.tape.append(bwd)
         return out
+
+    def _st_out_bwd(self, P, st: _STRec) -> torch.Tensor:
+        """out = proj_out(tokens) + x: d(out) into x's gradient, and through proj_out into the gradient of the running token
+        stream (the residual adds of the blocks share it), which it returns."""
+        name, mod, c, M = st.name, st.mod, st.x.c, st.M
+        assert st.out.gw, name
+        dO = st.out.g
+        self._dresid(P, name, st.x, dO, M)
+        dcur = self._f32(P, M, st.inner)
+        self._bwd_linear(P, name + ".proj_out", dO, M, c, st.hw,
+                         [linear_seg(st.blocks[-1].xpl, st.inner, st.hw, "B:" + name + ".po.w",
+                                     self._pgrad(mod.proj_out.weight).view(c, st.inner), dcur, M)],
+                         bias=[self._pgrad(mod.proj_out.bias)])
+        return dcur
+
+    def _ff_bwd(self, P, st: _STRec, blk: _BlockRec, dcur):
+        """out = ff2(geglu(ff1(LN3(x3)))) + x3: dcur is d(out) and gets LN3's data gradient added."""
+        tb, p, ffi, M, hw, inner = blk.tb, blk.p, blk.ffi, st.M, st.hw, st.inner
+        dffh = self._f32(P, M, ffi)
+        self._bwd_linear(P, p + ".ff2", dcur, M, inner, hw,
+                         [linear_seg(blk.ffh, ffi, hw, "B:" + p + ".ff2.w", self._pgrad(tb.ff.net[2].weight), dffh, M)],
+                         bias=[self._pgrad(tb.ff.net[2].bias)])
+        dn3 = self._f32(P, M, inner)
+        ff1_seg = [linear_seg(blk.n3, inner, hw, "B:" + p + ".ff1.w", self._pgrad(tb.ff.net[0].proj.weight), dn3, M)]
+        # fused: d(GEGLU pre-activation) goes straight to operand planes + bias column sums (never written as fp32)
+        fused, du = self.fuse_geglu_bwd and ffi % 64 == 0, None
+        if not fused:
+            du = self._f32(P, M, 2 * ffi)
+            P.bwd.append((self.lib.wd_geglu_bwd, (blk.u.data_ptr(), 2 * ffi, dffh.data_ptr(), ffi, M, ffi, du.data_ptr(), 2 * ffi),
+                          p + ".geglu:bwd"))
+        self._bwd_linear(P, p + ".ff1", du, M, 2 * ffi, hw, ff1_seg, bias=[self._pgrad(tb.ff.net[0].proj.bias)],
+                         geglu=(blk.u, dffh, ffi) if fused else None)
+        self._ln_bwd(P, p + ".norm3:bwd", blk.x3, M, inner, tb.norm3, p + ".norm3", dn3, dcur, 1)
+
+    def _attn_layer_bwd(self, P, st: _STRec, blk: _BlockRec, a: _AttnRec, dcur):
+        """out = to_out(attention(q(LN(x)), K, V)) + x, self or cross: dcur is d(out) and gets the LayerNorm's data gradient added;
+        a cross-attention leaves d(K | V) in its columns of the build's ``dkv``."""
+        p, tag, at, M, hw, inner = blk.p, a.tag, a.at, st.M, st.hw, st.inner
+        heads, d = st.mod.heads, st.mod.d_head
+        do = self._f32(P, M, inner)
+        self._bwd_linear(P, f"{p}.{tag}.out", dcur, M, inner, hw,
+                         [linear_seg(a.o, inner, hw, f"B:{p}.{tag}.o.w", self._pgrad(at.to_out[0].weight), do, M)],
+                         bias=[self._pgrad(at.to_out[0].bias)])
+        dn = self._f32(P, M, inner)
+        if a.self_attn:  # q holds the q | k | v rows, dq their gradient
+            proj, dq, q = "a1.qkv", self._f32(P, M, 3 * inner), a.q.data_ptr()
+            self._attn_bwd(P, f"{p}.a1:bwd", q, 3 * inner, q + 4 * inner, 3 * inner, q + 8 * inner, 3 * inner, do, heads, hw, hw, d,
+                           d ** -0.5, dq.data_ptr(), 3 * inner, dq.data_ptr() + 4 * inner, 3 * inner)
+            wg = self._pgroup([at.to_q.weight, at.to_k.weight, at.to_v.weight])
+        else:
+            proj, dq = tag + ".q", self._f32(P, M, inner)
+            kv, dkv = self._kv.data_ptr() + 4 * a.ko, self._bs.dkv.data_ptr() + 4 * a.ko
+            self._attn_bwd(P, f"{p}.{tag}:bwd", a.q.data_ptr(), inner, kv, self.kv_total, kv + 4 * inner, self.kv_total, do, heads,
+                           hw, self._ctx_len, d, d ** -0.5, dq.data_ptr(), inner, dkv, self.kv_total)
+            wg = self._pgrad(at.to_q.weight)
+        self._bwd_linear(P, f"{p}.{proj}", dq, M, dq.shape[1], hw, [linear_seg(a.n, inner, hw, f"B:{p}.{proj}.w", wg, dn, M)])
+        self._ln_bwd(P, f"{p}.{a.ln}({tag}):bwd", a.x, M, inner, getattr(blk.tb, a.ln), f"{p}.{a.ln}", dn, dcur, 1)
+
+    def _st_in_bwd(self, P, st: _STRec, dcur):
+        """tokens = proj_in(GroupNorm(x)): dcur through proj_in and the norm into x's gradient."""
+        name, mod, c, M = st.name, st.mod, st.x.c, st.M
+        dg = self._f32(P, M, c)
+        self._bwd_linear(P, name + ".proj_in", dcur, M, st.inner, st.hw,
+                         [linear_seg(st.gpl, c, st.hw, "B:" + name + ".pi.w", self._pgrad(mod.proj_in.weight).view(st.inner, c),
+                                     dg, M)], bias=[self._pgrad(mod.proj_in.bias)])
+        self._gn_bwd(P, name + ".gn", [st.x], mod.norm, 1e-6, False, dg)
 
     # ------------------------------------------------------------------------------------------ plan
     def _size_scratch(self, B, H, W, L, ctx_len=0, phosc_len=0):
@@ -884,7 +927,49 @@ class TrainEngine(UNetEngine):
         ``P.keep_in`` (uint8 [B], ``load_keep``); a float p in (0, 1) - dropped with probability p, drawn on the device per
         global sample row (``wd_label_rows_keep``).  Either way the rows the kernel writes are the residual of the time_embed.2
         GEMM and label_emb's backward reads the ids it writes (-1 for a dropped sample: no gradient row)."""
-        # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1): refused before any device work; a plan is built for its p's
+        key, label_drop = self._train_key(B, H, W, ctx_len, phosc_len, label_drop)
+        P = self._cached_plan(self._tplans, key)
+        if P is not None:
+            return P
+        if self._tplans:
+            # scratch buffers and the gradient-accumulate flags are sized / decided per plan: one live shape at a time
+            self._tplans.clear()
+            self._scr = {k: v for k, v in self._scr.items() if isinstance(k, tuple)}
+        m = self.model
+        P = self._begin_plan(TrainPlan(), B)
+        self._bs = _Build()
+        try:
+            P.row_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+            L = ctx_len + phosc_len
+            self._size_scratch(B, H, W, L, ctx_len, phosc_len)
+            self._inputs(P, H, W, ctx_len, phosc_len)
+            # the conditioning path is differentiated, so it is part of every step
+            groups = self._conditioning(P, P.step, ctx_len, phosc_len)
+            self._bs.dkv = self._f32(P, B * L, self.kv_total)
+            emb = self._embed_fwd(P, label_drop)
+            # head, trunk, tail: the GEMM forms, whose operand planes the backward list reads
+            head, xin = self._head_gemm(P, P.step, "input_blocks.0", P.x_in, "in")
+            first = TAct(head.t, m.model_channels, H, W, head.stats)
+            last = self._trunk(P, first)
+            self._bs.gn_names[id(m.out[0])] = "out.gn"
+            P.out = torch.empty((B, m.out_channels, last.h, last.w), dtype=torch.float32, device=self.device)
+            gpl, _ = self._tail_gemm(P, P.step, "out.conv", last, 1e-5, nchw=P.out)
+            self._tail_bwd(P, last, gpl)
+            self._replay_tape(P)
+            self._embed_bwd(P, first, xin, emb)
+            self._cond_bwd(P, groups, L)
+            self._flush_dw(P)
+            self._flush_deferred(P)
+            P.bwd_segments = self._arena_segments(P)
+        finally:
+            self._bs = None
+        self._tplans[key] = P
+        return P
+
+    def _train_key(self, B, H, W, ctx_len, phosc_len, label_drop):
+        """Refuses what cannot train and returns (cache key, label_drop as the plan takes it).  No device work and no change to the
+        engine: a refused call leaves the cached plans as they were."""
+        # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1); a plan is built for its p's
         drops = tuple(DO.check_p(mod.out_layers[2].p) for _, mod in self._walk() if isinstance(mod, ResBlockParams))
         key = (B, H, W, ctx_len, phosc_len, self.npass) + ((drops,) if any(drops) else ())
         if label_drop is not None:
@@ -895,39 +980,20 @@ class TrainEngine(UNetEngine):
             if self.model.num_classes is None:
                 raise ValueError("writer dropout needs a class-conditional model (num_classes)")
             key += (("label_drop", label_drop),)
-        P = self._cached_plan(self._tplans, key)
-        if P is not None:
-            return P
-        if self._tplans:
-            # scratch buffers and the gradient-accumulate flags are sized / decided per plan: one live shape at a time
-            self._tplans.clear()
-            self._scr = {k: v for k, v in self._scr.items() if isinstance(k, tuple)}
-        m = self.model
-        lib = self.lib
         if ctx_len == 0:
             raise NotImplementedError("context=None: every reference script conditions on the word (unet.py:1605)")
         if phosc_len and self.variant != "phosc":
             raise ValueError("phoscLabels are an input of UNetModelPhosc only")
-        P = self._begin_plan(TrainPlan(), B)
-        P.row_base = torch.zeros(1, dtype=torch.int64, device=self.device)
-        L = ctx_len + phosc_len
-        self._tape = []
-        self._pw = set()
-        self._deferred, self._deferred_outs = [], {}
-        self._gn_names = {}
-        self._done_at, self._closure = {}, 0
-        dev = self.device
-        mc = m.model_channels
-        ted = 4 * mc
-        cd = m.context_dim
-        self._size_scratch(B, H, W, L, ctx_len, phosc_len)
-        step = P.step
-        self._inputs(P, H, W, ctx_len, phosc_len)
-        # the conditioning path is differentiated, so it is part of every step
-        groups = self._conditioning(P, step, ctx_len, phosc_len)
-        self._dkv = self._f32(P, B * L, self.kv_total)
+        if self.model.out_channels > 32:
+            raise NotImplementedError("out_channels > 32")  # (the gradient planes of the output convolution are 32 wide)
+        return key, label_drop
 
-        # ---- time / writer embedding with the SiLU pre-activations kept
+    def _embed_fwd(self, P, label_drop):
+        """Appends the time / writer embedding and all FiLM projections (into ``self._film``) to ``P.step``, with the writer-dropout
+        launch in front of time_embed.2 for a plan with ``label_drop``.  Returns what ``_embed_bwd`` reads: the planes and SiLU
+        pre-activations (te, pre1, e1, pre2, e2) and the writer ids of label_emb's backward."""
+        m, lib, B, dev, step = self.model, self.lib, self._B, self.device, P.step
+        mc, ted = m.model_channels, 4 * m.model_channels
         te = self._planes(P, B, mc)
         step.append((lib.wd_timestep_embedding, (P.t_in.data_ptr(), B, self._w["freqs"].data_ptr(), mc // 2, *self._hilo(te), mc),
                      "timestep_embedding"))
@@ -963,99 +1029,98 @@ class TrainEngine(UNetEngine):
         e2 = self._planes(P, B, ted)
         step.append((lib.wd_split, (pre2.data_ptr(), ted, B, ted, 1, *self._hilo(e2), ted), "emb_layers.0(SiLU)"))
         self._film = self._f32(P, B, self.film_total)
-        self._dfilm = self._f32(P, B, self.film_total)
+        self._bs.dfilm = self._f32(P, B, self.film_total)
         self._gemm(step, "emb_layers(all)", [self._src(e2, ted)], "film.w", B, 1, bias=self._w["film.b"], out_f32=self._film,
                    out_ld=self.film_total)
+        return te, pre1, e1, pre2, e2, y_bwd
 
-        # ---- head, trunk, tail: the GEMM forms, whose operand planes the backward list reads
-        head, xin = self._head_gemm(P, step, "input_blocks.0", P.x_in, "in")
-        first = TAct(head.t, mc, H, W, head.stats)
-        last = self._trunk(P, first)
-        self._gn_names[id(m.out[0])] = "out.gn"
-        oc = m.out_channels
-        Mo, hwo = B * last.h * last.w, last.h * last.w
-        P.out = torch.empty((B, oc, last.h, last.w), dtype=torch.float32, device=dev)
-        gpl, _ = self._tail_gemm(P, step, "out.conv", last, 1e-5, nchw=P.out)
+    def _tail_bwd(self, P, last: TAct, gpl):
+        """Opens ``P.bwd``: d(out) (``P.dout``, NCHW) into token rows, the output convolution's backward, out.gn's backward."""
+        m, B = self.model, self._B
+        oc, Mo, hwo = m.out_channels, B * last.h * last.w, last.h * last.w
         tab, _, _ = self._table(last.h, last.w, "same")
-
-        # ================================ backward list ================================
-        bops = P.bwd
-        P.dout = torch.zeros((B, oc, last.h, last.w), dtype=torch.float32, device=dev)
-        if oc > 32:
-            raise NotImplementedError("out_channels > 32")
-        dtok = torch.zeros((Mo, 32), dtype=torch.float32, device=dev)  # columns >= oc stay zero
+        P.dout = torch.zeros((B, oc, last.h, last.w), dtype=torch.float32, device=self.device)
+        dtok = torch.zeros((Mo, 32), dtype=torch.float32, device=self.device)  # columns >= oc stay zero
         P.keep.append(dtok)
-        bops.append((lib.wd_nchw_to_tokens, (P.dout.data_ptr(), B, oc, hwo, dtok.data_ptr(), 32), "d(out):tokens"))
+        P.bwd.append((self.lib.wd_nchw_to_tokens, (P.dout.data_ptr(), B, oc, hwo, dtok.data_ptr(), 32), "d(out):tokens"))
         dg = self._f32(P, Mo, last.c)
         self._bwd_linear(P, "out.conv", dtok, Mo, oc, hwo,
-                         [dict(planes=gpl, c=last.c, ntaps=9, ftab=tab, btab=self._btable(last.h, last.w, "same"), hw_src=hwo,
-                               wb="B:out.w", wgrad=self._pgrad(m.out[2].weight).view(oc, -1), dx=[(dg, last.c, 0, 0, last.c)],
-                               dx_rows=Mo, dx_hw=hwo)], bias=[self._pgrad(m.out[2].bias)], npad=32)
+                         [conv3_seg(gpl, last.c, tab, self._btable(last.h, last.w, "same"), hwo, "B:out.w",
+                                    self._pgrad(m.out[2].weight).view(oc, -1), Dx(dg, last.c, 0, 0, last.c), Mo, hwo)],
+                         bias=[self._pgrad(m.out[2].bias)], npad=32)
         self._gn_bwd(P, "out.gn", [last], m.out[0], 1e-5, True, dg)
-        # closures = units of the backward list (a layer each); bucket boundaries fall between closures, where the deferred
-        # column sums collected so far are finished, so that every gradient written up to there is final
+
+    def _replay_tape(self, P):
+        """Appends the backward of every block to ``P.bwd``, last block first, and sets ``P.bwd_cuts``.  Closures = units of the
+        backward list (a layer each); bucket boundaries fall between closures, where the deferred column sums collected so far are
+        finished, so that every gradient written up to there is final."""
         # (bytes the backward pass will write: the dead heads of the reference - res.*, wrd_proj, attnc, to_kv, norm1 of the base
         # model - never get a gradient; this only balances the buckets, correctness does not depend on it)
         def _live(name):
             return not (name.startswith("res.") or name.startswith("wrd_proj.") or ".attnc." in name or ".to_kv." in name or
                         (self.variant == "base" and ".norm1." in name))
-        total = sum(_rup(p.numel(), 64) for n_, p in m.named_parameters() if _live(n_))
+        bs = self._bs
+        total = sum(_rup(p.numel(), 64) for n_, p in self.model.named_parameters() if _live(n_))
         first_plan = self._cut_closures is None
         cuts_seen: List[int] = []
         P.bwd_cuts = []  # [(index into P.bwd where the segment ends, closure index)]
-        self._closure = 1
-        for fn in reversed(self._tape):
+        bs.closure = 1
+        for fn in reversed(bs.tape):
             fn()
             self._flush_dw(P)
             want = (first_plan and self.nbuckets > 1 and len(cuts_seen) < self.nbuckets - 1 and
                     self._arena_used >= (len(cuts_seen) + 1) * total // self.nbuckets) or \
-                   (not first_plan and self._closure in self._cut_closures)
+                   (not first_plan and bs.closure in self._cut_closures)
             if want:
                 self._flush_deferred(P)
-                cuts_seen.append(self._closure)
-                P.bwd_cuts.append((len(P.bwd), self._closure))
-            self._closure += 1
+                cuts_seen.append(bs.closure)
+                P.bwd_cuts.append((len(P.bwd), bs.closure))
+            bs.closure += 1
         if first_plan:
             self._cut_closures = cuts_seen
-        # ---- input convolution: weight / bias gradient only
+
+    def _embed_bwd(self, P, first: TAct, xin, emb):
+        """Appends to ``P.bwd``: the input convolution's weight / bias gradient, then the FiLM projections, the time MLP and the
+        writer embedding, from d(FiLM rows) back to the timestep embedding."""
+        m, lib, B, bops = self.model, self.lib, self._B, P.bwd
+        te, pre1, e1, pre2, e2, y_bwd = emb
+        mc, ted = m.model_channels, 4 * m.model_channels
         assert first.gw
-        cin0 = m.in_channels
+        hw = first.h * first.w
         packed = self._f32(P, mc, self.kpad_in)
-        self._bwd_linear(P, "input_blocks.0", first.g, B * H * W, mc, H * W,
-                         [dict(planes=xin, c=self.kpad_in, ntaps=1, hw_src=H * W,
-                               wgrad_packed=(packed, self._pgrad(m.input_blocks[0][0].weight), cin0))],
+        self._bwd_linear(P, "input_blocks.0", first.g, B * hw, mc, hw,
+                         [BwdSeg(xin, self.kpad_in, 1, hw,
+                                 wgrad_packed=(packed, self._pgrad(m.input_blocks[0][0].weight), m.in_channels))],
                          bias=[self._pgrad(m.input_blocks[0][0].bias)])
-        # ---- FiLM projections -> time embedding MLP / writer embedding
         film_w = self._pgroup([l.weight for l in self._film_mods])
         film_b = self._pgroup([l.bias for l in self._film_mods])
         de2 = self._f32(P, B, ted)
-        self._bwd_linear(P, "emb_layers(all)", self._dfilm, B, self.film_total, 1,
-                         [dict(planes=e2, c=ted, ntaps=1, hw_src=1, wb="B:film.w", wgrad=film_w, dx=[(de2, ted, 0, 0, ted)],
-                               dx_rows=B, dx_hw=1)], bias=[film_b])
+        self._bwd_linear(P, "emb_layers(all)", self._bs.dfilm, B, self.film_total, 1,
+                         [linear_seg(e2, ted, 1, "B:film.w", film_w, de2, B)], bias=[film_b])
         dpre2 = self._f32(P, B, ted)
         bops.append((lib.wd_silu_bwd, (pre2.data_ptr(), de2.data_ptr(), B * ted, dpre2.data_ptr()), "emb SiLU:bwd"))
-        if has_lab:
+        if y_bwd is not None:
             dl = self._pgrad(m.label_emb.weight)
             bops.append((lib.wd_embedding_bwd, (y_bwd.data_ptr(), 1, B, dpre2.data_ptr(), ted, m.num_classes, ted, dl.data_ptr(),
                                                 self._pacc(dl)), "label_emb:bwd"))
         de1 = self._f32(P, B, ted)
         self._bwd_linear(P, "time_embed.2", dpre2, B, ted, 1,
-                         [dict(planes=e1, c=ted, ntaps=1, hw_src=1, wb="B:te2.w", wgrad=self._pgrad(m.time_embed[2].weight),
-                               dx=[(de1, ted, 0, 0, ted)], dx_rows=B, dx_hw=1)], bias=[self._pgrad(m.time_embed[2].bias)])
+                         [linear_seg(e1, ted, 1, "B:te2.w", self._pgrad(m.time_embed[2].weight), de1, B)],
+                         bias=[self._pgrad(m.time_embed[2].bias)])
         dpre1 = self._f32(P, B, ted)
         bops.append((lib.wd_silu_bwd, (pre1.data_ptr(), de1.data_ptr(), B * ted, dpre1.data_ptr()), "time SiLU:bwd"))
         self._bwd_linear(P, "time_embed.0", dpre1, B, ted, 1,
-                         [dict(planes=te, c=mc, ntaps=1, hw_src=1, wgrad=self._pgrad(m.time_embed[0].weight))],
-                         bias=[self._pgrad(m.time_embed[0].bias)])
-        # ---- K/V projections -> word encoder
-        kv_params = []
-        for at in self._kv_mods:
-            kv_params += [at.to_k.weight, at.to_v.weight]
-        kv_w = self._pgroup(kv_params)
+                         [BwdSeg(te, mc, 1, 1, wgrad=self._pgrad(m.time_embed[0].weight))], bias=[self._pgrad(m.time_embed[0].bias)])
+
+    def _cond_bwd(self, P, groups, L):
+        """Appends the conditioning path's backward to ``P.bwd``: d(K | V) through the K/V projections of every cross-attention
+        into d(context), then per token group the word encoder's attention, q|k|v projection and embedding table."""
+        m, lib, B, bops = self.model, self.lib, self._B, P.bwd
+        cd = m.context_dim
+        kv_w = self._pgroup([w for at in self._kv_mods for w in (at.to_k.weight, at.to_v.weight)])
         dctx = self._f32(P, B * L, cd)
-        self._bwd_linear(P, "cross.kv", self._dkv, B * L, self.kv_total, L,
-                         [dict(planes=P.ctx_pl, c=cd, ntaps=1, hw_src=L, wb="B:kv.w", wgrad=kv_w, dx=[(dctx, cd, 0, 0, cd)],
-                               dx_rows=B * L, dx_hw=L)])
+        self._bwd_linear(P, "cross.kv", self._bs.dkv, B * L, self.kv_total, L,
+                         [linear_seg(P.ctx_pl, cd, L, "B:kv.w", kv_w, dctx, B * L)])
         we = m.word_emb
         at = we.attention
         qkv_w = self._pgroup([at.linear_query.weight, at.linear_key.weight, at.linear_value.weight])
@@ -1074,30 +1139,27 @@ class TrainEngine(UNetEngine):
                            dqkv.data_ptr() + 4 * cd, 3 * cd)
             de = self._f32(P, B * n_tok, cd)
             self._bwd_linear(P, "word_emb.qkv", dqkv, B * n_tok, 3 * cd, n_tok,
-                             [dict(planes=e, c=cd, ntaps=1, hw_src=n_tok, wb="B:we.qkv.w", wgrad=qkv_w,
-                                   dx=[(de, cd, 0, 0, cd)], dx_rows=B * n_tok, dx_hw=n_tok)], bias=[qkv_b])
+                             [linear_seg(e, cd, n_tok, "B:we.qkv.w", qkv_w, de, B * n_tok)], bias=[qkv_b])
             bops.append((lib.wd_embedding_bwd, (ids.data_ptr(), i64, B * n_tok, de.data_ptr(), cd, we.embedding.weight.shape[0], cd,
                                                 dtab.data_ptr(), self._pacc(dtab)), "word_emb.embedding:bwd"))
-        self._flush_dw(P)
-        self._flush_deferred(P)
-        self._tape = []
-        # arena prefix that is final at each cut: the longest prefix (in carve order) of buffers whose last writer is a closure
-        # <= the cut's (buffers never written by this plan - dead heads - count as final)
-        P.bwd_segments = []  # [(bwd_begin, bwd_end, arena_begin, arena_end)]
+
+    def _arena_segments(self, P) -> List[tuple]:
+        """[(bwd_begin, bwd_end, arena_begin, arena_end)] per bucket of ``P.bwd_cuts``: the arena prefix that is final at each cut
+        is the longest prefix (in carve order) of buffers whose last writer is a closure <= the cut's (buffers never written by
+        this plan - dead heads - count as final)."""
+        segments = []
         lo_op, lo_ar = 0, 0
         for (op_end, closure) in P.bwd_cuts:
             hi_ar = lo_ar
             for (ptr, off, n) in self._carve_order:
                 if off < lo_ar:
                     continue
-                if self._done_at.get(ptr, 0) > closure:
+                if self._bs.done_at.get(ptr, 0) > closure:
                     break
                 hi_ar = off + n
-            P.bwd_segments.append((lo_op, op_end, lo_ar, hi_ar))
+            segments.append((lo_op, op_end, lo_ar, hi_ar))
             lo_op, lo_ar = op_end, hi_ar
-        P.bwd_segments.append((lo_op, len(P.bwd), lo_ar, self._arena_used))
-        self._tplans[key] = P
-        return P
+        return segments + [(lo_op, len(P.bwd), lo_ar, self._arena_used)]
 
     # ------------------------------------------------------------------------------------------ run
     def forward_train(self, x, t, context, y, phosc=None, writer_keep=None):
