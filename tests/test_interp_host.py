@@ -171,3 +171,37 @@ def test_mix_rate_without_interpolation_is_not_an_interpolating_call():
     assert random.getstate() == state
     assert tab.shape == (1, 8, 3, 2) and (tab == torch.tensor([3, 7], dtype=torch.int32)).all()
     assert torch.equal(m, torch.linspace(0, 1, 3))
+
+
+def test_mix_setup_draws_the_pairs_it_always_drew_and_a_refused_call_draws_none():
+    """The pairs of an accepted call: ``draw_style_pairs`` over the sampler's model-calling steps in loop order, forward by
+    forward within a step, and ``random`` left after exactly that many draws.  ``mix_rate`` / ``style_pairs`` are validated before
+    the draw, so a refused call leaves ``random`` where it was."""
+    import types
+
+    import pytest
+    from worddiffusion_amd import Diffusion
+    diff, n = Diffusion(noise_steps=8), 3
+    model = types.SimpleNamespace(interpolation=True)
+    skipping = diff._ddpm(lambda i: i in (7, 5, 2))
+    cases = ((None, list(reversed(range(1, 8))), 8), (skipping, [7, 5, 2], 8), (diff._ddim([7, 4, 1], 0.0), [0, 1, 2], 3),
+             (diff._dpmpp([6, 3], 2), [0, 1], 2))
+    for k, (sampler, rows, T) in enumerate(cases):
+        for cfg_scale, nf in ((3, 2), (0, 1)):
+            random.seed(k)
+            drawn = draw_style_pairs(nf * len(rows))
+            state = random.getstate()
+            want = torch.zeros((nf, T, n, 2), dtype=torch.int32)
+            for j, i in enumerate(rows):
+                for f in range(nf):
+                    want[f, i] = torch.tensor(drawn[nf * j + f], dtype=torch.int32)
+            random.seed(k)
+            tab, m, s = diff._mix_setup(model, n, 0.37, None, cfg_scale, **({} if sampler is None else dict(sampler=sampler)))
+            assert torch.equal(tab, want) and tab.dtype == torch.int32 and s == float(cfg_scale)
+            assert random.getstate() == state
+    random.seed(5)
+    state = random.getstate()
+    for mix_rate, style_pairs in ((torch.zeros(2), None), (0.5, (1, 2, 3)), (None, (1, 2)), (torch.zeros(4), (1, 2))):
+        with pytest.raises(ValueError):
+            diff._mix_setup(model, n, mix_rate, style_pairs, 3)
+        assert random.getstate() == state

@@ -6,7 +6,9 @@ update with on-device Philox noise + its timestep advance) is captured into a hi
 there is no per-step host->device traffic.  What a sampler is to that loop is a ``_Sampler``, fixed on the host before
 anything is launched: ``_ddpm`` (``sampling``, ``train.py:221-236``: ``x <- 1/sqrt(a) (x - (1-a)/sqrt(1-ah) eps) + sqrt(b) z``
 at t = T-1 .. 1; ``sampling3`` skips the model on most of those steps), ``_ddim`` (``sampling_ddim``: a subsequence) and
-``_dpmpp`` (``sampling_dpmpp``: a subsequence spaced in log-SNR, second-order multistep).
+``_dpmpp`` (``sampling_dpmpp``: a subsequence spaced in log-SNR, second-order multistep) - it contributes its tables and its one
+update launch; the rest of a step's tail is written once (``_step_tail``).  Everything else a public sampler settles before the
+loop travels in one ``_Call`` record, built by ``Diffusion._sample``, the prelude and epilogue the public samplers share.
 
 Facts preserved from the reference: the method is ``sampling`` (``sample`` is provided as
 an alias because ``sampling.py:119`` calls it); index 0 of the schedule is never used; with ``cfg_scale > 0``
@@ -124,8 +126,8 @@ class _Sampler(NamedTuple):
     steps: list
     t_first: int  # the timestep of the first step
     tau: Optional[list]  # the visited timesteps when FiLM rows and pairs are indexed by the step index; None: indexed by t
-    # update(lib, P, guide, zbuf, seed, sample_offset, device, known=None) -> end_step(stream), the launches that end a step;
-    # known = (x0, mask, eps or None, sqrt_ah, sqrt_1m_ah) on the device: ``wd_known_blend`` between the update and the advance
+    # update(lib, P, run) -> launch(stream): puts the sampler's tables (and any buffer of its own) on ``run.device`` and returns
+    # its one update launch, which keeps them alive; the rest of a step's tail is ``Diffusion._step_tail``
     update: Callable
     stats: dict  # what ``last_stats`` reports of the sampler itself
 
@@ -140,6 +142,75 @@ class _Known(NamedTuple):
     eps: Optional[torch.Tensor]  # the caller's fixed eps, fp32 [n, C*h*w]; None: stream WD_STREAM_KNOWN of the call's seed
 
 
+class _Call(NamedTuple):
+    """What one sampler call is to the reverse loop: everything ``Diffusion._sample`` settles on the host before anything is
+    launched, and what follows from it."""
+    sampler: _Sampler
+    noise_steps: int
+    tabulate_film: bool  # ``Diffusion.tabulate_film``
+    plain_forwards: int  # ``Diffusion.forwards_per_step``: the forwards of a step that has one prediction
+    known: Optional[_Known] = None
+    attention: Optional[tuple] = None  # (weights, N) of ``_attention_setup``
+    mix: Optional[tuple] = None  # (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale) of ``_mix_setup``
+    writer_free: Optional[float] = None  # the scale of ``_guidance_setup``
+    x_T: Optional[torch.Tensor] = None
+    noise: Optional[Sequence] = None
+    seed: Optional[int] = None
+    sample_offset: int = 0
+    record: Optional[list] = None
+    record_pred: Optional[list] = None
+    use_graph: bool = True
+
+    @property
+    def mix_forwards(self):
+        """The forwards per step of an interpolating call, each reading pairs of its own (0: the call does not interpolate)."""
+        return 0 if self.mix is None else int(self.mix[0].shape[0])
+
+    @property
+    def two(self):
+        """Whether a step has two predictions, which its update lerps (train.py:223-228 with two different forwards)."""
+        return self.mix_forwards == 2 or self.writer_free is not None
+
+    @property
+    def scale(self):
+        """The weight of that lerp; None for a step with one prediction."""
+        return None if not self.two else float(self.mix[2]) if self.mix is not None else float(self.writer_free)
+
+    @property
+    def forwards(self):
+        """``last_stats["forwards_per_step"]``."""
+        return self.mix_forwards or (2 if self.writer_free is not None else self.plain_forwards)
+
+    @property
+    def model_steps(self):
+        return sum(fwd for _, fwd, _ in self.sampler.steps)
+
+    @property
+    def model_calls(self):
+        return self.model_steps * (2 if self.two else 1)
+
+    @property
+    def plan_keywords(self):
+        """What ``engine.plan`` takes besides the shapes.  (The interpolation and guidance plans always tabulate the FiLM rows:
+        the pairs / rows of every step live in the table's index, not in a per-step upload.)"""
+        tau = self.sampler.tau
+        film_steps = self.noise_steps if (self.tabulate_film or self.mix is not None or self.writer_free is not None) else 0
+        kw = dict(film_steps=film_steps, mix=self.mix_forwards, film_timesteps=tuple(tau) if (film_steps and tau is not None) else None)
+        if self.attention is not None:
+            kw.update(attn_maps=True, attn_rows=self.attention[0].numel(), attn_by_step=tau is not None)
+        if self.writer_free is not None:
+            kw.update(guide=2)
+        return kw
+
+
+class _Run:
+    """The device side of one ``Diffusion._denoise`` call, filled phase by phase."""
+    # guide = (second prediction or None, lerp weight, where the guided prediction is kept or None) and draw = (noise buffer or
+    # None, seed, sample_offset) are argument runs of the update launches: device pointers, of buffers this record keeps alive
+    __slots__ = ("call", "lib", "engine", "plan", "inputs", "n", "npix", "device", "stream", "seed", "blend", "zbuf", "eps_g", "guide",
+                 "draw", "graphs")
+
+
 def latent_mask_from_pixels(mask_px):
     """A keep-mask over pixels [..., H, W] (H, W multiples of 8; nonzero / True = keep) -> the fp32 keep-mask [..., H/8, W/8] over
     the latent cells of the 8x VAE: an 8x8 min-pool, so a latent cell is kept only if every pixel it covers is."""
@@ -149,13 +220,6 @@ def latent_mask_from_pixels(mask_px):
     m = (m != 0).to(torch.float32)
     H, W = m.shape[-2:]
     return m.reshape(*m.shape[:-2], H // 8, 8, W // 8, 8).amin(dim=(-3, -1)).contiguous()
-
-
-def _blend_known(lib, P, known, p_args, seed, sample_offset, stream):
-    """The ``wd_known_blend`` launch of a step's tail; p_args = (t_dev, k_dev, tau, S) as the kernel takes them."""
-    x0, mask, eps, sa, sb = known
-    N.check(lib.wd_known_blend(P.x_in.data_ptr(), x0.data_ptr(), mask.data_ptr(), P.x_in.shape[0], P.x_in[0].numel(), sa.data_ptr(),
-                               sb.data_ptr(), *p_args, _dptr(eps), seed, sample_offset, stream), "wd_known_blend")
 
 
 class Diffusion:
@@ -355,26 +419,17 @@ class Diffusion:
         first = self.noise_steps - 1 if start is None else int(start)
         steps = [(i, calls_model is None or bool(calls_model(i)), first - i if i > 1 else None) for i in reversed(range(1, first + 1))]
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
-            ca, cb, cs = self._step_tables(device)
+        def update(lib, P, run):
+            ca, cb, cs = self._step_tables(run.device)
             if deterministic:  # regenerateFromtrain2.py:618 drops the sqrt(beta) * noise term
                 cs = torch.zeros_like(cs)
-            n, npix = P.x_in.shape[0], P.x_in[0].numel()
+            guide, draw = run.guide if run.call.two else (), run.draw
+            fn, what = (lib.wd_ddpm_step_cfg, "wd_ddpm_step_cfg") if guide else (lib.wd_ddpm_step, "wd_ddpm_step")
 
-            def end_step(stream):
-                if guide is not None:
-                    N.check(lib.wd_ddpm_step_cfg(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr(), guide[0],
-                                                 _dptr(guide[1]), n, npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
-                                                 P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddpm_step_cfg")
-                else:
-                    N.check(lib.wd_ddpm_step(P.x_in.data_ptr(), P.out.data_ptr(), n, npix, ca.data_ptr(), cb.data_ptr(),
-                                             cs.data_ptr(), P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream),
-                            "wd_ddpm_step")
-                if known is not None:
-                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), None, None, 0), seed, sample_offset, stream)
-                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream),
-                        "wd_advance_timestep")
-            return end_step
+            def launch(stream):
+                N.check(fn(P.x_in.data_ptr(), P.out.data_ptr(), *guide, run.n, run.npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
+                           P.t_dev.data_ptr(), *draw, stream), what)
+            return launch
         # (``steps`` is T - 1 even when steps skip the model: it counts the updates)
         return _Sampler(steps, first, None, update, dict(steps=first))
 
@@ -385,23 +440,14 @@ class Diffusion:
         tabs = self._ddim_tables(tau, eta, "cpu")
         steps = [(k, True, k if s != 0.0 else None) for k, s in enumerate(tabs[4].tolist())]  # (host tables: no device sync)
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
-            c = [t.to(device) for t in tabs]
-            tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
-            P.k_dev.zero_()
-            n, npix = P.x_in.shape[0], P.x_in[0].numel()
-            scale, eps_g = guide or (0.0, None)
+        def update(lib, P, run):
+            c = [t.to(run.device) for t in tabs]
+            guide, draw = run.guide, run.draw
 
-            def end_step(stream):
-                N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
-                                         scale, _dptr(eps_g), n, npix, *(t.data_ptr() for t in c), P.k_dev.data_ptr(),
-                                         P.t_dev.data_ptr(), _dptr(zbuf), seed, sample_offset, stream), "wd_ddim_step")
-                if known is not None:  # at the level of tau[k + 1] (index 0 after the last entry), read from k_dev
-                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau)), seed,
-                                 sample_offset, stream)
-                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
-                                             P.t_in.data_ptr(), n, stream), "wd_next_timestep")
-            return end_step
+            def launch(stream):
+                N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), *guide, run.n, run.npix, *(t.data_ptr() for t in c),
+                                         P.k_dev.data_ptr(), P.t_dev.data_ptr(), *draw, stream), "wd_ddim_step")
+            return launch
         stats = dict(sampler="ddim", steps=len(tau), eta=float(eta), timesteps=list(tau))
         return _Sampler(steps, tau[0], list(tau), update, stats)
 
@@ -413,24 +459,15 @@ class Diffusion:
         tabs = self._dpmpp_tables(tau, order, "cpu")
         steps = [(k, True, None) for k in range(len(tau))]
 
-        def update(lib, P, guide, zbuf, seed, sample_offset, device, known=None):
-            c = [t.to(device) for t in tabs]
-            tau_dev = torch.tensor(tau, dtype=torch.int32, device=device)
-            x0_prev = torch.empty_like(P.x_in)  # (the first step does not read it: c5[0] == 0)
-            P.k_dev.zero_()
-            n, npix = P.x_in.shape[0], P.x_in[0].numel()
-            scale, eps_g = guide or (0.0, None)
+        def update(lib, P, run):
+            c = [t.to(run.device) for t in tabs]
+            x0_prev = torch.empty_like(P.x_in)  # (the first step does not read it: c5[0] == 0; the blend changes x alone)
+            guide = run.guide
 
-            def end_step(stream):
-                N.check(lib.wd_dpmpp_step(P.x_in.data_ptr(), P.out.data_ptr(), P.out1.data_ptr() if guide is not None else None,
-                                          scale, _dptr(eps_g), x0_prev.data_ptr(), n, npix, *(t.data_ptr() for t in c),
-                                          P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
-                if known is not None:  # (x0_prev keeps the model's own data prediction: the blend changes x alone)
-                    _blend_known(lib, P, known, (P.t_dev.data_ptr(), P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau)), seed,
-                                 sample_offset, stream)
-                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(),
-                                             P.t_in.data_ptr(), n, stream), "wd_next_timestep")
-            return end_step
+            def launch(stream):
+                N.check(lib.wd_dpmpp_step(P.x_in.data_ptr(), P.out.data_ptr(), *guide, x0_prev.data_ptr(), run.n, run.npix,
+                                          *(t.data_ptr() for t in c), P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
+            return launch
         stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
         return _Sampler(steps, tau[0], list(tau), update, stats)
 
@@ -525,153 +562,196 @@ class Diffusion:
             mode = "fixed"
         return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
 
-    def _denoise(self, model, n, text_features, labels, phosc, device, sampler, x_T=None, noise=None, seed=None,
-                 sample_offset=0, record=None, use_graph=True, mix=None, record_pred=None, known=None, attention=None,
-                 writer_free=None):
-        """The one reverse loop.  Per visited step of ``sampler`` (``_ddpm`` / ``_ddim``): this step's ``noise`` entry into
-        the noise buffer if it has one, ``film_prepare`` and the forward(s) when the step calls the model, the sampler's update.
-        mix = (pairs int32 [nf, rows, n, 2], rates fp32 [n], guidance scale): writer-style interpolation with ``nf`` forwards per
-        step, forward f of a step reading pairs[f, its film_prepare argument]; nf = 2 ends the step with the guided update.
-        record_pred: a list that receives, per model-calling step, the predictions of its forwards (and, for nf = 2, the guided
-        one) - eager launches only, like ``record``.
-        known: a ``_Known``.  Its fixed eps (the caller's, or stream WD_STREAM_KNOWN of ``seed`` at the global rows) noises the
-        known latents to ``known.start``, where the loop then begins, and with a mask every step's tail blends the kept region
-        back in at the level the step reached (``wd_known_blend``, inside the captured graph).
-        attention: what ``_attention_setup`` returned.  The plan then holds three map accumulators, zeroed here, and every
-        model-calling step adds its weight times its maps (``wd_xattn_maps`` inside the captured step, the first forward of a
-        step only); the weighted mean lands in ``last_attention``.
-        writer_free: None, or the guidance scale of a writer-free guided call (``_guidance_setup``): a step is the conditional
-        forward, the forward without the writer term (``engine.plan`` guide = 2) and the guided update
-        ``torch.lerp(free, cond, scale)`` - the two-forward step of the interpolation mode with other FiLM rows."""
-        lib = N.lib()
-        eng = model.engine
-        nf = 0 if mix is None else int(mix[0].shape[0])
-        two = nf == 2 or writer_free is not None  # forwards per step with predictions of their own, lerped by the update
-        if nf:
-            eng.check_pairs(mix[0])  # first: nothing is launched for an id that does not fit the table
-            labels = None  # unused in this mode (unet.py:1558-1573)
-        eng.refresh_weights()
-        eng.check_ids(text_features, labels, phosc, need_y=not nf)  # host tensors here: no device sync
-        h, w = self.img_size[0] // 8, self.img_size[1] // 8
-        ctx_len = text_features.shape[1]
-        phosc_len = 0 if phosc is None else phosc.shape[1]
-        # (the interpolation plan always tabulates: the pairs of every step live in the table's index, not in a per-step upload)
-        film_steps = self.noise_steps if (self.tabulate_film or nf or writer_free is not None) else 0
-        P = eng.plan(n, h, w, ctx_len, phosc_len, film_steps=film_steps, mix=nf,
-                     film_timesteps=tuple(sampler.tau) if (film_steps and sampler.tau is not None) else None,
-                     **(dict(attn_maps=True, attn_rows=attention[0].numel(), attn_by_step=sampler.tau is not None)
-                        if attention is not None else {}),
-                     **(dict(guide=2) if writer_free is not None else {}))
-        fps = nf or (2 if writer_free is not None else self.forwards_per_step)
-        ncalls = sum(fwd for _, fwd, _ in sampler.steps)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-        npix = P.x_in[0].numel()
-        if known is not None and known.x0.shape[1] != npix:
-            raise ValueError(f"known holds {known.x0.shape[1]} values per sample, the model's latent {npix} {tuple(P.x_in.shape[1:])}")
-
+    def _denoise(self, model, n, text_features, labels, phosc, device, call):
+        """The one reverse loop of every sampler (``_ddpm`` / ``_ddim`` / ``_dpmpp``); ``call`` is the ``_Call`` of ``_sample``.
+        ``_plan_call`` refuses and plans; then, on a side stream, ``_start_latent`` and ``_upload`` fill the plan's buffers,
+        ``_step_tail`` builds the step, ``_capture`` turns it into one or two hipGraphs, ``_loop`` visits the sampler's steps and
+        ``_results`` leaves ``last_stats`` / ``last_attention`` and returns x.  The graphs are destroyed on every exit path, after
+        the stream that may still be running them has drained."""
+        run = self._plan_call(model, n, text_features, labels, phosc, device, call)
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            st = side.cuda_stream
-            blend = None
-            if known is not None:
-                kx0 = known.x0.to(device)
-                sa, sb = self._noise_tables(device)
-                keps = None
-                if known.start is not None or (known.mask is not None and known.mode == "fixed"):
-                    if known.eps is not None:
-                        keps = known.eps.to(device)
-                    else:
-                        keps = torch.empty_like(kx0)
-                        N.check(lib.wd_randn(keps.data_ptr(), n, npix, seed, sample_offset, N.STREAM_KNOWN, st), "wd_randn")
-                if known.mask is not None:
-                    blend = (kx0, known.mask.to(device), keps if known.mode == "fixed" else None, sa, sb)
-            if known is not None and known.start is not None:
-                level = torch.full((n,), known.start, dtype=torch.int64, device=device)
-                N.check(lib.wd_noise_images(kx0.data_ptr(), keps.data_ptr(), level.data_ptr(), sa.data_ptr(), sb.data_ptr(), n, npix,
-                                            P.x_in.data_ptr(), st), "wd_noise_images")
-            elif x_T is not None:
-                P.x_in.copy_(x_T.to(device))
-            else:
-                N.check(lib.wd_randn(P.x_in.data_ptr(), n, P.x_in[0].numel(), seed, sample_offset, 0, st), "wd_randn")
-            eng.load_inputs(P, None, None, text_features.to(device), labels.to(device) if labels is not None else None,
-                            phosc.to(device) if phosc is not None else None, check=False)
-            if nf:
-                eng.load_mix(P, mix[0].to(device), mix[1].to(device), check=False)
-            if attention is not None:
-                P.map_w.copy_(attention[0])
-                for acc in P.maps:
-                    acc.zero_()
-            eps_g = torch.empty_like(P.out) if (two and record_pred is not None) else None
-            P.t_dev.fill_(sampler.t_first)
-            P.t_in.fill_(sampler.t_first)
-            zbuf = torch.zeros_like(P.x_in) if noise is not None else None
-            scale = None if not two else float(mix[2]) if nf else float(writer_free)
-            end_step = sampler.update(lib, P, (scale, eps_g) if two else None, zbuf, seed, sample_offset, device, known=blend)
-            P.run_cond(st)
-            P.run_film(st)  # time MLP of every timestep; the FiLM rows follow per chunk of timesteps (P.film_prepare)
-            # before the capture: the captured step only reads the table (its rows are indexed by t, or by the DDIM step index)
-            if sampler.steps:
-                P.film_prepare(sampler.steps[0][0], st)
+        run.stream = side.cuda_stream
+        try:
+            with torch.cuda.stream(side):
+                self._start_latent(run)
+                self._upload(run)
+                step = self._step_tail(run)  # (kept out of ``run``, which it refers to: no reference cycle holds the buffers)
+                self._capture(run, step)
+                self._loop(run, step)
+                x = self._results(run)
+            torch.cuda.current_stream(device).wait_stream(side)
+        finally:
+            if run.graphs:
+                side.synchronize()
+                for g in run.graphs:
+                    run.lib.wd_graph_destroy(g)
+        return x
 
-            def one_step(stream, forward=True):
-                if forward:
-                    for _ in range(1 if two or nf else fps):
-                        P.run_step(stream)
-                    if two:  # train.py:223-228 with two different forwards: lerp(second, first, cfg_scale) feeds the update
-                        P.run_step1(stream)
-                end_step(stream)
+    def _plan_call(self, model, n, text_features, labels, phosc, device, call):
+        """Refuses ids that do not fit their tables (host tensors: nothing is launched for them and no device sync), repacks
+        weights that changed (``engine.refresh_weights``), gets the launch plan and settles the call's seed.  Launches nothing else."""
+        run = _Run()
+        run.call, run.lib, run.engine, run.n, run.device, run.graphs = call, N.lib(), model.engine, n, device, []
+        if call.mix is not None:
+            run.engine.check_pairs(call.mix[0])  # first: nothing is launched for an id that does not fit the table
+            labels = None  # unused in this mode (unet.py:1558-1573)
+        run.engine.refresh_weights()
+        run.engine.check_ids(text_features, labels, phosc, need_y=call.mix is None)
+        run.inputs = (text_features, labels, phosc)
+        run.plan = run.engine.plan(n, self.img_size[0] // 8, self.img_size[1] // 8, text_features.shape[1],
+                                   0 if phosc is None else phosc.shape[1], **call.plan_keywords)
+        run.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if call.seed is None else int(call.seed)
+        run.npix = run.plan.x_in[0].numel()
+        if call.known is not None and call.known.x0.shape[1] != run.npix:
+            raise ValueError(f"known holds {call.known.x0.shape[1]} values per sample, the model's latent {run.npix} "
+                             f"{tuple(run.plan.x_in.shape[1:])}")
+        return run
 
-            def capture(forward):
-                N.check(lib.wd_graph_begin(st), "wd_graph_begin")
-                try:
-                    one_step(st, forward)
-                finally:
-                    g = C.c_void_p()
-                    rc = lib.wd_graph_end(st, C.byref(g))
-                N.check(rc, "wd_graph_end")
-                return g
-
-            gexec = gskip = None
-            if use_graph and record is None and record_pred is None:
-                gexec = capture(True)
-                if ncalls < len(sampler.steps):
-                    gskip = capture(False)  # steps that reuse the previous predicted noise: update only
-            for row, fwd, z in sampler.steps:
-                if record is not None:
-                    record.append(P.x_in.clone())
-                if zbuf is not None and z is not None:
-                    zbuf.copy_(noise[z].to(device))
-                if fwd:
-                    P.film_prepare(row, st)  # FiLM rows of this step (computed per chunk of rows, see engine.plan)
-                if gexec is not None:
-                    N.check(lib.wd_graph_launch(gexec if fwd else gskip, st), "wd_graph_launch")
+    def _start_latent(self, run):
+        """Fills ``P.x_in``, the latent the loop starts from: the known latents noised to ``known.start`` (``wd_noise_images`` with
+        the call's fixed eps - the caller's, or ``wd_randn`` on stream WD_STREAM_KNOWN of the seed at the global rows), the
+        caller's ``x_T``, or ``wd_randn``.  With a mask, ``run.blend`` = (x0, mask, eps or None, sqrt_ah, sqrt_1m_ah) on the device is
+        what every step's ``wd_known_blend`` reads (eps None: it draws its noise per step)."""
+        call, lib, P, n, npix, device, st = run.call, run.lib, run.plan, run.n, run.npix, run.device, run.stream
+        known, run.blend = call.known, None
+        if known is not None:
+            kx0 = known.x0.to(device)
+            sa, sb = self._noise_tables(device)
+            keps = None
+            if known.start is not None or (known.mask is not None and known.mode == "fixed"):
+                if known.eps is not None:
+                    keps = known.eps.to(device)
                 else:
-                    one_step(st, fwd)
-                if record_pred is not None and fwd:
-                    record_pred.append((P.out.clone(),) if not two else (P.out.clone(), P.out1.clone(), eps_g.clone()))
-            x = P.x_in.clone()
-            self.last_attention = None
-            if attention is not None:
-                self.last_attention = {k: acc.clone().reshape(n, mh, mw, -1)
-                                       for k, acc, (mh, mw) in zip(("input", "middle", "output"), P.maps, P.map_hw)}
-        torch.cuda.current_stream(device).wait_stream(side)
-        if gexec is not None:
-            side.synchronize()
-            lib.wd_graph_destroy(gexec)
-            if gskip is not None:
-                lib.wd_graph_destroy(gskip)
-        self.last_stats = dict(sampler.stats, forwards_per_step=fps, graph=gexec is not None, seed=seed,
-                               sample_offset=sample_offset, model_calls=ncalls * (2 if two else nf or 1), known=known is not None,
+                    keps = torch.empty_like(kx0)
+                    N.check(lib.wd_randn(keps.data_ptr(), n, npix, run.seed, call.sample_offset, N.STREAM_KNOWN, st), "wd_randn")
+            if known.mask is not None:
+                run.blend = (kx0, known.mask.to(device), keps if known.mode == "fixed" else None, sa, sb)
+        if known is not None and known.start is not None:
+            level = torch.full((n,), known.start, dtype=torch.int64, device=device)
+            N.check(lib.wd_noise_images(kx0.data_ptr(), keps.data_ptr(), level.data_ptr(), sa.data_ptr(), sb.data_ptr(), n, npix,
+                                        P.x_in.data_ptr(), st), "wd_noise_images")
+        elif call.x_T is not None:
+            P.x_in.copy_(call.x_T.to(device))
+        else:
+            N.check(lib.wd_randn(P.x_in.data_ptr(), n, npix, run.seed, call.sample_offset, 0, st), "wd_randn")
+
+    def _upload(self, run):
+        """The call's side inputs into the plan's buffers: word ids, writer ids and PHOSC labels, the pairs and rates of an
+        interpolating call, the attention weights with zeroed accumulators, the first timestep; and the two buffers the loop
+        itself fills or reads: ``zbuf`` for a step's ``noise`` entry, ``eps_g`` for the guided prediction ``record_pred`` receives."""
+        call, P, device = run.call, run.plan, run.device
+        text_features, labels, phosc = run.inputs
+        run.engine.load_inputs(P, None, None, text_features.to(device), labels.to(device) if labels is not None else None,
+                               phosc.to(device) if phosc is not None else None, check=False)
+        if call.mix is not None:
+            run.engine.load_mix(P, call.mix[0].to(device), call.mix[1].to(device), check=False)
+        if call.attention is not None:
+            P.map_w.copy_(call.attention[0])
+            for acc in P.maps:
+                acc.zero_()
+        run.eps_g = torch.empty_like(P.out) if (call.two and call.record_pred is not None) else None
+        P.t_dev.fill_(call.sampler.t_first)
+        P.t_in.fill_(call.sampler.t_first)
+        run.zbuf = torch.zeros_like(P.x_in) if call.noise is not None else None
+        run.guide = (P.out1.data_ptr(), call.scale, _dptr(run.eps_g)) if call.two else (None, 0.0, None)
+        run.draw = (_dptr(run.zbuf), run.seed, call.sample_offset)
+
+    def _step_tail(self, run):
+        """One step as the loop and the capture launch it, ``step(stream, forward)``: the forward(s) (``run_step1`` after
+        ``run_step`` when the step has two predictions), the sampler's own update launch, ``wd_known_blend`` when a region is kept
+        and the advance.  A sampler indexed by t (``tau`` None) blends at the level t - 1 and advances with
+        ``wd_advance_timestep``; one that visits ``tau`` (put on the device here, its step counter ``k_dev`` zeroed) blends at the
+        level of tau[k + 1] (index 0 after the last entry) and advances with ``wd_next_timestep``."""
+        call, lib, P, n, npix = run.call, run.lib, run.plan, run.n, run.npix
+        update = call.sampler.update(lib, P, run)
+        tau, two = call.sampler.tau, call.two
+        forwards = 1 if (two or call.mix is not None) else call.plain_forwards
+        if tau is not None:
+            tau_dev = torch.tensor(tau, dtype=torch.int32, device=run.device)
+            P.k_dev.zero_()
+
+        def step(stream, forward=True):
+            if forward:
+                for _ in range(forwards):
+                    P.run_step(stream)
+                if two:  # train.py:223-228 with two different forwards: lerp(second, first, cfg_scale) feeds the update
+                    P.run_step1(stream)
+            update(stream)
+            if run.blend is not None:
+                x0, mask, eps, sa, sb = run.blend
+                level = (None, None, 0) if tau is None else (P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau))
+                N.check(lib.wd_known_blend(P.x_in.data_ptr(), x0.data_ptr(), mask.data_ptr(), n, npix, sa.data_ptr(), sb.data_ptr(),
+                                           P.t_dev.data_ptr(), *level, _dptr(eps), run.seed, call.sample_offset, stream), "wd_known_blend")
+            if tau is None:
+                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream), "wd_advance_timestep")
+            else:
+                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(), P.t_in.data_ptr(), n,
+                                             stream), "wd_next_timestep")
+        return step
+
+    def _capture(self, run, step):
+        """What the steps share, before any of them: the word embedding and cross-attention K/V (``run_cond``), the time MLP of
+        every timestep (``run_film``) and the FiLM rows of the first step - the captured step only reads the table, whose rows are
+        indexed by t or by the step index.  Then, unless the call is eager, one hipGraph of a whole step and, where steps reuse the
+        previous predicted noise, one of the tail alone; ``run.graphs`` holds each from the moment it exists."""
+        call, lib, P, st = run.call, run.lib, run.plan, run.stream
+        P.run_cond(st)
+        P.run_film(st)
+        if call.sampler.steps:
+            P.film_prepare(call.sampler.steps[0][0], st)
+        if not call.use_graph or call.record is not None or call.record_pred is not None:
+            return  # eager launches: asked for, or needed to read a step's tensors
+        for forward in (True, False) if call.model_steps < len(call.sampler.steps) else (True,):
+            N.check(lib.wd_graph_begin(st), "wd_graph_begin")
+            try:
+                step(st, forward)
+            finally:  # (ends the capture when a launch of the step raised, too)
+                g = C.c_void_p()
+                rc = lib.wd_graph_end(st, C.byref(g))
+            N.check(rc, "wd_graph_end")
+            run.graphs.append(g)
+
+    def _loop(self, run, step):
+        """Per visited step: x into ``record``, the step's ``noise`` entry into ``zbuf`` if it has one, the FiLM rows of the step
+        (``film_prepare``, computed per chunk of rows) when it calls the model, then the step - ``wd_graph_launch`` of the whole
+        step or of its tail, or its eager launches - and its predictions into ``record_pred``."""
+        call, lib, P, st, device = run.call, run.lib, run.plan, run.stream, run.device
+        record, record_pred, noise, zbuf, two = call.record, call.record_pred, call.noise, run.zbuf, call.two
+        gexec, gskip = (run.graphs + [None, None])[:2]
+        for row, fwd, z in call.sampler.steps:
+            if record is not None:
+                record.append(P.x_in.clone())
+            if zbuf is not None and z is not None:
+                zbuf.copy_(noise[z].to(device))
+            if fwd:
+                P.film_prepare(row, st)
+            if gexec is not None:
+                N.check(lib.wd_graph_launch(gexec if fwd else gskip, st), "wd_graph_launch")
+            else:
+                step(st, fwd)
+            if record_pred is not None and fwd:
+                record_pred.append((P.out.clone(),) if not two else (P.out.clone(), P.out1.clone(), run.eps_g.clone()))
+
+    def _results(self, run):
+        """x, cloned out of the plan's buffer; ``last_attention`` (the accumulators, cloned likewise, or None) and ``last_stats``."""
+        call, P, known = run.call, run.plan, run.call.known
+        x = P.x_in.clone()
+        self.last_attention = None
+        if call.attention is not None:
+            self.last_attention = {k: acc.clone().reshape(run.n, mh, mw, -1)
+                                   for k, acc, (mh, mw) in zip(("input", "middle", "output"), P.maps, P.map_hw)}
+        self.last_stats = dict(call.sampler.stats, forwards_per_step=call.forwards, graph=bool(run.graphs), seed=run.seed,
+                               sample_offset=call.sample_offset, model_calls=call.model_calls, known=known is not None,
                                start=None if known is None else known.start, known_noise=None if known is None else known.mode)
-        if attention is not None:
-            self.last_stats["attention_steps"] = attention[1]
-        if writer_free is not None:
+        if call.attention is not None:
+            self.last_stats["attention_steps"] = call.attention[1]
+        if call.writer_free is not None:
             self.last_stats["guidance"] = "writer_free"
         return x
 
     def _guidance_setup(self, model, guidance, cfg_scale, mix):
-        """The ``guidance`` argument of a sampler call, settled on the host: the ``writer_free`` argument of ``_denoise`` - None,
+        """The ``guidance`` argument of a sampler call, settled on the host: the ``writer_free`` field of the ``_Call`` - None,
         or the scale of the guided update.  ``guidance="writer_free"`` with ``cfg_scale > 0`` runs, per model-calling step, the
         conditional forward, the forward without the writer term and ``torch.lerp(free, cond, cfg_scale)``; with ``cfg_scale == 0``
         one forward runs, as behind the reference's ``if cfg_scale > 0`` (train.py:223), and the call is the plain one."""
@@ -690,7 +770,8 @@ class Diffusion:
         return s if s > 0 else None
 
     def _mix_setup(self, model, n, mix_rate, style_pairs, cfg_scale, *, sampler=None):
-        """The ``mix`` argument of ``_denoise`` for a sampler call, or None where the call does not interpolate.
+        """The ``mix`` field of the ``_Call`` of a sampler call, or None where the call does not interpolate (``_mix_check``, which
+        refuses a bad ``mix_rate`` / ``style_pairs`` before anything is drawn, then ``_mix_table``).
 
         Fixed-pair mode (``style_pairs`` given: one ``(s1, s2)`` or an int tensor [n, 2]; ``mix_rate`` a float or fp32 [n]): the
         same pair at every step, so the two guidance forwards of train.py:223-228 are identical and one runs.
@@ -701,16 +782,35 @@ class Diffusion:
         ``sampler`` (default ``_ddpm()``) says which steps those are: pairs are drawn for its model-calling steps only, in loop
         order, and the table is indexed as its FiLM rows are - by t, [nf, T, n, 2], or by the step index of its ``tau``,
         [nf, S, n, 2]."""
-        sampler = sampler or self._ddpm()
-        T = self.noise_steps if sampler.tau is None else len(sampler.tau)
+        checked = self._mix_check(model, n, mix_rate, style_pairs)
+        return None if checked is None else self._mix_table(checked, n, cfg_scale, sampler or self._ddpm())
+
+    def _mix_check(self, model, n, mix_rate, style_pairs):
+        """The deciding and validating half of ``_mix_setup``, which touches neither ``random`` nor the device: None where the
+        call does not interpolate, else (the fixed pairs, int32 [n, 2], or None where they are to be drawn; the rates, fp32 [n])."""
         if style_pairs is not None:
             if mix_rate is None:
                 raise ValueError("style_pairs needs a mix_rate (a float, or one per sample)")
             sp = torch.as_tensor(style_pairs)
             if sp.is_floating_point() or sp.shape not in ((2,), (n, 2)):
                 raise ValueError(f"style_pairs must be (s1, s2) or an integer tensor [{n}, 2]")
-            tab = sp.to(torch.int32).cpu().reshape(-1, 2).expand(n, 2).reshape(1, 1, n, 2).expand(1, T, n, 2).contiguous()
+            sp = sp.to(torch.int32).cpu().reshape(-1, 2).expand(n, 2)
         elif mix_rate is not None and getattr(model, "interpolation", False):
+            sp = None
+        else:
+            return None
+        m = torch.as_tensor(mix_rate, dtype=torch.float32).cpu().reshape(-1)
+        if m.numel() not in (1, n):
+            raise ValueError(f"mix_rate must be a float or hold one rate per sample ({n})")
+        return sp, m.expand(n).contiguous()
+
+    def _mix_table(self, checked, n, cfg_scale, sampler):
+        """The other half: the pairs table of a call ``_mix_check`` accepted - here the pairs are drawn - with its rates and scale."""
+        sp, m = checked
+        T = self.noise_steps if sampler.tau is None else len(sampler.tau)
+        if sp is not None:
+            tab = sp.reshape(1, 1, n, 2).expand(1, T, n, 2).contiguous()
+        else:
             steps = [row for row, fwd, _ in sampler.steps if fwd]
             nf = 2 if cfg_scale > 0 else 1
             drawn = draw_style_pairs(nf * len(steps))
@@ -718,12 +818,7 @@ class Diffusion:
             for k, i in enumerate(steps):
                 for f in range(nf):
                     tab[f, i] = torch.tensor(drawn[nf * k + f], dtype=torch.int32)
-        else:
-            return None
-        m = torch.as_tensor(mix_rate, dtype=torch.float32).cpu().reshape(-1)
-        if m.numel() not in (1, n):
-            raise ValueError(f"mix_rate must be a float or hold one rate per sample ({n})")
-        return tab, m.expand(n).contiguous(), float(cfg_scale)
+        return tab, m, float(cfg_scale)
 
     def _text_features(self, x_text, n, underscore=False):
         words = [x_text] * n if isinstance(x_text, str) else list(x_text)
@@ -763,6 +858,29 @@ class Diffusion:
             return image.permute(0, 3, 1, 2)
         raise NotImplementedError("latent=False (pixel-space UNet) is dead code in the reference (SURVEY.md 0.5)")
 
+    def _sample(self, who, model, vae, n, x_text, labels, args, build, *, phoscLabels=None, underscore=None, bulk=False,
+                attention=None, mix_rate=None, style_pairs=None, cfg_scale=3, guidance=None, **loop):
+        """What every public sampler does around its loop, after its own argument handling: ``_prepare``, the ``_Sampler``
+        (``build()``), the attention, interpolation and guidance arguments settled on the host - a refused call has launched
+        nothing and drawn nothing from ``random``: the pairs are drawn last - then ``_denoise`` on the ``_Call`` (``loop``: its
+        remaining fields) with the model in eval mode and in TRAIN mode afterwards, whatever happened (train.py:201,238), and
+        ``_finish``.  ``bulk`` (``sampling3``): the caller has put the model in eval mode and it stays there, and ``args.latent``
+        is not looked at."""
+        device, tf, phosc = self._prepare(who, model, n, x_text, args, phoscLabels, underscore, check_latent=not bulk)
+        sampler = build()
+        att = self._attention_setup(model, sampler, attention)
+        checked = self._mix_check(model, n, mix_rate, style_pairs)
+        wf = self._guidance_setup(model, guidance, cfg_scale, checked)
+        mix = None if checked is None else self._mix_table(checked, n, cfg_scale, sampler)
+        call = _Call(sampler, self.noise_steps, self.tabulate_film, self.forwards_per_step, attention=att, mix=mix, writer_free=wf, **loop)
+        model.eval()
+        try:
+            x = self._denoise(model, n, tf, labels, phosc, device, call)
+        finally:
+            if not bulk:
+                model.train()  # train.py:238 (unconditional)
+        return x if vae is None else self._finish(x, vae, args)
+
     @torch.no_grad()
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
@@ -799,19 +917,10 @@ class Diffusion:
         ``cfg_scale == 0`` the call is the plain one.  Without the argument ``cfg_scale`` stays inert outside interpolation mode,
         as in the reference, whose two forwards are identical (train.py:224-228).  Not together with the interpolation modes."""
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True)
-        device, tf, phosc = self._prepare("sampling", model, n, x_text, args, phoscLabels, underscore)
-        sampler = self._ddpm(start=None if kn is None else kn.start)
-        att = self._attention_setup(model, sampler, attention)
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
-        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
-        model.eval()
-        try:
-            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
-                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix,
-                              record_pred=record_pred, known=kn, attention=att, writer_free=wf)
-        finally:
-            model.train()  # train.py:238 (unconditional)
-        return self._finish(x, vae, args)
+        return self._sample("sampling", model, vae, n, x_text, labels, args, lambda: self._ddpm(start=None if kn is None else kn.start),
+                            phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
+                            style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
+                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph)
 
     @torch.no_grad()
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
@@ -838,19 +947,10 @@ class Diffusion:
             tau = kn.tau
         if noise is not None and len(noise) != len(tau):
             raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
-        device, tf, phosc = self._prepare("sampling_ddim", model, n, x_text, args, phoscLabels, underscore)
-        sampler = self._ddim(tau, eta)
-        att = self._attention_setup(model, sampler, attention)
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
-        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
-        model.eval()
-        try:
-            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, noise=noise, seed=seed,
-                              sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, record_pred=record_pred,
-                              known=kn, attention=att, writer_free=wf)
-        finally:
-            model.train()  # as ``sampling`` (train.py:238)
-        return self._finish(x, vae, args)
+        return self._sample("sampling_ddim", model, vae, n, x_text, labels, args, lambda: self._ddim(tau, eta),
+                            phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
+                            style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
+                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph)
 
     @torch.no_grad()
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
@@ -875,19 +975,11 @@ class Diffusion:
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=False, tau=tau)
         if kn is not None:
             tau = kn.tau
-        device, tf, phosc = self._prepare("sampling_dpmpp", model, n, x_text, args, phoscLabels, underscore)
-        sampler = self._dpmpp(tau, order, None if timesteps is not None else spacing)
-        att = self._attention_setup(model, sampler, attention)
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, cfg_scale, sampler=sampler)
-        wf = self._guidance_setup(model, guidance, cfg_scale, mix)
-        model.eval()
-        try:
-            x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_T, seed=seed, sample_offset=sample_offset,
-                              record=record, use_graph=use_graph, mix=mix, record_pred=record_pred, known=kn, attention=att,
-                              writer_free=wf)
-        finally:
-            model.train()  # as ``sampling`` (train.py:238)
-        return self._finish(x, vae, args)
+        return self._sample("sampling_dpmpp", model, vae, n, x_text, labels, args,
+                            lambda: self._dpmpp(tau, order, None if timesteps is not None else spacing), phoscLabels=phoscLabels,
+                            underscore=underscore, attention=attention, mix_rate=mix_rate, style_pairs=style_pairs, cfg_scale=cfg_scale,
+                            guidance=guidance, known=kn, x_T=x_T, seed=seed, sample_offset=sample_offset, record=record,
+                            record_pred=record_pred, use_graph=use_graph)
 
     sample = sampling  # sampling.py:119 / full_sampling.py:167 call .sample(...)
 
@@ -922,18 +1014,14 @@ class Diffusion:
             word_list = [x_text if isinstance(x_text, str) else x_text[0]] * n
         else:
             word_list = list(words)
-        device, tf, phosc = self._prepare("sampling3", model, n, word_list, args, phoscLabels, check_latent=False)
         full = bool(getattr(args, "fullSampling", False))
-        sampler = self._ddpm(None if full else (lambda i: self.sampling3_calls_model(i, self.noise_steps, epoch)),
-                             deterministic=not full)
-        att = self._attention_setup(model, sampler, attention)
-        mix = self._mix_setup(model, n, mix_rate, style_pairs, 0, sampler=sampler)  # (one forward per step: no guidance here)
-        x = self._denoise(model, n, tf, labels, phosc, device, sampler, x_T=x_t if noiseInput == 0 else x_T, noise=noise,
-                          seed=seed, sample_offset=sample_offset, record=record, use_graph=use_graph, mix=mix, attention=att)
-        if vae is None:
-            return x
-        image = self._finish(x, vae, args)
-        return 0, [image], image
+        calls_model = None if full else (lambda i: self.sampling3_calls_model(i, self.noise_steps, epoch))
+        # (cfg_scale 0: one forward per step, no guidance here)
+        out = self._sample("sampling3", model, vae, n, word_list, labels, args, lambda: self._ddpm(calls_model, deterministic=not full),
+                           phoscLabels=phoscLabels, bulk=True, attention=attention, mix_rate=mix_rate, style_pairs=style_pairs,
+                           cfg_scale=0, x_T=x_t if noiseInput == 0 else x_T, noise=noise, seed=seed, sample_offset=sample_offset,
+                           record=record, use_graph=use_graph)
+        return out if vae is None else (0, [out], out)
 
     def sampling_modify_condition(self, model, vae, latents, x_text, words, n, labels, args, **kw):
         """Argument order of ``trainModifyCondition.py:545``; that variant feeds writer id 1 for every sample
