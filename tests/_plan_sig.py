@@ -55,6 +55,16 @@ def signature(engine, P) -> tuple:
     return tuple(sig)
 
 
+def families(sig) -> dict:
+    """How often each kernel family is launched: {(function, family): count}; the family of a wd_gemm launch is its kernel
+    (wd_gemm_check_kernel, without tile, K cut and options), that of a wd_ff_fused launch its whole form, else the function alone."""
+    out = {}
+    for _section, name, _what, form in sig:
+        key = (name, form.split(" ")[0] if name == "wd_gemm" else form)
+        out[key] = out.get(key, 0) + 1
+    return out
+
+
 def _keyed(sig) -> dict:
     """(section, what, occurrence) -> (function, form), in plan order: a ``what`` may repeat (one word_emb chain per token group)."""
     out, seen = {}, {}

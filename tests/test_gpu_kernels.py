@@ -938,7 +938,8 @@ def test_noise_images_and_ema_exact():
 
 
 @pytest.mark.parametrize("B,hw,c,heads,L", [(3, 256, 320, 4, 10), (2, 70, 320, 4, 10), (2, 32, 64, 4, 7), (2, 64, 64, 2, 10),
-                                            (2, 48, 320, 8, 5), (2, 20, 64, 2, 5), (1, 5, 320, 4, 9)])
+                                            (2, 48, 320, 8, 5), (2, 20, 64, 2, 5), (1, 5, 320, 4, 9),
+                                            (2, 70, 320, 1, 10), (2, 70, 320, 2, 10)])  # (d = 320 / 160: --num_heads 1 / 2)
 def test_folded_cross_attention(B, hw, c, heads, L):
     """wd_xattn_fold + wd_xattn_fused == x + to_out(attention(to_q(LN(x)), K, V)) (unet.py:164-279,337-345) and the LayerNorm
     that follows, against fp64 torch."""

@@ -141,17 +141,29 @@ def test_fused_transformer_launch_equals_the_chain(B):
     operations on the same operands: output, next-GroupNorm statistics and the tok2 residual agree to max_rel 1e-5 (measured:
     up to 3.3e-6 - last-bit differences of the fp32 LayerNorm / softmax code as compiled into the two kernels, amplified by the
     peaked softmax of these random folds; not bit-identical); a second launch gives the same bits."""
-    blk = _Block(B)
+    _fused_equals_the_chain(_Block(B))
+
+
+def _fused_equals_the_chain(blk):
+    B = blk.B
     ref_out, ref_stat, ref_tok2 = blk.chain()
     out, stat, tok2 = blk.fused()
     assert torch.isfinite(out).all() and torch.isfinite(stat).all()
     assert max_rel(tok2.cpu(), ref_tok2.cpu()) <= 1e-5
     assert max_rel(out.cpu(), ref_out.cpu()) <= 1e-5
     assert max_rel(stat.cpu(), ref_stat.cpu()) <= 2e-6
-    print(f"B={B}: out bit-identical {torch.equal(out, ref_out)}, stat_part bit-identical {torch.equal(stat, ref_stat)}, "
-          f"max_rel out {max_rel(out.cpu(), ref_out.cpu()):.3g}")
+    print(f"B={B} heads={blk.heads} L={blk.L}: out bit-identical {torch.equal(out, ref_out)}, stat_part bit-identical "
+          f"{torch.equal(stat, ref_stat)}, max_rel out {max_rel(out.cpu(), ref_out.cpu()):.3g}")
     out2, stat2, tok22 = blk.fused()
     assert torch.equal(out, out2) and torch.equal(stat, stat2) and torch.equal(tok2, tok22)
+
+
+@pytest.mark.parametrize("heads,L", [(1, 10), (2, 10), (8, 5)])
+def test_fused_transformer_launch_equals_the_chain_at_other_head_counts(heads, L):
+    """The same comparison with d = 320 / 160 / 40 (--num_heads 1 / 2 / 8; eight heads fold with at most 5 keys: heads * L <= 40), at
+    the smallest m of the test above.  (The fold these launches read is held to fp64 at these head counts by
+    test_gpu_kernels.py::test_folded_cross_attention.)"""
+    _fused_equals_the_chain(_Block(4, heads=heads, L=L))
 
 
 def test_fused_transformer_refuses_what_it_does_not_cover():

@@ -10,90 +10,15 @@ The reference is ``oracle.unet_oracle`` in float64 under torch autograd on the C
 filled, the zero-initialised convolutions too, so that the backward pass is not silenced).  Gradients are held to the bound of
 test_gpu_model.py's gradient tests, per parameter: ||g - ref|| < 2e-4 ||ref|| + 1e-7."""
 import collections
-import functools
 
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import ddpm_oracle as D  # noqa: E402
-from oracle import unet_oracle as U  # noqa: E402
-from tests._common import FULL, make_args, max_rel  # noqa: E402
-from worddiffusion_amd import Diffusion, UNetModel, UNetModelPhosc  # noqa: E402
-from worddiffusion_amd.synthetic import fill_module_, synthetic_inputs, synthetic_tensor  # noqa: E402
-
-DEV = "cuda:0"
-CFGS = {"FULL": FULL}
-
-
-def case_inputs(cfg_name, B, hw, phosc_len, seeds, noised=False):
-    """(model input x, synthetic_inputs batch, eps) for seeds = (model, inputs, eps).  noised: x = noise_images(x0, t, eps) in
-    fp32, the first launch of TrainStep's graph (wd_noise_images, bit-identical to it: test_noise_images_and_ema_exact)."""
-    cfg = CFGS[cfg_name]
-    inp = synthetic_inputs(B, seed=seeds[1], hw=hw, num_classes=cfg["num_classes"], phosc_len=phosc_len)
-    eps = torch.from_numpy(np.random.RandomState(seeds[2]).standard_normal(tuple(inp["x"].shape)).astype(np.float32))
-    x = inp["x"]
-    if noised:
-        x = D.noise_images(D.schedule(1000)[2], x, inp["t"], eps)
-    return x, inp, eps
-
-
-@functools.lru_cache(maxsize=2)
-def reference64(cfg_name, variant, B, hw, phosc_len, seeds, noised=False):
-    """float64 oracle forward -> MSE -> autograd: (pred, loss, {name: grad}) of the parameters the loss reaches."""
-    cfg = CFGS[cfg_name]
-    x, inp, eps = case_inputs(cfg_name, B, hw, phosc_len, seeds, noised)
-    sd = {k: torch.from_numpy(synthetic_tensor(k, s, seeds[0])).double().requires_grad_(True)
-          for k, s in U.state_dict_shapes(cfg, variant)}
-    orc = U.UNetOracle(cfg, sd, variant, phosc_len > 0)
-    pred = orc(x.double(), inp["t"], inp["context"], inp["y"], inp.get("phosc"))
-    loss = torch.nn.functional.mse_loss(pred, eps.double())
-    loss.backward()
-    return pred.detach(), float(loss.detach()), {k: v.grad for k, v in sd.items() if v.grad is not None}
-
-
-def check_against_reference(pred, loss, grads, ref, label):
-    """Per-sample prediction (max_rel < 5e-5), loss (1e-5 relative), the set of parameters with a gradient, every gradient."""
-    pred_ref, loss_ref, gref = ref
-    pred = pred.detach().cpu().double()
-    assert pred.shape == pred_ref.shape
-    worst_pred = max(max_rel(pred[b], pred_ref[b]) for b in range(pred.shape[0]))
-    assert worst_pred < 5e-5, [b for b in range(pred.shape[0]) if max_rel(pred[b], pred_ref[b]) >= 5e-5]
-    assert abs(loss - loss_ref) <= 1e-5 * abs(loss_ref), (loss, loss_ref)
-    assert set(grads) == set(gref), sorted(set(grads) ^ set(gref))[:10]
-    worst, bad = ("", 0.0), []
-    for k, r in gref.items():
-        g = grads[k].detach().cpu().double()
-        assert tuple(g.shape) == tuple(r.shape), k
-        err, rn = float((g - r).norm()), float(r.norm())
-        if rn > 1e-6 and err / rn > worst[1]:
-            worst = (k, err / rn)
-        if not err < 2e-4 * rn + 1e-7:  # (a few gradients are analytically ~0: absolute floor)
-            bad.append((k, err, rn))
-    print(f"{label}: worst per-sample prediction error {worst_pred:.2e}, worst relative gradient error {worst[1]:.2e} ({worst[0]})")
-    assert not bad, f"{len(bad)} gradients off the reference: {bad[:8]}"
-
-
-def train_model(variant, phosc_on, seed):
-    cls = UNetModel if variant == "base" else UNetModelPhosc
-    m = cls(args=make_args(device=DEV, phosc=1 if phosc_on else 0), **FULL)
-    fill_module_(m, seed)
-    return m.to(DEV).train()
-
-
-def train_call(m, variant, x, inp, eps, phosc_len):
-    """model(...) in train mode -> MSELoss -> loss.backward() (train.py:287-291): (pred, loss, {name: grad})."""
-    kw = dict(timesteps=inp["t"].to(DEV), context=inp["context"].to(DEV), y=inp["y"].to(DEV))
-    if variant == "base":
-        pred = m(x.to(DEV), **kw)
-    else:
-        pred = m(x.to(DEV), inp["phosc"].to(DEV) if phosc_len else None, **kw)
-    loss = torch.nn.MSELoss()(eps.to(DEV), pred)
-    loss.backward()
-    torch.cuda.synchronize()
-    return pred, float(loss.detach()), {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+from tests._common import FULL, make_args  # noqa: E402
+from tests._train_ref import DEV, case_inputs, check_against_reference, reference64, train_call, train_model  # noqa: E402
+from worddiffusion_amd import Diffusion  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------ TrainStep at the benchmark shape
@@ -104,8 +29,8 @@ def test_train_step_gradients_at_the_benchmark_shape():
     from worddiffusion_amd.optim import FusedAdamW
     from worddiffusion_amd.training import TrainStep
     seeds = (0, 7, 11)
-    x0, inp, eps = case_inputs("FULL", 64, (8, 32), 0, seeds)
-    m = train_model("base", False, seeds[0])
+    x0, inp, eps = case_inputs(FULL, 64, (8, 32), 0, seeds)
+    m = train_model(FULL, "base", False, seeds[0])
     opt = FusedAdamW(m.parameters(), lr=0.0)
     step = TrainStep(m, Diffusion(noise_steps=1000, img_size=(64, 256), args=make_args(device=DEV)), opt, seed=99, use_graph=True)
     before = {k: v.detach().clone() for k, v in m.state_dict().items()}
@@ -114,7 +39,7 @@ def test_train_step_gradients_at_the_benchmark_shape():
     torch.cuda.synchronize()
     pred = step._P.out.cpu()
     grads = {k: g.clone() for k, g in step.eng.grads().items()}
-    check_against_reference(pred, loss, grads, reference64("FULL", "base", 64, (8, 32), 0, seeds, noised=True),
+    check_against_reference(pred, loss, grads, reference64(FULL, "base", 64, (8, 32), 0, seeds, noised=True),
                             "TrainStep FULL base B=64 (8, 32)")
     for k, v in m.state_dict().items():
         assert torch.equal(v, before[k]), f"{k}: lr = 0 moved the parameter"
@@ -134,10 +59,10 @@ def test_train_step_gradients_at_the_benchmark_shape():
 ])
 def test_training_gradients_at_the_edges(variant, B, hw, phosc_len):
     seeds = (55, 100 + B, 3)
-    x, inp, eps = case_inputs("FULL", B, hw, phosc_len, seeds)
-    m = train_model(variant, phosc_len > 0, seeds[0])
+    x, inp, eps = case_inputs(FULL, B, hw, phosc_len, seeds)
+    m = train_model(FULL, variant, phosc_len > 0, seeds[0])
     pred, loss, grads = train_call(m, variant, x, inp, eps, phosc_len)
-    check_against_reference(pred, loss, grads, reference64("FULL", variant, B, hw, phosc_len, seeds),
+    check_against_reference(pred, loss, grads, reference64(FULL, variant, B, hw, phosc_len, seeds),
                             f"FULL {variant} B={B} {hw} phosc_len={phosc_len}")
 
 
@@ -180,14 +105,14 @@ def test_training_engine_switches(switch, monkeypatch):
     if switch is not None:
         monkeypatch.setenv(*switch)  # (before the model's train_engine exists: the switches are read when it is built)
     seeds = (31, 8, 9)
-    x, inp, eps = case_inputs("FULL", 8, (8, 32), 0, seeds)
-    m = train_model("base", False, seeds[0])
+    x, inp, eps = case_inputs(FULL, 8, (8, 32), 0, seeds)
+    m = train_model(FULL, "base", False, seeds[0])
     pred, loss, grads = train_call(m, "base", x, inp, eps, 0)
     plans = list(m.train_engine._tplans.values())
     assert len(plans) == 1
     facts = plan_facts(plans[0])
     assert SWITCHES[switch](*facts), facts
-    check_against_reference(pred, loss, grads, reference64("FULL", "base", 8, (8, 32), 0, seeds), f"switch {switch}")
+    check_against_reference(pred, loss, grads, reference64(FULL, "base", 8, (8, 32), 0, seeds), f"switch {switch}")
 
 
 # ------------------------------------------------------------------------------------------ optimiser kernels at their edges

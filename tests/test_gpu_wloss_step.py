@@ -15,7 +15,7 @@ from oracle import ddpm_oracle as D  # noqa: E402
 from oracle import unet_oracle as U  # noqa: E402
 from tests._common import FULL, make_args  # noqa: E402
 from tests._wloss_ref import ulp_distance  # noqa: E402
-from tests.test_gpu_training import case_inputs, train_model  # noqa: E402
+from tests._train_ref import case_inputs, train_model  # noqa: E402
 from worddiffusion_amd import Diffusion  # noqa: E402
 from worddiffusion_amd.latents import loss_mask_columns  # noqa: E402
 from worddiffusion_amd.optim import FusedAdamW, weighted_mse_loss  # noqa: E402
@@ -55,7 +55,7 @@ def other_mask():
 
 
 def inputs():
-    x0, inp, eps = case_inputs("FULL", B, HW, 0, SEEDS)
+    x0, inp, eps = case_inputs(FULL, B, HW, 0, SEEDS)
     return x0, inp, eps
 
 
@@ -92,7 +92,7 @@ class Recorder:
 
 
 def make_step(record=False, **kw):
-    m = train_model("base", False, SEEDS[0])
+    m = train_model(FULL, "base", False, SEEDS[0])
     step = TrainStep(m, diffusion(), FusedAdamW(m.parameters(), lr=0.0), seed=99, **kw)
     if record:
         step.lib = Recorder(step.lib)
@@ -227,7 +227,7 @@ def test_alternating_masked_and_unmasked_calls():
 # ------------------------------------------------------------------------------------------------------------- G8
 def test_eval_loss_is_the_eval_forward_and_leaves_the_model_alone():
     x0, inp, eps = inputs()
-    m = train_model("base", False, SEEDS[0])
+    m = train_model(FULL, "base", False, SEEDS[0])
     diff = diffusion()
     before = {k: v.detach().clone() for k, v in m.state_dict().items()}
     args = (x0.to(DEV), inp["context"].to(DEV), inp["y"].to(DEV))

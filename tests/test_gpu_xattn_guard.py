@@ -87,9 +87,9 @@ def fold(o, B, c, heads, L):
                 mot_pl=bufs["mot_pl"][1].view(B, 2, XHJ * c), keep=(bufs, kv, wq, wo))
 
 
-# (c, heads, L, hw): heads * L = 1, 16, 17, 32, 33, 40, 40 and two more token counts
+# (c, heads, L, hw): heads * L = 1, 16, 17, 32, 33, 40, 40, two more token counts, and d = 160 at the model's 10 keys (--num_heads 2)
 SHAPES = [(64, 1, 1, 1), (64, 4, 4, 15), (64, 1, 17, 16), (64, 2, 16, 17), (320, 1, 33, 70), (320, 4, 10, 17), (320, 8, 5, 16),
-          (64, 4, 4, 70), (320, 4, 10, 1)]
+          (64, 4, 4, 70), (320, 4, 10, 1), (320, 2, 10, 17)]
 
 
 @pytest.mark.parametrize("c,heads,L,hw", SHAPES[:7])

@@ -874,6 +874,8 @@ class UNetEngine:
         cpg = ctot // 32
         has_perm = any(s.perm is not None for s in srcs)
         if has_perm and not (len(srcs) == 2 and srcs[1].perm is None and self.fuse_gn2 and not any(s.c % cpg for s in srcs)):
+            # (not reachable from a constructor argument: _resample plans the phase form only where _phase_map_readable says this
+            # GroupNorm takes it)
             raise NotImplementedError(f"{what}: a phase-major map (Upsample) is read by the two-source GroupNorm of a decoder block only")
         if any(s.c % cpg for s in srcs):
             # groups straddle the concat boundary: materialise the concat (never the case at 320+320 channels)
@@ -1031,7 +1033,18 @@ class UNetEngine:
         return (getattr(self, "use_up_phases", False) and self.use_wdirect and self.fuse_gn2 and self.npass == 3 and not self.use_slab and
                 not self.use_conv3)
 
-    def _resample(self, P, name, mod, x: Act, mode: str, tile: int = 0) -> Act:
+    def _phase_map_readable(self, cout: int, cskip: Optional[int]) -> bool:
+        """Can the consumer of an Upsample's output read it phase-major?  Only the two-source GroupNorm launch of the decoder block
+        behind it does (wd_gn_apply2 with a row permutation, ``_gn``): the block normalises [Upsample output | skip of ``cskip``
+        channels], and no group of cout + cskip channels may straddle the concat (320 + 320 does not; 640 + 320 has groups of 30)."""
+        if cskip is None or not self.fuse_gn2:
+            return False
+        cpg = (cout + cskip) // 32
+        return cpg > 0 and cout % cpg == 0 and cskip % cpg == 0
+
+    def _resample(self, P, name, mod, x: Act, mode: str, tile: int = 0, cskip: Optional[int] = None) -> Act:
+        """cskip (mode 'up'): the channels of the skip map that the next decoder block concatenates behind this Upsample's output
+        (None: no such block) - the phase-major form is planned only where that block's GroupNorm reads it (``_phase_map_readable``)."""
         ops = P.step
         B = self._B
         assert x.perm is None, name
@@ -1048,7 +1061,8 @@ class UNetEngine:
         out = self._f32(P, B * ho * wo, mod.cout)
         hw = x.h * x.w
         src4 = None
-        if mode == "up" and tile == 0 and (name + ".wph0") in self._w and self._up_phases_ok(mod) and wdirect_fills_chip(B * 4 * hw, mod.cout):
+        if (mode == "up" and tile == 0 and (name + ".wph0") in self._w and self._up_phases_ok(mod) and
+                self._phase_map_readable(mod.cout, cskip) and wdirect_fills_chip(B * 4 * hw, mod.cout)):
             # four 2x2 convolutions of the source map, one per output phase: 4 taps instead of 9, the weight image picked per tile;
             # the rows of a sample come out phase-major (Act.perm: the decoder block's GroupNorm reads them in raster order)
             key = (x.h, x.w, "up4")
@@ -1530,7 +1544,8 @@ class UNetEngine:
         m = self.model
         hs = [cur]
 
-        def run_layers(prefix, blk, cur, extra=None):
+        def run_layers(prefix, blk, cur, extra=None, cskip=None):
+            """extra: the skip map the block's first ResBlock concatenates; cskip: the channels of the skip map the NEXT block will."""
             for j, mod in enumerate(blk):
                 name = f"{prefix}.{j}"
                 if isinstance(mod, ResBlockParams):
@@ -1540,7 +1555,7 @@ class UNetEngine:
                 elif isinstance(mod, DownsampleParams):
                     cur = self._resample(P, name, mod, cur, "down")
                 elif isinstance(mod, UpsampleParams):
-                    cur = self._resample(P, name, mod, cur, "up")
+                    cur = self._resample(P, name, mod, cur, "up", cskip=cskip if j == len(blk) - 1 else None)
                 else:
                     raise TypeError(type(mod))
             return cur
@@ -1552,7 +1567,8 @@ class UNetEngine:
             hs.append(cur)
         cur = run_layers("mid", m.middle_block, cur)
         for i, blk in enumerate(m.output_blocks):
-            cur = run_layers(f"out{i}", blk, cur, extra=hs.pop())
+            extra = hs.pop()
+            cur = run_layers(f"out{i}", blk, cur, extra=extra, cskip=hs[-1].c if hs else None)
         return cur
 
     def _tail_gemm(self, P: Plan, ops, what, x: Act, eps, nchw: Optional[torch.Tensor] = None):

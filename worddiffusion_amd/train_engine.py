@@ -706,7 +706,9 @@ class TrainEngine(UNetEngine):
         self._bs.tape.append(bwd)
         return out
 
-    def _resample(self, P, name, mod, x: TAct, mode: str) -> TAct:
+    def _resample(self, P, name, mod, x: TAct, mode: str, cskip: Optional[int] = None) -> TAct:
+        """(cskip: what ``_trunk`` tells the inference planner about the Upsample's consumer - the training forward always runs the
+        9-tap form, whose output is in raster order.)"""
         ops = P.step
         B = self._B
         tab, ho, wo = self._table(x.h, x.w, mode)
