@@ -140,9 +140,11 @@ def release(engine):
     torch.cuda.empty_cache()
 
 
-def signature_at(engine, B, phosc_len=0, h=8, w=32, ctx_len=10) -> tuple:
-    """The signature of the forward's plan at batch ``B`` (plans only: nothing but ``refresh_weights`` launches); the plan is released."""
+def signature_at(engine, B, phosc_len=0, h=8, w=32, ctx_len=10, planner=None) -> tuple:
+    """The signature of the plan at batch ``B`` (plans only: nothing but ``refresh_weights`` launches); the plan is released.
+    ``planner`` is the planner call, ``planner(B, h, w)`` -> Plan: ``engine.plan_decode`` (h, w of the latents) or ``engine.plan_encode``
+    (h, w of the images) of a VAE engine; without it the forward's ``engine.plan(B, h, w, ctx_len, phosc_len)``."""
     engine.refresh_weights()
-    sig = signature(engine, engine.plan(B, h, w, ctx_len, phosc_len))
+    sig = signature(engine, planner(B, h, w) if planner is not None else engine.plan(B, h, w, ctx_len, phosc_len))
     release(engine)
     return sig
