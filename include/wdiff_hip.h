@@ -111,7 +111,11 @@ typedef struct wd_gemm_args {
                            * (sample, 128-row chunk, channel group): GroupNorm statistics for the consumer (wd_gn_apply),
                            * nchunk = max(1, hw_out / 128).  Needs 128-row tiles, hw_out | 128 or 128 | hw_out, whole
                            * groups per column tile, the vector epilogue (out_ld, rowvec_ld, resid_ld, out_pl_ld multiples of 4;
-                           * bias, rowvec, resid, out_f32 16-byte and out_hi / out_lo 8-byte aligned); not with GEGLU */
+                           * bias, rowvec, resid, out_f32 16-byte and out_hi / out_lo 8-byte aligned); not with GEGLU.
+                           * Accuracy (every producer of such partials: this epilogue, the combine launch, tile 64080, wd_ff_fused,
+                           * wd_conv3x3_in): var = sumsq / n - mean^2 formed from them in double is within ~1e-7 of the variance
+                           * of the fp32 values for any mean / std of a group (measured <= 1e-7 up to 256) - no fp32 stage sums
+                           * the values or their squares unshifted (csrc/wd_gemm_epi.h, WdStatAcc) */
     int32_t stat_cpg;     /* channels per statistics group */
     int32_t dbg;          /* 0 in production.  0x400: take the two-workgroups-per-CU kernel (wd_gemm4_kernel) wherever it is
                              legal, whatever the grid size (parity tests); 0x8000 / 0x10000: the 64 x 320 weights-to-registers
@@ -280,7 +284,10 @@ int wd_gemm_experimental(void);
 
 /* GroupNorm statistics, unet.py:427-431 (eps 1e-5) and :161-162 (eps 1e-6).  x: [B*hw][ld] fp32 with c channels in
  * groups of cpg.  Writes per (sample, chunk, group) partial (sum, sumsq) in double: part[((b*nchunk + j)*(c/cpg) + g)*2],
- * nchunk = wd_gn_nchunk(hw).  (wd_gemm can produce the same array in its epilogue: wd_gemm_args.stat_part.) */
+ * nchunk = wd_gn_nchunk(hw).  (wd_gemm can produce the same array in its epilogue: wd_gemm_args.stat_part.)
+ * Accuracy: the partials are the sum and the sum of squares of the fp32 values to double rounding (every stage in double; the
+ * square of an fp32 value is exact there), so the consumers' var = sumsq / n - mean^2 loses nothing to the producer at any
+ * mean / std of a group - tests/test_gpu_norm_offset.py runs it to 256. */
 int wd_gn_nchunk(int hw);
 int wd_gn_stats(const float* x, int ld, int batch, int hw, int c, int cpg, double* part, void* stream);
 /* part[batch][nchunk][ngroups][2] -> out[batch][1][ngroups][2] (fixed-order sum over the chunks): lets wd_gn_apply run with

@@ -28,6 +28,54 @@ __host__ __device__ __forceinline__ bool wd_epilogue_vec_ok(const wd_gemm_args& 
            (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0);
 }
 
+// Fused GroupNorm statistics, the accuracy rule: a producer's (sum, sum of squares) partials leave var = sumsq / n - mean^2,
+// formed in double by the consumers, accurate to ~1e-7 of the variance however far the group's mean is from zero.  (Plain fp32
+// sums anywhere are off by 2^-24 of the sum of squares, which that difference multiplies by (mean / std)^2: 2.4e-4 at 64.)
+// A thread's rows, the only stage with one step per row, stay in fp32 but are summed as d = v - pivot, the pivot being the first
+// value the thread saw in that column of that sample: d is exact for values within a factor two of the pivot (Sterbenz) and of
+// the size of the spread, not of the mean, so the fp32 roundings of sum(d) and sum(d^2) are relative to the spread.  wd_stat_finish
+// turns them into the plain sums in double (n p + S, n p^2 + 2 p S + Q); every later stage - the LDS hand-over, the sums over a
+// group's columns and over the row lanes - is in double.
+struct WdStatAcc {
+    float4 p, s, q;  // pivot, sum (v - p), sum (v - p)^2
+    int n;           // rows summed
+};
+__device__ __forceinline__ void wd_stat_reset(WdStatAcc& t) {
+    t.p = t.s = t.q = make_float4(0.f, 0.f, 0.f, 0.f);
+    t.n = 0;
+}
+__device__ __forceinline__ void wd_stat_add(WdStatAcc& t, const float4& v) {
+    if (t.n == 0) t.p = v;
+    const float4 d = make_float4(v.x - t.p.x, v.y - t.p.y, v.z - t.p.z, v.w - t.p.w);
+    t.s.x += d.x; t.s.y += d.y; t.s.z += d.z; t.s.w += d.w;
+    t.q.x += d.x * d.x; t.q.y += d.y * d.y; t.q.z += d.z * d.z; t.q.w += d.w * d.w;
+    ++t.n;
+}
+__device__ __forceinline__ void wd_stat_finish(const WdStatAcc& t, double (&su)[4], double (&sq)[4]) {
+    const float p[4] = {t.p.x, t.p.y, t.p.z, t.p.w}, s[4] = {t.s.x, t.s.y, t.s.z, t.s.w}, q[4] = {t.q.x, t.q.y, t.q.z, t.q.w};
+    const double n = (double)t.n;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double pj = (double)p[j], sj = (double)s[j];
+        su[j] = n * pj + sj;
+        sq[j] = n * pj * pj + 2.0 * pj * sj + (double)q[j];
+    }
+}
+
+// scr[sample][row lane][bn]: (sample, group, row lane) -> the sum over the group's columns, written over the group's first column
+template <int NT>
+__device__ __forceinline__ void wd_stat_reduce(double* scr, const int ns, const int nrl, const int ngt, const int bn, const int cpg,
+                                               const int tid) {
+    for (int it = tid; it < ns * ngt * nrl; it += NT) {
+        const int l = it % nrl, g = (it / nrl) % ngt, sidx2 = it / (nrl * ngt);
+        double* p = scr + (long)(sidx2 * nrl + l) * bn + g * cpg;
+        double su = 0.0;
+        for (int cc = 0; cc < cpg; ++cc) su += p[cc];
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): every read of this group's span precedes the write-back
+        p[0] = su;
+    }
+}
+
 // WS: the tile's values are not in the LDS image but still spread over the split-K slabs of a.ws - the combine pass sums them
 // here, row by row in the thread's own (row lane, column quad) pattern, instead of staging the sums through LDS first (the
 // statistics scratch behind the image position is used as usual).  Vector path only; the caller checks.
@@ -79,8 +127,13 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
         // more than the rest of a row's work.)
         const int rps_sh = 31 - __clz(rps);
         const int hw_sh = (a.hw_out & (a.hw_out - 1)) == 0 ? 31 - __clz(a.hw_out) : -1;
-        float* scr = ep + BM * LDE;               // statistics scratch [sample][row lane][BN][2]
-        float4 ssum = make_float4(0.f, 0.f, 0.f, 0.f), ssq = ssum;
+        // statistics: a thread's column sums and sums of squares (WdStatAcc) of the sample it is in.  WD_STAT_MAXNS == 2 and rows
+        // ascend, so `cur_s` only ever steps from 0 to 1: the finished sample's fp32 state is then parked in this thread's own two
+        // slots of the scratch (32 bytes each, read and written by no other thread before the barrier below) - nothing but `st`
+        // stays live across the row loop, whose loads in flight need the registers.
+        WdStatAcc st;
+        wd_stat_reset(st);
+        float* park = ep + BM * LDE + 2 * ((long)rl * BN + c);  // slot of sample 0; sample 1's is 2 * nrl * BN floats on
         int cur_s = 0;
         if (rl < nrl && no < nout) {
             float4 bx = make_float4(0, 0, 0, 0), bg = bx;
@@ -127,16 +180,15 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
                 }
                 if (stats) {
                     const int sidx2 = row >> rps_sh;
-                    if (sidx2 != cur_s) {  // rows ascend: flush the finished sample's column sums
-                        float* o = scr + ((cur_s * nrl + rl) * BN + c) * 2;
-                        *reinterpret_cast<float4*>(o) = make_float4(ssum.x, ssq.x, ssum.y, ssq.y);
-                        *reinterpret_cast<float4*>(o + 4) = make_float4(ssum.z, ssq.z, ssum.w, ssq.w);
-                        ssum = make_float4(0.f, 0.f, 0.f, 0.f);
-                        ssq = ssum;
+                    if (sidx2 != cur_s) {  // rows ascend: set the finished sample's column sums aside
+                        *reinterpret_cast<float4*>(park) = st.p;
+                        *reinterpret_cast<float4*>(park + 4) = st.s;
+                        *reinterpret_cast<float4*>(park + 2 * nrl * BN) = st.q;
+                        park[2 * nrl * BN + 4] = __int_as_float(st.n);
+                        wd_stat_reset(st);
                         cur_s = sidx2;
                     }
-                    ssum.x += v.x; ssum.y += v.y; ssum.z += v.z; ssum.w += v.w;
-                    ssq.x += v.x * v.x; ssq.y += v.y * v.y; ssq.z += v.z * v.z; ssq.w += v.w * v.w;
+                    wd_stat_add(st, v);
                 }
                 if (a.ln_gamma) {  // the row LayerNorm below reads the finished values back from the image
                     if constexpr (!WS) *reinterpret_cast<float4*>(ep + row * LDE + c) = v;
@@ -164,14 +216,63 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
             }
         }
         if (stats) {
-            // flush the running sample and zero-fill the (sample, row lane) slots this thread never reached
+            // ---- GroupNorm partial statistics of the finished tile: (sample in panel, group) = fixed-order sum over the group's
+            // columns, then over the row lanes, of the per-thread column sums (host guarantees the vector path, BN % cpg == 0,
+            // n % cpg == 0, and that BM and hw_out divide one another).  Everything stays in double: the scratch behind the image
+            // holds [quantity][sample][row lane][BN] doubles - the sums and the sums of squares together where that fits (one
+            // sample per panel, or 256 threads), else the sums go through it first and the sums of squares second.
             const int ns = BM > a.hw_out ? BM / a.hw_out : 1;
-            if (rl < nrl && c < BN) {
-                for (int s2 = cur_s; s2 < ns; ++s2) {
-                    float* o = scr + ((s2 * nrl + rl) * BN + c) * 2;
-                    const bool cur = (s2 == cur_s);
-                    *reinterpret_cast<float4*>(o) = cur ? make_float4(ssum.x, ssq.x, ssum.y, ssq.y) : make_float4(0, 0, 0, 0);
-                    *reinterpret_cast<float4*>(o + 4) = cur ? make_float4(ssum.z, ssq.z, ssum.w, ssq.w) : make_float4(0, 0, 0, 0);
+            double ssum[4] = {0.0, 0.0, 0.0, 0.0}, ssq[4] = {0.0, 0.0, 0.0, 0.0};  // the last sample of the panel
+            double s0[4] = {0.0, 0.0, 0.0, 0.0}, q0[4] = {0.0, 0.0, 0.0, 0.0};      // sample 0 of two
+            if (cur_s == 0 && ns > 1) {
+                wd_stat_finish(st, s0, q0);  // this thread never reached sample 1: its running sums are sample 0's
+            } else {
+                wd_stat_finish(st, ssum, ssq);
+                if (cur_s != 0) {  // (only with ns > 1, and then rl < nrl && c < BN: the parked slots are inside the scratch)
+                    WdStatAcc pv;
+                    pv.p = *reinterpret_cast<const float4*>(park);
+                    pv.s = *reinterpret_cast<const float4*>(park + 4);
+                    pv.q = *reinterpret_cast<const float4*>(park + 2 * nrl * BN);
+                    pv.n = __float_as_int(park[2 * nrl * BN + 4]);
+                    wd_stat_finish(pv, s0, q0);
+                }
+            }
+            const int cpg = a.stat_cpg;
+            const int ngt = BN / cpg;
+            const int nchunk = a.hw_out > BM ? a.hw_out / BM : 1;
+            const int ngs = a.n / cpg;  // groups per sample in the statistics array of this tensor
+            double* scr = reinterpret_cast<double*>(ep + BM * LDE);  // (BM * LDE * 4 is a multiple of 16)
+            const int nq = 2 * ns * nrl * BN * (int)sizeof(double) <= WD_STAT_SCRATCH ? 2 : 1;  // quantities per pass
+            for (int q0i = 0; q0i < 2; q0i += nq) {
+                if (q0i) __syncthreads();
+                if (rl < nrl && c < BN) {
+                    for (int qq = 0; qq < nq; ++qq) {
+                        const bool sq = q0i + qq;
+                        const double* lo = ns > 1 ? (sq ? q0 : s0) : (sq ? ssq : ssum);
+                        double* o = scr + ((long)(qq * ns) * nrl + rl) * BN + c;
+                        *reinterpret_cast<double2*>(o) = make_double2(lo[0], lo[1]);
+                        *reinterpret_cast<double2*>(o + 2) = make_double2(lo[2], lo[3]);
+                        if (ns > 1) {
+                            const double* hi = sq ? ssq : ssum;
+                            o += nrl * BN;
+                            *reinterpret_cast<double2*>(o) = make_double2(hi[0], hi[1]);
+                            *reinterpret_cast<double2*>(o + 2) = make_double2(hi[2], hi[3]);
+                        }
+                    }
+                }
+                __syncthreads();
+                wd_stat_reduce<NT>(scr, nq * ns, nrl, ngt, BN, cpg, tid);
+                __syncthreads();
+                // (quantity, sample, group) -> sum over the row lanes in fixed order
+                for (int it = tid; it < nq * ns * ngt; it += NT) {
+                    const int g = it % ngt, qs = it / ngt, sidx2 = qs % ns, qq = qs / ns;
+                    const int mrow = m0 + sidx2 * rps;
+                    if (mrow >= a.m || n0 + g * cpg >= a.n) continue;
+                    double su = 0.0;
+                    for (int l = 0; l < nrl; ++l) su += scr[(long)(qs * nrl + l) * BN + g * cpg];
+                    const int b = mrow / a.hw_out;
+                    const int chunk = (mrow - b * a.hw_out) / BM;
+                    a.stat_part[(((long)b * nchunk + chunk) * ngs + n0 / cpg + g) * 2 + q0i + qq] = su;
                 }
             }
         }
@@ -220,53 +321,6 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
                 *reinterpret_cast<uint2*>(a.out_hi + (long)m * a.out_pl_ld + c) = hh;
                 if (a.out_lo) *reinterpret_cast<uint2*>(a.out_lo + (long)m * a.out_pl_ld + c) = ll;
             }
-        }
-    }
-    if (!stats) return;
-    // ---- GroupNorm partial statistics of the finished tile: (sample in panel, group) = fixed-order sum over the
-    // row lanes and the group's columns of the per-thread column sums above (host guarantees the vector path, BN % cpg
-    // == 0, n % cpg == 0, and that BM and hw_out divide one another).
-    __syncthreads();
-    {
-        const int cpg = a.stat_cpg;
-        const int ns = BM > a.hw_out ? BM / a.hw_out : 1;
-        const int rps = BM > a.hw_out ? a.hw_out : BM;
-        const int ngt = BN / cpg;
-        const int nrl = NT / oc4;
-        const float* scr = ep + BM * LDE;
-        const int nchunk = a.hw_out > BM ? a.hw_out / BM : 1;
-        const int ngs = a.n / cpg;  // groups per sample in the statistics array of this tensor
-        // level 1: (sample, group, row lane) -> sum over the group's columns, written back over the lane's first slot
-        float* scw = ep + BM * LDE;
-        for (int it = tid; it < ns * ngt * nrl; it += NT) {
-            const int l = it % nrl, g = (it / nrl) % ngt, sidx2 = it / (nrl * ngt);
-            const float* p = scr + ((sidx2 * nrl + l) * BN + g * cpg) * 2;
-            float su = 0.f, sq = 0.f;
-            for (int cc = 0; cc < cpg; ++cc) {
-                su += p[2 * cc];
-                sq += p[2 * cc + 1];
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): every read of this group's span precedes the write-back
-            scw[((sidx2 * nrl + l) * BN + g * cpg) * 2] = su;
-            scw[((sidx2 * nrl + l) * BN + g * cpg) * 2 + 1] = sq;
-        }
-        __syncthreads();
-        // level 2: (sample, group) -> sum over the row lanes in fixed order
-        for (int it = tid; it < ns * ngt; it += NT) {
-            const int g = it % ngt, sidx2 = it / ngt;
-            const int mrow = m0 + sidx2 * rps;
-            if (mrow >= a.m || n0 + g * cpg >= a.n) continue;
-            double su = 0.0, sq = 0.0;
-            for (int l = 0; l < nrl; ++l) {
-                const float* p = scr + ((sidx2 * nrl + l) * BN + g * cpg) * 2;
-                su += (double)p[0];
-                sq += (double)p[1];
-            }
-            const int b = mrow / a.hw_out;
-            const int chunk = (mrow - b * a.hw_out) / BM;
-            double* o = a.stat_part + (((long)b * nchunk + chunk) * ngs + n0 / cpg + g) * 2;
-            o[0] = su;
-            o[1] = sq;
         }
     }
 }
@@ -333,7 +387,7 @@ __device__ __forceinline__ void wd_epilogue_tail(const wd_gemm_args& a, float* e
 // launch and its pass over the tensor disappear (ten of them on the 4x16 level of the base UNet).
 // WS = true: the values are summed from the split-K slabs of a.ws (the combine launch, 64 x 40 tiles of 256 threads); WS = false:
 // they are the finished fp32 image `img` (row pitch BN + 4) of a kernel that owns all of K (wd_gemmk_kernel, 64 x 80, 512 threads).
-// `ep`: scratch of NRL * BN * 2 floats + BN / stat_cpg doubles, not overlapping img.
+// `ep`: scratch of 2 * NRL * BN + 2 * BN / stat_cpg doubles (16-byte aligned), not overlapping img.
 template <int BN, int NT, bool WS>
 __device__ __forceinline__ void wd_gn_tile(const wd_gemm_args& a, const float* img, float* ep, const int m0, const int n0, const int tid) {
     constexpr int BM = 64, Q = BN / 4, NRL = NT / Q, KEEP = (BM + NRL - 1) / NRL;
@@ -366,7 +420,8 @@ __device__ __forceinline__ void wd_gn_tile(const wd_gemm_args& a, const float* i
     float4 bx = make_float4(0.f, 0.f, 0.f, 0.f), rv = bx;
     if (live && a.bias) bx = *reinterpret_cast<const float4*>(a.bias + no);
     if (live && a.rowvec) rv = *reinterpret_cast<const float4*>(a.rowvec + (long)(m0 / a.hw_out) * a.rowvec_ld + no);
-    float4 ssum = make_float4(0.f, 0.f, 0.f, 0.f), ssq = ssum;
+    WdStatAcc st;
+    wd_stat_reset(st);
 #pragma unroll
     for (int k = 0; k < KEEP; ++k) {
         if (!ok[k]) continue;
@@ -379,45 +434,33 @@ __device__ __forceinline__ void wd_gn_tile(const wd_gemm_args& a, const float* i
             const float4 q = *reinterpret_cast<const float4*>(a.resid + m * a.resid_ld + no);
             v[k].x += q.x; v[k].y += q.y; v[k].z += q.z; v[k].w += q.w;
         }
-        ssum.x += v[k].x; ssum.y += v[k].y; ssum.z += v[k].z; ssum.w += v[k].w;
-        ssq.x += v[k].x * v[k].x; ssq.y += v[k].y * v[k].y; ssq.z += v[k].z * v[k].z; ssq.w += v[k].w * v[k].w;
+        wd_stat_add(st, v[k]);
         if (a.out_f32) *reinterpret_cast<float4*>(a.out_f32 + m * a.out_ld + no) = v[k];
     }
-    // per-thread column sums -> (group, row lane) -> (group): the order of the ordinary combine
-    float* scr = ep;                                                  // [NRL][BN][2]
-    double* gs = reinterpret_cast<double*>(ep + NRL * BN * 2);        // [BN / stat_cpg][2]
-    if (live) {
-        float* o = scr + (rl * BN + c) * 2;
-        *reinterpret_cast<float4*>(o) = make_float4(ssum.x, ssq.x, ssum.y, ssq.y);
-        *reinterpret_cast<float4*>(o + 4) = make_float4(ssum.z, ssq.z, ssum.w, ssq.w);
-    }
-    __syncthreads();
+    double ssum[4], ssq[4];
+    wd_stat_finish(st, ssum, ssq);
+    // per-thread column sums -> (group, row lane) -> (group): the order and the arithmetic of the ordinary combine (all in double)
+    double* scr = reinterpret_cast<double*>(ep);    // [2][NRL][BN]: sums, sums of squares
+    double* gs = scr + 2 * NRL * BN;                 // [BN / stat_cpg][2]
     const int cps = a.stat_cpg, ngt = BN / cps;
-    for (int it = tid; it < ngt * NRL; it += NT) {
-        const int l = it % NRL, g = it / NRL;
-        const float* p = scr + (l * BN + g * cps) * 2;
-        float su = 0.f, sq = 0.f;
-        for (int cc = 0; cc < cps; ++cc) {
-            su += p[2 * cc];
-            sq += p[2 * cc + 1];
+    if (live) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const double* e = q ? ssq : ssum;
+            double* o = scr + (q * NRL + rl) * BN + c;
+            *reinterpret_cast<double2*>(o) = make_double2(e[0], e[1]);
+            *reinterpret_cast<double2*>(o + 2) = make_double2(e[2], e[3]);
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): every read of this group's span precedes the write-back
-        scr[(l * BN + g * cps) * 2] = su;
-        scr[(l * BN + g * cps) * 2 + 1] = sq;
     }
     __syncthreads();
-    if (tid < ngt && n0 + tid * cps < a.n) {
-        double su = 0.0, sq = 0.0;
-        for (int l = 0; l < NRL; ++l) {
-            const float* p = scr + (l * BN + tid * cps) * 2;
-            su += (double)p[0];
-            sq += (double)p[1];
-        }
-        gs[2 * tid] = su;
-        gs[2 * tid + 1] = sq;
-        double* o = a.stat_part + ((long)(m0 / a.hw_out) * (a.n / cps) + n0 / cps + tid) * 2;  // (one chunk per sample: hw_out == BM)
-        o[0] = su;
-        o[1] = sq;
+    wd_stat_reduce<NT>(scr, 2, NRL, ngt, BN, cps, tid);
+    __syncthreads();
+    if (tid < 2 * ngt && n0 + (tid % ngt) * cps < a.n) {
+        const int g = tid % ngt, q = tid / ngt;
+        double su = 0.0;
+        for (int l = 0; l < NRL; ++l) su += scr[(q * NRL + l) * BN + g * cps];
+        gs[2 * g + q] = su;
+        a.stat_part[((long)(m0 / a.hw_out) * (a.n / cps) + n0 / cps + g) * 2 + q] = su;  // (one chunk per sample: hw_out == BM)
     }
     __syncthreads();
     if (!live) return;

@@ -10,24 +10,35 @@ namespace {
 constexpr int GN_TOK = 32;  // tokens per statistics chunk
 
 // grid (nchunk, batch); block (64 * ceil(c/4/64), 2).  thread x owns channels 4x..4x+3, y splits tokens.
+// Every stage is in double: a thread's sums over its tokens (the square of an fp32 value is exact in double), the LDS hand-over,
+// the sum over the group's columns.  The partials are the sums of the fp32 values to double rounding, so the consumers'
+// var = sumsq / n - mean^2 loses nothing to the producer however far the group's mean is from zero (an fp32 sum of squares is off
+// by 2^-24 of itself, (mean / std)^2 times that in the variance).
 __global__ void gn_stats_kernel(const float* __restrict__ x, int ld, int hw, int c, int cpg, int nchunk,
                                 double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_sum = reinterpret_cast<float*>(smem);  // [2][c]
-    float* s_sq = s_sum + 2 * c;                    // [2][c]
+    double* s_sum = reinterpret_cast<double*>(smem);  // [2][c]
+    double* s_sq = s_sum + 2 * c;                     // [2][c]
     const int b = blockIdx.y, j = blockIdx.x;
     const int cx = threadIdx.x * 4;
     const int t0 = j * GN_TOK, t1 = min(hw, t0 + GN_TOK);
     if (cx < c) {
-        float4 s = make_float4(0, 0, 0, 0), q = make_float4(0, 0, 0, 0);
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
         const float* base = x + ((long)b * hw) * ld + cx;
         for (int t = t0 + threadIdx.y; t < t1; t += 2) {
             const float4 v = *reinterpret_cast<const float4*>(base + (long)t * ld);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
+            const double e[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s[k] += e[k];
+                q[k] = fma(e[k], e[k], q[k]);
+            }
         }
-        *reinterpret_cast<float4*>(s_sum + threadIdx.y * c + cx) = s;
-        *reinterpret_cast<float4*>(s_sq + threadIdx.y * c + cx) = q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s_sum[threadIdx.y * c + cx + k] = s[k];
+            s_sq[threadIdx.y * c + cx + k] = q[k];
+        }
     }
     __syncthreads();
     const int ng = c / cpg;
@@ -36,8 +47,8 @@ __global__ void gn_stats_kernel(const float* __restrict__ x, int ld, int hw, int
         double ds = 0.0, dq = 0.0;
         for (int k = 0; k < cpg; ++k) {
             const int ch = tid * cpg + k;
-            ds += (double)s_sum[ch] + (double)s_sum[c + ch];
-            dq += (double)s_sq[ch] + (double)s_sq[c + ch];
+            ds += s_sum[ch] + s_sum[c + ch];
+            dq += s_sq[ch] + s_sq[c + ch];
         }
         double* o = part + (((long)b * nchunk + j) * ng + tid) * 2;
         o[0] = ds;
@@ -482,7 +493,7 @@ extern "C" int wd_gn_stats(const float* x, int ld, int batch, int hw, int c, int
     const int bx = 64 * ((c / 4 + 63) / 64);
     if (bx * 2 > 1024) return WD_EINVAL;
     WdLaunchScope scope(WD_CLS_GNSTATS, st);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, batch), dim3(bx, 2), 4 * c * sizeof(float), st, x, ld, hw, c, cpg,
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, batch), dim3(bx, 2), 4 * c * sizeof(double), st, x, ld, hw, c, cpg,
                        nchunk, part);
     return wd_check_launch();
 }
