@@ -120,8 +120,13 @@ typedef struct wd_gemm_args {
     int32_t dbg;          /* 0 in production.  0x400: take the two-workgroups-per-CU kernel (wd_gemm4_kernel) wherever it is
                              legal, whatever the grid size (parity tests); 0x8000 / 0x10000: the 64 x 320 weights-to-registers
                              kernel keeps the per-tap A path / takes the slab form where it is legal, whatever WDIFF_GEMMW_SLAB
-                             says (in the args wd_gemm_check returns, 0x10000 = the launch takes the slab form); other bits
-                             are timing experiments */
+                             says (in the args wd_gemm_check returns, 0x10000 = the launch takes the slab form); 0x20000 /
+                             0x40000: the 64-row tiles of w_layout 3 (64320, 64080) keep the row loop of their epilogue / take
+                             its batched form - a thread's row loads in one round trip, then its stores - where that is legal,
+                             whatever WDIFF_EPI_BATCH says (in the args wd_gemm_check returns, 0x40000 = the 16-byte path of
+                             the launch's epilogue is the batched form; a launch whose pitches or addresses keep it off that
+                             path runs the element loop either way - wd_epilogue_batch_applies says both); other bits are timing
+                             experiments */
     int32_t* tickets;     /* NULL: split-K partials are combined by a second launch.  Else ntickets ints, ALL ZERO before the
                            * call and left all zero by it, not shared with a launch that may run concurrently: one arrival
                            * counter per output tile - the workgroup that finishes a tile's last K slice sums the slices from
@@ -180,6 +185,10 @@ int wd_gemm_check(const wd_gemm_args* args, wd_gemm_args* out);
 /* The launch family wd_gemm would run `args` on, by the name csrc/wd_gemm.hip gives it ("K_V1", "K_V2", "K_M16", "K_V4", "K_GEMMW",
  * "K_GEMMQ", ...; a static string), NULL where wd_gemm_check refuses them.  Host only: lets a test pin the kernel a case is about. */
 const char* wd_gemm_check_kernel(const wd_gemm_args* args);
+/* 1 when a launch of bm x bn tiles over `args` (as wd_gemm_check returns them) runs the batched epilogue: the 16-byte path
+ * (pitches % 4, fp32 operands 16-byte and planes 8-byte aligned), no K cut, activation none or SiLU, no ln_gamma / gn_gamma /
+ * a32 / resid_rows, m % bm == 0, n % bn == 0, hw_out % bm == 0, pitches below 2^22 elements.  Host only; the rule the kernels ask. */
+int wd_epilogue_batch_applies(const wd_gemm_args* args, int bm, int bn);
 
 /* wd_gemm_args.w_layout == 3: the weights of a GEMM with n % 320 == 0, ktot % 64 == 0 in FRAGMENT-MAJOR order - the 16 bytes
  * lane l of a v_mfma_f32_16x16x32_bf16 B fragment holds, W[16 ct + (l & 15)][32 ks + 8 (l >> 4) .. + 8], at byte
@@ -267,8 +276,13 @@ typedef struct wd_ff_args {
     const wd_bf16* w32_hi; /* folded tail (needs w3, npass 3): see above */
     const wd_bf16* w32_lo;
     const float* b32;
+    int32_t dbg; /* 0 in production.  0x20000 / 0x40000: the epilogue keeps its row loop / takes the batched form where it is legal,
+                    whatever WDIFF_EPI_BATCH says (in the args wd_ff_check returns, 0x40000 = the batched form, as wd_gemm_args.dbg) */
 } wd_ff_args;
 int wd_ff_fused(const wd_ff_args* args, void* stream);
+/* What wd_ff_fused would do with `args`, without launching anything (host only): WD_OK when it accepts them, else WD_EINVAL.  On
+ * WD_OK and out != NULL, *out receives the args as the kernel sees them (dbg resolved). */
+int wd_ff_check(const wd_ff_args* args, wd_ff_args* out);
 int wd_ff_supported(int c, int inner); /* 1 when wd_ff_fused covers the shape */
 int wd_ff_args_bytes(void); /* sizeof(wd_ff_args) as this library was built */
 

@@ -39,7 +39,12 @@ def timed(launch, iters):
     return 1e3 * e0.elapsed_time(e1) / iters
 
 
-def front(m, iters):
+def _epi_dbg(epi_batch):
+    """wd_ff_args.dbg for --epi-batch: 1 / 0 = the batched epilogue where legal / the row loop, whatever WDIFF_EPI_BATCH says."""
+    return 0 if epi_batch < 0 else 0x40000 if epi_batch else 0x20000
+
+
+def front(m, iters, epi_batch=-1):
     from tests.test_gpu_st_fused import _Block  # the seeded transformer block the fused launch is tested on
     if m % 256 == 0:
         blk = _Block(m // 256)
@@ -57,10 +62,13 @@ def front(m, iters):
     stat = torch.empty(blk.B, blk.hw // 64, 32, 2, dtype=torch.float64, device=DEV)
     tok2 = torch.empty(blk.m, blk.c, device=DEV)
     f = blk.fused_args(out, stat, tok2)
+    f.dbg = _epi_dbg(epi_batch)
+    r = N.WdFfArgs()
+    N.check(blk.lib.wd_ff_check(C.byref(f), C.byref(r)), "wd_ff_check")
     st = torch.cuda.current_stream().cuda_stream
     N.check(blk.lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused (front)")
     us = timed(lambda: blk.lib.wd_ff_fused(C.byref(f), st), iters)
-    print(f"wd_ff_fused front m={blk.m} ({blk.m // 64} workgroups): {us:7.1f} us   lib {N.LIB_PATH}")
+    print(f"wd_ff_fused front m={blk.m} ({blk.m // 64} workgroups) epi_batch={int(bool(r.dbg & 0x40000))}: {us:7.1f} us   lib {N.LIB_PATH}")
 
 
 def main():
@@ -69,9 +77,11 @@ def main():
     ap.add_argument("--front", type=int, default=0)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--m", type=int, default=16384)
+    ap.add_argument("--epi-batch", type=int, default=-1, help="1 / 0: the epilogue takes its batched form where legal / keeps the row loop "
+                    "(wd_ff_args.dbg 0x40000 / 0x20000), whatever WDIFF_EPI_BATCH says")
     a = ap.parse_args()
     if a.front:
-        return front(a.m, a.iters)
+        return front(a.m, a.iters, a.epi_batch)
     lib = N.lib()
     st = torch.cuda.current_stream().cuda_stream
     m, c, inner = a.m, 320, 1280
@@ -104,6 +114,7 @@ def main():
         f.w3_hi, f.w3_lo, f.b3 = w3f[0].data_ptr(), w3f[1].data_ptr(), b3.data_ptr()
         f.resid3, f.resid3_ld = res3.data_ptr(), c
     f.hw_out, f.npass = 1, 3
+    f.dbg = _epi_dbg(a.epi_batch)
     N.check(lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused")
     us = timed(lambda: lib.wd_ff_fused(C.byref(f), st), a.iters)
     fl = 2.0 * m * (3.0 * inner * c + (c * c if a.proj else 0))

@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--gemmw-slab", type=int, default=-1, help="with --wdirect 2: 1 / 0 = the 64 x 320 kernel takes its slab form where "
                     "legal / keeps the per-tap A path (wd_gemm_args.dbg 0x10000 / 0x8000), whatever WDIFF_GEMMW_SLAB says; the step's "
                     "four layer shapes are conv8x32, conv8x32cat, conv8x32id, conv8x32catid (--slab is the experimental slab-ORDER kernel)")
+    ap.add_argument("--epi-batch", type=int, default=-1, help="with --wdirect 2 / 3: 1 / 0 = the 64-row tiles take the batched epilogue where legal / "
+                    "keep the row loop (wd_gemm_args.dbg 0x40000 / 0x20000), whatever WDIFF_EPI_BATCH says")
     ap.add_argument("--cold", type=int, default=0, help="1: flush caches (1 GiB write) before every launch; "
                     "2: same, then read the weights once (emulates a prefetch) before the launch")
     ap.add_argument("--a32", type=int, default=0, help="1 (with --wdirect 2): src[0] is the fp32 map, GroupNorm + SiLU applied inside "
@@ -125,6 +127,8 @@ def main():
             g.w_layout, g.slab_rows, g.tile = 3, (w if ntaps == 9 else 0), (64320 if a.wdirect == 2 else 64080 if a.wdirect == 3 else 128160)
             if a.gemmw_slab >= 0:
                 g.dbg = a.dbg = a.dbg | (0x10000 if a.gemmw_slab else 0x8000)
+            if a.epi_batch >= 0:
+                g.dbg = a.dbg = a.dbg | (0x40000 if a.epi_batch else 0x20000)
             if a.a32:
                 x32 = torch.randn(m, cin, device=DEV)
                 nchunk = lib.wd_gn_nchunk(hw)
@@ -153,11 +157,14 @@ def main():
             g.dbg, g.ws, g.ws_floats = a.dbg, None, 0
         elif a.stamps:
             nk = (ktot // 64 + 1) & ~1 if a.wdirect else ktot // 64
-            sb = torch.zeros(8 * nk * 4, dtype=torch.int64, device=DEV)
+            sb = torch.zeros(8 * nk * 4 + 16, dtype=torch.int64, device=DEV)   # + [wave][2]: the epilogue (w-direct kernels)
             g.ws, g.ws_floats, g.dbg = sb.data_ptr(), 0, a.dbg | 0x100
             N.check(lib.wd_gemm(C.byref(g), st), name)
             torch.cuda.synchronize()
-            v = sb.cpu().view(8, nk, 4)
+            v = sb.cpu()[:8 * nk * 4].view(8, nk, 4)
+            if a.wdirect:
+                ep = sb.cpu()[8 * nk * 4:].view(8, 2)
+                print(f"{name} epilogue, finished image -> the wave's stores acknowledged (s_memtime ticks), per wave: {[int(x) for x in (ep[:, 1] - ep[:, 0]).tolist()]}")
             for wv in (0, 4):
                 w = v[wv]
                 wait = (w[:, 1] - w[:, 0]).float()       # barrier + vmcnt wait
@@ -203,7 +210,7 @@ def main():
             torch.cuda.synchronize()
             us = 1e3 * e0.elapsed_time(e1) / a.iters
         fl = 2.0 * m * cout * ktot
-        print(f"{name:12s} m={m:6d} n={cout:5d} k={ktot:5d} tile={a.tile:6d} npass={a.npass} slab={a.slab} gemmw_slab={a.gemmw_slab} ksplit={a.ksplit} cold={a.cold}: {us:8.1f} us  "
+        print(f"{name:12s} m={m:6d} n={cout:5d} k={ktot:5d} tile={a.tile:6d} npass={a.npass} slab={a.slab} gemmw_slab={a.gemmw_slab} epi_batch={a.epi_batch} ksplit={a.ksplit} cold={a.cold}: {us:8.1f} us  "
               f"{fl / us / 1e6:7.1f} TF/s algorithmic ({a.npass * fl / us / 1e6:7.1f} MFMA)", flush=True)
 
 

@@ -43,6 +43,36 @@ typedef __attribute__((ext_vector_type(4))) unsigned f_u32x4;
 
 __device__ __forceinline__ int f_lds_off(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
 
+// The GEMM epilogue of the launch's last product as wd_gemm_args: the bias and residual of its tail (plain: b2 + resid; proj_out: b3 +
+// resid3; folded: b32 + resid3), the outputs, the statistics.  Host and device build it here, so wd_ff_fused asks
+// wd_epilogue_batch_ok about the args the kernel will run.
+__host__ __device__ __forceinline__ wd_gemm_args ff_epi_args(const wd_ff_args& a, const bool proj, const bool fold) {
+    wd_gemm_args e = {};
+    e.m = a.m;
+    e.n = FC;
+    e.hw_out = a.hw_out > 0 ? a.hw_out : 1;
+    e.act = WD_ACT_NONE;
+    e.out_f32 = a.out_f32;
+    e.out_ld = a.out_ld;
+    e.out_hi = a.out_hi;
+    e.out_lo = a.out_lo;
+    e.out_pl_ld = a.out_pl_ld;
+    e.ksplit = 1;
+    e.stat_part = a.stat_part;
+    e.stat_cpg = a.stat_cpg;
+    e.bias = !proj ? a.b2 : fold ? a.b32 : a.b3;
+    e.resid = proj ? a.resid3 : a.resid;
+    e.resid_ld = proj ? a.resid3_ld : a.resid_ld;
+    e.dbg = a.dbg;
+    return e;
+}
+
+// the finished 64 x 320 image -> the outputs: the batched form where wd_ff_fused resolved it (wd_ff_args.dbg), else the row loop
+__device__ __forceinline__ void ff_epilogue(const wd_gemm_args& e, float* ep, const int m0, const int tid) {
+    if ((e.dbg & WD_EPI_BATCH_BIT) && wd_epilogue_batch_ok(e, FBM, FC)) wd_epilogue_rows<FBM, FC, FNT>(e, ep, m0, 0, tid);
+    else wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
+}
+
 template <int NPASS, bool PROJ, bool FRONT, bool FOLD>
 __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -708,30 +738,11 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
     // ---- the two K-halves summed in a fixed order through the fp32 image, then the shared GEMM epilogue (+ b2, + x, planes / fp32)
     __syncthreads();
     ksum_to_image();
-    wd_gemm_args e = {};
-    e.m = a.m;
-    e.n = FC;
-    e.hw_out = a.hw_out > 0 ? a.hw_out : 1;
-    e.act = WD_ACT_NONE;
-    e.out_f32 = a.out_f32;
-    e.out_ld = a.out_ld;
-    e.out_hi = a.out_hi;
-    e.out_lo = a.out_lo;
-    e.out_pl_ld = a.out_pl_ld;
-    e.ksplit = 1;
-    e.stat_part = a.stat_part;
-    e.stat_cpg = a.stat_cpg;
+    const wd_gemm_args e = ff_epi_args(a, PROJ, FOLD);
     if constexpr (!PROJ) {
-        e.bias = a.b2;
-        e.resid = a.resid;
-        e.resid_ld = a.resid_ld;
-        wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
+        ff_epilogue(e, ep, m0, tid);  // + b2, + resid
     } else if constexpr (FOLD) {
-        // the image already is tok2 W3^T + h (W3 W2)^T: + b32 = W3 b2 + b3, + x_in
-        e.bias = a.b32;
-        e.resid = a.resid3;
-        e.resid_ld = a.resid3_ld;
-        wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
+        ff_epilogue(e, ep, m0, tid);  // the image already is tok2 W3^T + h (W3 W2)^T: + b32 = W3 b2 + b3, + x_in
     } else {
         // ---- x' = image + b2 + x -> split-bf16 planes IN PLACE (a row's 320 floats = 1296 bytes with the pitch; its planes take
         // 2 x 640): wave w converts rows 8 w .. 8 w + 7, every read of those rows before the first write (same wave, in order)
@@ -806,10 +817,7 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
         }
         __syncthreads();  // every fragment read of the planes is done: the image goes over them
         ksum_to_image();
-        e.bias = a.b3;
-        e.resid = a.resid3;
-        e.resid_ld = a.resid3_ld;
-        wd_epilogue_from_image<FBM, FC, FNT>(e, ep, m0, 0, tid);
+        ff_epilogue(e, ep, m0, tid);  // + b3, + resid3
     }
 #endif
 }
@@ -843,9 +851,10 @@ extern "C" int wd_ff_args_bytes(void) { return (int)sizeof(wd_ff_args); }
 
 extern "C" int wd_ff_supported(int c, int inner) { return (c == FC && inner > 0 && inner % FCH == 0 && inner <= F_MAX_INNER) ? 1 : 0; }
 
-extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
-    if (!pa) return WD_EINVAL;
-    const wd_ff_args& a = *pa;
+// Every check and decision of wd_ff_fused, host only (no HIP call): WD_OK and `a` = the args as the kernel sees them (dbg resolved:
+// WD_EPI_BATCH_BIT alone says which epilogue form runs), or WD_EINVAL.
+static int wd_ff_resolve(const wd_ff_args& in, wd_ff_args& a) {
+    a = in;
     if (!wd_ff_supported(a.c, a.inner) || a.m <= 0 || (a.npass != 1 && a.npass != 3)) return WD_EINVAL;
     const bool front = a.x_in != nullptr;
     if (!a.w1_hi || !a.w2_hi || (a.npass == 3 && (!a.w1_lo || !a.w2_lo))) return WD_EINVAL;
@@ -870,6 +879,31 @@ extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
         if (!a.pi_hi || !a.pi_lo || !a.pi_b || !a.ln2_gamma || !a.ln2_beta || !a.ln3_gamma || !a.ln3_beta || (!a.tok2 && !fold)) return WD_EINVAL;
         if (!a.mq_a || !a.mot_a || !a.xb_a || !a.mq_b || !a.mot_b || !a.xb_b || !wd_xattn_supported(a.c, a.heads, a.L)) return WD_EINVAL;
     }
+    {
+        // the batched epilogue (wd_epilogue_rows): WDIFF_EPI_BATCH (default WD_EPI_BATCH_DEFAULT) is the switch, dbg WD_EPI_BATCH_OFF /
+        // _ON override it per call; wd_epilogue_batch_ok says where it is legal
+        static const bool batch_env = getenv("WDIFF_EPI_BATCH") ? atoi(getenv("WDIFF_EPI_BATCH")) != 0 : WD_EPI_BATCH_DEFAULT;
+        const bool want = (a.dbg & WD_EPI_BATCH_OFF) ? false : (a.dbg & WD_EPI_BATCH_ON) ? true : batch_env;
+        a.dbg &= ~(WD_EPI_BATCH_OFF | WD_EPI_BATCH_ON);
+        if (want && wd_epilogue_batch_shape(ff_epi_args(a, proj, fold), FBM, FC)) a.dbg |= WD_EPI_BATCH_BIT;
+    }
+    return WD_OK;
+}
+
+extern "C" int wd_ff_check(const wd_ff_args* in, wd_ff_args* out) {
+    if (!in) return WD_EINVAL;
+    wd_ff_args a;
+    const int rc = wd_ff_resolve(*in, a);
+    if (rc == WD_OK && out) *out = a;
+    return rc;
+}
+
+extern "C" int wd_ff_fused(const wd_ff_args* pa, void* stream) {
+    if (!pa) return WD_EINVAL;
+    wd_ff_args a;
+    const int rc = wd_ff_resolve(*pa, a);
+    if (rc != WD_OK) return rc;
+    const bool front = a.x_in != nullptr, proj = a.w3_hi != nullptr, fold = a.w32_hi != nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (fold) return front ? launch_ff<3, true, true, true>(a, st) : launch_ff<3, true, false, true>(a, st);
     if (front) return launch_ff<3, true, true>(a, st);

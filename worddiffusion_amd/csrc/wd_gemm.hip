@@ -2249,6 +2249,11 @@ struct WdResolved {
 // Every check and every decision of wd_gemm, host only (no HIP call): WD_OK and `r` filled, or WD_EINVAL.
 static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
     wd_gemm_args a = in;
+    // the batched epilogue of the 64-row tiles of w_layout 3 (wd_epilogue_rows): WDIFF_EPI_BATCH (default WD_EPI_BATCH_DEFAULT) is the
+    // switch, dbg WD_EPI_BATCH_OFF / _ON override it per call; the resolved WD_EPI_BATCH_BIT is set below for K_GEMMQ / K_GEMMW only
+    static const bool batch_env = getenv("WDIFF_EPI_BATCH") ? atoi(getenv("WDIFF_EPI_BATCH")) != 0 : WD_EPI_BATCH_DEFAULT;
+    const bool want_batch = (a.dbg & WD_EPI_BATCH_OFF) ? false : (a.dbg & WD_EPI_BATCH_ON) ? true : batch_env;
+    a.dbg &= ~(WD_EPI_BATCH_OFF | WD_EPI_BATCH_ON);
     static const int ks_env = getenv("WDIFF_GEMM_KS") ? atoi(getenv("WDIFF_GEMM_KS")) : 2;
     r.ks = ks_env == 1 ? 1 : 2;
     if (a.ksplit < 0 || a.ksplit > WD_MAX_KSPLIT) return WD_EINVAL;
@@ -2355,6 +2360,7 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         if (a.tile == 64080) {
             if (!wd_gemmq_applies(a)) return WD_EINVAL;
             if (a.gn_gamma && (40 % a.gn_cpg || 80 % a.gn_cpg)) return WD_EINVAL;
+            if (want_batch && wd_epilogue_batch_shape(a, 64, 80)) a.dbg |= WD_EPI_BATCH_BIT;
             r.a = a, r.kernel = K_GEMMQ;
             return WD_OK;
         }
@@ -2374,6 +2380,7 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
             a.dbg &= ~(WD_GEMMW_SLAB_OFF | WD_GEMMW_SLAB_ON);
             if (want && fits) a.dbg |= WD_GEMMW_SLAB_BIT;
         }
+        if (want_batch && a.tile == 64320 && wd_epilogue_batch_shape(a, 64, 320)) a.dbg |= WD_EPI_BATCH_BIT;
         r.a = a, r.kernel = K_GEMMW;
         return WD_OK;
     }
@@ -2500,6 +2507,10 @@ extern "C" int wd_gemm_check(const wd_gemm_args* in, wd_gemm_args* out) {
     const int rc = wd_gemm_resolve(*in, r);
     if (rc == WD_OK && out) *out = r.a;
     return rc;
+}
+
+extern "C" int wd_epilogue_batch_applies(const wd_gemm_args* a, int bm, int bn) {
+    return a && bm == 64 && bn > 0 && bn % 4 == 0 && wd_epilogue_batch_ok(*a, bm, bn) ? 1 : 0;
 }
 
 extern "C" const char* wd_gemm_check_kernel(const wd_gemm_args* in) {

@@ -3,6 +3,7 @@
 // partial store.  Replaces the elementwise tails of reference unet.py:660-669 (FiLM add, residual) and :128-136 (GEGLU).
 #pragma once
 #include "wd_common.h"
+#include "wd_gemm_priv.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -26,6 +27,25 @@ __host__ __device__ __forceinline__ bool wd_epilogue_vec_ok(const wd_gemm_args& 
            (((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.rowvec) |
               reinterpret_cast<uintptr_t>(a.resid) | reinterpret_cast<uintptr_t>(a.out_f32)) & 15) == 0) &&
            (((reinterpret_cast<uintptr_t>(a.out_hi) | reinterpret_cast<uintptr_t>(a.out_lo)) & 7) == 0);
+}
+
+// Does a launch of bm x bn tiles (bm = 64) over these RESOLVED args take the batched epilogue (wd_epilogue_rows below) instead of the
+// row loop of wd_epilogue_from_image.  Two parts.  The launch's SHAPE (wd_epilogue_batch_shape): the epilogue inside the GEMM launch
+// (no K cut), no activation or SiLU, the result stored as it is (no row LayerNorm, no GroupNorm of the result), planes sources (no
+// a32), the residual row of m is row m, every tile whole (m and n multiples of the tile) and inside one sample (no second sample's
+// statistics to park), and pitches small enough that a tile's byte offsets from its first element fit 31 bits - wd_gemm_resolve /
+// wd_ff_fused set WD_EPI_BATCH_BIT by it: the bit names the form of the launch's 16-byte path.  And the 16-byte path itself
+// (wd_epilogue_vec_ok), which depends on the pitches and addresses of a call as it always did: a launch off it runs the element loop
+// under either form.  wd_epilogue_batch_ok is both, the one statement of the rule: the kernels ask it before they branch.
+constexpr int WD_EPI_BATCH_MAX_LD = 1 << 22;
+__host__ __device__ __forceinline__ bool wd_epilogue_batch_shape(const wd_gemm_args& a, const int bm, const int bn) {
+    const bool pitches = (!a.out_f32 || a.out_ld < WD_EPI_BATCH_MAX_LD) && (!a.out_hi || a.out_pl_ld < WD_EPI_BATCH_MAX_LD) &&
+                         (!a.resid || a.resid_ld < WD_EPI_BATCH_MAX_LD);
+    return a.ksplit <= 1 && (a.act == WD_ACT_NONE || a.act == WD_ACT_SILU) && !a.ln_gamma && !a.gn_gamma && !a.a32 && !a.resid_rows &&
+           a.m % bm == 0 && a.n % bn == 0 && a.hw_out % bm == 0 && pitches;
+}
+__host__ __device__ __forceinline__ bool wd_epilogue_batch_ok(const wd_gemm_args& a, const int bm, const int bn) {
+    return wd_epilogue_vec_ok(a) && wd_epilogue_batch_shape(a, bm, bn);
 }
 
 // Fused GroupNorm statistics, the accuracy rule: a producer's (sum, sum of squares) partials leave var = sumsq / n - mean^2,
@@ -73,6 +93,74 @@ __device__ __forceinline__ void wd_stat_reduce(double* scr, const int ns, const 
         for (int cc = 0; cc < cpg; ++cc) su += p[cc];
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): every read of this group's span precedes the write-back
         p[0] = su;
+    }
+}
+
+// The hand-over both epilogue forms end in: `st` holds a thread's column sums of the last sample of the panel (a thread that
+// crossed into sample 1 left sample 0's state in `park`), nrl / rl / c / rps are the caller's row-lane geometry.
+template <int BM, int BN, int NT>
+__device__ __forceinline__ void wd_stat_handover(const wd_gemm_args& a, float* ep, const int m0, const int n0, const int tid,
+                                                 const WdStatAcc& st, const int cur_s, const float* park, const int nrl, const int rl,
+                                                 const int c, const int rps) {
+    constexpr int LDE = BN + 4;
+    // ---- GroupNorm partial statistics of the finished tile: (sample in panel, group) = fixed-order sum over the group's
+    // columns, then over the row lanes, of the per-thread column sums (host guarantees the vector path, BN % cpg == 0,
+    // n % cpg == 0, and that BM and hw_out divide one another).  Everything stays in double: the scratch behind the image
+    // holds [quantity][sample][row lane][BN] doubles - the sums and the sums of squares together where that fits (one
+    // sample per panel, or 256 threads), else the sums go through it first and the sums of squares second.
+    const int ns = BM > a.hw_out ? BM / a.hw_out : 1;
+    double ssum[4] = {0.0, 0.0, 0.0, 0.0}, ssq[4] = {0.0, 0.0, 0.0, 0.0};  // the last sample of the panel
+    double s0[4] = {0.0, 0.0, 0.0, 0.0}, q0[4] = {0.0, 0.0, 0.0, 0.0};      // sample 0 of two
+    if (cur_s == 0 && ns > 1) {
+        wd_stat_finish(st, s0, q0);  // this thread never reached sample 1: its running sums are sample 0's
+    } else {
+        wd_stat_finish(st, ssum, ssq);
+        if (cur_s != 0) {  // (only with ns > 1, and then rl < nrl && c < BN: the parked slots are inside the scratch)
+            WdStatAcc pv;
+            pv.p = *reinterpret_cast<const float4*>(park);
+            pv.s = *reinterpret_cast<const float4*>(park + 4);
+            pv.q = *reinterpret_cast<const float4*>(park + 2 * nrl * BN);
+            pv.n = __float_as_int(park[2 * nrl * BN + 4]);
+            wd_stat_finish(pv, s0, q0);
+        }
+    }
+    const int cpg = a.stat_cpg;
+    const int ngt = BN / cpg;
+    const int nchunk = a.hw_out > BM ? a.hw_out / BM : 1;
+    const int ngs = a.n / cpg;  // groups per sample in the statistics array of this tensor
+    double* scr = reinterpret_cast<double*>(ep + BM * LDE);  // (BM * LDE * 4 is a multiple of 16)
+    const int nq = 2 * ns * nrl * BN * (int)sizeof(double) <= WD_STAT_SCRATCH ? 2 : 1;  // quantities per pass
+    for (int q0i = 0; q0i < 2; q0i += nq) {
+        if (q0i) __syncthreads();
+        if (rl < nrl && c < BN) {
+            for (int qq = 0; qq < nq; ++qq) {
+                const bool sq = q0i + qq;
+                const double* lo = ns > 1 ? (sq ? q0 : s0) : (sq ? ssq : ssum);
+                double* o = scr + ((long)(qq * ns) * nrl + rl) * BN + c;
+                *reinterpret_cast<double2*>(o) = make_double2(lo[0], lo[1]);
+                *reinterpret_cast<double2*>(o + 2) = make_double2(lo[2], lo[3]);
+                if (ns > 1) {
+                    const double* hi = sq ? ssq : ssum;
+                    o += nrl * BN;
+                    *reinterpret_cast<double2*>(o) = make_double2(hi[0], hi[1]);
+                    *reinterpret_cast<double2*>(o + 2) = make_double2(hi[2], hi[3]);
+                }
+            }
+        }
+        __syncthreads();
+        wd_stat_reduce<NT>(scr, nq * ns, nrl, ngt, BN, cpg, tid);
+        __syncthreads();
+        // (quantity, sample, group) -> sum over the row lanes in fixed order
+        for (int it = tid; it < nq * ns * ngt; it += NT) {
+            const int g = it % ngt, qs = it / ngt, sidx2 = qs % ns, qq = qs / ns;
+            const int mrow = m0 + sidx2 * rps;
+            if (mrow >= a.m || n0 + g * cpg >= a.n) continue;
+            double su = 0.0;
+            for (int l = 0; l < nrl; ++l) su += scr[(long)(qs * nrl + l) * BN + g * cpg];
+            const int b = mrow / a.hw_out;
+            const int chunk = (mrow - b * a.hw_out) / BM;
+            a.stat_part[(((long)b * nchunk + chunk) * ngs + n0 / cpg + g) * 2 + q0i + qq] = su;
+        }
     }
 }
 
@@ -215,67 +303,7 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
                 }
             }
         }
-        if (stats) {
-            // ---- GroupNorm partial statistics of the finished tile: (sample in panel, group) = fixed-order sum over the group's
-            // columns, then over the row lanes, of the per-thread column sums (host guarantees the vector path, BN % cpg == 0,
-            // n % cpg == 0, and that BM and hw_out divide one another).  Everything stays in double: the scratch behind the image
-            // holds [quantity][sample][row lane][BN] doubles - the sums and the sums of squares together where that fits (one
-            // sample per panel, or 256 threads), else the sums go through it first and the sums of squares second.
-            const int ns = BM > a.hw_out ? BM / a.hw_out : 1;
-            double ssum[4] = {0.0, 0.0, 0.0, 0.0}, ssq[4] = {0.0, 0.0, 0.0, 0.0};  // the last sample of the panel
-            double s0[4] = {0.0, 0.0, 0.0, 0.0}, q0[4] = {0.0, 0.0, 0.0, 0.0};      // sample 0 of two
-            if (cur_s == 0 && ns > 1) {
-                wd_stat_finish(st, s0, q0);  // this thread never reached sample 1: its running sums are sample 0's
-            } else {
-                wd_stat_finish(st, ssum, ssq);
-                if (cur_s != 0) {  // (only with ns > 1, and then rl < nrl && c < BN: the parked slots are inside the scratch)
-                    WdStatAcc pv;
-                    pv.p = *reinterpret_cast<const float4*>(park);
-                    pv.s = *reinterpret_cast<const float4*>(park + 4);
-                    pv.q = *reinterpret_cast<const float4*>(park + 2 * nrl * BN);
-                    pv.n = __float_as_int(park[2 * nrl * BN + 4]);
-                    wd_stat_finish(pv, s0, q0);
-                }
-            }
-            const int cpg = a.stat_cpg;
-            const int ngt = BN / cpg;
-            const int nchunk = a.hw_out > BM ? a.hw_out / BM : 1;
-            const int ngs = a.n / cpg;  // groups per sample in the statistics array of this tensor
-            double* scr = reinterpret_cast<double*>(ep + BM * LDE);  // (BM * LDE * 4 is a multiple of 16)
-            const int nq = 2 * ns * nrl * BN * (int)sizeof(double) <= WD_STAT_SCRATCH ? 2 : 1;  // quantities per pass
-            for (int q0i = 0; q0i < 2; q0i += nq) {
-                if (q0i) __syncthreads();
-                if (rl < nrl && c < BN) {
-                    for (int qq = 0; qq < nq; ++qq) {
-                        const bool sq = q0i + qq;
-                        const double* lo = ns > 1 ? (sq ? q0 : s0) : (sq ? ssq : ssum);
-                        double* o = scr + ((long)(qq * ns) * nrl + rl) * BN + c;
-                        *reinterpret_cast<double2*>(o) = make_double2(lo[0], lo[1]);
-                        *reinterpret_cast<double2*>(o + 2) = make_double2(lo[2], lo[3]);
-                        if (ns > 1) {
-                            const double* hi = sq ? ssq : ssum;
-                            o += nrl * BN;
-                            *reinterpret_cast<double2*>(o) = make_double2(hi[0], hi[1]);
-                            *reinterpret_cast<double2*>(o + 2) = make_double2(hi[2], hi[3]);
-                        }
-                    }
-                }
-                __syncthreads();
-                wd_stat_reduce<NT>(scr, nq * ns, nrl, ngt, BN, cpg, tid);
-                __syncthreads();
-                // (quantity, sample, group) -> sum over the row lanes in fixed order
-                for (int it = tid; it < nq * ns * ngt; it += NT) {
-                    const int g = it % ngt, qs = it / ngt, sidx2 = qs % ns, qq = qs / ns;
-                    const int mrow = m0 + sidx2 * rps;
-                    if (mrow >= a.m || n0 + g * cpg >= a.n) continue;
-                    double su = 0.0;
-                    for (int l = 0; l < nrl; ++l) su += scr[(long)(qs * nrl + l) * BN + g * cpg];
-                    const int b = mrow / a.hw_out;
-                    const int chunk = (mrow - b * a.hw_out) / BM;
-                    a.stat_part[(((long)b * nchunk + chunk) * ngs + n0 / cpg + g) * 2 + q0i + qq] = su;
-                }
-            }
-        }
+        if (stats) wd_stat_handover<BM, BN, NT>(a, ep, m0, n0, tid, st, cur_s, park, nrl, rl, c, rps);
     }
     if (a.ln_gamma) {
         // ---- LayerNorm of every finished row -> the operand planes of the next GEMM (nn.LayerNorm of the transformer block that
@@ -325,11 +353,105 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
     }
 }
 
-// after the fp32 image of the tile is complete: split-K partial store, or the fused epilogue
+// The batched form of the 16-byte path for launches wd_epilogue_batch_ok accepts: the values and the order of the row loop above
+// (+ bias, + FiLM row, + residual, SiLU?, the column sums), so the bits of every output are the loop's, but a thread's rows
+// rl, rl + NRL, ... are unrolled and go through memory together:
+//   (a) every image quad from LDS, the bias and FiLM quads (one sample per tile: one row vector) and every residual row are requested;
+//   (b) ONE wait for all of them;
+//   (c) the rows in ascending order: arithmetic, then the row's stores - no load and no wait between the first and the last store.
+// In the loop every row paid a round trip of its own: vmcnt counts stores as well as loads, and the wait in front of a row's residual
+// load also drained the stores of the row before it.
+// The run-time flags (bias, rowvec, resid, out_f32, out_hi, out_lo) wrap no memory operation in a branch - hipcc's wait-count pass
+// would put the waits back.  Every operand is a buffer descriptor over the tile's own window (based at the
+// tile's first element, as long as its last row's last column), of ZERO bytes when the operand is absent: such a load returns
+// zeros (added only under the flag, or + 0.0f as the loop adds an absent bias) and such a store is dropped, as are those of a
+// thread's rows past the tile (offset WD_EPI_OOB).  The same bounds check keeps a wrong offset from leaving the window.
+typedef __attribute__((ext_vector_type(4))) unsigned wd_u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned wd_u32x2;
+constexpr uint32_t WD_EPI_OOB = 0x80000000u;
+
 template <int BM, int BN, int NT>
+__device__ __forceinline__ void wd_epilogue_rows(const wd_gemm_args& a, float* ep, const int m0, const int n0, const int tid) {
+    constexpr int LDE = BN + 4, Q = BN / 4, NRL = NT / Q, KEEP = (BM + NRL - 1) / NRL;
+    const int rl = tid / Q, c = (tid - rl * Q) * 4;
+    const bool live = rl < NRL;
+    const bool planes = a.out_hi != nullptr;
+    // a window of BM rows of pitch ld, BN columns of esz bytes, from (m0 + row0, n0) of p
+    auto window = [&](const void* p, const long row0, const int ld, const int rows, const int esz) {
+        const char* base = reinterpret_cast<const char*>(p) + (row0 * ld + n0) * esz;
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, p ? ((rows - 1) * ld + BN) * esz : 0, 0x00020000);
+    };
+    const __amdgpu_buffer_rsrc_t s_bias = window(a.bias, 0, 0, 1, 4);
+    const __amdgpu_buffer_rsrc_t s_rv = window(a.rowvec, a.rowvec ? m0 / a.hw_out : 0, a.rowvec_ld, 1, 4);
+    const __amdgpu_buffer_rsrc_t s_res = window(a.resid, m0, a.resid_ld, BM, 4);
+    const __amdgpu_buffer_rsrc_t s_f32 = window(a.out_f32, m0, a.out_ld, BM, 4);
+    const __amdgpu_buffer_rsrc_t s_hi = window(a.out_hi, m0, a.out_pl_ld, BM, 2);
+    const __amdgpu_buffer_rsrc_t s_lo = window(planes ? a.out_lo : nullptr, m0, a.out_pl_ld, BM, 2);
+    auto as_f4 = [](const wd_u32x4 u) { return __builtin_bit_cast(float4, u); };
+
+    // ---- (a) every load
+    float4 v[KEEP], r[KEEP];
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) {
+        const int row = rl + k * NRL;
+        v[k] = *reinterpret_cast<const float4*>(ep + (row < BM ? row : BM - 1) * LDE + c);  // (a row past the tile: any row, never stored)
+    }
+    const uint32_t vo_c = live ? (uint32_t)c * 4u : WD_EPI_OOB;
+    const float4 bx = as_f4(__builtin_amdgcn_raw_buffer_load_b128(s_bias, vo_c, 0, 0));
+    const float4 rv = as_f4(__builtin_amdgcn_raw_buffer_load_b128(s_rv, vo_c, 0, 0));
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) {
+        const int row = rl + k * NRL;
+        const uint32_t vo = (live && row < BM) ? ((uint32_t)row * (uint32_t)a.resid_ld + (uint32_t)c) * 4u : WD_EPI_OOB;
+        r[k] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(s_res, vo, 0, 0));
+    }
+    // ---- (b) one wait: vmcnt(0) lgkmcnt(0)
+    __builtin_amdgcn_s_waitcnt(0x0070);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- (c) the rows
+    const bool has_rv = a.rowvec != nullptr, has_res = a.resid != nullptr, silu = a.act == WD_ACT_SILU, stats = a.stat_part != nullptr;
+    WdStatAcc st;
+    wd_stat_reset(st);
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) {
+        const int row = rl + k * NRL;
+        const bool ok = live && row < BM;
+        float4 x = v[k];
+        x.x += bx.x; x.y += bx.y; x.z += bx.z; x.w += bx.w;
+        if (has_rv) {
+            x.x += rv.x; x.y += rv.y; x.z += rv.z; x.w += rv.w;
+        }
+        if (has_res) {
+            x.x += r[k].x; x.y += r[k].y; x.z += r[k].z; x.w += r[k].w;
+        }
+        if (silu) {
+            x.x = wd_silu(x.x); x.y = wd_silu(x.y); x.z = wd_silu(x.z); x.w = wd_silu(x.w);
+        }
+        if (stats && ok) wd_stat_add(st, x);
+        uint2 hh = make_uint2(0u, 0u), ll = hh;
+        if (planes) wd_split4(x, hh, ll);
+        const uint32_t vo_f = ok ? ((uint32_t)row * (uint32_t)a.out_ld + (uint32_t)c) * 4u : WD_EPI_OOB;
+        const uint32_t vo_p = ok ? ((uint32_t)row * (uint32_t)a.out_pl_ld + (uint32_t)c) * 2u : WD_EPI_OOB;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wd_u32x4, x), s_f32, vo_f, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(wd_u32x2, hh), s_hi, vo_p, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(wd_u32x2, ll), s_lo, vo_p, 0, 0);
+    }
+    // (one sample per tile: nothing parked, the running sums are the panel's)
+    if (stats) wd_stat_handover<BM, BN, NT>(a, ep, m0, n0, tid, st, 0, ep, NRL, rl, c, BM);
+}
+
+// after the fp32 image of the tile is complete: split-K partial store, or the fused epilogue (BATCH: the kernels whose 64-row tiles
+// may take the batched form - wd_gemmw_kernel's 64 x 320, wd_gemmq_kernel's 64 x 80)
+template <int BM, int BN, int NT, bool BATCH = false>
 __device__ __forceinline__ void wd_epilogue_tail(const wd_gemm_args& a, float* ep, const int m0, const int n0, const int tid,
                                                  const int sidx) {
     constexpr int LDE = BN + 4;
+    if constexpr (BATCH) {
+        if ((a.dbg & WD_EPI_BATCH_BIT) && wd_epilogue_batch_ok(a, BM, BN)) {
+            wd_epilogue_rows<BM, BN, NT>(a, ep, m0, n0, tid);
+            return;
+        }
+    }
     if (a.ksplit > 1) {  // raw partial sums of this K slice -> ws[sidx][m][n]; wd_gemm_reduce applies the epilogue
         float* ws = a.ws + (long)sidx * a.m * a.n;
         const bool v4 = (a.n & 3) == 0;

@@ -303,7 +303,7 @@ __global__ void __launch_bounds__(QNT, 1) wd_gemmq_kernel(const wd_gemm_args a, 
     Q_STAMP(6);
     // ---- epilogue on the finished image (scratch behind the four images)
     if (a.gn_gamma) wd_gn_tile<QBN, QNT, false>(a, buf, buf + IMG, m0, n0, tid);
-    else wd_epilogue_tail<QBM, QBN, QNT>(a, buf, m0, n0, tid, 0);
+    else wd_epilogue_tail<QBM, QBN, QNT, true>(a, buf, m0, n0, tid, 0);
     Q_STAMP(7);
 #endif
 }

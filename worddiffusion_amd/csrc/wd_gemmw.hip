@@ -628,7 +628,19 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
         }
         __syncthreads();
     }
-    wd_epilogue_tail<BM, BN, WNT>(a, ep, m0, n0, tid, sidx);
+    // (-DWD_GEMMW_STAMPS + a.dbg & 0x100: the epilogue of workgroup 0, finished image -> the wave's stores acknowledged, as u64 [wave][2] behind the
+    // per-stage stamps, i.e. at a.ws + 8 * 4 * (ktot / 64 rounded up to even); tools/gemm_bench.py --stamps)
+#ifdef WD_GEMMW_STAMPS
+    unsigned long long* se = reinterpret_cast<unsigned long long*>(a.ws) + 32l * ((a.ktot / 64 + 1) & ~1) + wave * 2;
+    if (stamp) se[0] = __builtin_amdgcn_s_memtime();
+#endif
+    wd_epilogue_tail<BM, BN, WNT, BM == 64 && !A32>(a, ep, m0, n0, tid, sidx);  // (A32: no registers to spare for the batched rows)
+#ifdef WD_GEMMW_STAMPS
+    if (stamp) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        se[1] = __builtin_amdgcn_s_memtime();
+    }
+#endif
 #endif
 }
 

@@ -391,6 +391,10 @@ class UNetEngine:
         # tap (wd_gemmw_kernel<..., SLAB>).  wd_gemm decides where that form is legal and reads the same variable for its default; an
         # engine built while it is set passes its value with every launch (wd_gemm_args.dbg 0x10000 / 0x8000).
         self.gemmw_slab = {None: None, "0": False}.get(os.environ.get("WDIFF_GEMMW_SLAB"), True)
+        # the batched epilogue of the 64-row tiles (wd_epilogue_rows: 64 x 320, 64 x 80, wd_ff_fused).  wd_gemm / wd_ff_fused decide where
+        # that form is legal and read the same variable for their default; an engine built while it is set passes its value with every
+        # such launch (wd_gemm_args.dbg / wd_ff_args.dbg 0x40000 / 0x20000).
+        self.epi_batch = {None: None, "0": False}.get(os.environ.get("WDIFF_EPI_BATCH"), True)
         # Upsample as four 2x2 convolutions of the source map (one per output phase, 4 taps instead of 9; upsample_phase_tables)
         self.use_up_phases = os.environ.get("WDIFF_UPSAMPLE_PHASES", "1") != "0"
         self._derived: Dict[str, tuple] = {}   # name -> (persistent fp32 tensor, function that recomputes it from the parameters)
@@ -772,6 +776,8 @@ class UNetEngine:
             a.w_hi, a.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
             if wdirect and self.gemmw_slab is not None:
                 a.dbg |= 0x10000 if self.gemmw_slab else 0x8000
+            if self.epi_batch is not None:
+                a.dbg |= 0x40000 if self.epi_batch else 0x20000
         elif span:
             meta = (srcs[0].ntaps, srcs[0].c, srcs[1].c if len(srcs) > 1 else 0)
             if wname not in self._w3:
@@ -1431,6 +1437,8 @@ class UNetEngine:
                 self._cur_plan.keep.append(part)
                 a.stat_part, a.stat_cpg, a.hw_out = part.data_ptr(), inner // 32, hw
                 stats = (part, nchunk, inner // 32)
+        if self.epi_batch is not None:
+            a.dbg |= 0x40000 if self.epi_batch else 0x20000
         self._cur_plan.keep.append(a)
         what = ".ff (fused)" if proj is None else ".ff + proj_out (fused)" if front is None else ": gn + proj_in + a1 + a2 + ff + proj_out (fused)"
         ops.append((self.lib.wd_ff_fused, (C.byref(a),), p + what))
