@@ -594,6 +594,34 @@ int wd_known_blend(float* x, const float* x0, const float* mask, int batch, int 
                    const float* sqrt_1m_ah, const int32_t* t_dev, const int32_t* k_dev, const int32_t* tau, int S,
                    const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
 
+/* Line sampling as overlapping windows (MultiDiffusion, Bar-Tal et al. 2023): a line latent, fp32 [lines][c][h][wl], is denoised
+ * as K windows of the model's own width w per line; window k of line s is model batch row b = s * K + k and begins at line
+ * column o = offsets[b] (int32 [lines][K], on the device so that a captured graph replays).  A window that does not fit
+ * (o < 0 or o + w > wl) is treated as absent; every access is checked against wl and w whatever offsets holds.
+ *
+ * wd_window_gather, before the forward(s):  win[b][ch][r][j] = line[s][ch][r][o + j] - the bits are copied, no arithmetic; an
+ * absent window is written 0.  win is fp32 [lines * K][c][h][w].
+ *
+ * wd_window_blend, after them: the K predictions of a line averaged into one line-wide prediction with the normalised weights
+ * wn, fp32 [lines][K][w] (the caller divides each window's profile by the sum over the windows that cover the column, in float64,
+ * and rounds to fp32 once).  Per line element (s, ch, r, J), over the windows k in ascending order that have o <= J < o + w and
+ * wn[s][k][J - o] != 0, every product and every sum rounded to fp32 on its own (no fma contraction):
+ *   acc = wn * e          for the first such window;
+ *   acc = acc + wn * e    for each later one;
+ *   line[s][ch][r][J] = acc,  or 0.0f where no window has a weight (the caller refuses such layouts).
+ * A window whose weight is 0 at that column is skipped, not multiplied: its prediction is not read there and a NaN in it does
+ * not spread.  A single covering window with weight 1 returns its value with its bits, -0.0 included (acc starts from the first
+ * product, not from 0).  win1 / line1: NULL together, or the second prediction of a guided step, blended with the same weights
+ * into a line buffer of its own in the same launch; line0 is the same either way.
+ * One output element per lane in both kernels: offsets are arbitrary, so a window's rows are not 16-byte aligned in general.
+ * WD_EINVAL (nothing launched): a NULL required pointer, win1 without line1 or the reverse, K outside 1..WD_WINDOW_MAX, w < 1,
+ * wl < w, lines, c or h < 1.  Neither allocates nor synchronises (capturable). */
+#define WD_WINDOW_MAX 32
+int wd_window_gather(const float* line, const int32_t* offsets, int lines, int K, int c, int h, int w, int wl, float* win,
+                     void* stream);
+int wd_window_blend(const float* win0, const float* win1, const float* wn, const int32_t* offsets, int lines, int K, int c,
+                    int h, int w, int wl, float* line0, float* line1, void* stream);
+
 /* strided device-to-device copy (rows x width_bytes); used to materialise a channel concat (unet.py:1750) only when
  * GroupNorm groups straddle the concat boundary. */
 int wd_copy2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch, int64_t width_bytes, int64_t rows,

@@ -2,8 +2,8 @@
 from .unet import UNetModel
 from .model import remap_attention_maps_state_dict, to_attention_maps_state_dict
 from .unetPhosc import UNetModelPhosc
-from .diffusion import EMA, Diffusion, label_padding, latent_mask_from_pixels
+from .diffusion import EMA, Diffusion, LineWindows, label_padding, latent_mask_from_pixels, window_profile
 from .vae import AutoencoderKL
 
 __all__ = ["UNetModel", "UNetModelPhosc", "Diffusion", "EMA", "label_padding", "latent_mask_from_pixels", "AutoencoderKL",
-           "remap_attention_maps_state_dict", "to_attention_maps_state_dict"]
+           "remap_attention_maps_state_dict", "to_attention_maps_state_dict", "LineWindows", "window_profile"]

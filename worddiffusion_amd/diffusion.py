@@ -9,6 +9,8 @@ at t = T-1 .. 1; ``sampling3`` skips the model on most of those steps), ``_ddim`
 ``_dpmpp`` (``sampling_dpmpp``: a subsequence spaced in log-SNR, second-order multistep) - it contributes its tables and its one
 update launch; the rest of a step's tail is written once (``_step_tail``).  Everything else a public sampler settles before the
 loop travels in one ``_Call`` record, built by ``Diffusion._sample``, the prelude and epilogue the public samplers share.
+A ``windows=`` call (``line_windows``) samples whole lines through the same loop: the state the tail works on is a line latent, and a
+model-calling step cuts it into overlapping windows of the model's width for the forward(s) and averages their predictions back.
 
 Facts preserved from the reference: the method is ``sampling`` (``sample`` is provided as
 an alias because ``sampling.py:119`` calls it); index 0 of the schedule is never used; with ``cfg_scale > 0``
@@ -142,6 +144,30 @@ class _Known(NamedTuple):
     eps: Optional[torch.Tensor]  # the caller's fixed eps, fp32 [n, C*h*w]; None: stream WD_STREAM_KNOWN of the call's seed
 
 
+WINDOW_MAX = N.DEFINES["WD_WINDOW_MAX"]  # the most windows a line may have (``wd_window_blend``)
+
+
+def window_profile(w, feather=0):
+    """The weight of a window's columns, fp32 [w]: ``min(j + 1, w - j, feather + 1) / (feather + 1)`` - 1 in the middle, a linear
+    ramp over ``feather`` columns at each end.  ``feather = 0`` is all ones: the plain average of MultiDiffusion as published."""
+    w, feather = int(w), int(feather)
+    if w < 1 or feather < 0:
+        raise ValueError(f"window_profile needs w >= 1 and feather >= 0, got w = {w}, feather = {feather}")
+    j = torch.arange(w, dtype=torch.float64)
+    ramp = torch.minimum(torch.minimum(j + 1, w - j), torch.tensor(float(feather + 1), dtype=torch.float64))
+    return (ramp / (feather + 1)).float()
+
+
+class LineWindows(NamedTuple):
+    """How the lines of a ``windows=`` sampler call are cut into windows of the model's width (``Diffusion.line_windows``); host
+    tensors, not to be written to."""
+    offsets: torch.Tensor  # int32 [n, K]: the first line column of window k of line s
+    wn: torch.Tensor  # fp32 [n, K, w]: the normalised weights ``wd_window_blend`` reads
+    width: int  # the line's latent columns
+    K: int
+    w: int
+
+
 class _Call(NamedTuple):
     """What one sampler call is to the reverse loop: everything ``Diffusion._sample`` settles on the host before anything is
     launched, and what follows from it."""
@@ -160,6 +186,7 @@ class _Call(NamedTuple):
     record: Optional[list] = None
     record_pred: Optional[list] = None
     use_graph: bool = True
+    windows: Optional[LineWindows] = None  # a line call: ``n`` counts lines, the model runs on n * K windows
 
     @property
     def mix_forwards(self):
@@ -206,9 +233,12 @@ class _Call(NamedTuple):
 class _Run:
     """The device side of one ``Diffusion._denoise`` call, filled phase by phase."""
     # guide = (second prediction or None, lerp weight, where the guided prediction is kept or None) and draw = (noise buffer or
-    # None, seed, sample_offset) are argument runs of the update launches: device pointers, of buffers this record keeps alive
-    __slots__ = ("call", "lib", "engine", "plan", "inputs", "n", "npix", "device", "stream", "seed", "blend", "zbuf", "eps_g", "guide",
-                 "draw", "graphs")
+    # None, seed, sample_offset) are argument runs of the update launches: device pointers, of buffers this record keeps alive.
+    # x, eps, eps1, n, npix are the state a step's tail works on: the plan's ``x_in`` / ``out`` / ``out1`` and the model batch for a
+    # plain call; the line latent, the blended line prediction(s) and the lines for a ``windows=`` call, whose model batch is
+    # ``nb`` = n * K and whose ``win`` = (offsets, wn) on the device with (lines, K, c, h, w, wl), the argument run of its two launches
+    __slots__ = ("call", "lib", "engine", "plan", "inputs", "n", "nb", "npix", "device", "stream", "seed", "blend", "zbuf", "eps_g",
+                 "guide", "draw", "graphs", "x", "eps", "eps1", "win")
 
 
 def latent_mask_from_pixels(mask_px):
@@ -427,7 +457,7 @@ class Diffusion:
             fn, what = (lib.wd_ddpm_step_cfg, "wd_ddpm_step_cfg") if guide else (lib.wd_ddpm_step, "wd_ddpm_step")
 
             def launch(stream):
-                N.check(fn(P.x_in.data_ptr(), P.out.data_ptr(), *guide, run.n, run.npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
+                N.check(fn(run.x.data_ptr(), run.eps.data_ptr(), *guide, run.n, run.npix, ca.data_ptr(), cb.data_ptr(), cs.data_ptr(),
                            P.t_dev.data_ptr(), *draw, stream), what)
             return launch
         # (``steps`` is T - 1 even when steps skip the model: it counts the updates)
@@ -445,7 +475,7 @@ class Diffusion:
             guide, draw = run.guide, run.draw
 
             def launch(stream):
-                N.check(lib.wd_ddim_step(P.x_in.data_ptr(), P.out.data_ptr(), *guide, run.n, run.npix, *(t.data_ptr() for t in c),
+                N.check(lib.wd_ddim_step(run.x.data_ptr(), run.eps.data_ptr(), *guide, run.n, run.npix, *(t.data_ptr() for t in c),
                                          P.k_dev.data_ptr(), P.t_dev.data_ptr(), *draw, stream), "wd_ddim_step")
             return launch
         stats = dict(sampler="ddim", steps=len(tau), eta=float(eta), timesteps=list(tau))
@@ -461,11 +491,11 @@ class Diffusion:
 
         def update(lib, P, run):
             c = [t.to(run.device) for t in tabs]
-            x0_prev = torch.empty_like(P.x_in)  # (the first step does not read it: c5[0] == 0; the blend changes x alone)
+            x0_prev = torch.empty_like(run.x)  # (the first step does not read it: c5[0] == 0; the blend changes x alone)
             guide = run.guide
 
             def launch(stream):
-                N.check(lib.wd_dpmpp_step(P.x_in.data_ptr(), P.out.data_ptr(), *guide, x0_prev.data_ptr(), run.n, run.npix,
+                N.check(lib.wd_dpmpp_step(run.x.data_ptr(), run.eps.data_ptr(), *guide, x0_prev.data_ptr(), run.n, run.npix,
                                           *(t.data_ptr() for t in c), P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
             return launch
         stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
@@ -499,7 +529,7 @@ class Diffusion:
         w[rows] = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(len(rows)), dtype=torch.float32)
         return w, len(rows)
 
-    def _known_setup(self, n, known, known_mask=None, start=None, known_noise="auto", x_T=None, *, draws_noise, tau=None):
+    def _known_setup(self, n, known, known_mask=None, start=None, known_noise="auto", x_T=None, *, draws_noise, tau=None, width=None):
         """The ``known`` / ``known_mask`` / ``start`` / ``known_noise`` arguments of a sampler call, validated and settled on the
         host (no device, no library): a ``_Known``, or None where the call passes none of them.
 
@@ -511,7 +541,8 @@ class Diffusion:
                      ``_Known.tau``, and the level noised to, ``_Known.start``, is the first of them.
         known_noise  "fresh": the blend draws its noise per step (RePaint); "fixed": one eps per sample, the one that noises to
                      ``start``; a tensor [n, C, h, w]: fixed and given; "auto": "fresh" where the call draws step noise itself
-                     (``draws_noise``: DDPM, DDIM with eta > 0), "fixed" otherwise - a deterministic sampler stays one."""
+                     (``draws_noise``: DDPM, DDIM with eta > 0), "fixed" otherwise - a deterministic sampler stays one.
+        width        the latent columns of a line of a ``windows=`` call, which take the place of w in every shape above."""
         T = self.noise_steps
         if known is None:
             if known_mask is not None or start is not None or not (isinstance(known_noise, str) and known_noise == "auto"):
@@ -519,7 +550,7 @@ class Diffusion:
             return None
         if known_mask is None and start is None:
             raise ValueError("known needs a known_mask (the region to keep), a start level, or both")
-        h, w = self.img_size[0] // 8, self.img_size[1] // 8
+        h, w = self.img_size[0] // 8, self.img_size[1] // 8 if width is None else int(width)
         x0 = torch.as_tensor(known)
         if not x0.is_floating_point() or x0.dim() != 4 or x0.shape[0] != n or tuple(x0.shape[2:]) != (h, w):
             raise ValueError(f"known must be a float tensor [{n}, C, {h}, {w}], got {x0.dtype} {tuple(x0.shape)}")
@@ -562,6 +593,92 @@ class Diffusion:
             mode = "fixed"
         return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
 
+    def line_windows(self, n, K, overlap=0, offsets=None, width=None, weight=None, feather=0):
+        """How ``n`` lines of ``K`` words each are cut into windows of the model's latent width w (``img_size[1] // 8``), for the
+        ``windows=`` argument of the samplers: a ``LineWindows``, settled on the host - nothing is launched.
+        offsets  None: window k begins at column k * (w - overlap), the same in every line; or ints [K] / [n, K] in 0 .. width - w.
+        width    the line's latent columns; None: K * w - (K - 1) * overlap.
+        weight   what a window's columns weigh in the average, >= 0, [w], [K, w] or [n, K, w]; None: ``window_profile(w, feather)``.
+        The normalised table is wn[s, k, j] = weight[s, k, j] / (the sum of the weights of the windows that cover column
+        offsets[s, k] + j), evaluated in float64 and rounded to fp32 once, as the sampler tables are.  Every column must be covered
+        (some window has wn > 0 there).  ValueError: an offset outside its range, a negative weight, K > WD_WINDOW_MAX, an uncovered
+        column (the message names the line and the column)."""
+        w = self.img_size[1] // 8
+        n, K = int(n), int(K)
+        if n < 1 or not 1 <= K <= WINDOW_MAX:
+            raise ValueError(f"line_windows needs n >= 1 lines of 1 .. {WINDOW_MAX} (WD_WINDOW_MAX) windows, got n = {n}, K = {K}")
+        overlap = int(overlap)
+        if not 0 <= overlap < w:
+            raise ValueError(f"overlap must be in 0 .. {w - 1} latent columns, got {overlap}")
+        if offsets is None:
+            off = (torch.arange(K, dtype=torch.int64) * (w - overlap)).expand(n, K)
+        else:
+            off = torch.as_tensor(offsets)
+            if off.is_floating_point() or off.dtype == torch.bool or tuple(off.shape) not in ((K,), (n, K)):
+                raise ValueError(f"offsets must be integers [{K}] or [{n}, {K}], got {off.dtype} {tuple(off.shape)}")
+            off = off.to(torch.int64).cpu().expand(n, K)
+        width = K * w - (K - 1) * overlap if width is None else int(width)
+        if width < w:
+            raise ValueError(f"a line is at least one window wide: width {width} < w = {w}")
+        bad = ((off < 0) | (off > width - w)).nonzero()
+        if len(bad):
+            s, k = (int(v) for v in bad[0])
+            raise ValueError(f"offset {int(off[s, k])} of window {k} of line {s} lies outside 0 .. {width - w} (width {width}, w = {w})")
+        wt = window_profile(w, feather) if weight is None else torch.as_tensor(weight)
+        if not wt.is_floating_point() or tuple(wt.shape) not in ((w,), (K, w), (n, K, w)):
+            raise ValueError(f"weight must be a float tensor [{w}], [{K}, {w}] or [{n}, {K}, {w}], got {wt.dtype} {tuple(wt.shape)}")
+        wt = wt.detach().to(torch.float32).cpu().expand(n, K, w)
+        if not bool((torch.isfinite(wt) & (wt >= 0)).all()):
+            raise ValueError("weight values must be finite and >= 0")
+        cols = (off[:, :, None] + torch.arange(w, dtype=torch.int64)).reshape(n, K * w)
+        total = torch.zeros(n, width, dtype=torch.float64).scatter_add_(1, cols, wt.double().reshape(n, K * w))
+        div = total.gather(1, cols).reshape(n, K, w)
+        wn = torch.where(div > 0, wt.double() / div, torch.zeros((), dtype=torch.float64)).float().contiguous()
+        covered = torch.zeros(n, width, dtype=torch.float32).scatter_add_(1, cols, (wn > 0).float().reshape(n, K * w)) > 0
+        if not bool(covered.all()):
+            s, J = (int(v) for v in (~covered).nonzero()[0])
+            raise ValueError(f"line {s}: column {J} is covered by no window (every column needs a window with a weight > 0 there)")
+        return LineWindows(off.to(torch.int32).contiguous(), wn, width, K, w)
+
+    def _line_setup(self, model, n, windows, x_text, labels, phoscLabels, attention, mix_rate, style_pairs):
+        """The ``windows`` argument of a sampler call and what it changes of the call's inputs, settled on the host before anything
+        is launched or drawn: (the model batch n * K, the n * K words, writer ids and PHOSC labels in model-batch order
+        b = s * K + k).  Refuses what does not compose with lines (NotImplementedError): ``attention=`` and writer-style
+        interpolation."""
+        K = windows.K
+        if attention is not None and attention is not False:
+            raise NotImplementedError("attention= with windows=: per-character maps of a line are not built")
+        if style_pairs is not None or (mix_rate is not None and getattr(model, "interpolation", False)):
+            raise NotImplementedError("writer-style interpolation (mix_rate / style_pairs) with windows=")
+        rows = list(x_text) if not isinstance(x_text, str) else None
+        if rows is not None and len(rows) == K and all(isinstance(v, str) for v in rows):
+            rows = [rows] * n  # one list of K words for every line
+        if rows is None or len(rows) != n or any(isinstance(r, str) or len(r) != K or not all(isinstance(v, str) for v in r) for r in rows):
+            raise ValueError(f"x_text of a windows= call must be a list of {n} lists of {K} words, or one list of {K} words for all lines")
+        words = [v for r in rows for v in r]
+        if labels is not None:
+            labels = torch.as_tensor(labels)
+            if tuple(labels.shape) != (n,):
+                raise ValueError(f"labels of a windows= call must hold one writer per line [{n}], got {tuple(labels.shape)}")
+            labels = labels.repeat_interleave(K)
+        if phoscLabels is not None:
+            p = torch.as_tensor(phoscLabels)
+            if not ((p.dim() == 3 and tuple(p.shape[:2]) == (n, K)) or (p.dim() == 2 and p.shape[0] == n * K)):
+                raise ValueError(f"phoscLabels of a windows= call must be [{n}, {K}, L] or [{n * K}, L], got {tuple(p.shape)}")
+            phoscLabels = p.reshape(n * K, p.shape[-1])
+        return n * K, words, labels, phoscLabels
+
+    def _line_width(self, windows, n):
+        """The latent columns of a line of the call (None without ``windows``), after checking that the layout is this call's."""
+        if windows is None:
+            return None
+        if not isinstance(windows, LineWindows):
+            raise TypeError(f"windows must be what Diffusion.line_windows returns, not {type(windows).__name__}")
+        if tuple(windows.offsets.shape) != (n, windows.K) or windows.w != self.img_size[1] // 8:
+            raise ValueError(f"windows lays out {windows.offsets.shape[0]} lines of windows {windows.w} wide; the call has n = {n} "
+                             f"lines and the model's latent is {self.img_size[1] // 8} wide")
+        return windows.width
+
     def _denoise(self, model, n, text_features, labels, phosc, device, call):
         """The one reverse loop of every sampler (``_ddpm`` / ``_ddim`` / ``_dpmpp``); ``call`` is the ``_Call`` of ``_sample``.
         ``_plan_call`` refuses and plans; then, on a side stream, ``_start_latent`` and ``_upload`` fill the plan's buffers,
@@ -590,30 +707,50 @@ class Diffusion:
 
     def _plan_call(self, model, n, text_features, labels, phosc, device, call):
         """Refuses ids that do not fit their tables (host tensors: nothing is launched for them and no device sync), repacks
-        weights that changed (``engine.refresh_weights``), gets the launch plan and settles the call's seed.  Launches nothing else."""
+        weights that changed (``engine.refresh_weights``), gets the launch plan and settles the call's seed.  Launches nothing else.
+        A ``windows=`` call plans the forward at the model batch n * K and the model's own h, w; its ``npix`` is the line's."""
         run = _Run()
         run.call, run.lib, run.engine, run.n, run.device, run.graphs = call, N.lib(), model.engine, n, device, []
+        win = call.windows
+        run.nb = n if win is None else n * win.K
         if call.mix is not None:
             run.engine.check_pairs(call.mix[0])  # first: nothing is launched for an id that does not fit the table
             labels = None  # unused in this mode (unet.py:1558-1573)
         run.engine.refresh_weights()
         run.engine.check_ids(text_features, labels, phosc, need_y=call.mix is None)
         run.inputs = (text_features, labels, phosc)
-        run.plan = run.engine.plan(n, self.img_size[0] // 8, self.img_size[1] // 8, text_features.shape[1],
+        run.plan = run.engine.plan(run.nb, self.img_size[0] // 8, self.img_size[1] // 8, text_features.shape[1],
                                    0 if phosc is None else phosc.shape[1], **call.plan_keywords)
+        shape = tuple(run.plan.x_in.shape[1:]) if win is None else tuple(run.plan.x_in.shape[1:3]) + (win.width,)
+        run.npix = math.prod(shape)
+        if win is not None:  # (a plain call's x_T and noise are checked by the copies that read them, as ever)
+            given = [("x_T", call.x_T)] + [(f"noise[{i}]", z) for i, z in enumerate(call.noise or ())]
+            for name, t in given:
+                if t is not None and tuple(t.shape) != (n,) + shape:
+                    raise ValueError(f"{name} of a windows= call must be line-shaped {[n, *shape]}, got {list(t.shape)}")
         run.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if call.seed is None else int(call.seed)
-        run.npix = run.plan.x_in[0].numel()
         if call.known is not None and call.known.x0.shape[1] != run.npix:
-            raise ValueError(f"known holds {call.known.x0.shape[1]} values per sample, the model's latent {run.npix} "
-                             f"{tuple(run.plan.x_in.shape[1:])}")
+            raise ValueError(f"known holds {call.known.x0.shape[1]} values per sample, the model's latent {run.npix} {shape}")
         return run
 
     def _start_latent(self, run):
-        """Fills ``P.x_in``, the latent the loop starts from: the known latents noised to ``known.start`` (``wd_noise_images`` with
+        """Fills ``run.x``, the latent the loop starts from: the known latents noised to ``known.start`` (``wd_noise_images`` with
         the call's fixed eps - the caller's, or ``wd_randn`` on stream WD_STREAM_KNOWN of the seed at the global rows), the
         caller's ``x_T``, or ``wd_randn``.  With a mask, ``run.blend`` = (x0, mask, eps or None, sqrt_ah, sqrt_1m_ah) on the device is
-        what every step's ``wd_known_blend`` reads (eps None: it draws its noise per step)."""
+        what every step's ``wd_known_blend`` reads (eps None: it draws its noise per step).
+        First it settles the state a step's tail works on (``run.x`` / ``eps`` / ``eps1``): the plan's own buffers, or, for a
+        ``windows=`` call, the line latent and line prediction(s) with the layout's offsets and weights on the device
+        (``run.win``) - the start latent is then the line's: line s depends on (seed, sample_offset + s) only."""
         call, lib, P, n, npix, device, st = run.call, run.lib, run.plan, run.n, run.npix, run.device, run.stream
+        if call.windows is None:
+            run.x, run.eps, run.eps1, run.win = P.x_in, P.out, P.out1 if call.two else None, None
+        else:
+            W = call.windows
+            c, h, w = P.x_in.shape[1:]
+            run.x = torch.empty((n, c, h, W.width), dtype=torch.float32, device=device)
+            run.eps = torch.empty_like(run.x)
+            run.eps1 = torch.empty_like(run.x) if call.two else None
+            run.win = (W.offsets.to(device), W.wn.to(device), (n, W.K, c, h, w, W.width))
         known, run.blend = call.known, None
         if known is not None:
             kx0 = known.x0.to(device)
@@ -630,11 +767,11 @@ class Diffusion:
         if known is not None and known.start is not None:
             level = torch.full((n,), known.start, dtype=torch.int64, device=device)
             N.check(lib.wd_noise_images(kx0.data_ptr(), keps.data_ptr(), level.data_ptr(), sa.data_ptr(), sb.data_ptr(), n, npix,
-                                        P.x_in.data_ptr(), st), "wd_noise_images")
+                                        run.x.data_ptr(), st), "wd_noise_images")
         elif call.x_T is not None:
-            P.x_in.copy_(call.x_T.to(device))
+            run.x.copy_(call.x_T.to(device))
         else:
-            N.check(lib.wd_randn(P.x_in.data_ptr(), n, npix, run.seed, call.sample_offset, 0, st), "wd_randn")
+            N.check(lib.wd_randn(run.x.data_ptr(), n, npix, run.seed, call.sample_offset, 0, st), "wd_randn")
 
     def _upload(self, run):
         """The call's side inputs into the plan's buffers: word ids, writer ids and PHOSC labels, the pairs and rates of an
@@ -650,11 +787,11 @@ class Diffusion:
             P.map_w.copy_(call.attention[0])
             for acc in P.maps:
                 acc.zero_()
-        run.eps_g = torch.empty_like(P.out) if (call.two and call.record_pred is not None) else None
+        run.eps_g = torch.empty_like(run.eps) if (call.two and call.record_pred is not None) else None
         P.t_dev.fill_(call.sampler.t_first)
         P.t_in.fill_(call.sampler.t_first)
-        run.zbuf = torch.zeros_like(P.x_in) if call.noise is not None else None
-        run.guide = (P.out1.data_ptr(), call.scale, _dptr(run.eps_g)) if call.two else (None, 0.0, None)
+        run.zbuf = torch.zeros_like(run.x) if call.noise is not None else None
+        run.guide = (run.eps1.data_ptr(), call.scale, _dptr(run.eps_g)) if call.two else (None, 0.0, None)
         run.draw = (_dptr(run.zbuf), run.seed, call.sample_offset)
 
     def _step_tail(self, run):
@@ -662,31 +799,40 @@ class Diffusion:
         ``run_step`` when the step has two predictions), the sampler's own update launch, ``wd_known_blend`` when a region is kept
         and the advance.  A sampler indexed by t (``tau`` None) blends at the level t - 1 and advances with
         ``wd_advance_timestep``; one that visits ``tau`` (put on the device here, its step counter ``k_dev`` zeroed) blends at the
-        level of tau[k + 1] (index 0 after the last entry) and advances with ``wd_next_timestep``."""
-        call, lib, P, n, npix = run.call, run.lib, run.plan, run.n, run.npix
+        level of tau[k + 1] (index 0 after the last entry) and advances with ``wd_next_timestep``.
+        A ``windows=`` call wraps the forward(s) of a step in its two launches: ``wd_window_gather`` cuts the line into the plan's
+        ``x_in`` before them, ``wd_window_blend`` averages the plan's ``out`` (and ``out1``) into the line prediction(s) after them;
+        update and blend then work on the line, the advance on the model batch.  A step without a forward runs neither."""
+        call, lib, P, n, nb, npix = run.call, run.lib, run.plan, run.n, run.nb, run.npix
         update = call.sampler.update(lib, P, run)
         tau, two = call.sampler.tau, call.two
         forwards = 1 if (two or call.mix is not None) else call.plain_forwards
         if tau is not None:
             tau_dev = torch.tensor(tau, dtype=torch.int32, device=run.device)
             P.k_dev.zero_()
+        x, win = run.x, run.win
 
         def step(stream, forward=True):
             if forward:
+                if win is not None:
+                    N.check(lib.wd_window_gather(x.data_ptr(), win[0].data_ptr(), *win[2], P.x_in.data_ptr(), stream), "wd_window_gather")
                 for _ in range(forwards):
                     P.run_step(stream)
                 if two:  # train.py:223-228 with two different forwards: lerp(second, first, cfg_scale) feeds the update
                     P.run_step1(stream)
+                if win is not None:
+                    N.check(lib.wd_window_blend(P.out.data_ptr(), P.out1.data_ptr() if two else None, win[1].data_ptr(), win[0].data_ptr(),
+                                                *win[2], run.eps.data_ptr(), _dptr(run.eps1), stream), "wd_window_blend")
             update(stream)
             if run.blend is not None:
                 x0, mask, eps, sa, sb = run.blend
                 level = (None, None, 0) if tau is None else (P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau))
-                N.check(lib.wd_known_blend(P.x_in.data_ptr(), x0.data_ptr(), mask.data_ptr(), n, npix, sa.data_ptr(), sb.data_ptr(),
+                N.check(lib.wd_known_blend(x.data_ptr(), x0.data_ptr(), mask.data_ptr(), n, npix, sa.data_ptr(), sb.data_ptr(),
                                            P.t_dev.data_ptr(), *level, _dptr(eps), run.seed, call.sample_offset, stream), "wd_known_blend")
             if tau is None:
-                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), n, stream), "wd_advance_timestep")
+                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), nb, stream), "wd_advance_timestep")
             else:
-                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(), P.t_in.data_ptr(), n,
+                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(), P.t_in.data_ptr(), nb,
                                              stream), "wd_next_timestep")
         return step
 
@@ -721,7 +867,7 @@ class Diffusion:
         gexec, gskip = (run.graphs + [None, None])[:2]
         for row, fwd, z in call.sampler.steps:
             if record is not None:
-                record.append(P.x_in.clone())
+                record.append(run.x.clone())
             if zbuf is not None and z is not None:
                 zbuf.copy_(noise[z].to(device))
             if fwd:
@@ -731,12 +877,15 @@ class Diffusion:
             else:
                 step(st, fwd)
             if record_pred is not None and fwd:
-                record_pred.append((P.out.clone(),) if not two else (P.out.clone(), P.out1.clone(), run.eps_g.clone()))
+                pred = (P.out.clone(),) if not two else (P.out.clone(), P.out1.clone())
+                if run.win is not None:  # the window predictions, then the line prediction(s) they were blended into
+                    pred += (run.eps.clone(),) if not two else (run.eps.clone(), run.eps1.clone())
+                record_pred.append(pred + ((run.eps_g.clone(),) if two else ()))
 
     def _results(self, run):
         """x, cloned out of the plan's buffer; ``last_attention`` (the accumulators, cloned likewise, or None) and ``last_stats``."""
         call, P, known = run.call, run.plan, run.call.known
-        x = P.x_in.clone()
+        x = run.x.clone()
         self.last_attention = None
         if call.attention is not None:
             self.last_attention = {k: acc.clone().reshape(run.n, mh, mw, -1)
@@ -748,6 +897,8 @@ class Diffusion:
             self.last_stats["attention_steps"] = call.attention[1]
         if call.writer_free is not None:
             self.last_stats["guidance"] = "writer_free"
+        if call.windows is not None:
+            self.last_stats.update(windows=call.windows.K, line_width=call.windows.width, model_batch=run.nb)
         return x
 
     def _guidance_setup(self, model, guidance, cfg_scale, mix):
@@ -865,11 +1016,16 @@ class Diffusion:
         nothing and drawn nothing from ``random``: the pairs are drawn last - then ``_denoise`` on the ``_Call`` (``loop``: its
         remaining fields) with the model in eval mode and in TRAIN mode afterwards, whatever happened (train.py:201,238), and
         ``_finish``.  ``bulk`` (``sampling3``): the caller has put the model in eval mode and it stays there, and ``args.latent``
-        is not looked at."""
-        device, tf, phosc = self._prepare(who, model, n, x_text, args, phoscLabels, underscore, check_latent=not bulk)
+        is not looked at.  With ``windows`` (``loop``'s, a ``LineWindows``) ``n`` counts lines: ``_line_setup`` refuses what lines do not
+        compose with and spreads words, writers and PHOSC labels over the model batch n * K; the loop and the result are the line's."""
+        nb = n
+        if loop.get("windows") is not None:
+            nb, x_text, labels, phoscLabels = self._line_setup(model, n, loop["windows"], x_text, labels, phoscLabels, attention, mix_rate,
+                                                               style_pairs)
+        device, tf, phosc = self._prepare(who, model, nb, x_text, args, phoscLabels, underscore, check_latent=not bulk)
         sampler = build()
         att = self._attention_setup(model, sampler, attention)
-        checked = self._mix_check(model, n, mix_rate, style_pairs)
+        checked = self._mix_check(model, nb, mix_rate, style_pairs)
         wf = self._guidance_setup(model, guidance, cfg_scale, checked)
         mix = None if checked is None else self._mix_table(checked, n, cfg_scale, sampler)
         call = _Call(sampler, self.noise_steps, self.tabulate_film, self.forwards_per_step, attention=att, mix=mix, writer_free=wf, **loop)
@@ -885,7 +1041,7 @@ class Diffusion:
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
                  style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto", attention=None,
-                 guidance=None):
+                 guidance=None, windows=None):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
@@ -915,18 +1071,28 @@ class Diffusion:
         guided update ``torch.lerp(free, cond, cfg_scale)``; ``last_stats`` reports ``forwards_per_step == 2`` and
         ``guidance``, ``record_pred`` receives (cond, free, guided) and ``attention`` reads the conditional forward.  With
         ``cfg_scale == 0`` the call is the plain one.  Without the argument ``cfg_scale`` stays inert outside interpolation mode,
-        as in the reference, whose two forwards are identical (train.py:224-228).  Not together with the interpolation modes."""
-        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True)
+        as in the reference, whose two forwards are identical (train.py:224-228).  Not together with the interpolation modes.
+
+        ``windows=line_windows(n, K, ...)`` (DESIGN.md "Lines"): whole lines in one call, as K overlapping windows of the model's
+        width per line (MultiDiffusion).  ``n`` counts lines; ``x_text`` is n lists of K words (or one list for every line),
+        ``labels`` one writer per line, ``phoscLabels`` [n, K, L] or [n * K, L]; ``x_T``, ``noise``, ``known``, ``known_mask``,
+        ``start`` and ``record`` are line-shaped, [n, C, h, width], and so is the result.  Every model-calling step gathers the
+        windows, runs the forward(s) at batch n * K and averages the predictions into one line prediction, on which the ordinary
+        update, guidance and known-region blend run; line s depends on (seed, sample_offset + s) only.  ``last_stats`` gains
+        ``windows``, ``line_width`` and ``model_batch``; ``record_pred`` receives (window predictions, line prediction), or (window
+        cond, window free, line cond, line free, guided line).  ``attention=`` and the interpolation modes are refused
+        (NotImplementedError) before anything is launched or drawn."""
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True, width=self._line_width(windows, n))
         return self._sample("sampling", model, vae, n, x_text, labels, args, lambda: self._ddpm(start=None if kn is None else kn.start),
                             phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
                             style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
-                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph)
+                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph, windows=windows)
 
     @torch.no_grad()
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
                       phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
                       use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None, start=None,
-                      known_noise="auto", attention=None, guidance=None):
+                      known_noise="auto", attention=None, guidance=None, windows=None):
         """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
         ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
         deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
@@ -939,10 +1105,11 @@ class Diffusion:
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling``; with ``start`` the call visits the entries of
         its usual schedule that are <= start (``steps`` and ``timesteps`` of ``last_stats`` are the retained ones, FiLM rows,
         pairs and ``noise`` are indexed by them) and the first of them is the level noised to.  With ``eta = 0`` the default
-        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention`` and
-        ``guidance`` as in ``sampling``."""
+        ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention``,
+        ``guidance`` and ``windows`` as in ``sampling``."""
         tau = self.ddim_timesteps(steps, timesteps)
-        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau)
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau,
+                               width=self._line_width(windows, n))
         if kn is not None:
             tau = kn.tau
         if noise is not None and len(noise) != len(tau):
@@ -950,13 +1117,13 @@ class Diffusion:
         return self._sample("sampling_ddim", model, vae, n, x_text, labels, args, lambda: self._ddim(tau, eta),
                             phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
                             style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
-                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph)
+                            sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph, windows=windows)
 
     @torch.no_grad()
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
                        mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
                        record_pred=None, use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None,
-                       start=None, known_noise="auto", attention=None, guidance=None):
+                       start=None, known_noise="auto", attention=None, guidance=None, windows=None):
         """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
         ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
         the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
@@ -967,19 +1134,19 @@ class Diffusion:
         returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
         ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``.
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling_ddim`` (the default noise is the fixed eps: no
-        step draws); the first retained step is first order, like the first step of any call.  ``attention`` and ``guidance`` as in
-        ``sampling``."""
+        step draws); the first retained step is first order, like the first step of any call.  ``attention``, ``guidance`` and
+        ``windows`` as in ``sampling``."""
         tau = self.dpmpp_timesteps(steps, spacing, timesteps)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
-        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=False, tau=tau)
+        kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=False, tau=tau, width=self._line_width(windows, n))
         if kn is not None:
             tau = kn.tau
         return self._sample("sampling_dpmpp", model, vae, n, x_text, labels, args,
                             lambda: self._dpmpp(tau, order, None if timesteps is not None else spacing), phoscLabels=phoscLabels,
                             underscore=underscore, attention=attention, mix_rate=mix_rate, style_pairs=style_pairs, cfg_scale=cfg_scale,
                             guidance=guidance, known=kn, x_T=x_T, seed=seed, sample_offset=sample_offset, record=record,
-                            record_pred=record_pred, use_graph=use_graph)
+                            record_pred=record_pred, use_graph=use_graph, windows=windows)
 
     sample = sampling  # sampling.py:119 / full_sampling.py:167 call .sample(...)
 
@@ -993,7 +1160,7 @@ class Diffusion:
     @torch.no_grad()
     def sampling3(self, epoch, x_t, words, phoscLabels, model, model1, vae, emaOld, noiseInput, n, x_text, labels, args,
                   mix_rate=None, cfg_scale=3, seed=None, sample_offset=0, use_graph=True, x_T=None, noise=None, record=None, *,
-                  style_pairs=None, attention=None):
+                  style_pairs=None, attention=None, windows=None):
         """Bulk-regeneration sampler of ``regenerateFromtrain2.py:465-648`` (same argument order): the predicted noise is
         refreshed only on the steps of ``sampling3_calls_model`` (1 in 5) and reused in between, and unless
         ``args.fullSampling`` the update is deterministic (no ``sqrt(beta) * noise`` term, ``:618``).  ``noiseInput == 0``
@@ -1006,7 +1173,10 @@ class Diffusion:
         each of those steps and none for the others.  (The reference's own loop accepts ``mix_rate`` and does not hand it to
         the model, ``:587,591``: there the argument has no effect; here it selects the blend, as it does in ``sampling``.)
         ``attention`` as in ``sampling``: the steps that reuse the previous prediction run no forward and add nothing, and
-        ``attention_steps`` counts the model-calling steps of the window only."""
+        ``attention_steps`` counts the model-calling steps of the window only.  ``windows`` (line sampling, see ``sampling``) is
+        refused: this loop regenerates single words."""
+        if windows is not None:
+            raise NotImplementedError("sampling3 with windows=: the step-skipping bulk sampler regenerates single words")
         if emaOld == 1:
             model = model1
         model.eval()  # and it stays in eval mode: ``#model.train()`` is commented out at regenerateFromtrain2.py:622

@@ -15,6 +15,8 @@ depend on the batch size or the number of ranks.  Host-side pieces restated from
                         (``latents.build_latent_cache``), then exit.
   * ``--init_latents`` - regenerate FROM such a cache: ``--keep_cols A:B`` keeps those latent columns of every row's own latent
                         and re-draws the rest, ``--start T`` begins from the latent noised to level T (``regenerate(known=...)``).
+  * ``--lines``       - whole lines instead of gt rows: every ``writer<TAB>word word ...`` row of the file is one sampler call's
+                        line of overlapping word windows (``regenerate_lines``, ``Diffusion.sampling(..., windows=)``).
   * ``interpolate``   - one strip per gt row: the row's word in ``mix_steps`` styles from writer ``s1`` to writer ``s2``
                         (``sampling.py --interpolation --mix_rate`` renders one such blend of two random writers per call).
 """
@@ -273,10 +275,79 @@ def interpolate(model, diffusion, rows: Sequence[Tuple[str, str, str]], args, st
     return start, outs
 
 
+def read_lines(path: str) -> List[Tuple[str, Tuple[str, ...]]]:
+    """[(writer id, the words of the line)] of a ``--lines`` file: one row per line, ``writer<TAB>word word ...``.  Empty rows are
+    skipped; a row without a tab or without a word is an error that names it."""
+    rows = []
+    with open(path, "r") as f:
+        for i, line in enumerate(f.read().splitlines()):
+            if not line.strip():
+                continue
+            writer, tab, text = line.partition("\t")
+            if not tab or not writer.strip() or not text.split():
+                raise ValueError(f"{path}, row {i + 1}: expected 'writer<TAB>word word ...', got {line!r}")
+            rows.append((writer.strip(), tuple(text.split())))
+    return rows
+
+
+@torch.no_grad()
+def regenerate_lines(model, diffusion, lines: Sequence[Tuple[str, Sequence[str]]], wr_dict: Dict[str, int], args, vae=None,
+                     batch: int = 64, out_dir: Optional[str] = None, seed: int = 0, rank: Optional[int] = None,
+                     world: Optional[int] = None, overlap: int = 2, feather: int = 0, phosc_of=None, sampler: str = "ddpm",
+                     ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
+                     guidance: Optional[str] = None, cfg_scale: float = 3.0):
+    """Samples every line once (this rank's shard of them) through the ``windows=`` argument of the chosen sampler: a line of K
+    words is K windows of the model's width that overlap by ``overlap`` latent columns, weighted by ``window_profile(w, feather)``.
+    One call takes lines of one K, so the lines are ordered by (K, row index) - a line's place in that order is its global sample
+    index in the noise stream, whatever the batch size or the number of ranks - and every group runs in chunks of ``batch // K``
+    lines (at least 1).  Returns {row index: latent or image}.  With ``out_dir`` row i is written as ``line_<i>.png`` (a VAE was
+    given) or ``line_<i>.npy`` (latents)."""
+    _check_sampler(sampler)
+    r0, w0, _ = env_rank_world()
+    rank = r0 if rank is None else rank
+    world = w0 if world is None else world
+    order = sorted(range(len(lines)), key=lambda i: (len(lines[i][1]), i))
+    first, count = shard_range(len(order), rank, world)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    outs = {}
+    pos = first
+    while pos < first + count:
+        K = len(lines[order[pos]][1])
+        per_call = max(1, batch // K)
+        chunk = [i for i in order[pos:min(pos + per_call, first + count)] if len(lines[i][1]) == K]  # (a chunk ends with its group)
+        n = len(chunk)
+        words = [list(lines[i][1]) for i in chunk]
+        labels = torch.tensor([wr_dict[lines[i][0]] for i in chunk], dtype=torch.int64)
+        kw = dict(seed=seed, sample_offset=pos, windows=diffusion.line_windows(n, K, overlap=overlap, feather=feather))
+        if phosc_of is not None:
+            kw.update(phoscLabels=torch.stack([torch.stack([phosc_of(wd) for wd in row]) for row in words]))
+        if guidance is not None:
+            kw.update(guidance=guidance, cfg_scale=cfg_scale)
+        if sampler == "ddim":
+            res = diffusion.sampling_ddim(model, vae, n, words, labels, args, steps=ddim_steps, eta=eta, **kw)
+        elif sampler == "dpmpp":
+            res = diffusion.sampling_dpmpp(model, vae, n, words, labels, args, steps=dpmpp_steps, order=dpmpp_order, spacing=dpmpp_spacing,
+                                           **kw)
+        else:
+            res = diffusion.sampling(model, vae, n, words, labels, args, **kw)
+        for i, item in zip(chunk, res.detach().cpu()):
+            outs[i] = item
+            if out_dir is None:
+                continue
+            if vae is None:
+                np.save(os.path.join(out_dir, f"line_{i}.npy"), item.numpy())
+            else:
+                arr = (item.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).numpy()
+                write_png(os.path.join(out_dir, f"line_{i}.png"), arr if arr.shape[2] == 3 else arr[:, :, 0])
+        pos += n
+    return outs
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The command line of ``main`` (flags follow ``full_sampling.py:40-66`` where they exist); needs no device."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--gt_train", required=True)
+    ap.add_argument("--gt_train", default=None, help="the ground-truth list: 'writer,image word' rows (required unless --lines)")
     ap.add_argument("--models_path", default=None, help="directory holding models/ema_ckpt.pt (reference layout)")
     ap.add_argument("--save_path", required=True)
     ap.add_argument("--writer_dict", default="./writers_dict_train.json")
@@ -334,12 +405,30 @@ def build_parser() -> argparse.ArgumentParser:
                          "middle / output [rows, h, w, 10], images, words); base model only")
     ap.add_argument("--attn_window", default=None, metavar="HI:LO",
                     help="--attn_maps: average over the model-calling steps with LO <= t <= HI only (default: all of them)")
+    ap.add_argument("--lines", default=None, metavar="FILE",
+                    help="sample whole lines instead of the gt rows: every row of FILE is 'writer<TAB>word word ...' and becomes one "
+                         "image (or latent), line_<row index>, of overlapping word windows denoised together")
+    ap.add_argument("--line_overlap", type=int, default=2, metavar="V", help="--lines: latent columns two neighbouring words share")
+    ap.add_argument("--line_feather", type=int, default=0, metavar="F",
+                    help="--lines: latent columns over which a window's weight ramps up at its ends (0: the plain average)")
     return ap
 
 
 def parse_args(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.gt_train is None and a.lines is None:
+        ap.error("the following arguments are required: --gt_train")
+    if a.lines is not None:
+        for flag, on in (("--gt_train", a.gt_train), ("--skip_steps 1", a.skip_steps), ("--style_pair", a.style_pair),
+                         ("--mix_rate", a.mix_rate), ("--init_latents", a.init_latents), ("--attn_maps", a.attn_maps),
+                         ("--encode_images", a.encode_images)):
+            if on:
+                ap.error(f"--lines does not take {flag}")
+        if not 0 <= a.line_overlap < 32:
+            ap.error(f"--line_overlap must be in [0, 31] latent columns, not {a.line_overlap}")
+        if a.line_feather < 0:
+            ap.error(f"--line_feather must be >= 0, not {a.line_feather}")
     if a.sampler != "ddpm" and a.skip_steps:
         ap.error(f"--sampler {a.sampler} and --skip_steps 1 are two ways to run fewer steps: choose one")
     if a.sampler == "ddim" and not 1 <= a.ddim_steps <= a.noise_steps - 1:
@@ -405,7 +494,8 @@ def main(argv=None):
         return
     args = types.SimpleNamespace(device=dev, interpolation=bool(a.interpolation), charLevelEmb=0, charImages=0, attentionMaps=0, ocrTraining=0,
                                  imgConditioned=0, wrdChrWrStyl=0, phosc=a.phosc, phos=0, latent=True, fullSampling=False)
-    rows = read_gt(a.gt_train)
+    lines = read_lines(a.lines) if a.lines is not None else None
+    rows = read_gt(a.gt_train) if lines is None else [(writer, f"line_{i}", " ".join(words)) for i, (writer, words) in enumerate(lines)]
     wr = writer_dict(rows, a.writer_dict)
     cls = UNetModelPhosc if a.phosc else UNetModel
     unet = cls(image_size=(64, 256), in_channels=4, model_channels=a.emb_dim, out_channels=4, num_res_blocks=a.num_res_blocks,
@@ -425,6 +515,13 @@ def main(argv=None):
         if not a.alphabet_csv:
             ap.error("--phosc 1 needs --alphabet_csv (the PHOS shape-count table)")
         phosc_of = make_phosc_of(a.alphabet_csv)
+    if lines is not None:
+        res = regenerate_lines(ema_model, diffusion, lines, wr, args, vae=vae, batch=a.batch_size, out_dir=os.path.join(a.save_path, "images"),
+                               seed=a.seed, overlap=a.line_overlap, feather=a.line_feather, phosc_of=phosc_of, sampler=a.sampler,
+                               ddim_steps=a.ddim_steps, eta=a.eta, dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order,
+                               dpmpp_spacing=a.dpmpp_spacing, guidance=a.guidance, cfg_scale=a.cfg_scale)
+        print(f"[rank {rank}/{world}] {len(res)} of {len(lines)} lines written to {a.save_path}/images")
+        return
     if a.style_pair is not None:
         start, res = interpolate(ema_model, diffusion, rows, args, tuple(a.style_pair), a.mix_steps, vae=vae,
                                  out_dir=os.path.join(a.save_path, "images"), seed=a.seed, phosc_of=phosc_of, sampler=a.sampler,
