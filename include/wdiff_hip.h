@@ -594,6 +594,36 @@ int wd_known_blend(float* x, const float* x0, const float* mask, int batch, int 
                    const float* sqrt_1m_ah, const int32_t* t_dev, const int32_t* k_dev, const int32_t* tau, int S,
                    const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
 
+/* Resampling jumps of a known-region call (RePaint, Lugmayr et al. 2022, section 4.2 and algorithm 1).  The reverse loop of a
+ * resampled call walks a table of entries: entry k = *k_dev starts from the level tau'[k] (the table wd_next_timestep and
+ * wd_known_blend read) and is either a sampler's ordinary step down the schedule or a jump back UP it.
+ *
+ * wd_forward_jump, the up entry: x [batch][n_per_sample] at the level `from` is diffused forward to the level `to` > from,
+ *   x = g1[k] * x + g2[k] * z,   both products and the sum rounded to fp32 on their own (no fma contraction),
+ * with g1 = sqrt(Q/A), g2 = sqrt(1 - Q/A), A = alpha_hat[from], Q = alpha_hat[to], tabulated per walk entry by the caller
+ * (float64, rounded to fp32 once; fp32 [entries], read at k only).  Kept and free cells are diffused alike.
+ *
+ * wd_walk_randn: out [batch][n_per_sample] = N(0,1), the noise a down entry's kernels then read through their `noise`
+ * argument - `which` = WD_WALK_STEP for the step's z, WD_WALK_BLEND for the z of a wd_known_blend that draws per step.
+ *
+ * The draw, in both: z is read from `noise` when given (wd_forward_jump), else it comes from Philox4x32-10 keyed by seed with
+ * counter (element / 4, WD_TAG_WALK | which << 26 | k, sample_offset + sample index), which = WD_WALK_JUMP for the jump.  k is
+ * the WALK INDEX, not the timestep: a level that is visited twice draws afresh on each visit, which the timestep-keyed draws
+ * of wd_ddpm_step, wd_ddim_step and wd_known_blend would not.  A row's draws depend on (seed, sample_offset + row, k) only.
+ * WD_TAG_WALK is the fourth tag family and the four are disjoint in the tag's top two bits: a bare timestep t < 2^30 has 00,
+ * WD_TAG_KNOWN | p (p < 2^30) has 01, 0x80000000 | stream_id (stream ids < 2^30) has 10, and WD_TAG_WALK | which << 26 | k
+ * (which <= 2 < 4, k < 2^26, so everything below bit 28) has 11.  The caller keeps k < 2^26; the kernels use k's low 26 bits.
+ * WD_EINVAL (nothing launched): a NULL required pointer (x, g1, g2, k_dev; out, k_dev), n_per_sample % 4, x / noise / out not
+ * 16-byte aligned, which outside 0 .. 2.  Neither allocates nor synchronises (capturable). */
+#define WD_TAG_WALK 0xC0000000
+#define WD_WALK_STEP 0
+#define WD_WALK_BLEND 1
+#define WD_WALK_JUMP 2
+int wd_forward_jump(float* x, int batch, int n_per_sample, const float* g1, const float* g2, const int32_t* k_dev,
+                    const float* noise, uint64_t seed, uint64_t sample_offset, void* stream);
+int wd_walk_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sample_offset, int which,
+                  const int32_t* k_dev, void* stream);
+
 /* Line sampling as overlapping windows (MultiDiffusion, Bar-Tal et al. 2023): a line latent, fp32 [lines][c][h][wl], is denoised
  * as K windows of the model's own width w per line; window k of line s is model batch row b = s * K + k and begins at line
  * column o = offsets[b] (int32 [lines][K], on the device so that a captured graph replays).  A window that does not fit

@@ -97,6 +97,7 @@ VAE_MAX_LATENT, STREAM_VAE_POSTERIOR, STREAM_DROPOUT0, NCLASS = (
     DEFINES[n] for n in ("WD_VAE_MAX_LATENT", "WD_STREAM_VAE_POSTERIOR", "WD_STREAM_DROPOUT0", "WD_NCLASS"))
 STREAM_KNOWN, TAG_KNOWN = DEFINES["WD_STREAM_KNOWN"], DEFINES["WD_TAG_KNOWN"]
 STREAM_LABEL_DROP = DEFINES["WD_STREAM_LABEL_DROP"]
+TAG_WALK, WALK_STEP, WALK_BLEND, WALK_JUMP = (DEFINES[n] for n in ("WD_TAG_WALK", "WD_WALK_STEP", "WD_WALK_BLEND", "WD_WALK_JUMP"))
 CLASS_NAMES = ("gemm", "gn_stats", "gn_apply", "layernorm", "attention", "other", "gemm_other_tiles", "gemm_splitk_reduce",
                "gemm_two_per_cu", "gemm_weights_to_registers", "feed_forward_fused", "weight_gradient", "gemm_small_maps_whole_k")
 assert len(CLASS_NAMES) == NCLASS, "CLASS_NAMES must name every profiling class of the header (WD_NCLASS)"

@@ -93,22 +93,7 @@ __global__ void tok_to_nchw_kernel(const float* __restrict__ x, int ld, int batc
     }
 }
 
-// ---- normal draws from Philox4x32-10 (wd_philox.h) ---------------------------------------------------
-__device__ __forceinline__ float4 philox_normal4(uint64_t seed, uint64_t sample, uint32_t tag, uint32_t e4) {
-    uint32_t c[4] = {e4, tag, (uint32_t)sample, (uint32_t)(sample >> 32)};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    // Box-Muller on (0,1] uniforms
-    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(c[1] >> 8)) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u3 = ((float)(c[3] >> 8)) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    float s0, c0, s1, c1;
-    sincosf(6.283185307179586f * u1, &s0, &c0);
-    sincosf(6.283185307179586f * u3, &s1, &c1);
-    return make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
-}
-
+// ---- normal draws from Philox4x32-10: philox_normal4 (wd_philox.h) -----------------------------------
 // x = ca[t] * (x - cb[t] * eps) + cs[t] * z  with the reference's rounding order (no contraction)
 __global__ void ddpm_step_kernel(float* __restrict__ x, const float* __restrict__ eps, int batch, int n4,
                                  const float* __restrict__ ca, const float* __restrict__ cb,

@@ -22,6 +22,23 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
     }
 }
 
+// ---- normal draws: Box-Muller on (0,1] uniforms.  Four N(0,1) values for the elements 4 e4 .. 4 e4 + 3 of sample `sample`
+// (wd_misc.hip: the step kernels, wd_randn, the posterior; wd_resample.hip: the walk's draws).  Every uniform and the angle is
+// exact or a single fp32 product, and no product here feeds a sum: the bits do not depend on the contraction mode of the file.
+__device__ __forceinline__ float4 philox_normal4(uint64_t seed, uint64_t sample, uint32_t tag, uint32_t e4) {
+    uint32_t c[4] = {e4, tag, (uint32_t)sample, (uint32_t)(sample >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    const float u1 = ((float)(c[1] >> 8)) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    const float u3 = ((float)(c[3] >> 8)) * (1.0f / 16777216.0f);
+    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+    float s0, c0, s1, c1;
+    sincosf(6.283185307179586f * u1, &s0, &c0);
+    sincosf(6.283185307179586f * u3, &s1, &c1);
+    return make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
+}
+
 // ---- training dropout (wd_dropout): the keep decision of the four consecutive elements idx .. idx + 3 of sample `row`,
 // idx = token * c + channel (a multiple of 4): one draw, element idx + k is kept iff word k >= thr.
 __device__ __forceinline__ uint64_t wd_dropout_row(const wd_dropout& d, int b) {

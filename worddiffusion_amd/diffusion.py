@@ -11,6 +11,8 @@ update launch; the rest of a step's tail is written once (``_step_tail``).  Ever
 loop travels in one ``_Call`` record, built by ``Diffusion._sample``, the prelude and epilogue the public samplers share.
 A ``windows=`` call (``line_windows``) samples whole lines through the same loop: the state the tail works on is a line latent, and a
 model-calling step cuts it into overlapping windows of the model's width for the forward(s) and averages their predictions back.
+A ``resample=`` call (``resample_walk``) walks a table of entries instead of the plain schedule: most are the sampler's steps, some
+diffuse the state forward again (``wd_forward_jump``), and every draw is keyed by the walk entry rather than by the timestep.
 
 Facts preserved from the reference: the method is ``sampling`` (``sample`` is provided as
 an alias because ``sampling.py:119`` calls it); index 0 of the schedule is never used; with ``cfg_scale > 0``
@@ -132,6 +134,26 @@ class _Sampler(NamedTuple):
     # its one update launch, which keeps them alive; the rest of a step's tail is ``Diffusion._step_tail``
     update: Callable
     stats: dict  # what ``last_stats`` reports of the sampler itself
+    walk: Optional["_Walk"] = None  # a resampled call: ``steps`` and ``tau`` are the walk's, row = index into ``noise`` = the walk index k
+
+
+WALK_MAX = 16384  # the most entries a resampled call may walk: its FiLM table has one time-MLP row per entry
+
+
+class _Walk(NamedTuple):
+    """The walk of a resampled call (``Diffusion.resample_walk``, no GPU): per entry k, in loop order."""
+    tau: list  # tau'[k]: the level entry k starts from
+    to: list  # the level it reaches: the next visited timestep (0 after the last) of a down entry, the level jumped to of an up entry
+    up: list  # bool: an up entry (``wd_forward_jump``), else a step of the sampler
+    g1: torch.Tensor  # fp32 [entries]: sqrt(alpha_hat[to] / alpha_hat[from]) at the up entries, 0 elsewhere
+    g2: torch.Tensor  # fp32 [entries]: sqrt(1 - alpha_hat[to] / alpha_hat[from]) likewise
+    resample: int
+    jump: int
+
+    @property
+    def down(self):
+        """The walk indices of the down entries."""
+        return [k for k, u in enumerate(self.up) if not u]
 
 
 class _Known(NamedTuple):
@@ -378,15 +400,16 @@ class Diffusion:
             return [T - 1]
         return list(reversed([1 + ((T - 2) * k) // (S - 1) for k in range(S)]))
 
-    def _ddim_tables(self, tau, eta, device):
+    def _ddim_tables(self, tau, eta, device, to=None):
         """The five per-step coefficients of ``wd_ddim_step`` (fp32 [S] each), with a = alpha_hat[tau[k]], p = alpha_hat of the
         predecessor and sigma = eta sqrt((1-p)/(1-a)) sqrt(1 - a/p):  c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt(p),
         c4 = sqrt(max(1 - p - sigma^2, 0)), c5 = sigma.  Evaluated in float64 from the fp32 betas (alpha and its cumprod
-        recomputed in float64: the fp32 ``1 - alpha_hat[0]`` has lost half its digits) and rounded to fp32 once."""
+        recomputed in float64: the fp32 ``1 - alpha_hat[0]`` has lost half its digits) and rounded to fp32 once.
+        ``to``: the level every entry lands on, where that is not the next entry's (the down entries of a resampled walk)."""
         ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
         tau = [int(t) for t in tau]
         a = ah[tau]
-        p = ah[tau[1:] + [0]]
+        p = ah[tau[1:] + [0] if to is None else [int(t) for t in to]]
         sigma = float(eta) * torch.sqrt((1 - p) / (1 - a)) * torch.sqrt(1 - a / p)
         c4 = torch.sqrt(torch.clamp(1 - p - sigma * sigma, min=0.0))
         return tuple(c.float().to(device).contiguous() for c in (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt(p), c4, sigma))
@@ -420,34 +443,95 @@ class Diffusion:
             tau.append(max(cand, S - k))
         return tau
 
-    def _dpmpp_tables(self, tau, order, device):
+    def _dpmpp_tables(self, tau, order, device, to=None, restart=()):
         """The five per-step coefficients of ``wd_dpmpp_step`` (fp32 [S] each), with a = alpha_hat[tau[k]], p = alpha_hat of the
         predecessor (alpha_hat[0] after the last entry, as in ``_ddim_tables``) and h_k = lambda(p) - lambda(a):
         c1 = sqrt(1-a), c2 = 1/sqrt(a), c3 = sqrt((1-p)/(1-a)), c4 = -sqrt(p) expm1(-h_k), c5 = h_k / (2 h_{k-1}).  c5 = 0 makes a
         step first order: k = 0, every k at ``order`` 1, and always the last step (no extrapolation into index 0).  Evaluated
-        in float64 from the fp32 betas and rounded to fp32 once."""
+        in float64 from the fp32 betas and rounded to fp32 once.
+        ``to`` as in ``_ddim_tables``; ``restart``: entries that are first order as well - the down entries of a resampled walk
+        that follow a jump, where the stored data prediction belongs to another level.  h_{k-1} is that of the entry before."""
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
         ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
         tau = [int(t) for t in tau]
         a = ah[tau]
-        p = ah[tau[1:] + [0]]
+        p = ah[tau[1:] + [0] if to is None else [int(t) for t in to]]
         h = 0.5 * torch.log(p / (1 - p)) - 0.5 * torch.log(a / (1 - a))
         c5 = torch.zeros_like(h)
         if order == 2 and len(tau) > 2:
             c5[1:-1] = h[1:-1] / (2 * h[:-2])
+        c5[list(restart)] = 0.0
         tabs = (torch.sqrt(1 - a), 1 / torch.sqrt(a), torch.sqrt((1 - p) / (1 - a)), -torch.sqrt(p) * torch.expm1(-h), c5)
         return tuple(c.float().to(device).contiguous() for c in tabs)
 
     # --------------------------------------------------------------------------------------------------
-    def _ddpm(self, calls_model=None, deterministic=False, start=None):
+    def resample_walk(self, tau, jump=10, resample=1):
+        """The walk of a resampled call over the visited timesteps ``tau`` (RePaint, Lugmayr et al. 2022, algorithm 1, on any
+        sampler's schedule): a ``_Walk``, settled on the host.  With S = len(tau), down(i) the sampler's step from tau[i] to
+        tau[i + 1] (0 after the last) and j, r = jump, resample:
+
+            m = 0
+            while m < S:
+                down(m); m += 1
+                if m % j == 0 and m < S:
+                    repeat r - 1 times:  up from tau[m] to tau[m - j];  down(m - j) .. down(m - 1)
+
+        S + (r-1) floor((S-1)/j) j down entries and (r-1) floor((S-1)/j) up entries; every entry starts at the level the one
+        before it reached and the last reaches 0; r = 1 or j >= S is the plain schedule.  An up entry from a level with
+        A = alpha_hat[from] to one with Q = alpha_hat[to] carries g1 = sqrt(Q/A), g2 = sqrt(1 - Q/A), evaluated in float64
+        (alpha_hat recomputed as in ``_ddim_tables``) and rounded to fp32 once.  ValueError: more than WALK_MAX entries."""
+        tau, j, r = [int(t) for t in tau], int(jump), int(resample)
+        S = len(tau)
+        ups = (r - 1) * ((S - 1) // j)
+        if S + ups * j + ups > WALK_MAX:
+            raise ValueError(f"resample={r}, jump={j} over {S} steps walks {S + ups * j + ups} entries; the limit is {WALK_MAX} "
+                             f"(WALK_MAX: one FiLM time row per entry)")
+        frm, to, up = [], [], []
+
+        def entry(a, b, is_up):
+            frm.append(a), to.append(b), up.append(is_up)
+        m = 0
+        while m < S:
+            entry(tau[m], tau[m + 1] if m + 1 < S else 0, False)
+            m += 1
+            if m % j == 0 and m < S:
+                for _ in range(r - 1):
+                    entry(tau[m], tau[m - j], True)
+                    for i in range(m - j, m):
+                        entry(tau[i], tau[i + 1], False)
+        ah = torch.cumprod(1.0 - self.beta.detach().cpu().double(), dim=0)
+        ratio = ah[to] / ah[frm]
+        is_up = torch.tensor(up)
+        zero = torch.zeros((), dtype=torch.float64)
+        g1 = torch.where(is_up, torch.sqrt(ratio), zero).float().contiguous()
+        g2 = torch.where(is_up, torch.sqrt(torch.clamp(1 - ratio, min=0.0)), zero).float().contiguous()
+        return _Walk(frm, to, up, g1, g2, r, j)
+
+    @staticmethod
+    def _walk_tables(walk, tabs):
+        """The per-step tables of the walk's down entries, spread over all its entries (0 at the up entries, which read none)."""
+        down = torch.tensor(walk.down, dtype=torch.int64)
+        return tuple(torch.zeros(len(walk.up), dtype=t.dtype).index_copy_(0, down, t).contiguous() for t in tabs)
+
+    @staticmethod
+    def _walk_steps(walk, draws):
+        """``_Sampler.steps`` of a walk: (k, a down entry, k where entry k makes a draw - an up entry its jump's z, a down entry
+        its step's z where ``draws(k)`` - else None)."""
+        return [(k, not u, k if (u or draws(k)) else None) for k, u in enumerate(walk.up)]
+
+    def _ddpm(self, calls_model=None, deterministic=False, start=None, walk=None):
         """The DDPM family: t = T-1 .. 1 (train.py:221; ``start`` .. 1 for a call that begins at that level), the model called
         where ``calls_model(t)`` holds (None: everywhere; a step that does not call it reuses the previous predicted noise) and
         one entry of ``noise`` per step while t > 1, counted on skipped steps too.  A step ends with ``wd_ddpm_step`` (the
         guided ``wd_ddpm_step_cfg`` after two forwards), ``wd_known_blend`` at the level t - 1 when a region is kept, and
-        ``wd_advance_timestep``."""
+        ``wd_advance_timestep``.
+        ``walk`` (a resampled call, over ``first .. 1``): the loop runs in table form over the walk - ``wd_ddpm_step`` still reads
+        t = ``*t_dev``, which ``wd_next_timestep`` sets to tau'[k]; FiLM rows and ``noise`` are indexed by the walk index k."""
         first = self.noise_steps - 1 if start is None else int(start)
         steps = [(i, calls_model is None or bool(calls_model(i)), first - i if i > 1 else None) for i in reversed(range(1, first + 1))]
+        if walk is not None:
+            steps = self._walk_steps(walk, lambda k: walk.tau[k] > 1)
 
         def update(lib, P, run):
             ca, cb, cs = self._step_tables(run.device)
@@ -461,14 +545,24 @@ class Diffusion:
                            P.t_dev.data_ptr(), *draw, stream), what)
             return launch
         # (``steps`` is T - 1 even when steps skip the model: it counts the updates)
+        if walk is not None:
+            return _Sampler(steps, first, list(walk.tau), update, dict(steps=first), walk)
         return _Sampler(steps, first, None, update, dict(steps=first))
 
-    def _ddim(self, tau, eta):
+    def _ddim(self, tau, eta, walk=None):
         """DDIM over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows, pairs and ``noise`` are indexed by k,
         the model is called at every step and ``noise[k]`` is read only where c5[k] != 0.  A step ends with ``wd_ddim_step``,
-        ``wd_known_blend`` at the level tau[k + 1] when a region is kept, and ``wd_next_timestep``."""
-        tabs = self._ddim_tables(tau, eta, "cpu")
-        steps = [(k, True, k if s != 0.0 else None) for k, s in enumerate(tabs[4].tolist())]  # (host tables: no device sync)
+        ``wd_known_blend`` at the level tau[k + 1] when a region is kept, and ``wd_next_timestep``.
+        ``walk`` (a resampled call, over ``tau``): k is the walk index; a down entry's coefficients are those of its (level from,
+        level to), as ``_ddim_tables`` computes them."""
+        if walk is None:
+            tabs = self._ddim_tables(tau, eta, "cpu")
+            steps = [(k, True, k if s != 0.0 else None) for k, s in enumerate(tabs[4].tolist())]  # (host tables: no device sync)
+        else:
+            down = walk.down
+            tabs = self._walk_tables(walk, self._ddim_tables([walk.tau[k] for k in down], eta, "cpu", to=[walk.to[k] for k in down]))
+            sigma = tabs[4].tolist()
+            steps = self._walk_steps(walk, lambda k: sigma[k] != 0.0)
 
         def update(lib, P, run):
             c = [t.to(run.device) for t in tabs]
@@ -479,15 +573,24 @@ class Diffusion:
                                          P.k_dev.data_ptr(), P.t_dev.data_ptr(), *draw, stream), "wd_ddim_step")
             return launch
         stats = dict(sampler="ddim", steps=len(tau), eta=float(eta), timesteps=list(tau))
-        return _Sampler(steps, tau[0], list(tau), update, stats)
+        return _Sampler(steps, tau[0], list(tau if walk is None else walk.tau), update, stats, walk)
 
-    def _dpmpp(self, tau, order, spacing=None):
+    def _dpmpp(self, tau, order, spacing=None, walk=None):
         """DPM-Solver++(2M) over the visited timesteps ``tau``: step k is timestep tau[k]; FiLM rows and pairs are indexed by k,
         the model is called at every step and no step draws noise.  The previous data prediction lives in a buffer of the
         update's own, written by every step and read only where c5[k] != 0.  A step ends with ``wd_dpmpp_step``,
-        ``wd_known_blend`` as in ``_ddim`` and ``wd_next_timestep``."""
-        tabs = self._dpmpp_tables(tau, order, "cpu")
-        steps = [(k, True, None) for k in range(len(tau))]
+        ``wd_known_blend`` as in ``_ddim`` and ``wd_next_timestep``.
+        ``walk`` (a resampled call, over ``tau``): k is the walk index; coefficients as in ``_ddim``, h_{k-1} is that of the down
+        entry before, and the down entry after a jump is first order - the stored data prediction belongs to another level."""
+        if walk is None:
+            tabs = self._dpmpp_tables(tau, order, "cpu")
+            steps = [(k, True, None) for k in range(len(tau))]
+        else:
+            down = walk.down
+            restart = [i for i, k in enumerate(down) if k and walk.up[k - 1]]
+            tabs = self._walk_tables(walk, self._dpmpp_tables([walk.tau[k] for k in down], order, "cpu", to=[walk.to[k] for k in down],
+                                                              restart=restart))
+            steps = self._walk_steps(walk, lambda k: False)
 
         def update(lib, P, run):
             c = [t.to(run.device) for t in tabs]
@@ -499,7 +602,7 @@ class Diffusion:
                                           *(t.data_ptr() for t in c), P.k_dev.data_ptr(), stream), "wd_dpmpp_step")
             return launch
         stats = dict(sampler="dpmpp", steps=len(tau), order=int(order), spacing=spacing, timesteps=list(tau))
-        return _Sampler(steps, tau[0], list(tau), update, stats)
+        return _Sampler(steps, tau[0], list(tau if walk is None else walk.tau), update, stats, walk)
 
     def _attention_setup(self, model, sampler, attention):
         """The ``attention`` argument of a sampler call, settled on the host (no device, no library): None, or (weights, N) - the
@@ -592,6 +695,29 @@ class Diffusion:
             eps = eps.detach().to(torch.float32).cpu().reshape(n, -1).contiguous()
             mode = "fixed"
         return _Known(x0, mask, start, None if tau is None else list(tau), mode, eps)
+
+    def _resample_setup(self, model, tau, resample, jump, known, attention=None, mix_rate=None, style_pairs=None, noise=None):
+        """The ``resample`` / ``jump`` arguments of a sampler call, validated and settled on the host (no device, no library, no
+        draw): None where the call does not resample (``resample`` 1: the plain path, whatever ``jump`` holds), else the ``_Walk``
+        over ``tau``, the timesteps the plain call would visit.  ValueError: ``resample`` or ``jump`` not an int >= 1, no
+        ``known_mask`` (nothing to harmonise), a walk of more than WALK_MAX entries, a ``noise`` list that does not hold one tensor
+        per walk entry.  NotImplementedError: ``attention=`` (the accumulators would count revisits) and writer-style
+        interpolation."""
+        for name, v in (("resample", resample), ("jump", jump)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1, not {v!r}")
+        if resample == 1:
+            return None
+        if known is None or known.mask is None:
+            raise ValueError("resample > 1 needs a known_mask: without a kept region there is nothing to harmonise")
+        if attention is not None and attention is not False:
+            raise NotImplementedError("attention= with resample > 1: the accumulators would count the revisited steps")
+        if style_pairs is not None or (mix_rate is not None and getattr(model, "interpolation", False)):
+            raise NotImplementedError("writer-style interpolation (mix_rate / style_pairs) with resample > 1")
+        walk = self.resample_walk(tau, jump, resample)
+        if noise is not None and len(noise) != len(walk.up):
+            raise ValueError(f"noise of a resampled call must hold one entry per walk entry ({len(walk.up)})")
+        return walk
 
     def line_windows(self, n, K, overlap=0, offsets=None, width=None, weight=None, feather=0):
         """How ``n`` lines of ``K`` words each are cut into windows of the model's latent width w (``img_size[1] // 8``), for the
@@ -790,7 +916,9 @@ class Diffusion:
         run.eps_g = torch.empty_like(run.eps) if (call.two and call.record_pred is not None) else None
         P.t_dev.fill_(call.sampler.t_first)
         P.t_in.fill_(call.sampler.t_first)
-        run.zbuf = torch.zeros_like(run.x) if call.noise is not None else None
+        # (a resampled call that draws its own step noise fills ``zbuf`` on the device, per walk entry: ``_step_tail``)
+        fills = call.noise is None and call.sampler.walk is not None and any(fwd and z is not None for _, fwd, z in call.sampler.steps)
+        run.zbuf = torch.zeros_like(run.x) if (call.noise is not None or fills) else None
         run.guide = (run.eps1.data_ptr(), call.scale, _dptr(run.eps_g)) if call.two else (None, 0.0, None)
         run.draw = (_dptr(run.zbuf), run.seed, call.sample_offset)
 
@@ -802,17 +930,44 @@ class Diffusion:
         level of tau[k + 1] (index 0 after the last entry) and advances with ``wd_next_timestep``.
         A ``windows=`` call wraps the forward(s) of a step in its two launches: ``wd_window_gather`` cuts the line into the plan's
         ``x_in`` before them, ``wd_window_blend`` averages the plan's ``out`` (and ``out1``) into the line prediction(s) after them;
-        update and blend then work on the line, the advance on the model batch.  A step without a forward runs neither."""
+        update and blend then work on the line, the advance on the model batch.  A step without a forward runs neither.
+        A resampled call (``sampler.walk``) visits the walk table tau', so blend and advance are right as they stand, and its draws
+        are keyed by the walk index k: a down entry that draws its own step noise fills ``zbuf`` first (``wd_walk_randn``,
+        WD_WALK_STEP), which the update reads through its ``noise`` argument, and a blend that draws per step reads a second
+        buffer filled likewise (WD_WALK_BLEND).  ``step(stream, up=True)`` is an up entry: ``wd_forward_jump`` on the whole state -
+        its z the entry's ``noise`` tensor, or its own draw - and the advance, nothing else."""
         call, lib, P, n, nb, npix = run.call, run.lib, run.plan, run.n, run.nb, run.npix
         update = call.sampler.update(lib, P, run)
-        tau, two = call.sampler.tau, call.two
+        tau, two, walk = call.sampler.tau, call.two, call.sampler.walk
         forwards = 1 if (two or call.mix is not None) else call.plain_forwards
         if tau is not None:
             tau_dev = torch.tensor(tau, dtype=torch.int32, device=run.device)
             P.k_dev.zero_()
         x, win = run.x, run.win
+        zfill = kbuf = None
+        if walk is not None:
+            g1, g2 = walk.g1.to(run.device), walk.g2.to(run.device)
+            zfill = run.zbuf if call.noise is None else None
+            kbuf = torch.empty_like(x) if (run.blend is not None and run.blend[2] is None) else None
+            jump_draw = (_dptr(run.zbuf) if call.noise is not None else None, run.seed, call.sample_offset)
 
-        def step(stream, forward=True):
+        def fill(buf, which, stream):
+            N.check(lib.wd_walk_randn(buf.data_ptr(), n, npix, run.seed, call.sample_offset, which, P.k_dev.data_ptr(), stream),
+                    "wd_walk_randn")
+
+        def advance(stream):
+            if tau is None:
+                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), nb, stream), "wd_advance_timestep")
+            else:
+                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(), P.t_in.data_ptr(), nb,
+                                             stream), "wd_next_timestep")
+
+        def step(stream, forward=True, up=False):
+            if up:
+                N.check(lib.wd_forward_jump(x.data_ptr(), n, npix, g1.data_ptr(), g2.data_ptr(), P.k_dev.data_ptr(), *jump_draw, stream),
+                        "wd_forward_jump")
+                advance(stream)
+                return
             if forward:
                 if win is not None:
                     N.check(lib.wd_window_gather(x.data_ptr(), win[0].data_ptr(), *win[2], P.x_in.data_ptr(), stream), "wd_window_gather")
@@ -823,24 +978,26 @@ class Diffusion:
                 if win is not None:
                     N.check(lib.wd_window_blend(P.out.data_ptr(), P.out1.data_ptr() if two else None, win[1].data_ptr(), win[0].data_ptr(),
                                                 *win[2], run.eps.data_ptr(), _dptr(run.eps1), stream), "wd_window_blend")
+            if zfill is not None:
+                fill(zfill, N.WALK_STEP, stream)
             update(stream)
             if run.blend is not None:
                 x0, mask, eps, sa, sb = run.blend
+                if kbuf is not None:
+                    fill(kbuf, N.WALK_BLEND, stream)
+                    eps = kbuf
                 level = (None, None, 0) if tau is None else (P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau))
                 N.check(lib.wd_known_blend(x.data_ptr(), x0.data_ptr(), mask.data_ptr(), n, npix, sa.data_ptr(), sb.data_ptr(),
                                            P.t_dev.data_ptr(), *level, _dptr(eps), run.seed, call.sample_offset, stream), "wd_known_blend")
-            if tau is None:
-                N.check(lib.wd_advance_timestep(P.t_dev.data_ptr(), -1, P.t_in.data_ptr(), nb, stream), "wd_advance_timestep")
-            else:
-                N.check(lib.wd_next_timestep(P.k_dev.data_ptr(), tau_dev.data_ptr(), len(tau), P.t_dev.data_ptr(), P.t_in.data_ptr(), nb,
-                                             stream), "wd_next_timestep")
+            advance(stream)
         return step
 
     def _capture(self, run, step):
         """What the steps share, before any of them: the word embedding and cross-attention K/V (``run_cond``), the time MLP of
         every timestep (``run_film``) and the FiLM rows of the first step - the captured step only reads the table, whose rows are
         indexed by t or by the step index.  Then, unless the call is eager, one hipGraph of a whole step and, where steps reuse the
-        previous predicted noise, one of the tail alone; ``run.graphs`` holds each from the moment it exists."""
+        previous predicted noise, one of the tail alone - for a resampled call, one of the up entry; ``run.graphs`` holds each from
+        the moment it exists."""
         call, lib, P, st = run.call, run.lib, run.plan, run.stream
         P.run_cond(st)
         P.run_film(st)
@@ -848,10 +1005,11 @@ class Diffusion:
             P.film_prepare(call.sampler.steps[0][0], st)
         if not call.use_graph or call.record is not None or call.record_pred is not None:
             return  # eager launches: asked for, or needed to read a step's tensors
+        up = call.sampler.walk is not None  # a resampled call's entries without a forward are its up entries
         for forward in (True, False) if call.model_steps < len(call.sampler.steps) else (True,):
             N.check(lib.wd_graph_begin(st), "wd_graph_begin")
             try:
-                step(st, forward)
+                step(st, forward, up and not forward)
             finally:  # (ends the capture when a launch of the step raised, too)
                 g = C.c_void_p()
                 rc = lib.wd_graph_end(st, C.byref(g))
@@ -861,21 +1019,23 @@ class Diffusion:
     def _loop(self, run, step):
         """Per visited step: x into ``record``, the step's ``noise`` entry into ``zbuf`` if it has one, the FiLM rows of the step
         (``film_prepare``, computed per chunk of rows) when it calls the model, then the step - ``wd_graph_launch`` of the whole
-        step or of its tail, or its eager launches - and its predictions into ``record_pred``."""
+        step or of its tail, or its eager launches - and its predictions into ``record_pred``.  An up entry of a resampled call
+        is a step without a forward whose launches are the jump's: x into ``record``, its ``noise`` entry, its graph."""
         call, lib, P, st, device = run.call, run.lib, run.plan, run.stream, run.device
         record, record_pred, noise, zbuf, two = call.record, call.record_pred, call.noise, run.zbuf, call.two
         gexec, gskip = (run.graphs + [None, None])[:2]
+        up = call.sampler.walk is not None  # (as in ``_capture``: the second graph of a resampled call is its up entry)
         for row, fwd, z in call.sampler.steps:
             if record is not None:
                 record.append(run.x.clone())
-            if zbuf is not None and z is not None:
+            if noise is not None and z is not None:
                 zbuf.copy_(noise[z].to(device))
             if fwd:
                 P.film_prepare(row, st)
             if gexec is not None:
                 N.check(lib.wd_graph_launch(gexec if fwd else gskip, st), "wd_graph_launch")
             else:
-                step(st, fwd)
+                step(st, fwd, up and not fwd)
             if record_pred is not None and fwd:
                 pred = (P.out.clone(),) if not two else (P.out.clone(), P.out1.clone())
                 if run.win is not None:  # the window predictions, then the line prediction(s) they were blended into
@@ -893,6 +1053,9 @@ class Diffusion:
         self.last_stats = dict(call.sampler.stats, forwards_per_step=call.forwards, graph=bool(run.graphs), seed=run.seed,
                                sample_offset=call.sample_offset, model_calls=call.model_calls, known=known is not None,
                                start=None if known is None else known.start, known_noise=None if known is None else known.mode)
+        walk = call.sampler.walk
+        self.last_stats.update(resample=1 if walk is None else walk.resample, jump=None if walk is None else walk.jump,
+                               walk=len(call.sampler.steps))
         if call.attention is not None:
             self.last_stats["attention_steps"] = call.attention[1]
         if call.writer_free is not None:
@@ -1041,7 +1204,7 @@ class Diffusion:
     def sampling(self, model, vae, n, x_text, labels, args, mix_rate=None, cfg_scale=3, phoscLabels=None,
                  noise=None, x_T=None, seed=None, sample_offset=0, record=None, use_graph=True, underscore=None, *,
                  style_pairs=None, record_pred=None, known=None, known_mask=None, start=None, known_noise="auto", attention=None,
-                 guidance=None, windows=None):
+                 guidance=None, windows=None, resample=1, jump=10):
         """``train.py:200`` signature; extra keyword-only style arguments (phoscLabels, noise, x_T, seed,
         sample_offset) serve the PHOSC variant (``trainGWModifyCondition.py:249``), the parity tests and
         rank-sharded sampling.  ``vae=None`` returns the denoised latents.  ``underscore``: word ids from the 53-class
@@ -1081,9 +1244,22 @@ class Diffusion:
         update, guidance and known-region blend run; line s depends on (seed, sample_offset + s) only.  ``last_stats`` gains
         ``windows``, ``line_width`` and ``model_batch``; ``record_pred`` receives (window predictions, line prediction), or (window
         cond, window free, line cond, line free, guided line).  ``attention=`` and the interpolation modes are refused
+        (NotImplementedError) before anything is launched or drawn.
+
+        ``resample=r, jump=j`` (DESIGN.md "Resampling jumps"; ``resample_walk``): RePaint's resampling on top of ``known_mask`` -
+        after every ``jump`` visited steps the state is diffused forward again by those steps (``wd_forward_jump``, kept and free
+        cells alike) and they are denoised once more, ``resample - 1`` times per stretch, so that the free region is re-drawn in the
+        context of what the kept one has become.  ``resample=1`` (the default) is the call without the argument, launch for
+        launch.  In a resampled call every draw is keyed by the walk entry, so a revisited level draws afresh; ``noise`` holds
+        one tensor per walk entry (a down entry's step z, an up entry's jump z), ``record`` receives x before every entry and
+        ``last_stats`` reports ``resample``, ``jump``, ``walk`` (entries) and ``model_calls`` (down entries, times the forwards
+        of a guided step).  Needs a ``known_mask`` (ValueError); ``attention=`` and the interpolation modes are refused
         (NotImplementedError) before anything is launched or drawn."""
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=True, width=self._line_width(windows, n))
-        return self._sample("sampling", model, vae, n, x_text, labels, args, lambda: self._ddpm(start=None if kn is None else kn.start),
+        first = self.noise_steps - 1 if kn is None or kn.start is None else kn.start
+        walk = self._resample_setup(model, range(first, 0, -1), resample, jump, kn, attention, mix_rate, style_pairs, noise)
+        return self._sample("sampling", model, vae, n, x_text, labels, args,
+                            lambda: self._ddpm(start=None if kn is None else kn.start, walk=walk),
                             phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
                             style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
                             sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph, windows=windows)
@@ -1092,7 +1268,7 @@ class Diffusion:
     def sampling_ddim(self, model, vae, n, x_text, labels, args, steps=50, eta=0.0, *, timesteps=None, mix_rate=None, cfg_scale=3,
                       phoscLabels=None, noise=None, x_T=None, seed=None, sample_offset=0, record=None, record_pred=None,
                       use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None, start=None,
-                      known_noise="auto", attention=None, guidance=None, windows=None):
+                      known_noise="auto", attention=None, guidance=None, windows=None, resample=1, jump=10):
         """DDIM sampling (Song et al. 2020) with the same trained model: ``steps`` UNet evaluations over the subsequence
         ``ddim_timesteps(steps)`` of the schedule (or the explicit ``timesteps``) instead of ``noise_steps - 1``.  ``eta = 0`` is
         deterministic given x_T (``seed`` then only draws x_T); ``eta = 1`` has the DDPM posterior variance; in between the
@@ -1106,15 +1282,17 @@ class Diffusion:
         its usual schedule that are <= start (``steps`` and ``timesteps`` of ``last_stats`` are the retained ones, FiLM rows,
         pairs and ``noise`` are indexed by them) and the first of them is the level noised to.  With ``eta = 0`` the default
         ``known_noise`` is one fixed eps per sample, so the call stays deterministic given ``seed``.  ``attention``,
-        ``guidance`` and ``windows`` as in ``sampling``."""
+        ``guidance``, ``windows`` and ``resample`` / ``jump`` as in ``sampling``; the walk is built over the retained schedule
+        and ``jump`` counts visited steps."""
         tau = self.ddim_timesteps(steps, timesteps)
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=float(eta) > 0, tau=tau,
                                width=self._line_width(windows, n))
         if kn is not None:
             tau = kn.tau
-        if noise is not None and len(noise) != len(tau):
+        walk = self._resample_setup(model, tau, resample, jump, kn, attention, mix_rate, style_pairs, noise)
+        if walk is None and noise is not None and len(noise) != len(tau):
             raise ValueError(f"noise must hold one tensor per visited step ({len(tau)})")
-        return self._sample("sampling_ddim", model, vae, n, x_text, labels, args, lambda: self._ddim(tau, eta),
+        return self._sample("sampling_ddim", model, vae, n, x_text, labels, args, lambda: self._ddim(tau, eta, walk),
                             phoscLabels=phoscLabels, underscore=underscore, attention=attention, mix_rate=mix_rate,
                             style_pairs=style_pairs, cfg_scale=cfg_scale, guidance=guidance, known=kn, x_T=x_T, noise=noise, seed=seed,
                             sample_offset=sample_offset, record=record, record_pred=record_pred, use_graph=use_graph, windows=windows)
@@ -1123,7 +1301,7 @@ class Diffusion:
     def sampling_dpmpp(self, model, vae, n, x_text, labels, args, steps=20, order=2, *, spacing="logsnr", timesteps=None,
                        mix_rate=None, cfg_scale=3, phoscLabels=None, x_T=None, seed=None, sample_offset=0, record=None,
                        record_pred=None, use_graph=True, underscore=None, style_pairs=None, known=None, known_mask=None,
-                       start=None, known_noise="auto", attention=None, guidance=None, windows=None):
+                       start=None, known_noise="auto", attention=None, guidance=None, windows=None, resample=1, jump=10):
         """DPM-Solver++(2M) sampling (Lu et al. 2022) with the same trained model: ``steps`` UNet evaluations over
         ``dpmpp_timesteps(steps, spacing)`` (or the explicit ``timesteps``), each step extrapolating the data prediction from
         the previous step's (``order = 2``; ``order = 1`` is DDIM with eta = 0 on the same timesteps).  The first and the last
@@ -1134,16 +1312,18 @@ class Diffusion:
         returns latents, ``phoscLabels``, ``mix_rate`` / ``style_pairs``, ``record`` / ``record_pred``.  ``last_stats`` carries
         ``sampler="dpmpp"``, ``steps``, ``order``, ``spacing`` (None with explicit ``timesteps``) and ``timesteps``.
         ``known`` / ``known_mask`` / ``start`` / ``known_noise`` as in ``sampling_ddim`` (the default noise is the fixed eps: no
-        step draws); the first retained step is first order, like the first step of any call.  ``attention``, ``guidance`` and
-        ``windows`` as in ``sampling``."""
+        step draws); the first retained step is first order, like the first step of any call.  ``attention``, ``guidance``,
+        ``windows`` and ``resample`` / ``jump`` as in ``sampling_ddim``; the step after a jump is first order as well (only the
+        jumps draw, and a blend with ``known_noise="fresh"``)."""
         tau = self.dpmpp_timesteps(steps, spacing, timesteps)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, not {order!r}")
         kn = self._known_setup(n, known, known_mask, start, known_noise, x_T, draws_noise=False, tau=tau, width=self._line_width(windows, n))
         if kn is not None:
             tau = kn.tau
+        walk = self._resample_setup(model, tau, resample, jump, kn, attention, mix_rate, style_pairs)
         return self._sample("sampling_dpmpp", model, vae, n, x_text, labels, args,
-                            lambda: self._dpmpp(tau, order, None if timesteps is not None else spacing), phoscLabels=phoscLabels,
+                            lambda: self._dpmpp(tau, order, None if timesteps is not None else spacing, walk), phoscLabels=phoscLabels,
                             underscore=underscore, attention=attention, mix_rate=mix_rate, style_pairs=style_pairs, cfg_scale=cfg_scale,
                             guidance=guidance, known=kn, x_T=x_T, seed=seed, sample_offset=sample_offset, record=record,
                             record_pred=record_pred, use_graph=use_graph, windows=windows)
@@ -1160,7 +1340,7 @@ class Diffusion:
     @torch.no_grad()
     def sampling3(self, epoch, x_t, words, phoscLabels, model, model1, vae, emaOld, noiseInput, n, x_text, labels, args,
                   mix_rate=None, cfg_scale=3, seed=None, sample_offset=0, use_graph=True, x_T=None, noise=None, record=None, *,
-                  style_pairs=None, attention=None, windows=None):
+                  style_pairs=None, attention=None, windows=None, resample=1, jump=10):
         """Bulk-regeneration sampler of ``regenerateFromtrain2.py:465-648`` (same argument order): the predicted noise is
         refreshed only on the steps of ``sampling3_calls_model`` (1 in 5) and reused in between, and unless
         ``args.fullSampling`` the update is deterministic (no ``sqrt(beta) * noise`` term, ``:618``).  ``noiseInput == 0``
@@ -1174,9 +1354,11 @@ class Diffusion:
         the model, ``:587,591``: there the argument has no effect; here it selects the blend, as it does in ``sampling``.)
         ``attention`` as in ``sampling``: the steps that reuse the previous prediction run no forward and add nothing, and
         ``attention_steps`` counts the model-calling steps of the window only.  ``windows`` (line sampling, see ``sampling``) is
-        refused: this loop regenerates single words."""
+        refused: this loop regenerates single words; so is ``resample > 1``: it keeps no region."""
         if windows is not None:
             raise NotImplementedError("sampling3 with windows=: the step-skipping bulk sampler regenerates single words")
+        if resample != 1:
+            raise NotImplementedError("sampling3 with resample > 1: the step-skipping bulk sampler keeps no region to harmonise")
         if emaOld == 1:
             model = model1
         model.eval()  # and it stays in eval mode: ``#model.train()`` is commented out at regenerateFromtrain2.py:622

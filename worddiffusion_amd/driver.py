@@ -131,7 +131,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                world: Optional[int] = None, skip_steps: bool = False, phosc_of=None, mix_rate=None, sampler: str = "ddpm",
                ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
                known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto",
-               attention=None, attn_out: Optional[str] = None, guidance: Optional[str] = None, cfg_scale: float = 3.0):
+               attention=None, attn_out: Optional[str] = None, guidance: Optional[str] = None, cfg_scale: float = 3.0,
+               resample: int = 1, jump: int = 10):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -145,7 +146,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``known`` (a ``LatentCache``, or any mapping image name -> latent [C, h, w]): every gt row is regenerated from its own cached
     latent - ``keep_cols = (a, b)`` keeps the latent columns a <= column < b and re-draws the rest, ``start`` begins the loop
     from the latent noised to that level, ``known_noise`` as in ``Diffusion.sampling``.  A row whose latent is missing raises
-    KeyError naming it, before anything is sampled.  Not with ``skip_steps``.
+    KeyError naming it, before anything is sampled.  Not with ``skip_steps``.  ``resample`` / ``jump`` (``Diffusion.sampling``):
+    RePaint's resampling jumps around the kept columns; ``resample > 1`` needs ``keep_cols``.
 
     ``attention`` (True or a timestep window ``(t_hi, t_lo)``, as in ``Diffusion.sampling``): every call also leaves its
     per-character cross-attention maps; ``attn_out`` (a ``.npz`` path; a relative one lands in ``out_dir``, beside the images)
@@ -159,6 +161,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     if attn_out is not None and attention is None:
         attention = True
     _check_sampler(sampler, skip_steps)
+    if resample != 1 and (skip_steps or keep_cols is None):
+        raise ValueError("resample > 1 needs kept columns (known= with keep_cols=) and is not supported by the step-skipping sampler")
     if known is None and (keep_cols is not None or start is not None):
         raise ValueError("keep_cols and start need the known latents (known=)")
     if known is not None:
@@ -191,6 +195,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
             kw.update(guidance=guidance, cfg_scale=cfg_scale)
         if known is not None:
             kw.update(known=torch.stack(latents[b0:b0 + batch]), known_mask=kmask, start=start, known_noise=known_noise)
+        if resample != 1:
+            kw.update(resample=resample, jump=jump)
         if sampler == "ddim":
             res = diffusion.sampling_ddim(model, vae, len(chunk), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
         elif sampler == "dpmpp":
@@ -400,6 +406,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--init_latents: keep the latent columns A <= column < B of the 32 and re-draw the rest")
     ap.add_argument("--start", type=int, default=None, metavar="T",
                     help="--init_latents: begin from the latent noised to level T (1 .. noise_steps - 1) instead of from noise")
+    ap.add_argument("--resample", type=int, default=1, metavar="R",
+                    help="--keep_cols: RePaint's resampling - every stretch of --jump steps is diffused forward again and denoised "
+                         "once more, R - 1 times (1: off)")
+    ap.add_argument("--jump", type=int, default=10, metavar="J", help="--resample: the length of a stretch, in visited steps")
     ap.add_argument("--attn_maps", default=None, metavar="FILE",
                     help="also save the per-character cross-attention maps of every generated row (.npz beside the images: input / "
                          "middle / output [rows, h, w, 10], images, words); base model only")
@@ -448,6 +458,17 @@ def parse_args(argv=None):
             ap.error("--init_latents needs --keep_cols A:B, --start T, or both")
         if a.start is not None and not 1 <= a.start <= a.noise_steps - 1:
             ap.error(f"--start must be in [1, {a.noise_steps - 1}] (--noise_steps {a.noise_steps})")
+    if a.resample < 1 or a.jump < 1:
+        ap.error("--resample and --jump must be >= 1")
+    if a.resample > 1:
+        if a.skip_steps:
+            ap.error("--skip_steps 1 does not take --resample")
+        if a.keep_cols is None:  # (--lines keeps no region yet: it does not take --init_latents)
+            ap.error("--resample needs a kept region (--init_latents with --keep_cols): without one there is nothing to harmonise")
+        if a.attn_maps is not None:
+            ap.error("--resample does not take --attn_maps: the maps would count the revisited steps")
+        if a.interpolation and a.mix_rate is not None:
+            ap.error("--resample cannot be combined with --interpolation with a --mix_rate")
     if a.attn_window is not None:
         if a.attn_maps is None:
             ap.error("--attn_window needs --attn_maps (the file to write)")
@@ -537,7 +558,7 @@ def main(argv=None):
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
                             phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
                             dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing, known=known,
-                            keep_cols=a.keep_cols, start=a.start,
+                            keep_cols=a.keep_cols, start=a.start, resample=a.resample, jump=a.jump,
                             guidance=a.guidance, cfg_scale=a.cfg_scale,
                             attention=None if a.attn_maps is None else (a.attn_window or True),
                             attn_out=None if a.attn_maps is None else
