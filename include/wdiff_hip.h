@@ -390,7 +390,11 @@ int wd_xattn_fused(const float* x, int ld, int batch, int hw, int c, const float
  * wd_emb_combine writes SiLU(time[t] + label[y_b]) for T consecutive timesteps (time points at the first one) and every
  * sample b as operand planes (row t*B + b; y_b is clamped to [0, num_classes) - the host range-checks it, the reference
  * raises an index error), one wd_gemm then gives the FiLM vectors of those T steps, and wd_select_rows copies the rows of
- * the current step out of the resident chunk: row ((*t_dev) % chunk)*B + b (chunk = T of the table: one table for all steps). */
+ * the current step out of the resident chunk: row ((*t_dev) % chunk)*B + b (chunk = T of the table: one table for all steps).
+ * label == NULL: the rows are SiLU(time[t]); out_lo == NULL: the hi plane only.
+ * WD_EINVAL (nothing launched): wd_emb_combine - a NULL time / out_hi (or y with a label), ted or out_ld not a multiple of 4,
+ * out_ld < ted, time / label not 16-byte aligned, out_hi / out_lo not 8-byte aligned;  wd_select_rows - a NULL pointer,
+ * row_floats not a multiple of 4, table / out not 16-byte aligned. */
 int wd_emb_combine(const float* time, const float* label, const int64_t* y, int num_classes, int T, int B, int ted,
                    wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream);
 int wd_select_rows(const float* table, const int32_t* t_dev, int batch, int64_t row_floats, int chunk, float* out,
@@ -402,7 +406,7 @@ int wd_select_rows(const float* table, const int32_t* t_dev, int batch, int64_t 
  * wd_emb_combine_mix: wd_emb_combine with that blend as the label term; pairs is [T][B][2] (row t*B + b).  With m_b = 0 / 1 the
  * planes equal wd_emb_combine's for y_b = s1 / s2 bit for bit.
  * wd_label_mix: the blended rows themselves, out fp32 [B][ted], pairs [B][2] (the residual rows of the time_embed.2 GEMM on
- * the path that does not tabulate). */
+ * the path that does not tabulate); WD_EINVAL (nothing launched): a NULL pointer, ted % 4, label / out not 16-byte aligned. */
 int wd_emb_combine_mix(const float* time, const float* label, const int32_t* pairs, const float* mix, int num_classes, int T, int B,
                        int ted, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream);
 int wd_label_mix(const float* label, const int32_t* pairs, const float* mix, int num_classes, int B, int ted, float* out,
@@ -448,7 +452,10 @@ int wd_linear_fold(const float* w3, const float* w2, const float* b2, const floa
                    float* b32, void* stream);
 
 /* nn.Embedding lookup + positional encoding (CharacterEncoder, unet.py:860-872; PE skipped when pe == NULL,
- * unetPhosc.py:726-729): planes[r][:] = table[ids[r]][:] + pe[r % seq_len][:]. ids are int64 or int32. */
+ * unetPhosc.py:726-729): planes[r][:] = table[ids[r]][:] + pe[r % seq_len][:]. ids are int64 or int32, clamped to
+ * [0, vocab) (the reference raises an index error); out_lo == NULL: the hi plane only.
+ * WD_EINVAL (nothing launched): a NULL ids / table / out_hi, c or out_ld not a multiple of 4, out_ld < c, table / pe not
+ * 16-byte aligned, out_hi / out_lo not 8-byte aligned. */
 int wd_embed_tokens(const void* ids, int ids_are_i64, int rows, int seq_len, const float* table, int vocab, int c,
                     const float* pe, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream);
 
@@ -476,14 +483,16 @@ int wd_tokens_to_nchw(const float* x, int ld, int batch, int c, int hw, float* o
  * evaluated with the reference's rounding order (no fma contraction), ca = 1/sqrt(alpha), cb = (1-alpha)/sqrt(1-alpha_hat),
  * cs = sqrt(beta) tabulated by the caller.  t = *t_dev (device int32, so that a captured graph can be replayed).
  * noise != NULL: z is read from it (parity tests); else z ~ N(0,1) from Philox4x32-10 keyed by seed with counter
- * (element/4, t, sample_offset + sample index): a sample's noise does not depend on how the batch is sharded. */
+ * (element/4, t, sample_offset + sample index): a sample's noise does not depend on how the batch is sharded.
+ * WD_EINVAL (nothing launched): a NULL required pointer, n_per_sample % 4, x / eps / noise not 16-byte aligned. */
 int wd_ddpm_step(float* x, const float* eps, int batch, int n_per_sample, const float* ca, const float* cb,
                  const float* cs, const int32_t* t_dev, const float* noise, uint64_t seed, uint64_t sample_offset,
                  void* stream);
 
 /* wd_ddpm_step on the guided prediction eps = torch.lerp(second, first, scale) (train.py:228), formed as torch forms it:
  * first - (first - second) * (1 - scale) when |scale| >= 0.5, second + scale * (first - second) otherwise.  The update and the
- * Philox stream are wd_ddpm_step's, bit for bit.  eps_out != NULL also receives eps. */
+ * Philox stream are wd_ddpm_step's, bit for bit.  eps_out != NULL also receives eps.
+ * WD_EINVAL (nothing launched): as wd_ddpm_step, for x / first / second / eps_out / noise. */
 int wd_ddpm_step_cfg(float* x, const float* first, const float* second, float scale, float* eps_out, int batch, int n_per_sample,
                      const float* ca, const float* cb, const float* cs, const int32_t* t_dev, const float* noise, uint64_t seed,
                      uint64_t sample_offset, void* stream);
@@ -533,7 +542,8 @@ int wd_dpmpp_step(float* x, const float* eps, const float* second, float scale, 
  * (tau int32 [S]).  After the last visited step k stays at S - 1. */
 int wd_next_timestep(int32_t* k_dev, const int32_t* tau, int S, int32_t* t_dev, int64_t* t64, int batch, void* stream);
 
-/* N(0,1) fill with the same Philox stream family (x_T, train.py:217; noise_images eps, train.py:193). */
+/* N(0,1) fill with the same Philox stream family (x_T, train.py:217; noise_images eps, train.py:193).
+ * WD_EINVAL (nothing launched): out NULL or not 16-byte aligned, n_per_sample % 4. */
 int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sample_offset, uint32_t stream_id,
              void* stream);
 

@@ -637,6 +637,7 @@ __global__ void posterior_sample_kernel(const float* __restrict__ mean, const fl
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
 
@@ -652,8 +653,9 @@ extern "C" int wd_timestep_embedding(const int64_t* t, int batch, const float* f
 
 extern "C" int wd_embed_tokens(const void* ids, int ids_are_i64, int rows, int seq_len, const float* table, int vocab,
                                int c, const float* pe, wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream) {
-    if (!ids || !table || !out_hi || rows <= 0 || seq_len <= 0 || vocab <= 0 || c <= 0 || c % 4 || out_ld % 4)
+    if (!ids || !table || !out_hi || rows <= 0 || seq_len <= 0 || vocab <= 0 || c <= 0 || c % 4 || out_ld % 4 || out_ld < c)
         return WD_EINVAL;
+    if (!aligned16(table) || !aligned16(pe) || !aligned8(out_hi) || !aligned8(out_lo)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(embed_kernel, dim3(grid_for((long)rows * (c / 4))), dim3(256), 0, st, ids, ids_are_i64, rows,
@@ -694,6 +696,7 @@ extern "C" int wd_ddpm_step(float* x, const float* eps, int batch, int n_per_sam
                             uint64_t sample_offset, void* stream) {
     if (!x || !eps || !ca || !cb || !cs || !t_dev || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4)
         return WD_EINVAL;
+    if (!aligned16(x) || !aligned16(eps) || !aligned16(noise)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, eps,
@@ -711,7 +714,7 @@ extern "C" int wd_advance_timestep(int32_t* t_dev, int delta, int64_t* t64, int 
 
 extern "C" int wd_randn(float* out, int batch, int n_per_sample, uint64_t seed, uint64_t sample_offset,
                         uint32_t stream_id, void* stream) {
-    if (!out || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4) return WD_EINVAL;
+    if (!out || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4 || !aligned16(out)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(randn_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, out, batch,
@@ -752,8 +755,10 @@ extern "C" int wd_ema_update(float* ema, const float* p, int64_t n, double beta,
 
 extern "C" int wd_emb_combine(const float* time, const float* label, const int64_t* y, int num_classes, int T, int B, int ted,
                               wd_bf16* out_hi, wd_bf16* out_lo, int out_ld, void* stream) {
-    if (!time || !out_hi || T <= 0 || B <= 0 || ted <= 0 || ted % 4 || out_ld % 4 || (label && (!y || num_classes <= 0)))
+    if (!time || !out_hi || T <= 0 || B <= 0 || ted <= 0 || ted % 4 || out_ld % 4 || out_ld < ted ||
+        (label && (!y || num_classes <= 0)))
         return WD_EINVAL;
+    if (!aligned16(time) || !aligned16(label) || !aligned8(out_hi) || !aligned8(out_lo)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(emb_combine_kernel, dim3(grid_for((long)T * B * (ted / 4))), dim3(256), 0, st, time, label, y, num_classes, T,
@@ -764,6 +769,7 @@ extern "C" int wd_emb_combine(const float* time, const float* label, const int64
 extern "C" int wd_select_rows(const float* table, const int32_t* t_dev, int batch, int64_t row_floats, int chunk, float* out,
                               void* stream) {
     if (!table || !t_dev || !out || batch <= 0 || row_floats <= 0 || row_floats % 4 || chunk <= 0) return WD_EINVAL;
+    if (!aligned16(table) || !aligned16(out)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(select_rows_kernel, dim3(grid_for((long)batch * (row_floats / 4))), dim3(256), 0, st, table, t_dev, batch,
@@ -786,6 +792,7 @@ extern "C" int wd_emb_combine_mix(const float* time, const float* label, const i
 extern "C" int wd_label_mix(const float* label, const int32_t* pairs, const float* mix, int num_classes, int B, int ted, float* out,
                             void* stream) {
     if (!label || !pairs || !mix || !out || num_classes <= 0 || B <= 0 || ted <= 0 || ted % 4) return WD_EINVAL;
+    if (!aligned16(label) || !aligned16(out)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(label_mix_kernel, dim3(grid_for((long)B * (ted / 4))), dim3(256), 0, st, label, pairs, mix, num_classes, B, ted,
@@ -826,6 +833,7 @@ extern "C" int wd_ddpm_step_cfg(float* x, const float* first, const float* secon
                                 const float* noise, uint64_t seed, uint64_t sample_offset, void* stream) {
     if (!x || !first || !second || !ca || !cb || !cs || !t_dev || batch <= 0 || n_per_sample <= 0 || n_per_sample % 4)
         return WD_EINVAL;
+    if (!aligned16(x) || !aligned16(first) || !aligned16(second) || !aligned16(eps_out) || !aligned16(noise)) return WD_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(ddpm_step_cfg_kernel, dim3(grid_for((long)batch * (n_per_sample / 4))), dim3(256), 0, st, x, first, second,
