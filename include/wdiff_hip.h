@@ -40,6 +40,24 @@ typedef uint16_t wd_bf16;
 
 #define WD_MAX_KSPLIT 64 /* largest wd_gemm_args.ksplit */
 
+/* The bits of wd_gemm_args.dbg / wd_ff_args.dbg / wd_dw_args.dbg a caller may set or a check returns (0 in production; the bits
+ * below 0x100 are timing ablations of the experimental slab-order kernel).  FORCE_*: take that kernel form wherever it is legal,
+ * whatever the grid size or the environment says (parity tests).  *_OFF / *_ON: override the named environment switch for this
+ * call; both are cleared in the args a check returns, where *_BIT says which form the launch takes. */
+#define WD_DBG_STAMPS 0x100           /* cycle stamps of workgroup 0 into ws / wd_dw_args.stamps (a library built with WDIFF_STAMPS=1) */
+#define WD_DBG_STAGGER 0x200          /* resolved only: the second K-half wave group multiplies one stage late */
+#define WD_DBG_FORCE_V4 0x400         /* the two-workgroups-per-CU kernel (wd_gemm4_kernel) */
+#define WD_DBG_FORCE_CONV3 0x1000     /* the row-shared-taps kernel for w_layout 2 (wd_conv3_kernel, experimental build) */
+#define WD_DBG_FORCE_TICKETS 0x2000   /* the in-launch split-K combine (tickets) */
+#define WD_DBG_GEMMW_INSTEP 0x4000    /* timing experiment: the K-half groups of the per-tap 64 x 320 kernel run in step, none a stage late */
+#define WD_GEMMW_SLAB_OFF 0x8000      /* WDIFF_GEMMW_SLAB: the 64 x 320 weights-to-registers kernel keeps the per-tap A path ... */
+#define WD_GEMMW_SLAB_ON 0x10000      /* ... takes the slab form (3x3 / pad 1 / stride 1 source rows from an LDS slab) where it is legal */
+#define WD_GEMMW_SLAB_BIT 0x10000     /* resolved: the launch takes the slab form */
+#define WD_EPI_BATCH_OFF 0x20000      /* WDIFF_EPI_BATCH: the 64-row tiles (64320, 64080, wd_ff_fused) keep the row loop of their epilogue ... */
+#define WD_EPI_BATCH_ON 0x40000       /* ... take its batched form - a thread's row loads in one round trip, then its stores - where it is legal */
+#define WD_EPI_BATCH_BIT 0x40000      /* resolved: the 16-byte path of the launch's epilogue is the batched form */
+#define WD_DBG_FORCE_V8 0x80000       /* the ring-of-four kernel with dedicated loader waves (wd_gemm8_kernel) */
+
 /* One A-operand source of the tap-gather GEMM.  K contribution = ntaps * c.
  * Row m of the output (sample b = m / hw_out, position p = m % hw_out) reads, for tap t,
  * source row  b*hw_src + gather[t*hw_out + p]  (all-zero row when that entry is < 0);
@@ -117,16 +135,12 @@ typedef struct wd_gemm_args {
                            * of the fp32 values for any mean / std of a group (measured <= 1e-7 up to 256) - no fp32 stage sums
                            * the values or their squares unshifted (csrc/wd_gemm_epi.h, WdStatAcc) */
     int32_t stat_cpg;     /* channels per statistics group */
-    int32_t dbg;          /* 0 in production.  0x400: take the two-workgroups-per-CU kernel (wd_gemm4_kernel) wherever it is
-                             legal, whatever the grid size (parity tests); 0x8000 / 0x10000: the 64 x 320 weights-to-registers
-                             kernel keeps the per-tap A path / takes the slab form where it is legal, whatever WDIFF_GEMMW_SLAB
-                             says (in the args wd_gemm_check returns, 0x10000 = the launch takes the slab form); 0x20000 /
-                             0x40000: the 64-row tiles of w_layout 3 (64320, 64080) keep the row loop of their epilogue / take
-                             its batched form - a thread's row loads in one round trip, then its stores - where that is legal,
-                             whatever WDIFF_EPI_BATCH says (in the args wd_gemm_check returns, 0x40000 = the 16-byte path of
-                             the launch's epilogue is the batched form; a launch whose pitches or addresses keep it off that
-                             path runs the element loop either way - wd_epilogue_batch_applies says both); other bits are timing
-                             experiments */
+    int32_t dbg;          /* 0 in production, else WD_DBG_* / WD_GEMMW_SLAB_* / WD_EPI_BATCH_* above.  WD_GEMMW_SLAB_OFF / _ON and
+                             WD_EPI_BATCH_OFF / _ON apply to the tiles of w_layout 3 (the slab form: 64320; the batched epilogue:
+                             64320 and 64080); in the args wd_gemm_check returns they are cleared and WD_DBG_STAGGER,
+                             WD_GEMMW_SLAB_BIT, WD_EPI_BATCH_BIT say what the launch does (a launch whose pitches or addresses
+                             keep it off the 16-byte epilogue path runs the element loop either way - wd_epilogue_batch_applies
+                             says both) */
     int32_t* tickets;     /* NULL: split-K partials are combined by a second launch.  Else ntickets ints, ALL ZERO before the
                            * call and left all zero by it, not shared with a launch that may run concurrently: one arrival
                            * counter per output tile - the workgroup that finishes a tile's last K slice sums the slices from
@@ -276,8 +290,8 @@ typedef struct wd_ff_args {
     const wd_bf16* w32_hi; /* folded tail (needs w3, npass 3): see above */
     const wd_bf16* w32_lo;
     const float* b32;
-    int32_t dbg; /* 0 in production.  0x20000 / 0x40000: the epilogue keeps its row loop / takes the batched form where it is legal,
-                    whatever WDIFF_EPI_BATCH says (in the args wd_ff_check returns, 0x40000 = the batched form, as wd_gemm_args.dbg) */
+    int32_t dbg; /* 0 in production.  WD_EPI_BATCH_OFF / _ON: the epilogue keeps its row loop / takes the batched form where it is legal,
+                    whatever WDIFF_EPI_BATCH says (in the args wd_ff_check returns, WD_EPI_BATCH_BIT = the batched form, as wd_gemm_args.dbg) */
 } wd_ff_args;
 int wd_ff_fused(const wd_ff_args* args, void* stream);
 /* What wd_ff_fused would do with `args`, without launching anything (host only): WD_OK when it accepts them, else WD_EINVAL.  On
@@ -806,7 +820,7 @@ typedef struct wd_dw_args {
     int32_t npass;            /* 3: hi.hi + hi.lo + lo.hi, 1: hi.hi */
     int32_t accumulate;       /* 1: grad += */
     int32_t nslice;           /* 0: automatic (wd_dw_slices), else <= m / 64 */
-    int32_t dbg;
+    int32_t dbg;              /* 0 in production.  WD_DBG_STAMPS: cycle sums into `stamps` */
     int32_t reserved;
     void* stamps;             /* NULL (debug builds: 16 u64 of cycle sums, see csrc/wd_dw.hip) */
     const wd_dw_item* items;  /* set by wd_dw_group (device memory); callers leave it NULL */

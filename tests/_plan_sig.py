@@ -14,7 +14,7 @@ import ctypes as C
 
 from worddiffusion_amd import _native as N
 
-SLAB_BIT = 0x10000  # wd_gemm_args.dbg of the RESOLVED args: the launch takes the slab form (include/wdiff_hip.h)
+SLAB_BIT = N.GEMMW_SLAB_BIT  # wd_gemm_args.dbg of the RESOLVED args: the launch takes the slab form (include/wdiff_hip.h)
 
 
 def _struct(args):

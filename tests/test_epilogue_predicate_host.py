@@ -1,6 +1,6 @@
 """wd_epilogue_batch_ok (csrc/wd_gemm_epi.h), the one rule that says which launches take the batched 64-row tile epilogue, asked
 without a GPU: through wd_epilogue_batch_applies on resolved args, and through the dbg bit wd_gemm_check / wd_ff_check resolve
-(0x40000 / 0x20000 force the form on / off for a call, resolved 0x40000 = batched form taken).  Nothing is launched.  The shapes of
+(WD_EPI_BATCH_ON / _OFF force the form on / off for a call, resolved WD_EPI_BATCH_BIT = batched form taken).  Nothing is launched.  The shapes of
 the B = 64 step are stated here by hand; tests/test_gpu_epilogue_batched.py asks the same of the plan the engine really builds."""
 import ctypes
 
@@ -9,7 +9,7 @@ import pytest
 from tests.test_host_logic import _P, _PLANES, _gemm_args
 from worddiffusion_amd import _native as N
 
-ON, OFF = 0x40000, 0x20000
+ON, OFF = N.EPI_BATCH_ON, N.EPI_BATCH_OFF
 _M = 64 * 256  # B = 64 samples of 8 x 32
 _CONV = dict(w_layout=3, tile=64320, slab_rows=32, bias=_P)
 _STAT = dict(stat_part=_P, stat_cpg=10)
@@ -69,6 +69,19 @@ def test_resolved_bit_follows_the_predicate(name):
     assert not off.dbg & (ON | OFF)
     on.dbg &= ~ON
     assert bytes(on) == bytes(off)  # the switch decides nothing else
+
+
+@pytest.mark.parametrize("switch", ["WD_GEMMW_SLAB", "WD_EPI_BATCH"])
+def test_request_bits_resolve_on_the_smallest_slab_shape(switch):
+    """The smallest legal slab launch (one 64 x 320 tile: a 3x3 source of 64 channels over one 8 x 8 image): *_ON resolves to
+    *_BIT, *_OFF clears it, and neither request bit of the switch is left in the args wd_gemm_check returns.  ksplit = 1: neither
+    form goes with a K cut, which wd_gemm would otherwise choose for a grid of one tile."""
+    on_bit, off_bit, bit = (N.DEFINES[f"{switch}_{k}"] for k in ("ON", "OFF", "BIT"))
+    a = _gemm_args(64, 320, 64, [(64, 9, True, 64)], w_layout=3, tile=64320, slab_rows=8, ksplit=1)
+    a.dbg = on_bit
+    assert _resolve(a).dbg & (on_bit | off_bit) == bit
+    a.dbg = off_bit
+    assert _resolve(a).dbg & (on_bit | off_bit | bit) == 0
 
 
 def test_predicate_on_single_conditions():

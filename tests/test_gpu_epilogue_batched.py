@@ -1,10 +1,10 @@
 """The batched form of the 64-row tile epilogue (wd_epilogue_rows, csrc/wd_gemm_epi.h): a thread's row loads in one round trip, then
 its rows' arithmetic and stores.  It is the row loop's arithmetic in the row loop's order, so every case launches twice through the
-C ABI - dbg 0x40000 (the batched form wherever wd_epilogue_batch_ok finds it legal) and dbg 0x20000 (the row loop, what
+C ABI - dbg WD_EPI_BATCH_ON (the batched form wherever wd_epilogue_batch_ok finds it legal) and dbg WD_EPI_BATCH_OFF (the row loop, what
 WDIFF_EPI_BATCH=0 runs) - and asks for
 
   * the same BITS in out_f32, both planes and stat_part;
-  * the resolved dbg bit 0x40000 on the first launch only (else the loop is compared with itself);
+  * the resolved dbg bit WD_EPI_BATCH_BIT on the first launch only (else the loop is compared with itself);
   * the batched result against the fp64 reference with the bounds of tests/test_gpu_gemmw_slab.py (result and planes rel_err < 2e-5,
     statistics max_rel < 1e-5), so that two equal wrong answers do not pass.
 
@@ -31,8 +31,8 @@ from worddiffusion_amd.engine import geglu_interleave  # noqa: E402
 from worddiffusion_amd.synthetic import fill_module_, synthetic_inputs  # noqa: E402
 
 DEV = "cuda:0"
-EPI_ON, EPI_OFF = 0x40000, 0x20000   # wd_gemm_args.dbg / wd_ff_args.dbg: override WDIFF_EPI_BATCH; resolved 0x40000 = batched form taken
-SLAB_ON, SLAB_OFF = 0x10000, 0x8000
+EPI_ON, EPI_OFF = N.EPI_BATCH_ON, N.EPI_BATCH_OFF   # wd_gemm_args.dbg / wd_ff_args.dbg: override WDIFF_EPI_BATCH; resolved EPI_ON = batched form taken
+SLAB_ON, SLAB_OFF = N.GEMMW_SLAB_ON, N.GEMMW_SLAB_OFF
 
 
 def _both(cs_kw, P, batched=True, dbg=0):

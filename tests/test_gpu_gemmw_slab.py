@@ -1,6 +1,6 @@
 """The slab form of the 64 x 320 weights-to-registers kernel (wd_gemmw_kernel<..., SLAB>, csrc/wd_gemmw.hip): the rows of a 3x3 /
 pad 1 / stride 1 source copied into LDS once per 64-channel chunk, the taps read as shifts of the slab row, K walked chunk-major.
-Every case runs wd_gemm through the C ABI twice - dbg 0x10000 (the slab form wherever wd_gemm finds it legal) and dbg 0x8000 (the
+Every case runs wd_gemm through the C ABI twice - dbg WD_GEMMW_SLAB_ON (the slab form wherever wd_gemm finds it legal) and dbg WD_GEMMW_SLAB_OFF (the
 per-tap form, what WDIFF_GEMMW_SLAB=0 runs) - and checks
 
   * the slab launch against the fp64 reference (F.conv2d on the fp32 inputs, + the fp64 1x1 of an identity second source) with the
@@ -24,10 +24,11 @@ from tests import _guard as G  # noqa: E402
 from tests._common import FULL, make_args, max_rel, rel_err  # noqa: E402
 from tests.test_gpu_pitch import DENSE, PITCH, _case, _conv, _launch, _unpl  # noqa: E402
 from worddiffusion_amd import UNetModel  # noqa: E402
+from worddiffusion_amd import _native as N  # noqa: E402
 from worddiffusion_amd.synthetic import fill_module_, synthetic_inputs  # noqa: E402
 
 DEV = "cuda:0"
-SLAB_ON, SLAB_OFF = 0x10000, 0x8000   # wd_gemm_args.dbg: override WDIFF_GEMMW_SLAB for the call; resolved 0x10000 = slab form taken
+SLAB_ON, SLAB_OFF = N.GEMMW_SLAB_ON, N.GEMMW_SLAB_OFF   # wd_gemm_args.dbg: override WDIFF_GEMMW_SLAB for the call; resolved SLAB_ON = slab form taken
 
 
 def _both(d, P, slab_expected=True, **kw):

@@ -225,7 +225,7 @@ def test_gemm_split_k(ksplit):
     tk = torch.zeros(4096, dtype=torch.int32, device=DEV)
     for _ in range(3):
         out3, pl3 = run_gemm(srcs, wcat.to(DEV), m, hw, bias=bias.to(DEV), rowvec=film.to(DEV), resid=res.to(DEV),
-                             want_planes=True, ksplit=ksplit, tickets=tk, dbg=0x2000)
+                             want_planes=True, ksplit=ksplit, tickets=tk, dbg=N.DBG_FORCE_TICKETS)
         assert torch.equal(out3, out) and torch.equal(pl3, pl)
         assert int(tk.abs().sum()) == 0
 
@@ -233,7 +233,7 @@ def test_gemm_split_k(ksplit):
 @pytest.mark.parametrize("B,hh,ww,c1,c2,n,ksplit", [(4, 4, 16, 320, 640, 320, 1), (3, 8, 32, 64, 0, 160, 1), (5, 5, 7, 128, 64, 200, 1),
                                                       (4, 4, 16, 320, 640, 320, 3), (64, 8, 32, 64, 0, 320, 1)])
 def test_gemm_two_workgroups_per_cu_kernel(B, hh, ww, c1, c2, n, ksplit):
-    """wd_gemm4_kernel (32-deep stages, four waves, 64-row half epilogues; dbg 0x400 forces it): 3x3 gather source + optional
+    """wd_gemm4_kernel (32-deep stages, four waves, 64-row half epilogues; dbg WD_DBG_FORCE_V4 forces it): 3x3 gather source + optional
     identity skip source, FiLM row vector, residual, planes out, ragged M / N, split-K - vs fp64, and vs the v2 kernel."""
     g = torch.Generator().manual_seed(B + hh + ww + c1 + n)
     hw, m = hh * ww, B * hh * ww
@@ -250,7 +250,7 @@ def test_gemm_two_workgroups_per_cu_kernel(B, hh, ww, c1, c2, n, ksplit):
         ref = ref + a2.double() @ wcat[:, 9 * c1:].double().t()
         srcs.append((planes_of(a2.to(DEV)), c2, 1, None, 0))
     kw = dict(bias=bias.to(DEV), rowvec=film.to(DEV), resid=res.to(DEV), want_planes=True, ksplit=ksplit, tile=128160)
-    out, pl = run_gemm(srcs, wcat.to(DEV), m, hw, dbg=0x400, **kw)
+    out, pl = run_gemm(srcs, wcat.to(DEV), m, hw, dbg=N.DBG_FORCE_V4, **kw)
     assert rel_err(out.cpu(), ref) < 2e-5 and rel_err(unplanes(pl).cpu(), ref) < 2e-5
     out0, _ = run_gemm(srcs, wcat.to(DEV), m, hw, **kw)
     assert max_rel(out.cpu(), out0.cpu()) < 5e-6
@@ -527,9 +527,9 @@ def test_gemm_weights_to_registers_kernel_statistics(B, hh, ww, cin, n, tile, ks
 @pytest.mark.parametrize("B,hh,ww,c1,c2,n,ksplit,npass", [(4, 4, 16, 320, 640, 320, 1, 3), (3, 8, 32, 64, 0, 160, 1, 3), (5, 5, 7, 128, 64, 200, 1, 3),
                                                             (4, 4, 16, 320, 640, 320, 3, 3), (64, 8, 32, 64, 0, 320, 1, 3), (2, 8, 32, 32, 0, 320, 1, 3),
                                                             (3, 8, 32, 96, 32, 160, 2, 1), (64, 8, 32, 320, 0, 320, 1, 3)])
-@pytest.mark.parametrize("sel", [0x80000])
+@pytest.mark.parametrize("sel", [N.DBG_FORCE_V8])
 def test_gemm_deep_pipeline_kernel(B, hh, ww, c1, c2, n, ksplit, npass, sel):
-    """wd_gemm8_kernel (dbg 0x80000 forces it): 32-deep stages in a ring of four LDS buffers, counted vmcnt, four dedicated loader
+    """wd_gemm8_kernel (dbg WD_DBG_FORCE_V8 forces it): 32-deep stages in a ring of four LDS buffers, counted vmcnt, four dedicated loader
     waves + eight compute waves with two fragment sets -
     3x3 gather source + optional identity skip source, FiLM row vector, residual, planes out, ragged M / N, split-K, short K loops
     (1 .. 3 stages: the prologue / drain paths), single-pass bf16 - vs fp64 and vs the v2 kernel; repeated launches give the same bits
@@ -562,7 +562,7 @@ def test_gemm_deep_pipeline_kernel(B, hh, ww, c1, c2, n, ksplit, npass, sel):
         assert torch.equal(out, out2) and torch.equal(pl, pl2)
 
 
-@pytest.mark.parametrize("k,sel", [(32, 0x80000), (64, 0x80000), (96, 0x80000), (128, 0x80000), (160, 0x80000), (320, 0x80000)])
+@pytest.mark.parametrize("k,sel", [(k, N.DBG_FORCE_V8) for k in (32, 64, 96, 128, 160, 320)])
 def test_gemm_deep_pipeline_kernel_short_loops(k, sel):
     """1 .. 10 stages of a plain linear through wd_gemm8_kernel: every length of the prologue / steady state / drain."""
     if not N.lib().wd_gemm_experimental():
@@ -585,7 +585,7 @@ def test_gemm_two_workgroups_per_cu_kernel_geglu():
     ref = h[:, :inner] * F.gelu(h[:, inner:])
     for npass, tol in ((3, 2e-5), (1, 2e-2)):
         out, pl = run_gemm([(planes_of(a.to(DEV)), dim, 1, None, 0)], geglu_interleave(w, 80).to(DEV), m, 1, npass=npass,
-                           bias=geglu_interleave(b, 80).to(DEV), act=N.ACT_GEGLU, want_planes=True, tile=128160, dbg=0x400)
+                           bias=geglu_interleave(b, 80).to(DEV), act=N.ACT_GEGLU, want_planes=True, tile=128160, dbg=N.DBG_FORCE_V4)
         assert rel_err(out.cpu(), ref) < tol and rel_err(unplanes(pl).cpu(), ref) < tol
 
 
@@ -746,7 +746,7 @@ def test_gemm_fused_groupnorm_statistics(B, hh, ww, cin, n, ksplit):
     if ksplit != 1:  # the same launch with the in-launch split-K combine: identical output and statistics
         out_sep, part_sep = out.clone(), part.clone()
         tk = torch.zeros(1024, dtype=torch.int32, device=DEV)
-        lib_args.tickets, lib_args.ntickets, lib_args.dbg = tk.data_ptr(), tk.numel(), 0x2000
+        lib_args.tickets, lib_args.ntickets, lib_args.dbg = tk.data_ptr(), tk.numel(), N.DBG_FORCE_TICKETS
         out.zero_()
         part.fill_(float("nan"))
         N.check(lib.wd_gemm(C.byref(lib_args), _st()), "wd_gemm+stats+tickets")
@@ -1033,9 +1033,9 @@ def test_folded_cross_attention_pair():
 @pytest.mark.parametrize("B,h,w,cin,cout,skip,ksplit", [(3, 8, 32, 64, 160, 0, 1), (2, 8, 32, 128, 320, 64, 1), (3, 5, 7, 64, 96, 0, 1),
                                                           (5, 4, 16, 64, 320, 128, 0), (2, 3, 200, 64, 64, 0, 1),
                                                           (64, 8, 32, 320, 320, 0, 1)])
-@pytest.mark.parametrize("form", [0x1000])
+@pytest.mark.parametrize("form", [N.DBG_FORCE_CONV3])
 def test_conv3x3_row_shared_taps_kernel(B, h, w, cin, cout, skip, ksplit, form):
-    """wd_gemm with w_layout 2 (wd_conv3_kernel, forced by dbg 0x1000: the three taps of a kernel row share one A tile, 16x16x32 MFMA,
+    """wd_gemm with w_layout 2 (wd_conv3_kernel, forced by dbg WD_DBG_FORCE_CONV3: the three taps of a kernel row share one A tile, 16x16x32 MFMA,
     stagger) vs F.conv2d (+ 1x1 skip over a second source), incl. panels that straddle samples, narrow / wide images, split-K, and
     the headline shape."""
     if not N.lib().wd_gemm_experimental():

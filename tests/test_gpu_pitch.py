@@ -276,8 +276,8 @@ _FORMS = {
     "V2 64x64 3x3 + skip": ("K_V2", lambda n: dict(_conv(n), tile=64064), _N100),
     "M16 linear": ("K_M16", lambda n: dict(_linear(130, 128, n), tile=128160), dict(a=160, c=160, d=160)),
     "M16 3x3 + skip, ragged n": ("K_M16", lambda n: dict(_conv(n), tile=128160), dict(a=200, c=200, d=200)),
-    "V4 linear": ("K_V4", lambda n: dict(_linear(130, 128, n), tile=128160, dbg=0x400), dict(a=160, c=160, d=160)),
-    "V4 3x3 + skip": ("K_V4", lambda n: dict(_conv(n), tile=128160, dbg=0x400), dict(a=160, c=200, d=160)),
+    "V4 linear": ("K_V4", lambda n: dict(_linear(130, 128, n), tile=128160, dbg=N.DBG_FORCE_V4), dict(a=160, c=160, d=160)),
+    "V4 3x3 + skip": ("K_V4", lambda n: dict(_conv(n), tile=128160, dbg=N.DBG_FORCE_V4), dict(a=160, c=200, d=160)),
     "W 64x320 linear": ("K_GEMMW", lambda n: dict(_linear(130, 64, n), tile=64320, w_layout=3), dict(a=320, c=320, d=320)),
     "W 64x320 3x3 + skip": ("K_GEMMW", lambda n: dict(_conv(n), tile=64320, w_layout=3), dict(a=320, c=320, d=320)),
     "W 64x320 3x3 + skip, computed rows": ("K_GEMMW", lambda n: dict(_conv(n), tile=64320, w_layout=3, slab_rows=8), dict(a=320, c=320, d=320)),
@@ -393,7 +393,7 @@ def test_gemm_run_of_weight_rows_into_a_column_slice():
     _check(_case(kernel="K_V1", w_embed=16, planes=False, **dict(dv, tile=128064)), _pitch(out=(156, 40)), "rows 16..116, V1: ")
 
 
-# ---- K cut: the separate combine launch and the in-launch combine (tickets + dbg 0x2000)
+# ---- K cut: the separate combine launch and the in-launch combine (tickets + dbg WD_DBG_FORCE_TICKETS)
 def _gn_ref(ref, hw, cpg, gam, bet, eps, silu):
     m, n = ref.shape
     y = F.group_norm(ref.reshape(m // hw, hw, n).permute(0, 2, 1), n // cpg, gam.double(), bet.double(), eps)
@@ -410,7 +410,7 @@ def test_gemm_k_cut_on_pitched_operands(name, ksplit, tickets):
     output with resid == out_f32 accumulates in place (reference acc0 + A W^T + bias) - in the flat combine launch, and with tickets
     inside the GEMM's own epilogue.  wd_gemm keeps the tickets only for whole column tiles on the LDS-staged kernels: the
     tickets = True runs of the other cases assert that they resolve to the combine launch."""
-    kw = dict(ksplit=ksplit, tickets=tickets, dbg=0x2000 if tickets else 0)
+    kw = dict(ksplit=ksplit, tickets=tickets, dbg=N.DBG_FORCE_TICKETS if tickets else 0)
     if name == "direct, n 160":
         cs = _case(kernel="K_M16", **dict(_conv(160), tile=128160, **kw))
     elif name == "image, n 100":

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 from tests._common import DEEP, FULL, FWD_CASES, SMALL, golden_state_dict, load_golden, make_args
 from worddiffusion_amd import Diffusion, UNetModel, UNetModelPhosc, label_padding
 from worddiffusion_amd import _native as N
-from worddiffusion_amd.engine import conv_gather_table, geglu_interleave
+from worddiffusion_amd.engine import conv_gather_table, gather_hint, geglu_interleave
 
 
 @pytest.mark.parametrize("tag", sorted(FWD_CASES))
@@ -527,3 +527,14 @@ def test_plan_train_refuses_before_any_device_work():
     with pytest.raises(NotImplementedError, match="out_channels"):
         wide.plan_train(2, 4, 8, 10)
     assert not eng._tplans and not wide._tplans
+
+
+@pytest.mark.parametrize("h,w", [(8, 32), (4, 16), (5, 7)])
+def test_gather_table_width_hint(h, w):
+    """The width a gather table lets the GEMM planner pass as wd_gemm_args.slab_rows (same_w, down_w): the image width of a
+    3x3 / pad 1 / stride 1 table, the OUTPUT width of a stride-2 one, nothing for a table the kernel has to read."""
+    wo = {mode: conv_gather_table(h, w, mode)[2] for mode in ("same", "down", "down_rb", "up")}
+    assert gather_hint("same", w, wo["same"]) == (w, 0) and wo["same"] == w
+    assert gather_hint("down", w, wo["down"]) == (0, (w + 1) // 2)
+    assert gather_hint("down_rb", w, wo["down_rb"]) == (0, 0) and gather_hint("up", w, wo["up"]) == (0, 0)
+    assert gather_hint("up4", w, 2 * w) == (0, 0)

@@ -1,6 +1,9 @@
 """The ctypes binding is derived from include/wdiff_hip.h: the parser on a synthetic header, the derived layouts against what the
 C compiler makes of the real header, and the three device-table records against their byte-level specification.  No GPU."""
 import ctypes as C
+import glob
+import os
+import re
 import struct
 import subprocess
 
@@ -151,3 +154,29 @@ def test_table_records_byte_for_byte(cls, fmt, size, rows):
     for row in rows:
         assert bytes(rec(*row)) == struct.pack(fmt, *row), row
     assert bytes((rec * len(rows))(*rows)) == b"".join(struct.pack(fmt, *row) for row in rows)
+
+
+SELECTORS = N.DBG_NAMES  # every bit of wd_gemm_args.dbg / wd_ff_args.dbg / wd_dw_args.dbg a caller may set or a check returns
+
+
+def test_form_selectors_are_named_once_in_the_header():
+    """Each selector is one bit of its own; the resolved *_BIT of a switch is its *_ON request bit."""
+    values = [N.DEFINES[n] for n in SELECTORS]
+    assert all(v > 0 and v & (v - 1) == 0 for v in values), dict(zip(SELECTORS, values))
+    assert len(set(values)) == len(values) == 11
+    for switch in ("WD_GEMMW_SLAB", "WD_EPI_BATCH"):
+        assert N.DEFINES[switch + "_BIT"] == N.DEFINES[switch + "_ON"] != N.DEFINES[switch + "_OFF"]
+    assert (N.GEMMW_SLAB_BIT, N.EPI_BATCH_BIT, N.DBG_STAMPS) == (N.GEMMW_SLAB_ON, N.EPI_BATCH_ON, N.DEFINES["WD_DBG_STAMPS"])
+
+
+def test_no_selector_literal_left_in_python():
+    """A plain text search: no line of the package, the tests or the tools that speaks of the selector word still carries a
+    hexadecimal literal - the values live in include/wdiff_hip.h alone."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    word, literal = "dbg", re.compile(r"0[xX][0-9a-fA-F]")
+    hits = []
+    for sub in ("worddiffusion_amd", "tests", "tools"):
+        for path in sorted(glob.glob(os.path.join(root, sub, "**", "*.py"), recursive=True)):
+            with open(path) as f:
+                hits += [f"{os.path.relpath(path, root)}:{i}" for i, line in enumerate(f, 1) if word in line and literal.search(line)]
+    assert not hits, hits

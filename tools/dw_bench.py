@@ -54,7 +54,7 @@ def main():
         g.m, g.n, g.c, g.npass, g.nslice = m, n, c, a.npass, ns
         if a.stamps:
             sb = torch.zeros(16, dtype=torch.int64, device=DEV)
-            g.stamps, g.dbg = sb.data_ptr(), 0x100
+            g.stamps, g.dbg = sb.data_ptr(), N.DBG_STAMPS
             N.check(lib.wd_dw(C.byref(g), st), name)
             torch.cuda.synchronize()
             v = sb.cpu().view(2, 2, 4)

@@ -41,7 +41,7 @@ def timed(launch, iters):
 
 def _epi_dbg(epi_batch):
     """wd_ff_args.dbg for --epi-batch: 1 / 0 = the batched epilogue where legal / the row loop, whatever WDIFF_EPI_BATCH says."""
-    return 0 if epi_batch < 0 else 0x40000 if epi_batch else 0x20000
+    return 0 if epi_batch < 0 else N.EPI_BATCH_ON if epi_batch else N.EPI_BATCH_OFF
 
 
 def front(m, iters, epi_batch=-1):
@@ -68,7 +68,7 @@ def front(m, iters, epi_batch=-1):
     st = torch.cuda.current_stream().cuda_stream
     N.check(blk.lib.wd_ff_fused(C.byref(f), st), "wd_ff_fused (front)")
     us = timed(lambda: blk.lib.wd_ff_fused(C.byref(f), st), iters)
-    print(f"wd_ff_fused front m={blk.m} ({blk.m // 64} workgroups) epi_batch={int(bool(r.dbg & 0x40000))}: {us:7.1f} us   lib {N.LIB_PATH}")
+    print(f"wd_ff_fused front m={blk.m} ({blk.m // 64} workgroups) epi_batch={int(bool(r.dbg & N.EPI_BATCH_BIT))}: {us:7.1f} us   lib {N.LIB_PATH}")
 
 
 def main():
@@ -78,7 +78,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--m", type=int, default=16384)
     ap.add_argument("--epi-batch", type=int, default=-1, help="1 / 0: the epilogue takes its batched form where legal / keeps the row loop "
-                    "(wd_ff_args.dbg 0x40000 / 0x20000), whatever WDIFF_EPI_BATCH says")
+                    "(wd_ff_args.dbg WD_EPI_BATCH_ON / _OFF), whatever WDIFF_EPI_BATCH says")
     a = ap.parse_args()
     if a.front:
         return front(a.m, a.iters, a.epi_batch)

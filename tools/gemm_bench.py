@@ -53,10 +53,10 @@ def main():
     ap.add_argument("--wdirect", type=int, default=0, help="1 / 2: fragment-major weights, 128 x 160 / 64 x 320 weights-to-registers kernel (w_layout 3); 3: the 64 x 80 whole-K kernel for 64-position samples (tile 64080); "
                     "the result is compared with the default kernel's first")
     ap.add_argument("--gemmw-slab", type=int, default=-1, help="with --wdirect 2: 1 / 0 = the 64 x 320 kernel takes its slab form where "
-                    "legal / keeps the per-tap A path (wd_gemm_args.dbg 0x10000 / 0x8000), whatever WDIFF_GEMMW_SLAB says; the step's "
+                    "legal / keeps the per-tap A path (wd_gemm_args.dbg WD_GEMMW_SLAB_ON / _OFF), whatever WDIFF_GEMMW_SLAB says; the step's "
                     "four layer shapes are conv8x32, conv8x32cat, conv8x32id, conv8x32catid (--slab is the experimental slab-ORDER kernel)")
     ap.add_argument("--epi-batch", type=int, default=-1, help="with --wdirect 2 / 3: 1 / 0 = the 64-row tiles take the batched epilogue where legal / "
-                    "keep the row loop (wd_gemm_args.dbg 0x40000 / 0x20000), whatever WDIFF_EPI_BATCH says")
+                    "keep the row loop (wd_gemm_args.dbg WD_EPI_BATCH_ON / _OFF), whatever WDIFF_EPI_BATCH says")
     ap.add_argument("--cold", type=int, default=0, help="1: flush caches (1 GiB write) before every launch; "
                     "2: same, then read the weights once (emulates a prefetch) before the launch")
     ap.add_argument("--a32", type=int, default=0, help="1 (with --wdirect 2): src[0] is the fp32 map, GroupNorm + SiLU applied inside "
@@ -114,10 +114,10 @@ def main():
         tk = torch.zeros(8192, dtype=torch.int32, device=DEV)
         if a.tickets:
             g.tickets, g.ntickets = tk.data_ptr(), tk.numel()
-            g.dbg = g.dbg | 0x2000
+            g.dbg = g.dbg | N.DBG_FORCE_TICKETS
         if a.conv3 and kind == "conv3":
             g.w_layout, g.slab_rows = 2, w
-            g.dbg = a.dbg | 0x1000
+            g.dbg = a.dbg | N.DBG_FORCE_CONV3
         if a.wdirect and cout % 160 == 0 and kind != "geglu":
             N.check(lib.wd_gemm(C.byref(g), st), name)   # reference result from the default kernel
             ref = out.clone()
@@ -126,9 +126,9 @@ def main():
             g.w_hi, g.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
             g.w_layout, g.slab_rows, g.tile = 3, (w if ntaps == 9 else 0), (64320 if a.wdirect == 2 else 64080 if a.wdirect == 3 else 128160)
             if a.gemmw_slab >= 0:
-                g.dbg = a.dbg = a.dbg | (0x10000 if a.gemmw_slab else 0x8000)
+                g.dbg = a.dbg = a.dbg | (N.GEMMW_SLAB_ON if a.gemmw_slab else N.GEMMW_SLAB_OFF)
             if a.epi_batch >= 0:
-                g.dbg = a.dbg = a.dbg | (0x40000 if a.epi_batch else 0x20000)
+                g.dbg = a.dbg = a.dbg | (N.EPI_BATCH_ON if a.epi_batch else N.EPI_BATCH_OFF)
             if a.a32:
                 x32 = torch.randn(m, cin, device=DEV)
                 nchunk = lib.wd_gn_nchunk(hw)
@@ -146,7 +146,7 @@ def main():
             print(f"{name}: w-direct vs default kernel max |diff| {float((out - ref).abs().max()):.3e}  (max |ref| {float(ref.abs().max()):.3f})", flush=True)
         if a.stamps and a.wdirect == 3:
             sb = torch.zeros(64, dtype=torch.int64, device=DEV)
-            g.ws, g.ws_floats, g.dbg = sb.data_ptr(), 0, a.dbg | 0x100
+            g.ws, g.ws_floats, g.dbg = sb.data_ptr(), 0, a.dbg | N.DBG_STAMPS
             N.check(lib.wd_gemm(C.byref(g), st), name)
             torch.cuda.synchronize()
             v = sb.cpu().view(8, 8)
@@ -158,7 +158,7 @@ def main():
         elif a.stamps:
             nk = (ktot // 64 + 1) & ~1 if a.wdirect else ktot // 64
             sb = torch.zeros(8 * nk * 4 + 16, dtype=torch.int64, device=DEV)   # + [wave][2]: the epilogue (w-direct kernels)
-            g.ws, g.ws_floats, g.dbg = sb.data_ptr(), 0, a.dbg | 0x100
+            g.ws, g.ws_floats, g.dbg = sb.data_ptr(), 0, a.dbg | N.DBG_STAMPS
             N.check(lib.wd_gemm(C.byref(g), st), name)
             torch.cuda.synchronize()
             v = sb.cpu()[:8 * nk * 4].view(8, nk, 4)

@@ -93,6 +93,12 @@ WdSrc, WdGemmArgs, WdFfArgs, WdDwArgs, WdDwItem, WdDropout, WdRepackEntry, WdAda
                          "wd_adamw_table_entry", "wd_colsum_entry"))
 WD_OK, WD_EINVAL, WD_ELAUNCH, WD_ESTATE = (DEFINES[n] for n in ("WD_OK", "WD_EINVAL", "WD_ELAUNCH", "WD_ESTATE"))
 ACT_NONE, ACT_SILU, ACT_GEGLU = (DEFINES[n] for n in ("WD_ACT_NONE", "WD_ACT_SILU", "WD_ACT_GEGLU"))
+# the bits of wd_gemm_args.dbg / wd_ff_args.dbg / wd_dw_args.dbg (kernel-form selectors of the parity tests and the benchmark tools)
+DBG_NAMES = ("WD_DBG_STAMPS", "WD_DBG_STAGGER", "WD_DBG_FORCE_V4", "WD_DBG_FORCE_CONV3", "WD_DBG_FORCE_TICKETS", "WD_DBG_GEMMW_INSTEP",
+             "WD_GEMMW_SLAB_OFF", "WD_GEMMW_SLAB_ON", "WD_EPI_BATCH_OFF", "WD_EPI_BATCH_ON", "WD_DBG_FORCE_V8")
+(DBG_STAMPS, DBG_STAGGER, DBG_FORCE_V4, DBG_FORCE_CONV3, DBG_FORCE_TICKETS, DBG_GEMMW_INSTEP, GEMMW_SLAB_OFF, GEMMW_SLAB_ON, EPI_BATCH_OFF,
+ EPI_BATCH_ON, DBG_FORCE_V8) = (DEFINES[n] for n in DBG_NAMES)
+GEMMW_SLAB_BIT, EPI_BATCH_BIT = DEFINES["WD_GEMMW_SLAB_BIT"], DEFINES["WD_EPI_BATCH_BIT"]  # in the args a check returns: the form taken
 VAE_MAX_LATENT, STREAM_VAE_POSTERIOR, STREAM_DROPOUT0, NCLASS = (
     DEFINES[n] for n in ("WD_VAE_MAX_LATENT", "WD_STREAM_VAE_POSTERIOR", "WD_STREAM_DROPOUT0", "WD_NCLASS"))
 STREAM_KNOWN, TAG_KNOWN = DEFINES["WD_STREAM_KNOWN"], DEFINES["WD_TAG_KNOWN"]

@@ -254,10 +254,10 @@ __global__ void __launch_bounds__(DW_NT, 1) wd_dw_kernel(const wd_dw_args a0, co
     // multiply half-step, one half-step before the data is read.
     // Each group runs its own straight-line loop (a branch around the MFMA block inside one shared loop made hipcc copy the 100
     // accumulator registers at the join); the barriers pair up by count: both groups execute U + 1 half-steps.
-    // (-DWD_DW_STAMPS + a.dbg & 0x100: s_memtime sums of workgroup 0's waves 0 and 4 into a.stamps - per kind of half-step
+    // (-DWD_DW_STAMPS + a.dbg & WD_DBG_STAMPS: s_memtime sums of workgroup 0's waves 0 and 4 into a.stamps - per kind of half-step
     // (0 read, 1 multiply) the ticks spent in DMA issue, the work, the waits and the barrier; tools/dw_bench.py --stamps)
 #ifdef WD_DW_STAMPS
-    const bool stamp = (a.dbg & 0x100) && blockIdx.x == 0 && a.stamps;
+    const bool stamp = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && a.stamps;
     unsigned long long tsum[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, t0 = 0, t1 = 0, t2 = 0, t3 = 0;
 #define DW_STAMP(v) if (stamp) v = __builtin_amdgcn_s_memtime()
 #define DW_STAMP_SUM(kind, ksub)                                     \

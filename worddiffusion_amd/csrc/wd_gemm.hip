@@ -575,10 +575,10 @@ __global__ void __launch_bounds__(256 * KS, 1) wd_gemm2_kernel(const wd_gemm_arg
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        const bool stamp16 = (a.dbg & 0x100) && blockIdx.x == 0 && lane == 0 && a.ws;
+        const bool stamp16 = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && lane == 0 && a.ws;
         unsigned long long* sb16 = reinterpret_cast<unsigned long long*>(a.ws) + (long)wave * nk * 4;
-        if (a.dbg & 0x200 ? kh == 1 : false) {
-            // stagger (a.dbg & 0x200): the second K-half group multiplies one stage late, so its LDS reads fall under the
+        if (a.dbg & WD_DBG_STAGGER ? kh == 1 : false) {
+            // stagger (a.dbg & WD_DBG_STAGGER): the second K-half group multiplies one stage late, so its LDS reads fall under the
             // first group's MFMAs and vice versa.  It keeps TWO fragment sets and alternates between them, so the reads of
             // stage k never wait for the MFMAs of stage k-1 to have consumed their operands (the loop is unrolled by two to
             // keep the register indices static).
@@ -695,7 +695,7 @@ __global__ void __launch_bounds__(256 * KS, 1) wd_gemm2_kernel(const wd_gemm_arg
         // late group (its own loop, so that the fragments carried across the barrier do not constrain the early group's
         // register allocation): multiply the fragments of the previous stage while the early group reads this one; only
         // then (fragments dead) compute and issue its share of the next stage's DMA, then read this stage
-        const bool stamp_l = (a.dbg & 0x100) && blockIdx.x == 0 && lane == 0 && a.ws;
+        const bool stamp_l = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && lane == 0 && a.ws;
         unsigned long long* sbuf_l = reinterpret_cast<unsigned long long*>(a.ws) + (long)wave * nk * 4;
         for (int kit = 0; kit < nk; ++kit) {
             if (stamp_l) sbuf_l[kit * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -723,8 +723,8 @@ __global__ void __launch_bounds__(256 * KS, 1) wd_gemm2_kernel(const wd_gemm_arg
         }
         if (nk > 0) mfma_stage(false, smem);
     } else {
-        // (a.dbg & 0x100: per-stage cycle stamps of workgroup 0 into a.ws as u64 [wave][stage][4] - tools/gemm_bench.py --stamps)
-        const bool stamp = (a.dbg & 0x100) && blockIdx.x == 0 && lane == 0 && a.ws;
+        // (a.dbg & WD_DBG_STAMPS: per-stage cycle stamps of workgroup 0 into a.ws as u64 [wave][stage][4] - tools/gemm_bench.py --stamps)
+        const bool stamp = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && lane == 0 && a.ws;
         unsigned long long* sbuf = reinterpret_cast<unsigned long long*>(a.ws) + (long)wave * nk * 4;
         for (int kit = 0; kit < nk; ++kit) {
             if (stamp) sbuf[kit * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -1731,7 +1731,7 @@ __global__ void __launch_bounds__(512, 1) wd_conv3_kernel(const wd_gemm_args a, 
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    const bool stamp = (a.dbg & 0x100) && blockIdx.x == 0 && lane == 0 && a.ws && a.ksplit == 1;
+    const bool stamp = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && lane == 0 && a.ws && a.ksplit == 1;
     unsigned long long* sb = reinterpret_cast<unsigned long long*>(a.ws) + (long)wave * nk * 4;
     if (kh == 1) {
         // late group: DMA of the next stage first, then the previous stage's products, then this stage's fragments
@@ -2406,7 +2406,7 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         const wd_src& q0 = a.src[0];
         static const int conv3_mode = getenv("WDIFF_CONV3") ? atoi(getenv("WDIFF_CONV3")) : 0;
 #ifdef WDIFF_EXPERIMENTAL
-        const bool conv3_env = conv3_mode != 0 || (a.dbg & 0x1000);  // (dbg 0x1000: the parity tests pick the kernel)
+        const bool conv3_env = conv3_mode != 0 || (a.dbg & WD_DBG_FORCE_CONV3);  // (dbg WD_DBG_FORCE_CONV3: the parity tests pick the kernel)
 #else
         const bool conv3_env = false;
         (void)conv3_mode;
@@ -2444,19 +2444,19 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         // WDIFF_GEMM_V4: 0 never, 1 always (where legal), default 2 = when every CU gets at least two workgroups
         static const int v4_env = getenv("WDIFF_GEMM_V4") ? atoi(getenv("WDIFF_GEMM_V4")) : 2;
         const long wgs = (long)((a.m + 127) / 128) * ((a.n + 159) / 160) * a.ksplit;
-        use_v4 = v2ok && !a.stat_part && (v4_env == 1 || (v4_env == 2 && wgs >= 512) || (a.dbg & 0x400));
+        use_v4 = v2ok && !a.stat_part && (v4_env == 1 || (v4_env == 2 && wgs >= 512) || (a.dbg & WD_DBG_FORCE_V4));
     }
     {
         // in-launch split-K combine (tickets): v2 kernels only, vector epilogue (16-byte aligned everything), whole column tiles
         // Measured on the 4x16-level convolutions (M = 4096, 64 tiles x 4 slices of 80 KB): 46.0 us against 33.8 us for GEMM +
         // combine launch - the slabs of a tile are combined by ONE workgroup (64 busy CUs) behind an agent-scope release /
         // acquire, the combine launch spreads the same bytes over 512 workgroups - so the default is the second launch
-        // (the guide's rule: in-launch pays up to a few tens of KB of slabs per tile).  dbg 0x2000 forces it (parity tests).
+        // (the guide's rule: in-launch pays up to a few tens of KB of slabs per tile).  dbg WD_DBG_FORCE_TICKETS forces it (parity tests).
         static const bool fuse_env = getenv("WDIFF_GEMM_FUSE_COMBINE") ? atoi(getenv("WDIFF_GEMM_FUSE_COMBINE")) != 0 : false;
         const int bn = tile % 1000, bm = tile / 1000;
         const long ntile = (long)((a.m + bm - 1) / bm) * ((a.n + bn - 1) / bn);
         const bool aligned = (a.n & 3) == 0 && a.n % bn == 0 && wd_epilogue_vec_ok(a) && (reinterpret_cast<uintptr_t>(a.ws) & 15) == 0;
-        if (!((fuse_env || (a.dbg & 0x2000)) && a.tickets && a.ksplit > 1 && v2ok && !use_v4 && !conv3 && aligned && ntile <= a.ntickets))
+        if (!((fuse_env || (a.dbg & WD_DBG_FORCE_TICKETS)) && a.tickets && a.ksplit > 1 && v2ok && !use_v4 && !conv3 && aligned && ntile <= a.ntickets))
             a.tickets = nullptr;
     }
     // the GroupNorm epilogue exists in the combine launch of the 128 x 160 kernels only: anything else is an error, not a skipped norm
@@ -2475,18 +2475,18 @@ static int wd_gemm_resolve(const wd_gemm_args& in, WdResolved& r) {
         if (use_v4) return r.a = a, r.kernel = K_V4, WD_OK;
 #ifdef WDIFF_EXPERIMENTAL
         // ring kernel with dedicated loader waves (wd_gemm8_kernel): within +-5 % of the default kernel on every shape; no
-        // fused GroupNorm statistics (its 768-thread epilogue would need a larger statistics scratch).  WDIFF_GEMM_V8=1 takes it wherever legal, dbg 0x80000 forces it (parity tests).
+        // fused GroupNorm statistics (its 768-thread epilogue would need a larger statistics scratch).  WDIFF_GEMM_V8=1 takes it wherever legal, dbg WD_DBG_FORCE_V8 forces it (parity tests).
         static const int v8_env = getenv("WDIFF_GEMM_V8") ? atoi(getenv("WDIFF_GEMM_V8")) : 0;
         bool v8ok = a.ktot % 32 == 0 && a.src[0].ntaps <= 9 && !a.stat_part && !a.gn_gamma && a.act != WD_ACT_GEGLU &&
                     (a.nsrc == 1 || (a.src[1].gather == nullptr && a.src[1].ntaps == 1));
         for (int s8 = 0; s8 < a.nsrc; ++s8) v8ok = v8ok && (a.src[s8].c % 32 == 0);
-        if (v8ok && (v8_env == 1 || (a.dbg & 0x80000))) {
+        if (v8ok && (v8_env == 1 || (a.dbg & WD_DBG_FORCE_V8))) {
             if (a.ksplit > 1 && (a.ktot / 32 < a.ksplit || (long)a.ksplit * a.m * a.n > a.ws_floats)) a.ksplit = 1;
             a.tickets = nullptr;
             return r.a = a, r.kernel = K_V8, WD_OK;
         }
 #endif
-        if (v2ok && r.ks == 2 && m16 && stagger && nk64 / a.ksplit >= stagger_min) a.dbg |= 0x200;
+        if (v2ok && r.ks == 2 && m16 && stagger && nk64 / a.ksplit >= stagger_min) a.dbg |= WD_DBG_STAGGER;
         if (v2ok && r.ks == 2 && m16) return r.a = a, r.kernel = K_M16, WD_OK;
     }
 #ifdef WDIFF_EXPERIMENTAL

@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(QNT, 1) wd_gemmq_kernel(const wd_gemm_args a, 
         }
     };
 #ifdef WD_Q_STAMPS
-    unsigned long long* qst = (a.dbg & 0x100) && a.ws && blockIdx.x == 0 ? reinterpret_cast<unsigned long long*>(a.ws) + wave * 8 : nullptr;
+    unsigned long long* qst = (a.dbg & WD_DBG_STAMPS) && a.ws && blockIdx.x == 0 ? reinterpret_cast<unsigned long long*>(a.ws) + wave * 8 : nullptr;
 #define Q_STAMP(i) if (qst && lane == 0) qst[i] = __builtin_amdgcn_s_memtime()
 #else
 #define Q_STAMP(i)

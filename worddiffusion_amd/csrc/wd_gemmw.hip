@@ -542,9 +542,9 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
     // a 1 KB load holds its wave for 60-190 cycles while the vector memory path is busy (per-stage stamps: ~1400 cycles for twelve
     // from four waves at once, i.e. the ~33 B/clk a CU gets out of L2) - spread between the MFMAs they stalled the MFMA stream of
     // their own wave (8 % slower), as a burst they stall a wave whose SIMD partner is multiplying.
-    // (-DWD_GEMMW_STAMPS + a.dbg & 0x100: s_memtime stamps of workgroup 0 into a.ws as u64 [wave][stage][4], tools/gemm_bench.py --stamps)
+    // (-DWD_GEMMW_STAMPS + a.dbg & WD_DBG_STAMPS: s_memtime stamps of workgroup 0 into a.ws as u64 [wave][stage][4], tools/gemm_bench.py --stamps)
 #ifdef WD_GEMMW_STAMPS
-    const bool stamp = (a.dbg & 0x100) && blockIdx.x == 0 && lane == 0 && a.ws;
+    const bool stamp = (a.dbg & WD_DBG_STAMPS) && blockIdx.x == 0 && lane == 0 && a.ws;
     unsigned long long* sb = reinterpret_cast<unsigned long long*>(a.ws) + (long)wave * ((nk + 1) & ~1) * 4;
 #define WD_STAMP(i) if (stamp) sb[kit * 4 + (i)] = __builtin_amdgcn_s_memtime()
 #define WD_STAMP_LGKM() if (stamp) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -552,7 +552,7 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
 #define WD_STAMP(i)
 #define WD_STAMP_LGKM()
 #endif
-    if (kh == 0 || (a.dbg & 0x4000)) {
+    if (kh == 0 || (a.dbg & WD_DBG_GEMMW_INSTEP)) {
         auto half_step = [&](const int kit, const bf16x8 (&bcur)[5][NPL], bf16x8 (&bnext)[5][NPL]) {
             // (the MFMAs are register-only: without these fences hipcc moves them below the next stage's barrier and ds_write,
             // whose vmcnt(0) then waits for loads issued a few instructions earlier - the prefetch distance is gone)
@@ -628,7 +628,7 @@ __global__ void __launch_bounds__(WNT, 1) wd_gemmw_kernel(const wd_gemm_args a, 
         }
         __syncthreads();
     }
-    // (-DWD_GEMMW_STAMPS + a.dbg & 0x100: the epilogue of workgroup 0, finished image -> the wave's stores acknowledged, as u64 [wave][2] behind the
+    // (-DWD_GEMMW_STAMPS + a.dbg & WD_DBG_STAMPS: the epilogue of workgroup 0, finished image -> the wave's stores acknowledged, as u64 [wave][2] behind the
     // per-stage stamps, i.e. at a.ws + 8 * 4 * (ktot / 64 rounded up to even); tools/gemm_bench.py --stamps)
 #ifdef WD_GEMMW_STAMPS
     unsigned long long* se = reinterpret_cast<unsigned long long*>(a.ws) + 32l * ((a.ktot / 64 + 1) & ~1) + wave * 2;

@@ -20,7 +20,7 @@ import collections
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -314,12 +314,52 @@ class Act:
 StForm = collections.namedtuple("StForm", "form tail B h w c hw M heads d inner L tap gn_in xfold")
 
 
+def gather_hint(mode: str, w: int, wo: int) -> Tuple[int, int]:
+    """(same_w, down_w) of the table ``conv_gather_table(h, w, mode)`` with output width ``wo``: the image width the GEMM planner
+    may pass as wd_gemm_args.slab_rows, with which the kernel COMPUTES the source rows of the pad-1 geometry instead of reading the
+    table.  'same' (3x3 / pad 1 / stride 1): the image width; 'down' (stride 2): the OUTPUT width.  Every other table must be read,
+    so it gets no hint - 'down_rb' in particular pads right and bottom only."""
+    return (w if mode == "same" else 0), (wo if mode == "down" else 0)
+
+
+class GatherTable(NamedTuple):
+    """A tap-gather table (wd_src.gather) with what the planners know about it."""
+    dev: torch.Tensor   # int32 [ntaps][ho * wo] on the device
+    ho: int
+    wo: int
+    host: np.ndarray    # the same table on the host (slab_span)
+    same_w: int = 0     # gather_hint; a table not made by conv_gather_table has none
+    down_w: int = 0
+
+
+class Src(NamedTuple):
+    """One A-operand source of a GEMM being planned: the wd_src the kernel reads and the record of its gather table."""
+    raw: N.WdSrc
+    tab: Optional[GatherTable] = None
+
+
+class GemmOp(NamedTuple):
+    """A planned wd_gemm / wd_ff_fused launch: its args (kept alive by the plan, still open to the fusions of a consumer:
+    ``Act.prod``) and what its epilogue makes beside the output."""
+    args: object                           # N.WdGemmArgs | N.WdFfArgs
+    stats: Optional[tuple] = None          # ``Act.stats`` of the output, where the launch sums the GroupNorm statistics
+    ln_pl: Optional[torch.Tensor] = None   # planes of the LayerNorm of the output, where the launch writes them
+
+
+# The kernel form UNetEngine._gemm_form picks for one GEMM: kind "slab-order" | "wdirect" | "whole-k" | "generic", and the
+# wd_gemm_args fields that select it (w_layout, tile, slab_rows).
+GemmForm = collections.namedtuple("GemmForm", "kind fields")
+
+
 class Plan:
     def __init__(self):
         self.cond: List[tuple] = []
         self.step: List[tuple] = []
         self.keep: List[object] = []
         self.out: Optional[torch.Tensor] = None
+        # the zeroed arrival counters the plan's split-K launches take their ranges from (UNetEngine._give_tickets)
+        self.tickets: Optional[torch.Tensor] = None
+        self.ticket_off = 0
         # attention maps (UNetEngine.plan attn_maps): the tapped SpatialTransformers, their buffers fp32 [B, h*w, L] and (h, w),
         # the accumulate form's weight table
         self.map_taps: tuple = ()
@@ -389,11 +429,11 @@ class UNetEngine:
         self.use_wdirect = os.environ.get("WDIFF_GEMM_WDIRECT", "1") != "0"
         # ... with the rows of a 3x3 / pad 1 / stride 1 source copied into an LDS slab once per 64-channel chunk instead of gathered per
         # tap (wd_gemmw_kernel<..., SLAB>).  wd_gemm decides where that form is legal and reads the same variable for its default; an
-        # engine built while it is set passes its value with every launch (wd_gemm_args.dbg 0x10000 / 0x8000).
+        # engine built while it is set passes its value with every launch (wd_gemm_args.dbg WD_GEMMW_SLAB_ON / _OFF).
         self.gemmw_slab = {None: None, "0": False}.get(os.environ.get("WDIFF_GEMMW_SLAB"), True)
         # the batched epilogue of the 64-row tiles (wd_epilogue_rows: 64 x 320, 64 x 80, wd_ff_fused).  wd_gemm / wd_ff_fused decide where
         # that form is legal and read the same variable for their default; an engine built while it is set passes its value with every
-        # such launch (wd_gemm_args.dbg / wd_ff_args.dbg 0x40000 / 0x20000).
+        # such launch (wd_gemm_args.dbg / wd_ff_args.dbg WD_EPI_BATCH_ON / _OFF).
         self.epi_batch = {None: None, "0": False}.get(os.environ.get("WDIFF_EPI_BATCH"), True)
         # Upsample as four 2x2 convolutions of the source map (one per output phase, 4 taps instead of 9; upsample_phase_tables)
         self.use_up_phases = os.environ.get("WDIFF_UPSAMPLE_PHASES", "1") != "0"
@@ -428,10 +468,7 @@ class UNetEngine:
         self.fuse_gn = os.environ.get("WDIFF_FUSE_GN", "1") != "0"         # GroupNorm in the producer's split-K combine launch
         self.fuse_split = os.environ.get("WDIFF_FUSE_SPLIT", "1") != "0"   # resample inputs: planes from the producer's epilogue
         self._plans: Dict[tuple, Plan] = {}
-        self._tabs: Dict[tuple, torch.Tensor] = {}
-        self._tab_np: Dict[int, np.ndarray] = {}
-        self._same_w: Dict[int, int] = {}   # gather table pointer -> image width, for the 3x3 / pad 1 / stride 1 tables
-        self._down_w: Dict[int, int] = {}   # ... -> OUTPUT image width, for the 3x3 / pad 1 / stride 2 tables
+        self._tabs: Dict[tuple, object] = {}   # (h, w, mode) -> GatherTable; (h, w, "up4") -> (GatherTable, row permutation)
         self._ws = None
         self.device = None
 
@@ -627,7 +664,6 @@ class UNetEngine:
             self._w3_meta.clear()
             self._plans.clear()
             self._tabs.clear()
-            self._tab_np.clear()
             self._ws = None
             self._pack = None
         self.device = dev
@@ -669,19 +705,11 @@ class UNetEngine:
                                         wf[1].data_ptr(), stream), "wd_gemm_pack_w")
 
     # ------------------------------------------------------------------------------------------ helpers
-    def _table(self, h, w, mode):
+    def _table(self, h, w, mode) -> GatherTable:
         key = (h, w, mode)
         if key not in self._tabs:
             tab, ho, wo = conv_gather_table(h, w, mode)
-            dt = torch.from_numpy(tab).to(self.device)
-            self._tabs[key] = (dt, ho, wo)
-            self._tab_np[dt.data_ptr()] = tab
-            if mode == "down":
-                self._down_w[dt.data_ptr()] = wo
-            # ('down_rb' records nothing: a width hint becomes wd_gemm_args.slab_rows, with which the kernel COMPUTES the source rows of
-            # the pad-1 geometry instead of reading the table - the right / bottom table must be read)
-            if mode == "same":
-                self._same_w[dt.data_ptr()] = w
+            self._tabs[key] = GatherTable(torch.from_numpy(tab).to(self.device), ho, wo, tab, *gather_hint(mode, w, wo))
         return self._tabs[key]
 
     def _f32(self, P: Plan, *shape):
@@ -701,38 +729,41 @@ class UNetEngine:
             return None, None
         return planes[0].data_ptr() + byte_off, (planes[1].data_ptr() + byte_off if self.npass == 3 else None)
 
-    def _src(self, planes: torch.Tensor, c: int, ntaps: int = 1, gather: Optional[torch.Tensor] = None,
-             hw_src: int = 0, col_off: int = 0) -> N.WdSrc:
+    def _src(self, planes: torch.Tensor, c: int, ntaps: int = 1, gather: Optional[GatherTable] = None,
+             hw_src: int = 0, col_off: int = 0) -> Src:
         s = N.WdSrc()
-        s._tab_np = self._tab_np.get(gather.data_ptr()) if gather is not None else None
-        s._same_w = self._same_w.get(gather.data_ptr(), 0) if gather is not None else 0
-        s._down_w = self._down_w.get(gather.data_ptr(), 0) if gather is not None else 0
-        ld = planes.shape[2]
         s.hi = planes[0].data_ptr() + 2 * col_off
         s.lo = planes[1].data_ptr() + 2 * col_off
-        s.gather = _ptr(gather)
-        s.ld, s.c, s.ntaps, s.hw_src = ld, c, ntaps, hw_src
-        return s
+        s.gather = gather.dev.data_ptr() if gather is not None else None
+        s.ld, s.c, s.ntaps, s.hw_src = planes.shape[2], c, ntaps, hw_src
+        return Src(s, gather)
 
-    def _gemm(self, ops, what, srcs, wname, m, hw_out, bias=None, rowvec=None, rowvec_ld=0, resid=None,
-              resid_ld=0, resid_rows=None, act=N.ACT_NONE, out_f32=None, out_ld=0, out_pl=None, n=None, tile=0,
-              w_row_off=0, want_stats=False, a32=None, ln=None, w_groups=None):
-        """a32 = (Act, norm name, eps, silu): src[0] is that fp32 map, normalised while it is staged (wd_gemm_args.a32*).
-        ln: name of the LayerNorm whose output the epilogue also writes, as new planes ``a._ln_pl``, where wd_gemm takes it
-        (wd_gemm_args.ln_*; ``a._ln_pl`` is None otherwise).  w_groups = (count, stride): weight groups (wd_gemm_args.w_ngroups).
-        What wd_gemm can run is wd_gemm_check's answer; the tests written here are policy."""
+    def _gemm_args(self, srcs: List[Src], m, n, hw_out, a32=None) -> N.WdGemmArgs:
+        """The part of wd_gemm_args every kernel form shares and wd_gemm_check's answer turns on first: the sources, the shape,
+        the passes and the fp32 map src[0] stands for (a32, see ``_gemm``)."""
         a = N.WdGemmArgs()
         for i, s in enumerate(srcs):
-            a.src[i] = s
-        a.nsrc = len(srcs)
-        a.npass = self.npass
+            a.src[i] = s.raw
+        a.nsrc, a.npass = len(srcs), self.npass
+        a.m, a.n, a.ktot, a.hw_out = m, n, sum(s.raw.ntaps * s.raw.c for s in srcs), hw_out
+        if a32 is not None:
+            self._set_a32(a, *a32)
+        return a
+
+    def _gemm(self, ops, what, srcs: List[Src], wname, m, hw_out, bias=None, rowvec=None, rowvec_ld=0, resid=None,
+              resid_ld=0, resid_rows=None, act=N.ACT_NONE, out_f32=None, out_ld=0, out_pl=None, n=None, tile=0,
+              w_row_off=0, want_stats=False, a32=None, ln=None, w_groups=None) -> GemmOp:
+        """a32 = (Act, norm name, eps, silu): src[0] is that fp32 map, normalised while it is staged (wd_gemm_args.a32*).
+        ln: name of the LayerNorm whose output the epilogue also writes, as new planes ``GemmOp.ln_pl``, where wd_gemm takes it
+        (wd_gemm_args.ln_*; None otherwise).  w_groups = (count, stride): weight groups (wd_gemm_args.w_ngroups).
+        What wd_gemm can run is wd_gemm_check's answer; the tests written here are policy."""
         wp = self._w[wname]
         ktot = wp.shape[2]
-        assert ktot == sum(s.ntaps * s.c for s in srcs), (what, ktot, [(s.ntaps, s.c) for s in srcs])
         nrows = wp.shape[1] if n is None else n
+        a = self._gemm_args(srcs, m, nrows, hw_out, a32)
+        assert ktot == a.ktot, (what, ktot, [(s.raw.ntaps, s.raw.c) for s in srcs])
         a.w_hi = wp[0].data_ptr() + 2 * w_row_off * ktot
         a.w_lo = wp[1].data_ptr() + 2 * w_row_off * ktot
-        a.m, a.n, a.ktot, a.hw_out = m, nrows, ktot, hw_out
         a.bias = _ptr(bias)
         a.rowvec, a.rowvec_ld = rowvec, rowvec_ld
         a.resid, a.resid_ld, a.resid_rows = resid, resid_ld, resid_rows
@@ -740,8 +771,6 @@ class UNetEngine:
         a.out_f32, a.out_ld = _ptr(out_f32), out_ld
         if out_pl is not None:
             a.out_hi, a.out_lo, a.out_pl_ld = out_pl[0].data_ptr(), out_pl[1].data_ptr(), out_pl.shape[2]
-        if a32 is not None:
-            self._set_a32(a, *a32)
         if w_groups is not None:
             a.w_ngroups, a.w_group_stride = w_groups
         a.tile = tile
@@ -749,73 +778,101 @@ class UNetEngine:
             self._ws = torch.empty(128 * 128 * 160 * 8, dtype=torch.float32, device=self.device)  # 84 MB split-K scratch
         a.ksplit, a.ws, a.ws_floats = 0, self._ws.data_ptr(), self._ws.numel()
         self._give_tickets(a, m, nrows)
-        # ---- kernel form: the policy below picks a candidate, wd_gemm_check says whether it is legal
-        span = 0
-        if self.use_slab and w_row_off == 0 and (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather)):
-            tabnp = getattr(srcs[0], "_tab_np", None)
-            span = slab_span(tabnp, hw_out, srcs[0].hw_src, m)
-            # the slab kernel runs 128-row panels: only worth it when they fill the chip
-            if span > 192 or ((m + 127) // 128) * max(1, nrows // 160) < 96:
-                span = 0
-        s0 = srcs[0]
-        # fragment-major weights only for whole matrices with the auto tile and no activation, and not beside the experimental kernels
-        frag = not span and not self.use_conv3 and w_row_off == 0 and n is None and act == N.ACT_NONE and tile == 0
-        # the image width of a 3x3 gather table (wd_gemm_args.slab_rows): the OUTPUT width for a stride-2 table
-        width = (getattr(s0, "_down_w", 0) or getattr(s0, "_same_w", 0)) if s0.ntaps == 9 else 0
-        # (the K-cut layers of the 4 x 16 level stay on the LDS-staged kernel: the weights-to-registers kernel is 5 % faster on their
-        # long loops in isolation and 2 % slower inside the step - hence the chip-fill rule)
-        wdirect = (frag and self.use_wdirect and wdirect_fills_chip(m, nrows) and
-                   self._legal(a, w_layout=3, tile=64320, slab_rows=getattr(s0, "_same_w", 0) if s0.ntaps == 9 else 0))
-        # 3x3 layers over 64-position samples (the 4 x 16 level): 64 x 80 tiles with all of K inside the workgroup (wd_gemmq_kernel)
-        # instead of a K cut over workgroups + combine launch, where that grid holds 128 to 512 tiles
-        smallmap = (frag and not wdirect and self.use_smallmap and hw_out == 64 and 128 <= (m // 64) * (nrows // 80) <= 512 and
-                    self._legal(a, w_layout=3, tile=64080, slab_rows=width))
-        assert (a32 is None and w_groups is None) or wdirect, what
-        if wdirect or smallmap:
+        form = self._gemm_form(a, srcs, whole_w=w_row_off == 0 and n is None, w_row_off=w_row_off)
+        assert (a32 is None and w_groups is None) or form.kind == "wdirect", what
+        self._apply_form(a, form, wname, srcs)
+        ln_pl = self._fuse_ln(a, ln) if ln is not None else None
+        stats = self._fuse_stats(a, form) if want_stats else None
+        self._cur_plan.keep.append(a)
+        ops.append((self.lib.wd_gemm, (C.byref(a),), what))
+        return GemmOp(a, stats, ln_pl)
+
+    def _gemm_form(self, a, srcs: List[Src], whole_w: bool, w_row_off: int) -> GemmForm:
+        """The kernel form of the GEMM ``a`` (sources, shape, epilogue and tile filled in; whole_w: it reads the whole weight
+        matrix), the first of the candidates below that applies.  Each candidate is policy - where a form is worth taking; whether
+        wd_gemm can run it is wd_gemm_check's answer (``_legal``).  WDIFF_SLAB / WDIFF_CONV3 (experimental build): the slab-order
+        kernel goes first, and WDIFF_CONV3 keeps every GEMM off the fragment-major forms."""
+        s0, t0 = srcs[0].raw, srcs[0].tab
+        s1 = srcs[1].raw if len(srcs) > 1 else None
+        m, n, hw_out = a.m, a.n, a.hw_out
+        conv = s0.ntaps == 9 and t0 is not None
+        same_w = t0.same_w if conv else 0
+        identity_tail = s1 is None or (s1.ntaps == 1 and not s1.gather)
+        auto = a.act == N.ACT_NONE and a.tile == 0
+        # 1. slab-order weights (w_layout 1): 128-row panels whose source slab stays in LDS - only worth it when they fill the chip
+        if self.use_slab and w_row_off == 0 and identity_tail:
+            span = slab_span(t0.host if t0 is not None else None, hw_out, s0.hw_src, m)
+            if 0 < span <= 192 and ((m + 127) // 128) * max(1, n // 160) >= 96:
+                return GemmForm("slab-order", dict(w_layout=1, slab_rows=span))
+        # fragment-major weights (w_layout 3): only for whole matrices with the auto tile and no activation
+        if whole_w and auto and not self.use_conv3:
+            # 2. 64 x 320 tiles, weights straight to registers.  (The K-cut layers of the 4 x 16 level stay on the LDS-staged kernel:
+            # this one is 5 % faster on their long loops in isolation and 2 % slower inside the step - hence the chip-fill rule)
+            if self.use_wdirect and wdirect_fills_chip(m, n):
+                fields = dict(w_layout=3, tile=64320, slab_rows=same_w)
+                if self._legal(a, apply=False, **fields):
+                    return GemmForm("wdirect", fields)
+            # 3. 3x3 layers over 64-position samples (the 4 x 16 level): 64 x 80 tiles with all of K inside the workgroup
+            # (wd_gemmq_kernel) instead of a K cut over workgroups + combine launch, where that grid holds 128 to 512 tiles.
+            # slab_rows: the image width of the 3x3 table - the OUTPUT width for a stride-2 table
+            if self.use_smallmap and hw_out == 64 and 128 <= (m // 64) * (n // 80) <= 512:
+                fields = dict(w_layout=3, tile=64080, slab_rows=(t0.down_w or t0.same_w) if conv else 0)
+                if self._legal(a, apply=False, **fields):
+                    return GemmForm("whole-k", fields)
+        # 4. the generic kernels, wd_gemm's own choice.  w_layout 2 for a 3x3 same-convolution is a hint: it lets the kernel compute
+        # the source-row table (WDIFF_CONV3=1 also selects the row-shared-taps kernel for it)
+        if same_w and s0.c % 64 == 0 and auto and identity_tail and (s1 is None or s1.c % 64 == 0):
+            return GemmForm("generic", dict(w_layout=2, slab_rows=same_w))
+        return GemmForm("generic", {})
+
+    def _apply_form(self, a, form: GemmForm, wname, srcs: List[Src]):
+        """Sets the form's fields on ``a``, points it at the weight image the form reads (fragment-major / slab order: made on first
+        use) and passes the engine's own WDIFF_GEMMW_SLAB / WDIFF_EPI_BATCH with the forms those switches bear on."""
+        for k, v in form.fields.items():
+            setattr(a, k, v)
+        if form.kind in ("wdirect", "whole-k"):
             wf = self._wfrag(wname)
             a.w_hi, a.w_lo = wf[0].data_ptr(), wf[1].data_ptr()
-            if wdirect and self.gemmw_slab is not None:
-                a.dbg |= 0x10000 if self.gemmw_slab else 0x8000
+            if form.kind == "wdirect" and self.gemmw_slab is not None:
+                a.dbg |= N.GEMMW_SLAB_ON if self.gemmw_slab else N.GEMMW_SLAB_OFF
             if self.epi_batch is not None:
-                a.dbg |= 0x40000 if self.epi_batch else 0x20000
-        elif span:
-            meta = (srcs[0].ntaps, srcs[0].c, srcs[1].c if len(srcs) > 1 else 0)
+                a.dbg |= N.EPI_BATCH_ON if self.epi_batch else N.EPI_BATCH_OFF
+        elif form.kind == "slab-order":
+            meta = (srcs[0].raw.ntaps, srcs[0].raw.c, srcs[1].raw.c if len(srcs) > 1 else 0)
             if wname not in self._w3:
-                self._w3[wname] = slab_order(wp, *meta)
+                self._w3[wname] = slab_order(self._w[wname], *meta)
                 self._w3_meta[wname] = meta
             assert self._w3_meta[wname] == meta, wname
             w3 = self._w3[wname]
             a.w_hi, a.w_lo = w3[0].data_ptr(), w3[1].data_ptr()
-            a.w_layout, a.slab_rows = 1, span
-        else:
-            same_w = getattr(srcs[0], "_same_w", 0)  # (a hint: lets the kernel compute the source-row table; WDIFF_CONV3=1 also
-            #                                           selects the row-shared-taps kernel for it)
-            if (same_w and srcs[0].ntaps == 9 and srcs[0].c % 64 == 0 and act == N.ACT_NONE and tile == 0 and
-                    (len(srcs) == 1 or (srcs[1].ntaps == 1 and not srcs[1].gather and srcs[1].c % 64 == 0))):
-                a.w_layout, a.slab_rows = 2, same_w  # 3x3 same-convolution: the taps of a kernel row share their A tile
-        a._ln_pl = None
-        if ln is not None and self.fuse_ln and not self.use_slab:  # (WDIFF_SLAB=1 runs keep the LayerNorm launches)
-            pl = torch.zeros((2, m, nrows), dtype=torch.bfloat16, device=self.device)
-            if self._legal(a, out_hi=pl[0].data_ptr(), out_lo=pl[1].data_ptr(), out_pl_ld=nrows, ln_gamma=self._w[ln + ".g"].data_ptr(),
+
+    def _fuse_ln(self, a, ln: str) -> Optional[torch.Tensor]:
+        """The LayerNorm ``ln`` of the result in the GEMM's own epilogue, where wd_gemm takes it: the planes it then writes."""
+        if not self.fuse_ln or self.use_slab:  # (WDIFF_SLAB=1 runs keep the LayerNorm launches)
+            return None
+        pl = torch.zeros((2, a.m, a.n), dtype=torch.bfloat16, device=self.device)
+        if not self._legal(a, out_hi=pl[0].data_ptr(), out_lo=pl[1].data_ptr(), out_pl_ld=a.n, ln_gamma=self._w[ln + ".g"].data_ptr(),
                            ln_beta=self._w[ln + ".b"].data_ptr(), ln_eps=1e-5):
-                self._cur_plan.keep.append(pl)
-                a._ln_pl = pl
-        stats = None
-        # (the consumer's GroupNorm has 32 groups; the statistics layout is kept to sample sizes that are a multiple of the
-        # 128-row panel or exactly 64 rows, and off the experimental slab kernel)
-        if want_stats and self.fuse_stats and nrows % 32 == 0 and (hw_out % 128 == 0 or hw_out == 64) and not span:
-            cpg = nrows // 32
-            r = self._resolved(a, stat_part=a.ws, stat_cpg=cpg)  # (a placeholder for the partials: the count depends on the tile)
-            if r is not None:
-                nchunk = max(1, hw_out // (r.tile // 1000))  # (the statistics are kept per row panel of the tile)
-                part = torch.zeros((m // hw_out, nchunk, 32, 2), dtype=torch.float64, device=self.device)
-                self._cur_plan.keep.append(part)
-                a.stat_part, a.stat_cpg = part.data_ptr(), cpg
-                stats = (part, nchunk, cpg)
-        a._stats = stats
-        self._cur_plan.keep.append(a)
-        ops.append((self.lib.wd_gemm, (C.byref(a),), what))
-        return a
+            return None
+        self._cur_plan.keep.append(pl)
+        return pl
+
+    def _fuse_stats(self, a, form: GemmForm) -> Optional[tuple]:
+        """The GroupNorm statistics of the result from the GEMM's epilogue, where wd_gemm takes them: ``Act.stats`` of the output.
+        (The consumer's GroupNorm has 32 groups; the statistics layout is kept to sample sizes that are a multiple of the 128-row
+        panel or exactly 64 rows, and off the experimental slab kernel.)"""
+        m, n, hw_out = a.m, a.n, a.hw_out
+        if not (self.fuse_stats and n % 32 == 0 and (hw_out % 128 == 0 or hw_out == 64) and form.kind != "slab-order"):
+            return None
+        cpg = n // 32
+        r = self._resolved(a, stat_part=a.ws, stat_cpg=cpg)  # (a placeholder for the partials: the count depends on the tile)
+        if r is None:
+            return None
+        nchunk = max(1, hw_out // (r.tile // 1000))  # (the statistics are kept per row panel of the tile)
+        part = torch.zeros((m // hw_out, nchunk, 32, 2), dtype=torch.float64, device=self.device)
+        self._cur_plan.keep.append(part)
+        a.stat_part, a.stat_cpg = part.data_ptr(), cpg
+        return part, nchunk, cpg
 
     def _resolved(self, a, **fields) -> Optional[N.WdGemmArgs]:
         """``a`` with ``fields`` set (on a copy) as wd_gemm would launch it, or None where wd_gemm refuses it (wd_gemm_check)."""
@@ -844,15 +901,10 @@ class UNetEngine:
     def _wdirect_ok(self, srcs, m, n, hw_out, a32=None, **fields) -> bool:
         """Would wd_gemm run a GEMM over ``srcs`` into m x n as the 64 x 320 weights-to-registers kernel (with a32 / ``fields``)?
         Asked before the GEMM is planned; weights and output are placeholders (wd_gemm_check reads no memory)."""
-        a = N.WdGemmArgs()
-        for i, s in enumerate(srcs):
-            a.src[i] = s
-        a.nsrc, a.npass, a.m, a.n, a.ktot, a.hw_out = len(srcs), self.npass, m, n, sum(s.ntaps * s.c for s in srcs), hw_out
+        a = self._gemm_args(srcs, m, n, hw_out, a32)
         a.w_layout, a.tile = 3, 64320
         a.w_hi = a.w_lo = a.out_f32 = 16
         a.out_ld = n  # (a dense m x n output: wd_gemm_check refuses a pitch narrower than the width)
-        if a32 is not None:
-            self._set_a32(a, *a32)
         return self._legal(a, apply=False, **fields)
 
     def _give_tickets(self, a, m, n):
@@ -862,13 +914,11 @@ class UNetEngine:
         if ntick > 2048:
             return
         P = self._cur_plan
-        tk = getattr(P, "_tickets", None)
-        if tk is None or P._ticket_off + ntick > tk.numel():
-            tk = torch.zeros(1 << 16, dtype=torch.int32, device=self.device)
-            P.keep.append(tk)
-            P._tickets, P._ticket_off = tk, 0
-        a.tickets, a.ntickets = tk.data_ptr() + 4 * P._ticket_off, ntick
-        P._ticket_off += ntick
+        if P.tickets is None or P.ticket_off + ntick > P.tickets.numel():
+            P.tickets, P.ticket_off = torch.zeros(1 << 16, dtype=torch.int32, device=self.device), 0
+            P.keep.append(P.tickets)
+        a.tickets, a.ntickets = P.tickets.data_ptr() + 4 * P.ticket_off, ntick
+        P.ticket_off += ntick
 
     def _gn(self, P, ops, what, srcs: List[Act], gname, eps, silu, want_raw=False, dropout=None):
         """GroupNorm over the channel concat of ``srcs`` -> planes [M, sum c] (+ raw planes).  dropout: the wd_dropout of a training
@@ -967,14 +1017,12 @@ class UNetEngine:
         self._gn_stats(P, ops, what, s)
         return self._wdirect_ok([self._src32(s, taps, gather, hw)], M, ncols, hw, a32=(s, what, 0.0, False))
 
-    def _src32(self, x: Act, ntaps=1, gather=None, hw_src=0) -> N.WdSrc:
+    def _src32(self, x: Act, ntaps=1, gather: Optional[GatherTable] = None, hw_src=0) -> Src:
         """src[0] of a GEMM that reads the fp32 map itself (a32): channel count, taps and gather table only."""
         s = N.WdSrc()
-        s._tab_np = self._tab_np.get(gather.data_ptr()) if gather is not None else None
-        s._same_w = self._same_w.get(gather.data_ptr(), 0) if gather is not None else 0
-        s.hi, s.lo, s.gather = None, None, _ptr(gather)
+        s.hi, s.lo, s.gather = None, None, gather.dev.data_ptr() if gather is not None else None
         s.ld, s.c, s.ntaps, s.hw_src = x.c, x.c, ntaps, hw_src
-        return s
+        return Src(s, gather)
 
     def _gn_in_combine(self, s: Act, raw, gam, bet, eps, silu, cpg, pl, coff) -> bool:
         """Let the GEMM that produced ``s`` apply this GroupNorm as it combines its K slices (or in its own epilogue where it holds
@@ -1004,7 +1052,7 @@ class UNetEngine:
         hw, M = h * w, B * h * w
         cin, cout = mod.cin, mod.cout
         assert cin == sum(s.c for s in srcs)
-        tab, _, _ = self._table(h, w, "same")
+        tab = self._table(h, w, "same")
         need_raw = cin != cout
         h1 = self._f32(P, M, cout)
         if self._gn_in_consumer(P, ops, name + ".gn1", srcs, need_raw, M, hw, cout, taps=9, gather=tab):
@@ -1016,7 +1064,7 @@ class UNetEngine:
         g1 = self._gemm(ops, name + ".conv1", [s1], name + ".c1.w", M, hw,
                         bias=self._w[name + ".c1.b"], rowvec=self._film.data_ptr() + 4 * self.film_off[name],
                         rowvec_ld=self.film_total, out_f32=h1, out_ld=cout, want_stats=True, a32=in1)
-        h1a = Act(h1, cout, h, w, g1._stats, prod=g1)
+        h1a = Act(h1, cout, h, w, g1.stats, prod=g1.args)
         if self._gn_in_consumer(P, ops, name + ".gn2", [h1a], False, M, hw, cout, taps=9, gather=tab):
             s2, in2 = self._src32(h1a, 9, tab, hw), (h1a, name + ".gn2", 1e-5, True)
         else:
@@ -1031,7 +1079,7 @@ class UNetEngine:
             g2 = self._gemm(ops, name + ".conv2", [s2], name + ".c2.w", M, hw,
                             bias=self._w[name + ".c2.b"], resid=srcs[0].t.data_ptr(), resid_ld=cout, out_f32=out,
                             out_ld=cout, want_stats=True, a32=in2)
-        return Act(out, cout, h, w, g2._stats, prod=g2)
+        return Act(out, cout, h, w, g2.stats, prod=g2.args)
 
     def _up_phases_ok(self, mod) -> bool:
         """Is the phase form of an Upsample switched on (the 64 x 320 weights-to-registers kernel with weight groups; whether it
@@ -1054,7 +1102,8 @@ class UNetEngine:
         ops = P.step
         B = self._B
         assert x.perm is None, name
-        tab, ho, wo = self._table(x.h, x.w, mode)
+        tab = self._table(x.h, x.w, mode)
+        ho, wo = tab.ho, tab.wo
         pl = self._planes(P, B * x.h * x.w, x.c)
         pr = x.prod
         if (pr is not None and self.fuse_split and not pr.out_hi and pr.out_f32 == x.t.data_ptr() and
@@ -1074,9 +1123,7 @@ class UNetEngine:
             key = (x.h, x.w, "up4")
             if key not in self._tabs:
                 t4, pm = upsample_phase_tables(x.h, x.w)
-                dt, dp = torch.from_numpy(t4).to(self.device), torch.from_numpy(pm).to(self.device)
-                self._tabs[key] = (dt, dp)
-                self._tab_np[dt.data_ptr()] = t4
+                self._tabs[key] = (GatherTable(torch.from_numpy(t4).to(self.device), ho, wo, t4), torch.from_numpy(pm).to(self.device))
             tab4, perm = self._tabs[key]
             src4 = self._src(pl, x.c, 4, tab4, hw)
             groups = (4, mod.cout * 4 * x.c)
@@ -1092,10 +1139,10 @@ class UNetEngine:
                 self._pack = None
             gg = self._gemm(ops, name + ".conv (4 phases)", [src4], name + ".wph0", B * 4 * hw, 4 * hw,
                             bias=self._w[name + ".b"], out_f32=out, out_ld=mod.cout, want_stats=True, w_groups=groups)
-            return Act(out, mod.cout, ho, wo, gg._stats, prod=None, perm=perm)
+            return Act(out, mod.cout, ho, wo, gg.stats, prod=None, perm=perm)
         gg = self._gemm(ops, name + ".conv", [self._src(pl, x.c, 9, tab, x.h * x.w)], name + ".w", B * ho * wo, ho * wo,
                         bias=self._w[name + ".b"], out_f32=out, out_ld=mod.cout, want_stats=True, tile=tile)
-        return Act(out, mod.cout, ho, wo, gg._stats, prod=gg)
+        return Act(out, mod.cout, ho, wo, gg.stats, prod=gg.args)
 
     def _attention(self, ops, what, q, ldq, k, ldk, v, ldv, heads, nq, nk, d, scale, out_pl, out_f32=None,
                    out_rows=None, out_row0=0):
@@ -1211,7 +1258,7 @@ class UNetEngine:
             src, a32 = self._src(g, f.c), None
         g_in = self._gemm(P.step, name + ".proj_in", [src], name + ".pi.w", f.M, f.hw, bias=self._w[name + ".pi.b"], out_f32=tok,
                           out_ld=f.inner, a32=a32, ln=f"{name}.tb0.norm1" if self.variant == "phosc" else None)
-        return tok, g_in._ln_pl
+        return tok, g_in.ln_pl
 
     def _st_attention(self, P, f: StForm, p, tok, n1, tok2pl):
         """attn1 and attn2 of block ``p`` as ``f.form`` plans them -> (tok2, norm3 planes or None, what a maps tap reads).
@@ -1284,7 +1331,7 @@ class UNetEngine:
         tok1 = self._f32(P, M, inner)
         g = self._gemm(ops, p + ".a1.out", [self._src(o1, inner)], p + ".a1.o.w", M, hw, bias=self._w[p + ".a1.o.b"],
                        resid=tok.data_ptr(), resid_ld=inner, out_f32=tok1, out_ld=inner, ln=None if f.xfold else p + ".norm2")
-        return tok1, g._ln_pl
+        return tok1, g.ln_pl
 
     def _st_attn_plain(self, P, f: StForm, p, tag, x_in, n_in, next_ln=None, pack=False):
         """x_out = x_in + to_out(attention(to_q(n_in), K, V)) over the context's keys as wd_gemm -> wd_attention -> wd_gemm.  n_in:
@@ -1313,7 +1360,7 @@ class UNetEngine:
         x_out = self._f32(P, M, inner)
         g = self._gemm(ops, f"{p}.{tag}.out", [self._src(o, inner)], f"{p}.{tag}.o.w", M, hw, bias=self._w[f"{p}.{tag}.o.b"],
                        resid=x_in.data_ptr(), resid_ld=inner, out_f32=x_out, out_ld=inner, ln=f"{p}.{next_ln}" if next_ln else None)
-        return x_out, g._ln_pl
+        return x_out, g.ln_pl
 
     def _st_maps(self, P, f: StForm, p, x_in, fa, fb):
         """The attn2 softmax of block ``p`` summed over heads into this tap's map buffer.  x_in is what the attention launch just
@@ -1363,7 +1410,7 @@ class UNetEngine:
             self._st_ff(P, f, p, ffi, n3, tok2, None, xpl)
             g = self._gemm(ops, name + ".proj_out", [self._src(xpl, f.inner)], name + ".po.w", M, hw, bias=self._w[name + ".po.b"],
                            resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True)
-        return Act(out, c, f.h, f.w, g._stats, prod=g)
+        return Act(out, c, f.h, f.w, g.stats, prod=g.args)
 
     def _transformer_fused(self, P, f: StForm, name, mod: SpatialTransformerParams, x: Act) -> Act:
         """The SpatialTransformer (unet.py:398-412, one base-model block) as ONE wd_ff_fused launch with the transformer front
@@ -1387,7 +1434,7 @@ class UNetEngine:
                      heads=heads, L=L, tok2=_ptr(tok2))
         ffi = mod.transformer_blocks[0].ff.net[2].in_features
         fa = self._ff_fused(P.step, p, None, tok2, M, c, ffi, out, None, proj=(name, x.t, hw), front=front)
-        return Act(out, c, x.h, x.w, fa._stats, prod=fa)
+        return Act(out, c, x.h, x.w, fa.stats, prod=fa.args)
 
     def _fold_fused(self, name) -> bool:
         """Does wd_ff_fused run the proj_out tail of SpatialTransformer ``name`` folded (wd_ff_args.w32_*)?"""
@@ -1438,12 +1485,11 @@ class UNetEngine:
                 a.stat_part, a.stat_cpg, a.hw_out = part.data_ptr(), inner // 32, hw
                 stats = (part, nchunk, inner // 32)
         if self.epi_batch is not None:
-            a.dbg |= 0x40000 if self.epi_batch else 0x20000
+            a.dbg |= N.EPI_BATCH_ON if self.epi_batch else N.EPI_BATCH_OFF
         self._cur_plan.keep.append(a)
         what = ".ff (fused)" if proj is None else ".ff + proj_out (fused)" if front is None else ": gn + proj_in + a1 + a2 + ff + proj_out (fused)"
         ops.append((self.lib.wd_ff_fused, (C.byref(a),), p + what))
-        a._stats = stats
-        return a
+        return GemmOp(a, stats)
 
     # ------------------------------------------------------------------------------------------ plan
     @staticmethod
@@ -1516,7 +1562,7 @@ class UNetEngine:
         h0 = self._f32(P, B * H * W, cout)
         g0 = self._gemm(ops, what, [self._src(xin, self.kpad_in)], w + ".w", B * H * W, H * W, bias=self._w[w + ".b"], out_f32=h0,
                         out_ld=cout, want_stats=want_stats, tile=tile)
-        return Act(h0, cout, H, W, g0._stats), xin
+        return Act(h0, cout, H, W, g0.stats), xin
 
     def _map_taps(self, L: int) -> tuple:
         """The three SpatialTransformers whose attn2 softmax the reference returns with --attentionMaps 1 (unet.py:1645-1832: the
@@ -1584,7 +1630,7 @@ class UNetEngine:
         ``nchw``: the tensor a wd_tokens_to_nchw launch then writes them to.  Returns the planes and the token rows."""
         B, hw = self._B, x.h * x.w
         g, _ = self._gn(P, ops, "out.gn", [x], "out.gn", eps, True)
-        tab, _, _ = self._table(x.h, x.w, "same")
+        tab = self._table(x.h, x.w, "same")
         oc = self._w["out.w"].shape[1]
         otok = self._f32(P, B * hw, oc)
         self._gemm(ops, what, [self._src(g, x.c, 9, tab, hw)], "out.w", B * hw, hw, bias=self._w["out.b"], out_f32=otok, out_ld=oc)

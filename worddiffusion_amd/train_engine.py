@@ -28,7 +28,7 @@ import torch
 from . import _native as N
 from . import dropout as DO
 from .backward import conv_bwd_table
-from .engine import Act, Plan, UNetEngine, _ptr, check_writer_keep
+from .engine import Act, GatherTable, Plan, UNetEngine, _ptr, check_writer_keep
 from .layers import DownsampleParams, ResBlockParams, SpatialTransformerParams, UpsampleParams
 
 
@@ -92,7 +92,7 @@ class BwdSeg:
     channels read through ``ntaps`` taps of the forward table ``ftab`` (None: row for row) over ``hw_src`` source positions per
     sample; ``wgrad`` [n, c * ntaps] in OIHW order or None (``wgrad_packed`` = (packed [n, ld_k], OIHW destination, c_in) for the
     im2col input convolution); ``wb`` names the data-gradient weight of the ``dx`` destinations (Dx), whose rows are ``dx_rows``
-    output positions (``dx_hw`` per sample) through the inverse table ``btab``."""
+    output positions (``dx_hw`` per sample) through the inverse table ``btab`` (a GatherTable; ``ftab`` is the device tensor wd_dw reads)."""
     __slots__ = ("planes", "c", "ntaps", "hw_src", "ftab", "btab", "wb", "wgrad", "wgrad_packed", "dx", "dx_rows", "dx_hw")
 
     def __init__(self, planes, c, ntaps, hw_src, ftab=None, btab=None, wb=None, wgrad=None, wgrad_packed=None, dx=(), dx_rows=0,
@@ -145,7 +145,7 @@ class TrainEngine(UNetEngine):
         self._tplans: Dict[tuple, TrainPlan] = {}
         self._grad: Dict[int, torch.Tensor] = {}     # id(param) -> gradient buffer (possibly a view into a group)
         self._params: Dict[int, torch.nn.Parameter] = {}
-        self._btabs: Dict[tuple, torch.Tensor] = {}
+        self._btabs: Dict[tuple, GatherTable] = {}
         self._scr: Dict[str, torch.Tensor] = {}
         self._arena = None
         self._arena_used = 0
@@ -333,13 +333,11 @@ class TrainEngine(UNetEngine):
             self._scr[key] = torch.zeros(numel, dtype=dtype, device=self.device)
         return self._scr[key]
 
-    def _btable(self, h, w, mode):
+    def _btable(self, h, w, mode) -> GatherTable:
         key = (h, w, mode)
         if key not in self._btabs:
-            tab, _, _ = conv_bwd_table(h, w, mode)
-            dt = torch.from_numpy(tab).to(self.device)
-            self._btabs[key] = dt
-            self._tab_np[dt.data_ptr()] = tab
+            tab, ho, wo = conv_bwd_table(h, w, mode)
+            self._btabs[key] = GatherTable(torch.from_numpy(tab).to(self.device), ho, wo, tab)  # (an inverse table: no width hint)
         return self._btabs[key]
 
     # ------------------------------------------------------------------------------------------ backward emitters
@@ -626,7 +624,7 @@ class TrainEngine(UNetEngine):
         h, w = srcs[0].h, srcs[0].w
         hw, M = h * w, B * h * w
         cin, cout = mod.cin, mod.cout
-        tab, _, _ = self._table(h, w, "same")
+        tab = self._table(h, w, "same")
         need_raw = cin != cout
         # nn.Dropout(p) of out_layers (unet.py:616-623): on the planes conv2 reads, recomputed by the backward of the second norm
         p_drop = DO.check_p(mod.out_layers[2].p)
@@ -649,7 +647,7 @@ class TrainEngine(UNetEngine):
         g1 = self._gemm(ops, name + ".conv1", [self._src(a1, cin, 9, tab, hw)], name + ".c1.w", M, hw,
                         bias=self._w[name + ".c1.b"], rowvec=self._film.data_ptr() + 4 * self.film_off[name],
                         rowvec_ld=self.film_total, out_f32=h1t, out_ld=cout, want_stats=True)
-        h1 = TAct(h1t, cout, h, w, g1._stats)
+        h1 = TAct(h1t, cout, h, w, g1.stats)
         a2, _ = self._gn(P, ops, name + ".gn2", [h1], name + ".gn2", 1e-5, True, dropout=drop)
         outt = self._f32(P, M, cout)
         if need_raw:
@@ -660,7 +658,7 @@ class TrainEngine(UNetEngine):
             g2 = self._gemm(ops, name + ".conv2", [self._src(a2, cout, 9, tab, hw)], name + ".c2.w", M, hw,
                             bias=self._w[name + ".c2.b"], resid=srcs[0].t.data_ptr(), resid_ld=cout, out_f32=outt,
                             out_ld=cout, want_stats=True)
-        out = TAct(outt, cout, h, w, g2._stats)
+        out = TAct(outt, cout, h, w, g2.stats)
         self._bs.gn_names[id(mod.in_layers[0])] = name + ".gn1"
         self._bs.gn_names[id(mod.out_layers[0])] = name + ".gn2"
 
@@ -670,7 +668,7 @@ class TrainEngine(UNetEngine):
             dO = out.g
             btab = self._btable(h, w, "same")
             da2 = self._f32(P, M, cout)
-            segs = [conv3_seg(a2, cout, tab, btab, hw, "B:" + name + ".c2.w", self._pgrad(mod.out_layers[3].weight).view(cout, -1),
+            segs = [conv3_seg(a2, cout, tab.dev, btab, hw, "B:" + name + ".c2.w", self._pgrad(mod.out_layers[3].weight).view(cout, -1),
                               Dx(da2, cout, 0, 0, cout), M, hw)]
             biases = [self._pgrad(mod.out_layers[3].bias)]
             if need_raw:
@@ -688,7 +686,7 @@ class TrainEngine(UNetEngine):
             self._gn_bwd(P, name + ".gn2", [h1], mod.out_layers[0], 1e-5, True, da2, dropout=drop)
             da1 = self._f32(P, M, cin)
             self._bwd_linear(P, name + ".conv1", h1.g, M, cout, hw,
-                             [conv3_seg(a1, cin, tab, btab, hw, "B:" + name + ".c1.w",
+                             [conv3_seg(a1, cin, tab.dev, btab, hw, "B:" + name + ".c1.w",
                                         self._pgrad(mod.in_layers[2].weight).view(cout, -1), Dx(da1, cin, 0, 0, cin), M, hw)],
                              bias=[self._pgrad(mod.in_layers[2].bias)], film_off=self.film_off[name])
             self._gn_bwd(P, name + ".gn1", srcs, mod.in_layers[0], 1e-5, True, da1)
@@ -711,14 +709,15 @@ class TrainEngine(UNetEngine):
         9-tap form, whose output is in raster order.)"""
         ops = P.step
         B = self._B
-        tab, ho, wo = self._table(x.h, x.w, mode)
+        tab = self._table(x.h, x.w, mode)
+        ho, wo = tab.ho, tab.wo
         hw_in, M_in = x.h * x.w, B * x.h * x.w
         pl = self._planes(P, M_in, x.c)
         ops.append((self.lib.wd_split, (x.t.data_ptr(), x.c, M_in, x.c, 0, *self._hilo(pl), x.c), name + ":split"))
         outt = self._f32(P, B * ho * wo, mod.cout)
         gg = self._gemm(ops, name + ".conv", [self._src(pl, x.c, 9, tab, hw_in)], name + ".w", B * ho * wo, ho * wo,
                         bias=self._w[name + ".b"], out_f32=outt, out_ld=mod.cout, want_stats=True)
-        out = TAct(outt, mod.cout, ho, wo, gg._stats)
+        out = TAct(outt, mod.cout, ho, wo, gg.stats)
         conv = mod.op if mode == "down" else mod.conv
 
         def bwd():
@@ -734,7 +733,7 @@ class TrainEngine(UNetEngine):
                 du = self._f32(P, M_out, x.c)
                 dx, dx_rows, dx_hw = Dx(du, x.c, 0, 0, x.c), M_out, hw_out
             self._bwd_linear(P, name + ".conv", out.g, M_out, mod.cout, hw_out,
-                             [conv3_seg(pl, x.c, tab, btab, hw_in, "B:" + name + ".w", self._pgrad(conv.weight).view(mod.cout, -1),
+                             [conv3_seg(pl, x.c, tab.dev, btab, hw_in, "B:" + name + ".w", self._pgrad(conv.weight).view(mod.cout, -1),
                                         dx, dx_rows, dx_hw)],
                              bias=[self._pgrad(conv.bias)])
             if mode == "up":
@@ -810,7 +809,7 @@ class TrainEngine(UNetEngine):
         gg = self._gemm(ops, name + ".proj_out", [self._src(blocks[-1].xpl, inner)], name + ".po.w", M, hw,
                         bias=self._w[name + ".po.b"], resid=x.t.data_ptr(), resid_ld=c, out_f32=outt, out_ld=c,
                         want_stats=True)
-        out = TAct(outt, c, h, w, gg._stats)
+        out = TAct(outt, c, h, w, gg.stats)
 
         st = _STRec(name, mod, x, out, gpl, M, hw, inner, blocks)
 
@@ -1040,14 +1039,14 @@ class TrainEngine(UNetEngine):
         """Opens ``P.bwd``: d(out) (``P.dout``, NCHW) into token rows, the output convolution's backward, out.gn's backward."""
         m, B = self.model, self._B
         oc, Mo, hwo = m.out_channels, B * last.h * last.w, last.h * last.w
-        tab, _, _ = self._table(last.h, last.w, "same")
+        tab = self._table(last.h, last.w, "same")
         P.dout = torch.zeros((B, oc, last.h, last.w), dtype=torch.float32, device=self.device)
         dtok = torch.zeros((Mo, 32), dtype=torch.float32, device=self.device)  # columns >= oc stay zero
         P.keep.append(dtok)
         P.bwd.append((self.lib.wd_nchw_to_tokens, (P.dout.data_ptr(), B, oc, hwo, dtok.data_ptr(), 32), "d(out):tokens"))
         dg = self._f32(P, Mo, last.c)
         self._bwd_linear(P, "out.conv", dtok, Mo, oc, hwo,
-                         [conv3_seg(gpl, last.c, tab, self._btable(last.h, last.w, "same"), hwo, "B:out.w",
+                         [conv3_seg(gpl, last.c, tab.dev, self._btable(last.h, last.w, "same"), hwo, "B:out.w",
                                     self._pgrad(m.out[2].weight).view(oc, -1), Dx(dg, last.c, 0, 0, last.c), Mo, hwo)],
                          bias=[self._pgrad(m.out[2].bias)], npad=32)
         self._gn_bwd(P, "out.gn", [last], m.out[0], 1e-5, True, dg)

@@ -430,13 +430,13 @@ class VAEDecoderEngine(UNetEngine):
         ops = P.step
         B, h, w = self._B, x.h, x.w
         hw, M = h * w, B * h * w
-        tab, _, _ = self._table(h, w, "same")
+        tab = self._table(h, w, "same")
         need_raw = r.cin != r.cout
         a1, raw = self._gn(P, ops, name + ".gn1", [x], name + ".gn1", 1e-6, True, want_raw=need_raw)
         h1 = self._f32(P, M, r.cout)
         g1 = self._gemm(ops, name + ".conv1", [self._src(a1, r.cin, 9, tab, hw)], name + ".c1.w", M, hw,
                         bias=self._w[name + ".c1.b"], out_f32=h1, out_ld=r.cout, want_stats=True, tile=self.TILE)
-        a2, _ = self._gn(P, ops, name + ".gn2", [Act(h1, r.cout, h, w, g1._stats)], name + ".gn2", 1e-6, True)
+        a2, _ = self._gn(P, ops, name + ".gn2", [Act(h1, r.cout, h, w, g1.stats)], name + ".gn2", 1e-6, True)
         out = self._f32(P, M, r.cout)
         if need_raw:
             g2 = self._gemm(ops, name + ".conv2+shortcut", [self._src(a2, r.cout, 9, tab, hw), self._src(raw, r.cin)],
@@ -446,7 +446,7 @@ class VAEDecoderEngine(UNetEngine):
             g2 = self._gemm(ops, name + ".conv2", [self._src(a2, r.cout, 9, tab, hw)], name + ".c2.w", M, hw,
                             bias=self._w[name + ".c2.b"], resid=x.t.data_ptr(), resid_ld=r.cout, out_f32=out,
                             out_ld=r.cout, want_stats=True, tile=self.TILE)
-        return Act(out, r.cout, h, w, g2._stats)
+        return Act(out, r.cout, h, w, g2.stats)
 
     def _vae_attention(self, P: Plan, x: Act) -> Act:
         ops = P.step
@@ -462,7 +462,7 @@ class VAEDecoderEngine(UNetEngine):
         out = self._f32(P, M, c)
         gg = self._gemm(ops, "mid.attn.to_out+residual", [self._src(o, c)], "mid.at.o.w", M, hw, bias=self._w["mid.at.o.b"],
                         resid=x.t.data_ptr(), resid_ld=c, out_f32=out, out_ld=c, want_stats=True, tile=self.TILE)
-        return Act(out, c, h, w, gg._stats)
+        return Act(out, c, h, w, gg.stats)
 
     def plan_decode(self, B: int, H: int, W: int) -> Plan:
         key = ("vae", B, H, W, self.npass)
