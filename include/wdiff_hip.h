@@ -720,6 +720,29 @@ int wd_adamw_multi_scaled(const void* table, int ntensor, int64_t total_chunks, 
 int wd_grad_sqnorm_multi(const void* table, int ntensor, int64_t total_chunks, double* partial, float max_norm, float* ctl,
                          void* stream);
 
+/* Row-wise AdamW over a few rows of one embedding table (fitting new writers: DESIGN.md "Fitting new writers").  The row list is
+ * a HOST array of nrows distinct ids in [0, vocab), nrows in [1, WD_ROWS_MAX]; it is handed to the kernels by value, so nothing on
+ * the device has to outlive the call.  Both entry points return WD_EINVAL, with nothing launched, for: nrows outside
+ * [1, WD_ROWS_MAX], a row outside [0, vocab), duplicate rows, c % 4 != 0 (wd_adamw_rows), a NULL required pointer, a table,
+ * compact buffer or anchor that is not 16-byte aligned, ld / ema_ld that is not a multiple of 4 floats or < c.
+ *
+ * wd_row_slots: slots[b] = j where rows[j] == ids[b], else -1 (ids int64 [n], any value; slots int64 [n]).  slots is the `ids`
+ * argument of wd_embedding_bwd with vocab = nrows, which gives rows with id -1 no gradient: the gradient of the listed rows lands
+ * in a compact fp32 [nrows][c] buffer, in the summation order the full table uses.
+ *
+ * wd_adamw_rows: one launch updates table[rows[j]][0:c] (row pitch ld floats) for every j.  grad, m, v and the optional anchor
+ * are compact [nrows][c]; ema_table (NULL allowed) is a second table of vocab rows, pitch ema_ld, updated at the same rows under
+ * ema_mode 0 / 1 / 2 as wd_adamw_multi does; gscale (NULL allowed) is the device scalar of wd_adamw_multi_scaled.  With
+ * anchor == NULL the arithmetic is wd_adamw_multi's, in its fp32 op order.  With an anchor the decoupled decay pulls towards it:
+ *   p = p - fp32(lr * weight_decay) * (p - a)
+ * replaces p = p * fp32(1 - lr * weight_decay); every operation is rounded on its own and no product is contracted.  No row that
+ * is not listed is read or written, in either table; every (row, column) cell has one writer. */
+#define WD_ROWS_MAX 64
+int wd_row_slots(const int64_t* ids, int n, const int* rows, int nrows, int vocab, int64_t* slots, void* stream);
+int wd_adamw_rows(float* table, int ld, int c, const int* rows, int nrows, int vocab, const float* grad, float* m, float* v,
+                  const float* anchor, float* ema_table, int ema_ld, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int64_t step, int ema_mode, double ema_beta, const float* gscale, void* stream);
+
 /* dst[i] = scale * (overwrite ? src[i] : dst[i] + src[i]) over n fp32 elements, each operation rounded on its own.  With
  * overwrite != 0 dst is never read (it may hold anything, NaN included).  16-byte accesses where dst and src reach a 16-byte
  * boundary at the same element, scalar accesses for the ragged ends (or throughout).  dst and src must not overlap. */

@@ -880,6 +880,21 @@ __global__ void embedding_bwd_kernel(const void* __restrict__ ids, int i64, int 
     }
 }
 
+// slots[b] = j where rows[j] == ids[b], else -1: the ids of a compact wd_embedding_bwd (the row list travels in the arguments)
+struct slot_rows {
+    int row[WD_ROWS_MAX];
+};
+__global__ void row_slots_kernel(const int64_t* __restrict__ ids, int n, const slot_rows rows, int nrows,
+                                 int64_t* __restrict__ slots) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const int64_t id = ids[b];
+    int64_t slot = -1;
+    for (int j = 0; j < nrows; ++j)
+        if ((int64_t)rows.row[j] == id) slot = j;
+    slots[b] = slot;
+}
+
 // dst[i] += src[i]
 __global__ void add_kernel(float* __restrict__ dst, const float* __restrict__ src, long n4, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -1461,6 +1476,21 @@ extern "C" int wd_embedding_bwd(const void* ids, int ids_are_i64, int rows, cons
     WdLaunchScope scope(WD_CLS_OTHER, st);
     hipLaunchKernelGGL(embedding_bwd_kernel, dim3(grid_for((long)vocab * c)), dim3(256), 0, st, ids, ids_are_i64, rows, d, ld,
                        vocab, c, dtable, accumulate);
+    return wd_check_launch();
+}
+extern "C" int wd_row_slots(const int64_t* ids, int n, const int* rows, int nrows, int vocab, int64_t* slots, void* stream) {
+    if (!ids || !rows || !slots || n <= 0 || nrows < 1 || nrows > WD_ROWS_MAX || vocab < 1) return WD_EINVAL;
+    slot_rows rl;
+    for (int j = 0; j < nrows; ++j) {
+        if (rows[j] < 0 || rows[j] >= vocab) return WD_EINVAL;
+        for (int k = 0; k < j; ++k)
+            if (rows[k] == rows[j]) return WD_EINVAL;
+        rl.row[j] = rows[j];
+    }
+    for (int j = nrows; j < WD_ROWS_MAX; ++j) rl.row[j] = -1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(row_slots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ids, n, rl, nrows, slots);
     return wd_check_launch();
 }
 

@@ -327,6 +327,64 @@ __global__ __launch_bounds__(256) void wmse_stage2(const double* __restrict__ in
     if (threadIdx.x == 0) *loss = (float)(total / (double)batch);
 }
 
+// ---- row-wise AdamW over a few rows of one embedding table (wd_adamw_rows; specification in include/wdiff_hip.h) ---------------
+// The row list travels in the kernel arguments.  wd_adamw_multi's op order per element; with an anchor the decay step is
+// p - lrwd * (p - a).  One thread per float4 of one listed row: blockIdx.y is the slot.
+struct row_list {
+    int row[WD_ROWS_MAX];
+};
+__device__ __forceinline__ float adamw_row_elem(float p, float g, float& m, float& v, bool anchored, float a, float gs, bool scaled,
+                                                float decay, float lrwd, float omb1, float b2, float omb2, float step_size,
+                                                float bc2_sqrt, float eps) {
+    if (scaled) g = g * gs;
+    if (anchored) p = p - lrwd * (p - a);
+    else p = p * decay;
+    m = m + omb1 * (g - m);
+    v = v * b2;
+    v = v + (omb2 * g) * g;
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    return p + (-step_size * m) / denom;
+}
+__global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ table, int ld, int c4, const row_list rows,
+                                                         const float* __restrict__ grad, float* __restrict__ m,
+                                                         float* __restrict__ v, const float* __restrict__ anchor,
+                                                         float* __restrict__ ema_table, int ema_ld, float decay, float lrwd,
+                                                         float omb1, float b2, float omb2, float step_size, float bc2_sqrt,
+                                                         float eps, int ema_mode, float ema_b, float ema_omb,
+                                                         const float* __restrict__ gscale) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= c4) return;
+    const int64_t row = rows.row[j];
+    const int64_t ci = (int64_t)j * c4 + i;  // float4 index into the compact buffers
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(table + row * ld) + i;
+    const float gs = gscale ? *gscale : 1.0f;
+    const bool scaled = gscale != nullptr, anchored = anchor != nullptr;
+    float4 p = *p4, mm = reinterpret_cast<float4*>(m)[ci], vv = reinterpret_cast<float4*>(v)[ci];
+    const float4 g = reinterpret_cast<const float4*>(grad)[ci];
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (anchored) a = reinterpret_cast<const float4*>(anchor)[ci];
+    p.x = adamw_row_elem(p.x, g.x, mm.x, vv.x, anchored, a.x, gs, scaled, decay, lrwd, omb1, b2, omb2, step_size, bc2_sqrt, eps);
+    p.y = adamw_row_elem(p.y, g.y, mm.y, vv.y, anchored, a.y, gs, scaled, decay, lrwd, omb1, b2, omb2, step_size, bc2_sqrt, eps);
+    p.z = adamw_row_elem(p.z, g.z, mm.z, vv.z, anchored, a.z, gs, scaled, decay, lrwd, omb1, b2, omb2, step_size, bc2_sqrt, eps);
+    p.w = adamw_row_elem(p.w, g.w, mm.w, vv.w, anchored, a.w, gs, scaled, decay, lrwd, omb1, b2, omb2, step_size, bc2_sqrt, eps);
+    *p4 = p;
+    reinterpret_cast<float4*>(m)[ci] = mm;
+    reinterpret_cast<float4*>(v)[ci] = vv;
+    if (ema_table && ema_mode) {
+        float4* __restrict__ e4 = reinterpret_cast<float4*>(ema_table + row * ema_ld) + i;
+        if (ema_mode == 1) {
+            *e4 = p;  // warm-up: plain copy
+        } else {
+            float4 e = *e4;
+            e.x = e.x * ema_b + ema_omb * p.x;
+            e.y = e.y * ema_b + ema_omb * p.y;
+            e.z = e.z * ema_b + ema_omb * p.z;
+            e.w = e.w * ema_b + ema_omb * p.w;
+            *e4 = e;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int wd_adamw_table_entry_bytes(void) { return (int)sizeof(wd_adamw_table_entry); }
@@ -440,5 +498,38 @@ extern "C" int wd_weighted_mse_loss(const float* pred, const float* target, cons
         hipLaunchKernelGGL(wmse_stage1<false>, dim3((unsigned)batch), dim3(256), 0, st, pred, target, mask, batch, n4, t, weights,
                            grad, scratch);
     hipLaunchKernelGGL(wmse_stage2, dim3(1), dim3(256), 0, st, scratch, batch, t, weights, T, loss, sample_loss, hist, nbins);
+    return wd_check_launch();
+}
+
+extern "C" int wd_adamw_rows(float* table, int ld, int c, const int* rows, int nrows, int vocab, const float* grad, float* m,
+                             float* v, const float* anchor, float* ema_table, int ema_ld, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, int64_t step, int ema_mode, double ema_beta, const float* gscale,
+                             void* stream) {
+    if (!table || !rows || !grad || !m || !v || nrows < 1 || nrows > WD_ROWS_MAX || vocab < 1 || c < 4 || (c & 3) || ld < c ||
+        (ld & 3) || step <= 0 || ema_mode < 0 || ema_mode > 2)
+        return WD_EINVAL;
+    if (ema_table && (ema_ld < c || (ema_ld & 3))) return WD_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(m) |
+         reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(anchor) | reinterpret_cast<uintptr_t>(ema_table)) & 15u)
+        return WD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(gscale) & 3u) return WD_EINVAL;
+    row_list rl;
+    for (int j = 0; j < nrows; ++j) {
+        if (rows[j] < 0 || rows[j] >= vocab) return WD_EINVAL;
+        for (int k = 0; k < j; ++k)
+            if (rows[k] == rows[j]) return WD_EINVAL;
+        rl.row[j] = rows[j];
+    }
+    for (int j = nrows; j < WD_ROWS_MAX; ++j) rl.row[j] = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the scalars as wd_adamw_multi forms them (doubles, rounded once to fp32)
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float decay = (float)(1.0 - lr * weight_decay), lrwd = (float)(lr * weight_decay), omb1 = (float)(1.0 - beta1),
+                b2 = (float)beta2, omb2 = (float)(1.0 - beta2), step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const int c4 = c >> 2;
+    WdLaunchScope scope(WD_CLS_OTHER, st);
+    hipLaunchKernelGGL(adamw_rows_kernel, dim3((unsigned)((c4 + 255) / 256), (unsigned)nrows), dim3(256), 0, st, table, ld, c4, rl,
+                       grad, m, v, anchor, ema_table, ema_ld, decay, lrwd, omb1, b2, omb2, step_size, bc2_sqrt, (float)eps,
+                       ema_mode, (float)ema_beta, (float)(1.0 - ema_beta), gscale);
     return wd_check_launch();
 }

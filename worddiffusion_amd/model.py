@@ -210,6 +210,45 @@ class UNetBase(nn.Module):
                 self._train_engine.set_precision(mode)
         return self._train_engine
 
+    def add_writers(self, k: int, init="mean"):
+        """Grows the writer table by ``k`` rows (DESIGN.md "Fitting new writers") and returns the new ids,
+        ``list(range(old, old + k))``.  ``label_emb`` becomes an ``nn.Embedding(num_classes + k, ted)`` whose first rows are the old
+        ones bit for bit, so ``state_dict()`` keeps the reference's key layout and loads ``strict=True`` into a model built with
+        ``num_classes + k``.  ``init``: "mean" (the fp32 mean over the old rows), an int id or a list of ``k`` ids (copies of those
+        rows), or a float tensor [k, ted].  The engines are dropped - plans, packed tables and the gradient arena are sized for
+        the old table - and rebuilt lazily; an EMA copy is grown by the caller with the same call."""
+        if self.num_classes is None:
+            raise ValueError("add_writers needs a class-conditional model (num_classes)")
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"k must be an integer >= 1, got {k!r}")
+        old_w = self.label_emb.weight.detach()
+        old, ted = old_w.shape
+        if isinstance(init, str):
+            if init != "mean":
+                raise ValueError(f"init must be 'mean', a writer id, a list of {k} ids or a float tensor [{k}, {ted}], not {init!r}")
+            rows = old_w.float().mean(0, keepdim=True).expand(k, ted)
+        elif torch.is_tensor(init) and init.is_floating_point():
+            if tuple(init.shape) != (k, ted):
+                raise ValueError(f"an init tensor must be [{k}, {ted}], got {tuple(init.shape)}")
+            rows = init.detach().to(device=old_w.device, dtype=old_w.dtype)
+        else:
+            ids = [init] * k if isinstance(init, int) and not isinstance(init, bool) else \
+                (init.tolist() if torch.is_tensor(init) else list(init) if isinstance(init, (list, tuple)) else None)
+            if ids is None or len(ids) != k or any(isinstance(i, bool) or not isinstance(i, int) for i in ids):
+                raise ValueError(f"init must be 'mean', a writer id, a list of {k} ids or a float tensor [{k}, {ted}]")
+            if any(i < 0 or i >= old for i in ids):
+                raise ValueError(f"every init id must lie in [0, {old})")
+            rows = old_w[torch.tensor(ids, dtype=torch.long, device=old_w.device)]
+        emb = nn.Embedding(old + k, ted, device=old_w.device, dtype=old_w.dtype)
+        with torch.no_grad():
+            emb.weight[:old].copy_(old_w)
+            emb.weight[old:].copy_(rows)
+        emb.weight.requires_grad_(self.label_emb.weight.requires_grad)
+        self.label_emb = emb
+        self.num_classes = old + k
+        self._engine = self._train_engine = None
+        return list(range(old, old + k))
+
     def set_dropout_state(self, seed: int, row_base: int = 0):
         """Keys the training dropout of ``model(...)`` under autograd (``dropout.py``): the Philox seed, and the global row the
         next training forward gives its sample 0 - every forward then advances it by its batch."""

@@ -269,3 +269,156 @@ class FusedAdamW:
         # them must repack before their next use
         from .engine import note_native_write
         note_native_write()
+
+
+def check_rows(rows, vocab: int) -> tuple:
+    """A row list of the row-wise kernels (``wd_row_slots`` / ``wd_adamw_rows``): 1 .. WD_ROWS_MAX distinct integer ids in
+    [0, vocab) -> a tuple of ints, in the caller's order.  The C entry points refuse the same lists; this raises first, on the
+    host, with a message."""
+    try:
+        rows = tuple(rows.tolist() if torch.is_tensor(rows) else rows)
+    except TypeError:
+        raise ValueError(f"rows must be a sequence of writer ids, got {rows!r}") from None
+    rmax = N.DEFINES["WD_ROWS_MAX"]
+    if not 1 <= len(rows) <= rmax:
+        raise ValueError(f"rows must hold 1 .. {rmax} ids, got {len(rows)}")
+    if any(isinstance(r, bool) or not isinstance(r, int) for r in rows):
+        raise ValueError("rows must be integer ids")
+    if any(r < 0 or r >= int(vocab) for r in rows):
+        raise ValueError(f"every row must lie in [0, {int(vocab)})")
+    if len(set(rows)) != len(rows):
+        raise ValueError("rows must be distinct")
+    return rows
+
+
+class RowAdamW:
+    """AdamW (+ EMA) over a few rows of one embedding table, every other parameter frozen: the optimiser of embedding-only
+    fitting (DESIGN.md "Fitting new writers").  ``table_param`` is ``model.label_emb.weight``, ``rows`` the ids being fitted.  It
+    holds compact ``[R, c]`` buffers - ``row_grad`` (written by the frozen backward plan of ``TrainStep``), ``exp_avg``,
+    ``exp_avg_sq`` - and ``step()`` is one ``wd_adamw_rows`` launch, after the norm pass of ``wd_grad_sqnorm_multi`` over
+    ``row_grad`` when ``max_grad_norm`` is given (``grad_norm`` then holds the pre-clip norm, as in ``FusedAdamW``).
+
+    ``anchor``: None - plain decoupled decay towards zero, ``wd_adamw_multi``'s arithmetic; "init" - the rows' values at
+    construction; a float tensor [R, c].  With an anchor the decay pulls towards it, p -= lr * weight_decay * (p - a): decay
+    towards zero would drag a fitted row towards the writer-free point.  ``ema_model``: a model with a table of the same shape
+    (grown by the same ``add_writers`` call); its rows follow ``step_start_ema`` as in ``FusedAdamW``, nothing else of it is
+    touched."""
+
+    def __init__(self, table_param, rows, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, anchor=None, ema_model=None,
+                 ema_beta=0.995, step_start_ema=2000, max_grad_norm=None):
+        import ctypes as C
+        if not torch.is_tensor(table_param) or table_param.dim() != 2 or table_param.dtype != torch.float32:
+            raise ValueError("table_param must be a 2-d fp32 embedding table")
+        vocab, c = table_param.shape
+        self.rows = check_rows(rows, vocab)
+        if c % 4:
+            raise ValueError(f"the table's width must be a multiple of 4, got {c}")
+        if not table_param.is_cuda:
+            raise N.NativeError("RowAdamW needs a CUDA table (no CPU fallback)")
+        if not table_param.is_contiguous():
+            raise ValueError("table_param must be contiguous")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"max_grad_norm must be a positive number or inf, got {max_grad_norm}")
+        self.max_grad_norm = max_grad_norm
+        self.table = table_param
+        self.params = [table_param]
+        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, params=self.params)]
+        self.ema_beta, self.step_start_ema = ema_beta, step_start_ema
+        self.ema_table = None
+        if ema_model is not None:
+            et = getattr(getattr(ema_model, "label_emb", None), "weight", None)
+            if et is None or tuple(et.shape) != (vocab, c) or et.device != table_param.device or not et.is_contiguous():
+                raise ValueError("ema_model does not hold a writer table of the same shape on the same device")
+            self.ema_table = et
+        dev, R = table_param.device, len(self.rows)
+        self._rows_c = (C.c_int * R)(*self.rows)
+        self.step_count = 0
+        self.row_grad = torch.zeros(R, c, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros(R, c, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(R, c, dtype=torch.float32, device=dev)
+        if anchor is None:
+            self.anchor = None
+        elif isinstance(anchor, str):
+            if anchor != "init":
+                raise ValueError(f"anchor must be None, 'init' or a float tensor [{R}, {c}], not {anchor!r}")
+            self.anchor = table_param.detach()[list(self.rows)].clone()
+        else:
+            anchor = torch.as_tensor(anchor)
+            if not anchor.is_floating_point() or tuple(anchor.shape) != (R, c):
+                raise ValueError(f"anchor must be None, 'init' or a float tensor [{R}, {c}], got {tuple(anchor.shape)}")
+            self.anchor = anchor.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+        self._clip_ctl = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.grad_norm = self._clip_ctl[:1]
+        self._norm_table = self._partials = None
+
+    lr = property(lambda self: self.param_groups[0]["lr"])
+    betas = property(lambda self: self.param_groups[0]["betas"])
+    eps = property(lambda self: self.param_groups[0]["eps"])
+    weight_decay = property(lambda self: self.param_groups[0]["weight_decay"])
+
+    def zero_grad(self, set_to_none: bool = True):
+        self.row_grad.zero_()
+
+    def bind_grad(self, buf: torch.Tensor):
+        """Makes ``buf`` (fp32 [R, c] on the table's device: a frozen-trunk plan's ``row_grad``) the gradient ``step()`` reads."""
+        if buf.dtype != torch.float32 or tuple(buf.shape) != tuple(self.exp_avg.shape) or buf.device != self.table.device or \
+                not buf.is_contiguous():
+            raise ValueError(f"row_grad must be a contiguous fp32 {list(self.exp_avg.shape)} tensor on the table's device")
+        self.row_grad = buf
+        self._norm_table = None  # (it holds the old buffer's address)
+
+    def state_dict(self):
+        """The rows, the step and the three buffers (plus the anchor and the hyper-parameters)."""
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        return dict(rows=list(self.rows), step_count=self.step_count, row_grad=self.row_grad.clone(), exp_avg=self.exp_avg.clone(),
+                    exp_avg_sq=self.exp_avg_sq.clone(), anchor=None if self.anchor is None else self.anchor.clone(),
+                    param_group=group, ema_beta=self.ema_beta, step_start_ema=self.step_start_ema)
+
+    def load_state_dict(self, sd):
+        if tuple(sd["rows"]) != self.rows:
+            raise ValueError(f"loaded state is for rows {list(sd['rows'])}, this optimiser fits {list(self.rows)}")
+        for name in ("row_grad", "exp_avg", "exp_avg_sq"):
+            if tuple(sd[name].shape) != tuple(self.row_grad.shape):
+                raise ValueError(f"{name} has shape {tuple(sd[name].shape)}, expected {tuple(self.row_grad.shape)}")
+        if (sd.get("anchor") is None) != (self.anchor is None):
+            raise ValueError("loaded state and this optimiser disagree on having an anchor")
+        with torch.no_grad():
+            for name in ("row_grad", "exp_avg", "exp_avg_sq"):
+                getattr(self, name).copy_(sd[name])
+            if self.anchor is not None:
+                self.anchor.copy_(sd["anchor"])
+        for k, v in sd.get("param_group", {}).items():
+            self.param_groups[0][k] = tuple(v) if k == "betas" else v
+        self.step_count = int(sd["step_count"])
+        self.ema_beta = sd.get("ema_beta", self.ema_beta)
+        self.step_start_ema = sd.get("step_start_ema", self.step_start_ema)
+
+    def step(self):
+        lib, dev = N.lib(), self.table.device
+        vocab, c = self.table.shape
+        self.step_count += 1
+        mode = 0 if self.ema_table is None else (1 if (self.step_count - 1) < self.step_start_ema else 2)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        gscale = None
+        if self.max_grad_norm is not None:
+            if self._norm_table is None:  # a one-entry wd_adamw_multi table over row_grad: the norm pass reads g and n only
+                chunk = lib.wd_adamw_chunk()
+                n = self.row_grad.numel()
+                rec = N.WdAdamwTableEntry(0, self.row_grad.data_ptr(), 0, 0, 0, n, 0)
+                self._norm_table = torch.frombuffer((N.WdAdamwTableEntry * 1)(rec), dtype=torch.uint8).to(dev)
+                self._chunks = (n + chunk - 1) // chunk
+                self._partials = torch.empty(self._chunks, dtype=torch.float64, device=dev)
+            N.check(lib.wd_grad_sqnorm_multi(self._norm_table.data_ptr(), 1, self._chunks, self._partials.data_ptr(),
+                                             self.max_grad_norm, self._clip_ctl.data_ptr(), st), "wd_grad_sqnorm_multi")
+            gscale = self._clip_ctl.data_ptr() + 4
+        N.check(lib.wd_adamw_rows(self.table.data_ptr(), c, c, self._rows_c, len(self.rows), vocab, self.row_grad.data_ptr(),
+                                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                  None if self.anchor is None else self.anchor.data_ptr(),
+                                  None if self.ema_table is None else self.ema_table.data_ptr(), c, float(self.lr),
+                                  float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                                  self.step_count, mode, float(self.ema_beta), gscale, st), "wd_adamw_rows")
+        # the kernel changed the table (and the EMA copy) behind autograd's back: every engine repacks before its next use
+        from .engine import note_native_write
+        note_native_write()

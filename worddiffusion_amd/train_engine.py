@@ -46,6 +46,7 @@ class TrainPlan(Plan):
         super().__init__()
         self.bwd: List[tuple] = []
         self.dout: Optional[torch.Tensor] = None
+        self.row_grad: Optional[torch.Tensor] = None  # frozen-trunk plan (plan_train rows): the fitted rows' gradient, fp32 [R, ted]
         # training dropout: the wd_dropout of every ResBlock with p > 0 (read by the host at launch or capture) and the device
         # row base they all point to - uint64 [1] kept as int64 bits -, so a captured step draws new masks when replayed
         self.dropouts: List[DO.WdDropout] = []
@@ -114,7 +115,8 @@ def conv3_seg(planes, c: int, ftab, btab, hw_src: int, wb: str, wgrad, dx: Dx, d
 class _Build:
     """What one ``plan_train`` build collects on its way: made when the build starts, dropped when it ends or raises."""
 
-    def __init__(self):
+    def __init__(self, rows=None):
+        self.rows = rows                        # frozen-trunk plan: the label_emb rows being fitted (None: everything trains)
         self.tape: List[Callable] = []          # the backward of every block, in forward order
         self.pw = set()                         # parameter-gradient buffers the backward list has written (_pacc)
         self.deferred, self.deferred_outs = [], {}  # wd_colsum_finish_multi entries per round; rounds taken per buffer
@@ -239,15 +241,21 @@ class TrainEngine(UNetEngine):
         assert self._arena_used <= self._arena.numel()
         return out
 
-    def _pgrad(self, p: torch.nn.Parameter) -> torch.Tensor:
+    def _pgrad(self, p: torch.nn.Parameter, shape=None) -> Optional[torch.Tensor]:
+        """The gradient buffer of ``p`` (viewed as ``shape``) - or None in a frozen-trunk build, where no parameter has one: every
+        emitter then leaves out the launches whose only product it would be."""
+        if self._bs.rows is not None:
+            return None
         if id(p) not in self._grad:
             self._grad[id(p)] = self._carve(tuple(p.shape))
             self._params[id(p)] = p
-        return self._grad[id(p)]
+        return self._grad[id(p)] if shape is None else self._grad[id(p)].view(shape)
 
     def _pgroup(self, params: List[torch.nn.Parameter]) -> torch.Tensor:
         """One buffer whose row blocks are the gradients of ``params`` (weights the forward concatenates: all FiLM
-        projections, every cross-attention's K/V, the word encoder's q/k/v)."""
+        projections, every cross-attention's K/V, the word encoder's q/k/v).  None in a frozen-trunk build (_pgrad)."""
+        if self._bs.rows is not None:
+            return None
         key = ("group",) + tuple(id(p) for p in params)
         if key not in self._scr:
             tail = tuple(params[0].shape[1:])
@@ -262,7 +270,10 @@ class TrainEngine(UNetEngine):
         return self._scr[key]
 
     def _ppair(self, p0: torch.nn.Parameter, p1: torch.nn.Parameter) -> torch.Tensor:
-        """[2, c] buffer: row 0 is p0's gradient, row 1 p1's (norm scale / shift pairs come out of one column sum)."""
+        """[2, c] buffer: row 0 is p0's gradient, row 1 p1's (norm scale / shift pairs come out of one column sum).  None in a
+        frozen-trunk build (_pgrad)."""
+        if self._bs.rows is not None:
+            return None
         key = ("pair", id(p0), id(p1))
         if key not in self._scr:
             buf = self._carve((2,) + tuple(p0.shape))
@@ -410,6 +421,7 @@ class TrainEngine(UNetEngine):
         geglu = (u, dh, inner): d(output) is the GEGLU projection's and is NOT materialised - wd_dout_prep_geglu derives its planes
         and column sums from the saved pre-activation and the gradient of the activation's output (dout is None then)."""
         npad = n if npad is None else npad
+        bias = [b for b in bias if b is not None]  # (a frozen-trunk build has no bias gradient: _pgrad)
         forms = [self._dw_form(s, M, n, npad, hw_out) for s in segs]
         dpl, doutT, colpart = self._stage_dout(P, what, dout, M, n, npad, hw_out, segs, forms, bias, film_off, geglu)
         for si, (s, form) in enumerate(zip(segs, forms)):
@@ -463,7 +475,7 @@ class TrainEngine(UNetEngine):
         outs = (*self._hilo(dpl), _ptr(doutT[0]) if need_dw else None, _ptr(doutT[1]) if need_dw else None, _ptr(colpart))
         if geglu is not None:
             u, dh, inner = geglu
-            assert dout is None and n == 2 * inner and npad == n and colpart is not None and film_off is None, what
+            assert dout is None and n == 2 * inner and npad == n and (colpart is not None or not bias) and film_off is None, what
             P.bwd.append((lib.wd_dout_prep_geglu, (u.data_ptr(), u.shape[1], dh.data_ptr(), dh.shape[1], M, inner, mpad, *outs),
                           what + ":prep(geglu bwd)"))
         elif need_dpl or need_dw or colpart is not None:
@@ -545,13 +557,12 @@ class TrainEngine(UNetEngine):
         cpg = ctot // 32
         gam, bet = gn.weight, gn.bias
         gw, gb = self._w[self._bs.gn_names[id(gn)] + ".g"], self._w[self._bs.gn_names[id(gn)] + ".b"]
-        pair = self._ppair(bet, gam)  # [d beta | d gamma], the order of the planar sums
-        dbet, dgam = pair[0], pair[1]
+        pair = self._ppair(bet, gam)  # [d beta | d gamma], the order of the planar sums; None: frozen, the sums stay in scratch
         # one pass (the workgroup keeps its tile of dy / xhat in LDS) where the shape allows, else statistics pass + apply pass
         fused = self.fuse_gn_bwd and all(lib.wd_gn_bwd_fused_supported(hw, s.c, cpg) for s in srcs)
         nb = 1 if fused else lib.wd_gn_bwd_nchunk(hw)
         off = 0
-        accp = self._pacc(pair)
+        accp = self._pacc(pair) if pair is not None else 0
         for s in srcs:
             part, nchunk, pc = s.stats
             sums = self._f32(P, B, nb, 2, s.c)
@@ -571,12 +582,14 @@ class TrainEngine(UNetEngine):
             else:
                 ops.append((lib.wd_gn_bwd_stats, common, what + ":stats"))
                 ops.append((lib.wd_gn_bwd_apply, common + (g.data_ptr(), s.c, acc), what + ":apply"))
-            if len(srcs) == 1:
+            if pair is None:
+                pass  # (the by-product sums stay in ``sums``)
+            elif len(srcs) == 1:
                 self._param_colsum(ops, what + ":dbeta|dgamma", sums.data_ptr(), 2 * s.c, B * nb, 2 * s.c, pair.data_ptr(), accp)
             else:
-                self._param_colsum(ops, what + ":dbeta", sums.data_ptr(), 2 * s.c, B * nb, s.c, dbet.data_ptr() + 4 * off, accp)
+                self._param_colsum(ops, what + ":dbeta", sums.data_ptr(), 2 * s.c, B * nb, s.c, pair[0].data_ptr() + 4 * off, accp)
                 self._param_colsum(ops, what + ":dgamma", sums.data_ptr() + 4 * s.c, 2 * s.c, B * nb, s.c,
-                                   dgam.data_ptr() + 4 * off, accp)
+                                   pair[1].data_ptr() + 4 * off, accp)
             off += s.c
 
     def _ln_bwd(self, P, what, x: torch.Tensor, rows, c, ln: torch.nn.LayerNorm, name, dy: torch.Tensor, dx: torch.Tensor,
@@ -588,11 +601,13 @@ class TrainEngine(UNetEngine):
         ops.append((lib.wd_layernorm_bwd, (x.data_ptr(), c, dy.data_ptr(), c, rows, c, self._w[name + ".g"].data_ptr(), 1e-5,
                                            dx.data_ptr(), c, int(acc), colpart.data_ptr()), what))
         pair = self._ppair(ln.weight, ln.bias)  # [d gamma | d beta], the order of colpart
-        self._param_colsum(ops, what + ":dgamma|dbeta", colpart.data_ptr(), 2 * c, nblk, 2 * c, pair.data_ptr(), self._pacc(pair))
+        if pair is not None:
+            self._param_colsum(ops, what + ":dgamma|dbeta", colpart.data_ptr(), 2 * c, nblk, 2 * c, pair.data_ptr(), self._pacc(pair))
 
     def _attn_bwd(self, P, what, q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, dO: torch.Tensor, heads, nq, nk, d, scale, dq_ptr, lddq,
-                  dkv_ptr, dkv_pitch_floats):
-        """dq -> dq_ptr; [dK | dV] rows (b, j) -> dkv_ptr with the given row pitch (2*inner floats wide)."""
+                  dkv_ptr, dkv_pitch_floats, want_dkv=True):
+        """dq -> dq_ptr; [dK | dV] rows (b, j) -> dkv_ptr with the given row pitch (2*inner floats wide).  want_dkv False: nothing
+        reads them (the context of a frozen trunk), so the short-key form leaves its partial sums where they are."""
         ops = P.bwd
         lib = self.lib
         B = self._B
@@ -611,6 +626,8 @@ class TrainEngine(UNetEngine):
         part = self._f32(P, B, nwg, nk, 2, inner)
         ops.append((lib.wd_attention_bwd_small, (q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, dO.data_ptr(), dO.shape[1], B, heads, nq, nk,
                                                  d, float(scale), dq_ptr, lddq, part.data_ptr(), None), what))
+        if not want_dkv:
+            return
         row = nk * 2 * inner
         tmp = self._f32(P, B, row)
         self._colsum(ops, what + ":dkv", part.data_ptr(), row, B * nwg, row, nwg, tmp.data_ptr(), row, 0)
@@ -627,7 +644,8 @@ class TrainEngine(UNetEngine):
         tab = self._table(h, w, "same")
         need_raw = cin != cout
         # nn.Dropout(p) of out_layers (unet.py:616-623): on the planes conv2 reads, recomputed by the backward of the second norm
-        p_drop = DO.check_p(mod.out_layers[2].p)
+        # (a frozen trunk is evaluated as model.eval() evaluates it: no dropout whatever p the module carries)
+        p_drop = DO.check_p(mod.out_layers[2].p) if self._bs.rows is None else 0.0
         drop = self._dropout_args(P, mod, p_drop) if p_drop > 0 else None
         cpg = cin // 32
         parts = None
@@ -668,7 +686,7 @@ class TrainEngine(UNetEngine):
             dO = out.g
             btab = self._btable(h, w, "same")
             da2 = self._f32(P, M, cout)
-            segs = [conv3_seg(a2, cout, tab.dev, btab, hw, "B:" + name + ".c2.w", self._pgrad(mod.out_layers[3].weight).view(cout, -1),
+            segs = [conv3_seg(a2, cout, tab.dev, btab, hw, "B:" + name + ".c2.w", self._pgrad(mod.out_layers[3].weight, (cout, -1)),
                               Dx(da2, cout, 0, 0, cout), M, hw)]
             biases = [self._pgrad(mod.out_layers[3].bias)]
             if need_raw:
@@ -678,7 +696,7 @@ class TrainEngine(UNetEngine):
                     dxs.append(Dx(g, s.c, acc, coff, s.c))
                     coff += s.c
                 segs.append(BwdSeg(raw, cin, 1, hw, wb="B:" + name + ".skip.w",
-                                   wgrad=self._pgrad(mod.skip_connection.weight).view(cout, cin), dx=dxs, dx_rows=M, dx_hw=hw))
+                                   wgrad=self._pgrad(mod.skip_connection.weight, (cout, cin)), dx=dxs, dx_rows=M, dx_hw=hw))
                 biases.append(self._pgrad(mod.skip_connection.bias))
             else:
                 self._dresid(P, name, srcs[0], dO, M)
@@ -687,7 +705,7 @@ class TrainEngine(UNetEngine):
             da1 = self._f32(P, M, cin)
             self._bwd_linear(P, name + ".conv1", h1.g, M, cout, hw,
                              [conv3_seg(a1, cin, tab.dev, btab, hw, "B:" + name + ".c1.w",
-                                        self._pgrad(mod.in_layers[2].weight).view(cout, -1), Dx(da1, cin, 0, 0, cin), M, hw)],
+                                        self._pgrad(mod.in_layers[2].weight, (cout, -1)), Dx(da1, cin, 0, 0, cin), M, hw)],
                              bias=[self._pgrad(mod.in_layers[2].bias)], film_off=self.film_off[name])
             self._gn_bwd(P, name + ".gn1", srcs, mod.in_layers[0], 1e-5, True, da1)
             if parts is not None:
@@ -733,7 +751,7 @@ class TrainEngine(UNetEngine):
                 du = self._f32(P, M_out, x.c)
                 dx, dx_rows, dx_hw = Dx(du, x.c, 0, 0, x.c), M_out, hw_out
             self._bwd_linear(P, name + ".conv", out.g, M_out, mod.cout, hw_out,
-                             [conv3_seg(pl, x.c, tab.dev, btab, hw_in, "B:" + name + ".w", self._pgrad(conv.weight).view(mod.cout, -1),
+                             [conv3_seg(pl, x.c, tab.dev, btab, hw_in, "B:" + name + ".w", self._pgrad(conv.weight, (mod.cout, -1)),
                                         dx, dx_rows, dx_hw)],
                              bias=[self._pgrad(conv.bias)])
             if mode == "up":
@@ -834,7 +852,7 @@ class TrainEngine(UNetEngine):
         dcur = self._f32(P, M, st.inner)
         self._bwd_linear(P, name + ".proj_out", dO, M, c, st.hw,
                          [linear_seg(st.blocks[-1].xpl, st.inner, st.hw, "B:" + name + ".po.w",
-                                     self._pgrad(mod.proj_out.weight).view(c, st.inner), dcur, M)],
+                                     self._pgrad(mod.proj_out.weight, (c, st.inner)), dcur, M)],
                          bias=[self._pgrad(mod.proj_out.bias)])
         return dcur
 
@@ -876,7 +894,8 @@ class TrainEngine(UNetEngine):
             proj, dq = tag + ".q", self._f32(P, M, inner)
             kv, dkv = self._kv.data_ptr() + 4 * a.ko, self._bs.dkv.data_ptr() + 4 * a.ko
             self._attn_bwd(P, f"{p}.{tag}:bwd", a.q.data_ptr(), inner, kv, self.kv_total, kv + 4 * inner, self.kv_total, do, heads,
-                           hw, self._ctx_len, d, d ** -0.5, dq.data_ptr(), inner, dkv, self.kv_total)
+                           hw, self._ctx_len, d, d ** -0.5, dq.data_ptr(), inner, dkv, self.kv_total,
+                           want_dkv=self._bs.rows is None)
             wg = self._pgrad(at.to_q.weight)
         self._bwd_linear(P, f"{p}.{proj}", dq, M, dq.shape[1], hw, [linear_seg(a.n, inner, hw, f"B:{p}.{proj}.w", wg, dn, M)])
         self._ln_bwd(P, f"{p}.{a.ln}({tag}):bwd", a.x, M, inner, getattr(blk.tb, a.ln), f"{p}.{a.ln}", dn, dcur, 1)
@@ -886,7 +905,7 @@ class TrainEngine(UNetEngine):
         name, mod, c, M = st.name, st.mod, st.x.c, st.M
         dg = self._f32(P, M, c)
         self._bwd_linear(P, name + ".proj_in", dcur, M, st.inner, st.hw,
-                         [linear_seg(st.gpl, c, st.hw, "B:" + name + ".pi.w", self._pgrad(mod.proj_in.weight).view(st.inner, c),
+                         [linear_seg(st.gpl, c, st.hw, "B:" + name + ".pi.w", self._pgrad(mod.proj_in.weight, (st.inner, c)),
                                      dg, M)], bias=[self._pgrad(mod.proj_in.bias)])
         self._gn_bwd(P, name + ".gn", [st.x], mod.norm, 1e-6, False, dg)
 
@@ -923,12 +942,19 @@ class TrainEngine(UNetEngine):
         if self._ws is None or self._ws.numel() < 8 * 2 * cmax * 9 * cmax:
             self._ws = torch.empty(max(128 * 128 * 160 * 8, 8 * 2 * cmax * 9 * cmax), dtype=torch.float32, device=self.device)
 
-    def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0, label_drop=None) -> TrainPlan:
-        """label_drop: None - every sample keeps its writer term, the plan without the argument; "mask" - the term per sample from
+    def plan_train(self, B: int, H: int, W: int, ctx_len: int, phosc_len: int = 0, label_drop=None, rows=None) -> TrainPlan:
+        """rows: None - everything trains, the plan without the argument; a tuple of distinct writer ids - the frozen-trunk plan
+        that fits those rows of ``label_emb`` (DESIGN.md "Fitting new writers").  Its forward is the training forward WITHOUT
+        ResBlock dropout, whatever p the modules carry: a frozen trunk is evaluated as ``model.eval()`` evaluates it.  Its backward
+        is the full list minus every launch whose only product is the gradient of a frozen parameter - the data-gradient chain
+        down to the FiLM rows, emb_layers(all)'s dX and the embedding SiLU stay -, then ``wd_row_slots`` on the plan's ``y`` and
+        ``wd_embedding_bwd`` into ``P.row_grad``, compact fp32 [len(rows), ted].  No buffer of the gradient arena is carved or
+        written and there are no bucket cuts.
+        label_drop: None - every sample keeps its writer term, the plan without the argument; "mask" - the term per sample from
         ``P.keep_in`` (uint8 [B], ``load_keep``); a float p in (0, 1) - dropped with probability p, drawn on the device per
         global sample row (``wd_label_rows_keep``).  Either way the rows the kernel writes are the residual of the time_embed.2
         GEMM and label_emb's backward reads the ids it writes (-1 for a dropped sample: no gradient row)."""
-        key, label_drop = self._train_key(B, H, W, ctx_len, phosc_len, label_drop)
+        key, label_drop, rows = self._train_key(B, H, W, ctx_len, phosc_len, label_drop, rows)
         P = self._cached_plan(self._tplans, key)
         if P is not None:
             return P
@@ -938,7 +964,7 @@ class TrainEngine(UNetEngine):
             self._scr = {k: v for k, v in self._scr.items() if isinstance(k, tuple)}
         m = self.model
         P = self._begin_plan(TrainPlan(), B)
-        self._bs = _Build()
+        self._bs = _Build(rows)
         try:
             P.row_base = torch.zeros(1, dtype=torch.int64, device=self.device)
             L = ctx_len + phosc_len
@@ -958,21 +984,31 @@ class TrainEngine(UNetEngine):
             self._tail_bwd(P, last, gpl)
             self._replay_tape(P)
             self._embed_bwd(P, first, xin, emb)
-            self._cond_bwd(P, groups, L)
+            if rows is None:
+                self._cond_bwd(P, groups, L)
             self._flush_dw(P)
             self._flush_deferred(P)
-            P.bwd_segments = self._arena_segments(P)
+            P.bwd_segments = self._arena_segments(P) if rows is None else []
         finally:
             self._bs = None
         self._tplans[key] = P
         return P
 
-    def _train_key(self, B, H, W, ctx_len, phosc_len, label_drop):
-        """Refuses what cannot train and returns (cache key, label_drop as the plan takes it).  No device work and no change to the
-        engine: a refused call leaves the cached plans as they were."""
-        # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1); a plan is built for its p's
-        drops = tuple(DO.check_p(mod.out_layers[2].p) for _, mod in self._walk() if isinstance(mod, ResBlockParams))
-        key = (B, H, W, ctx_len, phosc_len, self.npass) + ((drops,) if any(drops) else ())
+    def _train_key(self, B, H, W, ctx_len, phosc_len, label_drop, rows=None):
+        """Refuses what cannot train and returns (cache key, label_drop and rows as the plan takes them).  No device work and no
+        change to the engine: a refused call leaves the cached plans as they were."""
+        if rows is not None:  # the frozen-trunk plan: no dropout, so no p in its key
+            if self.model.num_classes is None:
+                raise ValueError("fitting writer rows needs a class-conditional model (num_classes)")
+            if label_drop is not None:
+                raise ValueError("a row being fitted must keep its writer term: rows together with label_drop")
+            from .optim import check_rows
+            rows = check_rows(rows, self.model.num_classes)
+            key = (B, H, W, ctx_len, phosc_len, self.npass, ("rows", rows))
+        else:
+            # p outside [0, 1) cannot train (nn.Dropout itself accepts p = 1); a plan is built for its p's
+            drops = tuple(DO.check_p(mod.out_layers[2].p) for _, mod in self._walk() if isinstance(mod, ResBlockParams))
+            key = (B, H, W, ctx_len, phosc_len, self.npass) + ((drops,) if any(drops) else ())
         if label_drop is not None:
             if label_drop != "mask":
                 label_drop = DO.check_p(label_drop)
@@ -987,7 +1023,7 @@ class TrainEngine(UNetEngine):
             raise ValueError("phoscLabels are an input of UNetModelPhosc only")
         if self.model.out_channels > 32:
             raise NotImplementedError("out_channels > 32")  # (the gradient planes of the output convolution are 32 wide)
-        return key, label_drop
+        return key, label_drop, rows
 
     def _embed_fwd(self, P, label_drop):
         """Appends the time / writer embedding and all FiLM projections (into ``self._film``) to ``P.step``, with the writer-dropout
@@ -1047,7 +1083,7 @@ class TrainEngine(UNetEngine):
         dg = self._f32(P, Mo, last.c)
         self._bwd_linear(P, "out.conv", dtok, Mo, oc, hwo,
                          [conv3_seg(gpl, last.c, tab.dev, self._btable(last.h, last.w, "same"), hwo, "B:out.w",
-                                    self._pgrad(m.out[2].weight).view(oc, -1), Dx(dg, last.c, 0, 0, last.c), Mo, hwo)],
+                                    self._pgrad(m.out[2].weight, (oc, -1)), Dx(dg, last.c, 0, 0, last.c), Mo, hwo)],
                          bias=[self._pgrad(m.out[2].bias)], npad=32)
         self._gn_bwd(P, "out.gn", [last], m.out[0], 1e-5, True, dg)
 
@@ -1061,6 +1097,11 @@ class TrainEngine(UNetEngine):
             return not (name.startswith("res.") or name.startswith("wrd_proj.") or ".attnc." in name or ".to_kv." in name or
                         (self.variant == "base" and ".norm1." in name))
         bs = self._bs
+        if bs.rows is not None:  # no parameter gradient, so no arena prefix to finish: no cuts
+            P.bwd_cuts = []
+            for fn in reversed(bs.tape):
+                fn()
+            return
         total = sum(_rup(p.numel(), 64) for n_, p in self.model.named_parameters() if _live(n_))
         first_plan = self._cut_closures is None
         cuts_seen: List[int] = []
@@ -1082,17 +1123,20 @@ class TrainEngine(UNetEngine):
 
     def _embed_bwd(self, P, first: TAct, xin, emb):
         """Appends to ``P.bwd``: the input convolution's weight / bias gradient, then the FiLM projections, the time MLP and the
-        writer embedding, from d(FiLM rows) back to the timestep embedding."""
+        writer embedding, from d(FiLM rows) back to the timestep embedding.  A frozen-trunk build keeps only the chain to the
+        writer rows: emb_layers(all)'s data gradient, the embedding SiLU, then the row slots and the scatter into ``P.row_grad``."""
         m, lib, B, bops = self.model, self.lib, self._B, P.bwd
         te, pre1, e1, pre2, e2, y_bwd = emb
         mc, ted = m.model_channels, 4 * m.model_channels
         assert first.gw
-        hw = first.h * first.w
-        packed = self._f32(P, mc, self.kpad_in)
-        self._bwd_linear(P, "input_blocks.0", first.g, B * hw, mc, hw,
-                         [BwdSeg(xin, self.kpad_in, 1, hw,
-                                 wgrad_packed=(packed, self._pgrad(m.input_blocks[0][0].weight), m.in_channels))],
-                         bias=[self._pgrad(m.input_blocks[0][0].bias)])
+        rows = self._bs.rows
+        if rows is None:
+            hw = first.h * first.w
+            packed = self._f32(P, mc, self.kpad_in)
+            self._bwd_linear(P, "input_blocks.0", first.g, B * hw, mc, hw,
+                             [BwdSeg(xin, self.kpad_in, 1, hw,
+                                     wgrad_packed=(packed, self._pgrad(m.input_blocks[0][0].weight), m.in_channels))],
+                             bias=[self._pgrad(m.input_blocks[0][0].bias)])
         film_w = self._pgroup([l.weight for l in self._film_mods])
         film_b = self._pgroup([l.bias for l in self._film_mods])
         de2 = self._f32(P, B, ted)
@@ -1100,6 +1144,17 @@ class TrainEngine(UNetEngine):
                          [linear_seg(e2, ted, 1, "B:film.w", film_w, de2, B)], bias=[film_b])
         dpre2 = self._f32(P, B, ted)
         bops.append((lib.wd_silu_bwd, (pre2.data_ptr(), de2.data_ptr(), B * ted, dpre2.data_ptr()), "emb SiLU:bwd"))
+        if rows is not None:
+            # the slot of every sample's writer in the row list (-1: not being fitted), then the scatter into the compact buffer
+            R = len(rows)
+            rows_c = (C.c_int * R)(*rows)
+            slots = torch.empty((B,), dtype=torch.int64, device=self.device)
+            P.row_grad = torch.zeros((R, ted), dtype=torch.float32, device=self.device)
+            P.keep += [rows_c, slots]
+            bops.append((lib.wd_row_slots, (y_bwd.data_ptr(), B, rows_c, R, m.num_classes, slots.data_ptr()), "label_emb:row slots"))
+            bops.append((lib.wd_embedding_bwd, (slots.data_ptr(), 1, B, dpre2.data_ptr(), ted, R, ted, P.row_grad.data_ptr(), 0),
+                         "label_emb:bwd(rows)"))
+            return
         if y_bwd is not None:
             dl = self._pgrad(m.label_emb.weight)
             bops.append((lib.wd_embedding_bwd, (y_bwd.data_ptr(), 1, B, dpre2.data_ptr(), ted, m.num_classes, ted, dl.data_ptr(),

@@ -36,6 +36,13 @@ Weighted loss (``loss_weights`` / ``loss_bins`` / ``loss_mask``; DESIGN.md "Weig
 losses and adds them to a per-timestep histogram, inside the captured body.  Accumulation, clipping and data-parallel need no
 change: the gradient is still d loss / d pred of a per-rank mean over B, so the arena holds what it always held.  A step built
 without the new arguments, and never handed a mask, launches ``wd_mse_loss`` as before and allocates nothing new.
+
+Fitting new writers (an ``optim.RowAdamW`` as the optimiser; DESIGN.md "Fitting new writers"): the trunk is frozen and only the
+optimiser's rows of ``label_emb`` train.  The captured body is noise -> forward -> loss -> the frozen-trunk backward
+(``plan_train(rows=...)``: no weight gradient, no ResBlock dropout), whose last launch writes the optimiser's compact ``row_grad``;
+then ``opt.step()``.  Nothing assigns ``param.grad`` (frozen parameters keep ``grad is None``) and there is no all-reduce.  The loss
+launch is the same, so the weighted-loss arguments, ``t=`` / ``noise=`` / ``check=`` and the keying invariant work unchanged.
+Samples whose writer is not among the rows are legal: they cost a forward and add no gradient.
 """
 from __future__ import annotations
 
@@ -46,7 +53,7 @@ import torch
 
 from . import _native as N
 from .dropout import check_p
-from .optim import FusedAdamW, check_loss_weights, check_timesteps, expand_loss_mask
+from .optim import FusedAdamW, RowAdamW, check_loss_weights, check_timesteps, expand_loss_mask
 
 
 class TrainStep:
@@ -64,6 +71,16 @@ class TrainStep:
         writer-free guidance), drawn on the device inside the captured body under the keying invariant of the module docstring;
         ``last_writer_keep`` holds the decisions of the last call.  0 is the step without the argument, launch for launch."""
         self.label_dropout = check_p(label_dropout)
+        self.frozen = isinstance(optimizer, RowAdamW)
+        if self.frozen:  # refused before anything is launched
+            if accumulate != 1:
+                raise ValueError("fitting writer rows (RowAdamW) does not accumulate: accumulate must be 1")
+            if self.label_dropout > 0:
+                raise ValueError("a row being fitted must keep its writer term: label_dropout must be 0 with a RowAdamW")
+            if bucketed:
+                raise ValueError("fitting writer rows (RowAdamW) has no gradient buckets: bucketed must not be True")
+            if getattr(getattr(model, "label_emb", None), "weight", None) is not optimizer.table:
+                raise ValueError("the RowAdamW's table is not this model's label_emb.weight")
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
         if isinstance(loss_bins, bool) or int(loss_bins) != loss_bins or loss_bins < 0:
@@ -97,6 +114,8 @@ class TrainStep:
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
             self.rank = torch.distributed.get_rank(process_group)
+        if self.frozen and self.world > 1:
+            raise ValueError("fitting writer rows (RowAdamW) is single-process: world size must be 1")
         # data-parallel ranks must not draw the same (eps, t): the noise rows are keyed by the GLOBAL row of the step
         # (``(step * world + rank) * B + b``, so world ranks of batch B draw what one process of batch world*B would), and the
         # timesteps come from a per-rank host generator (a single process keeps the reference's global host RNG, train.py:281)
@@ -106,7 +125,11 @@ class TrainStep:
     def _prepare(self, B, H, W, L, dev, phosc_len=0):
         eng = self.eng
         eng.refresh_weights()
-        P = eng.plan_train(B, H, W, L, phosc_len, **(dict(label_drop=self.label_dropout) if self.label_dropout > 0 else {}))
+        if self.frozen:
+            P = eng.plan_train(B, H, W, L, phosc_len, rows=self.opt.rows)
+            self.opt.bind_grad(P.row_grad)  # the plan's last launch writes the optimiser's compact gradient
+        else:
+            P = eng.plan_train(B, H, W, L, phosc_len, **(dict(label_drop=self.label_dropout) if self.label_dropout > 0 else {}))
         ah = self.diffusion.alpha_hat.cpu()
         self._sa, self._sb = torch.sqrt(ah).to(dev).contiguous(), torch.sqrt(1 - ah).to(dev).contiguous()
         self._x0 = torch.zeros_like(P.x_in)
@@ -310,7 +333,8 @@ class TrainStep:
                     torch.distributed.all_reduce(arena, group=self.pg)  # one all-reduce of the whole arena (WDIFF_GRAD_BUCKETS=1)
                     arena.mul_(1.0 / (self.accumulate * self.world))
             if final:
-                self.eng.assign_grads()
+                if not self.frozen:
+                    self.eng.assign_grads()
                 self.opt.step()
                 self.eng.refresh_weights()
             else:
