@@ -196,7 +196,7 @@ int wd_gemm(const wd_gemm_args* args, void* stream);
  * WD_EINVAL.  On WD_OK and out != NULL, *out receives the args as the kernel sees them (tile, ksplit, tickets, slab_rows resolved).
  * Callers ask this rather than restate the rules above. */
 int wd_gemm_check(const wd_gemm_args* args, wd_gemm_args* out);
-/* The launch family wd_gemm would run `args` on, by the name csrc/wd_gemm.hip gives it ("K_V1", "K_V2", "K_M16", "K_V4", "K_GEMMW",
+/* The launch family wd_gemm would run `args` on, by the name csrc/wd_gemm_plan.hip gives it ("K_V1", "K_V2", "K_M16", "K_V4", "K_GEMMW",
  * "K_GEMMQ", ...; a static string), NULL where wd_gemm_check refuses them.  Host only: lets a test pin the kernel a case is about. */
 const char* wd_gemm_check_kernel(const wd_gemm_args* args);
 /* 1 when a launch of bm x bn tiles over `args` (as wd_gemm_check returns them) runs the batched epilogue: the 16-byte path

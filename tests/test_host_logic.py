@@ -439,6 +439,45 @@ def test_wd_gemm_check(name):
     assert out.ksplit > 1 if ksplit is None else out.ksplit == ksplit
 
 
+# ---- the launch family the planner (csrc/wd_gemm_plan.hip) picks, by the name wd_gemm_check_kernel gives it.  The switches that move
+# these decisions (WDIFF_GEMM_*) are assumed unset, as everywhere in the suite.
+_BIG = dict(m=128 * 128, n=640, hw_out=64)      # 128 x 4 tiles of 128 x 160 = 512 workgroups: every CU gets two
+_SMALL = dict(m=32 * 128, n=640, hw_out=64)     # 32 x 4 = 128 workgroups
+_LIN320 = [(320, 1, False, 0)]
+_GEMM_FAMILY = {
+    "c = 96 linear": (dict(m=130, n=100, hw_out=1, srcs=[(96, 1, False, 0)]), "K_V1"),
+    "c = 96 linear, tile 128160": (dict(m=4096, n=320, hw_out=64, srcs=[(96, 1, False, 0)], tile=128160), "K_V1"),
+    "tile 128064": (dict(m=4096, n=320, hw_out=64, srcs=_LIN320, tile=128064), "K_V2"),
+    "tile 64064": (dict(m=4096, n=320, hw_out=64, srcs=_LIN320, tile=64064), "K_V2"),
+    "tile 128128": (dict(m=4096, n=256, hw_out=64, srcs=_LIN320, tile=128128), "K_V2"),
+    "128160, fewer than 512 workgroups": (dict(srcs=_LIN320, tile=128160, ksplit=1, **_SMALL), "K_M16"),
+    "the same with WD_DBG_FORCE_V4": (dict(srcs=_LIN320, tile=128160, ksplit=1, dbg=N.DBG_FORCE_V4, **_SMALL), "K_V4"),
+    "128160, 512 workgroups, no statistics": (dict(srcs=_LIN320, tile=128160, ksplit=1, **_BIG), "K_V4"),
+    "the same with statistics": (dict(srcs=_LIN320, tile=128160, ksplit=1, stat_part=_P, stat_cpg=10, **_BIG), "K_M16"),
+    "tile 64320": (dict(m=64 * 256, n=320, hw_out=256, srcs=[(320, 9, True, 256)], w_layout=3, tile=64320, slab_rows=32), "K_GEMMW"),
+    "w_layout 3, tile 128160": (dict(m=64 * 256, n=320, hw_out=256, srcs=_LIN320, w_layout=3, tile=128160), "K_GEMMW"),
+    "tile 64080": (dict(m=64 * 64, n=640, hw_out=64, srcs=[(640, 9, True, 64)], w_layout=3, tile=64080, slab_rows=16), "K_GEMMQ"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_GEMM_FAMILY))
+def test_wd_gemm_check_kernel_family(name):
+    kw, family = _GEMM_FAMILY[name]
+    kw = dict(kw)
+    a = _gemm_args(kw.pop("m"), kw.pop("n"), kw.pop("hw_out"), kw.pop("srcs"), **kw)
+    assert N.lib().wd_gemm_check_kernel(ctypes.byref(a)) == family.encode()
+
+
+def test_wd_gemm_check_slab_order_weights_need_the_experimental_build():
+    """w_layout 1 (slab-order weights) is the opt-in slab kernel's: a library built without WDIFF_EXPERIMENTAL refuses it."""
+    lib = N.lib()
+    a = _gemm_args(64 * 256, 320, 256, [(320, 9, True, 256)], w_layout=1, slab_rows=66)
+    if lib.wd_gemm_experimental():
+        assert lib.wd_gemm_check_kernel(ctypes.byref(a)) == b"K_SLAB"
+    else:
+        assert lib.wd_gemm_check(ctypes.byref(a), None) == N.WD_EINVAL and lib.wd_gemm_check_kernel(ctypes.byref(a)) is None
+
+
 def test_wd_gemm_check_gn_needs_the_k_cut():
     """The refusal above is the K cut's: the same launch without the norm is legal and resolves to ksplit 1."""
     a = _gemm_args(256 * 64, 640, 64, [(640, 9, True, 64)], w_layout=3, tile=64320, stat_part=_P, stat_cpg=20)

@@ -881,11 +881,8 @@ static int wd_ff_resolve(const wd_ff_args& in, wd_ff_args& a) {
     }
     {
         // the batched epilogue (wd_epilogue_rows): WDIFF_EPI_BATCH (default WD_EPI_BATCH_DEFAULT) is the switch, dbg WD_EPI_BATCH_OFF /
-        // _ON override it per call; wd_epilogue_batch_ok says where it is legal
-        static const bool batch_env = getenv("WDIFF_EPI_BATCH") ? atoi(getenv("WDIFF_EPI_BATCH")) != 0 : WD_EPI_BATCH_DEFAULT;
-        const bool want = (a.dbg & WD_EPI_BATCH_OFF) ? false : (a.dbg & WD_EPI_BATCH_ON) ? true : batch_env;
-        a.dbg &= ~(WD_EPI_BATCH_OFF | WD_EPI_BATCH_ON);
-        if (want && wd_epilogue_batch_shape(ff_epi_args(a, proj, fold), FBM, FC)) a.dbg |= WD_EPI_BATCH_BIT;
+        // _ON override it per call (wd_want_epi_batch, shared with wd_gemm); wd_epilogue_batch_ok says where it is legal
+        if (wd_want_epi_batch(a.dbg) && wd_epilogue_batch_shape(ff_epi_args(a, proj, fold), FBM, FC)) a.dbg |= WD_EPI_BATCH_BIT;
     }
     return WD_OK;
 }

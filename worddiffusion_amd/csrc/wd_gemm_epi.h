@@ -1,4 +1,5 @@
-// Epilogue shared by every tap-gather GEMM kernel of libwdiff_hip.so (wd_gemm.hip, wd_gemmw.hip): the fp32 LDS image of an
+// Epilogue shared by every tap-gather GEMM kernel of libwdiff_hip.so (wd_gemm.hip, wd_gemm4.hip, wd_gemmw.hip, wd_gemmq.hip, wd_gemm_reduce.hip,
+// wd_gemm_exp.hip) and by wd_ff.hip: the fp32 LDS image of an
 // output tile -> bias / FiLM row vector / residual / activation / operand planes / fused GroupNorm statistics, or the split-K
 // partial store.  Replaces the elementwise tails of reference unet.py:660-669 (FiLM add, residual) and :128-136 (GEGLU).
 #pragma once
