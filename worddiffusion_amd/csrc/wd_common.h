@@ -68,20 +68,38 @@ __device__ __forceinline__ void wd_split4(const float4 v, uint2& hi, uint2& lo) 
                     wd_pack_bf16x2(v.z - __uint_as_float(h23 << 16), v.w - __uint_as_float(h23 & 0xffff0000u)));
 }
 
+// 1 / x as ONE v_rcp_f32 (1 ulp).  __fdividef is not that under this library's flags: hipcc expands it to the correctly rounded
+// division (2 x v_div_scale_f32, v_rcp_f32, four FMAs, v_div_fmas_f32, v_div_fixup_f32: ~10 VALU instructions per quotient).
+__device__ __forceinline__ float wd_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
 // x * sigmoid(x) on the hardware exp2 / rcp units (v_exp_f32, v_rcp_f32: 1 ulp each) - the IEEE expf + division form costs
-// ~25 VALU instructions per element, which made the SiLU the largest part of the GroupNorm-apply kernels' arithmetic
-__device__ __forceinline__ float wd_silu(float x) { return __fdividef(x, 1.0f + __expf(-x)); }
+// ~25 VALU instructions per element, which made the SiLU the largest part of the GroupNorm-apply kernels' arithmetic.
+// (x very negative: exp = inf, rcp = 0, the product -0, as the quotient gave.)
+__device__ __forceinline__ float wd_silu(float x) { return x * wd_rcp(1.0f + __expf(-x)); }
 // exact-erf GELU (unet.py:136 F.gelu default).  erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, the size of an fp32 ulp
-// of 1) on the hardware rcp / exp units: about a third of the instructions of libm's erff, which made this the largest
-// part of the GEGLU epilogue's arithmetic (40 gate values per thread and tile).
+// of 1) on the hardware rcp / exp units (wd_rcp of an argument >= 1, v_exp_f32): about a third of the instructions of libm's
+// erff, which made this the largest part of the GEGLU epilogue's arithmetic (40 gate values per thread and tile).
 __device__ __forceinline__ float wd_erf(float x) {
     const float ax = fabsf(x);
-    const float t = __fdividef(1.0f, 1.0f + 0.3275911f * ax);
+    const float t = wd_rcp(1.0f + 0.3275911f * ax);
     const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
     const float r = 1.0f - poly * __expf(-ax * ax);
     return copysignf(r, x);
 }
 __device__ __forceinline__ float wd_gelu_erf(float x) { return 0.5f * x * (1.0f + wd_erf(x * 0.70710678118654752440f)); }
+// the same expressions on two values at a time, element for element: hipcc issues the multiplies, adds and FMAs as v_pk_mul_f32 /
+// v_pk_add_f32 / v_pk_fma_f32 (rcp, exp and the sign transfer stay one per value)
+__device__ __forceinline__ wd_f32x2 wd_erf2(wd_f32x2 x) {
+    const wd_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
+    const wd_f32x2 d = 1.0f + 0.3275911f * ax;
+    const wd_f32x2 t = {wd_rcp(d.x), wd_rcp(d.y)};
+    const wd_f32x2 poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+    const wd_f32x2 s = -ax * ax;
+    const wd_f32x2 ex = {__expf(s.x), __expf(s.y)};
+    const wd_f32x2 r = 1.0f - poly * ex;
+    return wd_f32x2{copysignf(r.x, x.x), copysignf(r.y, x.y)};
+}
+__device__ __forceinline__ wd_f32x2 wd_gelu_erf2(wd_f32x2 x) { return 0.5f * x * (1.0f + wd_erf2(x * 0.70710678118654752440f)); }
 
 // 64-lane reductions on the DPP path (quad permutes + row rotates inside each row of 16 lanes, then one v_readlane per
 // row): ~10 VALU-rate instructions instead of six dependent ds_bpermute round trips through the LDS crossbar.

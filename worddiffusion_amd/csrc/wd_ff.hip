@@ -161,6 +161,20 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
             acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[i][0], w[0], acc[i], 0, 0, 0);
         }
     };
+    // the first product with the operands swapped: the A and B fragments of v_mfma_f32_16x16x32_bf16 have the same form (lane & 15 =
+    // row or column, lane >> 4 = k group), so the same registers serve, every dot product sums the same terms in the same order, and
+    // only the accumulator comes out transposed: lane (l15, lq), register r = hidden unit 4 lq + r of token 16 i + l15 - four
+    // K-neighbours of the second product in one lane
+    auto mfma12_t = [&](f32x4 (&acc)[4], const bf16x8 (&w)[NPL]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (NPL == 2) {
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], xa[i][NPL - 1], acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[NPL - 1], xa[i][0], acc[i], 0, 0, 0);
+            }
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], xa[i][0], acc[i], 0, 0, 0);
+        }
+    };
     constexpr int LDE = FC + 4;
     float* ep = reinterpret_cast<float*>(smem);   // [FBM][LDE] fp32 image of a finished product (over s_a and 1 KB of s_h)
     auto ksum_to_image = [&]() {  // the two K-halves of acc2 summed in a fixed order through the fp32 image (callers: barrier first)
@@ -693,29 +707,32 @@ __global__ void __launch_bounds__(FNT, 1) wd_ff_kernel(const wd_ff_args a) {
 #pragma unroll
         for (int g = 0; g < 20; ++g) {
             if ((g & 1) == 0) read_frags(s_a + (g >> 2) * SLAB, (g >> 1) & 1);
-            if (g & 1) mfma12(ag, ring[g % FRING]);
-            else mfma12(ax, ring[g % FRING]);
+            if (g & 1) mfma12_t(ag, ring[g % FRING]);
+            else mfma12_t(ax, ring[g % FRING]);
             // the slot is free: group g + FRING of this chunk, or of the next
             if (g + FRING < FGRP) issue(g % FRING, g + FRING, j);
             else issue(g % FRING, g + FRING - FGRP, j + 1);
             __builtin_amdgcn_sched_barrier(0);  // (else hipcc sinks the loads to just before their use: no ring left)
         }
-        // ---- GEGLU on the accumulators (x and gate of an element share lane and register), h -> LDS as split-bf16 planes
+        // ---- GEGLU on the transposed accumulators (x and gate of an element share lane and register; a lane's four registers are
+        // the hidden units 4 lq .. 4 lq + 3 of one token), two values at a time, h -> LDS as split-bf16 planes: the four units are
+        // eight contiguous bytes of the token's K row in each plane
         {
-            const int hcol = (j * 8 + wave) * 32 + l15;            // bias index of the x unit; its gate: + 16
-            const float bx = s_b1[hcol], bg = s_b1[hcol + 16];
-            const int slab = wave >> 2, ch = (wave & 3) * 2 + (l15 >> 3), e = (l15 & 7) * 2;
+            const float* pb = s_b1 + (j * 8 + wave) * 32 + 4 * lq;  // biases of the x units; their gates: + 16
+            const float4 bx = *reinterpret_cast<const float4*>(pb), bg = *reinterpret_cast<const float4*>(pb + 16);
+            const wd_f32x2 bx01 = {bx.x, bx.y}, bx23 = {bx.z, bx.w}, bg01 = {bg.x, bg.y}, bg23 = {bg.z, bg.w};
+            char* hq = hbuf + (wave >> 2) * SLAB + (lq & 1) * 8;
+            const int ch = (wave & 3) * 2 + (lq >> 1);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float h = (ax[i][r] + bx) * wd_gelu_erf(ag[i][r] + bg);
-                    uint32_t hb, lb;
-                    wd_split1(h, hb, lb);
-                    char* p = hbuf + slab * SLAB + f_lds_off(i * 16 + lq * 4 + r, ch) + e;
-                    *reinterpret_cast<unsigned short*>(p) = (unsigned short)hb;
-                    if (NPL == 2) *reinterpret_cast<unsigned short*>(p + FBM * 128) = (unsigned short)lb;
-                }
+            for (int i = 0; i < 4; ++i) {
+                const wd_f32x2 h01 = (wd_f32x2{ax[i][0], ax[i][1]} + bx01) * wd_gelu_erf2(wd_f32x2{ag[i][0], ag[i][1]} + bg01);
+                const wd_f32x2 h23 = (wd_f32x2{ax[i][2], ax[i][3]} + bx23) * wd_gelu_erf2(wd_f32x2{ag[i][2], ag[i][3]} + bg23);
+                uint2 hb, lb;
+                wd_split4(make_float4(h01.x, h01.y, h23.x, h23.y), hb, lb);
+                char* p = hq + f_lds_off(i * 16 + l15, ch);
+                *reinterpret_cast<uint2*>(p) = hb;
+                if (NPL == 2) *reinterpret_cast<uint2*>(p + FBM * 128) = lb;
+            }
         }
         __syncthreads();  // h(j) complete; (the other h image was last read before the previous barrier)
         // ---- second product: this wave's K-half (two k-steps of the chunk) x its 80 output columns

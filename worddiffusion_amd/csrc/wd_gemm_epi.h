@@ -247,10 +247,9 @@ __device__ __forceinline__ void wd_epilogue_from_image(const wd_gemm_args& a, fl
                 }
                 if (geglu) {  // columns [0, BN/2) of the tile are x, [BN/2, BN) their gates (weights packed that way)
                     const float4 g = *reinterpret_cast<const float4*>(ep + row * LDE + c + BN / 2);
-                    v.x = (v.x + bx.x) * wd_gelu_erf(g.x + bg.x);
-                    v.y = (v.y + bx.y) * wd_gelu_erf(g.y + bg.y);
-                    v.z = (v.z + bx.z) * wd_gelu_erf(g.z + bg.z);
-                    v.w = (v.w + bx.w) * wd_gelu_erf(g.w + bg.w);
+                    const wd_f32x2 h01 = (wd_f32x2{v.x, v.y} + wd_f32x2{bx.x, bx.y}) * wd_gelu_erf2(wd_f32x2{g.x, g.y} + wd_f32x2{bg.x, bg.y});
+                    const wd_f32x2 h23 = (wd_f32x2{v.z, v.w} + wd_f32x2{bx.z, bx.w}) * wd_gelu_erf2(wd_f32x2{g.z, g.w} + wd_f32x2{bg.z, bg.w});
+                    v = make_float4(h01.x, h01.y, h23.x, h23.y);
                 } else {
                     v.x += bx.x; v.y += bx.y; v.z += bx.z; v.w += bx.w;
                 }
