@@ -9,7 +9,13 @@ An entry is (section, function name, ``what``, form).  The form is a readable st
                 computed source rows), a32 (GroupNorm while staging), ln, gn, stat (GroupNorm statistics), f32 / planes (outputs)
   wd_ff_fused   front / no front, how proj_out rides along (folded / proj_out / none), whether tok2 is written, stat
   anything else the empty string: the function and its ``what`` are the form
-No address, row count, pitch or byte count enters."""
+No address, row count, pitch or byte count enters.
+
+``train_signature(engine, P)`` is the same for a ``TrainPlan`` of ``engine.plan_train``: the sections are ``cond``, ``step`` and ``bwd``
+(``P.bwd_cuts`` and ``P.bwd_segments`` are op indices and arena offsets: left out), with two more forms in the backward list:
+  wd_dw         ntaps, hw_out, hw_src, npass, accumulate and the token slices the library will take: the args carry nslice = 0,
+                so that is wd_dw_slices(m, n, c, ntaps), and with it the reduction path
+  wd_dw_group   the number of layers in the launch, ntaps, hw_out, hw_src and wd_dw_group_slices(m, n, c, ntaps, items)"""
 import ctypes as C
 
 from worddiffusion_amd import _native as N
@@ -39,20 +45,45 @@ def ff_form(a) -> str:
     return ", ".join(flags)
 
 
-def signature(engine, P) -> tuple:
+def dw_form(lib, a) -> str:
+    assert a.nslice == 0, "the plan fixes the slice count: the signature would have to say which"
+    return (f"ntaps={a.ntaps} hw_out={a.hw_out} hw_src={a.hw_src} npass={a.npass} accumulate={a.accumulate} "
+            f"slices={lib.wd_dw_slices(a.m, a.n, a.c, a.ntaps)}")
+
+
+def dw_group_form(lib, a, nitems) -> str:
+    assert a.nslice == 0, "the plan fixes the slice count: the signature would have to say which"
+    return (f"items={nitems} ntaps={a.ntaps} hw_out={a.hw_out} hw_src={a.hw_src} "
+            f"slices={lib.wd_dw_group_slices(a.m, a.n, a.c, a.ntaps, nitems)}")
+
+
+def _signature(engine, P, sections) -> tuple:
     lib = engine.lib
     sig = []
-    for section in ("cond", "step"):
+    for section in sections:
         for fn, args, what in getattr(P, section):
             name = fn.__name__
             if name == "wd_gemm":
                 form = gemm_form(lib, _struct(args))
             elif name == "wd_ff_fused":
                 form = ff_form(_struct(args))
+            elif name == "wd_dw":
+                form = dw_form(lib, _struct(args))
+            elif name == "wd_dw_group":
+                form = dw_group_form(lib, _struct(args), int(args[3]))
             else:
                 form = ""
             sig.append((section, name, what, form))
     return tuple(sig)
+
+
+def signature(engine, P) -> tuple:
+    return _signature(engine, P, ("cond", "step"))
+
+
+def train_signature(engine, P) -> tuple:
+    """``signature`` of a TrainPlan: forward lists and the backward list (the inference planner emits neither wd_dw form)."""
+    return _signature(engine, P, ("cond", "step", "bwd"))
 
 
 def families(sig) -> dict:
@@ -76,7 +107,7 @@ def _keyed(sig) -> dict:
 
 def _label(key) -> str:
     section, what, n = key
-    return ("cond: " if section == "cond" else "") + what + (f" #{n}" if n > 1 else "")
+    return {"cond": "cond: ", "bwd": "bwd: "}.get(section, "") + what + (f" #{n}" if n > 1 else "")
 
 
 def _names(keys) -> str:
@@ -130,12 +161,19 @@ def read_scan(path) -> dict:
 
 
 def release(engine):
-    """Drops every plan the engine holds and returns their buffers to the device (a B = 48 plan holds about 1 GB)."""
+    """Drops every plan the engine holds and returns their buffers to the device (a B = 48 plan holds about 1 GB).  A train
+    engine also lets go of its training plans, of the plan the last forward left for ``backward`` and of the scratch sized for
+    them; the gradient arena stays, so a ``param.grad`` handed out earlier stays valid."""
     import gc
 
     import torch
     engine._plans.clear()
     engine._cur_plan = None
+    if hasattr(engine, "_tplans"):
+        engine._tplans.clear()
+        engine._live = None
+        engine._scr = {k: v for k, v in engine._scr.items() if isinstance(k, tuple)}  # (as plan_train does between two shapes)
+        engine._cs_scratch = None
     gc.collect()
     torch.cuda.empty_cache()
 
@@ -146,5 +184,13 @@ def signature_at(engine, B, phosc_len=0, h=8, w=32, ctx_len=10, planner=None) ->
     (h, w of the images) of a VAE engine; without it the forward's ``engine.plan(B, h, w, ctx_len, phosc_len)``."""
     engine.refresh_weights()
     sig = signature(engine, planner(B, h, w) if planner is not None else engine.plan(B, h, w, ctx_len, phosc_len))
+    release(engine)
+    return sig
+
+
+def train_signature_at(engine, B, phosc_len=0, h=8, w=32, ctx_len=10) -> tuple:
+    """``train_signature`` of ``engine.plan_train(B, h, w, ctx_len, phosc_len)`` (a TrainEngine); plans only, the plan is released."""
+    engine.refresh_weights()
+    sig = train_signature(engine, engine.plan_train(B, h, w, ctx_len, phosc_len))
     release(engine)
     return sig

@@ -1,6 +1,7 @@
 """The float64 training reference the gradient tests share (tests/test_gpu_training.py, tests/test_gpu_shapes.py): one case's inputs,
 the oracle's forward -> MSE -> autograd in float64 on the CPU, the comparison with its bars, and the model -> MSELoss -> backward
-call of the HIP path.  Every function takes the model's config dict."""
+call of the HIP path.  Every function takes the model's config dict.  ``RunningReference`` is the same reference for the first B
+samples of one pool at many B (tests/test_gpu_train_thresholds.py): per-sample gradients summed in float64."""
 import functools
 
 import numpy as np
@@ -36,7 +37,12 @@ def reference64(cfg, variant, B, hw, phosc_len, seeds, noised=False):
 def _reference64(cfg_items, variant, B, hw, phosc_len, seeds, noised):
     cfg = dict(cfg_items)
     x, inp, eps = case_inputs(cfg, B, hw, phosc_len, seeds, noised)
-    sd = {k: torch.from_numpy(synthetic_tensor(k, s, seeds[0])).double().requires_grad_(True)
+    return batched_reference64(cfg, variant, x, inp, eps, phosc_len, seeds[0])
+
+
+def batched_reference64(cfg, variant, x, inp, eps, phosc_len, seed_w):
+    """One batched float64 forward -> mse_loss -> backward over the given inputs: (pred, loss, {name: grad})."""
+    sd = {k: torch.from_numpy(synthetic_tensor(k, s, seed_w)).double().requires_grad_(True)
           for k, s in U.state_dict_shapes(cfg, variant)}
     orc = U.UNetOracle(cfg, sd, variant, phosc_len > 0)
     pred = orc(x.double(), inp["t"], inp["context"], inp["y"], inp.get("phosc"))
@@ -65,6 +71,80 @@ def check_against_reference(pred, loss, grads, ref, label):
             bad.append((k, err, rn))
     print(f"{label}: worst per-sample prediction error {worst_pred:.2e}, worst relative gradient error {worst[1]:.2e} ({worst[0]})")
     assert not bad, f"{len(bad)} gradients off the reference: {bad[:8]}"
+
+
+def misses_the_gradient_bar(g, r) -> bool:
+    """The per-parameter gradient bar of ``check_against_reference``, for one float64 pair (gradient, reference)."""
+    return not float((g - r).norm()) < 2e-4 * float(r.norm()) + 1e-7
+
+
+class RunningReference:
+    """The float64 reference of ``reference64`` for the first B samples of one pool, for many B at the cost of one pass over the pool.
+
+    The oracle has no operation that couples samples (GroupNorm is per sample, LayerNorm per token, dropout is off), so with
+    S_b = sum((pred_b - eps_b)^2) and n elements per sample
+        grad(mse loss of the first B samples) = (sum over b < B of grad S_b) / (B n)
+    and the loss is the same expression in S_b itself.  Held: ONE float64 copy of the summed parameter gradients G (346 MB for
+    FULL base), the per-sample S_b and predictions, the count of samples folded in, and the gradient of the last advance (what
+    ``drop_one_share`` leaves out).  tests/test_train_running_ref_host.py holds ``at`` to the batched ``reference64`` construction."""
+    CHUNK = 16  # samples per oracle backward
+
+    def __init__(self, cfg, variant, pool_inputs, pool_eps, phosc_len, seed_w=0):
+        self.variant, self.inp, self.eps, self.phosc_len = variant, pool_inputs, pool_eps.double(), phosc_len
+        self.sd = {k: torch.from_numpy(synthetic_tensor(k, s, seed_w)).double().requires_grad_(True)
+                   for k, s in U.state_dict_shapes(cfg, variant)}
+        self.orc = U.UNetOracle(cfg, self.sd, variant, phosc_len > 0)
+        self.n = int(self.eps[0].numel())
+        self._reset()
+
+    def _reset(self):
+        self.count, self.S, self.pred = 0, [], []
+        self.G = None      # {name: sum over the samples folded in of grad S_b}, the parameters the loss reaches
+        self.last = None   # (first sample, end, {name: gradient}) of the last advance
+
+    def _advance(self, lo, hi):
+        s, inp = slice(lo, hi), self.inp
+        pred = self.orc(inp["x"][s].double(), inp["t"][s], inp["context"][s], inp["y"][s],
+                        inp["phosc"][s] if self.phosc_len else None)
+        S = ((pred - self.eps[s]) ** 2).flatten(1).sum(1)
+        names = list(self.sd)
+        got = torch.autograd.grad(S.sum(), [self.sd[k] for k in names], allow_unused=True)
+        g = {k: v for k, v in zip(names, got) if v is not None}
+        if self.G is None:
+            self.G = {k: v.clone() for k, v in g.items()}
+        else:
+            assert set(g) == set(self.G)
+            for k, v in g.items():
+                self.G[k] += v
+        self.S += [float(v) for v in S.detach()]
+        self.pred += list(pred.detach())
+        self.count, self.last = hi, (lo, hi, g)
+
+    def at(self, B):
+        """(pred[:B], loss, {name: grad}) of the mse loss over the first B samples: the tuple ``check_against_reference`` takes."""
+        assert 1 <= B <= self.eps.shape[0]
+        if B < self.count:
+            print(f"[running reference] {self.variant}: B = {B} after B = {self.count}: starting over from zero")
+            self._reset()
+        while self.count < B:
+            self._advance(self.count, min(B, self.count + self.CHUNK))
+        scale = 1.0 / (B * self.n)
+        return torch.stack(self.pred[:B]), sum(self.S[:B]) * scale, {k: v * scale for k, v in self.G.items()}
+
+    def drop_one_share(self):
+        """After an ``at(B)`` that advanced by exactly one sample: (parameters whose reference WITHOUT that sample's contribution,
+        (G - g_last) / (B n), misses the gradient bar against the reference, parameters asked) over those with reference norm
+        > 1e-6 - the teeth of the bar at this B.  None after any other advance."""
+        if self.last is None or self.last[1] != self.count or self.last[1] - self.last[0] != 1:
+            return None
+        scale = 1.0 / (self.count * self.n)
+        asked = broken = 0
+        for k, G in self.G.items():
+            ref = G * scale
+            if float(ref.norm()) > 1e-6:
+                asked += 1
+                broken += misses_the_gradient_bar((G - self.last[2][k]) * scale, ref)
+        return broken, asked
 
 
 def train_model(cfg, variant, phosc_on, seed):

@@ -1,14 +1,17 @@
 """Host side of the batch-threshold tests: the tables of tests/test_gpu_batch_thresholds.py are the batch sizes the committed scans
 list (profiles/plan_thresholds_<variant>.txt, written by tools/plan_thresholds.py), every one of them is run on both sides, and
 ``signature`` / ``diff`` of tests/_plan_sig.py say what they should on two small hand-made op lists (nothing is launched: the
-library only answers wd_gemm_check)."""
+library only answers wd_gemm_check).  The same for the training step: the tables of tests/test_gpu_train_thresholds.py against
+profiles/plan_thresholds_train_<variant>.txt, and ``train_signature`` on a hand-made backward list (wd_dw_slices and
+wd_dw_group_slices are host functions)."""
 import ctypes
 import types
 
 import pytest
 
 from tests import test_gpu_batch_thresholds as G
-from tests._plan_sig import diff, read_scan, signature
+from tests import test_gpu_train_thresholds as GT
+from tests._plan_sig import diff, read_scan, signature, train_signature
 from worddiffusion_amd import _native as N
 
 SCANNED_TO = {"base": 260, "phosc": 130}  # the top of each committed scan
@@ -49,6 +52,50 @@ def test_the_issue_table_is_in_the_base_scan():
     assert {32, 48, 64, 129, 192, 256} <= set(scan)
     assert "K_GEMMQ" in scan[32] and "K_GEMMQ" in scan[129] and "K_GEMMW" in scan[64] and "K_GEMMW" in scan[256]
     assert "+ wd_ff_fused x3" in scan[48] and "+ wd_ff_fused x1" in scan[192]
+
+
+# ---- the training step's tables
+@pytest.mark.parametrize("variant", sorted(GT.SCANNED_TO))
+def test_the_train_tables_are_the_committed_scans(variant):
+    assert GT.SCANNED_TO == {"base": 72, "phosc": 32}  # the ranges the training scans cover
+    with open(GT.scan_file(variant)) as f:
+        head = f.readline()
+    assert head.startswith("#") and f"FULL {variant} training step," in head and f"B = 1..{GT.SCANNED_TO[variant]};" in head, head
+    scan = read_scan(GT.scan_file(variant))
+    assert list(scan) == sorted(scan) and min(scan) >= 2 and max(scan) <= GT.SCANNED_TO[variant]
+    assert GT.THRESHOLDS[variant] == tuple(scan), "re-run tools/plan_thresholds.py --variant train-* and copy its B column into THRESHOLDS"
+    assert all(text.strip() and text != "same ops in another order" for text in scan.values())
+
+
+@pytest.mark.parametrize("variant", sorted(GT.SCANNED_TO))
+def test_no_train_threshold_is_dropped_from_the_cases(variant):
+    """Every listed b is a case of the cross-threshold test; b - 1, b and the scan's upper end are cases of the gradient test,
+    each once and in ascending order (the running reference then passes over the pool once)."""
+    scan = read_scan(GT.scan_file(variant))
+    assert [b for v, b in GT.THRESHOLD_CASES if v == variant] == list(scan)
+    ran = [B for v, B in GT.GRADIENT_CASES if v == variant]
+    assert ran == sorted(set(ran)) and set(ran) == {B for b in scan for B in (b - 1, b)} | {GT.SCANNED_TO[variant]}
+    names = {f.__name__: f for f in (GT.test_training_gradients_on_both_sides_of_a_threshold,
+                                     GT.test_a_sample_keeps_its_prediction_across_a_threshold)}
+    for name, cases in (("test_training_gradients_on_both_sides_of_a_threshold", GT.GRADIENT_CASES),
+                        ("test_a_sample_keeps_its_prediction_across_a_threshold", GT.THRESHOLD_CASES)):
+        marks = [mk for mk in names[name].pytestmark if mk.name == "parametrize"]
+        assert len(marks) == 1 and list(marks[0].args[1]) == cases, name
+    assert all(mk.name != "skip" and mk.name != "xfail" for f in names.values() for mk in f.pytestmark)
+
+
+def test_the_train_scans_show_what_the_training_planner_decides():
+    """The forms ``TrainEngine._dw_form`` and the library decide by the batch are among the differences the scans found: slice
+    counts of both wd_dw forms, K cuts of data-gradient GEMMs, and at B = 32 - the first batch whose 320 word tokens fill 64-row
+    units - the word encoder's weight gradients leaving transposed planes + wd_gemm for wd_dw."""
+    base, phosc = read_scan(GT.scan_file("base")), read_scan(GT.scan_file("phosc"))
+    for scan in (base, phosc):
+        assert any("wd_dw ntaps=" in t and "slices=" in t for t in scan.values())
+        assert any("wd_dw_group items=" in t for t in scan.values())
+        assert any("bwd: " in t and ":dX" in t and "ksplit=" in t for t in scan.values())
+    assert "bwd: cross.kv:dW0, bwd: word_emb.qkv:dW0: wd_gemm " in base[32] and "-> wd_dw ntaps=1 hw_out=64 hw_src=64" in base[32]
+    assert "- wd_transpose_planes x2: bwd: cross.kv:T(x0), bwd: word_emb.qkv:T(x0)" in base[32]
+    assert "+ wd_transpose_planes x2: bwd: cross.kv:T(x0), bwd: word_emb.qkv:T(x0)" in base[33]
 
 
 # ---- signature / diff on hand-made op lists
@@ -115,6 +162,48 @@ def test_signature_of_a_hand_made_plan():
         ("cond", "wd_embed_tokens", "word_emb.embedding", ""), qkv,
         ("step", "wd_gemm", "mid.0.conv1", CONV_WHOLE_K),
         ("step", "wd_ff_fused", "mid.1.tb0.ff + proj_out (fused)", "no front, proj_out folded, stat"))
+
+
+def _dw(m, n, c, ntaps, hw_out, hw_src, **fields):
+    a = N.WdDwArgs()
+    a.d_hi = a.d_lo = a.x_hi = a.x_lo = a.grad = a.ws = _P
+    a.m, a.n, a.c, a.ntaps, a.hw_out, a.hw_src, a.npass = m, n, c, ntaps, hw_out, hw_src, 3
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_train_signature_of_a_hand_made_backward_list():
+    """cond, step and bwd, with the two wd_dw forms: the slice count is the library's for the op's (m, n, c, ntaps) - the args carry
+    nslice = 0 -, no row count or address enters, and ``signature`` of the same plan is its forward part."""
+    lib = N.lib()
+    (eng, P), _ = _plans()
+    items = (N.WdDwItem * 5)()
+
+    def bwd(B, base):
+        return [(lib.wd_dout_prep, (), "mid.0.conv1:prep(dout)"),
+                (lib.wd_dw, (ctypes.byref(_dw(B * 64, 640, 640, 9, 64, 64, gather=base, grad=base + 64)),), "mid.0.conv1:dW0"),
+                (lib.wd_dw_group, (ctypes.byref(_dw(B * 64, 640, 640, 1, 64, 64, ws=base)), ctypes.cast(items, ctypes.c_void_p), base, 5),
+                 "dW group: a, b, c, d, e")]
+
+    P.bwd, P.bwd_cuts, P.bwd_segments = bwd(8, _P), [(1, 0)], [(0, 1, 0, 64)]
+    sig = train_signature(eng, P)
+    assert sig[:len(signature(eng, P))] == signature(eng, P) and len(sig) == len(signature(eng, P)) + 3
+    s9, s1g = lib.wd_dw_slices(512, 640, 640, 9), lib.wd_dw_group_slices(512, 640, 640, 1, 5)
+    assert s9 >= 1 and s1g >= 1
+    assert sig[-3:] == (("bwd", "wd_dout_prep", "mid.0.conv1:prep(dout)", ""),
+                        ("bwd", "wd_dw", "mid.0.conv1:dW0", f"ntaps=9 hw_out=64 hw_src=64 npass=3 accumulate=0 slices={s9}"),
+                        ("bwd", "wd_dw_group", "dW group: a, b, c, d, e", f"items=5 ntaps=1 hw_out=64 hw_src=64 slices={s1g}"))
+    # other addresses, cuts and segments: the same signature; another batch: only what the library decides by it
+    P.bwd, P.bwd_cuts, P.bwd_segments = bwd(8, _P << 4), [(2, 1)], [(0, 2, 0, 128)]
+    assert train_signature(eng, P) == sig and hash(train_signature(eng, P)) == hash(sig)
+    P.bwd = bwd(64, _P)
+    big = train_signature(eng, P)
+    t9, t1g = lib.wd_dw_slices(4096, 640, 640, 9), lib.wd_dw_group_slices(4096, 640, 640, 1, 5)
+    assert (big == sig) == ((s9, s1g) == (t9, t1g))
+    if t9 != s9:
+        assert f"bwd: mid.0.conv1:dW0: wd_dw ntaps=9 hw_out=64 hw_src=64 npass=3 accumulate=0 slices={s9} -> wd_dw ntaps=9 hw_out=64 " \
+               f"hw_src=64 npass=3 accumulate=0 slices={t9}" in diff(sig, big)
 
 
 def test_signature_holds_nothing_that_only_grows_with_the_batch():

@@ -18,7 +18,14 @@ most ``AutoencoderKL.ENCODE_CHUNK`` images.
     python tools/plan_thresholds.py --variant vae-enc --config 64,64,128,128:1 --latent 6x26 --max-batch 16 \\
         --out profiles/plan_thresholds_vae_enc_6x26.txt
 
-tests/test_plan_thresholds_host.py ties the tables of tests/test_gpu_batch_thresholds.py to the two committed UNet files,
+``--variant train-base | train-phosc``: the training step of the same model and inputs, ``TrainEngine.plan_train`` - its forward
+lists and its backward list (``train_signature_at``).
+
+    python tools/plan_thresholds.py --variant train-base --max-batch 72 --out profiles/plan_thresholds_train_base.txt
+    python tools/plan_thresholds.py --variant train-phosc --max-batch 32 --out profiles/plan_thresholds_train_phosc.txt
+
+tests/test_plan_thresholds_host.py ties the tables of tests/test_gpu_batch_thresholds.py to the two committed UNet files and
+those of tests/test_gpu_train_thresholds.py to the two training files,
 tests/test_vae_thresholds_host.py those of tests/_vae_cases.py to the VAE files (``scan_command`` there gives each file's command
 line): a pull request that moves a planner rule re-runs the scan and the tests then cover the new edges."""
 import argparse
@@ -30,14 +37,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import _common as T  # noqa: E402
-from tests._plan_sig import diff, signature_at  # noqa: E402
+from tests._plan_sig import diff, signature_at, train_signature_at  # noqa: E402
 from worddiffusion_amd import UNetModel, UNetModelPhosc  # noqa: E402
 from worddiffusion_amd.synthetic import fill_module_  # noqa: E402
 
 PHOSC_LEN = 769
 
+scan_at = signature_at
 ap = argparse.ArgumentParser()
-ap.add_argument("--variant", default="base", choices=["base", "phosc", "vae-dec", "vae-enc"])
+ap.add_argument("--variant", default="base", choices=["base", "phosc", "train-base", "train-phosc", "vae-dec", "vae-enc"])
 ap.add_argument("--min-batch", type=int, default=1)
 ap.add_argument("--max-batch", type=int, required=True)
 ap.add_argument("--config", default="128,256,512,512:2", help="vae-*: block_out_channels ':' layers_per_block")
@@ -61,20 +69,26 @@ if a.variant.startswith("vae-"):
     what = (f"VAE {'encoder' if enc else 'decoder'} block_out_channels={boc} layers_per_block={lpb}, {lh}x{lw} latents "
             f"({lh << f}x{lw << f} images)")
 else:
-    phosc_len = PHOSC_LEN if a.variant == "phosc" else 0
-    cls = UNetModel if a.variant == "base" else UNetModelPhosc
-    m = fill_module_(cls(args=T.make_args(device="cuda:0", phosc=1 if phosc_len else 0), **T.FULL), 1).to("cuda:0").eval()
-    eng = m.engine
+    train = a.variant.startswith("train-")
+    variant = a.variant[len("train-"):] if train else a.variant
+    phosc_len = PHOSC_LEN if variant == "phosc" else 0
+    cls = UNetModel if variant == "base" else UNetModelPhosc
+    m = fill_module_(cls(args=T.make_args(device="cuda:0", phosc=1 if phosc_len else 0), **T.FULL), 1).to("cuda:0")
+    m = m.train() if train else m.eval()
+    eng = m.train_engine if train else m.engine
+    if train:
+        scan_at = train_signature_at
     kw = dict(phosc_len=phosc_len)
-    what = f"FULL {a.variant}, 8x32 latents, 10 context tokens" + (f" + {phosc_len} PHOSC ints" if phosc_len else "")
+    what = (f"FULL {variant}{' training step' if train else ''}, 8x32 latents, 10 context tokens" +
+            (f" + {phosc_len} PHOSC ints" if phosc_len else ""))
 
 lines = [f"# plan thresholds: {what}, B = {a.min_batch}..{a.max_batch}; a line per B whose plan differs from that of B - 1 "
          "(tools/plan_thresholds.py)"]
 print(lines[0], flush=True)
 t0 = time.time()
-prev = signature_at(eng, a.min_batch - 1, **kw) if a.min_batch > 1 else None
+prev = scan_at(eng, a.min_batch - 1, **kw) if a.min_batch > 1 else None
 for B in range(a.min_batch, a.max_batch + 1):
-    sig = signature_at(eng, B, **kw)
+    sig = scan_at(eng, B, **kw)
     if prev is not None and sig != prev:
         lines.append(f"B={B}: {diff(prev, sig)}")
         print(lines[-1], flush=True)
