@@ -371,10 +371,12 @@ class _HipUNetStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, timesteps, context, y, phosc, anchor, writer_keep=None):
         eng = model.train_engine
-        ctx.eng = eng
-        return eng.forward_train(x.float(), timesteps, context, y, phosc, writer_keep=writer_keep).clone()
+        out = eng.forward_train(x.float(), timesteps, context, y, phosc, writer_keep=writer_keep).clone()
+        # the plan keeps the intermediates of this forward only until the next one: its identity is checked in backward
+        ctx.eng, ctx.fwd = eng, eng.last_forward()
+        return out
 
     @staticmethod
     def backward(ctx, gout):
-        ctx.eng.backward(gout.contiguous().float())
+        ctx.eng.backward(gout.contiguous().float(), forward=ctx.fwd)
         return None, None, None, None, None, None, torch.zeros_like(ctx.eng.model._anchor), None

@@ -54,6 +54,9 @@ class TrainPlan(Plan):
         # writer dropout (plan_train label_drop): the decision of the last forward, uint8 [B], written by wd_label_rows_keep; a
         # drawn one is keyed by a wd_dropout of its own in ``dropouts`` (same seed, same row base, the tag of dropout.label_tag)
         self.writer_keep: Optional[torch.Tensor] = None
+        # the engine's count of training forwards when this plan's intermediates were last written (TrainEngine.claim_forward):
+        # with the plan object, the identity of a forward that ``TrainEngine.backward`` checks
+        self.serial = 0
 
     def set_dropout_seed(self, seed: int):
         for d in self.dropouts:
@@ -145,6 +148,8 @@ class TrainEngine(UNetEngine):
         self.dw_group_max = int(os.environ.get("WDIFF_DW_GROUP", "8"))  # single-tap layers of one shape per grouped launch (1: off)
         self._bs: Optional[_Build] = None            # the plan build in progress
         self._tplans: Dict[tuple, TrainPlan] = {}
+        self._live: Optional[TrainPlan] = None       # the plan of the latest training forward: what ``backward`` differentiates
+        self._serial = 0                             # training forwards so far (TrainPlan.serial)
         self._grad: Dict[int, torch.Tensor] = {}     # id(param) -> gradient buffer (possibly a view into a group)
         self._params: Dict[int, torch.nn.Parameter] = {}
         self._btabs: Dict[tuple, GatherTable] = {}
@@ -1239,14 +1244,62 @@ class TrainEngine(UNetEngine):
             P.set_row_base(self.dropout_row_base)
             self.dropout_row_base += B
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.claim_forward(P)
         P.run_step(stream)
-        self._live = P
         return P.out
 
-    def backward(self, dout: torch.Tensor, assign: bool = True):
+    # One training shape is live per engine (plan_train), and a plan keeps the intermediates of ONE forward.  A forward is
+    # therefore identified by (plan, serial); whoever is about to overwrite a plan's intermediates says so first.
+    def claim_forward(self, P: TrainPlan) -> tuple:
+        """Called by whoever is about to run ``P.step`` (``forward_train``, ``TrainStep``): the plan becomes the one ``backward``
+        differentiates and every earlier forward's identity goes stale.  Returns the new identity (``last_forward``)."""
+        self._serial += 1
+        P.serial = self._serial
+        self._live = P
+        return (P, P.serial)
+
+    def last_forward(self) -> Optional[tuple]:
+        """The identity of the latest training forward, (plan, serial), for ``backward(forward=...)``; None before the first."""
+        return None if self._live is None else (self._live, self._live.serial)
+
+    def holds_plan(self, P: Optional[TrainPlan]) -> bool:
+        """Whether ``P`` is still a plan of this engine.  False once a plan of another key was built (or the precision changed):
+        the shared scratch ``P``'s launches point into is released then, so ``P`` must never run again."""
+        return P is not None and any(q is P for q in self._tplans.values())
+
+    def _check_forward(self, forward: tuple) -> TrainPlan:
+        P, serial = forward
+        what = "a later forward on this model overwrote the activations this backward needs"
+        if not self.holds_plan(P):
+            what += " (it ran at another shape or precision, which released this forward's training plan)"
+        elif self._live is P and P.serial == serial:
+            return P
+        raise RuntimeError(what + ": the HIP training path keeps the intermediates of one forward per model.  Run one forward per "
+                           "backward, and any other forward in between under torch.no_grad() or model.eval() (the inference "
+                           "engine, which leaves the training plan alone)")
+
+    def backward(self, dout: torch.Tensor, assign: bool = True, forward: Optional[tuple] = None):
         """Runs the backward list for d loss / d out (NCHW) and points ``param.grad`` at the gradient buffers (adding to
-        a ``.grad`` the caller kept, like autograd's accumulation)."""
-        P = self._live
+        a ``.grad`` the caller kept, like autograd's accumulation).
+
+        forward: the identity of the forward to differentiate, as ``last_forward()`` returned it right after that forward (the
+        autograd node of ``model(...)`` passes its own).  Raises a RuntimeError, before anything is copied, launched or assigned,
+        when that forward's plan was released or a later forward overwrote its intermediates.  None: the latest forward.
+
+        A second backward through one forward (``loss.backward(retain_graph=True)`` twice) is valid and repeats the first bit for
+        bit, so with ``assign`` the gradients end up exactly doubled, as autograd's accumulation would leave them: the backward
+        list never writes a buffer the forward saved (operand planes, pre-activations, GroupNorm statistics, K | V, attention
+        outputs are only read).  Every buffer it writes is its own - ``P.dout``, the activation gradients, whose first writer in list
+        order overwrites and later ones add (``_gacc`` / ``Dx.acc``), the parameter gradients (``_pacc``, the same rule) - or shared
+        scratch (``dpl``, ``doutT``, ``xT``, ``colpart``, ``attn_bwd``, the workspace) that is refilled before each read; the dropout
+        masks are re-derived from the plan's seed and device row base, which only a forward changes."""
+        if forward is not None:
+            P = self._check_forward(forward)
+        elif not self.holds_plan(self._live):
+            raise RuntimeError("backward without a training forward: forward_train has not run on this engine, or the plan of "
+                               "its latest forward was released since (a plan of another key, a change of precision)")
+        else:
+            P = self._live
         kept = []
         if assign:
             for k, p in self._params.items():

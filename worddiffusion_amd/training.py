@@ -108,6 +108,7 @@ class TrainStep:
         self.eng = model.train_engine
         self.step_index = 0
         self._key = None
+        self._P = None
         self._graph = None
         self.pg = process_group
         self.world, self.rank = 1, 0
@@ -271,10 +272,14 @@ class TrainStep:
         B, _, H, W = latents.shape
         phosc_len = 0 if phoscLabels is None else phoscLabels.shape[1]
         key = (B, H, W, text_features.shape[1], phosc_len, str(dev))
-        if key != self._key:
+        # the engine keeps one training plan: anything else that trains this model at another shape in between (model(...) under
+        # autograd, a second TrainStep) released the scratch this step's plan and captured graphs point into.  Then the plan is
+        # built and captured again; nothing of the old one runs (``_prepare`` only destroys its graphs, a host-side call).
+        if key != self._key or not self.eng.holds_plan(self._P):
             self._prepare(B, H, W, text_features.shape[1], dev, phosc_len)
             self._key = key
         lib, P = self.lib, self._P
+        self.eng.claim_forward(P)  # this call overwrites the plan's intermediates: a pending backward of model(...) is refused
         if check:  # out-of-range ids raise here instead of faulting a kernel (device tensors: one small sync; a loader that has
             self.eng.check_ids(text_features, labels, phoscLabels)  # checked its host tensors passes check=False)
             if t is not None and not t.is_cuda:
