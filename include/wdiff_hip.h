@@ -1015,6 +1015,65 @@ int wd_pool2x2_sum(const float* in, int batch, int h, int w, int c, float* out, 
 int wd_embedding_bwd(const void* ids, int ids_are_i64, int rows, const float* d, int ld, int vocab, int c, float* dtable,
                      int accumulate, void* stream);
 
+/* ---- The PHOSCnet word recogniser (ResPhoSCNetZSL/modules/models.py:15-80): the streaming stages between its GEMMs
+ * (csrc/wd_phoscnet.hip).  The network's nn.ReLU never enters a GEMM epilogue: it lives in the stage that turns one GEMM's fp32
+ * result into the next GEMM's split-bf16 operand.  Every stage is a grid-stride loop under the grid cap of the edge kernels
+ * (2048 workgroups of 256), launches nothing on WD_EINVAL, calls nothing but the launch (capturable), and takes the 16-byte load /
+ * 8-byte plane store path when every pitch is a multiple of 4 elements and every pointer on its 16-byte (fp32) / 8-byte (planes)
+ * grid, the element path otherwise - the same values either way. */
+
+/* nn.ReLU (+ nn.MaxPool2d((2, 2), stride 2) when pool == 2; models.py:21-29) of a token-major fp32 map x [batch*h*w][ld_in] with c
+ * channels -> split-bf16 planes out [batch*h'*w'][ld_out]: pool 1 keeps h' = h, w' = w; pool 2 has h' = h / 2, w' = w / 2 (floor: a
+ * last odd row or column is dropped; h, w >= 2).  Value: m = x (pool 1) or the largest of the four, then v = m > 0 ? m : +0; hi =
+ * bf16(v) (round to nearest even), lo = bf16(v - hi) - wd_split's planes bit for bit.  out_lo may be NULL.  Rows of an MLP
+ * ([batch][c], nn.Linear + nn.ReLU, models.py:53-58) are h = w = 1. */
+int wd_relu_pool_planes(const float* x, int ld_in, int batch, int h, int w, int c, int pool, wd_bf16* out_hi, wd_bf16* out_lo,
+                        int ld_out, void* stream);
+
+/* nn.ReLU, then TemporalPyramidPooling(levels) (pyramidpooling.py:88-113, mode "max") of the token-major fp32 map x [batch*h*w][ld]
+ * with c channels.  Level L: k = ceil(w / L) columns per bin, pad = k * L - w zero columns of which floor(pad / 2) go on the left;
+ * bin j is the maximum of max(x, 0) over all h rows and the padded columns [j * k, (j + 1) * k) (a bin of padding only is 0; a
+ * zero column never wins against a ReLU output, so padding only matters there).  Output column of (level i, channel ch, bin j):
+ * sum_{i' < i} c * levels[i'] + ch * levels[i] + j - the reference's x.view(num_sample, -1) of an NCHW tensor.  Writes the fp32
+ * row out_f32 [batch][ld_out] (may be NULL) and its split planes out_hi / out_lo [batch][ld_pl] (out_hi may be NULL when out_f32 is
+ * not; out_lo may be NULL).  levels: nlevels <= WD_TPP_MAX_LEVELS ints on the HOST, each in [1, WD_TPP_MAX_BINS], read before the
+ * launch. */
+#define WD_TPP_MAX_LEVELS 8
+#define WD_TPP_MAX_BINS 16
+int wd_tpp_max(const float* x, int ld, int batch, int h, int w, int c, const int32_t* levels, int nlevels, float* out_f32,
+               int ld_out, wd_bf16* out_hi, wd_bf16* out_lo, int ld_pl, void* stream);
+
+/* Bilinear resize with half-pixel centres, no antialias: cv2.resize(..., INTER_LINEAR) of the recogniser's inputs
+ * (ResPhoSCNetZSL/modules/datasets.py:91) and F.interpolate(mode="bilinear", align_corners=False).  x: batch * c planes of hs rows of
+ * pitch ld_in (ws values each); out: batch * c planes of h rows of pitch ld_out (w values each).  bgr != 0: output plane ch of a
+ * sample reads source plane c - 1 - ch.  Every operation below is rounded to fp32 on its own (no contraction), in this order:
+ *   the source coordinate (y + 0.5) * hs / h - 0.5, clamped at 0, in integers: n = max((2 y + 1) * hs - h, 0); y0 = n / (2 h);
+ *   y1 = min(y0 + 1, hs - 1);  ly = (float)(n - y0 * 2 h) / (float)(2 h) - one division of two exact values (a coordinate formed
+ *   in fp32 is off by 1.5e-5 of a pixel at the far edge of a 256-pixel image);  the same for x (x0, x1, lx)
+ *   top = (1 - lx) * s[y0][x0] + lx * s[y0][x1];  bot = (1 - lx) * s[y1][x0] + lx * s[y1][x1];  out = (1 - ly) * top + ly * bot
+ * (same size: ly = lx = 0 and out = s[y][x]). */
+int wd_resize_bilinear(const float* x, int ld_in, int batch, int c, int hs, int ws, float* out, int ld_out, int h, int w, int bgr,
+                       void* stream);
+
+/* The two heads' activations (models.py:60-61, :72-73) into one PHOSC row: out[b][j] = max(phos[b][j], 0) for j < n_phos (as
+ * wd_relu_pool_planes: x > 0 ? x : +0), out[b][n_phos + j] = 1 / (1 + exp(-phoc[b][j])) for j < n_phoc (expf and an IEEE division:
+ * within 1e-6 of the exact sigmoid).  phos [batch][ld_phos], phoc [batch][ld_phoc] may be the first columns of zero-padded GEMM
+ * outputs; out [batch][ld_out], ld_out >= n_phos + n_phoc. */
+int wd_phosc_finish(const float* phos, int ld_phos, int n_phos, const float* phoc, int ld_phoc, int n_phoc, int batch, float* out,
+                    int ld_out, void* stream);
+
+/* Zero-shot recognition (ResPhoSCNetZSL/modules/engine.py:130-146): the cosine of every prediction pred [batch][ld_pred] (d values)
+ * against every row of table [v][ld_table]: cos = dot / max(|x| * |y|, 1e-8) in fp32, |y| = table_norm[word] (fp32 [v], from the
+ * host in fp64 or any other source), |x| summed by the launch.  One workgroup per (sample, block of 64 words), one wave per word.
+ * Outputs, each optional: scores [batch][ld_scores]; best_idx [batch] int32 and best_score [batch]: the FIRST maximum (the
+ * reference's strict > over its iteration order); target_score [batch] = the score of word target_idx[b] (int32; NaN for an id
+ * outside [0, v); target_idx is required with it).  ws: [batch][v] floats, needed only when scores is NULL and one of the other
+ * outputs is asked for (WD_EINVAL without it); asking for nothing is WD_EINVAL.  The best / target outputs are a second launch
+ * over the scores (one workgroup per sample). */
+int wd_phosc_score(const float* pred, int ld_pred, int batch, int d, const float* table, int ld_table, const float* table_norm, int v,
+                   float* scores, int ld_scores, int32_t* best_idx, float* best_score, const int32_t* target_idx, float* target_score,
+                   float* ws, void* stream);
+
 /* hipGraph capture of a launch sequence (one denoising step) on `stream`. */
 int wd_graph_begin(void* stream);
 int wd_graph_end(void* stream, void** graph_exec_out);

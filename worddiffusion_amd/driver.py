@@ -17,6 +17,9 @@ depend on the batch size or the number of ranks.  Host-side pieces restated from
                         and re-draws the rest, ``--start T`` begins from the latent noised to level T (``regenerate(known=...)``).
   * ``--lines``       - whole lines instead of gt rows: every ``writer<TAB>word word ...`` row of the file is one sampler call's
                         line of overlapping word windows (``regenerate_lines``, ``Diffusion.sampling(..., windows=)``).
+  * ``--verify``      - the OCR filter the reference's ``regenerateFrom*.py`` pipelines end a batch with, on the recogniser that is
+                        in its checkout (``phoscnet.PHOSCnet`` / ``WordVerifier``): rejected rows are drawn again, then dropped;
+                        ``save_path/verify.csv`` logs every attempt (``regenerate(verifier=...)``).
   * ``interpolate``   - one strip per gt row: the row's word in ``mix_steps`` styles from writer ``s1`` to writer ``s2``
                         (``sampling.py --interpolation --mix_rate`` renders one such blend of two random writers per call).
 """
@@ -132,7 +135,8 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
                ddim_steps: int = 50, eta: float = 0.0, dpmpp_steps: int = 20, dpmpp_order: int = 2, dpmpp_spacing: str = "logsnr",
                known=None, keep_cols: Optional[Tuple[int, int]] = None, start: Optional[int] = None, known_noise="auto",
                attention=None, attn_out: Optional[str] = None, guidance: Optional[str] = None, cfg_scale: float = 3.0,
-               resample: int = 1, jump: int = 10):
+               resample: int = 1, jump: int = 10, verifier=None, verify_min_score: Optional[float] = None,
+               verify_lexicon: Optional[Sequence[str]] = None, verify_tries: int = 1, verify_csv: Optional[str] = None):
     """Samples every gt row once (this rank's shard of them), ``batch`` rows per ``sampling`` call.
 
     Returns ``(start, latents_or_images)`` for the shard.  With ``out_dir`` the results are written as
@@ -155,7 +159,25 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
     ``words[i]``.  ``attn_out`` alone means ``attention=True``.
 
     ``guidance="writer_free"`` with ``cfg_scale`` (``Diffusion.sampling``): classifier-free guidance on the writer, two forwards
-    per step.  Not with ``skip_steps``, whose sampler has no guidance."""
+    per step.  Not with ``skip_steps``, whose sampler has no guidance.
+
+    ``verifier`` (a ``phoscnet.WordVerifier``; the OCR filter the reference's ``regenerateFrom*.py`` pipelines end a batch with):
+    every decoded batch is scored against its own words.  A row is accepted when its score is at least ``verify_min_score``
+    (where given) and, where ``verify_lexicon`` is given, its word is the lexicon's best match.  Rejected rows are drawn again, up
+    to ``verify_tries`` draws in all: try t (0-based) of global row r is sample ``r + t * len(rows)`` of the noise stream, whatever
+    the batch size or the number of ranks, so a rerun repeats every draw (a redraw call spans the chunk's first to last rejected
+    row).  Rows still rejected after the last try are not written (the returned tensor keeps their last draw).  ``verify_csv``
+    receives one row per attempt: image, word, score, best word (empty without a lexicon), accepted (0 / 1), try.  Needs a VAE
+    (a ValueError before anything is launched otherwise); not with ``attention``."""
+    if verifier is not None:
+        if vae is None:
+            raise ValueError("verifier needs decoded images: pass the VAE (latents alone cannot be read)")
+        if attention is not None or attn_out is not None:
+            raise ValueError("verifier cannot be combined with attention maps (a redraw would replace a row's maps)")
+        if int(verify_tries) < 1:
+            raise ValueError(f"verify_tries must be at least 1, not {verify_tries}")
+    elif verify_min_score is not None or verify_lexicon is not None or verify_tries != 1 or verify_csv is not None:
+        raise ValueError("verify_min_score / verify_lexicon / verify_tries / verify_csv need a verifier")
     if guidance is not None and skip_steps:
         raise ValueError("guidance is not supported by the step-skipping sampler (skip_steps)")
     if attn_out is not None and attention is None:
@@ -183,41 +205,77 @@ def regenerate(model, diffusion, rows: Sequence[Tuple[str, str, str]], wr_dict: 
         latents = [_known_latent(known, image) for _, image, _ in mine]  # (all of them first: a missing row fails up front)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
-    for b0 in range(0, count, batch):
-        chunk = mine[b0:b0 + batch]
-        words = [t for _, _, t in chunk]
-        labels = torch.tensor([wr_dict[s] for s, _, _ in chunk], dtype=torch.int64)
+
+    def draw(lo: int, hi: int, offset: int):
+        """One sampler call for the shard's rows lo .. hi - 1 with sample ``offset + i`` of the noise stream for row lo + i."""
+        part = mine[lo:hi]
+        words = [t for _, _, t in part]
+        labels = torch.tensor([wr_dict[s] for s, _, _ in part], dtype=torch.int64)
         phosc = torch.stack([phosc_of(wd) for wd in words]) if phosc_of is not None else None
-        kw = dict(seed=seed, sample_offset=first + b0, mix_rate=mix_rate)
+        kw = dict(seed=seed, sample_offset=offset, mix_rate=mix_rate)
         if attention is not None:
             kw.update(attention=attention)
         if guidance is not None:
             kw.update(guidance=guidance, cfg_scale=cfg_scale)
         if known is not None:
-            kw.update(known=torch.stack(latents[b0:b0 + batch]), known_mask=kmask, start=start, known_noise=known_noise)
+            kw.update(known=torch.stack(latents[lo:hi]), known_mask=kmask, start=start, known_noise=known_noise)
         if resample != 1:
             kw.update(resample=resample, jump=jump)
         if sampler == "ddim":
-            res = diffusion.sampling_ddim(model, vae, len(chunk), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
+            res = diffusion.sampling_ddim(model, vae, len(part), words, labels, args, steps=ddim_steps, eta=eta, phoscLabels=phosc, **kw)
         elif sampler == "dpmpp":
-            res = diffusion.sampling_dpmpp(model, vae, len(chunk), words, labels, args, steps=dpmpp_steps, order=dpmpp_order,
+            res = diffusion.sampling_dpmpp(model, vae, len(part), words, labels, args, steps=dpmpp_steps, order=dpmpp_order,
                                            spacing=dpmpp_spacing, phoscLabels=phosc, **kw)
         elif skip_steps:
-            res = diffusion.sampling3(0, None, words, phosc, model, model, vae, 0, 1, len(chunk), words, labels, args, **kw)
+            res = diffusion.sampling3(0, None, words, phosc, model, model, vae, 0, 1, len(part), words, labels, args, **kw)
             res = res if vae is None else res[2]
         else:
-            res = diffusion.sampling(model, vae, len(chunk), words, labels, args, phoscLabels=phosc, **kw)
-        res = res.detach().cpu()
+            res = diffusion.sampling(model, vae, len(part), words, labels, args, phoscLabels=phosc, **kw)
+        return res.detach()
+
+    log = []  # verify_csv rows
+    for b0 in range(0, count, batch):
+        chunk = mine[b0:b0 + batch]
+        res = draw(b0, b0 + len(chunk), first + b0)
+        accepted = [True] * len(chunk)
+        if verifier is not None:
+            words = [t for _, _, t in chunk]
+            res = res.clone()
+            pending = list(range(len(chunk)))
+            for attempt in range(int(verify_tries)):
+                if attempt:
+                    lo, hi = pending[0], pending[-1] + 1
+                    again = draw(b0 + lo, b0 + hi, first + b0 + lo + attempt * len(rows))
+                    for i in pending:
+                        res[i] = again[i - lo]
+                sc, best, ok = verifier.verify(res[pending], [words[i] for i in pending], verify_min_score, verify_lexicon)
+                sc, ok = sc.cpu().tolist(), ok.cpu().tolist()
+                for j, i in enumerate(pending):
+                    log.append((chunk[i][1], words[i], sc[j], best[j] if best is not None else "", int(ok[j]), attempt))
+                pending = [i for j, i in enumerate(pending) if not ok[j]]
+                if not pending:
+                    break
+            for i in pending:
+                accepted[i] = False
+        res = res.cpu()
         outs.append(res)
         if attention is not None:
             maps.append({k: v.cpu() for k, v in diffusion.last_attention.items()})
         if out_dir is not None:
-            for (_, image, _), item in zip(chunk, res):
+            for (_, image, _), item, keep in zip(chunk, res, accepted):
+                if not keep:
+                    continue
                 if vae is None:
                     np.save(os.path.join(out_dir, f"{image}.npy"), item.numpy())
                 else:
                     arr = (item.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).numpy()
                     write_png(os.path.join(out_dir, f"{image}.png"), arr if arr.shape[2] == 3 else arr[:, :, 0])
+    if verify_csv is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(verify_csv)), exist_ok=True)
+        with open(verify_csv, "w") as f:
+            f.write("image,word,score,best_word,accepted,try\n")
+            for image, word, score, best, ok, attempt in log:
+                f.write(f"{image},{word},{score!r},{best},{ok},{attempt}\n")
     if attn_out is not None and maps:
         path = attn_out if (os.path.isabs(attn_out) or out_dir is None) else os.path.join(out_dir, attn_out)
         np.savez_compressed(path, images=np.array([image for _, image, _ in mine]), words=np.array([t for _, _, t in mine]),
@@ -418,6 +476,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lines", default=None, metavar="FILE",
                     help="sample whole lines instead of the gt rows: every row of FILE is 'writer<TAB>word word ...' and becomes one "
                          "image (or latent), line_<row index>, of overlapping word windows denoised together")
+    ap.add_argument("--verify", default=None, metavar="CKPT",
+                    help="a PHOSCnet checkpoint (ResPhoSCNetZSL state_dict): every decoded batch is read back by the recogniser, rejected "
+                         "rows are drawn again and, if still rejected, not written; save_path/verify.csv logs every attempt "
+                         "(needs --alphabet_csv and --stable_dif_path)")
+    ap.add_argument("--verify_min_score", type=float, default=None, metavar="S",
+                    help="--verify: accept a row when the cosine of its predicted PHOSC vector against its word's is at least S")
+    ap.add_argument("--verify_lexicon", default=None, metavar="FILE",
+                    help="--verify: one word per line; accept a row when its word is the best match among them")
+    ap.add_argument("--verify_tries", type=int, default=1, metavar="N", help="--verify: draws per row in all (N - 1 redraws)")
     ap.add_argument("--line_overlap", type=int, default=2, metavar="V", help="--lines: latent columns two neighbouring words share")
     ap.add_argument("--line_feather", type=int, default=0, metavar="F",
                     help="--lines: latent columns over which a window's weight ramps up at its ends (0: the plain average)")
@@ -439,6 +506,18 @@ def parse_args(argv=None):
             ap.error(f"--line_overlap must be in [0, 31] latent columns, not {a.line_overlap}")
         if a.line_feather < 0:
             ap.error(f"--line_feather must be >= 0, not {a.line_feather}")
+    if a.verify is None:
+        if a.verify_min_score is not None or a.verify_lexicon is not None or a.verify_tries != 1:
+            ap.error("--verify_min_score, --verify_lexicon and --verify_tries need --verify (the recogniser's checkpoint)")
+    else:
+        for flag, on in (("--lines", a.lines), ("--style_pair", a.style_pair), ("--encode_images", a.encode_images),
+                         ("--attn_maps", a.attn_maps)):
+            if on:
+                ap.error(f"--verify does not take {flag}")
+        if not a.alphabet_csv:
+            ap.error("--verify needs --alphabet_csv (the PHOS shape-count table)")
+        if a.verify_tries < 1:
+            ap.error(f"--verify_tries must be at least 1, not {a.verify_tries}")
     if a.sampler != "ddpm" and a.skip_steps:
         ap.error(f"--sampler {a.sampler} and --skip_steps 1 are two ways to run fewer steps: choose one")
     if a.sampler == "ddim" and not 1 <= a.ddim_steps <= a.noise_steps - 1:
@@ -501,6 +580,8 @@ def main(argv=None):
     from . import Diffusion, UNetModel, UNetModelPhosc
     ap, a = parse_args(argv)
     rank, world, local = env_rank_world()
+    if a.verify is not None and not a.stable_dif_path:
+        raise ValueError("--verify reads decoded images: it needs --stable_dif_path (the VAE); latents alone cannot be verified")
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     if a.encode_images:
@@ -554,12 +635,24 @@ def main(argv=None):
     if a.init_latents:
         from .latents import LatentCache
         known = LatentCache(a.init_latents)
+    verify_kw = {}
+    if a.verify is not None:
+        from .phoscnet import PHOSCnet, WordVerifier
+        net = PHOSCnet()
+        net.load_state_dict(torch.load(a.verify, map_location="cpu", weights_only=True), strict=True)
+        lexicon = None
+        if a.verify_lexicon:
+            with open(a.verify_lexicon) as f:
+                lexicon = [ln.strip() for ln in f if ln.strip()]
+        verify_kw = dict(verifier=WordVerifier(net.to(dev), a.alphabet_csv), verify_min_score=a.verify_min_score, verify_lexicon=lexicon,
+                         verify_tries=a.verify_tries,
+                         verify_csv=os.path.join(a.save_path, "verify.csv" if world == 1 else f"verify.rank{rank}.csv"))
     start, res = regenerate(ema_model, diffusion, rows, wr, args, vae=vae, batch=a.batch_size,
                             out_dir=os.path.join(a.save_path, "images"), seed=a.seed, skip_steps=bool(a.skip_steps),
                             phosc_of=phosc_of, mix_rate=a.mix_rate, sampler=a.sampler, ddim_steps=a.ddim_steps, eta=a.eta,
                             dpmpp_steps=a.dpmpp_steps, dpmpp_order=a.dpmpp_order, dpmpp_spacing=a.dpmpp_spacing, known=known,
                             keep_cols=a.keep_cols, start=a.start, resample=a.resample, jump=a.jump,
-                            guidance=a.guidance, cfg_scale=a.cfg_scale,
+                            guidance=a.guidance, cfg_scale=a.cfg_scale, **verify_kw,
                             attention=None if a.attn_maps is None else (a.attn_window or True),
                             attn_out=None if a.attn_maps is None else
                             (a.attn_maps if world == 1 else a.attn_maps[:-4] + f".rank{rank}.npz"))
