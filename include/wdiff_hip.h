@@ -799,6 +799,36 @@ int wd_weighted_mse_loss(const float* pred, const float* target, const float* ma
                          const int64_t* t, const float* weights, int T, float* grad, float* loss, float* sample_loss,
                          double* hist, int nbins, double* scratch, void* stream);
 
+/* CTC loss of nn.CTCLoss(reduction='sum', zero_infinity=True)(log_softmax(logits, 2), ...) (trainModifyCondition.py:73,757-799)
+ * and its gradient with respect to the RAW logits (the log-softmax is folded in), forward and backward in one call: two launches,
+ * no atomics on floating-point values, fixed summation order (the same bits on every run).  The blank is class 0.
+ *   logits      fp32, row (t, b) at logits + (t * batch + b) * ld, C classes per row, ld >= C
+ *   targets     int32 (targets_i64 = 0) or int64 (1), sample b at targets + b * tld, tld >= Lmax; may be NULL when Lmax == 0
+ *   input_len, target_len  int32 [batch] on the device
+ *   dlogits     NULL (loss only) or fp32 in the layout of logits with its own pitch dld >= C; EVERY row t < T of it is written
+ *   sample_nll  fp32 [batch]: -log P(target_b | logits_b), unscaled; +inf when no alignment exists
+ *   loss        fp32 [1] = (float)((double)scale * sum_b nll_b), b ascending in double, over the samples that count
+ *   status      int32 [batch]: 0, or bit 0 input_len outside [1, T], bit 1 target_len outside [0, Lmax], bit 2 an id outside [0, C)
+ * With l' the blank-extended target (S = 2 L + 1 states; a target id equal to the blank follows the same recursion, as in torch),
+ * p = softmax(logits[t, b, :]) and gamma_t(s) the posterior of state s at time t,
+ *   dlogits[t, b, c] = scale * (p[c] - sum over {s : l'_s = c} of gamma_t(s))   for t < input_len[b], 0 for t >= input_len[b].
+ * A sample whose nll is not finite (no alignment: zero_infinity) adds nothing to loss and has a zero gradient; so does a sample
+ * with status != 0, whose rows and targets are not read beyond what the check itself needs and whose sample_nll is 0.
+ * alpha and beta are kept in the log domain in double, so the gradient keeps its relative precision at any T and for logits
+ * however peaked.
+ * workspace: wd_ctc_workspace_bytes(T, batch, Lmax) bytes (8 * batch * (1 + T * (5 * Lmax + 3)); -1 for sizes outside the range),
+ * 8-byte aligned, no initial contents needed.  The function neither allocates nor synchronises (capturable).
+ * WD_EINVAL (nothing launched): logits, input_len, target_len, sample_nll, loss, status or workspace NULL; targets NULL or
+ * tld < Lmax with Lmax > 0; T outside [1, WD_CTC_MAX_T], C outside [1, WD_CTC_MAX_C], Lmax outside [0, WD_CTC_MAX_L], batch < 1;
+ * ld < C, dld < C with dlogits; targets_i64 not 0 or 1; workspace_bytes too small; a pointer not aligned to its element. */
+#define WD_CTC_MAX_T 1024
+#define WD_CTC_MAX_C 1024
+#define WD_CTC_MAX_L 127
+int64_t wd_ctc_workspace_bytes(int T, int batch, int Lmax);
+int wd_ctc_loss(const float* logits, int ld, int T, int batch, int C, const void* targets, int targets_i64, int tld, int Lmax,
+                const int32_t* input_len, const int32_t* target_len, float scale, float* dlogits, int dld, float* sample_nll,
+                float* loss, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- backward building blocks (training step, train.py:290: loss.backward()).  Contractions reuse wd_gemm:
  *  d(input)  = wd_gemm over d(output) planes with the mirrored gather table and transposed weights;
  *  d(weight) = wd_gemm over the token dimension, operands = the transposed planes made by wd_transpose_planes. */

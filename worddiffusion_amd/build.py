@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwdiff_hip.so")
-SOURCES = ["wd_gemm.hip", "wd_gemmw.hip", "wd_ff.hip", "wd_bwd.hip", "wd_gemm_reduce.hip", "wd_gemmq.hip", "wd_dw.hip", "wd_norm.hip", "wd_attn.hip", "wd_xattn.hip", "wd_misc.hip", "wd_window.hip", "wd_resample.hip", "wd_conv_in.hip", "wd_train.hip", "wd_pack.hip", "wd_gemm4.hip", "wd_gemm_plan.hip", "wd_phoscnet.hip", "wd_runtime.hip"]
+SOURCES = ["wd_gemm.hip", "wd_gemmw.hip", "wd_ff.hip", "wd_bwd.hip", "wd_gemm_reduce.hip", "wd_gemmq.hip", "wd_dw.hip", "wd_norm.hip", "wd_attn.hip", "wd_xattn.hip", "wd_misc.hip", "wd_window.hip", "wd_resample.hip", "wd_conv_in.hip", "wd_train.hip", "wd_ctc.hip", "wd_pack.hip", "wd_gemm4.hip", "wd_gemm_plan.hip", "wd_phoscnet.hip", "wd_runtime.hip"]
 HEADERS = [os.path.join(CSRC, "wd_common.h"), os.path.join(CSRC, "wd_gemm_epi.h"), os.path.join(CSRC, "wd_gemm_priv.h"), os.path.join(CSRC, "wd_gemm_tile.h"), os.path.join(CSRC, "wd_philox.h"), os.path.join(os.path.dirname(HERE), "include", "wdiff_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-fno-gpu-rdc"]
 # per-file flags.  wd_attn.hip: MFMA accumulators in ordinary VGPRs - for its 256-thread kernels hipcc otherwise keeps them in AGPRs and

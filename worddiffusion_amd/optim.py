@@ -122,6 +122,98 @@ def weighted_mse_loss(pred: torch.Tensor, target: torch.Tensor, t: Optional[torc
     return loss, grad, sample_loss
 
 
+def check_ctc_args(logits, targets, input_lengths, target_lengths):
+    """The arguments of ``ctc_loss`` -> (T, B, C, Lmax, targets int64 [B, Lmax], input_lengths int32 [B], target_lengths int32 [B]),
+    the three integer tensors on the host.  ``logits``: a float32 tensor [T, B, C] within the kernel's range; ``targets``: integer
+    [B, Lmax] (or flat [B * Lmax]) with every id of the first ``target_lengths[b]`` ones in [0, C); ``input_lengths`` in [1, T];
+    ``target_lengths`` in [0, Lmax].  Host arithmetic only (on device tensors it costs one small synchronisation each)."""
+    D = N.DEFINES
+    if not torch.is_tensor(logits) or logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError("logits must be a float32 tensor [T, B, C]")
+    T, B, C = (int(v) for v in logits.shape)
+    if not (1 <= T <= D["WD_CTC_MAX_T"] and B >= 1 and 1 <= C <= D["WD_CTC_MAX_C"]):
+        raise ValueError(f"ctc_loss takes 1 <= T <= {D['WD_CTC_MAX_T']}, B >= 1 and 1 <= C <= {D['WD_CTC_MAX_C']}, "
+                         f"got logits {list(logits.shape)}")
+
+    def ints(v, name):
+        v = torch.as_tensor(v)
+        if v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer tensor, got {v.dtype}")
+        return v.detach().cpu().long()
+
+    targets = ints(targets, "targets")
+    if targets.dim() == 1 and targets.numel() % B == 0:  # the reference passes the flattened token matrix
+        targets = targets.reshape(B, -1)
+    if targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError(f"targets must be [B, Lmax] (or flat [B * Lmax]) with B = {B}, got {list(targets.shape)}")
+    Lmax = int(targets.shape[1])
+    if Lmax > D["WD_CTC_MAX_L"]:
+        raise ValueError(f"ctc_loss takes targets of at most {D['WD_CTC_MAX_L']} ids, got {Lmax}")
+    il, tl = ints(input_lengths, "input_lengths"), ints(target_lengths, "target_lengths")
+    if tuple(il.shape) != (B,) or tuple(tl.shape) != (B,):
+        raise ValueError(f"input_lengths and target_lengths must be [{B}], got {list(il.shape)} and {list(tl.shape)}")
+    if not bool(((il >= 1) & (il <= T)).all()):
+        raise ValueError(f"every input length must lie in [1, {T}]")
+    if not bool(((tl >= 0) & (tl <= Lmax)).all()):
+        raise ValueError(f"every target length must lie in [0, {Lmax}]")
+    used = torch.arange(Lmax)[None, :] < tl[:, None]
+    if not bool((((targets >= 0) & (targets < C)) | ~used).all()):
+        raise ValueError(f"every target id must lie in [0, {C})")
+    return T, B, C, Lmax, targets.contiguous(), il.int().contiguous(), tl.int().contiguous()
+
+
+def ctc_loss(logits: torch.Tensor, targets, input_lengths, target_lengths, want_grad: bool = True, scale: float = 1.0):
+    """``scale * nn.CTCLoss(reduction='sum', zero_infinity=True)(log_softmax(logits, 2), targets, input_lengths, target_lengths)``
+    with the blank at class 0 (``trainModifyCondition.py:73,757-799``; the training step passes ``scale = ocr_weight / B``) and
+    its gradient with respect to the raw logits, in one ``wd_ctc_loss`` call
+
+    -> (loss [1], dlogits [T, B, C] or None, sample_nll [B]): device tensors; ``sample_nll`` is unscaled, ``inf`` for a sample
+    that has no alignment (it adds nothing to the loss and has a zero gradient).  The arguments are validated first
+    (``check_ctc_args``); the kernel runs on the GPU only."""
+    T, B, C, Lmax, targets, il, tl = check_ctc_args(logits, targets, input_lengths, target_lengths)
+    scale = float(scale)
+    if not scale == scale or scale in (float("inf"), float("-inf")):
+        raise ValueError(f"scale must be finite, got {scale}")
+    if not logits.is_cuda:
+        raise N.NativeError("ctc_loss runs on the GPU only (no CPU fallback)")
+    lib, dev = N.lib(), logits.device
+    logits = logits.detach().contiguous()
+    targets, il, tl = targets.to(dev), il.to(dev), tl.to(dev)
+    grad = torch.empty_like(logits) if want_grad else None
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    sample_nll = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.wd_ctc_workspace_bytes(T, B, Lmax)
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    N.check(lib.wd_ctc_loss(logits.data_ptr(), C, T, B, C, targets.data_ptr() if Lmax else None, 1, Lmax, Lmax, il.data_ptr(),
+                            tl.data_ptr(), scale, grad.data_ptr() if want_grad else None, C, sample_nll.data_ptr(),
+                            loss.data_ptr(), status.data_ptr(), work.data_ptr(), nbytes, st), "wd_ctc_loss")
+    return loss, grad, sample_nll
+
+
+def ctc_greedy_decode(logits, index2letter=None):
+    """Best-path decoding of CTC logits [T, B, C] (or [T, C]): the argmax of every step, repeats collapsed, blanks (class 0)
+    dropped -> one list of ids per sample, or one string per sample when ``index2letter`` (a mapping or sequence from id to
+    letter) is given.  Host code: a device tensor is copied once."""
+    logits = torch.as_tensor(logits)
+    if logits.dim() == 2:
+        logits = logits[:, None, :]
+    if logits.dim() != 3 or logits.shape[2] < 1:
+        raise ValueError(f"logits must be [T, B, C] or [T, C], got {list(logits.shape)}")
+    best = logits.detach().argmax(2).cpu().tolist()  # [T][B]
+    out = []
+    for b in range(logits.shape[1]):
+        seq, prev = [], -1
+        for row in best:
+            k = row[b]
+            if k != prev and k != 0:
+                seq.append(k)
+            prev = k
+        out.append(seq if index2letter is None else "".join(str(index2letter[k]) for k in seq))
+    return out
+
+
 class FusedAdamW:
     """``optim.AdamW(model.parameters(), lr=1e-4)`` (train.py:405) + ``EMA(0.995).step_ema`` (train.py:294,410) in one
     multi-tensor launch.  ``ema_model`` is optional; with it ``step()`` reproduces ``ema.step_ema(ema_model, model)``
